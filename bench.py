@@ -6,7 +6,9 @@ Default mode (--mode pairwise): one "step" = one computeUnaryCosts() of BASELINE
 ico6 data grid (40 962 vertices), ico4 control grid (2 562 nodes), 19 labels -> 48 678 evals = 3.18 M point samples -- as an
 iteration of a registration pays for it: the per (control point, label) rotations (estimate_rotation_matrix R/point.cpp:97-152:
 new every iteration), the three table kernels, and the 389 KB table delivered to host memory (the optimiser reads it there).
-All inputs are resident in HBM before the timed region starts.  The same JSON line carries, as extra objects (rank 0, N = 1):
+All inputs are resident in HBM before the timed region starts.  A plain run sets up, warms up (--warmup steps), times --steps steps and
+prints the headline line; --dump-outputs DIR then also writes the table of the last timed step (rank 0) to DIR/unary_costs.npy.  The inputs
+are seeded: the same arguments give the same inputs in every run.  With --full the same JSON line carries, as extra objects (rank 0, N = 1):
   steady            the table kernels alone, enqueued back to back (the round-1 headline definition)
   resample          Resampler::get_barycentric_weights for the 40 962 vertices of an ico6 sphere: queries/s per kernel and per call, its roofline,
                     the CPU port's rate beside it
@@ -24,8 +26,8 @@ Multi-GPU (--gpus N, one process per GPU under torch.distributed.run):
                     ranks wall time.
   --mode gmsm       BASELINE config 5: 64 synthetic subjects, set-up sharded by subject, every label step sharded by clique,
                     RCCL all-gather / gather over xGMI (newmsm_amd/dist.py); strong scaling.  value = subjects/hour.
-                    The default mode at N > 1 runs this as well and reports it as the "gmsm" object of its line (the group is the
-                    path that shards; MSM_BENCH_GMSM_SCALING=0 leaves it out).
+                    With --full the default mode at N > 1 runs this as well and reports it as the "gmsm" object of its line (the
+                    group is the path that shards; MSM_BENCH_GMSM_SCALING=0 leaves it out).
 """
 import argparse
 import json
@@ -746,11 +748,19 @@ def main():
     ap.add_argument("--dims", type=int, default=1)
     ap.add_argument("--subjects", type=int, default=64)
     ap.add_argument("--label-change", type=float, default=0.10, help="gMSM: fraction of the nodes whose label changes between two label steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the steady and roofline figures, the extra objects, the CPU "
+                                                        "baseline (without it a run sets up, warms up, times --steps steps and prints the headline line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the CPU legs of the extra objects")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra objects (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed to DIR/<name>.npy (pairwise mode: "
+                                                          "rank 0's unary cost table, L x N float64)")
     ap.add_argument("--dry-launch", action="store_true", help="launch the ranks, create the communicator, count the ranks through it, print that and stop "
                                                               "(no GPU work: the check that --gpus N really starts N ranks; gloo when no GPU is visible)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode != "pairwise":
+        ap.error("--dump-outputs is implemented for --mode pairwise only")
 
     # --gpus N outside a launcher: become the launcher's parent BEFORE torch or HIP are touched (the driver's N = 1 command shape with N > 1)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -830,7 +840,8 @@ def main():
         sync_all()
         t0 = time.perf_counter()
         res = bench_gmsm(ctx, args.subjects, comm, label_steps=max(2, min(args.steps, 8)), change=args.label_change)
-        res["template_allreduce"] = template_allreduce()
+        if args.full:
+            res["template_allreduce"] = template_allreduce()
         sync_all()
         if rank == 0:
             last = res["levels"][-1]
@@ -862,7 +873,6 @@ def main():
     samples = cf.L * int(ptr[-1])
     U = ctx.host_array((cf.L, cf.N))  # pinned: the table's copy to the host is one copy-engine command
 
-    cf.enable_timing(True)  # HIP events around the dominant kernel of every launch, on the launch stream
     with torch.cuda.stream(stream):
         for _ in range(args.warmup):
             cf.computeUnaryCosts(U)
@@ -872,32 +882,38 @@ def main():
             cf.computeUnaryCosts(U)  # rotations + table kernels + table on the host, synchronous: what an iteration pays
         sync_all()
         wall = time.perf_counter() - t0
-        # the kernels alone, enqueued back to back (no rotation kernel between them would be wrong: every call recomputes it)
-        for _ in range(args.warmup):
-            cf.computeUnaryCosts_async()
-        ctx.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ts = time.perf_counter()
-        e0.record(stream)
-        for _ in range(args.steps):
-            cf.computeUnaryCosts_async()
-        e1.record(stream)
-        ctx.synchronize()
-        steady_wall = time.perf_counter() - ts
-    step_ms = e0.elapsed_time(e1) / args.steps  # HIP events on the launch stream: rotations + the three table kernels
-    kt = cf.kernel_times()[-min(args.steps, 64):]
-    kernel_ms = float(np.mean(kt))  # the sampling kernel alone (the dominant kernel), last <= 64 launches of the timed region
     if not np.isfinite(U).all() and not os.environ.get("MSM_BENCH_NOCHECK"):
         raise SystemExit("non-finite unary costs")
-    Ucopy = np.array(U)
+    Ucopy = np.array(U)  # the table of the last timed step
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "unary_costs.npy"), Ucopy)  # (labels, control points) float64, as computeUnaryCosts delivers it
 
     wall = D.max_over_ranks(wall, comm)
-    kernel_ms = D.max_over_ranks(kernel_ms, comm)
+    if args.full:
+        cf.enable_timing(True)  # HIP events around the dominant kernel of every launch, on the launch stream
+        with torch.cuda.stream(stream):
+            # the kernels alone, enqueued back to back (no rotation kernel between them would be wrong: every call recomputes it)
+            for _ in range(args.warmup):
+                cf.computeUnaryCosts_async()
+            ctx.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ts = time.perf_counter()
+            e0.record(stream)
+            for _ in range(args.steps):
+                cf.computeUnaryCosts_async()
+            e1.record(stream)
+            ctx.synchronize()
+            steady_wall = time.perf_counter() - ts
+        step_ms = e0.elapsed_time(e1) / args.steps  # HIP events on the launch stream: rotations + the three table kernels
+        kt = cf.kernel_times()[-min(args.steps, 64):]
+        kernel_ms = float(np.mean(kt))  # the sampling kernel alone (the dominant kernel), last <= 64 launches of the back-to-back run
+        kernel_ms = D.max_over_ranks(kernel_ms, comm)
     # N > 1: the pairwise headline above is N independent replicas (weak scaling, no collective).  The path that does shard is the
-    # groupwise one, so the same run also measures it -- the SAME 64-subject group on N GPUs (strong scaling: set-up by subject with
+    # groupwise one, so a --full run also measures it -- the SAME 64-subject group on N GPUs (strong scaling: set-up by subject with
     # the RCCL all-gathers, label steps by clique) -- and reports it next to the headline; compare with "gmsm" of the N = 1 line.
     gmsm_scaling = None
-    if world > 1 and not args.no_extras and os.environ.get("MSM_BENCH_GMSM_SCALING", "1") != "0":
+    if world > 1 and args.full and not args.no_extras and os.environ.get("MSM_BENCH_GMSM_SCALING", "1") != "0":
         try:
             gmsm_scaling = bench_gmsm(ctx, args.subjects, comm, change=args.label_change)
             gmsm_scaling["scaling"] = "strong"
@@ -907,9 +923,6 @@ def main():
 
     if rank == 0:
         value = world * evals * args.steps / wall
-        abytes = algorithmic_bytes(samples, evals, args.dims)
-        kbytes = kernel_algorithmic_bytes(samples, evals, args.dims)
-        achieved = kbytes / (kernel_ms * 1e-3) / 1e9
         out = {
             "metric": "label-cost evals/sec",
             "value": value,
@@ -930,9 +943,14 @@ def main():
                 "step": "label rotations + sampling / fix-up / reduction kernels + the table copied to pinned host memory, one synchronous call",
                 "setup_not_in_step_ms": {"direction_table_of_the_target_once_per_level": raytable_ms},
             },
-            "steady": {"ms_per_step": steady_wall / args.steps * 1e3, "value": world * evals * args.steps / steady_wall,
-                       "definition": "table kernels (incl. the rotation kernel) enqueued back to back, no copy of the table to the host, one synchronisation at the end"},
-            "roofline": {
+        }
+        if args.full:
+            abytes = algorithmic_bytes(samples, evals, args.dims)
+            kbytes = kernel_algorithmic_bytes(samples, evals, args.dims)
+            achieved = kbytes / (kernel_ms * 1e-3) / 1e9
+            out["steady"] = {"ms_per_step": steady_wall / args.steps * 1e3, "value": world * evals * args.steps / steady_wall,
+                             "definition": "table kernels (incl. the rotation kernel) enqueued back to back, no copy of the table to the host, one synchronisation at the end"}
+            out["roofline"] = {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": pmc_traffic(args), "traffic_source": PMC_PROFILE + " (rocprofv3 --pmc passes of tools/collect_profile.sh, round 5)",
                 "kernel": DOMINANT_KERNEL, "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": kbytes,
@@ -942,8 +960,7 @@ def main():
                 # the whole table (rotation + sampling + fix-up + reduction kernels, HIP events around one step) against the full 8(d) figure
                 "step_ms_events": step_ms, "algorithmic_bytes_per_table": abytes,
                 "table_achieved": abytes / (step_ms * 1e-3) / 1e9, "table_frac": abytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            },
-        }
+            }
         if gmsm_scaling is not None:
             out["gmsm"] = gmsm_scaling
         threads = D.host_cores()  # cgroup / affinity aware: the GPU box gives one GPU's share of the host
@@ -952,7 +969,7 @@ def main():
             if os.environ.get("MSM_BENCH_TRACE"):
                 print("[bench %.1f s] %s" % (time.perf_counter() - t_start, name), file=sys.stderr, flush=True)
 
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             with torch.cuda.stream(stream):
                 stage("triclique_move")
                 out["triclique_move"] = {"d1": bench_triclique_move(ctx, 1, 200, 0 if args.no_cpu_baseline else threads),
@@ -986,7 +1003,7 @@ def main():
                     stage("gmsm.cpu_port")
                     out["gmsm"]["cpu_port"] = gmsm_cpu_port(args.subjects, threads, GMSM_LEVELS)
                     out["gmsm"]["vs_cpu_port"] = out["gmsm"]["subjects_per_hour"] / out["gmsm"]["cpu_port"]["projected_subjects_per_hour"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             Uo, rate, dt, reps = cpu_baseline(inp, kind, threads)
             out["cpu_baseline"] = {
                 "value": rate, "unit": "evals/s", "cores": threads, "kind": "port",
