@@ -123,16 +123,7 @@ int finish_tree(msm_mesh *m) {
 // Meshes of this size and above get their tree built on the GPU (octree_kernels.hip).  The level loop is some thirty launches for an ico4
 // mesh (170 us) against 400 us of single-threaded host build plus the upload of its arrays; below 2 048 triangles (ico3: 1 280) the host
 // build is the shorter one.  (Until round 3 the limit was 8 192: the level scan was one workgroup and a level six launches.)
-// MSMHIP_OCTREE=host|gpu forces one of them (tests compare the two).
-bool mesh_tree_on_gpu(const msm_mesh *m);
-static bool tree_on_gpu(const msm_mesh *m) { return mesh_tree_on_gpu(m); }
-bool mesh_tree_on_gpu(const msm_mesh *m) {
-    static const int mode = [] {
-        const char *e = std::getenv("MSMHIP_OCTREE");
-        return !e ? 0 : (std::strcmp(e, "host") == 0 ? 1 : (std::strcmp(e, "gpu") == 0 ? 2 : 0));
-    }();
-    return mode == 2 || (mode != 1 && m->gpu_tree_always) || (mode == 0 && m->T >= 2048);
-}
+bool mesh_tree_on_gpu(const msm_mesh *m) { return m->gpu_tree_always || m->T >= 2048; }
 
 int upload_staged(msm_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (bytes == 0) return MSM_OK;
@@ -150,11 +141,11 @@ static int ensure_tree_overlapped(msm_mesh *m, const std::function<void()> *over
 int ensure_tree(msm_mesh *m) { return ensure_tree_overlapped(m, nullptr); }
 
 int ensure_tree_pair(msm_mesh *a, msm_mesh *b) {
-    if (a->tree_valid || b->tree_valid || a == b || tree_on_gpu(a) == tree_on_gpu(b)) {
+    if (a->tree_valid || b->tree_valid || a == b || mesh_tree_on_gpu(a) == mesh_tree_on_gpu(b)) {
         const int st = ensure_tree(a);
         return st ? st : ensure_tree(b);
     }
-    msm_mesh *dev = tree_on_gpu(a) ? a : b, *host = dev == a ? b : a;
+    msm_mesh *dev = mesh_tree_on_gpu(a) ? a : b, *host = dev == a ? b : a;
     bool built = false;
     const std::function<void()> work = [&] {
         build_octree(host->xyz.data(), host->tri.data(), host->V, host->T, host->tree);
@@ -166,13 +157,13 @@ int ensure_tree_pair(msm_mesh *a, msm_mesh *b) {
 }
 
 int ensure_tree_begin(msm_mesh *m) {
-    if (m->tree_valid || m->oct_job || !tree_on_gpu(m)) return MSM_OK;
+    if (m->tree_valid || m->oct_job || !mesh_tree_on_gpu(m)) return MSM_OK;
     return gpu_build_octree_begin(m);
 }
 
 static int ensure_tree_overlapped(msm_mesh *m, const std::function<void()> *overlap) {
     if (m->tree_valid) return MSM_OK;
-    if (tree_on_gpu(m)) {
+    if (mesh_tree_on_gpu(m)) {
         int st;
         if (m->oct_job) {  // begun by ensure_tree_begin
             if (overlap && *overlap) (*overlap)();
@@ -190,20 +181,6 @@ static int ensure_tree_overlapped(msm_mesh *m, const std::function<void()> *over
         m->host_xyz_stale = false;
     }
     build_octree(m->xyz.data(), m->tri.data(), m->V, m->T, m->tree);
-    return upload_tree(m);
-}
-
-// new coordinates together with the search structure built for them elsewhere (e.g. on a worker thread)
-int install_coords_and_tree(msm_mesh *m, const double *xyz, FlatOctree &&tree) {
-    msm_ctx *ctx = m->ctx;
-    MSM_TRY(ctx_sync(ctx));
-    m->xyz.assign(xyz, xyz + 3 * (size_t)m->V);
-    {
-        const int st = upload_staged(ctx, m->d_xyz, m->xyz.data(), sizeof(double) * 3 * (size_t)m->V);
-        if (st) return st;
-    }
-    m->tree = std::move(tree);
-    m->rayrec_valid = false;
     return upload_tree(m);
 }
 
@@ -255,7 +232,7 @@ static bool ray_build_in_background() {
 // many subjects against the SAME targets (every level's target is the regular icosphere of its resolution; the template of a group):
 // the host arrays of the last few tables built in this process are kept (coordinates and triangles compared in full on a hit, so a
 // hash collision cannot hand out the wrong table), and a mesh with the same content takes a copy instead of the 10 - 14 ms of
-// build_octree + build_ray_table at ico6.  MSMHIP_RAY_CACHE=off | number of tables kept (default 8, ~10 MB of host memory each at ico6).
+// build_octree + build_ray_table at ico6.  kRayCacheTables are kept (~10 MB of host memory each at ico6).
 struct RayCacheEntry {
     uint64_t hash = 0;
     int V = 0, T = 0;
@@ -272,15 +249,7 @@ struct RayCacheEntry {
 static std::mutex g_ray_cache_mu;
 static std::list<std::shared_ptr<const RayCacheEntry>> g_ray_cache;  // most recently used first
 
-static size_t ray_cache_capacity() {
-    static const size_t cap = [] {
-        const char *e = std::getenv("MSMHIP_RAY_CACHE");
-        if (!e) return (size_t)8;
-        if (std::strcmp(e, "off") == 0) return (size_t)0;
-        return (size_t)std::max(0, std::atoi(e));
-    }();
-    return cap;
-}
+constexpr size_t kRayCacheTables = 8;
 
 static uint64_t content_hash(const msm_mesh *m) {
     auto mix = [](uint64_t h, const void *p, size_t bytes) {
@@ -309,7 +278,6 @@ static std::shared_ptr<const RayCacheEntry> ray_cache_find(const msm_mesh *m, ui
 }
 
 static void ray_cache_store(const msm_mesh *m, uint64_t h) {  // m->tree holds a freshly built table
-    if (ray_cache_capacity() == 0) return;
     auto e = std::make_shared<RayCacheEntry>();
     e->hash = h, e->V = m->V, e->T = m->T;
     e->xyz = m->xyz, e->tri = m->tri;
@@ -317,7 +285,7 @@ static void ray_cache_store(const msm_mesh *m, uint64_t h) {  // m->tree holds a
     e->ray_cell = m->tree.ray_cell, e->ray_edge = m->tree.ray_edge, e->ray_more = m->tree.ray_more, e->ray_excl = m->tree.ray_excl;
     std::lock_guard<std::mutex> lock(g_ray_cache_mu);
     g_ray_cache.push_front(std::move(e));
-    while (g_ray_cache.size() > ray_cache_capacity()) g_ray_cache.pop_back();
+    while (g_ray_cache.size() > kRayCacheTables) g_ray_cache.pop_back();
 }
 
 static void retire_ray_job(msm_mesh *m) {
@@ -331,7 +299,7 @@ static void retire_ray_job(msm_mesh *m) {
 int ensure_rays(msm_mesh *m, bool wait) {
     int st = ensure_masks(m);  // what the ray table cannot settle goes through the masked search
     if (st) return st;
-    if (m->host_xyz_stale) {  // coordinates written on the device (group.cpp: lane meshes): the table is keyed by and built from the host copy
+    if (m->host_xyz_stale) {  // coordinates written on the device (group.cpp: the set-up's fallback mesh): the table is keyed by and built from the host copy
         // on the context's stream (created non-blocking: the null stream does not wait for the kernels that wrote the coordinates there)
         MSM_TRY(stage_d2h(m->ctx, m->xyz.data(), m->d_xyz, sizeof(double) * 3 * (size_t)m->V));
         MSM_TRY(ctx_sync(m->ctx));
@@ -354,7 +322,7 @@ int ensure_rays(msm_mesh *m, bool wait) {
     };
     // (the switches that change what build_ray_table produces are read per call -- the tests flip them within a process: no cache then)
     const char *no_table = std::getenv("MSMHIP_DISABLE_RAYTABLE");
-    const bool cache_ok = ray_cache_capacity() > 0 && !(no_table && no_table[0] == '1') && !std::getenv("MSMHIP_RAY_G");
+    const bool cache_ok = !(no_table && no_table[0] == '1');
     const uint64_t chash = cache_ok ? content_hash(m) : 0;
     std::shared_ptr<const RayCacheEntry> hit = (!m->ray_job && cache_ok) ? ray_cache_find(m, chash) : nullptr;
     if (hit) {  // a mesh with these coordinates and triangles has had its table built in this process
@@ -503,9 +471,7 @@ int query_host(msm_mesh *target, const double *q, int N, int *tri_id, int *vid, 
     // writes its results where the caller has them -- over PCIe, in both directions at once, behind one launch -- and a raised status shows up in the mapped
     // flag: one kernel + one tiny launch + one synchronisation instead of a copy command in, the kernel, three copy commands out and a status copy
     // (126 us around a 16 us kernel at 40 962 queries, VERDICT r4 weak 4: five copy-engine commands of 10-15 us each, one after the other).
-    // MSMHIP_QUERY_DIRECT=off: the copy commands.
-    static const bool direct_off = [] { const char *e = std::getenv("MSMHIP_QUERY_DIRECT"); return e && std::strcmp(e, "off") == 0; }();
-    if (!direct_off && (q_on_device || mq) && (!tri_id || mt) && (!vid || mv) && (!w || mw) && ctx_flag(ctx) == MSM_OK) {
+    if ((q_on_device || mq) && (!tri_id || mt) && (!vid || mv) && (!w || mw) && ctx_flag(ctx) == MSM_OK) {
         MSM_TRY(drop_ctx_pending(ctx));  // a label step queued ahead shares the flag
         const double *sq_dev = q_on_device ? q_on_device : static_cast<const double *>(ctx_mapped(ctx, q, bq));
         int *t_dev = tri_id ? static_cast<int *>(ctx_mapped(ctx, tri_id, bt)) : nullptr, *v_dev = vid ? static_cast<int *>(ctx_mapped(ctx, vid, bv)) : nullptr;
@@ -584,12 +550,12 @@ int vertex_areas(msm_mesh *m, std::vector<double> &area) {
     return MSM_OK;
 }
 
-// Resampler::get_adaptive_barycentric_weights, R/resampler.cpp:72-140, the variant with an exclusion mask (and the comparison
-// path MSMHIP_SURGERY=host), in two halves: the 2 x N nearest-triangle queries run on the GPU (adaptive_queries); the list
+// Resampler::get_adaptive_barycentric_weights, R/resampler.cpp:72-140, the variant with an exclusion mask (or meshes of two
+// contexts), in two halves: the 2 x N nearest-triangle queries run on the GPU (adaptive_queries); the list
 // surgery (transpose, pick, area correction) is done on the host in the reference's serial order so that every sum has the
 // same operand order (adaptive_surgery: touches no handle, so callers may run several of them on worker threads).  Without a
 // mask everything runs on the device: adaptive_weights_dev below.
-int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, AdaptiveQueries &q, int directions) {
+int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, AdaptiveQueries &q) {
     const int nOld = in_mesh->V, nNew = new_mesh->V;
     q.fvid.resize(3 * (size_t)nNew);
     q.rvid.resize(3 * (size_t)nOld);
@@ -597,13 +563,10 @@ int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, A
     q.rw.resize(3 * (size_t)nOld);
     // the query points are the other mesh's vertices, which its handle keeps in HBM (same context, same stream)
     const bool same_ctx = in_mesh->ctx == new_mesh->ctx;
-    int st = MSM_OK;
-    if (directions & 1)
-        st = query_host(in_mesh, new_mesh->xyz.data(), nNew, nullptr, q.fvid.data(), q.fw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (forward)",
+    int st = query_host(in_mesh, new_mesh->xyz.data(), nNew, nullptr, q.fvid.data(), q.fw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (forward)",
                         same_ctx ? new_mesh->d_xyz : nullptr);
     if (st) return st;
-    if (directions & 2)
-        st = query_host(new_mesh, in_mesh->xyz.data(), nOld, nullptr, q.rvid.data(), q.rw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (reverse)",
+    st = query_host(new_mesh, in_mesh->xyz.data(), nOld, nullptr, q.rvid.data(), q.rw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (reverse)",
                         same_ctx ? in_mesh->d_xyz : nullptr);
     if (st) return st;
     q.closest.clear();
@@ -651,16 +614,15 @@ ResampleScratch &resample_scratch(msm_ctx *ctx) {
 }
 }  // namespace
 
-int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check, const DevTree *in_tree) {
-    // Everything is queued on in_mesh's context.  new_mesh may belong to another context of the same GPU (a lane of the gMSM
-    // set-up against the group's template) if its tree and adjacency are complete and synchronised: they are only read.
+int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check) {
+    // Everything is queued on in_mesh's context.  new_mesh may belong to another context of the same GPU (the fallback mesh of the
+    // gMSM set-up against the group's template) if its tree and adjacency are complete and synchronised: they are only read.
     const bool foreign = in_mesh->ctx != new_mesh->ctx;
     if (foreign && (in_mesh->ctx->device != new_mesh->ctx->device || !new_mesh->tree_valid || !new_mesh->d_tid_ptr))
         return fail(MSM_ERR_INVALID, "adaptive weights: the two meshes belong to different contexts");
     msm_ctx *ctx = in_mesh->ctx;
     const int nOld = in_mesh->V, nNew = new_mesh->V;
-    // in_tree: the search structure of in_mesh's current coordinates built elsewhere (a tree of a forest)
-    int st = in_tree ? (foreign ? MSM_OK : ensure_tree(new_mesh)) : (foreign ? ensure_tree(in_mesh) : ensure_tree_pair(in_mesh, new_mesh));
+    int st = foreign ? ensure_tree(in_mesh) : ensure_tree_pair(in_mesh, new_mesh);
     if (st) return st;
     if ((st = ensure_adjacency_dev(in_mesh)) || (st = ensure_adjacency_dev(new_mesh))) return st;
     ResampleScratch &s = resample_scratch(ctx);
@@ -685,7 +647,7 @@ int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out
     MSM_HIP(s.scan_tmp.ensure((size_t)std::max(nNew, nOld) / 4096 + 2));
     MSM_HIP(s.tval.ensure(cap));
     // forward: the new mesh's vertices in the old mesh's tree; reverse: the old vertices in the new mesh's tree (:74-78)
-    st = launch_query(ctx, in_tree ? *in_tree : dev_tree(in_mesh), new_mesh->d_xyz, nNew, nullptr, s.fvid.p, s.fw.p, MSM_WEIGHTS_PROJECTED);
+    st = launch_query(ctx, dev_tree(in_mesh), new_mesh->d_xyz, nNew, nullptr, s.fvid.p, s.fw.p, MSM_WEIGHTS_PROJECTED);
     if (st) return st;
     st = launch_query(ctx, dev_tree(new_mesh), in_mesh->d_xyz, nOld, nullptr, s.rvid.p, s.rw.p, MSM_WEIGHTS_PROJECTED);
     if (st) return st;
@@ -734,14 +696,9 @@ static int adaptive_weights_via_device(msm_mesh *in_mesh, msm_mesh *new_mesh, st
     return MSM_OK;
 }
 
-static bool surgery_on_device() {
-    static const bool host = [] { const char *e = std::getenv("MSMHIP_SURGERY"); return e && std::strcmp(e, "host") == 0; }();
-    return !host;
-}
-
 int adaptive_weights(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *excl, std::vector<int32_t> &row_ptr,
                      std::vector<int32_t> &col, std::vector<double> &val) {
-    if (!excl && in_mesh->ctx == new_mesh->ctx && surgery_on_device()) return adaptive_weights_via_device(in_mesh, new_mesh, row_ptr, col, val);
+    if (!excl && in_mesh->ctx == new_mesh->ctx) return adaptive_weights_via_device(in_mesh, new_mesh, row_ptr, col, val);
     AdaptiveQueries q;
     int st = adaptive_queries(in_mesh, new_mesh, excl != nullptr, q);
     if (st) return st;
@@ -1257,7 +1214,7 @@ int msm_adaptive_barycentric_weights(msm_mesh *in_mesh, msm_mesh *new_mesh, cons
 
 int msm_metric_resample(msm_mesh *in_mesh, const double *data, int32_t D, msm_mesh *new_mesh, const double *excl, double *out, double *excl_out) {
     if (!in_mesh || !new_mesh || !data || !out || D <= 0) return fail(MSM_ERR_INVALID, "msm_metric_resample: bad arguments");
-    if (!excl && !excl_out && in_mesh->ctx == new_mesh->ctx && surgery_on_device()) {
+    if (!excl && !excl_out && in_mesh->ctx == new_mesh->ctx) {
         // queries, list surgery and the weighted sums on the device; only the data go up and the resampled data come back
         msm_ctx *ctx = in_mesh->ctx;
         AdaptiveDev w;

@@ -180,34 +180,20 @@ int resample_weights(msm_cost *c) {
             if (cfw_at(c, j, k) > best) best = cfw_at(c, j, k);
         mw[k] = best;
     }
-    static const bool host_surgery = [] { const char *e = std::getenv("MSMHIP_SURGERY"); return e && std::strcmp(e, "host") == 0; }();
-    if (!host_surgery) {
-        // queries, weight lists and the weighted sum in HBM (resample_kernels.hip); the N sums come back for msm_cost_absolute_weights
-        msm_ctx *ctx = c->ctx;
-        AdaptiveDev w;
-        int st = adaptive_weights_dev(c->source, c->cpgrid, w);
-        if (st) return st;
-        MSM_HIP(c->d_maxw.ensure(Ns));
-        MSM_HIP(c->d_absw.ensure(N));
-        st = upload_staged(ctx, c->d_maxw.p, mw.data(), sizeof(double) * (size_t)Ns);
-        if (st) return st;
-        st = apply_weights_dev(ctx, w, c->d_maxw.p, 1, c->d_absw.p);
-        if (st) return st;
-        c->absw.resize(N);
-        MSM_TRY(stage_d2h(ctx, c->absw.data(), c->d_absw.p, sizeof(double) * (size_t)N));
-        MSM_TRY(ctx_sync(ctx));
-        return MSM_OK;
-    }
-    std::vector<int32_t> rp, col;
-    std::vector<double> val;
-    int st = adaptive_weights(c->source, c->cpgrid, nullptr, rp, col, val);
+    // queries, weight lists and the weighted sum in HBM (resample_kernels.hip); the N sums come back for msm_cost_absolute_weights
+    msm_ctx *ctx = c->ctx;
+    AdaptiveDev w;
+    int st = adaptive_weights_dev(c->source, c->cpgrid, w);
+    if (st) return st;
+    MSM_HIP(c->d_maxw.ensure(Ns));
+    MSM_HIP(c->d_absw.ensure(N));
+    st = upload_staged(ctx, c->d_maxw.p, mw.data(), sizeof(double) * (size_t)Ns);
+    if (st) return st;
+    st = apply_weights_dev(ctx, w, c->d_maxw.p, 1, c->d_absw.p);
     if (st) return st;
     c->absw.resize(N);
-    for (int k = 0; k < N; ++k) {
-        double acc = 0.0;
-        for (int e = rp[k]; e < rp[k + 1]; ++e) acc += mw[col[e]] * val[e];
-        c->absw[k] = acc;
-    }
+    MSM_TRY(stage_d2h(ctx, c->absw.data(), c->d_absw.p, sizeof(double) * (size_t)N));
+    MSM_TRY(ctx_sync(ctx));
     return MSM_OK;
 }
 
@@ -513,7 +499,7 @@ int msm_cost_get_source_data(msm_cost *c) {
     lap("resample_weights");
     msm_ctx *ctx = c->ctx;
     MSM_TRY(c->d_pptr.upload(c->pptr.data(), c->pptr.size(), ctx));
-    if (is_ho(c) || std::getenv("MSMHIP_NO_PATCH_SORT")) {
+    if (is_ho(c)) {
         MSM_TRY(c->d_pidx.upload_vec(c->pidx, ctx));
     } else {
         // Device-side order of the points of each patch: Morton order of their positions (launch_sort_patches), so that the

@@ -164,20 +164,10 @@ int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a)
 
 // ---- fused fusion move of the HO classes (move_kernels.hip) ----
 // bin slots and control triangles per workgroup (at most 64 and 8: the kernel's LDS holds 64 proposed triangles)
-static int env_int(const char *name, int dflt, int lo, int hi) {
-    const char *e = std::getenv(name);
-    if (!e) return dflt;
-    const int v = std::atoi(e);
-    return v < lo ? lo : (v > hi ? hi : v);
-}
-static const int kMoveSlots = env_int("MSMHIP_MOVE_SLOTS", 64, 8, 64), kMoveTriangles = env_int("MSMHIP_MOVE_TRIANGLES", 8, 1, 8);
+constexpr int kMoveSlots = 64, kMoveTriangles = 8;
 
 bool fused_move_applies(const msm_cost *c, const CliqueArgs &a) {
-    static const bool split = [] {
-        const char *e = std::getenv("MSMHIP_MOVE");  // "split": the three-kernel path of round 1 (kept for comparison)
-        return e && std::strcmp(e, "split") == 0;
-    }();
-    return !split && cost_is_ho(c) && a.ho_vals && a.tree.simple && a.tree.ray_G > 0 && a.rmode != 4 && a.rmode != 5 && c->pmax <= 128 && a.T > 0;
+    return cost_is_ho(c) && a.ho_vals && a.tree.simple && a.tree.ray_G > 0 && a.rmode != 4 && a.rmode != 5 && c->pmax <= 128 && a.T > 0;
 }
 
 // per get_source_data(): the workgroups' runs of control triangles and the label-independent part of every bin point
@@ -189,21 +179,18 @@ int ensure_move(msm_cost *c, const CliqueArgs &a) {
     // with many features per sample (the eight-lanes-per-sample passes of k_ho_move<., 2>) smaller workgroups do better: 88 against
     // 95 us at D = 32 with 48 slots / 6 triangles; with one feature the two shapes are level in the kernel and the larger is cheaper to launch
     const bool wide = a.kind == MSM_COST_HO_MULTIVARIATE && a.D >= 12;
-    const bool env_s = std::getenv("MSMHIP_MOVE_SLOTS") != nullptr, env_t = std::getenv("MSMHIP_MOVE_TRIANGLES") != nullptr;
-    int max_slots = (wide && !env_s) ? 48 : kMoveSlots, max_tris = (wide && !env_t) ? 6 : kMoveTriangles;
-    if (!env_s && !env_t) {
-        // A workgroup's time is a chain (proposed triangles, sampling rounds, similarity passes, last phase) whose length grows with the
-        // triangles it holds, and the whole grid is resident at once up to ~1000 workgroups: on the coarser control grids of a registration's
-        // first levels fewer triangles per workgroup shorten every chain at no cost (D = 32: 55 -> 41 us at ico3, 55 -> 34 us at ico2; the
-        // ico4 grid keeps 6 / 8).  The smallest run of triangles that still fits the grid into one residency round:
-        const int most = max_tris;
-        for (int t : {1, 2, 4, 6, 8})
-            if ((T + most - 1) / most <= 512 && t <= most && (T + t - 1) / t <= 1024) {  // only when the usual run leaves half the GPU empty
-                max_tris = t;
-                max_slots = 8 * t;
-                break;
-            }
-    }
+    int max_slots = wide ? 48 : kMoveSlots, max_tris = wide ? 6 : kMoveTriangles;
+    // A workgroup's time is a chain (proposed triangles, sampling rounds, similarity passes, last phase) whose length grows with the
+    // triangles it holds, and the whole grid is resident at once up to ~1000 workgroups: on the coarser control grids of a registration's
+    // first levels fewer triangles per workgroup shorten every chain at no cost (D = 32: 55 -> 41 us at ico3, 55 -> 34 us at ico2; the
+    // ico4 grid keeps 6 / 8).  The smallest run of triangles that still fits the grid into one residency round:
+    const int most = max_tris;
+    for (int t : {1, 2, 4, 6, 8})
+        if ((T + most - 1) / most <= 512 && t <= most && (T + t - 1) / t <= 1024) {  // only when the usual run leaves half the GPU empty
+            max_tris = t;
+            max_slots = 8 * t;
+            break;
+        }
     int slots = 0, nt = 0, cap = max_slots, first = 0;
     auto close = [&](int t_end) {
         if (nt > 0) blk.push_back(make_int4(first, nt, c->pptr[first], c->pptr[t_end] - c->pptr[first]));
@@ -331,10 +318,7 @@ static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling,
     if (st) return st;
     st = ctx_flag(ctx);
     if (st) return st;
-    // diagnostics: MSMHIP_MOVE_LABELS=device sends the labeling with a copy command, MSMHIP_MOVE_OUT=device brings the costs back with one
-    static const bool labels_by_copy = [] { const char *e = std::getenv("MSMHIP_MOVE_LABELS"); return e && std::strcmp(e, "device") == 0; }();
-    static const bool out_by_copy = [] { const char *e = std::getenv("MSMHIP_MOVE_OUT"); return e && std::strcmp(e, "device") == 0; }();
-    const bool packed = a.N <= 4 * kMoveLabelWords && a.L <= 256 && !labels_by_copy;
+    const bool packed = a.N <= 4 * kMoveLabelWords && a.L <= 256;
     MoveLabels lab;
     if (packed) std::memset(lab.w, 0, sizeof(uint32_t) * (size_t)((a.N + 3) / 4));
     for (int i = 0; i < a.N; ++i) {
@@ -342,7 +326,7 @@ static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling,
         if (packed) lab.w[i >> 2] |= (uint32_t)labeling[i] << ((i & 3) * 8);
     }
     void *pin = nullptr;
-    double *out_dev = out_by_copy ? nullptr : (double *)ctx_mapped(ctx, E, out_bytes);
+    double *out_dev = (double *)ctx_mapped(ctx, E, out_bytes);
     const bool direct = out_dev != nullptr;
     if (prefetch && (!direct || !packed || single)) return MSM_OK;  // not the fast form: the hint is ignored, the call itself will do everything
     if (!direct || !packed) {
@@ -351,7 +335,7 @@ static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling,
     }
     bool staged_copy = false;  // the costs come back with a copy command (the pinned block could not be mapped)
     if (!direct) {
-        if (ctx->io_dev && !out_by_copy) {
+        if (ctx->io_dev) {
             out_dev = (double *)((char *)ctx->io_dev + in_pad);
         } else {
             MSM_HIP(c->d_clique_out.ensure((size_t)8 * a.T));  // (also large enough for the T values of a single-combination call)
@@ -384,14 +368,7 @@ static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling,
     c->move_parity ^= 1;
     m.out = out_dev;
     m.host_flags = ctx->d_flag_map;
-    m.trace = nullptr;
     m.single = single ? 1 : 0;
-#ifdef MSM_MOVE_TRACE
-    static DevBuf<unsigned long long> trace_buf;
-    const size_t trace_words = 8 * (size_t)(8 * ((c->move_nblk + 7) / 8)) + 8;  // 8 stamps per workgroup of the grid, then 4 counters (ray_open_reason)
-    MSM_HIP(trace_buf.zero(trace_words, ctx->stream));
-    m.trace = trace_buf.p;
-#endif
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing) {
         e0 = c->ev0[c->ev_next];
@@ -418,16 +395,6 @@ static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling,
         return MSM_OK;
     }
     MSM_TRY(ctx_sync(ctx));
-#ifdef MSM_MOVE_TRACE
-    if (const char *path = std::getenv("MSMHIP_MOVE_TRACE")) {
-        std::vector<unsigned long long> h(trace_words);
-        MSM_HIP(hipMemcpy(h.data(), trace_buf.p, sizeof(unsigned long long) * trace_words, hipMemcpyDeviceToHost));
-        if (FILE *f = std::fopen(path, "wb")) {
-            std::fwrite(h.data(), sizeof(unsigned long long), trace_words, f);
-            std::fclose(f);
-        }
-    }
-#endif
     return fused_move_finish(c, a, m, packed ? &lab : nullptr, staged_copy, direct, pin, in_pad, out_bytes, out_dev, E);
 }
 

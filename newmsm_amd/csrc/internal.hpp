@@ -187,7 +187,7 @@ struct msm_mesh {
     std::vector<int32_t> tri;  // 3 x T SoA
     std::vector<double> feat;  // D x V host copy
     bool tree_valid = false;
-    bool gpu_tree_always = false;   // build the tree on the GPU whatever the size (the lane meshes of the gMSM set-up: the host never sees their coordinates)
+    bool gpu_tree_always = false;   // build the tree on the GPU whatever the size (the fallback mesh of the gMSM set-up: the host never sees its coordinates)
     bool host_xyz_stale = false;    // the coordinates were last written on the device only (group.cpp): fetched before any host-side use
     std::shared_ptr<void> oct_job;  // a GPU build that has been queued but not looked at yet (octree_kernels.hip)
     msm::FlatOctree tree;
@@ -232,14 +232,14 @@ struct AdaptiveQueries {
     std::vector<double> fw, rw;            // and their projected barycentric weights
 };
 // directions: 1 forward (new -> old), 2 reverse (old -> new), 3 both
-int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, AdaptiveQueries &q, int directions = 3);
+int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, AdaptiveQueries &q);
 // The same weights with queries AND list surgery on the device (resample_kernels.hip; no exclusion mask): the CSR stays in HBM.
 struct AdaptiveDev {
     int nOld = 0, nNew = 0;
     const int *row_ptr = nullptr, *col = nullptr;  // device; valid until the next adaptive_weights_dev on this context
     const double *val = nullptr;
 };
-int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check = true, const DevTree *in_tree = nullptr);  // check = false: the caller checks the status word
+int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check = true);  // check = false: the caller checks the status word
 // out (device, D x V(new)) = the weights applied to d_data (device, D x V(in)): barycentric_data_interpolation R/resampler.cpp:40-52
 int apply_weights_dev(msm_ctx *ctx, const AdaptiveDev &w, const double *d_data, int D, double *d_out);
 int ensure_adjacency_dev(msm_mesh *m);
@@ -247,7 +247,6 @@ int ensure_tree_pair(msm_mesh *a, msm_mesh *b);  // both trees; a host build of 
 void adaptive_surgery(const AdaptiveQueries &q, int nOld, int nNew, const std::vector<double> &oldA, const std::vector<double> &newA,
                       const double *excl, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col, std::vector<double> &val);
 void vertex_areas_of(const double *xyz, const int32_t *tri, int V, int T, const Adjacency &a, std::vector<double> &area);
-int install_coords_and_tree(msm_mesh *m, const double *xyz, FlatOctree &&tree);
 int ensure_tree(msm_mesh *m);  // build + upload the search structure if stale
 int gpu_build_octree(msm_mesh *m, const std::function<void()> *overlap = nullptr);
 // B trees over one triangle list and B coordinate sets, built together (octree_kernels.hip: gpu_build_forest); the arrays of tree b
@@ -275,7 +274,6 @@ struct Forest {
 };
 // component a of vertex i of tree b at d_xyz[a * comp_stride + b * tree_stride + i]; MSM_ERR_CAPACITY: a tree outgrew its arrays
 int gpu_build_forest(msm_ctx *ctx, Forest &f, const double *d_xyz, size_t comp_stride, size_t tree_stride, int V, const int32_t *d_tri, int T, int B);
-DevTree forest_tree(const Forest &f, int b);
 int gpu_build_octree_begin(msm_mesh *m);   // the same in two halves: queue the build ... 
 int gpu_build_octree_finish(msm_mesh *m);  // ... wait for it (one build at a time per context)
 int ensure_tree_begin(msm_mesh *m);        // api.cpp: starts the GPU build of an invalid tree (no-op otherwise); ensure_tree() completes it  // octree_kernels.hip: the same tree built in HBM from the mesh's device coordinates (MSM_ERR_CAPACITY: use the host build)

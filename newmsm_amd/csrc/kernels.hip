@@ -907,7 +907,7 @@ static inline int grid_for(int n, int block, int cap) {
 // lanes per query of the search kernels (search_device.hpp: group_search).  Eight while all wavefronts of the launch are resident at once
 // (4 per SIMD at the kernels' 124 registers: 32 768 queries) -- the launch is then one dependent chain, which eight lanes keep shortest
 // (2 562 queries: 7.4 us against 9.2 with four) --, four beyond that, where instruction issue counts as well (40 962 queries on an ico6
-// tree: 13.3 us against 17.2).  MSMHIP_QUERY_LANES=4|8 forces one.
+// tree: 13.3 us against 17.2).
 // The same queries against a target that has a direction table (a simple surface: every regular icosphere, a group's template): a lane per query looks its
 // direction's cell up, tests the (at most seven) candidate triangles' edge planes in float and, when the table vouches for the accepted one (ray_find: the
 // triangle the reference's search returns, provably), computes the weights from the triangle's record exactly as the searching lane of k_query does -- a
@@ -964,14 +964,7 @@ __global__ __launch_bounds__(256) void k_query_open(DevTree T, const double *__r
     }
 }
 
-int query_lanes(long long N) {
-    static const int forced = [] {
-        const char *e = std::getenv("MSMHIP_QUERY_LANES");
-        return e ? std::atoi(e) : 0;
-    }();
-    if (forced == 4 || forced == 8) return forced;
-    return N <= 32768 ? 8 : 4;
-}
+int query_lanes(long long N) { return N <= 32768 ? 8 : 4; }
 
 int launch_query(msm_ctx *ctx, const DevTree &T, const double *d_q, int N, int *d_tri, int *d_vid, double *d_w, int mode) {
     if (N <= 0) return MSM_OK;
@@ -986,8 +979,7 @@ int launch_query(msm_ctx *ctx, const DevTree &T, const double *d_q, int N, int *
 // d_open: N + 1 ints of scratch (the list of unsettled queries and, at d_open[N], their count); a target without a table: the complete search
 int launch_query_rays(msm_ctx *ctx, const DevTree &T, const double *d_q, int N, int *d_tri, int *d_vid, double *d_w, int mode, int *d_open) {
     if (N <= 0) return MSM_OK;
-    static const bool off = [] { const char *e = std::getenv("MSMHIP_QUERY_RAYS"); return e && std::strcmp(e, "off") == 0; }();
-    if (T.ray_G <= 0 || !d_open || off) return launch_query(ctx, T, d_q, N, d_tri, d_vid, d_w, mode);
+    if (T.ray_G <= 0 || !d_open) return launch_query(ctx, T, d_q, N, d_tri, d_vid, d_w, mode);
     MSM_HIP(hipMemsetAsync(d_open + N, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_query_rays, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, T, d_q, N, d_tri, d_vid, d_w, mode, d_open, d_open + N);
     hipLaunchKernelGGL(k_query_open<8>, dim3(256), dim3(256), 0, ctx->stream, T, d_q, N, d_open, d_open + N, d_tri, d_vid, d_w, mode, ctx->d_status);

@@ -138,32 +138,6 @@ __device__ __forceinline__ int ray_find_rec(const DevTree &T, const V3 &p, doubl
     if (t >= 0 && __float_as_int(ev.w) >= 0 && !ray_vouches(T, ev, p)) t = -1;  // its leaf may not list the triangle
     return t;
 }
-#ifdef MSM_MOVE_TRACE
-// diagnostics: why the table left a sample open -- 0 no cell, 1 no candidate near its threshold, 2 near but outside in FP64, 3 its leaf may not list it
-__device__ int ray_open_reason(const DevTree &T, const V3 &p) {
-    float fx, fy, fz;
-    const int4 c = ray_cell_of(T, p, fx, fy, fz);
-    if (c.x < 0) return 0;
-    int4 mo = make_int4(c.w, -1, -1, -1);
-    if (c.w < -1) mo = T.ray_more[-2 - c.w];
-    const double pn = norm(p);
-    int reason = 1;
-    for (int k = 0; k < 7; ++k) {
-        const int ck = k == 0 ? c.x : (k == 1 ? c.y : (k == 2 ? c.z : (k == 3 ? mo.x : (k == 4 ? mo.y : (k == 5 ? mo.z : mo.w)))));
-        if (ck < 0) break;
-        const float4 *r2 = T.ray_tri + (size_t)kRayPieces * ck;
-        const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
-        float least;
-        const int lvl = ray_accept_level(g0, g1, g2, fx, fy, fz, least);
-        if (lvl == 0) continue;
-        reason = 2;
-        const double2 *dq = reinterpret_cast<const double2 *>(r2 + 3);
-        const double2 q0 = dq[0], q1 = dq[1], q2 = dq[2], q3 = dq[3], q4 = dq[4];
-        if (lvl == 2 || ray_accepts_fp64(mk(q0.x, q0.y, q1.x), mk(q1.y, q2.x, q2.y), mk(q3.x, q3.y, q4.x), p, pn, (double)g0.w - kRayFloatAllowance + 1e-12)) return 3;
-    }
-    return reason;
-}
-#endif
 
 // the eight proposed triangles of control triangle t: combination k (bits A,B,C; 0 = current label), I/Fusion/Fusion.h:188-195
 template <bool kPacked>
@@ -286,12 +260,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
     __shared__ int s_npend;
 
     const int tid = threadIdx.x, lane = tid & 63;
-#ifdef MSM_MOVE_TRACE  // diagnostics: phase time stamps of every workgroup (tools/move_trace.py)
-#define MSM_STAMP(k) do { if (m.trace && tid == 0) m.trace[8 * (size_t)blockIdx.x + (k)] = wall_clock64(); } while (0)
-#else
-#define MSM_STAMP(k) do { } while (0)
-#endif
-    MSM_STAMP(0);
     if (blockIdx.x == 0 && tid == 0) m.defer_cnt[m.parity ^ 1] = 0u;  // the previous move's list has been consumed
     const int per = (m.nblk + 7) >> 3;  // the workgroups of an XCD (blockIdx % 8) take a contiguous run of control triangles
     const int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
@@ -327,7 +295,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
         s_flag[tid] = folded ? 1 : 0;
         s_flag[64 + tid] = 0;
     }
-    MSM_STAMP(1);
 
     // ---- samples: s = combination * nslots + slot (neighbouring lanes = neighbouring bin points of one combination)
     for (int base = 0; base < total; base += kThreads) {
@@ -342,7 +309,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
             wa = m.slot_w[3 * slot], wb = m.slot_w[3 * slot + 1], wc = m.slot_w[3 * slot + 2];
         }
         if (base == 0) __syncthreads();  // the proposed triangles are in LDS
-        if (base == 0) MSM_STAMP(2);
         if (s < total && !s_flag[el]) {
             const V3 p = moved_point(s_geo + 9 * el, wa, wb, wc);
             double2 d0, d1, d2, d3, d4, d5;
@@ -360,9 +326,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
                 }
             } else {
                 s_pend[atomicAdd(&s_npend, 1)] = s;
-#ifdef MSM_MOVE_TRACE
-                if (m.trace) atomicAdd(m.trace + 8 * (size_t)gridDim.x + ray_open_reason(a.tree, p), 1ull);
-#endif
             }
         }
         if (kMode >= 2) {
@@ -394,10 +357,8 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
             if (tt >= 0) s_vals[kk * m.cap + j] = similarity_from_moments(a.simmeasure, D, Moments{s_w[3 * tid], s_w[3 * tid + 1], s_w[3 * tid + 2], s_w[3 * kThreads + tid]});
         }
     }
-    MSM_STAMP(3);
     if (total == 0) __syncthreads();  // the barrier of the first round, for a run of empty bins
     __syncthreads();
-    MSM_STAMP(4);
 
     // ---- the samples the direction table left open (0.2 %): the octree leaf's candidates, eight lanes per sample
     // (search_device.hpp: group8_find); what even that cannot decide (no candidate in the leaf: sibling leaves, nearest vertex)
@@ -418,9 +379,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
             s_strain[h] = s_flag[h] ? 0.0 : move_strain(a, s_frame + 5 * (h >> 3), rr);
         }
     }
-#ifdef MSM_MOVE_TRACE
-    if (m.trace && tid == 0) m.trace[8 * (size_t)blockIdx.x + 7] = (unsigned long long)npend;  // how many samples this workgroup had to search for
-#endif
     for (int q0 = 0; q0 < npend; q0 += kThreads / 8) {  // workgroup-uniform
         const int q = q0 + (tid >> 3);
         const bool valid = q < npend;
@@ -465,7 +423,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
         }
     }
     __syncthreads();  // the open samples' values and the strains are in LDS
-    MSM_STAMP(5);
 
     // ---- one lane per evaluation: similarity in the reference's serial order + strain
     if (!ev) return;
@@ -486,7 +443,6 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
         return;
     }
     *dst = move_likelihood(a, n, s_stat + 3 * (tid >> 3), s_wda + (beg - s0), m.slot_cw ? s_cw + (beg - s0) : nullptr, s_sf + (beg - s0), wmean, vals) + s_strain[tid];
-    MSM_STAMP(6);
 }
 
 // The evaluations the main kernel could not finish: a wavefront each, eight lanes per open point (complete search), then the
@@ -563,29 +519,22 @@ int launch_move(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const Move
     if (a.T <= 0 || m.nblk <= 0) return MSM_OK;
     const int mode = move_mode(a);
     // 256 threads and two rounds of samples per workgroup.  Measured alternatives (D = 1 / D = 32 kernel time against 32 / 95 us):
-    // 512 threads, all samples of the 8 triangles in flight at once (MSMHIP_MOVE_THREADS=512) 37 / 102; 4 triangles and one round per
+    // 512 threads, all samples of the 8 triangles in flight at once 37 / 102; 4 triangles and one round per
     // workgroup 34.5 / 91, 2 triangles 46 / 107; the records of a wavefront's 64 first candidates fetched as a team through LDS
     // (neighbouring lanes reading neighbouring 16-byte pieces) 33 / 142.
-    static const int threads = [] { const char *e = std::getenv("MSMHIP_MOVE_THREADS"); return e && std::atoi(e) == 512 ? 512 : 256; }();
+    constexpr int threads = 256;
     const dim3 grid((unsigned)(8 * ((m.nblk + 7) / 8))), block(threads);
     const size_t lds = sizeof(double) * (64 * 9 + 8 * (size_t)m.cap + 3 * (size_t)m.cap + 24 + 40 + 64 + (mode >= 2 ? 4 * threads : 0)) +
                        sizeof(int) * (128 + 8 * (size_t)m.cap + (mode >= 2 ? 4 * threads : 0) + 16);
     if (lds > 64 * 1024) return fail(MSM_ERR_CAPACITY, "fusion move: %d bin slots per workgroup do not fit LDS", m.cap);
     const MoveLabels &lab = labels ? *labels : g_no_labels;
     if (ev_start) MSM_HIP(hipEventRecord(ev_start, ctx->stream));
-#define MSM_MOVE_LAUNCH(PACKED)                                                                                     \
-    do {                                                                                                            \
-        if (threads == 512) {                                                                                       \
-            if (mode == 0) hipLaunchKernelGGL((k_ho_move<PACKED, 0, 512>), grid, block, lds, ctx->stream, a, m, lab);     \
-            else if (mode == 1) hipLaunchKernelGGL((k_ho_move<PACKED, 1, 512>), grid, block, lds, ctx->stream, a, m, lab); \
-            else if (mode == 2) hipLaunchKernelGGL((k_ho_move<PACKED, 2, 512>), grid, block, lds, ctx->stream, a, m, lab); \
-            else hipLaunchKernelGGL((k_ho_move<PACKED, 3, 512>), grid, block, lds, ctx->stream, a, m, lab);                \
-        } else {                                                                                                    \
-            if (mode == 0) hipLaunchKernelGGL((k_ho_move<PACKED, 0, 256>), grid, block, lds, ctx->stream, a, m, lab);     \
-            else if (mode == 1) hipLaunchKernelGGL((k_ho_move<PACKED, 1, 256>), grid, block, lds, ctx->stream, a, m, lab); \
-            else if (mode == 2) hipLaunchKernelGGL((k_ho_move<PACKED, 2, 256>), grid, block, lds, ctx->stream, a, m, lab); \
-            else hipLaunchKernelGGL((k_ho_move<PACKED, 3, 256>), grid, block, lds, ctx->stream, a, m, lab);                \
-        }                                                                                                           \
+#define MSM_MOVE_LAUNCH(PACKED)                                                                                      \
+    do {                                                                                                             \
+        if (mode == 0) hipLaunchKernelGGL((k_ho_move<PACKED, 0, threads>), grid, block, lds, ctx->stream, a, m, lab);     \
+        else if (mode == 1) hipLaunchKernelGGL((k_ho_move<PACKED, 1, threads>), grid, block, lds, ctx->stream, a, m, lab); \
+        else if (mode == 2) hipLaunchKernelGGL((k_ho_move<PACKED, 2, threads>), grid, block, lds, ctx->stream, a, m, lab); \
+        else hipLaunchKernelGGL((k_ho_move<PACKED, 3, threads>), grid, block, lds, ctx->stream, a, m, lab);                \
     } while (0)
     if (labels) MSM_MOVE_LAUNCH(true);
     else MSM_MOVE_LAUNCH(false);

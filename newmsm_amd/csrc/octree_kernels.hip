@@ -616,8 +616,8 @@ int queue_levels(msm_ctx *ctx, OctJob &j, int count) {
 }
 }  // namespace
 
-// The build in two halves, so that a caller with several streams (group.cpp: the lanes of the gMSM set-up) can queue the levels of
-// one mesh and go on with another before looking at the outcome.  begin: everything up to and including the first batch of
+// The build in two halves, so that a caller (api.cpp: ensure_tree_pair; cost.cpp: patches_by_triangle) can queue the levels of
+// one mesh and go on with other work before looking at the outcome.  begin: everything up to and including the first batch of
 // levels, nothing waited for; finish: waits, queues more levels for deeper trees, then the grid, records and cones.  One build at a
 // time per context (the scratch arrays and the counters' landing place belong to the context).
 int gpu_build_octree_begin(msm_mesh *m) {
@@ -843,24 +843,6 @@ int gpu_build_forest(msm_ctx *ctx, Forest &f, const double *d_xyz, size_t comp_s
         f.info[b].grid_depth = std::min(hc[C_MAXDEPTH], 6);
     }
     return again ? finish() : MSM_OK;
-}
-
-DevTree forest_tree(const Forest &f, int b) {
-    DevTree t{};
-    t.node = f.node.p + (size_t)b * f.s_node;
-    t.parent = f.parent.p + (size_t)b * f.s_node;
-    t.leaf_tri = f.leaf_tri.p + (size_t)b * f.s_leaf;
-    t.cone = f.cone.p + (size_t)b * f.s_leaf;
-    t.rec = f.rec.p + (size_t)b * f.s_rec;
-    t.grid = f.grid.p + (size_t)b * f.s_grid;
-    t.grid_depth = f.info[b].grid_depth;
-    t.simple = 0;
-    t.mask = nullptr;
-    t.nnodes = f.info[b].nnodes;
-    t.ray_G = 0;
-    t.ray_cell = nullptr, t.ray_tri = nullptr, t.ray_more = nullptr, t.ray_excl = nullptr;
-    t.ray_r2lo = t.ray_r2hi = 0.0;
-    return t;
 }
 
 int gpu_build_octree(msm_mesh *m, const std::function<void()> *overlap) {

@@ -1069,7 +1069,6 @@ static size_t samples_lds(int pmax, int L, int nsplit) {
 // reason), and more when the patch is so large (coarse control grid under a fine data grid) that the per-label target
 // values would not fit in LDS otherwise.
 int unary_nsplit(int L, int pmax) {
-    if (const char *e = std::getenv("MSMHIP_NSPLIT")) return std::max(1, std::min(L, atoi(e)));  // experiments only
     int n = std::max(1, std::min(4, (int)(((size_t)L * pmax + kChunk - 1) / kChunk)));
     while (n < L && samples_lds(pmax, L, n) > 64 * 1024) ++n;
     return std::min(n, std::max(L, 1));

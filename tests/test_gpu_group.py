@@ -14,7 +14,14 @@ pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-9, 1e-11
 
 
-def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile=0.75, subject_orders=None, label_order_offset=2):
+def folded(xyz, scale=20.0, seed=5):
+    """strong normal jitter, back on the sphere of radius 100: a data mesh full of folds and slivers"""
+    rng = np.random.default_rng(seed)
+    x = xyz + rng.normal(scale=scale, size=xyz.shape)
+    return x / np.linalg.norm(x, axis=1, keepdims=True) * 100.0
+
+
+def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile=0.75, subject_orders=None, label_order_offset=2, fold=()):
     dxyz, dtri = M.make_mesh_from_icosa(data_order)
     cxyz, ctri = M.make_mesh_from_icosa(cp_order)
     txyz, ttri = dxyz, dtri  # template space = a regular sphere at data resolution
@@ -35,6 +42,8 @@ def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile
         if subject_orders is not None:  # subjects on data meshes of their own (different sizes: the set-up's scratch meshes follow)
             dxyz, dtri = (txyz0, ttri0) if subject_orders[s] == data_order else M.make_mesh_from_icosa(subject_orders[s])
         sph = synthetic.known_warp(dxyz, seed=40 + s, rot_deg=1.0 + s, amp=0.5)   # this subject's registered sphere so far
+        if s in fold:
+            sph = folded(sph)
         feat = synthetic.features(synthetic.known_warp(dxyz, seed=90 + s, rot_deg=2.0, amp=1.0), D, seed=5)
         regular = M.Mesh(ctx, dxyz, dtri)
         g.reset_meshspace(s, regular, feat)        # first call: _ORIG_MESHES = the regular sphere
@@ -84,10 +93,15 @@ def test_group_with_68_labels(ctx):
     assert np.allclose(g.computePairwiseCost(p, la, lb), og.pairwise_batch(p, la, lb), rtol=RTOL, atol=ATOL, equal_nan=True)
 
 
-def test_group_subjects_on_different_data_meshes(ctx):
-    """get_patch_data per subject resamples THAT subject's data mesh onto the template: subjects need not share a mesh.  The lanes of
-    the set-up keep scratch meshes per topology and rebuild them when the next subject's differs."""
-    g, og, _ = build(ctx, subject_orders=[4, 3, 4])
+@pytest.mark.parametrize("fold", [(), (1,)], ids=["plain", "folded"])
+def test_group_subjects_on_different_data_meshes(ctx, fold):
+    """get_patch_data per subject resamples THAT subject's data mesh onto the template: subjects need not share a mesh.  fold: the ico3
+    subject's data mesh is folded so badly that its trees outgrow the forest's arrays, and the set-up takes it label by label (stage_fallback)."""
+    g, og, keep = build(ctx, subject_orders=[4, 3, 4], fold=fold)
+    if fold:  # the forest's capacity rule (octree_kernels.hip: gpu_build_forest) holds the unrotated tree too
+        m = keep[2 + 2 * fold[0]]
+        st, _ = M.octree_signature(m.get_coords(), m.tri)
+        assert st["refs"] > 6 * m.T + 256 or st["nodes"] > m.T + 64, st
     rng = np.random.default_rng(5)
     for s, v, l in zip(rng.integers(0, 3, 30), rng.integers(0, 162, 30), rng.integers(0, g.L, 30)):
         ids, data = g.patch(s, v, l)
@@ -467,7 +481,7 @@ def test_group_full_size_properties_64_subjects_ico6(ctx):
     here, so this is checked through size-independent properties): a whole label step (20.7 M pair + 2.6 M triplet costs, processed
     control point by control point in four pieces, delivered into pinned memory behind the kernels) equals the explicit batch
     evaluators on sampled cliques, slices of the step equal the whole, no cost is left unwritten, and a second set-up
-    (pipelined, forest build, six lanes) reproduces the first bit for bit."""
+    (pipelined, forest build, label-batched kernels) reproduces the first bit for bit."""
     from newmsm_amd import problem
 
     S = 64

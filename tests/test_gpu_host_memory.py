@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 def test_staging_blocks_grow_and_rotate_under_a_group_setup(built, monkeypatch):
     """Staging blocks of 64 KB at first (MSMHIP_STAGE_MIN_KB): every upload of the set-up -- features, rotation matrices (72 V bytes per subject), search
-    structures, patch row offsets -- outgrows them or finds them busy while the two set-up pipelines, their batch streams and the lanes copy through the
+    structures, patch row offsets -- outgrows them or finds them busy while the two set-up pipelines and their batch streams copy through the
     contexts' blocks at once; subjects on data meshes of different sizes make the requests grow from subject to subject.  A block is never moved or freed
     while a copy may still read it (the round-4 set-up freed a context's one staging block on growth); the results equal the oracle's."""
     import test_gpu_group as T

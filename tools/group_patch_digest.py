@@ -1,5 +1,5 @@
 """tools/group_patch_digest.py [S] [data_order cp_order [label_order_offset]] -- sha256 over the exported set-up products (resampled maps, patch row offsets, patch index lists) of S subjects (default: ico6 / ico4):
-two builds or two settings of the library (MSMHIP_RANGE_GRID=off, MSMHIP_RANGE_CLUSTER=off, ...) must print the same digest."""
+two builds or two settings of the library (MSMHIP_RANGE_GRID=off or MSMHIP_RANGE_CLUSTER=off) must print the same digest."""
 import hashlib
 import os
 import sys

@@ -1,6 +1,6 @@
 """tools/time_query.py [reps] -- msm_query_triangles (Octree::get_closest_triangle + calc_barycentric_weights, R/octree.cpp:156-214,
 R/resampler.cpp:142-167) at the sizes a registration meets; wall time per call includes the copies of the host-array entry point, so run it
-under `rocprofv3 --kernel-trace --stats` for the kernel's own time (tools/collect_query_profile.sh).  MSMHIP_QUERY_LANES=4|8."""
+under `rocprofv3 --kernel-trace --stats` for the kernel's own time (tools/collect_query_profile.sh)."""
 import os
 import sys
 import time

@@ -1,5 +1,5 @@
 """tools/time_warp.py -- sphere_project_warp of the 40 962 data vertices through a control grid that has just moved (a new search tree per call, as in
-every iteration of a registration: M/mesh_registration.cpp:224), control grids ico2 / ico3 / ico4; MSMHIP_OCTREE=host|gpu forces where the tree is built"""
+every iteration of a registration: M/mesh_registration.cpp:224), control grids ico2 / ico3 / ico4"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
