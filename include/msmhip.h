@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 11  /* 11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 11  /* 11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -463,6 +463,40 @@ int msm_group_fusion_move_dev(msm_group *g, const int32_t *labeling, int32_t lab
  * step's GPU time in milliseconds (-1 when none was timed). */
 int msm_group_time_moves(msm_group *g, int enable);
 int msm_group_move_kernels_ms(msm_group *g, double *ms);
+
+
+/* ------------------------------------------------------------------------------------------------
+ * rigid level (--opt=RIGID / AFFINE).  Replaces Rigid_cost_function (M/rigid_costfunction.cpp): the rotation of the whole data
+ * grid by three Euler angles that maximises the summed similarity of every SOURCE vertex to the TARGET data around it.  The
+ * reference's per-vertex Neighbourhood and sparse similarity matrix are not kept: a vertex's query list depends only on the
+ * closest target triangle (one list per target triangle, built once) and its similarities only on the data (computed inline).
+ * Host arrays are complete on return.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct msm_rigid msm_rigid;
+
+/* Rigid_cost_function(target, source, FEAT) + set_simmeasure + initialise (:26-48): TARGET and SOURCE are both the level's data grid
+ * (SOURCE's coordinates are copied; min_sigma = calculate_MeanVD of them, R/mesh.cpp:276-293); in_feat (D x Vsource) and ref_feat
+ * (D x Vtarget) the level's featurespace.  simmeasure 1 (SSD) or 2 (correlation); anything else: MSM_ERR_INVALID (the reference computes
+ * all-zero similarities there).  The target mesh must outlive the handle, and its coordinates and triangles must not change while the
+ * handle exists: the query lists and min_sigma are built here, and the kernels read the target's coordinates on every evaluation. */
+msm_rigid *msm_rigid_create(msm_ctx *ctx, msm_mesh *target, msm_mesh *source, const double *in_feat, const double *ref_feat, int32_t D,
+                            int32_t simmeasure);
+void msm_rigid_destroy(msm_rigid *r);
+/* update_source (:50): SOURCE's coordinates (3 x V SoA) */
+int msm_rigid_set_source(msm_rigid *r, const double *xyz);
+int msm_rigid_get_source(msm_rigid *r, double *xyz);
+/* rigid_cost_mesh (:123-139) for n Euler triples (euler: n x 3; n <= 4 per launch, more are split): sums[k] = the cost of triple k;
+ * per_vertex (n x V, or NULL) = current_sim after each.  SOURCE is unchanged. */
+int msm_rigid_cost(msm_rigid *r, const double *euler, int32_t n, double *sums, double *per_vertex);
+/* rotate_in_mesh (:110-121): SOURCE rotated in place by euler_rotate (R/point.cpp:154-171) */
+int msm_rigid_rotate(msm_rigid *r, const double euler[3]);
+/* run (:164-228), quirks included: the optimiser's control flow on the host, one launch per gradient (three probes) and one per
+ * accepted-or-not step.  trace (cap x 6, may be NULL with cap 0): one row per iteration {loop, iter, per, step, grad_zero, accepted}
+ * where step is the step the iteration took and grad_zero the cost it evaluated; *n = the number of iterations (rows past cap are not
+ * written).  summary = {RECinit, RECfinal, evaluations}.  SOURCE holds the result. */
+int msm_rigid_run(msm_rigid *r, int32_t iters, double stepsize, double gradsampling, double *trace, int32_t cap, int32_t *n, double summary[3]);
+/* GPU time of the cost launches of the last msm_rigid_run / msm_rigid_cost (HIP events): ms[0] total milliseconds, ms[1] launches */
+int msm_rigid_kernel_ms(msm_rigid *r, double ms[2]);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@
 // newresampler::Mesh::pvalues.  Errors are thrown as msmhip::Error carrying the reference's exception text.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <mutex>
@@ -895,6 +896,63 @@ private:
     std::vector<int32_t> step_lab_;
     int step_label_ = -1;
     detail::HostBuffer quads_, octets_;
+};
+
+// Rigid_cost_function (M/rigid_costfunction.cpp) over msm_rigid_*: the rigid level.  target / source: the level's data grid (SPH_orig, both);
+// in_feat / ref_feat: the level's featurespace (D x V).  simmeasure 1 (SSD) or 2 (correlation).
+class RigidCostFunction {
+public:
+    struct Summary {
+        double RECinit = 0.0, RECfinal = 0.0;
+        int evaluations = 0;
+    };
+    RigidCostFunction(Context &ctx, Mesh &target, Mesh &source, const Matrix &in_feat, const Matrix &ref_feat, int D, int simmeasure)
+        : ctx_(ctx.handle()), target_(&target), source_(&source), in_(in_feat), ref_(ref_feat), D_(D), sim_(simmeasure), V_(source.nvertices()) {}
+    ~RigidCostFunction() { msm_rigid_destroy(h_); }
+    RigidCostFunction(const RigidCostFunction &) = delete;
+    RigidCostFunction &operator=(const RigidCostFunction &) = delete;
+
+    void initialise() {  // :32-48
+        msm_rigid_destroy(h_);
+        h_ = msm_rigid_create(ctx_, target_->handle(), source_->handle(), in_.data(), ref_.data(), D_, sim_);
+        if (!h_) throw Error(MSM_ERR_INVALID, msm_last_error());
+    }
+    void update_source(const Points &xyz) { check(msm_rigid_set_source(h_, to_soa(xyz).data())); }  // :50
+    Points get_source() const {
+        std::vector<double> s(3 * (size_t)V_);
+        check(msm_rigid_get_source(h_, s.data()));
+        return to_aos(s);
+    }
+    // rigid_cost_mesh (:123-139) for n Euler triples (n x 3); SOURCE unchanged
+    std::vector<double> cost(const std::vector<double> &euler, std::vector<double> *per_vertex = nullptr) {
+        const int n = (int)(euler.size() / 3);
+        std::vector<double> sums((size_t)n);
+        if (per_vertex) per_vertex->assign((size_t)n * V_, 0.0);
+        check(msm_rigid_cost(h_, euler.data(), n, sums.data(), per_vertex ? per_vertex->data() : nullptr));
+        return sums;
+    }
+    void rotate(const double euler[3]) { check(msm_rigid_rotate(h_, euler)); }  // rotate_in_mesh
+    // run (:164-228): SOURCE after the run; trace (optional) gets one row {loop, iter, per, step, grad_zero, accepted} per iteration
+    Points run(int iters, double stepsize, double gradsampling, std::vector<double> *trace = nullptr, Summary *summary = nullptr) {
+        int loops = 0;
+        for (double spacing = gradsampling; spacing > 0.05; spacing *= 0.5) ++loops;
+        const int cap = std::max(1, loops * iters);
+        std::vector<double> rows(6 * (size_t)cap);
+        int32_t n = 0;
+        double sm[3] = {0, 0, 0};
+        check(msm_rigid_run(h_, iters, stepsize, gradsampling, rows.data(), cap, &n, sm));
+        if (trace) trace->assign(rows.begin(), rows.begin() + 6 * (size_t)std::min(n, cap));
+        if (summary) summary->RECinit = sm[0], summary->RECfinal = sm[1], summary->evaluations = (int)sm[2];
+        return get_source();
+    }
+    msm_rigid *handle() const { return h_; }
+
+private:
+    msm_ctx *ctx_;
+    Mesh *target_, *source_;
+    Matrix in_, ref_;
+    int D_, sim_, V_;
+    msm_rigid *h_ = nullptr;
 };
 
 }  // namespace msmhip

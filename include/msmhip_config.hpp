@@ -10,7 +10,8 @@
 // std::vector<float> make them there: --lambda=0.0075 reaches the cost function as 0.007499999832361937.  newmsm_amd/config.py is the same
 // parser in Python; tests/test_cpp_config.py checks that the two agree.
 //
-// Reported instead of silently dropped: AFFINE / RIGID levels (the affine stage is outside the path: listed in `skipped`), --IN / --INc (FSL's
+// Reported instead of silently dropped: AFFINE / RIGID levels (listed in `skipped` unless levels_from_config(..., rigid = true) asks for them as
+// rigid levels), --IN / --INc (FSL's
 // histogram matching is not in the reference tree), --excl.  --regoption=5 (aMSM) needs the anatomical surfaces (command line: --inanat / --refanat):
 // levels_from_config(..., anat = true) says the caller has them.
 #ifndef MSMHIP_CONFIG_HPP
@@ -180,8 +181,10 @@ inline Config parse_config(const std::string &text, bool no_config = false) {
 
 // the DISCRETE levels of `c` for data with D feature rows; skipped (optional): index and method of the levels that are not DISCRETE
 // anat: the caller has the anatomical surfaces a --regoption=5 (aMSM) run needs (they come from the command line: --inanat / --refanat)
+// rigid: AFFINE / RIGID levels come back as levels with LevelSpec::rigid set (data grid, smoothing, --it, --simval, --stepsize, --gradsampling:
+// what Rigid_cost_function::set_parameters reads, M/rigid_costfunction.cpp:50-58) instead of being listed in `skipped`
 inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *varnorm = nullptr, std::vector<std::pair<int, std::string>> *skipped = nullptr,
-                                                 bool anat = false) {
+                                                 bool anat = false, bool rigid = false) {
     if (c.IN || c.INc) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
     if (c.excl) throw ConfigError("--excl (exclusion masks from the cut thresholds) is not wired into the level loop");
     if (c.regoption == 4)  // M/mesh_registration.cpp:101-102
@@ -198,6 +201,15 @@ inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *v
     if (varnorm) *varnorm = c.VN;
     std::vector<LevelSpec> levels;
     for (size_t i = 0; i < c.opt.size(); ++i) {
+        if (rigid && (c.opt[i] == "RIGID" || c.opt[i] == "AFFINE")) {  // "AFFINE" is for backward compatibility (M/mesh_registration.cpp:66)
+            LevelSpec lv;
+            lv.rigid = true;
+            lv.data_order = c.datagrid[i], lv.sigma_in = c.sigma_in[i], lv.sigma_ref = c.sigma_ref[i];
+            lv.options.iters = c.it[i], lv.options.cost.simmeasure = c.simval[i];
+            lv.stepsize = c.stepsize, lv.gradsampling = c.gradsampling;
+            levels.push_back(lv);
+            continue;
+        }
         if (c.opt[i] != "DISCRETE") {
             if (skipped) skipped->emplace_back((int)i, c.opt[i]);
             continue;

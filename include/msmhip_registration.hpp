@@ -241,21 +241,25 @@ struct LevelSpec {
     int data_order = 5, cp_order = 2;
     double sigma_in = 0.0, sigma_ref = 0.0;
     LevelOptions options;
+    // a RIGID level (levels_from_config(..., rigid = true)): Rigid_cost_function with options.iters, options.cost.simmeasure and these
+    bool rigid = false;
+    double stepsize = (double)0.01f, gradsampling = 0.5;
 };
 
 struct MultiresResult {
     Points sphere_reg;                            // the input sphere moved through the final warp ("sphere.reg", M/mesh_registration.cpp:352-356)
     std::vector<Points> level_reg;                // the registered data grid of every level
-    std::vector<std::vector<double>> energies;    // per level, per iteration
+    std::vector<std::vector<double>> energies;    // per level, per iteration (a RIGID level: its trace, six values per iteration)
     std::vector<std::vector<int32_t>> labelings;  // every iteration's labeling, level after level
 };
 
-// Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE levels without file I/O -- the C++ twin of
+// Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE and RIGID levels without file I/O -- the C++ twin of
 // newmsm_amd/registration.py: run_multiresolution (same calls in the same order; tests/test_cpp_host.py compares the two):
 //   per level  featurespace::initialise (M/featurespace.cpp:39-86: metric_resample of both data sets onto the level's icosphere, smooth_data,
 //              variance_normalise), project_CPgrid (M/mesh_registration.cpp:131-162: the warp of the previous level carried to the new data
 //              grid and control grid, unfold) and run_discrete_opt;
 //   at the end transform (:352-356).
+// A RIGID level runs Rigid_cost_function on the level's featurespace instead of run_discrete_opt (:66-72, 112-116): no control grid, no labelings.
 // in_* / ref_*: the input and reference spheres (radius 100) with their D x V data.
 inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, const Triangles &in_tri, const Matrix &in_data, const Points &ref_xyz,
                                            const Triangles &ref_tri, const Matrix &ref_data, int D, const std::vector<LevelSpec> &levels, bool varnorm,
@@ -284,15 +288,17 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
             if (varnorm) variance_normalise(f, ico.nvertices());
             feats[k] = std::move(f);
         }
-        Points sph_in, cp_start;
+        Points sph_in, cp_start, incurrent;
         bool have_cp_start = false;
         if (sph_reg_prev.empty()) {
             sph_in = ico_xyz;  // level 1, no transformed mesh: project_CPgrid only unfolds the (regular) data grid
         } else {
             auto [prev_xyz, prev_tri] = make_mesh_from_icosa(prev_order);
             Mesh prev(ctx, prev_xyz, prev_tri);
-            const Points incurrent = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(in_xyz, prev, sph_reg_prev); });
+            incurrent = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(in_xyz, prev, sph_reg_prev); });
             sph_in = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(ico_xyz, in_mesh, incurrent); });
+        }
+        if (!sph_reg_prev.empty() && !lv.rigid) {  // warp_CPgrid (a rigid level has no control grid)
             auto [cp_xyz, cp_tri] = make_mesh_from_icosa(lv.cp_order);
             Mesh cpm(ctx, PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(cp_xyz, in_mesh, incurrent); }), cp_tri);  // warp_CPgrid
             PhaseClock::timed(clock, "unfold", [&] { return unfold(cpm); });
@@ -303,6 +309,21 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
             Mesh moved(ctx, sph_in, ico_tri);
             PhaseClock::timed(clock, "unfold", [&] { return unfold(moved); });
             sph_in = moved.get_coords();
+        }
+        if (lv.rigid) {
+            Points reg = PhaseClock::timed(clock, "rigid", [&] {
+                RigidCostFunction rcf(ctx, ico, ico, feats[0], feats[1], D, lv.options.cost.simmeasure);
+                rcf.initialise();
+                rcf.update_source(sph_in);
+                std::vector<double> trace;
+                Points out = rcf.run(lv.options.iters, lv.stepsize, lv.gradsampling, &trace);
+                res.energies.push_back(std::move(trace));
+                return out;
+            });
+            res.level_reg.push_back(reg);
+            sph_reg_prev = std::move(reg);
+            prev_order = lv.data_order;
+            continue;
         }
         Matrix w_in, w_ref;
         Weighting weights;

@@ -159,6 +159,14 @@ SIGNATURES = {
     "msm_group_patch": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, c_ip, c_dp, C.c_int32, c_ip]),
     "msm_group_pairwise_batch": (C.c_int, [_VP, c_ip, c_ip, c_ip, C.c_int32, c_dp]),
     "msm_group_triplet_batch": (C.c_int, [_VP, c_ip, c_ip, c_ip, c_ip, C.c_int32, c_dp]),
+    "msm_rigid_create": (_VP, [_VP, _VP, _VP, c_dp, c_dp, C.c_int32, C.c_int32]),
+    "msm_rigid_destroy": (None, [_VP]),
+    "msm_rigid_set_source": (C.c_int, [_VP, c_dp]),
+    "msm_rigid_get_source": (C.c_int, [_VP, c_dp]),
+    "msm_rigid_cost": (C.c_int, [_VP, c_dp, C.c_int32, c_dp, c_dp]),
+    "msm_rigid_rotate": (C.c_int, [_VP, c_dp]),
+    "msm_rigid_run": (C.c_int, [_VP, C.c_int32, C.c_double, C.c_double, c_dp, C.c_int32, c_ip, c_dp]),
+    "msm_rigid_kernel_ms": (C.c_int, [_VP, c_dp]),
 }
 
 _lib = None

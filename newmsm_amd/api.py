@@ -907,3 +907,84 @@ class DiscreteGroupCostFunction:
         out = np.zeros(len(t_))
         check(lib().msm_group_triplet_batch(self.h, pt, pa, pb, pc, len(t_), out.ctypes.data_as(c_dp)))
         return out
+
+
+# ------------------------------------------------------------------ rigid level
+def rigid_loops(gradsampling):
+    """the number of outer loops of Rigid_cost_function::run (M/rigid_costfunction.cpp:173-225): the sampling spacing halves while it is > 0.05"""
+    n, spacing = 0, float(gradsampling)
+    while spacing > 0.05:
+        n, spacing = n + 1, spacing * 0.5
+    return n
+
+
+class RigidCostFunction:
+    """Rigid_cost_function (M/rigid_costfunction.cpp) over msm_rigid_*: the rotation of the level's data grid (SOURCE) that maximises its
+    summed similarity to the reference data (TARGET).  target / source: Meshes of the level's data grid (SPH_orig, both); in_feat / ref_feat:
+    the level's featurespace (D x V).  simmeasure 1 (SSD) or 2 (correlation)."""
+
+    def __init__(self, ctx, target, source, in_feat, ref_feat, simmeasure=1):
+        self.ctx, self.target, self.source = ctx, target, source
+        self.in_feat = np.ascontiguousarray(np.atleast_2d(in_feat), dtype=np.float64)
+        self.ref_feat = np.ascontiguousarray(np.atleast_2d(ref_feat), dtype=np.float64)
+        if self.in_feat.shape != (self.ref_feat.shape[0], source.V) or self.ref_feat.shape[1] != target.V:
+            raise ValueError("RigidCostFunction: features must be D x V of the source and of the target")
+        self.simmeasure = int(simmeasure)
+        self.V = source.V
+        self.h = None
+
+    def initialise(self):
+        """initialise (:32-48): min_sigma from SOURCE, the per-target-triangle query lists, the data on the device"""
+        self.close()
+        self.h = lib().msm_rigid_create(self.ctx.h, self.target.h, self.source.h, self.in_feat.ctypes.data_as(c_dp),
+                                        self.ref_feat.ctypes.data_as(c_dp), self.in_feat.shape[0], self.simmeasure)
+        if not self.h:
+            raise MsmError(-1, lib().msm_last_error().decode())
+        return self
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            lib().msm_rigid_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def update_source(self, xyz):
+        """update_source (:50): SOURCE's coordinates (V x 3)"""
+        check(lib().msm_rigid_set_source(self.h, _soa(xyz)[1]))
+
+    def get_source(self):
+        out = np.zeros((3, self.V))
+        check(lib().msm_rigid_get_source(self.h, out.ctypes.data_as(c_dp)))
+        return np.ascontiguousarray(out.T)
+
+    def cost(self, euler, per_vertex=False):
+        """rigid_cost_mesh (:123-139) for each Euler triple (n x 3): the sums, and with per_vertex=True also the n x V values; SOURCE unchanged"""
+        e, pe = _d(np.atleast_2d(euler))
+        n = e.shape[0]
+        sums = np.zeros(n)
+        pv = np.zeros((n, self.V)) if per_vertex else None
+        check(lib().msm_rigid_cost(self.h, pe, n, sums.ctypes.data_as(c_dp), pv.ctypes.data_as(c_dp) if pv is not None else None))
+        return (sums, pv) if per_vertex else sums
+
+    def rotate(self, euler):
+        """rotate_in_mesh (:110-121) of SOURCE in place"""
+        check(lib().msm_rigid_rotate(self.h, _d(np.asarray(euler, dtype=np.float64).reshape(3))[1]))
+
+    def run(self, iters=20, stepsize=0.01, gradsampling=0.5):
+        """run (:164-228).  Returns (SOURCE after the run (V x 3), trace, summary): trace rows {loop, iter, per, step, grad_zero, accepted},
+        summary dict(RECinit, RECfinal, evaluations)"""
+        cap = max(1, rigid_loops(gradsampling) * int(iters))
+        trace = np.zeros((cap, 6))
+        n = C.c_int32()
+        summary = np.zeros(3)
+        check(lib().msm_rigid_run(self.h, int(iters), float(stepsize), float(gradsampling), trace.ctypes.data_as(c_dp), cap, C.byref(n),
+                                  summary.ctypes.data_as(c_dp)))
+        return self.get_source(), trace[: n.value].copy(), dict(RECinit=summary[0], RECfinal=summary[1], evaluations=int(summary[2]))
+
+    def kernel_ms(self):
+        """GPU milliseconds and launches of the cost kernels of the last run / cost call"""
+        ms = np.zeros(2)
+        check(lib().msm_rigid_kernel_ms(self.h, ms.ctypes.data_as(c_dp)))
+        return float(ms[0]), int(ms[1])

@@ -10,8 +10,8 @@ Host logic only (no GPU, no library call).  Values whose option type is `float` 
 they become doubles, as `Utilities::Option<float>` / `std::vector<float>` do there: --lambda=0.0075 reaches the cost function as
 0.007499999832361937, --shearmod=0.4 as 0.4000000059604645.
 
-Out of scope here, reported instead of silently dropped: AFFINE / RIGID levels (`--opt=AFFINE,...`: the affine stage is not part of the path;
-`levels_from_config` lists them in `skipped`), --IN / --INc (FSL's histogram matching is not in the reference tree), --excl.  --regoption=5 (aMSM)
+Reported instead of silently dropped unless asked for: AFFINE / RIGID levels (`--opt=AFFINE,...`: `levels_from_config` lists them in
+`skipped`; with rigid=True it returns them as rigid levels).  Out of scope: --IN / --INc (FSL's histogram matching is not in the reference tree), --excl.  --regoption=5 (aMSM)
 needs the anatomical surfaces, which come from the command line (--inanat / --refanat): `levels_from_config(cfg, D, anat=True)` says the caller has them.
 """
 import numpy as np
@@ -121,13 +121,16 @@ def parse_config(text):
     return cfg
 
 
-def levels_from_config(cfg, D, anat=False, groupwise=False):
+def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False):
     """The DISCRETE levels of `cfg` (parse_config's result) for data with D feature rows, as keyword sets of run_multiresolution, plus what
     applies to the whole run: returns (levels, run_kw, skipped) -- run_multiresolution(ops, ..., levels, **run_kw).  skipped: the (index,
     method) of levels that are not DISCRETE (the affine stage is outside the path).  fix_parameters_for_level + NonLinearSRegDiscreteModel::
     set_parameters / initialize_cost_function (M/mesh_registration.cpp:786-817, M/DiscreteModel.cpp:26-60).  groupwise: the levels of a --groupwise
     run (group_registration.run_group_multiresolution), whose model has its own regulariser (strain triplets per subject, M/DiscreteGroupCostFunction.cpp:
-    26-52) whatever --regoption says: the checks on --regoption do not apply (Group_Mesh_registration::initialize_level has none)."""
+    26-52) whatever --regoption says: the checks on --regoption do not apply (Group_Mesh_registration::initialize_level has none).
+    rigid: AFFINE / RIGID levels come back as levels too, dict(method="RIGID", data_order, sigma_in, sigma_ref, iters, simmeasure, stepsize,
+    gradsampling) -- what Rigid_cost_function::set_parameters reads (M/rigid_costfunction.cpp:50-58) -- instead of being listed in `skipped`
+    (opt-in: the executables run them when MSMHIP_RIGID=on).  Groupwise runs refuse them whatever this says (group_registration.py)."""
     if cfg["IN"] or cfg["INc"]:
         raise ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available")
     if cfg["excl"]:
@@ -152,6 +155,10 @@ def levels_from_config(cfg, D, anat=False, groupwise=False):
         raise ConfigError("--regoption=1 (pairwise regulariser) is driven by FastPD only in the reference; Fusion / MCMC read triplets")
     levels, skipped = [], []
     for i, method in enumerate(cfg["opt"]):
+        if rigid and method in ("RIGID", "AFFINE"):  # "AFFINE" is for backward compatibility (M/mesh_registration.cpp:66)
+            levels.append(dict(method="RIGID", data_order=cfg["datagrid"][i], sigma_in=cfg["sigma_in"][i], sigma_ref=cfg["sigma_ref"][i], iters=cfg["it"][i],
+                               simmeasure=cfg["simval"][i], stepsize=cfg["stepsize"], gradsampling=cfg["gradsampling"]))
+            continue
         if method != "DISCRETE":
             skipped.append((i, method))
             continue
@@ -280,11 +287,11 @@ PRESETS = {
 }
 
 
-def preset_levels(name, D, iterations=None, anat=False):
+def preset_levels(name, D, iterations=None, anat=False, rigid=False):
     """(levels, run_kw, skipped) of a shipped configuration; iterations (optional): overrides --it of the DISCRETE levels, in order; anat: the caller
-    has the anatomical surfaces a --regoption=5 preset needs"""
-    levels, run_kw, skipped = levels_from_config(parse_config(PRESETS[name]), D, anat=anat)
+    has the anatomical surfaces a --regoption=5 preset needs; rigid: its AFFINE / RIGID levels are returned as levels (levels_from_config)"""
+    levels, run_kw, skipped = levels_from_config(parse_config(PRESETS[name]), D, anat=anat, rigid=rigid)
     if iterations is not None:
-        for lv, it in zip(levels, iterations):
+        for lv, it in zip([lv for lv in levels if lv.get("method") != "RIGID"], iterations):
             lv["iters"] = it
     return levels, run_kw, skipped

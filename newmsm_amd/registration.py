@@ -133,6 +133,20 @@ class ProductOps:
     def pairwise_solve(self, unary, paircosts, pairs, passes):
         return api.pairwise_icm(unary, paircosts, pairs, passes=passes)
 
+    # --- rigid level
+    def rigid_level(self, target_xyz, target_tri, ref_feat, source_xyz, source_tri, src_feat, sph_in, iters, simmeasure, stepsize, gradsampling):
+        """Rigid_cost_function(SPH_orig, SPH_orig, FEAT) + initialise, update_source(sph_in), run (M/mesh_registration.cpp:66-72, 112-116):
+        returns (the rotated data grid, the optimiser's trace)"""
+        target = self.mesh(target_xyz, target_tri)
+        source = target if source_xyz is target_xyz else self.mesh(source_xyz, source_tri)
+        rcf = api.RigidCostFunction(self.ctx, target, source, src_feat, ref_feat, simmeasure=simmeasure).initialise()
+        try:
+            rcf.update_source(sph_in)
+            xyz, trace, _ = rcf.run(iters=iters, stepsize=stepsize, gradsampling=gradsampling)
+        finally:
+            rcf.close()
+        return xyz, trace
+
 
 class _ProductCost:
     def __init__(self, cf):
@@ -378,7 +392,7 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
 
 def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data, levels, *, varnorm=False, timings=None, in_cfweight=None,
                         ref_cfweight=None, labelings_out=None, in_anat=None, ref_anat=None, **level_kw):
-    """Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE levels without file I/O:
+    """Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE and RIGID levels without file I/O:
 
     per level  featurespace::initialise (M/featurespace.cpp:39-86: metric_resample of both data sets onto the level's
                icosphere, smooth_data, variance_normalise), project_CPgrid (M/mesh_registration.cpp:131-162: the warp of the
@@ -386,7 +400,9 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
     at the end transform (:352-356): the input sphere moved through the final warp ("sphere.reg").
 
     in_* / ref_*: the input and reference spheres (radius 100) with their D x V data.  levels: dicts with data_order, cp_order
-    and optionally sg_order, sigma_in, sigma_ref, iters, mciters, cost_params.  in_cfweight / ref_cfweight (rows x V on the
+    and optionally sg_order, sigma_in, sigma_ref, iters, mciters, cost_params; a level with method="RIGID" (config.levels_from_config(...,
+    rigid=True)) runs Rigid_cost_function instead (ops.rigid_level): its regs entry is the rotated data grid, its energies entry the optimiser's
+    trace, and it adds no labelings.  in_cfweight / ref_cfweight (rows x V on the
     input / reference sphere, optional): cost-function weightings, brought to each level's grid by nearest-neighbour
     interpolation (downsample_cfweighting, M/mesh_registration.cpp:334-350).  labelings_out (optional list): receives every iteration's labeling, level
     after level (the parity tests compare the optimiser's decisions of two runs).  in_anat / ref_anat (V x 3 on the vertices of the input /
@@ -426,6 +442,7 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
                 ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies):
     """the level loop of run_multiresolution (see there)"""
     for lv in levels:
+        rigid = lv.get("method") == "RIGID"
         ico_xyz, ico_tri = ops.icosphere(lv["data_order"])
         ico = ops.mesh(ico_xyz, ico_tri)
         feats = []
@@ -445,6 +462,7 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
             prev_xyz, prev_tri = ops.icosphere(prev_order)
             incurrent = timed("sphere_project_warp", ops.sphere_project_warp, in_xyz, ops.mesh(prev_xyz, prev_tri), sph_reg_prev)
             sph_in = timed("sphere_project_warp", ops.sphere_project_warp, ico_xyz, in_mesh, incurrent)
+        if sph_reg_prev is not None and not rigid:  # a rigid level has no control grid (no warp_CPgrid)
             cp_xyz, cp_tri = ops.icosphere(lv["cp_order"])
             cpm = ops.mesh(timed("sphere_project_warp", ops.sphere_project_warp, cp_xyz, in_mesh, incurrent), cp_tri)  # warp_CPgrid
             timed("unfold", ops.unfold, cpm)
@@ -452,6 +470,13 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
         moved = ops.mesh(sph_in, ico_tri)
         timed("unfold", ops.unfold, moved)
         sph_in = ops.coords(moved)
+        if rigid:  # Rigid_cost_function on the level's featurespace: the grid rotated as a whole, no labelings
+            sph_reg, trace = timed("rigid", ops.rigid_level, ico_xyz, ico_tri, feats[1], ico_xyz, ico_tri, feats[0], sph_in, lv["iters"], lv["simmeasure"],
+                                   lv["stepsize"], lv["gradsampling"])
+            regs.append(sph_reg)
+            all_energies.append(trace)
+            sph_reg_prev, prev_order = sph_reg, lv["data_order"]
+            continue
         kw = dict(level_kw)
         kw.update({k: lv[k] for k in ("sg_order", "iters", "mciters", "mcparam", "cost_params", "kind", "rescale_labels", "optimiser", "simmeasure", "rmode",
                                       "converge") if k in lv})

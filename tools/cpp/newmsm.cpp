@@ -11,7 +11,7 @@
 //                    <out>sphere-<i>.LR.reg<surf>, <out>transformed_and_reprojected-<i><data> (M/group_mesh_registration.cpp:120-133, .h:79-82)
 //   -f               GIFTI (.surf.gii / .func.gii), ASCII (.asc / .dpv), ASCII_MAT (.asc / .txt) as set_output_format names them (:827-842)
 //
-// Outside the path and said so instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr), --trans, VTK output; the binary solve of
+// Outside the path and said so instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr unless MSMHIP_RIGID=on runs them), --trans, VTK output; the binary solve of
 // --dopt=HOCR / FastPD is a stand-in (iterated conditional modes: FastPD and ELC are licence-restricted and FSL-bound), so a run exercises the path exactly as
 // newmsm would but its labelings are not HOCR's.  tools/register_files.py is the same program in Python; tests/test_gpu_registration.py compares their files.
 //
@@ -181,7 +181,9 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const bool anat = !o.get("inanat").empty();
     bool varnorm = false;
     std::vector<std::pair<int, std::string>> skipped;
-    const std::vector<LevelSpec> levels = levels_from_config(parse_config(slurp(o.get("conf")), o.get("conf").empty()), D, &varnorm, &skipped, anat);
+    const char *rigid_env = std::getenv("MSMHIP_RIGID");  // "on": AFFINE / RIGID levels run (Rigid_cost_function on the GPU) instead of being skipped
+    const bool rigid = rigid_env && std::string(rigid_env) == "on";
+    const std::vector<LevelSpec> levels = levels_from_config(parse_config(slurp(o.get("conf")), o.get("conf").empty()), D, &varnorm, &skipped, anat, rigid);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
     Points in_anat, ref_anat;

@@ -25,7 +25,8 @@ and the template recentred and rescaled to RAD (M/group_mesh_registration.h:46-5
 120-133, .h:79-82): <out>sphere-<i>.reg<surf>, <out>sphere-<i>.LR.reg<surf>, <out>transformed_and_reprojected-<i><data> (the subject's data
 resampled from its registered sphere onto the TEMPLATE).
 
-Outside the path and reported instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr), --trans, --IN / --INc / --excl; the
+Outside the path and reported instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr unless MSMHIP_RIGID=on, which runs
+them), --trans, --IN / --INc / --excl; the
 binary solve of --dopt=HOCR / FastPD is a stand-in (iterated conditional modes: FastPD and ELC are licence-restricted and FSL-bound), so a run
 exercises the path exactly as newmsm would but its labelings are not HOCR's.
 """
@@ -103,8 +104,13 @@ def read_conf(path):
         return f.read()
 
 
+def rigid_enabled():
+    """MSMHIP_RIGID=on: AFFINE / RIGID levels run (Rigid_cost_function on the GPU) instead of being skipped"""
+    return os.environ.get("MSMHIP_RIGID", "") == "on"
+
+
 def discrete_levels(cfg, D, anat=False, groupwise=False):
-    levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise)
+    levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise)
     for index, method in skipped:
         print("register_files.py: level %d (--opt=%s) is outside the path (the affine stage stays on the CPU in newmsm): skipped" % (index + 1, method), file=sys.stderr)
     if not levels:
