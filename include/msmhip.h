@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 11  /* 11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 11  /* 11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -497,6 +497,18 @@ int msm_rigid_rotate(msm_rigid *r, const double euler[3]);
 int msm_rigid_run(msm_rigid *r, int32_t iters, double stepsize, double gradsampling, double *trace, int32_t cap, int32_t *n, double summary[3]);
 /* GPU time of the cost launches of the last msm_rigid_run / msm_rigid_cost (HIP events): ms[0] total milliseconds, ms[1] launches */
 int msm_rigid_kernel_ms(msm_rigid *r, double ms[2]);
+
+/* ------------------------------------------------------------------------------------------------
+ * strain maps of an aMSM run (save_transformed_data, M/mesh_registration.cpp:397-407).
+ * ---------------------------------------------------------------------------------------------- */
+/* calculate_strains(fit_radius, orig, final) (M/reg_tools.cpp:365-549): orig is the input anatomy with its own triangles (its normals are
+ * estimate_normals', R/mesh.cpp:133-150), final_xyz (3 x V SoA) the same vertices after the registration (project_anatomical_mesh's result).
+ * Per vertex i: the members j of |x_i - x_j| <= r with n_j . n_i >= 0, r = fit_radius grown by 0.5 until there are more than 8; a
+ * least-squares quadratic fit of the neighbourhood in i's tangent frame; the principal stretches of the deformation gradient.
+ * strains (4 x V): the maximum and minimum principal stretch and 0.5 (lambda^2 - 1) of each.  kept (V, optional): the member count;
+ * radius (V, optional): the final r.  V must equal orig's vertex count and fit_radius be > 0.  A mesh where some vertex can never
+ * have 9 members (the reference's radius would grow forever): MSM_ERR_INVALID.  Host arrays are complete on return. */
+int msm_calculate_strains(msm_mesh *orig, const double *final_xyz, int32_t V, double fit_radius, double *strains, int32_t *kept, double *radius);
 
 #ifdef __cplusplus
 }

@@ -236,6 +236,26 @@ inline Points barycentric_coords_resample(Mesh &from, const Points &coords, cons
     check(msm_barycentric_coords_resample(from.handle(), to_soa(coords).data(), to_soa(q).data(), (int32_t)(q.size() / 3), out.data()));
     return to_aos(out);
 }
+// project_anatomical_mesh (R/resampler.cpp:260-282): the vertices of `sphere` (the registered input sphere) placed on the anatomy by their barycentric
+// weights on `target` (the reference sphere); `anat` (the reference anatomy) gives the coordinates when it has target's vertex count, target's own
+// coordinates do otherwise.  The result has sphere's vertex count (and, in the reference, its triangles).
+inline Points project_anatomical_mesh(const Mesh &sphere, Mesh &target, const Points &anat) {
+    const Points coords = (int)(anat.size() / 3) == target.nvertices() ? anat : target.get_coords();
+    return barycentric_coords_resample(target, coords, sphere.get_coords());
+}
+// calculate_strains(fit_radius, orig, final) (M/reg_tools.cpp:365-549): orig is the input anatomy with its own triangles, final its vertices after the
+// registration.  Returns the 4 x V rows (maximum and minimum principal stretch, 0.5 (lambda^2 - 1) of each); kept / radius (optional): every
+// vertex's member count and final fit radius.
+inline Matrix calculate_strains(const Mesh &orig, const Points &final_xyz, double fit_radius = 2.0, std::vector<int32_t> *kept = nullptr,
+                                std::vector<double> *radius = nullptr) {
+    const int V = orig.nvertices();
+    Matrix strains(4 * (size_t)V);
+    if (kept) kept->assign(V, 0);
+    if (radius) radius->assign(V, 0.0);
+    check(msm_calculate_strains(orig.handle(), to_soa(final_xyz).data(), (int32_t)(final_xyz.size() / 3), fit_radius, strains.data(),
+                                kept ? kept->data() : nullptr, radius ? radius->data() : nullptr));
+    return strains;
+}
 // Mesh_registration::resample_anatomy (M/mesh_registration.cpp:250-332) without its surface_resample call [host]: see msm_resample_anatomy_grid
 struct AnatomyGrid {
     Points sphere_xyz;       // ANAT_ico, radius rad

@@ -167,6 +167,7 @@ SIGNATURES = {
     "msm_rigid_rotate": (C.c_int, [_VP, c_dp]),
     "msm_rigid_run": (C.c_int, [_VP, C.c_int32, C.c_double, C.c_double, c_dp, C.c_int32, c_ip, c_dp]),
     "msm_rigid_kernel_ms": (C.c_int, [_VP, c_dp]),
+    "msm_calculate_strains": (C.c_int, [_VP, c_dp, C.c_int32, C.c_double, c_dp, c_ip, c_dp]),
 }
 
 _lib = None

@@ -421,6 +421,29 @@ def barycentric_coords_resample(from_mesh, coords, q):
     return np.ascontiguousarray(out.T)
 
 
+def project_anatomical_mesh(sphere_mesh, target_mesh, anat_xyz):
+    """project_anatomical_mesh (R/resampler.cpp:260-282): every vertex of sphere_mesh (the registered input sphere) placed on the anatomy by its
+    barycentric weights on target_mesh (the reference sphere).  anat_xyz (the reference anatomy) gives the coordinates when it has target_mesh's
+    vertex count, target_mesh's own coordinates do otherwise.  Returns (V(sphere), 3); the result's triangles are sphere_mesh's."""
+    anat = np.asarray(anat_xyz, dtype=np.float64).reshape(-1, 3)
+    coords = anat if len(anat) == target_mesh.V else target_mesh.get_coords()
+    return barycentric_coords_resample(target_mesh, coords, sphere_mesh.get_coords())
+
+
+def calculate_strains(orig_mesh, final_xyz, fit_radius=2.0, with_neighbourhoods=False):
+    """calculate_strains(fit_radius, orig, final) (M/reg_tools.cpp:365-549) on the device: orig_mesh is the input anatomy with its own triangles,
+    final_xyz (V, 3) its vertices after the registration.  Returns the 4 x V rows (maximum and minimum principal stretch, 0.5 (lambda^2 - 1) of
+    each); with with_neighbourhoods also the member count and the final fit radius of every vertex."""
+    x, px = _soa(final_xyz)
+    V = x.shape[1]
+    strains = np.zeros((4, V))
+    kept = np.zeros(V, dtype=np.int32)
+    radius = np.zeros(V)
+    check(lib().msm_calculate_strains(orig_mesh.h, px, V, float(fit_radius), strains.ctypes.data_as(c_dp), kept.ctypes.data_as(c_ip),
+                                      radius.ctypes.data_as(c_dp)))
+    return (strains, kept, radius) if with_neighbourhoods else strains
+
+
 def smooth_data(orig_mesh, data, sph_low, sigma, excl=None):
     """newresampler::smooth_data (R/resampler.cpp:168-230); returns the smoothed D x V rows (and the smoothed mask)."""
     d, pd = _d(np.atleast_2d(data))

@@ -13,6 +13,7 @@
 //
 // The rotation matrices are built on the host with libm (device sin / cos may differ in the last bit).  Every decision and every value uses
 // the reference's FP64 operations in the reference's order (-ffp-contract=off); the weight's exp() is the device's.
+#include "frame_device.hpp"
 #include "kernels.hpp"
 #include "rigid.hpp"
 #include "search_device.hpp"
@@ -27,22 +28,6 @@ __device__ __forceinline__ V3 rot_t(const double *R, const V3 &v) {
 }
 
 __device__ __forceinline__ V3 src_vertex(const double *src, int V, int i) { return mk(src[i], src[V + i], src[2 * (size_t)V + i]); }
-
-// calculate_tangs (M/reg_tools.cpp:205-262) from the local normal a (already flipped towards the point)
-__device__ __forceinline__ void tangs_of(const V3 &a, V3 &e1, V3 &e2) {
-    double mag;
-    if (fabs(a.x) >= fabs(a.y) && fabs(a.x) >= fabs(a.z)) {
-        mag = sqrt(a.z * a.z + a.y * a.y);
-        e1 = mag == 0 ? mk(0.0, 0.0, 1.0) : mk(0.0, -a.z / mag, a.y / mag);
-    } else if (fabs(a.y) >= fabs(a.x) && fabs(a.y) >= fabs(a.z)) {
-        mag = sqrt(a.z * a.z + a.x * a.x);
-        e1 = mag == 0 ? mk(0.0, 0.0, 1.0) : mk(-a.z / mag, 0.0, a.x / mag);
-    } else {
-        mag = sqrt(a.y * a.y + a.x * a.x);
-        e1 = mag == 0 ? mk(1.0, 0.0, 0.0) : mk(-a.y / mag, a.x / mag, 0.0);
-    }
-    e2 = normalized(cross(a, e1));
-}
 
 // sim(q, i) of sparsesimkernel: -SSD (M/similarities.cpp:98-112) or corr (:54-96) between input column i and reference column q (dense data)
 __device__ __forceinline__ double sim_of(const RigidEvalArgs &a, int i, int q) {
@@ -82,18 +67,7 @@ __global__ __launch_bounds__(256) void k_rigid_eval(RigidEvalArgs a) {
     const double *rs = a.rot + (size_t)b * 3 * a.V;  // SOURCE rotated by probe b
     const V3 p = src_vertex(rs, a.V, i);
     // Mesh::local_normal (R/mesh.cpp:133-141) of the rotated mesh: the incident triangles' normals summed in trID order
-    V3 nsum = mk(0.0, 0.0, 0.0);
-    for (int k = a.stid_ptr[i]; k < a.stid_ptr[i + 1]; ++k) {
-        const int t = a.stid[k];
-        const V3 v0 = src_vertex(rs, a.V, a.stri[t]);
-        const V3 v1 = src_vertex(rs, a.V, a.stri[a.Ts + t]);
-        const V3 v2 = src_vertex(rs, a.V, a.stri[2 * (size_t)a.Ts + t]);
-        const V3 n = tri_normal(v0, v1, v2);
-        nsum.x += n.x;
-        nsum.y += n.y;
-        nsum.z += n.z;
-    }
-    V3 nrm = normalized(nsum);
+    V3 nrm = local_normal(rs, a.V, a.stri, a.Ts, a.stid_ptr, a.stid, i);
     if (dot(nrm, p) < 0) nrm = scale(nrm, -1.0);
     V3 e1, e2;
     tangs_of(nrm, e1, e2);

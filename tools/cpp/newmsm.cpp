@@ -6,7 +6,8 @@
 //   pairwise         set_input / set_reference (load, recentre, true_rescale to RAD: M/mesh_registration.cpp:416-438), set_anatomical as loaded (:434-438),
 //                    the configuration through the reference's grammar (msmhip_config.hpp = parse_reg_options :459-784), run_multiresolutions
 //                    (msmhip_registration.hpp = :30-50), then <out>sphere.reg<surf>, <out>sphere.LR.reg<surf>, <out>transformed_and_reprojected<data>
-//                    (:47-49, :352-408, M/mesh_registration.h:170)
+//                    (:47-49, :352-408, M/mesh_registration.h:170); with both anatomical meshes also <out>anat.reg.surf.gii (project_anatomical_mesh)
+//                    and <out>STRAINS.func.gii (calculate_strains, four rows), always GIFTI (:397-407)
 //   -g / --groupwise --meshes / --data path lists (read_ascii_list :871-884), --template, --mask; per subject <out>sphere-<i>.reg<surf>,
 //                    <out>sphere-<i>.LR.reg<surf>, <out>transformed_and_reprojected-<i><data> (M/group_mesh_registration.cpp:120-133, .h:79-82)
 //   -f               GIFTI (.surf.gii / .func.gii), ASCII (.asc / .dpv), ASCII_MAT (.asc / .txt) as set_output_format names them (:827-842)
@@ -24,6 +25,7 @@
 #include <map>
 #include <sstream>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "msmhip_config.hpp"
@@ -35,6 +37,7 @@ using namespace msmhip;
 namespace {
 
 constexpr double RAD = 100.0;
+constexpr double kStrainFitRadius = 2.0;  // calculate_strains(2, in_anat, ANAT_TRANS), M/mesh_registration.cpp:405
 
 struct Flag {
     const char *shortname, *longname, *help;
@@ -54,7 +57,7 @@ const Flag kFlags[] = {
     {"-M", "--inmesh", "input mesh (available formats: ASCII, GIFTI). Needs to be a sphere", true},
     {"-R", "--refmesh", "reference mesh (available formats: ASCII, GIFTI). Needs to be a sphere. If not included algorithm assumes reference mesh is equivalent input", true},
     {"-a", "--inanat", "input anatomical mesh (must either supply both input and reference anatomical surfaces or none)", true},
-    {"-A", "--refanat", "reference anatomical mesh", true},
+    {"-A", "--refanat", "reference anatomical mesh (with both: <out>anat.reg.surf.gii and <out>STRAINS.func.gii are written too)", true},
     {"-i", "--indata", "scalar or multivariate data for input - can be ASCII (.asc,.dpv,.txt) or GIFTI (.func.gii or .shape.gii)", true},
     {"-I", "--refdata", "scalar or multivariate data for reference", true},
     {"-t", "--trans", "Transformed source mesh (output of a previous registration): not supported here", true},
@@ -187,8 +190,9 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
     Points in_anat, ref_anat;
-    if (anat) {  // set_anatomical: loaded as they are
-        in_anat = io::load_surface(o.get("inanat")).first;
+    Triangles in_anat_tri;
+    if (anat) {  // set_anatomical: loaded as they are (in_anat keeps its triangles: its normals serve the strain map)
+        std::tie(in_anat, in_anat_tri) = io::load_surface(o.get("inanat"));
         ref_anat = io::load_surface(o.get("refanat")).first;
     }
     Matrix in_w, ref_w;
@@ -209,6 +213,13 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     io::save_surface(out + "sphere.LR.reg" + fmt.surf, res.level_reg.back(), last_tri);  // saveSPH_reg
     Mesh moved(ctx, res.sphere_reg, itri), target(ctx, rxyz, rtri);
     save_data(out + "transformed_and_reprojected" + fmt.data, rxyz, metric_resample(moved, idata, target), D);  // save_transformed_data
+    if (anat) {  // save_transformed_data's aMSM outputs (:397-407), GIFTI whatever -f says
+        const Points anat_reg = project_anatomical_mesh(moved, target, ref_anat);
+        io::save_surface(out + "anat.reg.surf.gii", anat_reg, itri);
+        if (o.has("verbose")) std::cout << "Calculate strains." << std::endl;
+        Mesh in_anat_mesh(ctx, in_anat, in_anat_tri);
+        io::save_metric(out + "STRAINS.func.gii", calculate_strains(in_anat_mesh, anat_reg, kStrainFitRadius), 4);
+    }
     if (o.has("verbose"))
         for (size_t k = 0; k < res.energies.size(); ++k) {
             std::cout << "level " << k + 1 << ": energies per iteration";

@@ -13,7 +13,11 @@ outputs of :47-49:
 with <surf> / <data> = .surf.gii / .func.gii (GIFTI), .asc / .dpv (ASCII), .asc / .txt (ASCII_MAT) as set_output_format (:827-842) names them.
 
 With --inanat / --refanat (both or none, CLI/newmsm.cpp:40-45) and --regoption=5 in the configuration the run is an aMSM one: the anatomical
-surfaces are loaded as they are (set_anatomical, M/mesh_registration.cpp:434-438: no recentre, no rescale).
+surfaces are loaded as they are (set_anatomical, M/mesh_registration.cpp:434-438: no recentre, no rescale).  Given both, save_transformed_data
+(:397-407) writes two more files, always GIFTI (Mesh::save of a name without an extension):
+    <out>anat.reg.surf.gii                    project_anatomical_mesh: the input sphere's topology, each registered vertex placed on the reference anatomy
+    <out>STRAINS.func.gii                     calculate_strains(2, in_anat, anat.reg): per vertex of the input anatomy the maximum and minimum principal
+                                              stretch and 0.5 (lambda^2 - 1) of each (four rows)
 
 Groupwise mode (CLI/newmsm.cpp:13-27, -g / --groupwise):
 
@@ -41,6 +45,7 @@ import newmsm_amd as M  # noqa: E402
 from newmsm_amd import config, group_registration, meshio, registration  # noqa: E402
 
 RAD = 100.0
+STRAIN_FIT_RADIUS = 2.0  # calculate_strains(2, in_anat, ANAT_TRANS), M/mesh_registration.cpp:405
 
 
 def on_sphere(xyz, rad=RAD):
@@ -184,8 +189,9 @@ def main(argv):
         raise SystemExit("Mesh_registration: input and reference data have different numbers of feature rows (%d, %d)" % (idata.shape[0], rdata.shape[0]))
     levels, run_kw = discrete_levels(config.parse_config(read_conf(a.conf)), idata.shape[0], anat=bool(a.inanat))
     cfw = {}
-    if a.inanat:  # set_anatomical: loaded as they are
-        cfw.update(in_anat=meshio.load_surface(a.inanat)[0], ref_anat=meshio.load_surface(a.refanat)[0])
+    if a.inanat:  # set_anatomical: loaded as they are (in_anat keeps its triangles: its normals serve the strain map)
+        in_anat, in_anat_tri = meshio.load_surface(a.inanat)
+        cfw.update(in_anat=in_anat, ref_anat=meshio.load_surface(a.refanat)[0])
     if a.inweight and a.refweight:
         cfw.update(in_cfweight=meshio.load_data(a.inweight, len(ixyz)), ref_cfweight=meshio.load_data(a.refweight, len(rxyz)))
     ctx = M.Context(a.device)
@@ -198,6 +204,12 @@ def main(argv):
     meshio.save_surface(out + "sphere.LR.reg" + surf_ext, level_regs[-1], last_tri)                 # saveSPH_reg
     moved, target = M.Mesh(ctx, reg, itri), M.Mesh(ctx, rxyz, rtri)
     save_data(out + "transformed_and_reprojected" + data_ext, rxyz, M.metric_resample(moved, idata, target))  # save_transformed_data
+    if a.inanat:  # save_transformed_data's aMSM outputs (:397-407), GIFTI whatever -f says
+        anat_reg = M.project_anatomical_mesh(moved, target, cfw["ref_anat"])
+        meshio.save_surface(out + "anat.reg.surf.gii", anat_reg, itri)
+        if a.verbose:
+            print("Calculate strains.")
+        meshio.save_metric(out + "STRAINS.func.gii", M.calculate_strains(M.Mesh(ctx, in_anat, in_anat_tri), anat_reg, STRAIN_FIT_RADIUS))
     if a.verbose:
         for k, e in enumerate(energies):
             print("level %d: energies per iteration %s" % (k + 1, [round(v, 4) for v in e]))
