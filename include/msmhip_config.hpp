@@ -12,7 +12,9 @@
 //
 // Reported instead of silently dropped: AFFINE / RIGID levels (listed in `skipped` unless levels_from_config(..., rigid = true) asks for them as
 // rigid levels), --IN / --INc (FSL's
-// histogram matching is not in the reference tree), --excl.  --regoption=5 (aMSM) needs the anatomical surfaces (command line: --inanat / --refanat):
+// histogram matching is not in the reference tree).  --excl / --cutthr are parsed into Config::excl / Config::cutthr and apply to the whole run: the
+// caller hands them to run_multiresolutions / run_group_multiresolutions (exclusion_from_config), which refuse --excl together with both cost-function
+// weightings.  --regoption=5 (aMSM) needs the anatomical surfaces (command line: --inanat / --refanat):
 // levels_from_config(..., anat = true) says the caller has them.
 #ifndef MSMHIP_CONFIG_HPP
 #define MSMHIP_CONFIG_HPP
@@ -179,6 +181,13 @@ inline Config parse_config(const std::string &text, bool no_config = false) {
     return c;
 }
 
+// --excl and --cutthr of `c` for run_multiresolutions / run_group_multiresolutions (_exclude and _threshold, M/mesh_registration.cpp:705-706)
+inline Exclusion exclusion_from_config(const Config &c) {
+    Exclusion e;
+    e.on = c.excl, e.lower = c.cutthr[0], e.upper = c.cutthr[1];
+    return e;
+}
+
 // the DISCRETE levels of `c` for data with D feature rows; skipped (optional): index and method of the levels that are not DISCRETE
 // anat: the caller has the anatomical surfaces a --regoption=5 (aMSM) run needs (they come from the command line: --inanat / --refanat)
 // rigid: AFFINE / RIGID levels come back as levels with LevelSpec::rigid set (data grid, smoothing, --it, --simval, --stepsize, --gradsampling:
@@ -186,7 +195,6 @@ inline Config parse_config(const std::string &text, bool no_config = false) {
 inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *varnorm = nullptr, std::vector<std::pair<int, std::string>> *skipped = nullptr,
                                                  bool anat = false, bool rigid = false) {
     if (c.IN || c.INc) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
-    if (c.excl) throw ConfigError("--excl (exclusion masks from the cut thresholds) is not wired into the level loop");
     if (c.regoption == 4)  // M/mesh_registration.cpp:101-102
         throw ConfigError("--regoption 4 has been removed from newMSM. Use --regoption 3 for spherical mesh regularisation or --regoption 5 for anatomical mesh "
                           "regularisation.");

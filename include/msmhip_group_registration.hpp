@@ -137,10 +137,12 @@ struct GroupMultiresResult {
 //              evaluate (:59-68): level 1 starts every subject on the data grid, later levels carry each subject's warp to the new data grid and
 //              control grid (project_CPgrid with the subject's index, M/mesh_registration.cpp:131-162), then run_discrete_opt (:70-118);
 //   at the end transform (:120-125).
-// meshes: per subject (xyz, tri), spheres of radius 100; datas: per subject D x V(mesh).
+// meshes: per subject (xyz, tri), spheres of radius 100; datas: per subject D x V(mesh).  excl (--excl, --cutthr): every subject's exclusion mask in the
+// feature preparation of every level (level_features); it does not enter the cost function.
 inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::vector<std::pair<Points, Triangles>> &meshes, const std::vector<Matrix> &datas, int D,
                                                       const Points &template_xyz, const Triangles &template_tri, const std::vector<GroupLevelSpec> &levels,
-                                                      bool varnorm, const std::vector<double> *mask = nullptr, PhaseClock *clock = nullptr) {
+                                                      bool varnorm, const std::vector<double> *mask = nullptr, PhaseClock *clock = nullptr,
+                                                      const Exclusion &excl = Exclusion()) {
     const int S = (int)meshes.size();
     if ((int)datas.size() != S) throw Error(MSM_ERR_INVALID, "featurespace::Initialize do not have the same number of datasets and surface meshes");  // M/featurespace.cpp:43-44
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "run_group_multiresolutions: no DISCRETE level");
@@ -154,10 +156,7 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
         Mesh ico(ctx, ico_xyz, ico_tri);
         std::vector<Matrix> feats;
         for (int s = 0; s < S; ++s) {
-            Matrix f = PhaseClock::timed(clock, "metric_resample", [&] { return metric_resample(*in_mesh[(size_t)s], datas[(size_t)s], ico); });
-            if (lv.sigma_in > 0.0) f = PhaseClock::timed(clock, "smooth_data", [&] { return smooth_data(ico, f, ico, lv.sigma_in); });
-            if (varnorm) variance_normalise(f, ico.nvertices());
-            feats.push_back(std::move(f));
+            feats.push_back(level_features(*in_mesh[(size_t)s], datas[(size_t)s], ico, lv.sigma_in, varnorm, excl, clock));
         }
         std::vector<Points> sph, cps_start;
         if (prev_regs.empty()) {
@@ -165,16 +164,12 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
         } else {
             auto [prev_xyz, prev_tri] = make_mesh_from_icosa(prev_order);
             Mesh prev_ico(ctx, prev_xyz, prev_tri);
-            auto [cp_xyz, cp_tri] = make_mesh_from_icosa(lv.cp_order);
             for (int s = 0; s < S; ++s) {
                 const Points &in_xyz = meshes[(size_t)s].first;
                 const Points incurrent = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(in_xyz, prev_ico, prev_regs[(size_t)s]); });
-                Mesh moved(ctx, PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(ico_xyz, *in_mesh[(size_t)s], incurrent); }), ico_tri);
-                Mesh cpm(ctx, PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(cp_xyz, *in_mesh[(size_t)s], incurrent); }), cp_tri);  // warp_CPgrid
-                PhaseClock::timed(clock, "unfold", [&] { return unfold(cpm); });
-                PhaseClock::timed(clock, "unfold", [&] { return unfold(moved); });
-                cps_start.push_back(cpm.get_coords());
-                sph.push_back(moved.get_coords());
+                Points cp;
+                sph.push_back(project_start(ctx, ico_xyz, ico_tri, *in_mesh[(size_t)s], incurrent, lv.cp_order, &cp, clock));
+                cps_start.push_back(std::move(cp));
             }
         }
         GroupLevelResult r = run_group_discrete_opt(ctx, template_xyz, template_tri, ico_xyz, ico_tri, feats, D, sph, lv.cp_order, lv.options,
@@ -197,7 +192,6 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
 // regulariser, so --regoption is not looked at (the twin of newmsm_amd/config.py: levels_from_config(..., groupwise=True)).
 inline std::vector<GroupLevelSpec> group_levels_from_config(const Config &c, bool *varnorm = nullptr) {
     if (c.IN || c.INc) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
-    if (c.excl) throw ConfigError("--excl (exclusion masks from the cut thresholds) is not wired into the level loop");
     for (const std::string &m : c.opt)
         if (m == "RIGID" || m == "AFFINE") throw ConfigError("AFFINE/RIGID registration is not supported in groupwise mode.");
     if (c.dopt != "HOCR") throw ConfigError("Groupwise mode is only supported in the HOCR version of MSM.");

@@ -11,6 +11,8 @@
 #define MSMHIP_REGISTRATION_HPP
 
 #include <chrono>
+#include <cmath>
+#include <iostream>
 #include <map>
 #include <memory>
 #include <string>
@@ -253,6 +255,65 @@ struct MultiresResult {
     std::vector<std::vector<int32_t>> labelings;  // every iteration's labeling, level after level
 };
 
+// --excl / --cutthr: exclusion masks from the cut thresholds in every level's feature preparation (level_features)
+struct Exclusion {
+    bool on = false;
+    double lower = 0.0, upper = 0.0001;  // --cutthr
+};
+
+// One data set of featurespace::initialise (M/featurespace.cpp:52-84) on a level's grid `ico`: metric_resample from its native mesh, smooth_data when
+// sigma > 0, variance_normalise when varnorm.  With excl.on the mask is create_exclusion of the native data over the cut range (1 = kept, 0 = every
+// feature inside it: the medial wall of real data); resampling and smoothing leave it out and each replaces the mask by its own on the grid
+// (R/resampler.cpp:54-67, 168-230); the variance statistics run over vertices with mask > 0 and the others stay as they are (M/reg_tools.cpp:804-843).
+// Made afresh at every level from the native data, as the reference does.  mask_out (optional): the level-grid mask (empty without excl.on).
+inline Matrix level_features(Mesh &mesh, const Matrix &data, Mesh &ico, double sigma, bool varnorm, const Exclusion &excl, PhaseClock *clock,
+                             std::vector<double> *mask_out = nullptr) {
+    std::vector<double> mask;
+    if (excl.on) mask = create_exclusion(data, mesh.nvertices(), excl.lower, excl.upper);
+    std::vector<double> *EXCL = excl.on ? &mask : nullptr;
+    Matrix f = PhaseClock::timed(clock, "metric_resample", [&] { return metric_resample(mesh, data, ico, EXCL); });
+    if (sigma > 0.0) f = PhaseClock::timed(clock, "smooth_data", [&] { return smooth_data(ico, f, ico, sigma, EXCL); });
+    if (varnorm) variance_normalise(f, ico.nvertices(), EXCL);
+    if (mask_out) *mask_out = std::move(mask);
+    return f;
+}
+
+// project_CPgrid (M/mesh_registration.cpp:131-162) for a level that starts from a warp of the input sphere, in_mesh -> moved_in: the warp of the
+// previous level carried to the input sphere (`incurrent`) or, at the first level, the --trans sphere.  The level's data grid is carried through it
+// and unfolded; so is its control grid (warp_CPgrid, M/DiscreteModel.h:140-143) when cp_start is given (a rigid level has no control grid).
+inline Points project_start(Context &ctx, const Points &ico_xyz, const Triangles &ico_tri, Mesh &in_mesh, const Points &moved_in, int cp_order, Points *cp_start,
+                            PhaseClock *clock) {
+    Mesh moved(ctx, PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(ico_xyz, in_mesh, moved_in); }), ico_tri);
+    if (cp_start) {
+        auto [cp_xyz, cp_tri] = make_mesh_from_icosa(cp_order);
+        Mesh cpm(ctx, PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(cp_xyz, in_mesh, moved_in); }), cp_tri);  // warp_CPgrid
+        PhaseClock::timed(clock, "unfold", [&] { return unfold(cpm); });
+        *cp_start = cpm.get_coords();
+    }
+    PhaseClock::timed(clock, "unfold", [&] { return unfold(moved); });
+    return moved.get_coords();
+}
+
+// The --trans sphere as project_CPgrid looks at it at the first level (M/mesh_registration.cpp:136-145): null when it was not given or has the input
+// sphere's coordinates (Mesh operator==, R/mesh.cpp:1285-1290: every coordinate within EPSILON = 1e-8), with the reference's warning.  It is taken as
+// it is, not recentred and not rescaled (set_transformed); it must have the input sphere's vertex count, because sphere_project_warp reads it at the
+// input sphere's vertex numbers (the reference would read out of bounds).
+inline const Points *usable_transformed(const Points *trans_xyz, const Points &in_xyz) {
+    if (!trans_xyz) return nullptr;
+    if (trans_xyz->size() != in_xyz.size())
+        throw Error(MSM_ERR_INVALID, "MeshREG ERROR:: the transformed mesh (--trans) has " + std::to_string(trans_xyz->size() / 3) + " vertices, the input mesh has " +
+                                         std::to_string(in_xyz.size() / 3));
+    for (size_t i = 0; i < in_xyz.size(); ++i)
+        if (!(std::fabs((*trans_xyz)[i] - in_xyz[i]) < 1e-8)) return trans_xyz;
+    std::cerr << " WARNING: transformed mesh has the same coordinates as the input mesh " << std::endl;
+    return nullptr;
+}
+
+inline const char *excl_with_weightings_message() {
+    return "--excl together with --inweight and --refweight is not available: downsample_cfweighting (M/mesh_registration.cpp:334-350) reads the level grid's "
+           "exclusion mask at vertex numbers of the weightings' own meshes, which is out of bounds or meaningless unless the two meshes have the same size";
+}
+
 // Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE and RIGID levels without file I/O -- the C++ twin of
 // newmsm_amd/registration.py: run_multiresolution (same calls in the same order; tests/test_cpp_host.py compares the two):
 //   per level  featurespace::initialise (M/featurespace.cpp:39-86: metric_resample of both data sets onto the level's icosphere, smooth_data,
@@ -261,14 +322,23 @@ struct MultiresResult {
 //   at the end transform (:352-356).
 // A RIGID level runs Rigid_cost_function on the level's featurespace instead of run_discrete_opt (:66-72, 112-116): no control grid, no labelings.
 // in_* / ref_*: the input and reference spheres (radius 100) with their D x V data.
+// trans_xyz (--trans, optional): the input sphere as an earlier registration left it (its sphere.reg), taken as it is.  Only the first level looks at
+// it: its data grid and control grid start carried through input sphere -> trans_xyz, which is what every later level does with the warp of the level
+// before it, so sphere_reg is the composition.  A first level that is RIGID has no control grid to carry (the reference would call warp_CPgrid on a
+// model that does not exist yet); its data grid is projected.
+// excl (--excl, --cutthr): masks in the feature preparation only.  They do not enter the cost function: combine_weighting (:234-248) returns ones
+// unless both weightings are given, and that combination is refused (excl_with_weightings_message).
 inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, const Triangles &in_tri, const Matrix &in_data, const Points &ref_xyz,
                                            const Triangles &ref_tri, const Matrix &ref_data, int D, const std::vector<LevelSpec> &levels, bool varnorm,
                                            PhaseClock *clock = nullptr, const Points *in_anat = nullptr, const Points *ref_anat = nullptr,
-                                           const Matrix *in_cfweight = nullptr, int in_cfrows = 0, const Matrix *ref_cfweight = nullptr, int ref_cfrows = 0) {
+                                           const Matrix *in_cfweight = nullptr, int in_cfrows = 0, const Matrix *ref_cfweight = nullptr, int ref_cfrows = 0,
+                                           const Points *trans_xyz = nullptr, const Exclusion &excl = Exclusion()) {
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "run_multiresolutions: no DISCRETE level");
     if ((in_anat != nullptr) != (ref_anat != nullptr)) throw Error(MSM_ERR_INVALID, "Error: must supply both anatomical meshes or none");  // CLI/newmsm.cpp:41-43
     if (in_anat && (in_anat->size() != in_xyz.size() || ref_anat->size() != ref_xyz.size()))
         throw Error(MSM_ERR_INVALID, "MeshREG ERROR:: input/reference anatomical mesh resolution is inconsistent with input/reference spherical mesh resolution.");
+    if (excl.on && in_cfweight && ref_cfweight) throw Error(MSM_ERR_INVALID, excl_with_weightings_message());
+    trans_xyz = usable_transformed(trans_xyz, in_xyz);
     Mesh in_mesh(ctx, in_xyz, in_tri), ref_mesh(ctx, ref_xyz, ref_tri);
     Anatomy anatomy;
     if (in_anat) anatomy.in_sphere = &in_mesh, anatomy.ref_sphere = &ref_mesh, anatomy.in_anat = in_anat, anatomy.ref_anat = ref_anat;
@@ -279,34 +349,22 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
         auto [ico_xyz, ico_tri] = make_mesh_from_icosa(lv.data_order);
         Mesh ico(ctx, ico_xyz, ico_tri);
         Matrix feats[2];
-        for (int k = 0; k < 2; ++k) {
-            Mesh &mesh = k == 0 ? in_mesh : ref_mesh;
-            const Matrix &data = k == 0 ? in_data : ref_data;
-            const double sigma = k == 0 ? lv.sigma_in : lv.sigma_ref;
-            Matrix f = PhaseClock::timed(clock, "metric_resample", [&] { return metric_resample(mesh, data, ico); });
-            if (sigma > 0.0) f = PhaseClock::timed(clock, "smooth_data", [&] { return smooth_data(ico, f, ico, sigma); });
-            if (varnorm) variance_normalise(f, ico.nvertices());
-            feats[k] = std::move(f);
-        }
+        for (int k = 0; k < 2; ++k)
+            feats[k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref, varnorm, excl, clock);
+        // project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         Points sph_in, cp_start, incurrent;
-        bool have_cp_start = false;
-        if (sph_reg_prev.empty()) {
-            sph_in = ico_xyz;  // level 1, no transformed mesh: project_CPgrid only unfolds the (regular) data grid
-        } else {
+        const Points *moved_in = trans_xyz;
+        if (!sph_reg_prev.empty()) {
             auto [prev_xyz, prev_tri] = make_mesh_from_icosa(prev_order);
             Mesh prev(ctx, prev_xyz, prev_tri);
             incurrent = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(in_xyz, prev, sph_reg_prev); });
-            sph_in = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(ico_xyz, in_mesh, incurrent); });
+            moved_in = &incurrent;
         }
-        if (!sph_reg_prev.empty() && !lv.rigid) {  // warp_CPgrid (a rigid level has no control grid)
-            auto [cp_xyz, cp_tri] = make_mesh_from_icosa(lv.cp_order);
-            Mesh cpm(ctx, PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(cp_xyz, in_mesh, incurrent); }), cp_tri);  // warp_CPgrid
-            PhaseClock::timed(clock, "unfold", [&] { return unfold(cpm); });
-            cp_start = cpm.get_coords();
-            have_cp_start = true;
-        }
-        {
-            Mesh moved(ctx, sph_in, ico_tri);
+        const bool have_cp_start = moved_in && !lv.rigid;  // (a rigid level has no control grid: no warp_CPgrid)
+        if (moved_in) {
+            sph_in = project_start(ctx, ico_xyz, ico_tri, in_mesh, *moved_in, lv.cp_order, have_cp_start ? &cp_start : nullptr, clock);
+        } else {  // level 1, no transformed mesh: project_CPgrid only unfolds the (regular) data grid
+            Mesh moved(ctx, ico_xyz, ico_tri);
             PhaseClock::timed(clock, "unfold", [&] { return unfold(moved); });
             sph_in = moved.get_coords();
         }

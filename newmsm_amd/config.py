@@ -11,7 +11,9 @@ they become doubles, as `Utilities::Option<float>` / `std::vector<float>` do the
 0.007499999832361937, --shearmod=0.4 as 0.4000000059604645.
 
 Reported instead of silently dropped unless asked for: AFFINE / RIGID levels (`--opt=AFFINE,...`: `levels_from_config` lists them in
-`skipped`; with rigid=True it returns them as rigid levels).  Out of scope: --IN / --INc (FSL's histogram matching is not in the reference tree), --excl.  --regoption=5 (aMSM)
+`skipped`; with rigid=True it returns them as rigid levels).  Out of scope: --IN / --INc (FSL's histogram matching is not in the reference tree).
+--excl / --cutthr are parsed into cfg["excl"] / cfg["cutthr"] and apply to the whole run: the caller hands them to run_multiresolution /
+run_group_multiresolution (`run_options(cfg)`), which refuse --excl together with both cost-function weightings.  --regoption=5 (aMSM)
 needs the anatomical surfaces, which come from the command line (--inanat / --refanat): `levels_from_config(cfg, D, anat=True)` says the caller has them.
 """
 import numpy as np
@@ -133,8 +135,6 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False):
     (opt-in: the executables run them when MSMHIP_RIGID=on).  Groupwise runs refuse them whatever this says (group_registration.py)."""
     if cfg["IN"] or cfg["INc"]:
         raise ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available")
-    if cfg["excl"]:
-        raise ConfigError("--excl (exclusion masks from the cut thresholds) is not wired into run_multiresolution")
     if groupwise:
         pass
     elif cfg["regoption"] == 4:  # M/mesh_registration.cpp:101-102
@@ -170,6 +170,12 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False):
                            simmeasure=cfg["simval"][i], rmode=rmode, rescale_labels=cfg["rescaleL"], optimiser=optimiser, cost_params=params,
                            anat_order=cfg["anatgrid"][i] if i < len(cfg["anatgrid"]) else cfg["CPgrid"][i] + 2))
     return levels, dict(varnorm=cfg["VN"]), skipped
+
+
+def run_options(cfg):
+    """What a configuration sets for the whole run besides levels_from_config's run_kw: --excl and --cutthr, as keyword arguments of
+    run_multiresolution / run_group_multiresolution (_exclude and _threshold, M/mesh_registration.cpp:705-706)"""
+    return dict(excl=bool(cfg["excl"]), cutthr=(cfg["cutthr"][0], cfg["cutthr"][1]))
 
 
 # The shipped configurations the BASELINE configs name, as text (the files themselves live in the reference tree, which is not available at run

@@ -15,7 +15,7 @@ result is not the reference's optimum."""
 import numpy as np
 
 from . import api
-from .registration import ProductOps, apply_labeling
+from .registration import ProductOps, apply_labeling, level_features, project_start
 
 
 class ProductGroupOps(ProductOps):
@@ -147,7 +147,7 @@ def run_group_level(ops, template_xyz, template_tri, data_xyz, data_tri, feats, 
 
 
 def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, levels, *, mask=None, varnorm=False, fixnan=False, timings=None,
-                              labelings_out=None, **level_kw):
+                              labelings_out=None, excl=False, cutthr=(0.0, 0.0001), **level_kw):
     """Group_Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50 over the overrides of M/group_mesh_registration.cpp) without
     file I/O:
 
@@ -160,8 +160,9 @@ def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, le
 
     meshes: per subject (xyz, tri), spheres of radius 100; datas: per subject D x V(mesh); template_*: the sphere the patches are compared on
     (--template); levels: dicts as config.levels_from_config builds them (data_order, cp_order, sg_order, sigma_in, iters, simmeasure,
-    cost_params["lambda_"]); mask: V(template) weights (--mask).  Returns (registered input spheres, per-level S x V x 3 registered data grids,
-    per-level energies)."""
+    cost_params["lambda_"]); mask: V(template) weights (--mask); excl, cutthr (--excl, --cutthr): every subject's exclusion mask from the cut
+    thresholds in the feature preparation of every level (registration.level_features) -- it does not enter the cost function.  Returns (registered input spheres,
+    per-level S x V x 3 registered data grids, per-level energies)."""
     import time
 
     clock = timings if timings is not None else {}
@@ -183,28 +184,19 @@ def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, le
         ico = ops.mesh(ico_xyz, ico_tri)
         feats = []
         for s in range(S):
-            f = timed("metric_resample", ops.metric_resample, in_mesh[s], datas[s], ico)
-            if lv.get("sigma_in", 0.0) > 0.0:
-                f = timed("smooth_data", ops.smooth_data, ico, f, lv["sigma_in"])
-            if varnorm:
-                f = ops.variance_normalise(f)
-            feats.append(f)
+            feats.append(level_features(ops, timed, in_mesh[s], datas[s], ico, lv.get("sigma_in", 0.0), varnorm, None, excl, cutthr)[0])
         cps_start = None
         if prev_regs is None:
             sph = [ico_xyz for _ in range(S)]  # ALL_SPH_REG.resize(num_subjects, SPH_orig), :60-61
         else:
             prev_xyz, prev_tri = ops.icosphere(prev_order)
             prev_ico = ops.mesh(prev_xyz, prev_tri)
-            cp_xyz, cp_tri = ops.icosphere(lv["cp_order"])
             sph, cps_start = [], []
             for s in range(S):
                 incurrent = timed("sphere_project_warp", ops.sphere_project_warp, in_xyz[s], prev_ico, prev_regs[s])
-                moved = ops.mesh(timed("sphere_project_warp", ops.sphere_project_warp, ico_xyz, in_mesh[s], incurrent), ico_tri)
-                cpm = ops.mesh(timed("sphere_project_warp", ops.sphere_project_warp, cp_xyz, in_mesh[s], incurrent), cp_tri)  # warp_CPgrid
-                timed("unfold", ops.unfold, cpm)
-                timed("unfold", ops.unfold, moved)
-                cps_start.append(ops.coords(cpm))
-                sph.append(ops.coords(moved))
+                moved, cp = project_start(ops, timed, ico_xyz, ico_tri, in_mesh[s], incurrent, lv["cp_order"])
+                cps_start.append(cp)
+                sph.append(moved)
         kw = dict(level_kw)
         kw.update({k: lv[k] for k in ("sg_order", "iters", "simmeasure") if k in lv})
         if "cost_params" in lv:

@@ -10,6 +10,7 @@ The loop itself is caller logic; everything it calls goes through an `ops` objec
 libmsmhip through the C ABI; the parity tests pass an oracle-backed object with the same methods, so that the two runs
 differ in nothing but the implementation of the path (tests/helpers.py, tests/test_gpu_registration.py).
 """
+import sys
 import time
 
 import numpy as np
@@ -17,6 +18,9 @@ import numpy as np
 from . import api
 
 RAD = 100.0  # M/reg_tools.h
+EXCL_WITH_WEIGHTINGS = ("--excl together with --inweight and --refweight is not available: downsample_cfweighting (M/mesh_registration.cpp:334-350) reads the "
+                        "level grid's exclusion mask at vertex numbers of the weightings' own meshes, which is out of bounds or meaningless unless the two "
+                        "meshes have the same size")
 
 
 class ProductOps:
@@ -52,9 +56,12 @@ class ProductOps:
         api.sphere_project_warp_mesh(mesh, from_mesh, to_xyz)
 
     # --- featurespace::initialise
-    def metric_resample(self, in_mesh, data, new_mesh, slot=None):
+    def metric_resample(self, in_mesh, data, new_mesh, slot=None, excl=None):
         """slot (optional): a name under which the result may live in a pinned buffer of the context that the NEXT call with the same name reuses
-        (the copy engine writes it directly: no staging memcpy of the D x V matrix); None: a fresh numpy array"""
+        (the copy engine writes it directly: no staging memcpy of the D x V matrix); None: a fresh numpy array.  excl (optional, V(in_mesh): the
+        --excl mask, 0 = excluded): returns (data, the resampled mask), both fresh arrays"""
+        if excl is not None:
+            return api.metric_resample(in_mesh, data, new_mesh, excl=excl)
         if slot is None:
             return api.metric_resample(in_mesh, data, new_mesh)
         out = self.ctx.scratch_host_array("metric_resample:" + slot, (np.atleast_2d(data).shape[0], new_mesh.V))
@@ -81,11 +88,15 @@ class ProductOps:
         if token is not None:
             self.ctx.release_host_array(token)
 
-    def smooth_data(self, mesh, data, sigma):
-        return api.smooth_data(mesh, data, mesh, sigma)
+    def smooth_data(self, mesh, data, sigma, excl=None):
+        """with excl (V(mesh)): returns (data, the smoothed mask)"""
+        return api.smooth_data(mesh, data, mesh, sigma, excl=excl)
 
-    def variance_normalise(self, data):
-        return api.variance_normalise(data)
+    def variance_normalise(self, data, excl=None):
+        return api.variance_normalise(data, excl=excl)
+
+    def create_exclusion(self, data, thrl, thru):
+        return api.create_exclusion(data, thrl, thru)
 
     def nearest_neighbour(self, mesh, data, q_xyz):
         return api.nearest_neighbour_interpolation(mesh, data, q_xyz)
@@ -248,6 +259,59 @@ def combine_costfunction_weighting(sourceweight, resampledtargetweight):
     return new
 
 
+def level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot=None, excl=False, cutthr=(0.0, 0.0001)):
+    """One data set of featurespace::initialise (M/featurespace.cpp:52-84) on a level's grid `ico`: metric_resample from its native mesh, smooth_data
+    when sigma > 0, variance_normalise when varnorm.  Returns (features D x V(ico), mask).  excl (--excl): the mask is create_exclusion of the native
+    data over the cut range cutthr (1 = kept, 0 = every feature inside the range: the medial wall of real data); resampling and smoothing leave it
+    out and each hands back the mask on the grid, which replaces it (R/resampler.cpp:54-67, 168-230); the variance statistics run over vertices
+    with mask > 0 and the others stay as they are (M/reg_tools.cpp:804-843).  Made afresh at every level from the native data, as the reference does.
+    Without excl the ops are called exactly as before the option existed (an ops object need not know of masks) and the mask is None."""
+    if not excl:
+        f = timed("metric_resample", ops.metric_resample, *((mesh, data, ico) if slot is None else (mesh, data, ico, slot)))
+        if sigma > 0.0:
+            f = timed("smooth_data", ops.smooth_data, ico, f, sigma)
+        return (ops.variance_normalise(f) if varnorm else f), None
+    mask = ops.create_exclusion(data, cutthr[0], cutthr[1])
+    f, mask = timed("metric_resample", lambda: ops.metric_resample(mesh, data, ico, excl=mask))
+    if sigma > 0.0:
+        f, mask = timed("smooth_data", lambda: ops.smooth_data(ico, f, sigma, excl=mask))
+    if varnorm:
+        f = ops.variance_normalise(f, excl=mask)
+    return f, mask
+
+
+def project_start(ops, timed, ico_xyz, ico_tri, in_mesh, moved_in, cp_order):
+    """project_CPgrid (M/mesh_registration.cpp:131-162) for a level that starts from a warp of the input sphere, in_mesh -> moved_in: the warp of
+    the previous level carried to the input sphere (`incurrent`) or, at the first level, the --trans sphere.  The level's data grid is carried
+    through it and unfolded; so is its control grid (warp_CPgrid, M/DiscreteModel.h:140-143) unless cp_order is None (a rigid level has no control
+    grid).  Returns (data grid, control grid or None)."""
+    moved = ops.mesh(timed("sphere_project_warp", ops.sphere_project_warp, ico_xyz, in_mesh, moved_in), ico_tri)
+    cp_start = None
+    if cp_order is not None:
+        cp_xyz, cp_tri = ops.icosphere(cp_order)
+        cpm = ops.mesh(timed("sphere_project_warp", ops.sphere_project_warp, cp_xyz, in_mesh, moved_in), cp_tri)  # warp_CPgrid
+        timed("unfold", ops.unfold, cpm)
+        cp_start = ops.coords(cpm)
+    timed("unfold", ops.unfold, moved)
+    return ops.coords(moved), cp_start
+
+
+def usable_transformed(trans_xyz, in_xyz):
+    """The --trans sphere as project_CPgrid looks at it at the first level (M/mesh_registration.cpp:136-145): None when it was not given or has the
+    input sphere's coordinates (Mesh operator==, R/mesh.cpp:1285-1290: every coordinate within EPSILON = 1e-8), with the reference's warning.  It
+    is taken as it is, not recentred and not rescaled (set_transformed); it must have the input sphere's vertex count, because sphere_project_warp
+    reads it at the input sphere's vertex numbers (the reference would read out of bounds)."""
+    if trans_xyz is None:
+        return None
+    trans_xyz = np.asarray(trans_xyz, dtype=np.float64)
+    if trans_xyz.ndim != 2 or trans_xyz.shape[1] != 3 or len(trans_xyz) != len(in_xyz):
+        raise ValueError("MeshREG ERROR:: the transformed mesh (--trans) has %d vertices, the input mesh has %d" % (len(trans_xyz), len(in_xyz)))
+    if np.all(np.abs(trans_xyz - in_xyz) < 1e-8):
+        print(" WARNING: transformed mesh has the same coordinates as the input mesh ", file=sys.stderr)
+        return None
+    return trans_xyz
+
+
 def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source_tri, src_feat, sph_reg, cp_order, *, sg_order=None,
                        iters=3, mciters=200, mcparam=0.8, seed=0, kind="univariate", simmeasure=2, rmode=3, labeldist=0.5,
                        rescale_labels=False, cost_params=None, timings=None, cp_start=None, in_weight=None, ref_weight=None,
@@ -391,7 +455,8 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
 
 
 def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data, levels, *, varnorm=False, timings=None, in_cfweight=None,
-                        ref_cfweight=None, labelings_out=None, in_anat=None, ref_anat=None, **level_kw):
+                        ref_cfweight=None, labelings_out=None, in_anat=None, ref_anat=None, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001),
+                        **level_kw):
     """Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE and RIGID levels without file I/O:
 
     per level  featurespace::initialise (M/featurespace.cpp:39-86: metric_resample of both data sets onto the level's
@@ -408,7 +473,18 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
     after level (the parity tests compare the optimiser's decisions of two runs).  in_anat / ref_anat (V x 3 on the vertices of the input /
     reference sphere; both or none, CLI/newmsm.cpp:40-45): the anatomical surfaces of a --regoption=5 (aMSM) run; a level's "anat_order" is its
     --anatgrid.  recentre() of the regular spheres
-    (a shift of ~1e-15) is not applied.  Returns (sphere_reg, per-level registered data grids, per-level energies)."""
+    (a shift of ~1e-15) is not applied.
+    trans_xyz (V(input) x 3, optional; --trans): the input sphere as an earlier registration left it (its sphere.reg), taken as it is.  Only the
+    first level looks at it (project_CPgrid, M/mesh_registration.cpp:136-145): its data grid and control grid start carried through input sphere ->
+    trans_xyz, which is what every later level does with the warp of the level before it, so the run continues the earlier one and sphere_reg is
+    the composition.  A first level that is RIGID has no control grid to carry (the reference would call warp_CPgrid on a model that does not exist
+    yet); its data grid is projected.  Coordinates equal to the input sphere's: the reference's warning, and the run goes on without it.
+    excl, cutthr (--excl, --cutthr): exclusion masks from the cut thresholds in every level's feature preparation (level_features).  They do not
+    enter the cost function: combine_weighting (M/mesh_registration.cpp:234-248) returns ones unless both weightings are given, and with both,
+    downsample_cfweighting (:334-350) would read the level-grid mask at vertex numbers of the weightings' own meshes -- refused.
+    Returns (sphere_reg, per-level registered data grids, per-level energies)."""
+    if excl and in_cfweight is not None and ref_cfweight is not None:
+        raise ValueError(EXCL_WITH_WEIGHTINGS)
     clock = timings if timings is not None else {}
 
     def timed(name, fn, *a):
@@ -418,6 +494,7 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
         return out
 
     in_xyz = np.asarray(in_xyz, dtype=np.float64)
+    trans_xyz = usable_transformed(trans_xyz, in_xyz)
     in_mesh, ref_mesh = ops.mesh(in_xyz, in_tri), ops.mesh(ref_xyz, ref_tri)
     sph_reg_prev, prev_order, regs, all_energies = None, None, [], []
     # the two data matrices go up once per level: in page-locked memory for the run, their uploads skip the staging blocks (ProductOps.pin; absent elsewhere)
@@ -432,14 +509,14 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
                 else:
                     ref_data = arr
         return _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data, levels, varnorm, in_cfweight, ref_cfweight, labelings_out, in_anat,
-                           ref_anat, ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies)
+                           ref_anat, ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz, excl, cutthr)
     finally:
         for t in pins:
             ops.unpin(t)
 
 
 def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data, levels, varnorm, in_cfweight, ref_cfweight, labelings_out, in_anat, ref_anat,
-                ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies):
+                ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001)):
     """the level loop of run_multiresolution (see there)"""
     for lv in levels:
         rigid = lv.get("method") == "RIGID"
@@ -449,27 +526,19 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
         for mesh, data, sigma, slot in ((in_mesh, in_data, lv.get("sigma_in", 0.0), "in"), (ref_mesh, ref_data, lv.get("sigma_ref", 0.0), "ref")):
             # (a level's matrices are consumed -- uploaded by the cost function and the target mesh -- before the next level asks for its own: the
             # result slots are reused from level to level)
-            f = timed("metric_resample", ops.metric_resample, mesh, data, ico, slot)
-            if sigma > 0.0:
-                f = timed("smooth_data", ops.smooth_data, ico, f, sigma)
-            if varnorm:
-                f = ops.variance_normalise(f)
-            feats.append(f)
-        cp_start = None
+            feats.append(level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot, excl, cutthr)[0])
+        # project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         if sph_reg_prev is None:
-            sph_in = ico_xyz  # level 1, no transformed mesh: project_CPgrid only unfolds the (regular) data grid
+            moved_in = trans_xyz
         else:
             prev_xyz, prev_tri = ops.icosphere(prev_order)
-            incurrent = timed("sphere_project_warp", ops.sphere_project_warp, in_xyz, ops.mesh(prev_xyz, prev_tri), sph_reg_prev)
-            sph_in = timed("sphere_project_warp", ops.sphere_project_warp, ico_xyz, in_mesh, incurrent)
-        if sph_reg_prev is not None and not rigid:  # a rigid level has no control grid (no warp_CPgrid)
-            cp_xyz, cp_tri = ops.icosphere(lv["cp_order"])
-            cpm = ops.mesh(timed("sphere_project_warp", ops.sphere_project_warp, cp_xyz, in_mesh, incurrent), cp_tri)  # warp_CPgrid
-            timed("unfold", ops.unfold, cpm)
-            cp_start = ops.coords(cpm)
-        moved = ops.mesh(sph_in, ico_tri)
-        timed("unfold", ops.unfold, moved)
-        sph_in = ops.coords(moved)
+            moved_in = timed("sphere_project_warp", ops.sphere_project_warp, in_xyz, ops.mesh(prev_xyz, prev_tri), sph_reg_prev)  # incurrent
+        if moved_in is None:  # level 1, no transformed mesh: project_CPgrid only unfolds the (regular) data grid
+            moved = ops.mesh(ico_xyz, ico_tri)
+            timed("unfold", ops.unfold, moved)
+            sph_in, cp_start = ops.coords(moved), None
+        else:  # (a rigid level has no control grid: no warp_CPgrid)
+            sph_in, cp_start = project_start(ops, timed, ico_xyz, ico_tri, in_mesh, moved_in, None if rigid else lv["cp_order"])
         if rigid:  # Rigid_cost_function on the level's featurespace: the grid rotated as a whole, no labelings
             sph_reg, trace = timed("rigid", ops.rigid_level, ico_xyz, ico_tri, feats[1], ico_xyz, ico_tri, feats[0], sph_in, lv["iters"], lv["simmeasure"],
                                    lv["stepsize"], lv["gradsampling"])

@@ -4,6 +4,7 @@
 //
 //   flags            src/msmOptions.h:59-157 (short and long forms, `--key=value` or `--key value`); -h / --help prints them
 //   pairwise         set_input / set_reference (load, recentre, true_rescale to RAD: M/mesh_registration.cpp:416-438), set_anatomical as loaded (:434-438),
+//                    -t / --trans: set_transformed, the sphere.reg of an earlier run as loaded (:440-443), the first level's starting point (:136-145),
 //                    the configuration through the reference's grammar (msmhip_config.hpp = parse_reg_options :459-784), run_multiresolutions
 //                    (msmhip_registration.hpp = :30-50), then <out>sphere.reg<surf>, <out>sphere.LR.reg<surf>, <out>transformed_and_reprojected<data>
 //                    (:47-49, :352-408, M/mesh_registration.h:170); with both anatomical meshes also <out>anat.reg.surf.gii (project_anatomical_mesh)
@@ -12,9 +13,14 @@
 //                    <out>sphere-<i>.LR.reg<surf>, <out>transformed_and_reprojected-<i><data> (M/group_mesh_registration.cpp:120-133, .h:79-82)
 //   -f               GIFTI (.surf.gii / .func.gii), ASCII (.asc / .dpv), ASCII_MAT (.asc / .txt) as set_output_format names them (:827-842)
 //
-// Outside the path and said so instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr unless MSMHIP_RIGID=on runs them), --trans, VTK output; the binary solve of
-// --dopt=HOCR / FastPD is a stand-in (iterated conditional modes: FastPD and ELC are licence-restricted and FSL-bound), so a run exercises the path exactly as
-// newmsm would but its labelings are not HOCR's.  tools/register_files.py is the same program in Python; tests/test_gpu_registration.py compares their files.
+// --excl / --cutthr of the configuration: exclusion masks in every level's feature preparation (msmhip_registration.hpp: level_features) and, pairwise, in the
+// final resampling of save_transformed_data (:371-383).
+//
+// Outside the path and said so instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr unless MSMHIP_RIGID=on runs them),
+// --IN / --INc, --excl together with both weightings, VTK output; --trans in groupwise mode is ignored with a note on stderr (CLI/newmsm.cpp:13-27 never
+// hands it to a groupwise run); the binary solve of --dopt=HOCR / FastPD is a stand-in (iterated conditional modes: FastPD and ELC are licence-restricted and
+// FSL-bound), so a run exercises the path exactly as newmsm would but its labelings are not HOCR's.  tools/register_files.py is the same program in Python;
+// tests/test_gpu_registration.py compares their files.
 //
 // Errors: a MeshregException's message on stderr, exit status 1 (CLI/newmsm.cpp:62-68).
 #include <cmath>
@@ -60,7 +66,7 @@ const Flag kFlags[] = {
     {"-A", "--refanat", "reference anatomical mesh (with both: <out>anat.reg.surf.gii and <out>STRAINS.func.gii are written too)", true},
     {"-i", "--indata", "scalar or multivariate data for input - can be ASCII (.asc,.dpv,.txt) or GIFTI (.func.gii or .shape.gii)", true},
     {"-I", "--refdata", "scalar or multivariate data for reference", true},
-    {"-t", "--trans", "Transformed source mesh (output of a previous registration): not supported here", true},
+    {"-t", "--trans", "Transformed source mesh (output of a previous registration, i.e. sphere.reg.gii): the starting point of the first level", true},
     {"-w", "--inweight", "cost function weighting for input", true},
     {"-W", "--refweight", "cost function weighting for reference", true},
     {"-o", "--out", "output basename", true},
@@ -173,7 +179,6 @@ void note_skipped(const std::vector<std::pair<int, std::string>> &skipped) {
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
     for (const char *flag : {"inmesh", "indata", "refdata"})
         if (o.get(flag).empty()) throw Error(MSM_ERR_INVALID, std::string("newmsm: --") + flag + " is required");
-    if (o.has("trans")) throw Error(MSM_ERR_INVALID, "newmsm: --trans (a previous registration as the starting point) is not wired into the level loop");
     if (o.get("inanat").empty() != o.get("refanat").empty()) throw Error(MSM_ERR_INVALID, "Error: must supply both anatomical meshes or none");  // CLI/newmsm.cpp:41-43
     auto [ixyz0, itri] = io::load_surface(o.get("inmesh"));
     auto [rxyz0, rtri] = io::load_surface(o.get("refmesh").empty() ? o.get("inmesh") : o.get("refmesh"));
@@ -186,7 +191,9 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     std::vector<std::pair<int, std::string>> skipped;
     const char *rigid_env = std::getenv("MSMHIP_RIGID");  // "on": AFFINE / RIGID levels run (Rigid_cost_function on the GPU) instead of being skipped
     const bool rigid = rigid_env && std::string(rigid_env) == "on";
-    const std::vector<LevelSpec> levels = levels_from_config(parse_config(slurp(o.get("conf")), o.get("conf").empty()), D, &varnorm, &skipped, anat, rigid);
+    const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
+    const std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid);
+    const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
     Points in_anat, ref_anat;
@@ -202,17 +209,23 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
         in_w = io::load_data(o.get("inweight"), &in_wr, (long)(ixyz.size() / 3));
         ref_w = io::load_data(o.get("refweight"), &ref_wr, (long)(rxyz.size() / 3));
     }
+    Points trans;
+    if (!o.get("trans").empty()) trans = io::load_surface(o.get("trans")).first;  // set_transformed: as loaded, no recentre, no rescale
     Context ctx(device);
     if (o.has("verbose"))
         std::cout << "This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,
-                                                    anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr);
+                                                    anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr,
+                                                    o.get("trans").empty() ? nullptr : &trans, excl);
     const std::string out = o.get("out");
     io::save_surface(out + "sphere.reg" + fmt.surf, res.sphere_reg, itri);  // transform
     const Triangles last_tri = make_mesh_from_icosa(levels.back().data_order).second;
     io::save_surface(out + "sphere.LR.reg" + fmt.surf, res.level_reg.back(), last_tri);  // saveSPH_reg
     Mesh moved(ctx, res.sphere_reg, itri), target(ctx, rxyz, rtri);
-    save_data(out + "transformed_and_reprojected" + fmt.data, rxyz, metric_resample(moved, idata, target), D);  // save_transformed_data
+    // save_transformed_data (:358-383): with --excl a fresh mask from the native input data keeps the cut out of the resampling
+    std::vector<double> in_excl;
+    if (excl.on) in_excl = create_exclusion(idata, moved.nvertices(), excl.lower, excl.upper);
+    save_data(out + "transformed_and_reprojected" + fmt.data, rxyz, metric_resample(moved, idata, target, excl.on ? &in_excl : nullptr), D);
     if (anat) {  // save_transformed_data's aMSM outputs (:397-407), GIFTI whatever -f says
         const Points anat_reg = project_anatomical_mesh(moved, target, ref_anat);
         io::save_surface(out + "anat.reg.surf.gii", anat_reg, itri);
@@ -235,6 +248,7 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     const std::vector<std::string> mesh_files = read_ascii_list(o.get("meshes")), data_files = read_ascii_list(o.get("data"));
     if (mesh_files.size() != data_files.size())
         throw Error(MSM_ERR_INVALID, "featurespace::Initialize do not have the same number of datasets and surface meshes");  // M/featurespace.cpp:43-44
+    if (o.has("trans")) std::cerr << "newmsm: --trans is not used in groupwise mode: ignored" << std::endl;
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
     bool varnorm = false;
     const std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm);  // refuses AFFINE / RIGID levels and optimisers other than HOCR
@@ -265,7 +279,8 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     Context ctx(device);
     if (o.has("verbose"))
         std::cout << "This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
-    const GroupMultiresResult res = run_group_multiresolutions(ctx, meshes, datas, D, txyz, ttri, levels, varnorm, mask.empty() ? nullptr : &mask);
+    const GroupMultiresResult res = run_group_multiresolutions(ctx, meshes, datas, D, txyz, ttri, levels, varnorm, mask.empty() ? nullptr : &mask, nullptr,
+                                                               exclusion_from_config(cfg));
     const Triangles last_tri = make_mesh_from_icosa(levels.back().data_order).second;
     Mesh target(ctx, txyz, ttri);
     const std::string out = o.get("out");

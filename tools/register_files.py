@@ -19,6 +19,12 @@ surfaces are loaded as they are (set_anatomical, M/mesh_registration.cpp:434-438
     <out>STRAINS.func.gii                     calculate_strains(2, in_anat, anat.reg): per vertex of the input anatomy the maximum and minimum principal
                                               stretch and 0.5 (lambda^2 - 1) of each (four rows)
 
+With -t / --trans=<sphere.reg of an earlier run> (set_transformed, :440-443: loaded as it is, no recentre, no rescale) the first level starts from that
+registration (project_CPgrid, :136-145) and sphere.reg is the composition: the two-stage workflow of the reference's guide (folding first, then
+myelin or multimodal features).  It needs the input mesh's vertex count; with the input mesh's coordinates the reference's warning is printed and
+the run goes on without it.  --excl (with --cutthr) in the configuration keeps the cut (every feature inside the thresholds: the zero-valued medial
+wall) out of every level's resampling, smoothing and variance normalisation and out of the final resampling of save_transformed_data (:371-383).
+
 Groupwise mode (CLI/newmsm.cpp:13-27, -g / --groupwise):
 
     python tools/register_files.py --groupwise --meshes=mesh_list.txt --data=data_list.txt --template=template.sphere.surf.gii [--mask=mask.func.gii] \
@@ -27,10 +33,11 @@ Groupwise mode (CLI/newmsm.cpp:13-27, -g / --groupwise):
 --meshes / --data: text files with one path per line (read_ascii_list, M/mesh_registration.cpp:871-884), subject i = line i of both; every mesh
 and the template recentred and rescaled to RAD (M/group_mesh_registration.h:46-57,72-77).  Outputs, per subject i (M/group_mesh_registration.cpp:
 120-133, .h:79-82): <out>sphere-<i>.reg<surf>, <out>sphere-<i>.LR.reg<surf>, <out>transformed_and_reprojected-<i><data> (the subject's data
-resampled from its registered sphere onto the TEMPLATE).
+resampled from its registered sphere onto the TEMPLATE: without a mask, M/group_mesh_registration.cpp:127-133).  --trans is ignored there with a note
+on stderr (CLI/newmsm.cpp never hands it to a groupwise run).
 
 Outside the path and reported instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr unless MSMHIP_RIGID=on, which runs
-them), --trans, --IN / --INc / --excl; the
+them), --IN / --INc, --excl together with both weightings; the
 binary solve of --dopt=HOCR / FastPD is a stand-in (iterated conditional modes: FastPD and ELC are licence-restricted and FSL-bound), so a run
 exercises the path exactly as newmsm would but its labelings are not HOCR's.
 """
@@ -80,7 +87,7 @@ def parse_args(argv):
     ap.add_argument("-I", "--refdata", default="", help="scalar or multivariate data for reference")
     ap.add_argument("-w", "--inweight", default="", help="cost function weighting for input")
     ap.add_argument("-W", "--refweight", default="", help="cost function weighting for reference")
-    ap.add_argument("-t", "--trans", default="", help="(not supported: initialisation from a previous registration)")
+    ap.add_argument("-t", "--trans", default="", help="transformed source mesh (output of a previous registration, i.e. sphere.reg.surf.gii): the first level starts from it")
     ap.add_argument("-a", "--inanat", default="", help="input anatomical mesh (the input sphere's vertices on the anatomical surface; --regoption=5)")
     ap.add_argument("-A", "--refanat", default="", help="reference anatomical mesh")
     ap.add_argument("-g", "--groupwise", action="store_true", help="run newMSM in groupwise mode")
@@ -131,6 +138,8 @@ def main_groupwise(a, surf_ext, data_ext):
     mesh_files, data_files = read_ascii_list(a.meshes), read_ascii_list(a.data)
     if len(mesh_files) != len(data_files):
         raise SystemExit("featurespace::Initialize do not have the same number of datasets and surface meshes")  # M/featurespace.cpp:43-44
+    if a.trans:
+        print("register_files.py: --trans is not used in groupwise mode: ignored", file=sys.stderr)
     cfg = config.parse_config(read_conf(a.conf))
     if any(m in ("RIGID", "AFFINE") for m in cfg["opt"]):
         raise SystemExit("AFFINE/RIGID registration is not supported in groupwise mode.")  # M/group_mesh_registration.cpp:29-30
@@ -153,7 +162,7 @@ def main_groupwise(a, surf_ext, data_ext):
     if a.verbose:
         print("This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
     regs, level_regs, energies = group_registration.run_group_multiresolution(group_registration.ProductGroupOps(ctx), meshes, datas, txyz, ttri, levels, mask=mask,
-                                                                              fixnan=cfg["fixnan"], **run_kw)
+                                                                              fixnan=cfg["fixnan"], **run_kw, **config.run_options(cfg))
     last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])[1]
     target = M.Mesh(ctx, txyz, ttri)
     for s in range(len(meshes)):
@@ -177,8 +186,6 @@ def main(argv):
     for flag in ("inmesh", "indata", "refdata"):
         if not getattr(a, flag):
             raise SystemExit("register_files.py: --%s is required" % flag)
-    if a.trans:
-        raise SystemExit("register_files.py: --trans (a previous registration as the starting point) is not wired into the level loop")
     if bool(a.inanat) != bool(a.refanat):
         raise SystemExit("Error: must supply both anatomical meshes or none")  # CLI/newmsm.cpp:41-43
     ixyz, itri = meshio.load_surface(a.inmesh)
@@ -187,8 +194,12 @@ def main(argv):
     idata, rdata = meshio.load_data(a.indata, len(ixyz)), meshio.load_data(a.refdata, len(rxyz))
     if idata.shape[0] != rdata.shape[0]:
         raise SystemExit("Mesh_registration: input and reference data have different numbers of feature rows (%d, %d)" % (idata.shape[0], rdata.shape[0]))
-    levels, run_kw = discrete_levels(config.parse_config(read_conf(a.conf)), idata.shape[0], anat=bool(a.inanat))
-    cfw = {}
+    cfg = config.parse_config(read_conf(a.conf))
+    levels, run_kw = discrete_levels(cfg, idata.shape[0], anat=bool(a.inanat))
+    excl = config.run_options(cfg)
+    cfw = dict(excl)
+    if a.trans:  # set_transformed: as loaded
+        cfw.update(trans_xyz=meshio.load_surface(a.trans)[0])
     if a.inanat:  # set_anatomical: loaded as they are (in_anat keeps its triangles: its normals serve the strain map)
         in_anat, in_anat_tri = meshio.load_surface(a.inanat)
         cfw.update(in_anat=in_anat, ref_anat=meshio.load_surface(a.refanat)[0])
@@ -203,7 +214,11 @@ def main(argv):
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])
     meshio.save_surface(out + "sphere.LR.reg" + surf_ext, level_regs[-1], last_tri)                 # saveSPH_reg
     moved, target = M.Mesh(ctx, reg, itri), M.Mesh(ctx, rxyz, rtri)
-    save_data(out + "transformed_and_reprojected" + data_ext, rxyz, M.metric_resample(moved, idata, target))  # save_transformed_data
+    if excl["excl"]:  # save_transformed_data (:371-383): a fresh mask from the native input data keeps the cut out of the resampling
+        resampled = M.metric_resample(moved, idata, target, excl=M.create_exclusion(idata, *excl["cutthr"]))[0]
+    else:
+        resampled = M.metric_resample(moved, idata, target)
+    save_data(out + "transformed_and_reprojected" + data_ext, rxyz, resampled)
     if a.inanat:  # save_transformed_data's aMSM outputs (:397-407), GIFTI whatever -f says
         anat_reg = M.project_anatomical_mesh(moved, target, cfw["ref_anat"])
         meshio.save_surface(out + "anat.reg.surf.gii", anat_reg, itri)
