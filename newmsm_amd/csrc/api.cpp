@@ -76,37 +76,21 @@ int check_status(msm_ctx *ctx, const char *what) {
 static int upload_tree(msm_mesh *m) {
     msm_ctx *ctx = m->ctx;
     MSM_HIP(hipSetDevice(ctx->device));
-    auto grow = [&](void **p, size_t &cap, size_t need, size_t elem) -> hipError_t {
-        if (need <= cap && *p) return hipSuccess;
-        if (*p) (void)msm::pool_free(*p);
-        *p = nullptr;
-        cap = need + need / 4 + 16;
-        return msm::pool_malloc(p, cap * elem);
-    };
-    MSM_HIP(grow((void **)&m->d_node, m->cap_node, m->tree.node.size(), sizeof(int4)));
-    MSM_HIP(grow((void **)&m->d_parent, m->cap_parent, m->tree.node.size(), sizeof(int32_t)));
-    MSM_HIP(grow((void **)&m->d_leaf_tri, m->cap_leaf, m->tree.leaf_tri.size(), sizeof(int32_t)));
-    MSM_HIP(grow((void **)&m->d_cone, m->cap_cone, m->tree.leaf_tri.size(), sizeof(float4)));
-    MSM_HIP(grow((void **)&m->d_rec, m->cap_rec, (size_t)m->T, sizeof(TriRec)));
-    MSM_HIP(grow((void **)&m->d_grid, m->cap_grid, m->tree.grid.size(), sizeof(int32_t)));
-    MSM_HIP(grow((void **)&m->d_nodebox, m->cap_box, m->tree.node.size(), sizeof(double4)));
-    struct Part {
-        void *dst;
-        const void *src;
-        size_t bytes;
-    };
-    const Part parts[] = {
-        {m->d_node, m->tree.node.data(), m->tree.node.size() * sizeof(int4)},
-        {m->d_parent, m->tree.parent.data(), m->tree.parent.size() * sizeof(int32_t)},
-        {m->d_leaf_tri, m->tree.leaf_tri.data(), m->tree.leaf_tri.size() * sizeof(int32_t)},
-        {m->d_grid, m->tree.grid.data(), m->tree.grid.size() * sizeof(int32_t)},
-        {m->d_nodebox, m->tree.nodebox.data(), m->tree.nodebox.size() * sizeof(double4)},
-    };
-    for (const Part &pt : parts) MSM_TRY(stage_h2d(ctx, pt.dst, pt.src, pt.bytes));  // pinned staging blocks (stager.cpp): a host memcpy each, then DMA at link speed
-    {
-        int st = launch_build_recs(ctx, m->d_xyz, m->V, m->d_tri, m->T, m->d_rec, m->d_tcone, m->d_leaf_tri, (int)m->tree.leaf_tri.size(), m->d_cone);
-        if (st) return st;
-    }
+    const FlatOctree &t = m->tree;
+    MSM_HIP(m->d_node.ensure(t.node.size()));
+    MSM_HIP(m->d_parent.ensure(t.node.size()));
+    MSM_HIP(m->d_leaf_tri.ensure(t.leaf_tri.size()));
+    MSM_HIP(m->d_cone.ensure(t.leaf_tri.size()));
+    MSM_HIP(m->d_rec.ensure((size_t)m->T));
+    MSM_HIP(m->d_grid.ensure(t.grid.size()));
+    MSM_HIP(m->d_nodebox.ensure(t.node.size()));
+    // pinned staging blocks (stager.cpp): a host memcpy each, then DMA at link speed
+    MSM_TRY(stage_h2d(ctx, m->d_node.p, t.node.data(), t.node.size() * sizeof(int4)));
+    MSM_TRY(stage_h2d(ctx, m->d_parent.p, t.parent.data(), t.parent.size() * sizeof(int32_t)));
+    MSM_TRY(stage_h2d(ctx, m->d_leaf_tri.p, t.leaf_tri.data(), t.leaf_tri.size() * sizeof(int32_t)));
+    MSM_TRY(stage_h2d(ctx, m->d_grid.p, t.grid.data(), t.grid.size() * sizeof(int32_t)));
+    MSM_TRY(stage_h2d(ctx, m->d_nodebox.p, t.nodebox.data(), t.nodebox.size() * sizeof(double4)));
+    MSM_TRY(launch_build_recs(ctx, m->d_xyz.p, m->V, m->d_tri.p, m->T, m->d_rec.p, m->d_tcone.p, m->d_leaf_tri.p, (int)t.leaf_tri.size(), m->d_cone.p));
     MSM_TRY(ctx_sync(ctx));
     return finish_tree(m);
 }
@@ -135,6 +119,15 @@ int upload_staged(msm_ctx *ctx, void *dst, const void *src, size_t bytes) {
         return MSM_OK;
     }
     return stage_h2d(ctx, dst, src, bytes);
+}
+
+int refresh_host_xyz(msm_mesh *m, msm_ctx *via) {
+    if (!m->host_xyz_stale) return MSM_OK;
+    // on a context's stream (created non-blocking: the null stream does not wait for the kernels that wrote the coordinates there)
+    MSM_TRY(stage_d2h(via, m->xyz.data(), m->d_xyz.p, sizeof(double) * 3 * (size_t)m->V));
+    MSM_TRY(ctx_sync(via));
+    m->host_xyz_stale = false;
+    return MSM_OK;
 }
 
 static int ensure_tree_overlapped(msm_mesh *m, const std::function<void()> *overlap);
@@ -174,29 +167,16 @@ static int ensure_tree_overlapped(msm_mesh *m, const std::function<void()> *over
         if (st == MSM_OK) return finish_tree(m);
         if (st != MSM_ERR_CAPACITY) return st;  // a tree that outgrew the preallocated arrays (a degenerate mesh): the host build below
     }
-    if (m->host_xyz_stale) {
-        // on the context's stream (created non-blocking: the null stream does not wait for the kernels that wrote the coordinates there)
-        MSM_TRY(stage_d2h(m->ctx, m->xyz.data(), m->d_xyz, sizeof(double) * 3 * (size_t)m->V));
-        MSM_TRY(ctx_sync(m->ctx));
-        m->host_xyz_stale = false;
-    }
+    MSM_TRY(refresh_host_xyz(m, m->ctx));
     build_octree(m->xyz.data(), m->tri.data(), m->V, m->T, m->tree);
     return upload_tree(m);
 }
 
 int ensure_masks(msm_mesh *m) {
-    int st = ensure_tree(m);
-    if (st) return st;
+    MSM_TRY(ensure_tree(m));
     if (m->masks_valid) return MSM_OK;
-    const size_t need = (size_t)std::max(m->tree.nmask_blocks, 1) * 64;
-    if (need > m->cap_mask || !m->d_mask) {
-        if (m->d_mask) (void)msm::pool_free(m->d_mask);
-        m->d_mask = nullptr;
-        m->cap_mask = need + need / 4;
-        MSM_HIP(msm::pool_malloc((void **)&m->d_mask, m->cap_mask * sizeof(unsigned long long)));
-    }
-    st = launch_build_masks(m->ctx, dev_tree(m), m->d_nodebox, m->d_mask);
-    if (st) return st;
+    MSM_HIP(m->d_mask.ensure((size_t)std::max(m->tree.nmask_blocks, 1) * 64));
+    MSM_TRY(launch_build_masks(m->ctx, dev_tree(m), m->d_nodebox.p, m->d_mask.p));
     m->masks_valid = true;
     return MSM_OK;
 }
@@ -238,13 +218,7 @@ struct RayCacheEntry {
     int V = 0, T = 0;
     std::vector<double> xyz;
     std::vector<int32_t> tri;
-    bool simple = false;
-    int ray_G = 0;
-    double ray_r2lo = 0, ray_r2hi = 0;
-    decltype(FlatOctree::ray_cell) ray_cell;
-    decltype(FlatOctree::ray_edge) ray_edge;
-    decltype(FlatOctree::ray_more) ray_more;
-    decltype(FlatOctree::ray_excl) ray_excl;
+    RayTable rays;
 };
 static std::mutex g_ray_cache_mu;
 static std::list<std::shared_ptr<const RayCacheEntry>> g_ray_cache;  // most recently used first
@@ -281,8 +255,7 @@ static void ray_cache_store(const msm_mesh *m, uint64_t h) {  // m->tree holds a
     auto e = std::make_shared<RayCacheEntry>();
     e->hash = h, e->V = m->V, e->T = m->T;
     e->xyz = m->xyz, e->tri = m->tri;
-    e->simple = m->tree.simple, e->ray_G = m->tree.ray_G, e->ray_r2lo = m->tree.ray_r2lo, e->ray_r2hi = m->tree.ray_r2hi;
-    e->ray_cell = m->tree.ray_cell, e->ray_edge = m->tree.ray_edge, e->ray_more = m->tree.ray_more, e->ray_excl = m->tree.ray_excl;
+    e->rays = m->tree.rays;
     std::lock_guard<std::mutex> lock(g_ray_cache_mu);
     g_ray_cache.push_front(std::move(e));
     while (g_ray_cache.size() > kRayCacheTables) g_ray_cache.pop_back();
@@ -297,43 +270,26 @@ static void retire_ray_job(msm_mesh *m) {
 }
 
 int ensure_rays(msm_mesh *m, bool wait) {
-    int st = ensure_masks(m);  // what the ray table cannot settle goes through the masked search
-    if (st) return st;
-    if (m->host_xyz_stale) {  // coordinates written on the device (group.cpp: the set-up's fallback mesh): the table is keyed by and built from the host copy
-        // on the context's stream (created non-blocking: the null stream does not wait for the kernels that wrote the coordinates there)
-        MSM_TRY(stage_d2h(m->ctx, m->xyz.data(), m->d_xyz, sizeof(double) * 3 * (size_t)m->V));
-        MSM_TRY(ctx_sync(m->ctx));
-        m->host_xyz_stale = false;
-    }
+    MSM_TRY(ensure_masks(m));  // what the ray table cannot settle goes through the masked search
+    MSM_TRY(refresh_host_xyz(m, m->ctx));  // coordinates written on the device (group.cpp: the set-up's fallback mesh): the table is keyed by and built from the host copy
     if (m->rays_valid) return ensure_rayrec(m);
     msm_ctx *ctx = m->ctx;
     if (m->ray_job && m->ray_job->gen != m->tree_gen) retire_ray_job(m);
     const char *mode = std::getenv("MSMHIP_RAYTABLE");
     if (mode && std::strcmp(mode, "off") == 0) return MSM_OK;
-    auto take_rays = [&](FlatOctree &b) {
-        m->tree.simple = b.simple;
-        m->tree.ray_G = b.ray_G;
-        m->tree.ray_r2lo = b.ray_r2lo;
-        m->tree.ray_r2hi = b.ray_r2hi;
-        m->tree.ray_cell = std::move(b.ray_cell);
-        m->tree.ray_edge = std::move(b.ray_edge);
-        m->tree.ray_more = std::move(b.ray_more);
-        m->tree.ray_excl = std::move(b.ray_excl);
-    };
     // (the switches that change what build_ray_table produces are read per call -- the tests flip them within a process: no cache then)
     const char *no_table = std::getenv("MSMHIP_DISABLE_RAYTABLE");
     const bool cache_ok = !(no_table && no_table[0] == '1');
     const uint64_t chash = cache_ok ? content_hash(m) : 0;
     std::shared_ptr<const RayCacheEntry> hit = (!m->ray_job && cache_ok) ? ray_cache_find(m, chash) : nullptr;
     if (hit) {  // a mesh with these coordinates and triangles has had its table built in this process
-        m->tree.simple = hit->simple, m->tree.ray_G = hit->ray_G, m->tree.ray_r2lo = hit->ray_r2lo, m->tree.ray_r2hi = hit->ray_r2hi;
-        m->tree.ray_cell = hit->ray_cell, m->tree.ray_edge = hit->ray_edge, m->tree.ray_more = hit->ray_more, m->tree.ray_excl = hit->ray_excl;
+        m->tree.rays = hit->rays;
     } else if (!m->ray_job && (wait || !ray_build_in_background())) {
         if (m->tree.node.empty()) {  // the tree was built on the GPU: the table's builder walks a host copy of the same tree
             FlatOctree host_tree;
             build_octree(m->xyz.data(), m->tri.data(), m->V, m->T, host_tree);
             build_ray_table(m->xyz.data(), m->tri.data(), m->V, m->T, host_tree);
-            take_rays(host_tree);
+            m->tree.rays = std::move(host_tree.rays);
         } else {
             build_ray_table(m->xyz.data(), m->tri.data(), m->V, m->T, m->tree);
         }
@@ -355,33 +311,20 @@ int ensure_rays(msm_mesh *m, bool wait) {
         }
         if (!wait && !m->ray_job->done.load(std::memory_order_acquire)) return MSM_OK;  // not yet: the complete search serves this call
         m->ray_job->th.join();
-        take_rays(m->ray_job->tree);
+        m->tree.rays = std::move(m->ray_job->tree.rays);
         m->ray_job.reset();
     }
     if (!hit && cache_ok) ray_cache_store(m, chash);
-    if (m->tree.ray_G > 0) {
-        auto grow = [&](void **p, size_t &cap, size_t need, size_t elem) -> hipError_t {
-            if (need <= cap && *p) return hipSuccess;
-            if (*p) (void)msm::pool_free(*p);
-            *p = nullptr;
-            cap = need + need / 4 + 16;
-            return msm::pool_malloc(p, cap * elem);
-        };
-        MSM_HIP(grow((void **)&m->d_ray_cell, m->cap_ray_cell, m->tree.ray_cell.size(), sizeof(int4)));
-        MSM_HIP(grow((void **)&m->d_ray_edge, m->cap_ray_edge, m->tree.ray_edge.size(), sizeof(float4)));
-        {
-            int st = upload_staged(ctx, m->d_ray_cell, m->tree.ray_cell.data(), m->tree.ray_cell.size() * sizeof(int4));
-            if (!st) st = upload_staged(ctx, m->d_ray_edge, m->tree.ray_edge.data(), m->tree.ray_edge.size() * sizeof(float4));
-            if (st) return st;
-        }
-        MSM_HIP(grow((void **)&m->d_ray_more, m->cap_ray_more, m->tree.ray_more.size() + 1, sizeof(int4)));
-        MSM_HIP(grow((void **)&m->d_ray_excl, m->cap_ray_excl, m->tree.ray_excl.size() + 1, sizeof(int4)));
-        {
-            int st = MSM_OK;
-            if (!m->tree.ray_more.empty()) st = upload_staged(ctx, m->d_ray_more, m->tree.ray_more.data(), m->tree.ray_more.size() * sizeof(int4));
-            if (!st && !m->tree.ray_excl.empty()) st = upload_staged(ctx, m->d_ray_excl, m->tree.ray_excl.data(), m->tree.ray_excl.size() * sizeof(int4));
-            if (st) return st;
-        }
+    const RayTable &r = m->tree.rays;
+    if (r.G > 0) {
+        MSM_HIP(m->d_ray_cell.ensure(r.cell.size()));
+        MSM_HIP(m->d_ray_edge.ensure(r.edge.size()));
+        MSM_TRY(upload_staged(ctx, m->d_ray_cell.p, r.cell.data(), r.cell.size() * sizeof(int4)));
+        MSM_TRY(upload_staged(ctx, m->d_ray_edge.p, r.edge.data(), r.edge.size() * sizeof(float4)));
+        MSM_HIP(m->d_ray_more.ensure(r.more.size() + 1));
+        MSM_HIP(m->d_ray_excl.ensure(r.excl.size() + 1));
+        MSM_TRY(upload_staged(ctx, m->d_ray_more.p, r.more.data(), r.more.size() * sizeof(int4)));  // (nothing queued for an empty list)
+        MSM_TRY(upload_staged(ctx, m->d_ray_excl.p, r.excl.data(), r.excl.size() * sizeof(int4)));
         MSM_TRY(ctx_sync(ctx));
         m->rayrec_valid = false;
     }
@@ -391,38 +334,32 @@ int ensure_rays(msm_mesh *m, bool wait) {
 
 // (re)fills the per-triangle records of the ray-table path after the tree or the features changed
 static int ensure_rayrec(msm_mesh *m) {
-    if (m->tree.ray_G <= 0 || m->rayrec_valid) return MSM_OK;
-    if ((size_t)m->T > m->cap_ray_rec || !m->d_ray_tri) {
-        if (m->d_ray_tri) (void)msm::pool_free(m->d_ray_tri);
-        m->d_ray_tri = nullptr;
-        m->cap_ray_rec = (size_t)m->T + m->T / 4 + 16;
-        MSM_HIP(msm::pool_malloc((void **)&m->d_ray_tri, m->cap_ray_rec * kRayPieces * sizeof(float4)));
-    }
-    int st = launch_build_raytri(m->ctx, m->d_rec, m->d_ray_edge, m->T, m->D >= 1 ? m->d_feat : nullptr, m->D, m->d_ray_tri);
-    if (st) return st;
+    if (m->tree.rays.G <= 0 || m->rayrec_valid) return MSM_OK;
+    MSM_HIP(m->d_ray_tri.ensure((size_t)m->T * kRayPieces));
+    MSM_TRY(launch_build_raytri(m->ctx, m->d_rec.p, m->d_ray_edge.p, m->T, m->D >= 1 ? m->d_feat.p : nullptr, m->D, m->d_ray_tri.p));
     m->rayrec_valid = true;
     return MSM_OK;
 }
 
 DevTree dev_tree(const msm_mesh *m) {
     DevTree t;
-    t.node = m->d_node;
-    t.parent = m->d_parent;
-    t.leaf_tri = m->d_leaf_tri;
-    t.cone = m->d_cone;
-    t.rec = m->d_rec;
-    t.grid = m->d_grid;
+    t.node = m->d_node.p;
+    t.parent = m->d_parent.p;
+    t.leaf_tri = m->d_leaf_tri.p;
+    t.cone = m->d_cone.p;
+    t.rec = m->d_rec.p;
+    t.grid = m->d_grid.p;
     t.grid_depth = m->tree.grid_depth;
-    t.mask = m->masks_valid ? m->d_mask : nullptr;
-    t.simple = m->tree.simple ? 1 : 0;
+    t.mask = m->masks_valid ? m->d_mask.p : nullptr;
+    t.simple = m->tree.rays.simple ? 1 : 0;
     t.nnodes = m->tree.nnodes();
-    t.ray_G = m->rays_valid ? m->tree.ray_G : 0;
-    t.ray_cell = m->d_ray_cell;
-    t.ray_tri = m->d_ray_tri;
-    t.ray_more = m->d_ray_more;
-    t.ray_excl = m->d_ray_excl;
-    t.ray_r2lo = m->tree.ray_r2lo;
-    t.ray_r2hi = m->tree.ray_r2hi;
+    t.ray_G = m->rays_valid ? m->tree.rays.G : 0;
+    t.ray_cell = m->d_ray_cell.p;
+    t.ray_tri = m->d_ray_tri.p;
+    t.ray_more = m->d_ray_more.p;
+    t.ray_excl = m->d_ray_excl.p;
+    t.ray_r2lo = m->tree.rays.r2lo;
+    t.ray_r2hi = m->tree.rays.r2hi;
     return t;
 }
 
@@ -436,18 +373,9 @@ const Adjacency &mesh_adjacency(msm_mesh *m) {
 
 // get_barycentric_weights on the device for host-resident query points
 static hipError_t ctx_scratch(msm_ctx *ctx, int slot, size_t bytes, void **out) {
-    if (bytes > ctx->q_cap[slot] || !ctx->q_buf[slot]) {
-        if (ctx->q_buf[slot]) (void)msm::pool_free(ctx->q_buf[slot]);
-        ctx->q_buf[slot] = nullptr;
-        ctx->q_cap[slot] = bytes + bytes / 4 + 256;
-        hipError_t e = msm::pool_malloc(&ctx->q_buf[slot], ctx->q_cap[slot]);
-        if (e != hipSuccess) {
-            ctx->q_cap[slot] = 0;
-            return e;
-        }
-    }
-    *out = ctx->q_buf[slot];
-    return hipSuccess;
+    const hipError_t e = ctx->q_buf[slot].ensure(bytes);
+    *out = ctx->q_buf[slot].p;
+    return e;
 }
 
 constexpr int kRayQueryMin = 4096;  // queries from which a target's direction table is used by the plain search entry points (kernels.hip: launch_query_rays)
@@ -564,10 +492,10 @@ int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, A
     // the query points are the other mesh's vertices, which its handle keeps in HBM (same context, same stream)
     const bool same_ctx = in_mesh->ctx == new_mesh->ctx;
     int st = query_host(in_mesh, new_mesh->xyz.data(), nNew, nullptr, q.fvid.data(), q.fw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (forward)",
-                        same_ctx ? new_mesh->d_xyz : nullptr);
+                        same_ctx ? new_mesh->d_xyz.p : nullptr);
     if (st) return st;
     st = query_host(new_mesh, in_mesh->xyz.data(), nOld, nullptr, q.rvid.data(), q.rw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (reverse)",
-                        same_ctx ? in_mesh->d_xyz : nullptr);
+                        same_ctx ? in_mesh->d_xyz.p : nullptr);
     if (st) return st;
     q.closest.clear();
     if (with_closest) {
@@ -587,18 +515,16 @@ int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, A
 }
 
 int ensure_adjacency_dev(msm_mesh *m) {
-    if (m->d_tid_ptr) return MSM_OK;
+    if (m->d_tid_ptr.p) return MSM_OK;
     msm_ctx *ctx = m->ctx;
     const Adjacency &adj = mesh_adjacency(m);
-    MSM_HIP(msm::pool_malloc((void **)&m->d_tid_ptr, sizeof(int32_t) * adj.tid_ptr.size()));
-    MSM_HIP(msm::pool_malloc((void **)&m->d_tid, sizeof(int32_t) * std::max<size_t>(adj.tid.size(), 1)));
-    MSM_HIP(msm::pool_malloc((void **)&m->d_fold, sizeof(int32_t) * (2 + (size_t)m->V)));
-    int st = upload_staged(ctx, m->d_tid_ptr, adj.tid_ptr.data(), sizeof(int32_t) * adj.tid_ptr.size());
-    if (st) return st;
-    if (!adj.tid.empty()) {
-        st = upload_staged(ctx, m->d_tid, adj.tid.data(), sizeof(int32_t) * adj.tid.size());
-        if (st) return st;
-    }
+    MSM_HIP(m->d_tid_ptr.ensure(adj.tid_ptr.size(), true));
+    MSM_HIP(m->d_tid.ensure(std::max<size_t>(adj.tid.size(), 1), true));
+    MSM_HIP(m->d_fold.ensure(2 + (size_t)m->V, true));
+    // (through the context's pinned staging block, like every upload of the library: the GPU never reads the caller's pageable pages, whose pinning by the
+    // runtime for an asynchronous copy outlives nothing the library controls)
+    MSM_TRY(upload_staged(ctx, m->d_tid_ptr.p, adj.tid_ptr.data(), sizeof(int32_t) * adj.tid_ptr.size()));
+    MSM_TRY(upload_staged(ctx, m->d_tid.p, adj.tid.data(), sizeof(int32_t) * adj.tid.size()));
     MSM_TRY(ctx_sync(ctx));
     return MSM_OK;
 }
@@ -618,7 +544,7 @@ int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out
     // Everything is queued on in_mesh's context.  new_mesh may belong to another context of the same GPU (the fallback mesh of the
     // gMSM set-up against the group's template) if its tree and adjacency are complete and synchronised: they are only read.
     const bool foreign = in_mesh->ctx != new_mesh->ctx;
-    if (foreign && (in_mesh->ctx->device != new_mesh->ctx->device || !new_mesh->tree_valid || !new_mesh->d_tid_ptr))
+    if (foreign && (in_mesh->ctx->device != new_mesh->ctx->device || !new_mesh->tree_valid || !new_mesh->d_tid_ptr.p))
         return fail(MSM_ERR_INVALID, "adaptive weights: the two meshes belong to different contexts");
     msm_ctx *ctx = in_mesh->ctx;
     const int nOld = in_mesh->V, nNew = new_mesh->V;
@@ -647,13 +573,13 @@ int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out
     MSM_HIP(s.scan_tmp.ensure((size_t)std::max(nNew, nOld) / 4096 + 2));
     MSM_HIP(s.tval.ensure(cap));
     // forward: the new mesh's vertices in the old mesh's tree; reverse: the old vertices in the new mesh's tree (:74-78)
-    st = launch_query(ctx, dev_tree(in_mesh), new_mesh->d_xyz, nNew, nullptr, s.fvid.p, s.fw.p, MSM_WEIGHTS_PROJECTED);
+    st = launch_query(ctx, dev_tree(in_mesh), new_mesh->d_xyz.p, nNew, nullptr, s.fvid.p, s.fw.p, MSM_WEIGHTS_PROJECTED);
     if (st) return st;
-    st = launch_query(ctx, dev_tree(new_mesh), in_mesh->d_xyz, nOld, nullptr, s.rvid.p, s.rw.p, MSM_WEIGHTS_PROJECTED);
+    st = launch_query(ctx, dev_tree(new_mesh), in_mesh->d_xyz.p, nOld, nullptr, s.rvid.p, s.rw.p, MSM_WEIGHTS_PROJECTED);
     if (st) return st;
-    st = launch_vertex_areas(ctx, in_mesh->d_xyz, nOld, in_mesh->d_tri, in_mesh->T, in_mesh->d_tid_ptr, in_mesh->d_tid, s.ta.p, s.oldA.p);
+    st = launch_vertex_areas(ctx, in_mesh->d_xyz.p, nOld, in_mesh->d_tri.p, in_mesh->T, in_mesh->d_tid_ptr.p, in_mesh->d_tid.p, s.ta.p, s.oldA.p);
     if (st) return st;
-    st = launch_vertex_areas(ctx, new_mesh->d_xyz, nNew, new_mesh->d_tri, new_mesh->T, new_mesh->d_tid_ptr, new_mesh->d_tid, s.ta.p, s.newA.p);
+    st = launch_vertex_areas(ctx, new_mesh->d_xyz.p, nNew, new_mesh->d_tri.p, new_mesh->T, new_mesh->d_tid_ptr.p, new_mesh->d_tid.p, s.ta.p, s.newA.p);
     if (st) return st;
     AdaptiveDevArgs a;
     a.nOld = nOld, a.nNew = nNew;
@@ -842,23 +768,18 @@ void msm_ctx_destroy(msm_ctx *ctx) {
     // is idle before any of them goes -- other streams of the family (a group's copy stream and lanes) may have been given their addresses
     (void)hipDeviceSynchronize();
     stager_destroy(ctx);
-    for (void *b : ctx->q_buf)
-        if (b) (void)msm::pool_free(b);
     if (ctx->io_pin) (void)hipHostFree(ctx->io_pin);
     if (ctx->h_flag) (void)hipHostFree(ctx->h_flag);
     if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
     if (ctx->q_ev0) (void)hipEventDestroy(ctx->q_ev0);
     if (ctx->q_ev1) (void)hipEventDestroy(ctx->q_ev1);
-    if (ctx->oct_box) (void)msm::pool_free(ctx->oct_box);
-    if (ctx->oct_ints) (void)msm::pool_free(ctx->oct_ints);
-    if (ctx->oct_counters) (void)msm::pool_free(ctx->oct_counters);
     if (ctx->oct_hcounters) (void)hipHostFree(ctx->oct_hcounters);
     for (auto &b : ctx->host_blocks) (void)(b.registered ? hipHostUnregister(b.host) : hipHostFree(b.host));
     if (ctx->d_status) (void)msm::pool_free(ctx->d_status);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-    if (g_live_contexts.fetch_sub(1) == 1) msm::pool_trim();
+    delete ctx;  // its device buffers (query scratch, the octree build's work area, the resampler's) go back to the pool here ...
+    if (g_live_contexts.fetch_sub(1) == 1) msm::pool_trim();  // ... so the pool is emptied after, not before
 }
 
 int msm_ctx_synchronize(msm_ctx *ctx) {
@@ -996,11 +917,11 @@ msm_mesh *msm_mesh_create(msm_ctx *ctx, const double *xyz, int32_t V, const int3
     (void)hipSetDevice(ctx->device);
     // uploads go through the context's pinned staging block: what the runtime does with an asynchronous copy from pageable memory depends on
     // whether it has seen the pages before (a megabyte took anything from 40 us to 25 ms, paid by whichever call synchronised next)
-    if (msm::pool_malloc((void **)&m->d_xyz, sizeof(double) * 3 * (size_t)V) != hipSuccess ||
-        upload_staged(ctx, m->d_xyz, m->xyz.data(), sizeof(double) * 3 * (size_t)V) != MSM_OK ||
-        msm::pool_malloc((void **)&m->d_tri, sizeof(int32_t) * 3 * (size_t)T) != hipSuccess ||
-        upload_staged(ctx, m->d_tri, m->tri.data(), sizeof(int32_t) * 3 * (size_t)T) != MSM_OK ||
-        msm::pool_malloc((void **)&m->d_tcone, sizeof(float4) * (size_t)T) != hipSuccess ||
+    if (m->d_xyz.ensure(3 * (size_t)V, true) != hipSuccess ||
+        upload_staged(ctx, m->d_xyz.p, m->xyz.data(), sizeof(double) * 3 * (size_t)V) != MSM_OK ||
+        m->d_tri.ensure(3 * (size_t)T, true) != hipSuccess ||
+        upload_staged(ctx, m->d_tri.p, m->tri.data(), sizeof(int32_t) * 3 * (size_t)T) != MSM_OK ||
+        m->d_tcone.ensure((size_t)T, true) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {  // the mesh is on the device when the call returns (other streams may use it: group.cpp)
         fail(MSM_ERR_HIP, "msm_mesh_create: device allocation failed");
         msm_mesh_destroy(m);
@@ -1013,9 +934,7 @@ void msm_mesh_destroy(msm_mesh *m) {
     if (!m) return;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    for (void *p : {(void *)m->d_xyz, (void *)m->d_tri, (void *)m->d_tcone, (void *)m->d_feat, (void *)m->d_node, (void *)m->d_parent, (void *)m->d_leaf_tri, (void *)m->d_cone, (void *)m->d_rec, (void *)m->d_grid, (void *)m->d_nodebox, (void *)m->d_mask, (void *)m->d_ray_cell, (void *)m->d_ray_edge, (void *)m->d_ray_tri, (void *)m->d_ray_more, (void *)m->d_ray_excl, (void *)m->d_tid_ptr, (void *)m->d_tid, (void *)m->d_fold})
-        if (p) (void)msm::pool_free(p);
-    delete m;
+    delete m;  // the device arrays go back to the pool with their DevBuf members
 }
 
 int msm_mesh_update_coords(msm_mesh *m, const double *xyz) {
@@ -1024,7 +943,7 @@ int msm_mesh_update_coords(msm_mesh *m, const double *xyz) {
     MSM_TRY(ctx_sync(m->ctx));  // the host copy may still be the source of an async upload
     m->xyz.assign(xyz, xyz + 3 * (size_t)m->V);
     m->tree_valid = false;
-    const int st = upload_staged(m->ctx, m->d_xyz, m->xyz.data(), sizeof(double) * 3 * (size_t)m->V);
+    const int st = upload_staged(m->ctx, m->d_xyz.p, m->xyz.data(), sizeof(double) * 3 * (size_t)m->V);
     if (st) return st;
     MSM_TRY(ctx_sync(m->ctx));  // as with the pageable copy this replaces: the coordinates have arrived when the call returns
     return MSM_OK;
@@ -1056,17 +975,11 @@ int msm_mesh_set_features(msm_mesh *m, const double *feat, int32_t D) {
     std::vector<double> vm((size_t)D * V);  // vertex-major rows so that a gather by vertex id reads D contiguous values
     for (int d = 0; d < D; ++d)
         for (int v = 0; v < V; ++v) vm[(size_t)v * D + d] = feat[(size_t)d * V + v];
-    if (m->d_feat && m->D != D) {
-        (void)msm::pool_free(m->d_feat);
-        m->d_feat = nullptr;
-    }
-    if (!m->d_feat) MSM_HIP(msm::pool_malloc((void **)&m->d_feat, sizeof(double) * (size_t)D * V));
+    if (m->D != D) m->d_feat.release();  // exactly D x V, whichever way D changes
+    MSM_HIP(m->d_feat.ensure((size_t)D * V, true));
     m->D = D;
     m->rayrec_valid = false;
-    {
-        const int st = upload_staged(m->ctx, m->d_feat, vm.data(), sizeof(double) * (size_t)D * V);  // pinned staging: pageable copies of megabytes crawl
-        if (st) return st;
-    }
+    MSM_TRY(upload_staged(m->ctx, m->d_feat.p, vm.data(), sizeof(double) * (size_t)D * V));  // pinned staging: pageable copies of megabytes crawl
     MSM_TRY(ctx_sync(m->ctx));
     return MSM_OK;
 }
@@ -1098,9 +1011,9 @@ int msm_mesh_octree_signature(msm_mesh *m, int64_t stats[5], uint64_t *signature
     std::vector<double4> box(n);
     std::vector<int32_t> leaf((size_t)std::max(ne, 1));
     msm_ctx *ctx = m->ctx;
-    MSM_TRY(stage_d2h(ctx, node.data(), m->d_node, sizeof(int4) * (size_t)n));
-    MSM_TRY(stage_d2h(ctx, box.data(), m->d_nodebox, sizeof(double4) * (size_t)n));
-    if (ne > 0) MSM_TRY(stage_d2h(ctx, leaf.data(), m->d_leaf_tri, sizeof(int32_t) * (size_t)ne));
+    MSM_TRY(stage_d2h(ctx, node.data(), m->d_node.p, sizeof(int4) * (size_t)n));
+    MSM_TRY(stage_d2h(ctx, box.data(), m->d_nodebox.p, sizeof(double4) * (size_t)n));
+    if (ne > 0) MSM_TRY(stage_d2h(ctx, leaf.data(), m->d_leaf_tri.p, sizeof(int32_t) * (size_t)ne));
     MSM_TRY(ctx_sync(ctx));
     uint64_t sum = 0;
     for (int i = 0; i < n; ++i) {
@@ -1334,7 +1247,7 @@ int msm_mesh_sphere_project_warp(msm_mesh *sphere, msm_mesh *from, const double 
     MSM_HIP(ctx_scratch(ctx, 1, bc, (void **)&dc));
     st = upload_staged(ctx, dc, to_xyz, bc);
     if (st) return st;
-    st = launch_warp(ctx, dev_tree(from), sphere->d_xyz, N, dc, V, true, sphere->d_xyz);
+    st = launch_warp(ctx, dev_tree(from), sphere->d_xyz.p, N, dc, V, true, sphere->d_xyz.p);
     if (st) return st;
     // the host copy follows (unfold's repair, get_coords and the set-up code read it)
     sphere->tree_valid = false;
@@ -1342,7 +1255,7 @@ int msm_mesh_sphere_project_warp(msm_mesh *sphere, msm_mesh *from, const double 
     void *pin = nullptr;  // through the pinned block: a copy into the pageable vector itself is staged by the runtime at a fraction of the speed
     st = ctx_io_pinned(ctx, bx, &pin);
     if (st) return st;
-    MSM_HIP(hipMemcpyAsync(pin, sphere->d_xyz, bx, hipMemcpyDeviceToHost, ctx->stream));
+    MSM_HIP(hipMemcpyAsync(pin, sphere->d_xyz.p, bx, hipMemcpyDeviceToHost, ctx->stream));
     st = check_status(ctx, "msm_mesh_sphere_project_warp");  // synchronises; on a failed search the unmoved points stay (the reference throws)
     std::memcpy(sphere->xyz.data(), pin, bx);
     sphere->host_xyz_stale = false;
@@ -1366,7 +1279,7 @@ int msm_smooth_data(msm_mesh *orig, const double *data, int32_t D, msm_mesh *sph
     DevBuf<double> dunit, ddata, dexcl, dout, dexo;
     DevBuf<int> dcv;
     MSM_HIP(dcv.ensure(N));
-    st = launch_closest_vertex(ctx, dev_tree(orig), sphlow->d_xyz, N, dcv.p);  // Octree(orig).get_closest_vertex_ID(ci), :182
+    st = launch_closest_vertex(ctx, dev_tree(orig), sphlow->d_xyz.p, N, dcv.p);  // Octree(orig).get_closest_vertex_ID(ci), :182
     if (st) return st;
     MSM_HIP(dunit.ensure(smooth_scratch_doubles(N)));
     MSM_HIP(ddata.ensure((size_t)D * orig->V));
@@ -1376,7 +1289,7 @@ int msm_smooth_data(msm_mesh *orig, const double *data, int32_t D, msm_mesh *sph
     MSM_HIP(dout.ensure((size_t)D * N));
     if (excl && excl_out) MSM_HIP(dexo.ensure(N));
     const double ang = 4 * asin(sigma / (2 * kRad));  // :175, with the host's libm like the reference
-    st = launch_smooth(ctx, sphlow->d_xyz, N, dunit.p, dcv.p, ddata.p, orig->V, D, sigma, cos(ang), excl ? dexcl.p : nullptr, dout.p,
+    st = launch_smooth(ctx, sphlow->d_xyz.p, N, dunit.p, dcv.p, ddata.p, orig->V, D, sigma, cos(ang), excl ? dexcl.p : nullptr, dout.p,
                        (excl && excl_out) ? dexo.p : nullptr);
     if (st) return st;
     MSM_TRY(dout.download(out, (size_t)D * N, ctx));

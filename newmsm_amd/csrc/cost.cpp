@@ -51,7 +51,7 @@ int ensure_label_rotations(msm_cost *c) {
     const int N = c->cpgrid->V;
     MSM_HIP(c->d_rnl.ensure((size_t)N * c->L * 9));
     MSM_HIP(c->d_moved.ensure((size_t)N * c->L * 3));
-    int st = launch_label_rotations(c->ctx, c->cpgrid->d_xyz, N, c->d_rot.p, c->d_labels.p, c->L, c->d_rnl.p, c->d_moved.p);
+    int st = launch_label_rotations(c->ctx, c->cpgrid->d_xyz.p, N, c->d_rot.p, c->d_labels.p, c->L, c->d_rnl.p, c->d_moved.p);
     if (st) return st;
     c->rotations_valid = true;
     return MSM_OK;
@@ -92,7 +92,7 @@ int patches_by_range(msm_cost *c) {
     c->pidx_asc_on_device = false;
     for (int attempt = 0; attempt < 3; ++attempt) {
         MSM_HIP(c->d_slots.ensure((size_t)N * cap));
-        int st = launch_range(ctx, c->cpgrid->d_xyz, N, c->source->d_xyz, Ns, c->d_maxsep.p, c->p.range, cap, c->d_slots.p, c->d_counts.p, c->d_chunkb.p,
+        int st = launch_range(ctx, c->cpgrid->d_xyz.p, N, c->source->d_xyz.p, Ns, c->d_maxsep.p, c->p.range, cap, c->d_slots.p, c->d_counts.p, c->d_chunkb.p,
                               c->d_counts.p + N);
         if (st) return st;
         MSM_TRY(c->d_counts.download(counts.data(), (size_t)N + 1, ctx));
@@ -153,7 +153,7 @@ int patches_by_triangle(msm_cost *c) {
     int st = mesh_tree_on_gpu(c->cpgrid) ? MSM_OK : ensure_tree_begin(c->source);
     if (st) return st;
     st = query_host(c->cpgrid, c->source->xyz.data(), Ns, tri.data(), nullptr, nullptr, MSM_WEIGHTS_RAW, "get_source_data (HO)",
-                    c->source->ctx == c->cpgrid->ctx ? c->source->d_xyz : nullptr);  // the source's vertices are in HBM already
+                    c->source->ctx == c->cpgrid->ctx ? c->source->d_xyz.p : nullptr);  // the source's vertices are in HBM already
     if (st) return st;
     // both trees on the GPU (a control grid of 2 048 triangles or more): the source's build is queued now and runs while the host bins
     if (mesh_tree_on_gpu(c->cpgrid)) {
@@ -203,7 +203,7 @@ int ensure_unary_table(msm_cost *c) {
     if (st) return st;
     st = need(c, c->L > 0, "labels");
     if (st) return st;
-    st = need(c, c->target->d_feat != nullptr && c->target->D == c->D, "target features matching the source features");
+    st = need(c, c->target->d_feat.p != nullptr && c->target->D == c->D, "target features matching the source features");
     if (st) return st;
     msm_ctx *ctx = c->ctx;
     const int N = c->cpgrid->V;
@@ -217,16 +217,16 @@ int ensure_unary_table(msm_cost *c) {
     if (st) return st;
     UnaryLaunch u;
     u.tree = dev_tree(c->target);
-    u.tfeat = c->target->d_feat;
+    u.tfeat = c->target->d_feat.p;
     u.D = c->D;
     u.N = N;
     u.L = c->L;
-    u.cp = c->cpgrid->d_xyz;
+    u.cp = c->cpgrid->d_xyz.p;
     st = ensure_label_rotations(c);
     if (st) return st;
     u.rnl = c->d_rnl.p;
     u.labels = c->d_labels.p;
-    u.src = c->source->d_xyz;
+    u.src = c->source->d_xyz.p;
     u.Nsrc = c->source->V;
     u.sfeat = c->d_sfeat.p;
     u.cfw = c->cfw.empty() ? nullptr : c->d_cfw.p;
@@ -509,7 +509,7 @@ int msm_cost_get_source_data(msm_cost *c) {
         if (!c->pidx_asc_on_device) MSM_TRY(c->d_pidx_asc.upload_vec(c->pidx, ctx));
         MSM_HIP(c->d_pidx.ensure(std::max<size_t>(c->pidx.size(), 1)));
         MSM_HIP(c->d_code.ensure(c->source->V));
-        st = launch_sort_patches(ctx, c->source->d_xyz, c->source->V, c->d_pptr.p, c->ngroups, c->d_pidx_asc.p, c->d_code.p, c->d_pidx.p);
+        st = launch_sort_patches(ctx, c->source->d_xyz.p, c->source->V, c->d_pptr.p, c->ngroups, c->d_pidx_asc.p, c->d_code.p, c->d_pidx.p);
         if (st) return st;
     }
     MSM_TRY(c->d_absw.upload(c->absw.data(), c->absw.size(), ctx));

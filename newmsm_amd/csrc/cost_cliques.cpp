@@ -71,7 +71,7 @@ int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a)
     a.P = (int)(c->pairs.size() / 2);
     a.triplets = c->d_triplets.p;
     a.pairs = c->d_pairs.p;
-    a.cp = g->d_xyz;
+    a.cp = g->d_xyz.p;
     a.ocp = c->d_ocp.p;
     a.orig = c->d_orig.p;
     a.Norig = (int)(c->orig_xyz.size() / 3);
@@ -88,9 +88,9 @@ int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a)
     a.rexp = c->p.rexp;
     a.mvdmax = c->mvdmax;
     a.percentile = c->p.percentile;
-    a.tfeat = c->target->d_feat;
+    a.tfeat = c->target->d_feat.p;
     a.D = c->D;
-    a.src = c->source->d_xyz;
+    a.src = c->source->d_xyz.p;
     a.Nsrc = c->source->V;
     a.sfeat = c->d_sfeat.p;
     a.cfw = c->cfw.empty() ? nullptr : c->d_cfw.p;
@@ -107,7 +107,7 @@ int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a)
     a.status = ctx->d_status;
     if (need_triplets && cost_is_ho(c)) {
         if (!c->have_source) return fail(MSM_ERR_STATE, "msm_cost: get_source_data() must be called first");
-        if (!c->target->d_feat || c->target->D != c->D) return fail(MSM_ERR_STATE, "msm_cost: target features must match the source features");
+        if (!c->target->d_feat.p || c->target->D != c->D) return fail(MSM_ERR_STATE, "msm_cost: target features must match the source features");
         // the triclique likelihood is evaluated by hundreds of fusion moves per level and its two kernel families sum in
         // different orders, so this path waits for the direction table instead of switching to it mid-run
         st = ensure_rays(c->target, true);  // includes the sub-cell masks the group search uses
@@ -118,7 +118,7 @@ int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a)
             a.sfeat_vm = c->d_sfeat_vm.p;
             a.cfw_vm = c->cfw.empty() ? nullptr : c->d_cfw_vm.p;
         }
-        if (c->target->tree.ray_G > 0 && c->pmax <= 1024 && a.T < (1 << 18)) {  // fusion moves: sample -> fix up -> reduce
+        if (c->target->tree.rays.G > 0 && c->pmax <= 1024 && a.T < (1 << 18)) {  // fusion moves: sample -> fix up -> reduce
             const size_t nv = 8 * c->pidx.size();
             MSM_HIP(c->d_ho_vals.ensure(std::max<size_t>(nv, 1)));
             MSM_HIP(c->d_ho_pending.ensure(std::max<size_t>(nv, 1)));

@@ -43,10 +43,12 @@ struct DevBuf {
         cap = n;
         owned = false;
     }
-    hipError_t ensure(size_t n) {
+    // room for n elements; a buffer that has to grow gets a quarter more than asked for.  exact: none of that -- for arrays whose size is fixed
+    // by their owner (a mesh's coordinates, what a tree build sizes from the triangle count)
+    hipError_t ensure(size_t n, bool exact = false) {
         if (n <= cap && p) return hipSuccess;
         release();
-        cap = n + n / 4 + 16;
+        cap = exact ? n : n + n / 4 + 16;
         hipError_t e = msm::pool_malloc((void **)&p, cap * sizeof(T));
         if (e != hipSuccess) {
             p = nullptr;

@@ -218,7 +218,7 @@ int subject_patches(msm_group *g, int s, msm_ctx *ctx, msm_group::Pipe *pipe, co
     bool early = false;
     for (int attempt = 0; attempt < 3; ++attempt) {
         MSM_HIP(d_slots.ensure((size_t)M * cap));
-        int st = launch_range(ctx, d_c.p, M, g->tmpl->d_xyz, Vt, d_sep.p, g->p.range, cap, d_slots.p, d_counts.p, pipe->d_chunkb.p, d_counts.p + M, L,
+        int st = launch_range(ctx, d_c.p, M, g->tmpl->d_xyz.p, Vt, d_sep.p, g->p.range, cap, d_slots.p, d_counts.p, pipe->d_chunkb.p, d_counts.p + M, L,
                               g->rgrid_valid ? &g->rgrid : nullptr);
         if (st) return st;
         early = attempt == 0 && list_hint > 0;
@@ -635,7 +635,7 @@ int group_common_setup(msm_group *g) {
     MSM_HIP(g->d_pairs.ensure(std::max<size_t>(2 * (size_t)g->npairs, 1)));
     bool pairs_done = false;
     if (S >= 2) {
-        int st = gpu_build_forest(ctx, g->cp_forest, g->d_cp_soa.p, (size_t)S * N, (size_t)N, N, g->cpmesh[0]->d_tri, g->Tc, S);
+        int st = gpu_build_forest(ctx, g->cp_forest, g->d_cp_soa.p, (size_t)S * N, (size_t)N, N, g->cpmesh[0]->d_tri.p, g->Tc, S);
         if (st == MSM_OK) {
             std::vector<int2> info(S);
             for (int b = 0; b < S; ++b) info[b] = make_int2(g->cp_forest.info[b].nnodes, g->cp_forest.info[b].grid_depth);
@@ -794,11 +794,7 @@ static int rotate_subject(msm_group *g, msm_mesh *dm, msm_ctx *ctx, std::vector<
     const double centre[3] = {g->labels[0], g->labels[L], g->labels[2 * (size_t)L]};
     const double *d_mats = nullptr;
     if (g->rotation_mode == 1) {
-        if (dm->host_xyz_stale) {
-            MSM_TRY(stage_d2h(ctx, dm->xyz.data(), dm->d_xyz, sizeof(double) * 3 * (size_t)V));
-            MSM_TRY(ctx_sync(ctx));
-            dm->host_xyz_stale = false;
-        }
+        MSM_TRY(refresh_host_xyz(dm, ctx));  // (through the pipeline's context, not the mesh's)
         rot9.resize(9 * (size_t)V);
         std::atomic<int> bad{0};
         const double *xyz = dm->xyz.data();
@@ -812,7 +808,7 @@ static int rotate_subject(msm_group *g, msm_mesh *dm, msm_ctx *ctx, std::vector<
         if (st) return st;
         d_mats = d_rot9.p;
     }
-    return launch_rotate_to_labels(ctx, dm->d_xyz, V, centre, g->d_labels3.p, L, d_mats, d_out, (size_t)L * V);
+    return launch_rotate_to_labels(ctx, dm->d_xyz.p, V, centre, g->d_labels3.p, L, d_mats, d_out, (size_t)L * V);
 }
 
 static int stage_prepare(msm_group *g, int s, msm_group::Stage &b, msm_ctx *ctx) {
@@ -843,7 +839,7 @@ static int stage_prepare(msm_group *g, int s, msm_group::Stage &b, msm_ctx *ctx)
     lap("slab");
     // the L trees, built together (one chain of launches per subject instead of one per label); a tree that outgrows its arrays
     // (a degenerate mesh) sends the subject down the per-label builds of stage_fallback
-    st = gpu_build_forest(ctx, b.forest, b.d_rot.p, LV, (size_t)V, V, dm->d_tri, T, L);
+    st = gpu_build_forest(ctx, b.forest, b.d_rot.p, LV, (size_t)V, V, dm->d_tri.p, T, L);
     b.forest_ok = st != MSM_ERR_CAPACITY;
     if (st && b.forest_ok) return st;
     lap("forest");
@@ -901,14 +897,14 @@ static int stage_batch(msm_group *g, int s, msm_group::Stage &b, int which, msm_
     fd.s_node = b.forest.s_node, fd.s_leaf = b.forest.s_leaf, fd.s_rec = b.forest.s_rec, fd.s_grid = b.forest.s_grid;
     fd.info = w.info[which].p;
     // forward: the template's vertices in every label's tree; reverse: every label's vertices in the template's tree (:74-78)
-    st = launch_query_forest(ctx, fd, L, tm->d_xyz, Vt, w.fvid.p, w.fw.p, LVt);
+    st = launch_query_forest(ctx, fd, L, tm->d_xyz.p, Vt, w.fvid.p, w.fw.p, LVt);
     if (st) return st;
     MSM_HIP(w.open.ensure(LV + 1));
     st = launch_query_rays(ctx, dev_tree(tm), b.d_rot.p, (int)LV, nullptr, w.rvid.p, w.rw.p, MSM_WEIGHTS_PROJECTED, w.open.p);  // (the template's direction table: group_setup_pipeline)
     if (st) return st;
-    st = launch_vertex_areas_batch(ctx, b.d_rot.p, LV, (size_t)V, V, dm->d_tri, T, dm->d_tid_ptr, dm->d_tid, L, w.ta.p, w.oldA.p);
+    st = launch_vertex_areas_batch(ctx, b.d_rot.p, LV, (size_t)V, V, dm->d_tri.p, T, dm->d_tid_ptr.p, dm->d_tid.p, L, w.ta.p, w.oldA.p);
     if (st) return st;
-    st = launch_vertex_areas_batch(ctx, tm->d_xyz, (size_t)Vt, 0, Vt, tm->d_tri, Tt, tm->d_tid_ptr, tm->d_tid, 1, w.ta.p, w.newA.p);
+    st = launch_vertex_areas_batch(ctx, tm->d_xyz.p, (size_t)Vt, 0, Vt, tm->d_tri.p, Tt, tm->d_tid_ptr.p, tm->d_tid.p, 1, w.ta.p, w.newA.p);
     if (st) return st;
     AdaptiveDevArgs a;
     a.nOld = V, a.nNew = Vt;
@@ -951,7 +947,7 @@ static int stage_fallback(msm_group *g, int s, msm_group::Stage &b, msm_group::P
     }
     for (int l = 0; l < L; ++l) {
         for (int a = 0; a < 3; ++a)
-            MSM_HIP(hipMemcpyAsync(m->d_xyz + (size_t)a * V, b.d_rot.p + a * LV + (size_t)l * V, sizeof(double) * (size_t)V, hipMemcpyDeviceToDevice, ctx->stream));
+            MSM_HIP(hipMemcpyAsync(m->d_xyz.p + (size_t)a * V, b.d_rot.p + a * LV + (size_t)l * V, sizeof(double) * (size_t)V, hipMemcpyDeviceToDevice, ctx->stream));
         m->tree_valid = false;
         m->host_xyz_stale = true;
         AdaptiveDev w;
@@ -1052,7 +1048,7 @@ static int group_setup_pipeline(msm_group *g, const int32_t *subjects, int n) {
         MSM_HIP(g->d_rg_bad.ensure(1));
         MSM_HIP(g->d_rg_tmp.ensure(cells / 4096 + 2));
         const double origin = -1.01 * kRad, inv_h = (double)G / (2.02 * kRad);
-        st = launch_range_grid_build(ctx, g->tmpl->d_xyz, g->tmpl->V, G, origin, inv_h, g->d_rg_start.p, g->d_rg_cursor.p, g->d_rg_ids.p, g->d_rg_bad.p, g->d_rg_tmp.p);
+        st = launch_range_grid_build(ctx, g->tmpl->d_xyz.p, g->tmpl->V, G, origin, inv_h, g->d_rg_start.p, g->d_rg_cursor.p, g->d_rg_ids.p, g->d_rg_bad.p, g->d_rg_tmp.p);
         if (st) return st;
         g->rgrid.start = g->d_rg_start.p, g->rgrid.ids = g->d_rg_ids.p, g->rgrid.bad = g->d_rg_bad.p, g->rgrid.G = G, g->rgrid.origin = origin, g->rgrid.inv_h = inv_h;
         g->rgrid_valid = true;

@@ -21,9 +21,7 @@ namespace msm {
 // ---------------------------------------------------------------- errors
 void set_error(const char *fmt, ...);
 int fail(int code, const char *fmt, ...);
-// pool.cpp: device memory of the handles (size-classed free lists over hipMalloc / hipFree)
-hipError_t pool_malloc(void **p, size_t bytes);
-hipError_t pool_free(void *p);
+// pool.cpp: device memory of the handles (size-classed free lists over hipMalloc / hipFree; taken and given back through DevBuf, devbuf.hpp)
 void pool_trim();
 size_t pool_idle_bytes();
 
@@ -66,6 +64,19 @@ static_assert(sizeof(TriRec) == 128, "TriRec must be 128 bytes");
 // (kernels.hip: k_build_raytri).
 constexpr int kRayPieces = 9;
 
+// Direction (ray) table of a simple surface (octree.cpp: build_ray_table), the host side; G == 0 when absent.
+struct RayTable {
+    // closed, consistently oriented, star-shaped about the origin, covering the sphere exactly once: every ray from
+    // the origin meets exactly one triangle (true for the icosphere targets; false for folded meshes)
+    bool simple = false;
+    int G = 0;                   // cube-map cells per face axis
+    std::vector<int4> cell;      // 6 x G x G: up to four candidate triangles per direction cell, -1 padded
+    std::vector<float4> edge;    // 3 per triangle: inward unit normal of the plane (origin, edge k); .w: see octree.cpp
+    std::vector<int4> more;      // candidates 4..7 of the cells that have more than four
+    std::vector<int4> excl;      // up to seven leaf boxes a query must not lie in for its triangle to be vouched for: {b0, b1, b2, count} and, for count > 3, {b3 .. b6} in the next record
+    double r2lo = 0, r2hi = 0;   // squared radius range of the query points the table is valid for
+};
+
 struct FlatOctree {
     // node[n].x >= 0: internal node, children are node[n].x .. +7 in (i,j,k) order.
     // node[n].x <  0: leaf with (-x - 1) entries starting at node[n].y (a multiple of 8) in leaf_tri / cone;
@@ -82,16 +93,7 @@ struct FlatOctree {
     // halvings, so the cell of a point is found arithmetically and the descent starts there.
     std::vector<int32_t> grid;
     int grid_depth = 0;
-    // closed, consistently oriented, star-shaped about the origin, covering the sphere exactly once: every ray from
-    // the origin meets exactly one triangle (true for the icosphere targets; false for folded meshes)
-    bool simple = false;
-    // Ray table of a simple surface (octree.cpp: build_ray_table); ray_G == 0 when absent.
-    int ray_G = 0;                   // cube-map cells per face axis
-    std::vector<int4> ray_cell;      // 6 x G x G: up to four candidate triangles per direction cell, -1 padded
-    std::vector<float4> ray_edge;    // 3 per triangle: inward unit normal of the plane (origin, edge k); .w: see octree.cpp
-    std::vector<int4> ray_more;      // candidates 4..7 of the cells that have more than four
-    std::vector<int4> ray_excl;      // up to seven leaf boxes a query must not lie in for its triangle to be vouched for: {b0, b1, b2, count} and, for count > 3, {b3 .. b6} in the next record
-    double ray_r2lo = 0, ray_r2hi = 0;  // squared radius range of the query points the table is valid for
+    RayTable rays;  // see there; filled by build_ray_table
     int64_t stats[5] = {0, 0, 0, 0, 0};
     // a tree built on the GPU (octree_kernels.hip) has no host arrays: `node` etc. stay empty and these describe it
     int dev_nnodes = 0, dev_entries = 0;
@@ -100,7 +102,7 @@ struct FlatOctree {
 };
 // builds the tree exactly as Octree::initialize_tree / add_triangle do (R/octree.cpp:42-141)
 void build_octree(const double *xyz /*3 x V SoA*/, const int32_t *tri /*3 x T SoA*/, int V, int T, FlatOctree &out);
-// decides FlatOctree::simple and, for a simple surface, fills the ray table of an already built tree
+// decides RayTable::simple and, for a simple surface, fills the ray table (tree.rays) of an already built tree
 void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOctree &tree);
 
 // device view of a mesh's search structure
@@ -112,10 +114,10 @@ struct DevTree {
     const TriRec *rec;
     const int32_t *grid;
     int grid_depth;  // G = 1 << grid_depth cells per axis
-    int simple;  // see FlatOctree::simple
+    int simple;  // see RayTable::simple
     const unsigned long long *mask;  // 64 per mask block (see FlatOctree::node), or nullptr before the masks are built
     int nnodes;
-    // ray table (FlatOctree::ray_*); ray_G == 0: none
+    // ray table (RayTable); ray_G == 0: none
     int ray_G;
     const int4 *ray_cell;
     const float4 *ray_tri;   // kRayPieces float4 per triangle
@@ -138,8 +140,7 @@ struct msm_ctx {
     int *d_status = nullptr;  // first error code raised by a kernel (atomicMin), 0 when clean
     int *h_status = nullptr;  // pinned
     // grow-only scratch of the host-array query entry points (hipMalloc / hipFree per call cost more than the queries)
-    void *q_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // queries, triangle ids, vertex ids, weights, the list of queries the direction table left open
-    size_t q_cap[5] = {0, 0, 0, 0, 0};
+    msm::DevBuf<char> q_buf[5];  // queries, triangle ids, vertex ids, weights, the list of queries the direction table left open
     // pinned staging blocks of every host <-> device copy whose host side is not pinned memory of this library (stager.cpp): grow only, event fenced,
     // never moved; created and destroyed with the context
     msm::Stager *stager = nullptr;
@@ -163,9 +164,9 @@ struct msm_ctx {
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
     bool q_timing = false, q_timed = false;
     // scratch of the GPU octree build (octree_kernels.hip), grow only
-    double *oct_box = nullptr;
-    int *oct_ints = nullptr, *oct_counters = nullptr, *oct_hcounters = nullptr;
-    size_t oct_cap_box = 0, oct_cap_ints = 0;
+    msm::DevBuf<double> oct_box;
+    msm::DevBuf<int> oct_ints, oct_counters;
+    int *oct_hcounters = nullptr;  // pinned
     // msm_host_alloc blocks: pinned host memory the GPU writes results into directly
     struct HostBlock {
         char *host;
@@ -191,35 +192,32 @@ struct msm_mesh {
     bool host_xyz_stale = false;    // the coordinates were last written on the device only (group.cpp): fetched before any host-side use
     std::shared_ptr<void> oct_job;  // a GPU build that has been queued but not looked at yet (octree_kernels.hip)
     msm::FlatOctree tree;
-    // device
-    double *d_xyz = nullptr;   // 3 x V SoA
-    int32_t *d_tri = nullptr;  // 3 x T SoA
-    float4 *d_tcone = nullptr; // per-triangle bounding cone (scratch of the record kernel)
-    double *d_feat = nullptr;  // V x D (vertex-major: one row per vertex for gathers)
-    int4 *d_node = nullptr;
-    double4 *d_nodebox = nullptr;
-    unsigned long long *d_mask = nullptr;
     bool masks_valid = false;
     bool rays_valid = false;
-    int32_t *d_parent = nullptr;
-    int32_t *d_leaf_tri = nullptr;
-    float4 *d_cone = nullptr;
-    msm::TriRec *d_rec = nullptr;
-    int32_t *d_grid = nullptr;
-    int4 *d_ray_cell = nullptr;
-    float4 *d_ray_edge = nullptr;
-    float4 *d_ray_tri = nullptr;
-    int4 *d_ray_more = nullptr, *d_ray_excl = nullptr;
-    size_t cap_ray_more = 0, cap_ray_excl = 0;
     bool rayrec_valid = false;  // d_ray_tri matches the current coordinates and features
-    size_t cap_ray_cell = 0, cap_ray_edge = 0, cap_ray_rec = 0;
-    size_t cap_node = 0, cap_parent = 0, cap_box = 0, cap_leaf = 0, cap_cone = 0, cap_rec = 0, cap_grid = 0, cap_mask = 0;  // one per buffer
     msm::Adjacency adj;
     bool adj_valid = false;
-    int32_t *d_tid_ptr = nullptr, *d_tid = nullptr;  // Mpoint::trID lists as CSR (unfold's fold test)
-    int32_t *d_fold = nullptr;                       // [0] folded count, [1] vertices without a triangle, then V flags
+    // device: every array is owned here and goes back to the pool with the mesh
+    msm::DevBuf<double> d_xyz;    // 3 x V SoA
+    msm::DevBuf<int32_t> d_tri;   // 3 x T SoA
+    msm::DevBuf<float4> d_tcone;  // per-triangle bounding cone (scratch of the record kernel)
+    msm::DevBuf<double> d_feat;   // V x D (vertex-major: one row per vertex for gathers)
+    msm::DevBuf<int4> d_node;
+    msm::DevBuf<double4> d_nodebox;
+    msm::DevBuf<unsigned long long> d_mask;
+    msm::DevBuf<int32_t> d_parent, d_leaf_tri;
+    msm::DevBuf<float4> d_cone;
+    msm::DevBuf<msm::TriRec> d_rec;
+    msm::DevBuf<int32_t> d_grid;
+    msm::DevBuf<int4> d_ray_cell;
+    msm::DevBuf<float4> d_ray_edge;
+    msm::DevBuf<float4> d_ray_tri;  // kRayPieces per triangle
+    msm::DevBuf<int4> d_ray_more, d_ray_excl;
+    msm::DevBuf<int32_t> d_tid_ptr, d_tid;  // Mpoint::trID lists as CSR (unfold's fold test)
+    msm::DevBuf<int32_t> d_fold;            // [0] folded count, [1] vertices without a triangle, then V flags
     // background build of the ray table (api.cpp: ensure_rays): the job of the current tree, and finished-with jobs of
-    // earlier trees that are joined when the mesh goes
+    // earlier trees that are joined when the mesh goes.  Declared after `tri`, which the job's thread reads: members are
+    // destroyed in reverse order, so the jobs are joined before the triangles go.
     uint64_t tree_gen = 0;
     std::shared_ptr<msm::RayJob> ray_job;
     std::vector<std::shared_ptr<msm::RayJob>> stale_jobs;
@@ -242,12 +240,15 @@ struct AdaptiveDev {
 int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check = true);  // check = false: the caller checks the status word
 // out (device, D x V(new)) = the weights applied to d_data (device, D x V(in)): barycentric_data_interpolation R/resampler.cpp:40-52
 int apply_weights_dev(msm_ctx *ctx, const AdaptiveDev &w, const double *d_data, int D, double *d_out);
-int ensure_adjacency_dev(msm_mesh *m);
-int ensure_tree_pair(msm_mesh *a, msm_mesh *b);  // both trees; a host build of one runs while the GPU builds the other  // Mpoint::trID lists as CSR in HBM (d_tid_ptr / d_tid)
+int ensure_adjacency_dev(msm_mesh *m);  // Mpoint::trID lists as CSR in HBM (d_tid_ptr / d_tid), and d_fold
+// the host copy of the coordinates follows the device when they were last written there (msm_mesh::host_xyz_stale); fetched on via's stream
+int refresh_host_xyz(msm_mesh *m, msm_ctx *via);
+int ensure_tree_pair(msm_mesh *a, msm_mesh *b);  // both trees; a host build of one runs while the GPU builds the other
 void adaptive_surgery(const AdaptiveQueries &q, int nOld, int nNew, const std::vector<double> &oldA, const std::vector<double> &newA,
                       const double *excl, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col, std::vector<double> &val);
 void vertex_areas_of(const double *xyz, const int32_t *tri, int V, int T, const Adjacency &a, std::vector<double> &area);
 int ensure_tree(msm_mesh *m);  // build + upload the search structure if stale
+// octree_kernels.hip: the same tree built in HBM from the mesh's device coordinates (MSM_ERR_CAPACITY: use the host build)
 int gpu_build_octree(msm_mesh *m, const std::function<void()> *overlap = nullptr);
 // B trees over one triangle list and B coordinate sets, built together (octree_kernels.hip: gpu_build_forest); the arrays of tree b
 // start b * s_* elements into the shared buffers
@@ -276,7 +277,7 @@ struct Forest {
 int gpu_build_forest(msm_ctx *ctx, Forest &f, const double *d_xyz, size_t comp_stride, size_t tree_stride, int V, const int32_t *d_tri, int T, int B);
 int gpu_build_octree_begin(msm_mesh *m);   // the same in two halves: queue the build ... 
 int gpu_build_octree_finish(msm_mesh *m);  // ... wait for it (one build at a time per context)
-int ensure_tree_begin(msm_mesh *m);        // api.cpp: starts the GPU build of an invalid tree (no-op otherwise); ensure_tree() completes it  // octree_kernels.hip: the same tree built in HBM from the mesh's device coordinates (MSM_ERR_CAPACITY: use the host build)
+int ensure_tree_begin(msm_mesh *m);        // api.cpp: starts the GPU build of an invalid tree (no-op otherwise); ensure_tree() completes it
 bool mesh_tree_on_gpu(const msm_mesh *m);  // api.cpp: is this mesh's tree built by the GPU kernels (large meshes) or on the host
 int finish_tree(msm_mesh *m);       // what follows either build: validity flags, generation
 int ensure_masks(msm_mesh *m);  // + the per-leaf sub-cell masks the cost kernels use (built on the GPU)

@@ -334,20 +334,20 @@ constexpr int kRayExclMax = 7;
 
 void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOctree &out) {
     auto tick_ = std::chrono::steady_clock::now();
-    out.ray_G = 0;
-    out.ray_cell.clear();
-    out.ray_edge.clear();
-    out.simple = simple_star_surface(xyz, tri, V, T);
+    out.rays.G = 0;
+    out.rays.cell.clear();
+    out.rays.edge.clear();
+    out.rays.simple = simple_star_surface(xyz, tri, V, T);
     const char *no_table = std::getenv("MSMHIP_DISABLE_RAYTABLE");  // testing: force the complete search everywhere
-    if (!out.simple || (no_table && no_table[0] == '1')) return;
+    if (!out.rays.simple || (no_table && no_table[0] == '1')) return;
     TICK("simple");
     const std::vector<double> margin = safe_margins(xyz, tri, V, T);
     TICK("margins");
-    out.ray_edge.assign((size_t)3 * T, make_float4(0.f, 0.f, 0.f, 2.f));
-    out.ray_excl.clear();
-    out.ray_more.clear();
-    out.ray_r2lo = (kRad - kRayShell) * (kRad - kRayShell);
-    out.ray_r2hi = (kRad + kRayShell) * (kRad + kRayShell);
+    out.rays.edge.assign((size_t)3 * T, make_float4(0.f, 0.f, 0.f, 2.f));
+    out.rays.excl.clear();
+    out.rays.more.clear();
+    out.rays.r2lo = (kRad - kRayShell) * (kRad - kRayShell);
+    out.rays.r2hi = (kRad + kRayShell) * (kRad + kRayShell);
     std::vector<char> usable(T, 0);
     const int workers = host_workers();
     // exclusion records are collected per chunk and numbered afterwards (chunks are contiguous triangle ranges, so the
@@ -438,22 +438,22 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
         }
         e[1].w = __builtin_bit_cast(float, (int32_t)excl);
         e[2].w = 0.f;
-        for (int k = 0; k < 3; ++k) out.ray_edge[(size_t)3 * t + k] = e[k];
+        for (int k = 0; k < 3; ++k) out.rays.edge[(size_t)3 * t + k] = e[k];
         usable[t] = 1;
     }
     });
     for (const Chunk &c : chunk_out) {
-        const int base = (int)out.ray_excl.size();
+        const int base = (int)out.rays.excl.size();
         for (size_t k = 0; k < c.excl.size(); ++k) {
-            out.ray_excl.push_back(c.excl[k]);
-            if (c.owner[k] >= 0) out.ray_edge[(size_t)3 * c.owner[k] + 1].w = __builtin_bit_cast(float, (int32_t)(base + (int)k));
+            out.rays.excl.push_back(c.excl[k]);
+            if (c.owner[k] >= 0) out.rays.edge[(size_t)3 * c.owner[k] + 1].w = __builtin_bit_cast(float, (int32_t)(base + (int)k));
         }
     }
     TICK("edges+robust");
     // cube map: face f = 2*axis + (negative side); (u, v) = the two other components over |major component|
     int G = 8;
     while (G < 512 && (double)G * G * 6 < 4.0 * T) G *= 2;
-    out.ray_G = G;
+    out.rays.G = G;
     const size_t ncell = (size_t)6 * G * G;
     struct Cand {
         uint32_t cell;
@@ -530,7 +530,7 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
             for (const Cand &c : f) cand[(size_t)fill[c.cell]++] = c;
     }
     TICK("bucket");
-    out.ray_cell.assign(ncell, make_int4(-1, -1, -1, -1));
+    out.rays.cell.assign(ncell, make_int4(-1, -1, -1, -1));
     parallel_chunks((int)ncell, workers, [&](int, int c_begin, int c_end) {
         for (int c = c_begin; c < c_end; ++c)
             std::sort(cand.data() + count[c], cand.data() + count[c + 1],
@@ -538,17 +538,17 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
     });
     for (size_t c = 0; c < ncell; ++c) {
         const Cand *first = cand.data() + count[c], *last = cand.data() + count[c + 1];
-        int32_t *slot = &out.ray_cell[c].x;
+        int32_t *slot = &out.rays.cell[c].x;
         const int ncand = (int)(last - first);
         if (ncand <= 4) {
             for (int k = 0; k < ncand; ++k) slot[k] = first[k].tri;
         } else {
             for (int k = 0; k < 3; ++k) slot[k] = first[k].tri;
-            slot[3] = -2 - (int)out.ray_more.size();
+            slot[3] = -2 - (int)out.rays.more.size();
             int4 more = make_int4(-1, -1, -1, -1);
             int32_t *ms = &more.x;
             for (int k = 0; k < 4 && 3 + k < ncand; ++k) ms[k] = first[3 + k].tri;
-            out.ray_more.push_back(more);
+            out.rays.more.push_back(more);
         }
     }
     TICK("cells");
@@ -664,10 +664,10 @@ void build_octree(const double *xyz, const int32_t *tri, int V, int T, FlatOctre
     }
 
     TICK("octree: insertion");
-    out.simple = false;  // decided together with the ray table (build_ray_table), which only the cost kernels need
-    out.ray_G = 0;
-    out.ray_cell.clear();
-    out.ray_edge.clear();
+    out.rays.simple = false;  // decided together with the ray table (build_ray_table), which only the cost kernels need
+    out.rays.G = 0;
+    out.rays.cell.clear();
+    out.rays.edge.clear();
 
     // Leaf entries are padded to multiples of 8 (id -1, a cone nothing passes): 8 cones = one 128-byte line.
     const int n = (int)b.nodes.size();
@@ -778,20 +778,20 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
     build_octree(xyz, tri, V, T, o);
     build_ray_table(xyz, tri, V, T, o);
     for (int k = 0; k < 10; ++k) report[k] = 0;
-    report[7] = o.simple ? 1 : 0;
-    if (o.ray_G <= 0) return MSM_OK;
+    report[7] = o.rays.simple ? 1 : 0;
+    if (o.rays.G <= 0) return MSM_OK;
     std::vector<int> guarded;  // triangles with exclusion boxes: every fifth point is placed above one of them
     for (int t = 0; t < T; ++t) {
-        if (o.ray_edge[3 * (size_t)t].w >= 2.f) ++report[5];
-        else if (__builtin_bit_cast(int32_t, o.ray_edge[3 * (size_t)t + 1].w) >= 0) guarded.push_back(t);
+        if (o.rays.edge[3 * (size_t)t].w >= 2.f) ++report[5];
+        else if (__builtin_bit_cast(int32_t, o.rays.edge[3 * (size_t)t + 1].w) >= 0) guarded.push_back(t);
     }
     report[6] = (int64_t)guarded.size();
     DevTree dt{};
-    dt.ray_G = o.ray_G;
-    dt.ray_cell = o.ray_cell.data();
-    dt.ray_more = o.ray_more.data();
-    dt.ray_excl = o.ray_excl.data();
-    dt.ray_r2lo = o.ray_r2lo, dt.ray_r2hi = o.ray_r2hi;
+    dt.ray_G = o.rays.G;
+    dt.ray_cell = o.rays.cell.data();
+    dt.ray_more = o.rays.more.data();
+    dt.ray_excl = o.rays.excl.data();
+    dt.ray_r2lo = o.rays.r2lo, dt.ray_r2hi = o.rays.r2hi;
     // the records themselves: every leaf that meets the shell region of a guarded triangle without listing it must be refused
     for (int t : guarded) {
         const V3 v[3] = {vtx(xyz, V, tri[t]), vtx(xyz, V, tri[T + t]), vtx(xyz, V, tri[2 * (size_t)T + t])};
@@ -814,7 +814,7 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
             const double4 b = o.nodebox[leaf];
             const V3 centre = mk(b.x + 0.5 * b.w, b.y + 0.5 * b.w, b.z + 0.5 * b.w);
             ++report[8];
-            if (ray_vouches(dt, o.ray_edge[3 * (size_t)t + 1], centre)) ++report[4];
+            if (ray_vouches(dt, o.rays.edge[3 * (size_t)t + 1], centre)) ++report[4];
         }
     }
     uint64_t rs = seed * 6364136223846793005ull + 1442695040888963407ull;
@@ -865,14 +865,14 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
         float fx, fy, fz;
         const int4 cell = ray_cell_of(dt, p, fx, fy, fz);
         int4 more = make_int4(cell.w, -1, -1, -1);
-        if (cell.x >= 0 && cell.w < -1) more = o.ray_more[-2 - cell.w];
+        if (cell.x >= 0 && cell.w < -1) more = o.rays.more[-2 - cell.w];
         const int cand[7] = {cell.x, cell.y, cell.z, more.x, more.y, more.z, more.w};
         const double pn = norm(p);
         bool by_float = false, by_fp64 = false, bad = false;
         for (int k = 0; k < 7 && cell.x >= 0; ++k) {
             const int t = cand[k];
             if (t < 0) break;
-            const float4 e0 = o.ray_edge[3 * (size_t)t], e1 = o.ray_edge[3 * (size_t)t + 1], e2 = o.ray_edge[3 * (size_t)t + 2];
+            const float4 e0 = o.rays.edge[3 * (size_t)t], e1 = o.rays.edge[3 * (size_t)t + 1], e2 = o.rays.edge[3 * (size_t)t + 2];
             float least;
             const int lvl = ray_accept_level(e0, e1, e2, fx, fy, fz, least);
             bool ok = lvl == 2;

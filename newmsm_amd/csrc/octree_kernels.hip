@@ -614,6 +614,38 @@ int queue_levels(msm_ctx *ctx, OctJob &j, int count) {
     MSM_HIP(hipMemcpyAsync(j.h_counters, j.w.counters, sizeof(int) * (B == 1 ? (size_t)C_COUNT : (size_t)B * (C_COUNT + 1)), hipMemcpyDeviceToHost, ctx->stream));
     return MSM_OK;
 }
+
+// What a build of one tree over T triangles works in: the capacities of its arrays, the number of ints its work area takes, and that work
+// area carved out of a block of ints.  One mesh (gpu_build_octree_begin) is a forest of one tree with every stride zero.
+struct OctCaps {
+    int nodes, refs, arena, open, chunks;
+    explicit OctCaps(int T) : nodes(T + 64), refs(6 * T + 256), arena(8 * T + 512), open(nodes), chunks(refs / kChunk + open + 64) {}
+};
+size_t oct_work_ints(const OctCaps &c) {
+    return (size_t)2 * c.refs + (size_t)8 * c.open + (size_t)c.open + (size_t)8 * c.open + (size_t)4 * c.chunks + (size_t)8 * c.chunks + 16 +
+           8 * ((size_t)c.open / kScanThreads + 2) + ((size_t)c.refs + 3) / 4;
+}
+// fills w's work arrays and capacities; the caller sets the tree's own arrays (box, node, parent, nodebox, counters, leaf_tri) and the strides
+void oct_carve(OctWork &w, int *base, const OctCaps &c) {
+    int *p = base;
+    w.list[0] = p, p += c.refs;
+    w.list[1] = p, p += c.refs;
+    for (int k = 0; k < 2; ++k) {
+        w.open_node[k] = p, p += c.open;
+        w.open_off[k] = p, p += c.open;
+        w.open_len[k] = p, p += c.open;
+        w.open_chunk[k] = p, p += c.open;
+        w.chunk_open[k] = p, p += c.chunks;
+        w.chunk_beg[k] = p, p += c.chunks;
+    }
+    w.split = p, p += c.open;
+    p += (4 - ((p - base) & 3)) & 3;  // 16-byte alignment of the int4 accesses below
+    w.ctot = p, p += (size_t)8 * c.open;
+    w.cc = p, p += (size_t)8 * c.chunks;
+    w.agg = p, p += 8 * ((size_t)c.open / kScanThreads + 2);
+    w.flags = reinterpret_cast<unsigned char *>(p);
+    w.cap_nodes = c.nodes, w.cap_refs = c.refs, w.cap_arena = c.arena, w.cap_open = c.open, w.cap_chunks = c.chunks;
+}
 }  // namespace
 
 // The build in two halves, so that a caller (api.cpp: ensure_tree_pair; cost.cpp: patches_by_triangle) can queue the levels of
@@ -623,75 +655,36 @@ int queue_levels(msm_ctx *ctx, OctJob &j, int count) {
 int gpu_build_octree_begin(msm_mesh *m) {
     msm_ctx *ctx = m->ctx;
     const int T = m->T, V = m->V;
-    const int cap_nodes = T + 64, cap_refs = 6 * T + 256, cap_arena = 8 * T + 512, cap_open = cap_nodes, cap_chunks = cap_refs / kChunk + cap_open + 64;
+    const OctCaps c(T);
     MSM_HIP(hipSetDevice(ctx->device));
-    if ((size_t)6 * T > ctx->oct_cap_box) {
-        if (ctx->oct_box) (void)msm::pool_free(ctx->oct_box);
-        ctx->oct_box = nullptr;
-        ctx->oct_cap_box = (size_t)6 * T + 1024;
-        MSM_HIP(msm::pool_malloc((void **)&ctx->oct_box, ctx->oct_cap_box * sizeof(double)));
-    }
-    const size_t need_ints = (size_t)2 * cap_refs + (size_t)8 * cap_open + (size_t)cap_open + (size_t)8 * cap_open + (size_t)4 * cap_chunks + (size_t)8 * cap_chunks + 16 +
-                             8 * ((size_t)cap_open / kScanThreads + 2) + ((size_t)cap_refs + 3) / 4;
-    if (need_ints > ctx->oct_cap_ints) {
-        if (ctx->oct_ints) (void)msm::pool_free(ctx->oct_ints);
-        ctx->oct_ints = nullptr;
-        ctx->oct_cap_ints = need_ints + 4096;
-        MSM_HIP(msm::pool_malloc((void **)&ctx->oct_ints, ctx->oct_cap_ints * sizeof(int)));
-    }
-    if (!ctx->oct_counters) {
-        MSM_HIP(msm::pool_malloc((void **)&ctx->oct_counters, sizeof(int) * (C_COUNT + 1)));
+    // the context's scratch, with some slack for the next mesh; the mesh's arrays exactly (T does not change)
+    MSM_HIP(ctx->oct_box.ensure((size_t)6 * T + 1024, true));
+    MSM_HIP(ctx->oct_ints.ensure(oct_work_ints(c) + 4096, true));
+    if (!ctx->oct_counters.p) {
+        MSM_HIP(ctx->oct_counters.ensure(C_COUNT + 1, true));
         MSM_HIP(hipHostMalloc((void **)&ctx->oct_hcounters, sizeof(int) * (C_COUNT + 1)));
     }
-    struct {
-        double *box;
-        int *ints, *counters, *h_counters;
-    } s{ctx->oct_box, ctx->oct_ints, ctx->oct_counters, ctx->oct_hcounters};
-    auto grow = [&](void **p, size_t &cap, size_t need, size_t elem) -> hipError_t {
-        if (need <= cap && *p) return hipSuccess;
-        if (*p) (void)msm::pool_free(*p);
-        *p = nullptr;
-        cap = need;
-        return msm::pool_malloc(p, cap * elem);
-    };
-    MSM_HIP(grow((void **)&m->d_node, m->cap_node, cap_nodes, sizeof(int4)));
-    MSM_HIP(grow((void **)&m->d_parent, m->cap_parent, cap_nodes, sizeof(int32_t)));
-    MSM_HIP(grow((void **)&m->d_nodebox, m->cap_box, cap_nodes, sizeof(double4)));
-    MSM_HIP(grow((void **)&m->d_leaf_tri, m->cap_leaf, cap_arena, sizeof(int32_t)));
-    MSM_HIP(grow((void **)&m->d_cone, m->cap_cone, cap_arena, sizeof(float4)));
-    MSM_HIP(grow((void **)&m->d_rec, m->cap_rec, (size_t)T, sizeof(TriRec)));
-    MSM_HIP(grow((void **)&m->d_grid, m->cap_grid, (size_t)64 * 64 * 64, sizeof(int32_t)));
+    MSM_HIP(m->d_node.ensure(c.nodes, true));
+    MSM_HIP(m->d_parent.ensure(c.nodes, true));
+    MSM_HIP(m->d_nodebox.ensure(c.nodes, true));
+    MSM_HIP(m->d_leaf_tri.ensure(c.arena, true));
+    MSM_HIP(m->d_cone.ensure(c.arena, true));
+    MSM_HIP(m->d_rec.ensure((size_t)T, true));
+    MSM_HIP(m->d_grid.ensure((size_t)64 * 64 * 64, true));
 
     OctWork w;
-    w.box = s.box;
-    w.node = m->d_node;
-    w.parent = m->d_parent;
-    w.nodebox = m->d_nodebox;
-    w.counters = s.counters;
-    int *p = s.ints;
-    w.list[0] = p, p += cap_refs;
-    w.list[1] = p, p += cap_refs;
-    for (int k = 0; k < 2; ++k) {
-        w.open_node[k] = p, p += cap_open;
-        w.open_off[k] = p, p += cap_open;
-        w.open_len[k] = p, p += cap_open;
-        w.open_chunk[k] = p, p += cap_open;
-        w.chunk_open[k] = p, p += cap_chunks;
-        w.chunk_beg[k] = p, p += cap_chunks;
-    }
-    w.split = p, p += cap_open;
-    p += (4 - ((p - s.ints) & 3)) & 3;  // 16-byte alignment of the int4 accesses below
-    w.ctot = p, p += (size_t)8 * cap_open;
-    w.cc = p, p += (size_t)8 * cap_chunks;
-    w.agg = p, p += 8 * ((size_t)cap_open / kScanThreads + 2);
-    w.flags = reinterpret_cast<unsigned char *>(p);
-    w.leaf_tri = m->d_leaf_tri;
-    w.cap_nodes = cap_nodes, w.cap_refs = cap_refs, w.cap_arena = cap_arena, w.cap_open = cap_open, w.cap_chunks = cap_chunks;
+    w.box = ctx->oct_box.p;
+    w.node = m->d_node.p;
+    w.parent = m->d_parent.p;
+    w.nodebox = m->d_nodebox.p;
+    w.counters = ctx->oct_counters.p;
+    w.leaf_tri = m->d_leaf_tri.p;
+    oct_carve(w, ctx->oct_ints.p, c);
 
     // root: node 0 with the cube (-101, 101) and every triangle
     const int root_chunks = (T + kChunk - 1) / kChunk;
     w.s_box = w.s_node = w.s_cnt = w.s_ints = w.s_leaf = 0;
-    hipLaunchKernelGGL(k_oct_boxes, dim3((T + 255) / 256), dim3(256), 0, ctx->stream, m->d_xyz, (size_t)V, (size_t)0, m->d_tri, T, s.box, w.list[0], (size_t)0, (size_t)0);
+    hipLaunchKernelGGL(k_oct_boxes, dim3((T + 255) / 256), dim3(256), 0, ctx->stream, m->d_xyz.p, (size_t)V, (size_t)0, m->d_tri.p, T, ctx->oct_box.p, w.list[0], (size_t)0, (size_t)0);
     hipLaunchKernelGGL(k_oct_init, dim3((std::max(root_chunks, C_COUNT + 1) + 255) / 256), dim3(256), 0, ctx->stream, w, T, root_chunks);
     auto job = std::make_shared<OctJob>();
     job->w = w;
@@ -714,10 +707,7 @@ int gpu_build_octree_finish(msm_mesh *m) {
         if (st) return st;
         MSM_TRY(ctx_sync(ctx));
     }
-    struct {
-        int *h_counters;
-    } s{ctx->oct_hcounters};
-    const int *hc = s.h_counters;
+    const int *hc = ctx->oct_hcounters;
     if ((hc[C_OVERFLOW] & 2) && std::getenv("MSMHIP_TIMING"))
         fprintf(stderr, "  octree build: a k_oct_scan workgroup waited in vain for an earlier one (%d CUs, not all of the launch resident?): host build instead\n", ctx->num_cus);
     if (hc[C_OVERFLOW] || hc[C_NOPEN] != 0) return MSM_ERR_CAPACITY;
@@ -730,9 +720,9 @@ int gpu_build_octree_finish(msm_mesh *m) {
     o.stats[0] = hc[C_NNODES], o.stats[1] = hc[C_NLEAVES], o.stats[2] = hc[C_MAXDEPTH], o.stats[3] = hc[C_REFS], o.stats[4] = hc[C_MAXLEAF];
     const int G = 1 << o.grid_depth;
     const size_t cells = (size_t)G * G * G;
-    hipLaunchKernelGGL(k_oct_grid, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, m->d_node, o.grid_depth, m->d_grid);
+    hipLaunchKernelGGL(k_oct_grid, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, m->d_node.p, o.grid_depth, m->d_grid.p);
     MSM_HIP(hipGetLastError());
-    return launch_build_recs(ctx, m->d_xyz, V, m->d_tri, T, m->d_rec, m->d_tcone, m->d_leaf_tri, o.dev_entries, m->d_cone);
+    return launch_build_recs(ctx, m->d_xyz.p, V, m->d_tri.p, T, m->d_rec.p, m->d_tcone.p, m->d_leaf_tri.p, o.dev_entries, m->d_cone.p);
 }
 
 // B trees at once: the same triangle list over B coordinate sets (gMSM: a subject's data mesh rotated to every label), every level's
@@ -742,11 +732,10 @@ int gpu_build_octree_finish(msm_mesh *m) {
 int gpu_build_forest(msm_ctx *ctx, Forest &f, const double *d_xyz, size_t comp_stride, size_t tree_stride, int V, const int32_t *d_tri, int T, int B) {
     if (B <= 0 || T <= 0) return fail(MSM_ERR_INVALID, "gpu_build_forest: bad arguments");
     MSM_HIP(hipSetDevice(ctx->device));
-    const int cap_nodes = T + 64, cap_refs = 6 * T + 256, cap_arena = 8 * T + 512, cap_open = cap_nodes, cap_chunks = cap_refs / kChunk + cap_open + 64;
-    const size_t per_ints = ((size_t)2 * cap_refs + (size_t)8 * cap_open + (size_t)cap_open + (size_t)8 * cap_open + (size_t)4 * cap_chunks + (size_t)8 * cap_chunks + 16 +
-                             8 * ((size_t)cap_open / kScanThreads + 2) + ((size_t)cap_refs + 3) / 4 + 3) & ~(size_t)3;
+    const OctCaps c(T);
+    const size_t per_ints = (oct_work_ints(c) + 3) & ~(size_t)3;  // every tree's block starts 16-byte aligned
     f.B = B, f.T = T, f.V = V;
-    f.s_node = (size_t)cap_nodes, f.s_leaf = (size_t)cap_arena, f.s_rec = (size_t)T, f.s_grid = (size_t)64 * 64 * 64;
+    f.s_node = (size_t)c.nodes, f.s_leaf = (size_t)c.arena, f.s_rec = (size_t)T, f.s_grid = (size_t)64 * 64 * 64;
     MSM_HIP(f.node.ensure(f.s_node * B));
     MSM_HIP(f.parent.ensure(f.s_node * B));
     MSM_HIP(f.nodebox.ensure(f.s_node * B));
@@ -770,27 +759,8 @@ int gpu_build_forest(msm_ctx *ctx, Forest &f, const double *d_xyz, size_t comp_s
     w.parent = f.parent.p;
     w.nodebox = f.nodebox.p;
     w.counters = f.counters.p;
-    // within a tree's block of ints the arrays lie as in gpu_build_octree_begin; the blocks of consecutive trees per_ints apart,
-    // so every array's stride is per_ints
-    int *p = f.ints.p;
-    w.list[0] = p, p += cap_refs;
-    w.list[1] = p, p += cap_refs;
-    for (int k = 0; k < 2; ++k) {
-        w.open_node[k] = p, p += cap_open;
-        w.open_off[k] = p, p += cap_open;
-        w.open_len[k] = p, p += cap_open;
-        w.open_chunk[k] = p, p += cap_open;
-        w.chunk_open[k] = p, p += cap_chunks;
-        w.chunk_beg[k] = p, p += cap_chunks;
-    }
-    w.split = p, p += cap_open;
-    p += (4 - ((p - f.ints.p) & 3)) & 3;
-    w.ctot = p, p += (size_t)8 * cap_open;
-    w.cc = p, p += (size_t)8 * cap_chunks;
-    w.agg = p, p += 8 * ((size_t)cap_open / kScanThreads + 2);
-    w.flags = reinterpret_cast<unsigned char *>(p);
     w.leaf_tri = f.leaf_tri.p;
-    w.cap_nodes = cap_nodes, w.cap_refs = cap_refs, w.cap_arena = cap_arena, w.cap_open = cap_open, w.cap_chunks = cap_chunks;
+    oct_carve(w, f.ints.p, c);  // the blocks of consecutive trees lie per_ints apart, so every work array's stride is per_ints
     w.s_box = (size_t)6 * T, w.s_node = f.s_node, w.s_cnt = (size_t)(C_COUNT + 1), w.s_ints = per_ints, w.s_leaf = f.s_leaf;
     const unsigned UB = (unsigned)B;
     const int root_chunks = (T + kChunk - 1) / kChunk;

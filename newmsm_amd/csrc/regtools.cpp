@@ -78,17 +78,8 @@ int msm_mesh_unfold(msm_mesh *m, double radius, int32_t *passes, int32_t *first_
     msm_ctx *ctx = m->ctx;
     MSM_HIP(hipSetDevice(ctx->device));
     const int V = m->V, T = m->T;
+    MSM_TRY(ensure_adjacency_dev(m));
     const Adjacency &adj = mesh_adjacency(m);
-    if (!m->d_tid_ptr) {
-        MSM_HIP(msm::pool_malloc((void **)&m->d_tid_ptr, sizeof(int32_t) * adj.tid_ptr.size()));
-        MSM_HIP(msm::pool_malloc((void **)&m->d_tid, sizeof(int32_t) * std::max<size_t>(adj.tid.size(), 1)));
-        MSM_HIP(msm::pool_malloc((void **)&m->d_fold, sizeof(int32_t) * (2 + (size_t)V)));
-        // (through the context's pinned staging block, like every upload of the library: the GPU never reads the caller's pageable pages, whose pinning by the
-        // runtime for an asynchronous copy outlives nothing the library controls)
-        int st = upload_staged(ctx, m->d_tid_ptr, adj.tid_ptr.data(), sizeof(int32_t) * adj.tid_ptr.size());
-        if (!st && !adj.tid.empty()) st = upload_staged(ctx, m->d_tid, adj.tid.data(), sizeof(int32_t) * adj.tid.size());
-        if (st) return st;
-    }
     if (passes) *passes = 0;
     if (first_folded) *first_folded = 0;
     std::vector<int32_t> flags;
@@ -96,16 +87,16 @@ int msm_mesh_unfold(msm_mesh *m, double radius, int32_t *passes, int32_t *first_
     std::vector<V3> grads;
     FoldMesh fm{m->xyz.data(), m->tri.data(), &adj, V, T};
     for (int it = 0;; ++it) {
-        int st = launch_fold_detect(ctx, m->d_xyz, V, m->d_tri, T, m->d_tid_ptr, m->d_tid, m->d_fold);
+        int st = launch_fold_detect(ctx, m->d_xyz.p, V, m->d_tri.p, T, m->d_tid_ptr.p, m->d_tid.p, m->d_fold.p);
         if (st) return st;
         int32_t head[2];
-        MSM_TRY(stage_d2h(ctx, head, m->d_fold, sizeof(head)));
+        MSM_TRY(stage_d2h(ctx, head, m->d_fold.p, sizeof(head)));
         MSM_TRY(ctx_sync(ctx));
         if (head[1] > 0) return fail(MSM_ERR_INVALID, "get_triangle: index exceeds face dimensions");  // a vertex without triangles, R/mesh.h:82-86
         if (it == 0 && first_folded) *first_folded = head[0];
         if (head[0] == 0) break;  // the usual case: nothing is folded and nothing leaves the GPU but two counters
         flags.resize(V);
-        MSM_TRY(stage_d2h(ctx, flags.data(), m->d_fold + 2, sizeof(int32_t) * (size_t)V));
+        MSM_TRY(stage_d2h(ctx, flags.data(), m->d_fold.p + 2, sizeof(int32_t) * (size_t)V));
         MSM_TRY(ctx_sync(ctx));
         folded.clear();
         for (int v = 0; v < V; ++v)
@@ -125,7 +116,7 @@ int msm_mesh_unfold(msm_mesh *m, double radius, int32_t *passes, int32_t *first_
             fm.set(folded[k], scale(pp, radius));
         }
         m->tree_valid = false;
-        st = upload_staged(ctx, m->d_xyz, m->xyz.data(), sizeof(double) * 3 * (size_t)V);
+        st = upload_staged(ctx, m->d_xyz.p, m->xyz.data(), sizeof(double) * 3 * (size_t)V);
         if (st) return st;
         if (passes) *passes = it + 1;
         if (it + 1 == 1000) break;

@@ -78,7 +78,7 @@ RigidEvalArgs eval_args(msm_rigid *r) {
     a.Ts = r->Ts;
     a.stid_ptr = r->stid_ptr.p;
     a.stid = r->stid.p;
-    a.txyz = r->target->d_xyz;
+    a.txyz = r->target->d_xyz.p;
     a.Vt = r->Vt;
     a.qptr = r->qptr.p;
     a.qidx = r->qidx.p;

@@ -54,11 +54,7 @@ int calculate_strains(msm_mesh *orig, const double *final_xyz, double fit_radius
     const int V = orig->V;
     MSM_HIP(hipSetDevice(ctx->device));
     MSM_TRY(drop_ctx_pending(ctx));
-    if (orig->host_xyz_stale) {
-        MSM_TRY(stage_d2h(ctx, orig->xyz.data(), orig->d_xyz, sizeof(double) * 3 * (size_t)V));
-        MSM_TRY(ctx_sync(ctx));
-        orig->host_xyz_stale = false;
-    }
+    MSM_TRY(refresh_host_xyz(orig, ctx));
     const double *x = orig->xyz.data();
     double extent = 0.0;
     for (int d = 0; d < 3; ++d) {
@@ -82,10 +78,10 @@ int calculate_strains(msm_mesh *orig, const double *final_xyz, double fit_radius
     a.g = grid_of(x, V, fit_radius, &C);
     a.V = V;
     a.T = orig->T;
-    a.orig = orig->d_xyz;
-    a.tri = orig->d_tri;
-    a.tid_ptr = orig->d_tid_ptr;
-    a.tid = orig->d_tid;
+    a.orig = orig->d_xyz.p;
+    a.tri = orig->d_tri.p;
+    a.tid_ptr = orig->d_tid_ptr.p;
+    a.tid = orig->d_tid.p;
     a.fit_radius = fit_radius;
     MSM_TRY(b.fin.upload(final_xyz, 3 * (size_t)V, ctx));
     const size_t v3 = 3 * (size_t)V;
