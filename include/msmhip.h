@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 11  /* 11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 11  /* 11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -509,6 +509,52 @@ int msm_rigid_kernel_ms(msm_rigid *r, double ms[2]);
  * radius (V, optional): the final r.  V must equal orig's vertex count and fit_radius be > 0.  A mesh where some vertex can never
  * have 9 members (the reference's radius would grow forever): MSM_ERR_INVALID.  Host arrays are complete on return. */
 int msm_calculate_strains(msm_mesh *orig, const double *final_xyz, int32_t V, double fit_radius, double *strains, int32_t *kept, double *radius);
+
+/* ------------------------------------------------------------------------------------------------
+ * after a groupwise run: dedrifting and the group's statistics.  Replaces what the reference's tutorial pipeline does with wb_command and nibabel
+ * once gMSM has written its spheres (gMSM_scripts/gMSM_tutorial/gw_MSM.sh:65-128, compare_stats.py; docs/guide.md, "After registration, we apply
+ * dedrifting").  Per subject s: M_s its input sphere as the run used it (recentred, radius 100), R_s its registered sphere (sphere-<s>.reg: the
+ * same triangles), F_s its data (D x V_s); T the template.  All searches and weights are Resampler::get_barycentric_weights (R/resampler.cpp:142-167).
+ * Call order: accumulate every subject, finish, correct every subject, group statistics.  Everything between the uploads of a subject's arrays and
+ * the downloads of its results stays on the device; the subjects' resampled maps stay resident in the handle (S x D x V(T) doubles).
+ * Agreement with wb_command's own arithmetic (-surface-modify-sphere -recenter, -surface-distortion -local-affine-method) is unpinned: Workbench is
+ * not available to this project; the definitions below are the contract.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct msm_dedrift msm_dedrift;
+/* One handle per group of num_subjects subjects on the template's context.  The template must outlive the handle. */
+msm_dedrift *msm_dedrift_create(msm_ctx *ctx, msm_mesh *template_mesh, int32_t num_subjects);
+void msm_dedrift_destroy(msm_dedrift *d);
+/* forget the running sum, the warp and the resident maps: the handle serves another group of the same size on the same template */
+int msm_dedrift_reset(msm_dedrift *d);
+/* gw_MSM.sh:76-80 (-surface-sphere-project-unproject, the inverse of one registration) and one term of :82-87 (-surface-average): for every vertex of
+ * T the closest triangle of reg (= R_s) and its weights, applied to orig_xyz (= M_s, 3 x V SoA, V = reg's vertex count) without normalisation --
+ * project_anatomical_mesh's sum (R/resampler.cpp:260-282) -- and added to the running sum.  The tutorial passes the template as the sphere to
+ * unproject to, which is the same thing exactly when M_s is the template (its situation); M_s is the general form.  The additions happen in the
+ * order of the calls.  Optional outputs (each may be NULL; with all three NULL the call only queues its work and msm_dedrift_finish reports a failed
+ * search): tri_id (V(T)) and w (3 x V(T)) the search's decisions, inverse_xyz (3 x V(T)) the subject's inverse.  A later all-reduce of the running
+ * sum over ranks fits between the last accumulate and finish; nothing else about several ranks is built. */
+int msm_dedrift_accumulate(msm_dedrift *d, msm_mesh *reg, const double *orig_xyz, int32_t V, int32_t *tri_id, double *w, double *inverse_xyz);
+/* gw_MSM.sh:82-92 (-surface-average, -surface-modify-sphere 100 -recenter): drift = running sum / S; the dedrift warp W = drift minus the midpoint of
+ * its axis-aligned bounding box, every vertex scaled to length 100.  W stays on the device for msm_dedrift_correct; warp_xyz / drift_xyz (3 x V(T),
+ * optional) receive copies.  Fails with MSM_ERR_STATE unless all S subjects have been accumulated. */
+int msm_dedrift_finish(msm_dedrift *d, double *warp_xyz, double *drift_xyz);
+/* gw_MSM.sh:94-128 for subject `subject`: corrected_s = sphere_project_warp(R_s, T, W) (-surface-sphere-project-unproject with the dedrift warp,
+ * R/resampler.cpp:311-328) -- reg holds corrected_s afterwards, as msm_mesh_sphere_project_warp leaves a mesh; resampled_s = metric_resample of data
+ * (D x V) from corrected_s onto T (-metric-resample ADAP_BARY_AREA; the arithmetic of msm_metric_resample), kept resident; distortion_s (2 x V):
+ * per triangle of M_s (orig_xyz) against the same triangle of corrected_s, J and R as triangle_strain forms them (M/reg_tools.cpp:578-593, through the
+ * tangent frames of calculate_triangular_strain :698-743), per vertex the plain mean over its incident triangles in trID order of log2 J (row 0,
+ * areal) and log2 R (row 1, shape) (-surface-distortion -local-affine-method -log2).  Outputs may be NULL; tri_id (V) / w (3 x V): the decisions of
+ * the search of R_s's vertices on T.  D must be the same for every subject of a group. */
+int msm_dedrift_correct(msm_dedrift *d, int32_t subject, msm_mesh *reg, const double *orig_xyz, int32_t V, const double *data, int32_t D,
+                        double *corrected_xyz, double *resampled, double *distortion, int32_t *tri_id, double *w);
+/* a subject's maps on the template (D x V(T)) from the host instead of from msm_dedrift_correct: group statistics of maps that exist already (the
+ * un-dedrifted transformed_and_reprojected-<i> files of the run, compare_stats.py's "before") */
+int msm_dedrift_set_map(msm_dedrift *d, int32_t subject, const double *map, int32_t D);
+/* gw_MSM.sh:108-119 (-metric-merge, -metric-reduce MEAN / STDEV) and compare_stats.py:12-69 over the resident maps: mean, stdev (D x V(T)): over the
+ * subjects, two passes in subject order, population form; cc (D x S x S): Pearson correlation over the vertices (numpy.corrcoef's quantity); dice
+ * (D x S x S): masks x > numpy.percentile(x, percentile) (linear interpolation between order statistics; compare_stats.py:20-23 uses 75),
+ * 2 |A and B| / (|A| + |B|).  Any output may be NULL (its kernels are not run).  The group figures are the means over the pairs i < j. */
+int msm_dedrift_group_stats(msm_dedrift *d, double percentile, double *mean, double *stdev, double *cc, double *dice);
 
 #ifdef __cplusplus
 }

@@ -168,6 +168,14 @@ SIGNATURES = {
     "msm_rigid_run": (C.c_int, [_VP, C.c_int32, C.c_double, C.c_double, c_dp, C.c_int32, c_ip, c_dp]),
     "msm_rigid_kernel_ms": (C.c_int, [_VP, c_dp]),
     "msm_calculate_strains": (C.c_int, [_VP, c_dp, C.c_int32, C.c_double, c_dp, c_ip, c_dp]),
+    "msm_dedrift_create": (_VP, [_VP, _VP, C.c_int32]),
+    "msm_dedrift_destroy": (None, [_VP]),
+    "msm_dedrift_reset": (C.c_int, [_VP]),
+    "msm_dedrift_accumulate": (C.c_int, [_VP, _VP, c_dp, C.c_int32, c_ip, c_dp, c_dp]),
+    "msm_dedrift_finish": (C.c_int, [_VP, c_dp, c_dp]),
+    "msm_dedrift_correct": (C.c_int, [_VP, C.c_int32, _VP, c_dp, C.c_int32, c_dp, C.c_int32, c_dp, c_dp, c_dp, c_ip, c_dp]),
+    "msm_dedrift_set_map": (C.c_int, [_VP, C.c_int32, c_dp, C.c_int32]),
+    "msm_dedrift_group_stats": (C.c_int, [_VP, C.c_double, c_dp, c_dp, c_dp, c_dp]),
 }
 
 _lib = None

@@ -111,5 +111,27 @@ __device__ __forceinline__ double triangular_strain(const V3 o[3], const V3 f[3]
     return triangular_strain_from(strain_frame(o), f, mu, kappa, k_exp);
 }
 
+// The two invariants triangle_strain forms on the way to its energy (M/reg_tools.cpp:578-593): J, the area ratio of the deformed triangle to the
+// original, and R, the ratio of its major to its minor stretch.  Same frames and the same operations as triangular_strain_from up to that point.
+__device__ __forceinline__ void triangular_strain_JR(const StrainFrame &fr, const V3 f[3], double &J, double &R) {
+    const V3 nF = tri_normal(f[0], f[1], f[2]);
+    V3 t1, t2;
+    tangent_pair(nF, t1, t2);
+    const V3 d1 = fr.dswap ? t2 : t1, d2 = fr.dswap ? t1 : t2;
+    double B[3][2];
+    for (int i = 0; i < 3; ++i) {
+        B[i][0] = f[i].x * d1.x + f[i].y * d1.y + f[i].z * d1.z;
+        B[i][1] = f[i].x * d2.x + f[i].y * d2.y + f[i].z * d2.z;
+    }
+    const double c0c = B[1][0] - B[0][0], c1c = B[1][1] - B[0][1], c4c = B[2][0] - B[0][0], c5c = B[2][1] - B[0][1];
+    const double F00 = c0c * fr.i00 + c4c * fr.i10, F01 = c0c * fr.i01 + c4c * fr.i11;
+    const double F10 = c1c * fr.i00 + c5c * fr.i10, F11 = c1c * fr.i01 + c5c * fr.i11;
+    const double G[9] = {F00 * F00 + F10 * F10, F00 * F01 + F10 * F11, 0, F01 * F00 + F11 * F10, F01 * F01 + F11 * F11, 0, 0, 0, 1};
+    const double I1 = G[0] + G[4] + G[8];
+    J = sqrt(det3(G));
+    const double I1st = (I1 - 1.0) / J;
+    R = (I1st <= 2) ? 1.0 : 0.5 * (I1st + sqrt(I1st * I1st - 4));
+}
+
 
 }  // namespace msm

@@ -180,12 +180,12 @@ def save_ascii(path, xyz, tri, values=None):
     _write_ascii(path, xyz, tri, values)
 
 
-def _g(x):
-    """a float as std::ostream writes it by default (6 significant digits, %g)"""
-    return "%g" % float(np.float32(x))
+def _g(x, digits=6):
+    """a float as std::ostream writes it by default (6 significant digits, %g); 9 digits give the float back exactly"""
+    return "%.*g" % (digits, float(np.float32(x)))
 
 
-def save_dpv(path, xyz, values):
+def save_dpv(path, xyz, values, digits=6):
     """Mesh::save_dpv, R/mesh.cpp:707-741: `index x y z value` per vertex (indices below 100 zero-padded to three digits), first data row only"""
     xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
     val = np.atleast_2d(np.asarray(values, dtype=np.float64))[0]
@@ -193,7 +193,7 @@ def save_dpv(path, xyz, values):
         raise MeshIOError("Mesh::save_dpv, data and mesh dimensions do not agree")
     with open(path, "w") as f:
         for i, (p, v) in enumerate(zip(xyz, val)):
-            f.write("%s %s %s %s %s\n" % ("%03d" % i if i < 100 else str(i), _g(p[0]), _g(p[1]), _g(p[2]), _g(v)))
+            f.write("%s %s %s %s %s\n" % ("%03d" % i if i < 100 else str(i), _g(p[0], digits), _g(p[1], digits), _g(p[2], digits), _g(v, digits)))
 
 
 def load_dpv(path):
@@ -204,11 +204,11 @@ def load_dpv(path):
     return a[:, 1:4].copy(), a[:, 4][None, :].copy()
 
 
-def save_matrix(path, data):
+def save_matrix(path, data, digits=6):
     """Mesh::save_matrix, R/mesh.cpp:743-766: one line per data row, values separated (and followed) by a blank"""
     with open(path, "w") as f:
         for row in np.atleast_2d(np.asarray(data, dtype=np.float64)):
-            f.write("".join(_g(v) + " " for v in row) + "\n")
+            f.write("".join(_g(v, digits) + " " for v in row) + "\n")
 
 
 def load_matrix(path):
