@@ -249,6 +249,15 @@ int msm_mesh_unfold(msm_mesh *m, double radius, int32_t *passes, int32_t *first_
 /* [host] variance_normalise M/reg_tools.cpp:804-843: data D x V in place; excl (V values, > 0 keeps the vertex) or NULL.
  * The running mean / variance recurrence of the reference is serial per feature row, so it stays on the host. */
 int msm_variance_normalise(double *data, int32_t D, int32_t V, const double *excl);
+/* multivariate_histogram_normalization M/reg_tools.cpp:745-802 (--IN / --INc) on the GPU: every feature row of n_src source matrices (src: n_src x D x Vs)
+ * is matched to the same row of ONE target matrix (ref: D x Vt) through 256-bin histograms, whose statistics are computed once.  The reference
+ * hands the matching itself to FSL's MISCMATHS::Histogram (generate / generateCDF / match), which is not in its tree: the definition followed here is
+ * written down in DESIGN.md section 5.11 and restated in tests/histmatch_literal.py; agreement with FSL itself is unpinned.  A value is counted when it
+ * is finite and its mask is > 0; src_excl (optional: n_src x src_excl_rows x Vs) and ref_excl (optional: ref_excl_rows x Vt) are the EXCL meshes' data,
+ * row d of a mask serves feature row d when the mask has that many rows, row 0 otherwise (:764-767).  Counted source values become the target value at
+ * their quantile; the others, and rows without counted values or without a range on either side, stay as they are.  out: n_src x D x Vs (may be src). */
+int msm_histogram_match(msm_ctx *ctx, int32_t n_src, int32_t D, int32_t Vs, const double *src, const double *src_excl, int32_t src_excl_rows,
+                        int32_t Vt, const double *ref, const double *ref_excl, int32_t ref_excl_rows, double *out);
 /* [host] MCMC::optimise M/mcmc_opt.h:31-134 over the tables of msm_cost_unary_table (L x N) and msm_cost_triplet_table
  * (T x L x L x L): `iters` sweeps over the triplets, each proposing one label drawn from std::geometric_distribution(mcparam)
  * (std::mt19937 seeded with `seed`; the reference seeds from std::random_device) and keeping the cheapest of the eight

@@ -332,6 +332,16 @@ inline int unfold(Mesh &SOURCE, double RAD = 100.0, int *first_folded = nullptr)
 inline void variance_normalise(Matrix &DATA, int V, const std::vector<double> *EXCL = nullptr) {
     check(msm_variance_normalise(DATA.data(), (int32_t)(DATA.size() / V), V, EXCL ? EXCL->data() : nullptr));
 }
+// multivariate_histogram_normalization(IN, REF, EXCL_IN, EXCL_REF), M/reg_tools.cpp:745-802 (--IN / --INc), for n_src source matrices (srcs: n_src x D x
+// Vs, one after the other) against ONE target (ref: D x Vt) on the GPU, by the definition of DESIGN.md section 5.11; src_excl (n_src x src_rows x Vs) and
+// ref_excl (ref_rows x Vt) are the masks or null.  Returns the matched copy of srcs.
+inline Matrix histogram_match(Context &ctx, int n_src, int D, int Vs, const Matrix &srcs, int Vt, const Matrix &ref, const std::vector<double> *src_excl = nullptr,
+                              int src_rows = 0, const std::vector<double> *ref_excl = nullptr, int ref_rows = 0) {
+    Matrix out(srcs.size());
+    check(msm_histogram_match(ctx.handle(), n_src, D, Vs, srcs.data(), src_excl ? src_excl->data() : nullptr, src_rows, Vt, ref.data(),
+                              ref_excl ? ref_excl->data() : nullptr, ref_rows, out.data()));
+    return out;
+}
 // MCMC::optimise, M/mcmc_opt.h:31-134, over the tables of getUnaryCosts() (L x N) and getTCosts() (T x L x L x L)
 inline void mcmc_optimise(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
                           double dist_param, int mciters, uint64_t seed, std::vector<int32_t> &labeling) {

@@ -11,8 +11,8 @@
 // parser in Python; tests/test_cpp_config.py checks that the two agree.
 //
 // Reported instead of silently dropped: AFFINE / RIGID levels (listed in `skipped` unless levels_from_config(..., rigid = true) asks for them as
-// rigid levels), --IN / --INc (FSL's
-// histogram matching is not in the reference tree).  --excl / --cutthr are parsed into Config::excl / Config::cutthr and apply to the whole run: the
+// rigid levels), --IN / --INc (refused unless levels_from_config(..., &intensity) asks for the histogram matching of DESIGN.md section 5.11: FSL's own is not
+// in the reference tree, so agreement with it is unpinned).  --excl / --cutthr are parsed into Config::excl / Config::cutthr and apply to the whole run: the
 // caller hands them to run_multiresolutions / run_group_multiresolutions (exclusion_from_config), which refuse --excl together with both cost-function
 // weightings.  --regoption=5 (aMSM) needs the anatomical surfaces (command line: --inanat / --refanat):
 // levels_from_config(..., anat = true) says the caller has them.
@@ -188,13 +188,22 @@ inline Exclusion exclusion_from_config(const Config &c) {
     return e;
 }
 
+// --IN / --INc of `c` as M/mesh_registration.cpp:694-703 reads them: --INc decides both when it is set, --IN otherwise
+inline IntensityNorm intensity_from_config(const Config &c) {
+    IntensityNorm n;
+    n.on = c.INc || c.IN, n.cut = c.INc;
+    return n;
+}
+
 // the DISCRETE levels of `c` for data with D feature rows; skipped (optional): index and method of the levels that are not DISCRETE
 // anat: the caller has the anatomical surfaces a --regoption=5 (aMSM) run needs (they come from the command line: --inanat / --refanat)
 // rigid: AFFINE / RIGID levels come back as levels with LevelSpec::rigid set (data grid, smoothing, --it, --simval, --stepsize, --gradsampling:
 // what Rigid_cost_function::set_parameters reads, M/rigid_costfunction.cpp:50-58) instead of being listed in `skipped`
+// intensity (optional; opt-in): --IN / --INc are taken instead of refused and *intensity receives what the level loops need
 inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *varnorm = nullptr, std::vector<std::pair<int, std::string>> *skipped = nullptr,
-                                                 bool anat = false, bool rigid = false) {
-    if (c.IN || c.INc) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
+                                                 bool anat = false, bool rigid = false, IntensityNorm *intensity = nullptr) {
+    if (intensity) *intensity = intensity_from_config(c);
+    if ((c.IN || c.INc) && !intensity) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
     if (c.regoption == 4)  // M/mesh_registration.cpp:101-102
         throw ConfigError("--regoption 4 has been removed from newMSM. Use --regoption 3 for spherical mesh regularisation or --regoption 5 for anatomical mesh "
                           "regularisation.");

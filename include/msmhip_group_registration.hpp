@@ -138,11 +138,13 @@ struct GroupMultiresResult {
 //              control grid (project_CPgrid with the subject's index, M/mesh_registration.cpp:131-162), then run_discrete_opt (:70-118);
 //   at the end transform (:120-125).
 // meshes: per subject (xyz, tri), spheres of radius 100; datas: per subject D x V(mesh).  excl (--excl, --cutthr): every subject's exclusion mask in the
-// feature preparation of every level (level_features); it does not enter the cost function.
+// feature preparation of every level (level_features); it does not enter the cost function.  inorm (--IN / --INc): every later subject's data is histogram
+// matched to subject 0's after all are resampled and smoothed and before variance normalisation (finish_features: (S - 1) D rows against one target, one
+// call); inorm.cut makes the masks exist as --excl does.  The final resampling of a groupwise run has no matching (M/group_mesh_registration.cpp:127-133).
 inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::vector<std::pair<Points, Triangles>> &meshes, const std::vector<Matrix> &datas, int D,
                                                       const Points &template_xyz, const Triangles &template_tri, const std::vector<GroupLevelSpec> &levels,
                                                       bool varnorm, const std::vector<double> *mask = nullptr, PhaseClock *clock = nullptr,
-                                                      const Exclusion &excl = Exclusion()) {
+                                                      const Exclusion &excl = Exclusion(), const IntensityNorm &inorm = IntensityNorm()) {
     const int S = (int)meshes.size();
     if ((int)datas.size() != S) throw Error(MSM_ERR_INVALID, "featurespace::Initialize do not have the same number of datasets and surface meshes");  // M/featurespace.cpp:43-44
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "run_group_multiresolutions: no DISCRETE level");
@@ -155,8 +157,16 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
         auto [ico_xyz, ico_tri] = make_mesh_from_icosa(lv.data_order);
         Mesh ico(ctx, ico_xyz, ico_tri);
         std::vector<Matrix> feats;
-        for (int s = 0; s < S; ++s) {
-            feats.push_back(level_features(*in_mesh[(size_t)s], datas[(size_t)s], ico, lv.sigma_in, varnorm, excl, clock));
+        if (inorm.on || inorm.cut) {  // resample and smooth only: matching and variance normalisation follow when every subject's data is there
+            Exclusion masked = excl;
+            masked.on = excl.on || inorm.cut;
+            std::vector<std::vector<double>> masks((size_t)S);
+            for (int s = 0; s < S; ++s) feats.push_back(level_features(*in_mesh[(size_t)s], datas[(size_t)s], ico, lv.sigma_in, false, masked, clock, &masks[(size_t)s]));
+            finish_features(ctx, feats, masks, masked.on, D, ico.nvertices(), inorm, varnorm, clock);
+        } else {
+            for (int s = 0; s < S; ++s) {
+                feats.push_back(level_features(*in_mesh[(size_t)s], datas[(size_t)s], ico, lv.sigma_in, varnorm, excl, clock));
+            }
         }
         std::vector<Points> sph, cps_start;
         if (prev_regs.empty()) {
@@ -190,8 +200,10 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
 // The levels of a --groupwise run from a configuration (msmhip_config.hpp: parse_config), as Group_Mesh_registration reads it: every level DISCRETE
 // ("AFFINE/RIGID registration is not supported in groupwise mode.", M/group_mesh_registration.cpp:29-30), the optimiser HOCR (:87); the model has its own
 // regulariser, so --regoption is not looked at (the twin of newmsm_amd/config.py: levels_from_config(..., groupwise=True)).
-inline std::vector<GroupLevelSpec> group_levels_from_config(const Config &c, bool *varnorm = nullptr) {
-    if (c.IN || c.INc) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
+// intensity (optional; opt-in): --IN / --INc are taken instead of refused and *intensity receives what the level loop needs
+inline std::vector<GroupLevelSpec> group_levels_from_config(const Config &c, bool *varnorm = nullptr, IntensityNorm *intensity = nullptr) {
+    if (intensity) *intensity = intensity_from_config(c);
+    if ((c.IN || c.INc) && !intensity) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
     for (const std::string &m : c.opt)
         if (m == "RIGID" || m == "AFFINE") throw ConfigError("AFFINE/RIGID registration is not supported in groupwise mode.");
     if (c.dopt != "HOCR") throw ConfigError("Groupwise mode is only supported in the HOCR version of MSM.");

@@ -261,6 +261,11 @@ struct Exclusion {
     double lower = 0.0, upper = 0.0001;  // --cutthr
 };
 
+// --IN / --INc (levels_from_config(..., &intensity) opts in): on = _IN, cut = _cut, which --INc alone sets (M/mesh_registration.cpp:694-703)
+struct IntensityNorm {
+    bool on = false, cut = false;
+};
+
 // One data set of featurespace::initialise (M/featurespace.cpp:52-84) on a level's grid `ico`: metric_resample from its native mesh, smooth_data when
 // sigma > 0, variance_normalise when varnorm.  With excl.on the mask is create_exclusion of the native data over the cut range (1 = kept, 0 = every
 // feature inside it: the medial wall of real data); resampling and smoothing leave it out and each replaces the mask by its own on the grid
@@ -276,6 +281,29 @@ inline Matrix level_features(Mesh &mesh, const Matrix &data, Mesh &ico, double s
     if (varnorm) variance_normalise(f, ico.nvertices(), EXCL);
     if (mask_out) *mask_out = std::move(mask);
     return f;
+}
+
+// The tail of featurespace::initialise (M/featurespace.cpp:75-83) over data sets that level_features has resampled and smoothed (varnorm = false there):
+// with inorm.on every data set i >= 1 is histogram matched to data set 0 -- one call, the target's statistics computed once -- with the masks as they stand
+// after smoothing (masked: --excl or --INc), then variance_normalise of every data set when varnorm.  The reference's order is a quirk in a pairwise run,
+// whose data sets are (input, reference): there the REFERENCE data is matched to the INPUT data.  feats: D x V(ico) each.
+inline void finish_features(Context &ctx, std::vector<Matrix> &feats, const std::vector<std::vector<double>> &masks, bool masked, int D, int V,
+                            const IntensityNorm &inorm, bool varnorm, PhaseClock *clock) {
+    const size_t n = feats.size();
+    if (inorm.on && n > 1) {
+        Matrix srcs;
+        std::vector<double> src_masks;
+        for (size_t i = 1; i < n; ++i) {
+            srcs.insert(srcs.end(), feats[i].begin(), feats[i].end());
+            if (masked) src_masks.insert(src_masks.end(), masks[i].begin(), masks[i].end());
+        }
+        const Matrix matched = PhaseClock::timed(clock, "histogram_match", [&] {
+            return histogram_match(ctx, (int)n - 1, D, V, srcs, V, feats[0], masked ? &src_masks : nullptr, 1, masked ? &masks[0] : nullptr, 1);
+        });
+        for (size_t i = 1; i < n; ++i) feats[i].assign(matched.begin() + (long)((i - 1) * (size_t)D * V), matched.begin() + (long)(i * (size_t)D * V));
+    }
+    if (varnorm)
+        for (size_t i = 0; i < n; ++i) variance_normalise(feats[i], V, masked ? &masks[i] : nullptr);
 }
 
 // project_CPgrid (M/mesh_registration.cpp:131-162) for a level that starts from a warp of the input sphere, in_mesh -> moved_in: the warp of the
@@ -328,11 +356,14 @@ inline const char *excl_with_weightings_message() {
 // model that does not exist yet); its data grid is projected.
 // excl (--excl, --cutthr): masks in the feature preparation only.  They do not enter the cost function: combine_weighting (:234-248) returns ones
 // unless both weightings are given, and that combination is refused (excl_with_weightings_message).
+// inorm (--IN / --INc): in every level's feature preparation, RIGID levels included, the reference data is histogram matched to the input data after both
+// are resampled and smoothed and before variance normalisation (finish_features); inorm.cut makes the masks exist as --excl does (M/featurespace.cpp:61).
+// The final resampling is the caller's (transformed_data).
 inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, const Triangles &in_tri, const Matrix &in_data, const Points &ref_xyz,
                                            const Triangles &ref_tri, const Matrix &ref_data, int D, const std::vector<LevelSpec> &levels, bool varnorm,
                                            PhaseClock *clock = nullptr, const Points *in_anat = nullptr, const Points *ref_anat = nullptr,
                                            const Matrix *in_cfweight = nullptr, int in_cfrows = 0, const Matrix *ref_cfweight = nullptr, int ref_cfrows = 0,
-                                           const Points *trans_xyz = nullptr, const Exclusion &excl = Exclusion()) {
+                                           const Points *trans_xyz = nullptr, const Exclusion &excl = Exclusion(), const IntensityNorm &inorm = IntensityNorm()) {
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "run_multiresolutions: no DISCRETE level");
     if ((in_anat != nullptr) != (ref_anat != nullptr)) throw Error(MSM_ERR_INVALID, "Error: must supply both anatomical meshes or none");  // CLI/newmsm.cpp:41-43
     if (in_anat && (in_anat->size() != in_xyz.size() || ref_anat->size() != ref_xyz.size()))
@@ -348,9 +379,19 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
     for (const LevelSpec &lv : levels) {
         auto [ico_xyz, ico_tri] = make_mesh_from_icosa(lv.data_order);
         Mesh ico(ctx, ico_xyz, ico_tri);
-        Matrix feats[2];
-        for (int k = 0; k < 2; ++k)
-            feats[k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref, varnorm, excl, clock);
+        std::vector<Matrix> feats(2);
+        if (inorm.on || inorm.cut) {  // resample and smooth only: matching and variance normalisation follow when both data sets are there
+            Exclusion masked = excl;
+            masked.on = excl.on || inorm.cut;
+            std::vector<std::vector<double>> masks(2);
+            for (int k = 0; k < 2; ++k)
+                feats[(size_t)k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref, false, masked,
+                                                  clock, &masks[(size_t)k]);
+            finish_features(ctx, feats, masks, masked.on, D, ico.nvertices(), inorm, varnorm, clock);
+        } else {
+            for (int k = 0; k < 2; ++k)
+                feats[(size_t)k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref, varnorm, excl, clock);
+        }
         // project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         Points sph_in, cp_start, incurrent;
         const Points *moved_in = trans_xyz;
@@ -402,6 +443,22 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
     Mesh last(ctx, last_xyz, last_tri);
     res.sphere_reg = PhaseClock::timed(clock, "sphere_project_warp", [&] { return sphere_project_warp(in_xyz, last, sph_reg_prev); });
     return res;
+}
+
+// save_transformed_data without its file I/O (M/mesh_registration.cpp:358-395): the native input data resampled from the registered input sphere `moved`
+// onto the reference sphere.  excl.on: fresh masks from the native data keep the cut out of the resampling (:371-375).  inorm.on: the native input data is
+// first histogram matched to the native reference data (:376-380) -- this way round here, unlike in the levels' feature preparation -- with those masks
+// under --excl only (--INc's cut alone makes none here).
+inline Matrix transformed_data(Context &ctx, Mesh &moved, const Matrix &in_data, Mesh &target, const Matrix &ref_data, int D, const Exclusion &excl = Exclusion(),
+                               const IntensityNorm &inorm = IntensityNorm()) {
+    std::vector<double> in_excl;
+    if (excl.on) in_excl = create_exclusion(in_data, moved.nvertices(), excl.lower, excl.upper);
+    if (!inorm.on) return metric_resample(moved, in_data, target, excl.on ? &in_excl : nullptr);
+    std::vector<double> ref_excl;
+    if (excl.on) ref_excl = create_exclusion(ref_data, target.nvertices(), excl.lower, excl.upper);
+    const Matrix matched = histogram_match(ctx, 1, D, moved.nvertices(), in_data, target.nvertices(), ref_data, excl.on ? &in_excl : nullptr, 1,
+                                           excl.on ? &ref_excl : nullptr, 1);
+    return metric_resample(moved, matched, target, excl.on ? &in_excl : nullptr);
 }
 
 }  // namespace msmhip

@@ -95,6 +95,7 @@ SIGNATURES = {
     "msm_mesh_unfold": (C.c_int, [_VP, C.c_double, c_ip, c_ip]),
     "msm_mesh_prepare_search": (C.c_int, [_VP, C.c_int, c_ip]),
     "msm_variance_normalise": (C.c_int, [c_dp, C.c_int32, C.c_int32, c_dp]),
+    "msm_histogram_match": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, C.c_int32, C.c_int32, c_dp, c_dp, C.c_int32, c_dp]),
     "msm_mcmc_optimise": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_uint64, c_ip]),
     "msm_fusion_icm_step": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_pairwise_icm": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip]),

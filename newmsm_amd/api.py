@@ -466,6 +466,32 @@ def variance_normalise(data, excl=None):
     return out
 
 
+def histogram_match(ctx, src, ref, src_excl=None, ref_excl=None):
+    """multivariate_histogram_normalization (M/reg_tools.cpp:745-802; --IN / --INc) on the GPU: src (D x Vs, or n x D x Vs for n source matrices
+    against the one target) matched row by row to ref (D x Vt) through 256-bin histograms, by the definition of DESIGN.md section 5.11.  src_excl
+    (rows x Vs or Vs; n x rows x Vs for n sources) / ref_excl (rows x Vt or Vt): the EXCL masks, a value counts when it is finite and its mask
+    is > 0; row d of a mask serves feature row d when the mask has that many rows, row 0 otherwise.  Returns the matched copy, shaped like src."""
+    s, ps = _d(src)
+    shape = s.shape
+    s3 = s.reshape((1,) * (3 - s.ndim) + s.shape) if s.ndim < 3 else s
+    assert s3.ndim == 3
+    n, D, Vs = s3.shape
+    r, pr = _d(np.atleast_2d(ref))
+    assert r.ndim == 2 and r.shape[0] == D, "the target has %s rows, the sources %d" % (r.shape[:1], D)
+    pse, se_rows, pre, re_rows = None, 0, None, 0
+    if src_excl is not None:
+        se, pse = _d(src_excl)
+        se = se.reshape(n, -1, Vs)
+        se_rows = se.shape[1]
+    if ref_excl is not None:
+        re_, pre = _d(np.atleast_2d(ref_excl))
+        assert re_.shape[1] == r.shape[1]
+        re_rows = re_.shape[0]
+    out = np.empty(s3.shape)
+    check(lib().msm_histogram_match(ctx.h, n, D, Vs, ps, pse, se_rows, r.shape[1], pr, pre, re_rows, out.ctypes.data_as(c_dp)))
+    return out.reshape(shape)
+
+
 def mcmc_optimise(unary, tcosts, triplets, labeling, mcparam=0.8, iters=100, seed=0):
     """MCMC::optimise (M/mcmc_opt.h:31-134) over the unary (L x N) and triplet (T x L x L x L) tables; returns the new labeling."""
     U, pu = _d(unary)

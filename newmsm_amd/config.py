@@ -11,7 +11,8 @@ they become doubles, as `Utilities::Option<float>` / `std::vector<float>` do the
 0.007499999832361937, --shearmod=0.4 as 0.4000000059604645.
 
 Reported instead of silently dropped unless asked for: AFFINE / RIGID levels (`--opt=AFFINE,...`: `levels_from_config` lists them in
-`skipped`; with rigid=True it returns them as rigid levels).  Out of scope: --IN / --INc (FSL's histogram matching is not in the reference tree).
+`skipped`; with rigid=True it returns them as rigid levels), --IN / --INc (refused unless `levels_from_config(..., histmatch=True)` asks for the
+histogram matching of DESIGN.md section 5.11: FSL's own is not in the reference tree, so agreement with it is unpinned).
 --excl / --cutthr are parsed into cfg["excl"] / cfg["cutthr"] and apply to the whole run: the caller hands them to run_multiresolution /
 run_group_multiresolution (`run_options(cfg)`), which refuse --excl together with both cost-function weightings.  --regoption=5 (aMSM)
 needs the anatomical surfaces, which come from the command line (--inanat / --refanat): `levels_from_config(cfg, D, anat=True)` says the caller has them.
@@ -123,7 +124,7 @@ def parse_config(text):
     return cfg
 
 
-def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False):
+def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmatch=False):
     """The DISCRETE levels of `cfg` (parse_config's result) for data with D feature rows, as keyword sets of run_multiresolution, plus what
     applies to the whole run: returns (levels, run_kw, skipped) -- run_multiresolution(ops, ..., levels, **run_kw).  skipped: the (index,
     method) of levels that are not DISCRETE (the affine stage is outside the path).  fix_parameters_for_level + NonLinearSRegDiscreteModel::
@@ -132,8 +133,10 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False):
     26-52) whatever --regoption says: the checks on --regoption do not apply (Group_Mesh_registration::initialize_level has none).
     rigid: AFFINE / RIGID levels come back as levels too, dict(method="RIGID", data_order, sigma_in, sigma_ref, iters, simmeasure, stepsize,
     gradsampling) -- what Rigid_cost_function::set_parameters reads (M/rigid_costfunction.cpp:50-58) -- instead of being listed in `skipped`
-    (opt-in: the executables run them when MSMHIP_RIGID=on).  Groupwise runs refuse them whatever this says (group_registration.py)."""
-    if cfg["IN"] or cfg["INc"]:
+    (opt-in: the executables run them when MSMHIP_RIGID=on).  Groupwise runs refuse them whatever this says (group_registration.py).
+    histmatch: --IN / --INc are taken instead of refused (opt-in: the executables do when MSMHIP_HISTMATCH=on) and run_kw carries what the level
+    loops need: intensity (_IN) and cut (_cut: set by --INc alone, M/mesh_registration.cpp:694-703)."""
+    if (cfg["IN"] or cfg["INc"]) and not histmatch:
         raise ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available")
     if groupwise:
         pass
@@ -169,7 +172,10 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False):
                            sigma_ref=cfg["sigma_ref"][i], iters=cfg["it"][i], mciters=cfg["mciters"][i], mcparam=cfg["mcparam"], kind=kind,
                            simmeasure=cfg["simval"][i], rmode=rmode, rescale_labels=cfg["rescaleL"], optimiser=optimiser, cost_params=params,
                            anat_order=cfg["anatgrid"][i] if i < len(cfg["anatgrid"]) else cfg["CPgrid"][i] + 2))
-    return levels, dict(varnorm=cfg["VN"]), skipped
+    run_kw = dict(varnorm=cfg["VN"])
+    if histmatch:  # :694-703: --INc decides both when it is set, --IN otherwise
+        run_kw.update(intensity=bool(cfg["INc"] or cfg["IN"]), cut=bool(cfg["INc"]))
+    return levels, run_kw, skipped
 
 
 def run_options(cfg):

@@ -15,7 +15,7 @@ result is not the reference's optimum."""
 import numpy as np
 
 from . import api
-from .registration import ProductOps, apply_labeling, level_features, project_start
+from .registration import ProductOps, apply_labeling, finish_features, level_features, project_start
 
 
 class ProductGroupOps(ProductOps):
@@ -147,7 +147,7 @@ def run_group_level(ops, template_xyz, template_tri, data_xyz, data_tri, feats, 
 
 
 def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, levels, *, mask=None, varnorm=False, fixnan=False, timings=None,
-                              labelings_out=None, excl=False, cutthr=(0.0, 0.0001), **level_kw):
+                              labelings_out=None, excl=False, cutthr=(0.0, 0.0001), intensity=False, cut=False, **level_kw):
     """Group_Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50 over the overrides of M/group_mesh_registration.cpp) without
     file I/O:
 
@@ -161,7 +161,10 @@ def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, le
     meshes: per subject (xyz, tri), spheres of radius 100; datas: per subject D x V(mesh); template_*: the sphere the patches are compared on
     (--template); levels: dicts as config.levels_from_config builds them (data_order, cp_order, sg_order, sigma_in, iters, simmeasure,
     cost_params["lambda_"]); mask: V(template) weights (--mask); excl, cutthr (--excl, --cutthr): every subject's exclusion mask from the cut
-    thresholds in the feature preparation of every level (registration.level_features) -- it does not enter the cost function.  Returns (registered input spheres,
+    thresholds in the feature preparation of every level (registration.level_features) -- it does not enter the cost function.  intensity, cut (--IN /
+    --INc): every later subject's data is histogram matched to subject 0's after all are resampled and smoothed and before variance normalisation
+    (registration.finish_features: (S - 1) D rows against one target, one call); cut makes the masks exist as --excl does.  The final resampling of
+    a groupwise run has no matching (M/group_mesh_registration.cpp:127-133).  Returns (registered input spheres,
     per-level S x V x 3 registered data grids, per-level energies)."""
     import time
 
@@ -183,8 +186,12 @@ def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, le
         ico_xyz, ico_tri = ops.icosphere(lv["data_order"])
         ico = ops.mesh(ico_xyz, ico_tri)
         feats = []
-        for s in range(S):
-            feats.append(level_features(ops, timed, in_mesh[s], datas[s], ico, lv.get("sigma_in", 0.0), varnorm, None, excl, cutthr)[0])
+        if intensity or cut:
+            prepared = [level_features(ops, timed, in_mesh[s], datas[s], ico, lv.get("sigma_in", 0.0), False, None, excl or cut, cutthr) for s in range(S)]
+            feats = finish_features(ops, timed, [p[0] for p in prepared], [p[1] for p in prepared], intensity, varnorm)
+        else:
+            for s in range(S):
+                feats.append(level_features(ops, timed, in_mesh[s], datas[s], ico, lv.get("sigma_in", 0.0), varnorm, None, excl, cutthr)[0])
         cps_start = None
         if prev_regs is None:
             sph = [ico_xyz for _ in range(S)]  # ALL_SPH_REG.resize(num_subjects, SPH_orig), :60-61

@@ -98,6 +98,13 @@ class ProductOps:
     def create_exclusion(self, data, thrl, thru):
         return api.create_exclusion(data, thrl, thru)
 
+    def histogram_match(self, srcs, ref, src_excls=None, ref_excl=None):
+        """multivariate_histogram_normalization (--IN / --INc) of every matrix of the list `srcs` (equal shapes) against the one target `ref`, with
+        their masks (a list like srcs, and the target's; both or none): ONE call, the target's statistics are computed once.  Returns the list of
+        matched copies."""
+        out = api.histogram_match(self.ctx, np.stack([np.atleast_2d(s) for s in srcs]), ref, None if src_excls is None else np.stack(src_excls), ref_excl)
+        return list(out)
+
     def nearest_neighbour(self, mesh, data, q_xyz):
         return api.nearest_neighbour_interpolation(mesh, data, q_xyz)
 
@@ -280,6 +287,35 @@ def level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot=None, excl=
     return f, mask
 
 
+def finish_features(ops, timed, feats, masks, intensity, varnorm):
+    """The tail of featurespace::initialise (M/featurespace.cpp:75-83) over data sets that level_features has resampled and smoothed (varnorm=False):
+    with intensity (--IN / --INc) every data set i >= 1 is histogram matched to data set 0, with the masks as they stand after smoothing (None
+    without --excl / --INc); then variance_normalise of every data set when varnorm.  The reference's order is a quirk in a pairwise run, whose data
+    sets are (input, reference): there the REFERENCE data is matched to the INPUT data.  Returns the list of feature matrices."""
+    feats = list(feats)
+    if intensity and len(feats) > 1:
+        masked = masks[0] is not None
+        feats[1:] = timed("histogram_match", ops.histogram_match, feats[1:], feats[0], list(masks[1:]) if masked else None, masks[0])
+    if varnorm:
+        feats = [ops.variance_normalise(f) if m is None else ops.variance_normalise(f, excl=m) for f, m in zip(feats, masks)]
+    return feats
+
+
+def transformed_data(ops, moved_mesh, in_data, ref_mesh, ref_data=None, *, excl=False, cutthr=(0.0, 0.0001), intensity=False):
+    """save_transformed_data without its file I/O (M/mesh_registration.cpp:358-395): the native input data resampled from the registered input sphere
+    (moved_mesh) onto the reference sphere.  excl (--excl): fresh masks from the native data keep the cut out of the resampling (:371-375).
+    intensity (--IN / --INc): the native input data is first histogram matched to the native reference data (:376-380) -- this way round here, unlike
+    in the levels' feature preparation -- with those masks under --excl only (--INc's cut alone makes none here).  Without intensity the ops are
+    called exactly as before the option existed."""
+    in_mask = ops.create_exclusion(in_data, cutthr[0], cutthr[1]) if excl else None
+    if intensity:
+        ref_mask = ops.create_exclusion(ref_data, cutthr[0], cutthr[1]) if excl else None
+        in_data = ops.histogram_match([in_data], ref_data, [in_mask] if excl else None, ref_mask)[0]
+    if excl:
+        return ops.metric_resample(moved_mesh, in_data, ref_mesh, excl=in_mask)[0]
+    return ops.metric_resample(moved_mesh, in_data, ref_mesh)
+
+
 def project_start(ops, timed, ico_xyz, ico_tri, in_mesh, moved_in, cp_order):
     """project_CPgrid (M/mesh_registration.cpp:131-162) for a level that starts from a warp of the input sphere, in_mesh -> moved_in: the warp of
     the previous level carried to the input sphere (`incurrent`) or, at the first level, the --trans sphere.  The level's data grid is carried
@@ -456,7 +492,7 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
 
 def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data, levels, *, varnorm=False, timings=None, in_cfweight=None,
                         ref_cfweight=None, labelings_out=None, in_anat=None, ref_anat=None, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001),
-                        **level_kw):
+                        intensity=False, cut=False, **level_kw):
     """Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE and RIGID levels without file I/O:
 
     per level  featurespace::initialise (M/featurespace.cpp:39-86: metric_resample of both data sets onto the level's
@@ -482,6 +518,10 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
     excl, cutthr (--excl, --cutthr): exclusion masks from the cut thresholds in every level's feature preparation (level_features).  They do not
     enter the cost function: combine_weighting (M/mesh_registration.cpp:234-248) returns ones unless both weightings are given, and with both,
     downsample_cfweighting (:334-350) would read the level-grid mask at vertex numbers of the weightings' own meshes -- refused.
+    intensity, cut (--IN / --INc; config.levels_from_config(..., histmatch=True)): in every level's feature preparation, RIGID levels included, the
+    reference data is histogram matched to the input data after both are resampled and smoothed and before variance normalisation (finish_features:
+    the reference's order, a quirk); cut (--INc) makes the exclusion masks exist as --excl does (M/featurespace.cpp:61).  The final resampling is
+    the caller's (transformed_data).
     Returns (sphere_reg, per-level registered data grids, per-level energies)."""
     if excl and in_cfweight is not None and ref_cfweight is not None:
         raise ValueError(EXCL_WITH_WEIGHTINGS)
@@ -509,24 +549,31 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
                 else:
                     ref_data = arr
         return _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data, levels, varnorm, in_cfweight, ref_cfweight, labelings_out, in_anat,
-                           ref_anat, ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz, excl, cutthr)
+                           ref_anat, ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz, excl, cutthr, intensity, cut)
     finally:
         for t in pins:
             ops.unpin(t)
 
 
 def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data, levels, varnorm, in_cfweight, ref_cfweight, labelings_out, in_anat, ref_anat,
-                ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001)):
+                ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001), intensity=False, cut=False):
     """the level loop of run_multiresolution (see there)"""
     for lv in levels:
         rigid = lv.get("method") == "RIGID"
         ico_xyz, ico_tri = ops.icosphere(lv["data_order"])
         ico = ops.mesh(ico_xyz, ico_tri)
-        feats = []
+        feats, masks = [], []
         for mesh, data, sigma, slot in ((in_mesh, in_data, lv.get("sigma_in", 0.0), "in"), (ref_mesh, ref_data, lv.get("sigma_ref", 0.0), "ref")):
             # (a level's matrices are consumed -- uploaded by the cost function and the target mesh -- before the next level asks for its own: the
             # result slots are reused from level to level)
-            feats.append(level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot, excl, cutthr)[0])
+            if intensity or cut:  # resample and smooth only: matching and variance normalisation follow when both data sets are there
+                f, m = level_features(ops, timed, mesh, data, ico, sigma, False, slot, excl or cut, cutthr)
+                masks.append(m)
+            else:
+                f = level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot, excl, cutthr)[0]
+            feats.append(f)
+        if intensity or cut:
+            feats = finish_features(ops, timed, feats, masks, intensity, varnorm)
         # project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         if sph_reg_prev is None:
             moved_in = trans_xyz

@@ -176,6 +176,12 @@ void note_skipped(const std::vector<std::pair<int, std::string>> &skipped) {
         std::cerr << "newmsm: level " << sk.first + 1 << " (--opt=" << sk.second << ") is outside the path (the affine stage stays on the CPU in newmsm): skipped" << std::endl;
 }
 
+// MSMHIP_HISTMATCH=on: --IN / --INc run (histogram matching on the GPU) instead of ending the run with an error
+bool histmatch_enabled() {
+    const char *env = std::getenv("MSMHIP_HISTMATCH");
+    return env && std::string(env) == "on";
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
     for (const char *flag : {"inmesh", "indata", "refdata"})
         if (o.get(flag).empty()) throw Error(MSM_ERR_INVALID, std::string("newmsm: --") + flag + " is required");
@@ -192,7 +198,8 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const char *rigid_env = std::getenv("MSMHIP_RIGID");  // "on": AFFINE / RIGID levels run (Rigid_cost_function on the GPU) instead of being skipped
     const bool rigid = rigid_env && std::string(rigid_env) == "on";
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
-    const std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid);
+    IntensityNorm inorm;  // --IN / --INc: taken when MSMHIP_HISTMATCH=on, refused otherwise
+    const std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr);
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
@@ -216,16 +223,16 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
         std::cout << "This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,
                                                     anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr,
-                                                    o.get("trans").empty() ? nullptr : &trans, excl);
+                                                    o.get("trans").empty() ? nullptr : &trans, excl, inorm);
     const std::string out = o.get("out");
     io::save_surface(out + "sphere.reg" + fmt.surf, res.sphere_reg, itri);  // transform
     const Triangles last_tri = make_mesh_from_icosa(levels.back().data_order).second;
     io::save_surface(out + "sphere.LR.reg" + fmt.surf, res.level_reg.back(), last_tri);  // saveSPH_reg
     Mesh moved(ctx, res.sphere_reg, itri), target(ctx, rxyz, rtri);
-    // save_transformed_data (:358-383): with --excl a fresh mask from the native input data keeps the cut out of the resampling
-    std::vector<double> in_excl;
-    if (excl.on) in_excl = create_exclusion(idata, moved.nvertices(), excl.lower, excl.upper);
-    save_data(out + "transformed_and_reprojected" + fmt.data, rxyz, metric_resample(moved, idata, target, excl.on ? &in_excl : nullptr), D);
+    // save_transformed_data (:358-383): with --excl a fresh mask from the native input data keeps the cut out of the resampling; with --IN / --INc the
+    // native input data is matched to the native reference data first
+    if (inorm.on && o.has("verbose")) std::cout << "Intensity normalise." << std::endl;
+    save_data(out + "transformed_and_reprojected" + fmt.data, rxyz, transformed_data(ctx, moved, idata, target, rdata, D, excl, inorm), D);
     if (anat) {  // save_transformed_data's aMSM outputs (:397-407), GIFTI whatever -f says
         const Points anat_reg = project_anatomical_mesh(moved, target, ref_anat);
         io::save_surface(out + "anat.reg.surf.gii", anat_reg, itri);
@@ -251,7 +258,8 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("trans")) std::cerr << "newmsm: --trans is not used in groupwise mode: ignored" << std::endl;
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
     bool varnorm = false;
-    const std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm);  // refuses AFFINE / RIGID levels and optimisers other than HOCR
+    IntensityNorm inorm;
+    const std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm, histmatch_enabled() ? &inorm : nullptr);  // refuses AFFINE / RIGID levels and optimisers other than HOCR
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
     std::vector<std::pair<Points, Triangles>> meshes;
     for (size_t k = 0; k < mesh_files.size(); ++k) {
@@ -280,7 +288,7 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("verbose"))
         std::cout << "This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     const GroupMultiresResult res = run_group_multiresolutions(ctx, meshes, datas, D, txyz, ttri, levels, varnorm, mask.empty() ? nullptr : &mask, nullptr,
-                                                               exclusion_from_config(cfg));
+                                                               exclusion_from_config(cfg), inorm);
     const Triangles last_tri = make_mesh_from_icosa(levels.back().data_order).second;
     Mesh target(ctx, txyz, ttri);
     const std::string out = o.get("out");

@@ -37,7 +37,8 @@ resampled from its registered sphere onto the TEMPLATE: without a mask, M/group_
 on stderr (CLI/newmsm.cpp never hands it to a groupwise run).
 
 Outside the path and reported instead of silently dropped: AFFINE / RIGID levels (skipped with a note on stderr unless MSMHIP_RIGID=on, which runs
-them), --IN / --INc, --excl together with both weightings; the
+them), --IN / --INc (refused unless MSMHIP_HISTMATCH=on, which runs the histogram matching of DESIGN.md section 5.11 on the GPU: in every level's feature
+preparation and, pairwise, before the final resampling), --excl together with both weightings; the
 binary solve of --dopt=HOCR / FastPD is a stand-in (iterated conditional modes: FastPD and ELC are licence-restricted and FSL-bound), so a run
 exercises the path exactly as newmsm would but its labelings are not HOCR's.
 """
@@ -121,8 +122,14 @@ def rigid_enabled():
     return os.environ.get("MSMHIP_RIGID", "") == "on"
 
 
+def histmatch_enabled():
+    """MSMHIP_HISTMATCH=on: --IN / --INc run (histogram matching on the GPU) instead of ending the run with an error"""
+    return os.environ.get("MSMHIP_HISTMATCH", "") == "on"
+
+
 def discrete_levels(cfg, D, anat=False, groupwise=False):
-    levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise)
+    levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
+                                                        **(dict(histmatch=True) if histmatch_enabled() else {}))
     for index, method in skipped:
         print("register_files.py: level %d (--opt=%s) is outside the path (the affine stage stays on the CPU in newmsm): skipped" % (index + 1, method), file=sys.stderr)
     if not levels:
@@ -214,10 +221,11 @@ def main(argv):
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])
     meshio.save_surface(out + "sphere.LR.reg" + surf_ext, level_regs[-1], last_tri)                 # saveSPH_reg
     moved, target = M.Mesh(ctx, reg, itri), M.Mesh(ctx, rxyz, rtri)
-    if excl["excl"]:  # save_transformed_data (:371-383): a fresh mask from the native input data keeps the cut out of the resampling
-        resampled = M.metric_resample(moved, idata, target, excl=M.create_exclusion(idata, *excl["cutthr"]))[0]
-    else:
-        resampled = M.metric_resample(moved, idata, target)
+    # save_transformed_data (:371-383): with --excl a fresh mask from the native input data keeps the cut out of the resampling; with --IN / --INc the
+    # native input data is matched to the native reference data first
+    if run_kw.get("intensity") and a.verbose:
+        print("Intensity normalise.")
+    resampled = registration.transformed_data(registration.ProductOps(ctx), moved, idata, target, rdata, intensity=run_kw.get("intensity", False), **excl)
     save_data(out + "transformed_and_reprojected" + data_ext, rxyz, resampled)
     if a.inanat:  # save_transformed_data's aMSM outputs (:397-407), GIFTI whatever -f says
         anat_reg = M.project_anatomical_mesh(moved, target, cfw["ref_anat"])
