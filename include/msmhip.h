@@ -565,6 +565,23 @@ int msm_dedrift_set_map(msm_dedrift *d, int32_t subject, const double *map, int3
  * 2 |A and B| / (|A| + |B|).  Any output may be NULL (its kernels are not run).  The group figures are the means over the pairs i < j. */
 int msm_dedrift_group_stats(msm_dedrift *d, double percentile, double *mean, double *stdev, double *cc, double *dice);
 
+/* ------------------------------------------------------------------------------------------------
+ * after a cohort has been registered to one template, subject by subject (gMSM_scripts/newMSM_HCP_to_template_v2.sh, run_HCP_to_template_v2.sh,
+ * gMSM_tutorial/typical_MSM.sh; get_group_stats.py, compare_stats.py): the distortion maps and their summary without a dedrift handle, a mesh
+ * handle, a search or a tree.
+ * ---------------------------------------------------------------------------------------------- */
+/* wb_command -surface-distortion -local-affine-method -log2 by the definition of msm_dedrift_correct's distortion, for S
+ * deformed copies (final_xyz: S x 3 x V SoA each) of ONE original sphere (orig_xyz 3 x V SoA, tri 3 x T SoA): per triangle J and R as triangle_strain
+ * forms them, each triangle evaluated once per copy; per vertex the plain mean over its incident triangles in trID order of log2 J (row 0, areal)
+ * and log2 R (row 1, shape), 0 for a vertex without a triangle.  out: S x 2 x V.  One launch per step serves all S copies.  S <= 0, V <= 0 or a
+ * triangle index outside [0, V): MSM_ERR_INVALID, nothing is launched. */
+int msm_surface_distortion(msm_ctx *ctx, const double *orig_xyz, const int32_t *tri, int32_t V, int32_t T, const double *final_xyz, int32_t S, double *out);
+/* the distortion summary of compare_stats.py over |x[i]|, i < n: *mean (one sum of fixed shape: two calls give the same bits), *max, and for every
+ * percentiles[q] in [0, 100] values[q] = numpy.percentile(|x|, percentiles[q]) (linear interpolation between the two order statistics, which a radix
+ * select over an integer key finds across workgroups; integer counters only).  A NaN anywhere makes every output NaN, as numpy does; infinities are
+ * outside the contract.  mean / max may be NULL; np may be 0 (at most 16).  n <= 0, np < 0 or a percentile outside [0, 100]: MSM_ERR_INVALID. */
+int msm_abs_summary(msm_ctx *ctx, const double *x, int64_t n, const double *percentiles, int32_t np, double *mean, double *max, double *values);
+
 #ifdef __cplusplus
 }
 #endif

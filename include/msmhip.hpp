@@ -342,6 +342,30 @@ inline Matrix histogram_match(Context &ctx, int n_src, int D, int Vs, const Matr
                               ref_excl ? ref_excl->data() : nullptr, ref_rows, out.data()));
     return out;
 }
+// msm_surface_distortion: the distortion maps (S x 2 x V: log2 J, log2 R per vertex) of the deformed copies `finals` of one sphere, in one call
+inline Matrix surface_distortion(Context &ctx, const Points &orig_xyz, const Triangles &tri, const std::vector<Points> &finals) {
+    const int32_t V = (int32_t)(orig_xyz.size() / 3), T = (int32_t)(tri.size() / 3), S = (int32_t)finals.size();
+    std::vector<double> fin;
+    for (const Points &f : finals) {
+        if (f.size() != orig_xyz.size()) throw Error(MSM_ERR_INVALID, "surface_distortion: a deformed copy has another vertex count");
+        const std::vector<double> s = to_soa(f);
+        fin.insert(fin.end(), s.begin(), s.end());
+    }
+    Matrix out((size_t)S * 2 * (size_t)V);
+    check(msm_surface_distortion(ctx.handle(), to_soa(orig_xyz).data(), tri_to_soa(tri).data(), V, T, fin.data(), S, out.data()));
+    return out;
+}
+// msm_abs_summary: mean, maximum and numpy.percentile's values of |x|
+struct AbsSummary {
+    double mean = 0.0, max = 0.0;
+    std::vector<double> values;
+};
+inline AbsSummary abs_summary(Context &ctx, const Matrix &x, const std::vector<double> &percentiles) {
+    AbsSummary s;
+    s.values.assign(percentiles.size(), 0.0);
+    check(msm_abs_summary(ctx.handle(), x.data(), (int64_t)x.size(), percentiles.data(), (int32_t)percentiles.size(), &s.mean, &s.max, s.values.data()));
+    return s;
+}
 // MCMC::optimise, M/mcmc_opt.h:31-134, over the tables of getUnaryCosts() (L x N) and getTCosts() (T x L x L x L)
 inline void mcmc_optimise(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
                           double dist_param, int mciters, uint64_t seed, std::vector<int32_t> &labeling) {

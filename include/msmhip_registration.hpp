@@ -283,6 +283,20 @@ inline Matrix level_features(Mesh &mesh, const Matrix &data, Mesh &ico, double s
     return f;
 }
 
+// The reference side of every level's feature preparation, prepared once for many registrations against one reference: per level the output of
+// level_features for the reference data (resampled, smoothed, variance normalised unless --IN / --INc postpone that) and the level-grid mask.  It depends
+// on the reference, the level schedule, --excl / --cutthr and --INc, not on the subject: one cache serves runs that agree in those.  Filled on first use
+// and read afterwards; the entries are vectors the cache owns.  One cache serves one thread at a time.
+struct ReferenceCache {
+    struct Entry {
+        bool filled = false;
+        Matrix features;
+        std::vector<double> mask;
+    };
+    std::vector<Entry> levels;
+    int hits = 0, fills = 0;
+};
+
 // The tail of featurespace::initialise (M/featurespace.cpp:75-83) over data sets that level_features has resampled and smoothed (varnorm = false there):
 // with inorm.on every data set i >= 1 is histogram matched to data set 0 -- one call, the target's statistics computed once -- with the masks as they stand
 // after smoothing (masked: --excl or --INc), then variance_normalise of every data set when varnorm.  The reference's order is a quirk in a pairwise run,
@@ -359,11 +373,15 @@ inline const char *excl_with_weightings_message() {
 // inorm (--IN / --INc): in every level's feature preparation, RIGID levels included, the reference data is histogram matched to the input data after both
 // are resampled and smoothed and before variance normalisation (finish_features); inorm.cut makes the masks exist as --excl does (M/featurespace.cpp:61).
 // The final resampling is the caller's (transformed_data).
+// ref_cache (optional): the reference data's level_features output is taken from it, and put there by the first run that needs it, instead of being
+// computed at every level of every run; everything after it (finish_features, the level's target mesh) stays this run's own.  Without it every call is
+// what it was before the argument existed.
 inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, const Triangles &in_tri, const Matrix &in_data, const Points &ref_xyz,
                                            const Triangles &ref_tri, const Matrix &ref_data, int D, const std::vector<LevelSpec> &levels, bool varnorm,
                                            PhaseClock *clock = nullptr, const Points *in_anat = nullptr, const Points *ref_anat = nullptr,
                                            const Matrix *in_cfweight = nullptr, int in_cfrows = 0, const Matrix *ref_cfweight = nullptr, int ref_cfrows = 0,
-                                           const Points *trans_xyz = nullptr, const Exclusion &excl = Exclusion(), const IntensityNorm &inorm = IntensityNorm()) {
+                                           const Points *trans_xyz = nullptr, const Exclusion &excl = Exclusion(), const IntensityNorm &inorm = IntensityNorm(),
+                                           ReferenceCache *ref_cache = nullptr) {
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "run_multiresolutions: no DISCRETE level");
     if ((in_anat != nullptr) != (ref_anat != nullptr)) throw Error(MSM_ERR_INVALID, "Error: must supply both anatomical meshes or none");  // CLI/newmsm.cpp:41-43
     if (in_anat && (in_anat->size() != in_xyz.size() || ref_anat->size() != ref_xyz.size()))
@@ -376,22 +394,32 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
     MultiresResult res;
     Points sph_reg_prev;
     int prev_order = -1;
+    if (ref_cache && ref_cache->levels.size() < levels.size()) ref_cache->levels.resize(levels.size());
+    size_t li = 0;
     for (const LevelSpec &lv : levels) {
         auto [ico_xyz, ico_tri] = make_mesh_from_icosa(lv.data_order);
         Mesh ico(ctx, ico_xyz, ico_tri);
         std::vector<Matrix> feats(2);
-        if (inorm.on || inorm.cut) {  // resample and smooth only: matching and variance normalisation follow when both data sets are there
-            Exclusion masked = excl;
-            masked.on = excl.on || inorm.cut;
-            std::vector<std::vector<double>> masks(2);
-            for (int k = 0; k < 2; ++k)
-                feats[(size_t)k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref, false, masked,
-                                                  clock, &masks[(size_t)k]);
-            finish_features(ctx, feats, masks, masked.on, D, ico.nvertices(), inorm, varnorm, clock);
-        } else {
-            for (int k = 0; k < 2; ++k)
-                feats[(size_t)k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref, varnorm, excl, clock);
+        std::vector<std::vector<double>> masks(2);
+        const bool postponed = inorm.on || inorm.cut;  // resample and smooth only: matching and variance normalisation follow when both data sets are there
+        Exclusion masked = excl;
+        masked.on = excl.on || (postponed && inorm.cut);
+        ReferenceCache::Entry *entry = ref_cache ? &ref_cache->levels[li] : nullptr;
+        ++li;
+        for (int k = 0; k < 2; ++k) {
+            if (k == 1 && entry && entry->filled) {
+                feats[1] = entry->features, masks[1] = entry->mask;
+                ++ref_cache->hits;
+                continue;
+            }
+            feats[(size_t)k] = level_features(k == 0 ? in_mesh : ref_mesh, k == 0 ? in_data : ref_data, ico, k == 0 ? lv.sigma_in : lv.sigma_ref,
+                                              postponed ? false : varnorm, masked, clock, &masks[(size_t)k]);
+            if (k == 1 && entry) {
+                entry->features = feats[1], entry->mask = masks[1], entry->filled = true;
+                ++ref_cache->fills;
+            }
         }
+        if (postponed) finish_features(ctx, feats, masks, masked.on, D, ico.nvertices(), inorm, varnorm, clock);
         // project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         Points sph_in, cp_start, incurrent;
         const Points *moved_in = trans_xyz;

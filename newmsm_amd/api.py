@@ -492,6 +492,31 @@ def histogram_match(ctx, src, ref, src_excl=None, ref_excl=None):
     return out.reshape(shape)
 
 
+def surface_distortion(ctx, orig_xyz, tri, final_xyz):
+    """msm_surface_distortion: wb_command -surface-distortion -local-affine-method -log2 by the definition of DESIGN.md section 5.10 for S deformed
+    copies of one sphere in one call.  orig_xyz (V, 3), tri (T, 3), final_xyz (V, 3) or (S, V, 3).  Returns (2, V) or (S, 2, V): row 0 the areal
+    distortion (mean over a vertex's triangles of log2 J), row 1 the shape distortion (log2 R); 0 for a vertex without a triangle."""
+    x, px = _soa(orig_xyz)
+    t, pt = _tri_soa(tri)
+    f = np.asarray(final_xyz, dtype=np.float64)
+    single = f.ndim == 2
+    f = f.reshape(-1, x.shape[1], 3) if f.size else f.reshape(0, x.shape[1], 3)
+    fs = np.ascontiguousarray(f.transpose(0, 2, 1))  # S x 3 x V
+    out = np.zeros((max(len(fs), 1), 2, x.shape[1]))
+    check(lib().msm_surface_distortion(ctx.h, px, pt, x.shape[1], t.shape[1], fs.ctypes.data_as(c_dp), len(fs), out.ctypes.data_as(c_dp)))
+    return out[0] if single else out
+
+
+def abs_summary(ctx, x, percentiles=()):
+    """msm_abs_summary over |x| of all values of x: (mean, max, values) with values[q] = numpy.percentile(|x|, percentiles[q]) (linear interpolation)."""
+    a, pa = _d(np.asarray(x, dtype=np.float64).ravel())
+    p, pp = _d(np.asarray(percentiles, dtype=np.float64).ravel())
+    mean, mx = C.c_double(0.0), C.c_double(0.0)
+    values = np.zeros(max(len(p), 1))
+    check(lib().msm_abs_summary(ctx.h, pa, a.size, pp, len(p), C.byref(mean), C.byref(mx), values.ctypes.data_as(c_dp)))
+    return mean.value, mx.value, values[:len(p)]
+
+
 def mcmc_optimise(unary, tcosts, triplets, labeling, mcparam=0.8, iters=100, seed=0):
     """MCMC::optimise (M/mcmc_opt.h:31-134) over the unary (L x N) and triplet (T x L x L x L) tables; returns the new labeling."""
     U, pu = _d(unary)

@@ -11,6 +11,7 @@ libmsmhip through the C ABI; the parity tests pass an oracle-backed object with 
 differ in nothing but the implementation of the path (tests/helpers.py, tests/test_gpu_registration.py).
 """
 import sys
+import threading
 import time
 
 import numpy as np
@@ -287,6 +288,37 @@ def level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot=None, excl=
     return f, mask
 
 
+class ReferenceCache:
+    """The reference side of every level's feature preparation, prepared once for many registrations against one reference (cohort.py): per level
+    the output of level_features for the reference data -- resampled, smoothed, variance normalised unless --IN / --INc postpone that, and the
+    level-grid mask.  It depends on the reference, the level schedule, --excl / --cutthr and --INc, not on the subject: one cache serves runs that
+    agree in those (the key of an entry holds them, so a run that differs computes its own).  Filled on first use and read afterwards; it owns its
+    arrays -- copies on the host, never views of a context's reused result slot -- and is safe to share between threads, each with its own ops."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._entries = {}  # key -> [lock, (features, mask) or None]
+        self.hits = 0
+        self.fills = 0
+
+    def get(self, key, compute):
+        with self._lock:
+            entry = self._entries.setdefault(key, [threading.Lock(), None])
+        with entry[0]:  # a second thread that needs the entry being filled waits for it
+            if entry[1] is None:
+                f, m = compute()
+                entry[1] = (np.array(f, dtype=np.float64, order="C"), None if m is None else np.array(m, dtype=np.float64, order="C"))
+                for a in entry[1]:
+                    if a is not None:
+                        a.setflags(write=False)
+                with self._lock:
+                    self.fills += 1
+            else:
+                with self._lock:
+                    self.hits += 1
+            return entry[1]
+
+
 def finish_features(ops, timed, feats, masks, intensity, varnorm):
     """The tail of featurespace::initialise (M/featurespace.cpp:75-83) over data sets that level_features has resampled and smoothed (varnorm=False):
     with intensity (--IN / --INc) every data set i >= 1 is histogram matched to data set 0, with the masks as they stand after smoothing (None
@@ -492,7 +524,7 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
 
 def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data, levels, *, varnorm=False, timings=None, in_cfweight=None,
                         ref_cfweight=None, labelings_out=None, in_anat=None, ref_anat=None, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001),
-                        intensity=False, cut=False, **level_kw):
+                        intensity=False, cut=False, ref_cache=None, **level_kw):
     """Mesh_registration::run_multiresolutions (M/mesh_registration.cpp:30-50) for DISCRETE and RIGID levels without file I/O:
 
     per level  featurespace::initialise (M/featurespace.cpp:39-86: metric_resample of both data sets onto the level's
@@ -522,6 +554,9 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
     reference data is histogram matched to the input data after both are resampled and smoothed and before variance normalisation (finish_features:
     the reference's order, a quirk); cut (--INc) makes the exclusion masks exist as --excl does (M/featurespace.cpp:61).  The final resampling is
     the caller's (transformed_data).
+    ref_cache (optional, a ReferenceCache): the reference data's level_features output is taken from it, and put there by the first run that needs
+    it, instead of being computed at every level of every run; everything after it (finish_features, the level's target mesh) stays this run's own.
+    Without it every call is what it was before the argument existed.
     Returns (sphere_reg, per-level registered data grids, per-level energies)."""
     if excl and in_cfweight is not None and ref_cfweight is not None:
         raise ValueError(EXCL_WITH_WEIGHTINGS)
@@ -549,16 +584,16 @@ def run_multiresolution(ops, in_xyz, in_tri, in_data, ref_xyz, ref_tri, ref_data
                 else:
                     ref_data = arr
         return _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data, levels, varnorm, in_cfweight, ref_cfweight, labelings_out, in_anat,
-                           ref_anat, ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz, excl, cutthr, intensity, cut)
+                           ref_anat, ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz, excl, cutthr, intensity, cut, ref_cache)
     finally:
         for t in pins:
             ops.unpin(t)
 
 
 def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data, levels, varnorm, in_cfweight, ref_cfweight, labelings_out, in_anat, ref_anat,
-                ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001), intensity=False, cut=False):
+                ref_xyz, level_kw, sph_reg_prev, prev_order, regs, all_energies, trans_xyz=None, excl=False, cutthr=(0.0, 0.0001), intensity=False, cut=False, ref_cache=None):
     """the level loop of run_multiresolution (see there)"""
-    for lv in levels:
+    for li, lv in enumerate(levels):
         rigid = lv.get("method") == "RIGID"
         ico_xyz, ico_tri = ops.icosphere(lv["data_order"])
         ico = ops.mesh(ico_xyz, ico_tri)
@@ -567,10 +602,16 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
             # (a level's matrices are consumed -- uploaded by the cost function and the target mesh -- before the next level asks for its own: the
             # result slots are reused from level to level)
             if intensity or cut:  # resample and smooth only: matching and variance normalisation follow when both data sets are there
-                f, m = level_features(ops, timed, mesh, data, ico, sigma, False, slot, excl or cut, cutthr)
-                masks.append(m)
+                args = (False, slot, excl or cut, cutthr)
             else:
-                f = level_features(ops, timed, mesh, data, ico, sigma, varnorm, slot, excl, cutthr)[0]
+                args = (varnorm, slot, excl, cutthr)
+            if slot == "ref" and ref_cache is not None:
+                key = (li, lv["data_order"], float(sigma), bool(args[0]), bool(args[2]), tuple(float(c) for c in cutthr))
+                f, m = ref_cache.get(key, lambda: level_features(ops, timed, mesh, data, ico, sigma, *args))
+            else:
+                f, m = level_features(ops, timed, mesh, data, ico, sigma, *args)
+            if intensity or cut:
+                masks.append(m)
             feats.append(f)
         if intensity or cut:
             feats = finish_features(ops, timed, feats, masks, intensity, varnorm)
