@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 11  /* 11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 11  /* 11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -564,6 +564,24 @@ int msm_dedrift_set_map(msm_dedrift *d, int32_t subject, const double *map, int3
  * (D x S x S): masks x > numpy.percentile(x, percentile) (linear interpolation between order statistics; compare_stats.py:20-23 uses 75),
  * 2 |A and B| / (|A| + |B|).  Any output may be NULL (its kernels are not run).  The group figures are the means over the pairs i < j. */
 int msm_dedrift_group_stats(msm_dedrift *d, double percentile, double *mean, double *stdev, double *cc, double *dice);
+/* gMSM_scripts/run_cgMSM_ver_gw_iter.sh:171-192 (every subject of a child group pushed through its group's dedrifted registration C_g when two groups are
+ * merged): replaces the handle's warp W by warp_xyz (3 x V(T) SoA), a deformation of the template's vertices, taken as it is -- neither recentred nor
+ * rescaled.  msm_dedrift_correct may follow without any accumulate / finish, and the call may be repeated between subjects (child g's subjects go through
+ * C_g).  msm_dedrift_finish keeps its rule (MSM_ERR_STATE unless S subjects were accumulated) and replaces a set warp; msm_dedrift_reset forgets it.  NULL:
+ * MSM_ERR_INVALID.  An upload and a state flag: no kernel. */
+int msm_dedrift_set_warp(msm_dedrift *d, const double *warp_xyz);
+/* run_cgMSM_ver_gw_iter.sh:194-218 and extract_info.py (the figures of a merged group and of each of its child groups; the medial wall kept out of them):
+ * msm_dedrift_group_stats over the n listed resident subjects (distinct indices in [0, S), any order; matrices and sums follow the list's order) and the
+ * template vertices the mask keeps (mask: V(T) values, v is kept iff mask[v] > 0, a NaN is not kept; NULL keeps all; K = the kept count).
+ * mean, stdev (D x V(T)): over the listed subjects in list order, two passes, population form, for every vertex -- the mask does not enter.
+ * cc (D x n x n): numpy.corrcoef(x[keep], y[keep])[0, 1], diagonal 1.  dice (D x n x n): masks x[keep] > numpy.percentile(x[keep], percentile) (linear
+ * interpolation, virtual index and fraction from K), 2 |A and B| / (|A| + |B|), on the diagonal too.  cc_mean, dice_mean (D): the mean over the pairs
+ * a < b of the list, summed on the device in one fixed tree per matrix; NaN when n = 1.  Any output may be NULL (its kernels are not run; the means may be
+ * asked for without the matrices).  Integer atomics only: two calls give the same bits.  A pair tile of 8 x 8 listed subjects reads each of its map rows
+ * once.  MSM_ERR_INVALID: n < 1, an index out of range or repeated, a mask that keeps nothing, a percentile outside [0, 100]; MSM_ERR_STATE: a listed
+ * subject without resident maps.  Nothing is launched on either. */
+int msm_dedrift_group_stats_select(msm_dedrift *d, const int32_t *subjects, int32_t n, const double *mask, double percentile, double *mean, double *stdev,
+                                   double *cc, double *dice, double *cc_mean, double *dice_mean);
 
 /* ------------------------------------------------------------------------------------------------
  * after a cohort has been registered to one template, subject by subject (gMSM_scripts/newMSM_HCP_to_template_v2.sh, run_HCP_to_template_v2.sh,

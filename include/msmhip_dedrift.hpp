@@ -85,6 +85,23 @@ public:
         dice.assign((size_t)D_ * S_ * S_, 0.0);
         check(msm_dedrift_group_stats(h_, percentile, mean.data(), stdev.data(), cc.data(), dice.data()));
     }
+    // run_cgMSM_ver_gw_iter.sh:171-192: W (V(T) points, a deformation of the template's vertices) replaces the handle's warp as it is; correct may follow
+    // without accumulate / finish, and the warp may be replaced between subjects
+    void set_warp(const Points &W) { check(msm_dedrift_set_warp(h_, to_soa(W).data())); }
+    // run_cgMSM_ver_gw_iter.sh:194-218, extract_info.py: group_stats over the listed resident subjects (in the list's order) and the template vertices
+    // with mask > 0 (an empty mask keeps all); cc, dice: D x n x n; cc_mean, dice_mean: per feature the mean over the pairs a < b, from the device
+    void group_stats_select(const std::vector<int32_t> &subjects, const std::vector<double> &mask, double percentile, Matrix &mean, Matrix &stdev, Matrix &cc,
+                            Matrix &dice, std::vector<double> &cc_mean, std::vector<double> &dice_mean) {
+        const size_t n = subjects.size();
+        mean.assign((size_t)D_ * Vt_, 0.0);
+        stdev.assign((size_t)D_ * Vt_, 0.0);
+        cc.assign((size_t)D_ * n * n, 0.0);
+        dice.assign((size_t)D_ * n * n, 0.0);
+        cc_mean.assign(D_, 0.0);
+        dice_mean.assign(D_, 0.0);
+        check(msm_dedrift_group_stats_select(h_, subjects.data(), (int32_t)n, mask.empty() ? nullptr : mask.data(), percentile, mean.data(), stdev.data(),
+                                             cc.data(), dice.data(), cc_mean.data(), dice_mean.data()));
+    }
     int subjects() const { return S_; }
     int rows() const { return D_; }
 

@@ -177,6 +177,8 @@ SIGNATURES = {
     "msm_dedrift_correct": (C.c_int, [_VP, C.c_int32, _VP, c_dp, C.c_int32, c_dp, C.c_int32, c_dp, c_dp, c_dp, c_ip, c_dp]),
     "msm_dedrift_set_map": (C.c_int, [_VP, C.c_int32, c_dp, C.c_int32]),
     "msm_dedrift_group_stats": (C.c_int, [_VP, C.c_double, c_dp, c_dp, c_dp, c_dp]),
+    "msm_dedrift_set_warp": (C.c_int, [_VP, c_dp]),
+    "msm_dedrift_group_stats_select": (C.c_int, [_VP, c_ip, C.c_int32, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "msm_surface_distortion": (C.c_int, [_VP, c_dp, c_ip, C.c_int32, C.c_int32, c_dp, C.c_int32, c_dp]),
     "msm_abs_summary": (C.c_int, [_VP, c_dp, C.c_int64, c_dp, C.c_int32, c_dp, c_dp, c_dp]),
 }

@@ -17,6 +17,7 @@ struct msm_dedrift {
     int S = 0, Vt = 0, D = 0;
     int accumulated = 0;
     bool finished = false;
+    bool warp_set = false;  // the warp came from msm_dedrift_set_warp
     std::vector<char> have;  // per subject: its maps are resident
     DevBuf<double> sum, drift, warp;       // 3 x Vt each
     DevBuf<double> m_xyz, inverse, w;      // the subject in hand: its input sphere (3 x Vs), its inverse (3 x Vt), search weights (3 x max(Vt, Vs))
@@ -26,6 +27,8 @@ struct msm_dedrift {
     DevBuf<double> mean, sd, stats, thr, cc, dice;
     DevBuf<unsigned long long> bits;
     DevBuf<int32_t> count;
+    DevBuf<int32_t> list, kept;            // msm_dedrift_group_stats_select: the listed subjects, the kept vertices (ascending)
+    DevBuf<double> pair_mean;              // 2 x D: cc, then dice
 };
 
 namespace {
@@ -129,6 +132,43 @@ int group_stats(msm_dedrift *d, double percentile, double *mean, double *stdev, 
     return check_status(ctx, "msm_dedrift_group_stats");
 }
 
+// group_stats over the listed subjects and the kept vertices (kept empty: all of them).  Matrices and per-map arrays are indexed by list position.
+int group_stats_select(msm_dedrift *d, const int32_t *subjects, int n, const std::vector<int32_t> &kept, bool masked, double percentile, double *mean,
+                       double *stdev, double *cc, double *dice, double *cc_mean, double *dice_mean) {
+    msm_ctx *ctx = d->ctx;
+    const int D = d->D, Vt = d->Vt, nmaps = n * D, K = masked ? (int)kept.size() : Vt, words = (K + 63) / 64;
+    const size_t nmap = (size_t)D * Vt, nmat = (size_t)D * n * n;
+    const bool want_cc = cc || cc_mean, want_dice = dice || dice_mean;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    if (d->mean.ensure(nmap) || d->sd.ensure(nmap) || d->stats.ensure(2 * (size_t)nmaps) || d->thr.ensure(nmaps) || d->cc.ensure(nmat) ||
+        d->dice.ensure(nmat) || d->bits.ensure((size_t)nmaps * words) || d->count.ensure(nmaps) || d->pair_mean.ensure(2 * (size_t)D))
+        return stage_alloc_failed(sizeof(double) * (2 * nmap + 2 * nmat));
+    MSM_TRY(d->list.upload(subjects, n, ctx));
+    if (masked) MSM_TRY(d->kept.upload_vec(kept, ctx));
+    const int32_t *d_kept = masked ? d->kept.p : nullptr;
+    if (mean || stdev) MSM_TRY(launch_dedrift_moments_list(ctx, d->maps.p, d->list.p, n, nmap, d->mean.p, d->sd.p));
+    if (want_cc) {
+        MSM_TRY(launch_dedrift_map_stats_sel(ctx, d->maps.p, d->list.p, n, D, Vt, d_kept, K, d->stats.p));
+        MSM_TRY(launch_dedrift_tile_cc(ctx, d->maps.p, d->list.p, n, D, Vt, d_kept, K, d->stats.p, d->cc.p));
+        if (cc_mean) MSM_TRY(launch_dedrift_pair_mean(ctx, d->cc.p, D, n, d->pair_mean.p));
+    }
+    if (want_dice) {
+        const double vidx = (K - 1) * (percentile / 100.0);  // numpy.percentile over the K kept values
+        const double fl = std::floor(vidx);
+        MSM_TRY(launch_dedrift_masks_sel(ctx, d->maps.p, d->list.p, n, D, Vt, d_kept, K, (int)fl, vidx - fl, d->thr.p, d->bits.p, words, d->count.p));
+        MSM_TRY(launch_dedrift_tile_dice(ctx, d->bits.p, d->count.p, n, D, words, d->dice.p));
+        if (dice_mean) MSM_TRY(launch_dedrift_pair_mean(ctx, d->dice.p, D, n, d->pair_mean.p + D));
+    }
+    if (mean) MSM_TRY(d->mean.download(mean, nmap, ctx));
+    if (stdev) MSM_TRY(d->sd.download(stdev, nmap, ctx));
+    if (cc) MSM_TRY(d->cc.download(cc, nmat, ctx));
+    if (dice) MSM_TRY(d->dice.download(dice, nmat, ctx));
+    if (cc_mean) MSM_TRY(stage_d2h(ctx, cc_mean, d->pair_mean.p, sizeof(double) * D));
+    if (dice_mean) MSM_TRY(stage_d2h(ctx, dice_mean, d->pair_mean.p + D, sizeof(double) * D));
+    return check_status(ctx, "msm_dedrift_group_stats_select");
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,6 +214,7 @@ int msm_dedrift_reset(msm_dedrift *d) {
     MSM_HIP(hipMemsetAsync(d->sum.p, 0, sizeof(double) * 3 * (size_t)d->Vt, d->ctx->stream));
     d->accumulated = 0;
     d->finished = false;
+    d->warp_set = false;
     d->D = 0;
     d->have.assign(d->S, 0);
     return MSM_OK;
@@ -205,7 +246,7 @@ int msm_dedrift_correct(msm_dedrift *d, int32_t subject, msm_mesh *reg, const do
                         double *corrected_xyz, double *resampled, double *distortion, int32_t *tri_id, double *w) {
     if (!d || !reg || !orig_xyz || !data) return fail(MSM_ERR_INVALID, "msm_dedrift_correct: null argument");
     MSM_TRY(check_subject_mesh(d, reg, V, "msm_dedrift_correct"));
-    if (!d->finished) return fail(MSM_ERR_STATE, "msm_dedrift_correct: msm_dedrift_finish has not been called");
+    if (!d->finished && !d->warp_set) return fail(MSM_ERR_STATE, "msm_dedrift_correct: msm_dedrift_finish has not been called");
     if (subject < 0 || subject >= d->S) return fail(MSM_ERR_INVALID, "msm_dedrift_correct: subject %d of %d", subject, d->S);
     if (D < 1 || (d->D && D != d->D)) return fail(MSM_ERR_INVALID, "msm_dedrift_correct: %d data rows, the group has %d", D, d->D);
     d->D = D;
@@ -232,6 +273,38 @@ int msm_dedrift_group_stats(msm_dedrift *d, double percentile, double *mean, dou
     for (int s = 0; s < d->S; ++s)
         if (!d->have[s]) return fail(MSM_ERR_STATE, "msm_dedrift_group_stats: subject %d has no resampled maps yet", s);
     return group_stats(d, percentile, mean, stdev, cc, dice);
+}
+
+int msm_dedrift_set_warp(msm_dedrift *d, const double *warp_xyz) {
+    if (!d || !warp_xyz) return fail(MSM_ERR_INVALID, "msm_dedrift_set_warp: null argument");
+    msm_ctx *ctx = d->ctx;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(d->warp.upload(warp_xyz, 3 * (size_t)d->Vt, ctx));  // on the context's stream: behind a correct that still reads the previous warp
+    d->warp_set = true;
+    return MSM_OK;
+}
+
+int msm_dedrift_group_stats_select(msm_dedrift *d, const int32_t *subjects, int32_t n, const double *mask, double percentile, double *mean, double *stdev,
+                                   double *cc, double *dice, double *cc_mean, double *dice_mean) {
+    if (!d || !subjects) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: null argument");
+    if (!(percentile >= 0.0 && percentile <= 100.0)) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: percentile %g (0 .. 100)", percentile);
+    if (n < 1 || n > d->S) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: %d subjects listed, the group has %d", n, d->S);
+    std::vector<char> seen(d->S, 0);
+    for (int a = 0; a < n; ++a) {
+        const int s = subjects[a];
+        if (s < 0 || s >= d->S) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: subject %d of %d", s, d->S);
+        if (seen[s]) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: subject %d is listed twice", s);
+        seen[s] = 1;
+    }
+    for (int a = 0; a < n; ++a)
+        if (!d->have[subjects[a]]) return fail(MSM_ERR_STATE, "msm_dedrift_group_stats_select: subject %d has no resampled maps yet", subjects[a]);
+    std::vector<int32_t> kept;
+    if (mask) {
+        for (int v = 0; v < d->Vt; ++v)
+            if (mask[v] > 0) kept.push_back(v);  // a NaN is not kept
+        if (kept.empty()) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: the mask keeps no vertex");
+    }
+    return group_stats_select(d, subjects, n, kept, mask != nullptr, percentile, mean, stdev, cc, dice, cc_mean, dice_mean);
 }
 
 }  // extern "C"

@@ -27,4 +27,19 @@ int launch_dedrift_masks(msm_ctx *ctx, const double *d_maps, int nmaps, int Vt, 
 // dice[d][i][j] = 2 |A and B| / (|A| + |B|)
 int launch_dedrift_pair_dice(msm_ctx *ctx, const unsigned long long *d_bits, const int32_t *d_count, int S, int D, int words, double *d_dice);
 
+// --- the same figures over a list of the resident subjects (d_list: n positions -> subject) and the kept vertices (d_kept: K ascending vertex ids, or
+// nullptr with K = Vt); stats, thr, bits and count are indexed by list position (a * D + d), the matrices are D x n x n
+int launch_dedrift_moments_list(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, size_t nmap, double *d_mean, double *d_sd);
+int launch_dedrift_map_stats_sel(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K,
+                                 double *d_stats);
+// order statistics k, k + 1 and fraction gamma of K values; words = ceil(K / 64), bit j of a map's mask is its j-th kept vertex
+int launch_dedrift_masks_sel(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K, int k,
+                             double gamma, double *d_thr, unsigned long long *d_bits, int words, int32_t *d_count);
+// one workgroup per tile of 8 x 8 listed subjects and feature: every map row (mask row) is read once per tile
+int launch_dedrift_tile_cc(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K,
+                           const double *d_stats, double *d_cc);
+int launch_dedrift_tile_dice(msm_ctx *ctx, const unsigned long long *d_bits, const int32_t *d_count, int n, int D, int words, double *d_dice);
+// out[m] = the mean over the pairs a < b of matrix m (n x n) of d_mat, one fixed tree per matrix; NaN when n = 1
+int launch_dedrift_pair_mean(msm_ctx *ctx, const double *d_mat, int nmat, int n, double *d_out);
+
 }  // namespace msm

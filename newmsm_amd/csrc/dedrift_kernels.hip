@@ -15,6 +15,18 @@
 //                         order-preserving integer key (8 passes of 8 bits, integer LDS counters); the threshold; the mask x > threshold as one
 //                         ballot word per 64 vertices; its population count.
 //   k_dedrift_pair_dice   one wavefront per (pair, feature): popcount of the ANDed masks.  Integer work: exact.
+// The same figures over a list of the resident subjects and the template vertices a mask keeps (msm_dedrift_group_stats_select):
+//   k_dedrift_moments_list   k_dedrift_moments with subject s read through the list.
+//   k_dedrift_map_stats_sel  k_dedrift_map_stats and
+//   k_dedrift_masks_sel      k_dedrift_masks for the listed maps, over the kept vertices only: the histogram counts kept keys, order statistics and
+//                            the interpolation take K = the kept count, bit j of a map's mask belongs to the j-th kept vertex.
+//   k_dedrift_tile_cc        one workgroup per (tile of 8 x 8 listed subjects, feature): a lane loads one vertex of the tile's 16 map rows and feeds
+//                            all 64 pairs from it, so a map row is read once per tile and not once per pair; the 64 sums of a lane are reduced over
+//                            block_sum's tree, eight side by side.  The tile comes from the grid's coordinates (the lower triangle's workgroups
+//                            leave at once): no search for the pair.
+//   k_dedrift_tile_dice      the same tiling over the mask words: AND + popcount, integer sums over the same tree.
+//   k_dedrift_pair_mean      one workgroup per matrix: the sum over the upper triangle (lane t takes the columns i + 1 + t, + 256, ... of every row
+//                            i, rows ascending; block_sum), divided by the number of pairs; NaN for a single subject.
 //
 // No floating-point atomics anywhere: every floating-point sum has a fixed shape, two runs give the same bits.
 #include "dedrift.hpp"
@@ -145,19 +157,61 @@ __global__ __launch_bounds__(kBlock) void k_dedrift_moments(const double *__rest
     sd[i] = sqrt(q / S);
 }
 
-__global__ __launch_bounds__(kBlock) void k_dedrift_map_stats(const double *__restrict__ maps, int Vt, double *__restrict__ stats) {
-    __shared__ double lds[kBlock];
-    const double *x = maps + (size_t)blockIdx.x * Vt;
+__global__ __launch_bounds__(kBlock) void k_dedrift_moments_list(const double *__restrict__ maps, const int32_t *__restrict__ list, int S, size_t n,
+                                                                 double *__restrict__ mean, double *__restrict__ sd) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
     double a = 0.0;
-    for (int i = threadIdx.x; i < Vt; i += kBlock) a += x[i];
-    const double mu = block_sum(a, lds) / Vt;
+    for (int s = 0; s < S; ++s) a += maps[(size_t)list[s] * n + i];
+    const double mu = a / S;
     double q = 0.0;
-    for (int i = threadIdx.x; i < Vt; i += kBlock) {
+    for (int s = 0; s < S; ++s) {
+        const double d = maps[(size_t)list[s] * n + i] - mu;
+        q += d * d;
+    }
+    mean[i] = mu;
+    sd[i] = sqrt(q / S);
+}
+
+// a map row as it is (X = const double *), or its entries at the kept vertices only
+struct KeptRow {
+    const double *x;
+    const int32_t *kept;  // ascending vertex ids
+    __device__ __forceinline__ double operator[](int j) const { return x[kept[j]]; }
+};
+
+// mean of x[0 .. n) and the root of its summed squared deviations, a fixed 256-leaf tree each
+template <class X>
+__device__ __forceinline__ void map_mean_root(const X x, int n, double *lds, double &mu, double &root) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += kBlock) a += x[i];
+    mu = block_sum(a, lds) / n;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < n; i += kBlock) {
         const double d = x[i] - mu;
         q += d * d;
     }
-    const double ss = block_sum(q, lds);
-    if (threadIdx.x == 0) stats[2 * (size_t)blockIdx.x] = mu, stats[2 * (size_t)blockIdx.x + 1] = sqrt(ss);
+    root = sqrt(block_sum(q, lds));
+}
+
+__global__ __launch_bounds__(kBlock) void k_dedrift_map_stats(const double *__restrict__ maps, int Vt, double *__restrict__ stats) {
+    __shared__ double lds[kBlock];
+    double mu, root;
+    map_mean_root(maps + (size_t)blockIdx.x * Vt, Vt, lds, mu, root);
+    if (threadIdx.x == 0) stats[2 * (size_t)blockIdx.x] = mu, stats[2 * (size_t)blockIdx.x + 1] = root;
+}
+
+// workgroup a * D + d: row d of listed subject a, over the K kept vertices (kept == nullptr: all Vt = K of them)
+__global__ __launch_bounds__(kBlock) void k_dedrift_map_stats_sel(const double *__restrict__ maps, const int32_t *__restrict__ list, int D, int Vt,
+                                                                  const int32_t *__restrict__ kept, int K, double *__restrict__ stats) {
+    __shared__ double lds[kBlock];
+    const double *x = maps + ((size_t)list[blockIdx.x / D] * D + blockIdx.x % D) * Vt;
+    double mu, root;
+    if (kept)
+        map_mean_root(KeptRow{x, kept}, K, lds, mu, root);
+    else
+        map_mean_root(x, K, lds, mu, root);
+    if (threadIdx.x == 0) stats[2 * (size_t)blockIdx.x] = mu, stats[2 * (size_t)blockIdx.x + 1] = root;
 }
 
 // pair p of the list (0,1) (0,2) ... (0,S-1) (1,2) ...
@@ -202,13 +256,14 @@ __device__ __forceinline__ double key_value(unsigned long long k) {
     return __longlong_as_double((long long)u);
 }
 
-__global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restrict__ maps, int Vt, int k, double gamma, double *__restrict__ thr_out,
-                                                         unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
+// the masks of one map x[0 .. n) for a kWide-wide workgroup; results go to slot `out` of thr_out, bits (words words per slot) and count
+template <class X>
+__device__ __forceinline__ void percentile_mask(const X x, int n, int k, double gamma, int out, double *__restrict__ thr_out,
+                                                unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
     __shared__ int hist[256];
     __shared__ unsigned long long s_prefix, s_min;
     __shared__ int s_k, s_cnt;
     const int t = threadIdx.x;
-    const double *x = maps + (size_t)blockIdx.x * Vt;
     if (t == 0) s_prefix = 0, s_k = k;
     // the k-th smallest key (0-based), eight bits at a time from the top
     for (int pass = 0; pass < 8; ++pass) {
@@ -216,7 +271,7 @@ __global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restric
         if (t < 256) hist[t] = 0;
         __syncthreads();
         const unsigned long long prefix = s_prefix, himask = pass == 0 ? 0ull : (~0ull << (shift + 8));
-        for (int i = t; i < Vt; i += kWide) {
+        for (int i = t; i < n; i += kWide) {
             const unsigned long long key = order_key(x[i]);
             if ((key & himask) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255)], 1);
         }
@@ -240,7 +295,7 @@ __global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restric
     __syncthreads();
     int cnt = 0;
     unsigned long long mn = ~0ull;
-    for (int i = t; i < Vt; i += kWide) {
+    for (int i = t; i < n; i += kWide) {
         const unsigned long long key = order_key(x[i]);
         if (key <= lo_key)
             ++cnt;
@@ -250,7 +305,7 @@ __global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restric
     atomicAdd(&s_cnt, cnt);
     atomicMin(&s_min, mn);
     __syncthreads();
-    const unsigned long long hi_key = (k + 1 >= Vt || s_cnt > k + 1) ? lo_key : s_min;
+    const unsigned long long hi_key = (k + 1 >= n || s_cnt > k + 1) ? lo_key : s_min;
     // numpy's _lerp: a + (b - a) t, and b - (b - a) (1 - t) from t = 0.5 on
     const double a = key_value(lo_key), b = key_value(hi_key), diff = b - a;
     const double thr = gamma >= 0.5 ? b - diff * (1 - gamma) : a + diff * gamma;
@@ -261,15 +316,31 @@ __global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restric
     int ones = 0;
     for (int base = (t >> 6) * 64; base < words * 64; base += kWide) {  // wavefront-uniform
         const int i = base + lane;
-        const unsigned long long word = __ballot(i < Vt && x[i] > thr);
+        const unsigned long long word = __ballot(i < n && x[i] > thr);
         if (lane == 0) {
-            bits[(size_t)blockIdx.x * words + (base >> 6)] = word;
+            bits[(size_t)out * words + (base >> 6)] = word;
             ones += __popcll(word);
         }
     }
     if (lane == 0) atomicAdd(&s_cnt, ones);
     __syncthreads();
-    if (t == 0) thr_out[blockIdx.x] = thr, count[blockIdx.x] = s_cnt;
+    if (t == 0) thr_out[out] = thr, count[out] = s_cnt;
+}
+
+__global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restrict__ maps, int Vt, int k, double gamma, double *__restrict__ thr_out,
+                                                         unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
+    percentile_mask(maps + (size_t)blockIdx.x * Vt, Vt, k, gamma, blockIdx.x, thr_out, bits, words, count);
+}
+
+// workgroup a * D + d: row d of listed subject a, over the K kept vertices (kept == nullptr: all Vt = K of them); words = ceil(K / 64)
+__global__ __launch_bounds__(kWide) void k_dedrift_masks_sel(const double *__restrict__ maps, const int32_t *__restrict__ list, int D, int Vt,
+                                                             const int32_t *__restrict__ kept, int K, int k, double gamma, double *__restrict__ thr_out,
+                                                             unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
+    const double *x = maps + ((size_t)list[blockIdx.x / D] * D + blockIdx.x % D) * Vt;
+    if (kept)
+        percentile_mask(KeptRow{x, kept}, K, k, gamma, blockIdx.x, thr_out, bits, words, count);
+    else
+        percentile_mask(x, K, k, gamma, blockIdx.x, thr_out, bits, words, count);
 }
 
 __global__ __launch_bounds__(64) void k_dedrift_pair_dice(const unsigned long long *__restrict__ bits, const int32_t *__restrict__ count, int S, int D,
@@ -296,6 +367,122 @@ __global__ __launch_bounds__(64) void k_dedrift_pair_dice(const unsigned long lo
         out[(size_t)i * S + j] = r;
         out[(size_t)j * S + i] = r;
     }
+}
+
+constexpr int kTile = 8;  // listed subjects along each side of a pair tile
+
+// kTile sums of one value per lane each, side by side over block_sum's tree; lane b < kTile returns sum b (the other lanes' value is not used)
+template <class T>
+__device__ __forceinline__ T tile_sums(const T (&v)[kTile], T (*lds)[kBlock]) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int b = 0; b < kTile; ++b) lds[b][t] = v[b];
+    __syncthreads();
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int b = 0; b < kTile; ++b) lds[b][t] += lds[b][t + s];
+        }
+        __syncthreads();
+    }
+    const T r = lds[t < kTile ? t : 0][0];
+    __syncthreads();
+    return r;
+}
+
+// workgroup (tj, ti, d), ti <= tj: the pairs of the listed subjects ti * 8 + a and tj * 8 + b of feature d.  A position past the list's end reads
+// the list's last subject and writes nothing.  stats is indexed by list position.
+__global__ __launch_bounds__(kBlock) void k_dedrift_tile_cc(const double *__restrict__ maps, const int32_t *__restrict__ list, int n, int D, int Vt,
+                                                            const int32_t *__restrict__ kept, int K, const double *__restrict__ stats,
+                                                            double *__restrict__ cc) {
+    __shared__ double lds[kTile][kBlock];
+    const int tj = blockIdx.x, ti = blockIdx.y, d = blockIdx.z;
+    if (ti > tj) return;
+    const double *xr[kTile], *xc[kTile];
+    double mr[kTile], mc[kTile];
+#pragma unroll
+    for (int a = 0; a < kTile; ++a) {
+        const int ia = min(ti * kTile + a, n - 1), ib = min(tj * kTile + a, n - 1);
+        xr[a] = maps + ((size_t)list[ia] * D + d) * Vt, mr[a] = stats[2 * ((size_t)ia * D + d)];
+        xc[a] = maps + ((size_t)list[ib] * D + d) * Vt, mc[a] = stats[2 * ((size_t)ib * D + d)];
+    }
+    double acc[kTile][kTile];
+#pragma unroll
+    for (int a = 0; a < kTile; ++a)
+#pragma unroll
+        for (int b = 0; b < kTile; ++b) acc[a][b] = 0.0;
+    for (int j = threadIdx.x; j < K; j += kBlock) {
+        const int v = kept ? kept[j] : j;
+        double r[kTile], c[kTile];
+#pragma unroll
+        for (int a = 0; a < kTile; ++a) r[a] = xr[a][v] - mr[a], c[a] = xc[a][v] - mc[a];
+#pragma unroll
+        for (int a = 0; a < kTile; ++a)
+#pragma unroll
+            for (int b = 0; b < kTile; ++b) acc[a][b] += r[a] * c[b];
+    }
+    double *out = cc + (size_t)d * n * n;
+#pragma unroll
+    for (int a = 0; a < kTile; ++a) {
+        const double dot = tile_sums(acc[a], lds);
+        const int ia = ti * kTile + a, ib = tj * kTile + (int)threadIdx.x;
+        if (threadIdx.x >= kTile || ia >= n || ib >= n) continue;
+        if (ia == ib) out[(size_t)ia * n + ia] = 1.0;
+        if (ia < ib) {  // a diagonal tile holds every pair twice: the copy above the diagonal serves both entries
+            const double rho = dot / (stats[2 * ((size_t)ia * D + d) + 1] * stats[2 * ((size_t)ib * D + d) + 1]);
+            out[(size_t)ia * n + ib] = rho;
+            out[(size_t)ib * n + ia] = rho;
+        }
+    }
+}
+
+// the same tiles over the masks (bits, count: indexed by list position); the diagonal follows the formula (NaN for an empty mask)
+__global__ __launch_bounds__(kBlock) void k_dedrift_tile_dice(const unsigned long long *__restrict__ bits, const int32_t *__restrict__ count, int n, int D,
+                                                              int words, double *__restrict__ dice) {
+    __shared__ int lds[kTile][kBlock];
+    const int tj = blockIdx.x, ti = blockIdx.y, d = blockIdx.z;
+    if (ti > tj) return;
+    const unsigned long long *br[kTile], *bc[kTile];
+#pragma unroll
+    for (int a = 0; a < kTile; ++a) {
+        br[a] = bits + ((size_t)min(ti * kTile + a, n - 1) * D + d) * words;
+        bc[a] = bits + ((size_t)min(tj * kTile + a, n - 1) * D + d) * words;
+    }
+    int acc[kTile][kTile];
+#pragma unroll
+    for (int a = 0; a < kTile; ++a)
+#pragma unroll
+        for (int b = 0; b < kTile; ++b) acc[a][b] = 0;
+    for (int j = threadIdx.x; j < words; j += kBlock) {
+        unsigned long long r[kTile], c[kTile];
+#pragma unroll
+        for (int a = 0; a < kTile; ++a) r[a] = br[a][j], c[a] = bc[a][j];
+#pragma unroll
+        for (int a = 0; a < kTile; ++a)
+#pragma unroll
+            for (int b = 0; b < kTile; ++b) acc[a][b] += __popcll(r[a] & c[b]);
+    }
+    double *out = dice + (size_t)d * n * n;
+#pragma unroll
+    for (int a = 0; a < kTile; ++a) {
+        const int both = tile_sums(acc[a], lds);
+        const int ia = ti * kTile + a, ib = tj * kTile + (int)threadIdx.x;
+        if (threadIdx.x >= kTile || ia >= n || ib >= n || ia > ib) continue;
+        const double r = 2.0 * both / (double)(count[(size_t)ia * D + d] + count[(size_t)ib * D + d]);
+        out[(size_t)ia * n + ib] = r;
+        out[(size_t)ib * n + ia] = r;
+    }
+}
+
+// workgroup m: the mean over the pairs a < b of matrix m (n x n)
+__global__ __launch_bounds__(kBlock) void k_dedrift_pair_mean(const double *__restrict__ mat, int n, double *__restrict__ out) {
+    __shared__ double lds[kBlock];
+    const double *m = mat + (size_t)blockIdx.x * n * n;
+    double a = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1 + threadIdx.x; j < n; j += kBlock) a += m[(size_t)i * n + j];
+    const double sum = block_sum(a, lds);
+    if (threadIdx.x == 0) out[blockIdx.x] = n > 1 ? sum / (n * (n - 1) / 2.0) : NAN;
 }
 
 }  // namespace
@@ -354,6 +541,51 @@ int launch_dedrift_masks(msm_ctx *ctx, const double *d_maps, int nmaps, int Vt, 
 int launch_dedrift_pair_dice(msm_ctx *ctx, const unsigned long long *d_bits, const int32_t *d_count, int S, int D, int words, double *d_dice) {
     const int npairs = S * (S - 1) / 2;
     hipLaunchKernelGGL(k_dedrift_pair_dice, dim3(npairs + S, D), dim3(64), 0, ctx->stream, d_bits, d_count, S, D, words, d_dice);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_dedrift_moments_list(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, size_t nmap, double *d_mean, double *d_sd) {
+    if (nmap == 0) return MSM_OK;
+    hipLaunchKernelGGL(k_dedrift_moments_list, dim3((unsigned)((nmap + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, d_maps, d_list, n, nmap, d_mean,
+                       d_sd);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_dedrift_map_stats_sel(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K,
+                                 double *d_stats) {
+    hipLaunchKernelGGL(k_dedrift_map_stats_sel, dim3(n * D), dim3(kBlock), 0, ctx->stream, d_maps, d_list, D, Vt, d_kept, K, d_stats);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_dedrift_masks_sel(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K, int k,
+                             double gamma, double *d_thr, unsigned long long *d_bits, int words, int32_t *d_count) {
+    hipLaunchKernelGGL(k_dedrift_masks_sel, dim3(n * D), dim3(kWide), 0, ctx->stream, d_maps, d_list, D, Vt, d_kept, K, k, gamma, d_thr, d_bits, words,
+                       d_count);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+// both tile kernels: ceil(n / 8)^2 workgroups per feature, of which the lower triangle's leave at once
+int launch_dedrift_tile_cc(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K,
+                           const double *d_stats, double *d_cc) {
+    const int nt = (n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_dedrift_tile_cc, dim3(nt, nt, D), dim3(kBlock), 0, ctx->stream, d_maps, d_list, n, D, Vt, d_kept, K, d_stats, d_cc);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_dedrift_tile_dice(msm_ctx *ctx, const unsigned long long *d_bits, const int32_t *d_count, int n, int D, int words, double *d_dice) {
+    const int nt = (n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_dedrift_tile_dice, dim3(nt, nt, D), dim3(kBlock), 0, ctx->stream, d_bits, d_count, n, D, words, d_dice);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_dedrift_pair_mean(msm_ctx *ctx, const double *d_mat, int nmat, int n, double *d_out) {
+    hipLaunchKernelGGL(k_dedrift_pair_mean, dim3(nmat), dim3(kBlock), 0, ctx->stream, d_mat, n, d_out);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

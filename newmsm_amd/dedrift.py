@@ -98,6 +98,29 @@ class Dedrift:
                                             cc.ctypes.data_as(c_dp), dice.ctypes.data_as(c_dp)))
         return mean, stdev, cc, dice
 
+    def set_warp(self, W):
+        """msm_dedrift_set_warp: W (V(T), 3), a deformation of the template's vertices, replaces the handle's warp as it is; correct may follow"""
+        w, pw = api._soa(W)
+        assert w.shape[1] == self.Vt
+        check(lib().msm_dedrift_set_warp(self.h, pw))
+
+    def group_stats_select(self, subjects, mask=None, percentile=75.0):
+        """msm_dedrift_group_stats_select: (mean, stdev (D, V(T)), cc, dice (D, n, n), cc_mean, dice_mean (D)) over the listed resident subjects, in the
+        list's order, and the vertices with mask > 0 (None: all)"""
+        idx = np.ascontiguousarray(np.asarray(subjects, dtype=np.int32).ravel())
+        D, n = self.D, len(idx)
+        pm = None
+        if mask is not None:
+            m, pm = api._d(np.asarray(mask, dtype=np.float64).ravel())
+            assert m.size == self.Vt
+        mean, stdev = np.zeros((D, self.Vt)), np.zeros((D, self.Vt))
+        cc, dice = np.zeros((D, n, n)), np.zeros((D, n, n))
+        cc_mean, dice_mean = np.zeros(D), np.zeros(D)
+        check(lib().msm_dedrift_group_stats_select(self.h, idx.ctypes.data_as(c_ip), n, pm, C.c_double(float(percentile)), mean.ctypes.data_as(c_dp),
+                                                   stdev.ctypes.data_as(c_dp), cc.ctypes.data_as(c_dp), dice.ctypes.data_as(c_dp),
+                                                   cc_mean.ctypes.data_as(c_dp), dice_mean.ctypes.data_as(c_dp)))
+        return mean, stdev, cc, dice, cc_mean, dice_mean
+
 
 class ProductOps:
     """The calls of dedrift_group answered by libmsmhip.  The subjects' registered spheres are kept as mesh handles from accumulate to correct."""
@@ -131,6 +154,20 @@ class ProductOps:
 
     def group_stats(self, st, percentile):
         return st["d"].group_stats(percentile)
+
+    def set_warp(self, st, W):
+        st["d"].set_warp(W)
+
+    def group_stats_select(self, st, subjects, mask, percentile):
+        return st["d"].group_stats_select(subjects, mask, percentile)
+
+    def distortion_summary(self, distortions):
+        """distortion_summary's figures through msm_abs_summary"""
+        areal = np.concatenate([np.asarray(d)[0].ravel() for d in distortions])
+        shape = np.concatenate([np.asarray(d)[1].ravel() for d in distortions])
+        a_mean, a_max, a_p = api.abs_summary(self.ctx, areal, (95.0, 98.0))
+        s_mean, s_max, _ = api.abs_summary(self.ctx, shape)
+        return dict(areal_mean=a_mean, areal_max=a_max, areal_95=float(a_p[0]), areal_98=float(a_p[1]), shape_mean=s_mean, shape_max=s_max)
 
     def end(self, st):
         st["d"].close()
