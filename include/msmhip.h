@@ -578,8 +578,9 @@ int msm_dedrift_set_warp(msm_dedrift *d, const double *warp_xyz);
  * interpolation, virtual index and fraction from K), 2 |A and B| / (|A| + |B|), on the diagonal too.  cc_mean, dice_mean (D): the mean over the pairs
  * a < b of the list, summed on the device in one fixed tree per matrix; NaN when n = 1.  Any output may be NULL (its kernels are not run; the means may be
  * asked for without the matrices).  Integer atomics only: two calls give the same bits.  A pair tile of 8 x 8 listed subjects reads each of its map rows
- * once.  MSM_ERR_INVALID: n < 1, an index out of range or repeated, a mask that keeps nothing, a percentile outside [0, 100]; MSM_ERR_STATE: a listed
- * subject without resident maps.  Nothing is launched on either. */
+ * once.  msm_dedrift_group_stats is this computation with every subject listed in order and no mask: the same bits.  MSM_ERR_INVALID: n < 1, an index
+ * out of range or repeated, a mask that keeps nothing, a percentile outside [0, 100]; MSM_ERR_STATE: a listed subject without resident maps.  Nothing
+ * is launched on either. */
 int msm_dedrift_group_stats_select(msm_dedrift *d, const int32_t *subjects, int32_t n, const double *mask, double percentile, double *mean, double *stdev,
                                    double *cc, double *dice, double *cc_mean, double *dice_mean);
 

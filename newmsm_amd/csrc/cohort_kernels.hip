@@ -13,27 +13,14 @@
 //
 // No floating-point atomics anywhere: every floating-point sum has a fixed shape, two runs give the same bits.
 #include "cohort.hpp"
+#include "reduce_device.hpp"
 #include "strain_device.hpp"
 
 namespace msm {
 
 namespace {
 
-constexpr int kBlock = 256;
-
-// the sum of one value per lane of a kBlock-wide workgroup, as a fixed binary tree over LDS (every lane gets it)
-__device__ __forceinline__ double block_sum(double v, double *lds) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (t < s) lds[t] += lds[t + s];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
-}
+constexpr int kBlock = kSumBlock;
 
 __global__ __launch_bounds__(kBlock) void k_triangle_distortion(const double *__restrict__ m, const double *__restrict__ fin, int V,
                                                                 const int32_t *__restrict__ tri, int T, int S, double *__restrict__ tl) {

@@ -27,7 +27,7 @@ struct msm_dedrift {
     DevBuf<double> mean, sd, stats, thr, cc, dice;
     DevBuf<unsigned long long> bits;
     DevBuf<int32_t> count;
-    DevBuf<int32_t> list, kept;            // msm_dedrift_group_stats_select: the listed subjects, the kept vertices (ascending)
+    DevBuf<int32_t> list, kept;            // group statistics: the listed subjects, the kept vertices (ascending)
     DevBuf<double> pair_mean;              // 2 x D: cc, then dice
 };
 
@@ -104,37 +104,16 @@ int correct(msm_dedrift *d, int subject, msm_mesh *reg, const double *orig_xyz, 
     return MSM_OK;
 }
 
-int group_stats(msm_dedrift *d, double percentile, double *mean, double *stdev, double *cc, double *dice) {
-    msm_ctx *ctx = d->ctx;
-    const int S = d->S, D = d->D, Vt = d->Vt, nmaps = S * D, words = (Vt + 63) / 64;
-    const size_t nmap = (size_t)D * Vt, nmat = (size_t)D * S * S;
-    MSM_HIP(hipSetDevice(ctx->device));
-    MSM_TRY(drop_ctx_pending(ctx));
-    if (d->mean.ensure(nmap) || d->sd.ensure(nmap) || d->stats.ensure(2 * (size_t)nmaps) || d->thr.ensure(nmaps) || d->cc.ensure(nmat) ||
-        d->dice.ensure(nmat) || d->bits.ensure((size_t)nmaps * words) || d->count.ensure(nmaps))
-        return stage_alloc_failed(sizeof(double) * (2 * nmap + 2 * nmat));
-    if (mean || stdev) MSM_TRY(launch_dedrift_moments(ctx, d->maps.p, S, nmap, d->mean.p, d->sd.p));
-    if (cc) {
-        MSM_TRY(launch_dedrift_map_stats(ctx, d->maps.p, nmaps, Vt, d->stats.p));
-        MSM_TRY(launch_dedrift_pair_cc(ctx, d->maps.p, S, D, Vt, d->stats.p, d->cc.p));
-    }
-    if (dice) {
-        // numpy.percentile, method "linear": the virtual index (n - 1) q with q = percentile / 100, between the order statistics floor and floor + 1
-        const double vidx = (Vt - 1) * (percentile / 100.0);
-        const double fl = std::floor(vidx);
-        MSM_TRY(launch_dedrift_masks(ctx, d->maps.p, nmaps, Vt, (int)fl, vidx - fl, d->thr.p, d->bits.p, words, d->count.p));
-        MSM_TRY(launch_dedrift_pair_dice(ctx, d->bits.p, d->count.p, S, D, words, d->dice.p));
-    }
-    if (mean) MSM_TRY(d->mean.download(mean, nmap, ctx));
-    if (stdev) MSM_TRY(d->sd.download(stdev, nmap, ctx));
-    if (cc) MSM_TRY(d->cc.download(cc, nmat, ctx));
-    if (dice) MSM_TRY(d->dice.download(dice, nmat, ctx));
-    return check_status(ctx, "msm_dedrift_group_stats");
-}
+// The whole set without a mask goes through the per-pair kernels up to this many subjects, through the tile kernels above it (the same bits either way).
+// Measured on an MI355X at ico6, D = 2, medians of 30 (profiles/hierarchy_time_parent.json): the whole call with the per-pair kernels
+// against the tile kernels 0.36 / 0.48 ms at S = 2, 0.39 / 0.53 at 8 and 9, 0.39 / 0.55 at 16, 0.68 / 0.74 at 64 and 3.76 / 2.03 at 256, the same call
+// twice differing by 1 %: one to three tiles per feature are a latency chain on one to three CUs.  64 is the largest measured size at which the tiles lose.
+constexpr int kPerPairMax = 64;
 
-// group_stats over the listed subjects and the kept vertices (kept empty: all of them).  Matrices and per-map arrays are indexed by list position.
-int group_stats_select(msm_dedrift *d, const int32_t *subjects, int n, const std::vector<int32_t> &kept, bool masked, double percentile, double *mean,
-                       double *stdev, double *cc, double *dice, double *cc_mean, double *dice_mean) {
+// the group statistics over n listed subjects (subjects == nullptr: the subjects 0 .. n - 1, no list is uploaded) and the kept vertices (!masked: all of
+// them).  Matrices and per-map arrays are indexed by list position.  `what` names the entry point for check_status.
+int group_stats(msm_dedrift *d, const char *what, const int32_t *subjects, int n, const std::vector<int32_t> &kept, bool masked, double percentile,
+                double *mean, double *stdev, double *cc, double *dice, double *cc_mean, double *dice_mean) {
     msm_ctx *ctx = d->ctx;
     const int D = d->D, Vt = d->Vt, nmaps = n * D, K = masked ? (int)kept.size() : Vt, words = (K + 63) / 64;
     const size_t nmap = (size_t)D * Vt, nmat = (size_t)D * n * n;
@@ -144,20 +123,27 @@ int group_stats_select(msm_dedrift *d, const int32_t *subjects, int n, const std
     if (d->mean.ensure(nmap) || d->sd.ensure(nmap) || d->stats.ensure(2 * (size_t)nmaps) || d->thr.ensure(nmaps) || d->cc.ensure(nmat) ||
         d->dice.ensure(nmat) || d->bits.ensure((size_t)nmaps * words) || d->count.ensure(nmaps) || d->pair_mean.ensure(2 * (size_t)D))
         return stage_alloc_failed(sizeof(double) * (2 * nmap + 2 * nmat));
-    MSM_TRY(d->list.upload(subjects, n, ctx));
+    if (subjects) MSM_TRY(d->list.upload(subjects, n, ctx));
     if (masked) MSM_TRY(d->kept.upload_vec(kept, ctx));
-    const int32_t *d_kept = masked ? d->kept.p : nullptr;
-    if (mean || stdev) MSM_TRY(launch_dedrift_moments_list(ctx, d->maps.p, d->list.p, n, nmap, d->mean.p, d->sd.p));
+    const int32_t *d_list = subjects ? d->list.p : nullptr, *d_kept = masked ? d->kept.p : nullptr;
+    if (mean || stdev) MSM_TRY(launch_dedrift_moments(ctx, d->maps.p, d_list, n, nmap, d->mean.p, d->sd.p));
+    const bool per_pair = !subjects && !masked && n <= kPerPairMax;
     if (want_cc) {
-        MSM_TRY(launch_dedrift_map_stats_sel(ctx, d->maps.p, d->list.p, n, D, Vt, d_kept, K, d->stats.p));
-        MSM_TRY(launch_dedrift_tile_cc(ctx, d->maps.p, d->list.p, n, D, Vt, d_kept, K, d->stats.p, d->cc.p));
+        MSM_TRY(launch_dedrift_map_stats(ctx, d->maps.p, d_list, n, D, Vt, d_kept, K, d->stats.p));
+        if (per_pair)
+            MSM_TRY(launch_dedrift_pair_cc(ctx, d->maps.p, n, D, Vt, d->stats.p, d->cc.p));
+        else
+            MSM_TRY(launch_dedrift_tile_cc(ctx, d->maps.p, d_list, n, D, Vt, d_kept, K, d->stats.p, d->cc.p));
         if (cc_mean) MSM_TRY(launch_dedrift_pair_mean(ctx, d->cc.p, D, n, d->pair_mean.p));
     }
     if (want_dice) {
         const double vidx = (K - 1) * (percentile / 100.0);  // numpy.percentile over the K kept values
         const double fl = std::floor(vidx);
-        MSM_TRY(launch_dedrift_masks_sel(ctx, d->maps.p, d->list.p, n, D, Vt, d_kept, K, (int)fl, vidx - fl, d->thr.p, d->bits.p, words, d->count.p));
-        MSM_TRY(launch_dedrift_tile_dice(ctx, d->bits.p, d->count.p, n, D, words, d->dice.p));
+        MSM_TRY(launch_dedrift_masks(ctx, d->maps.p, d_list, n, D, Vt, d_kept, K, (int)fl, vidx - fl, d->thr.p, d->bits.p, words, d->count.p));
+        if (per_pair)
+            MSM_TRY(launch_dedrift_pair_dice(ctx, d->bits.p, d->count.p, n, D, words, d->dice.p));
+        else
+            MSM_TRY(launch_dedrift_tile_dice(ctx, d->bits.p, d->count.p, n, D, words, d->dice.p));
         if (dice_mean) MSM_TRY(launch_dedrift_pair_mean(ctx, d->dice.p, D, n, d->pair_mean.p + D));
     }
     if (mean) MSM_TRY(d->mean.download(mean, nmap, ctx));
@@ -166,7 +152,7 @@ int group_stats_select(msm_dedrift *d, const int32_t *subjects, int n, const std
     if (dice) MSM_TRY(d->dice.download(dice, nmat, ctx));
     if (cc_mean) MSM_TRY(stage_d2h(ctx, cc_mean, d->pair_mean.p, sizeof(double) * D));
     if (dice_mean) MSM_TRY(stage_d2h(ctx, dice_mean, d->pair_mean.p + D, sizeof(double) * D));
-    return check_status(ctx, "msm_dedrift_group_stats_select");
+    return check_status(ctx, what);
 }
 
 }  // namespace
@@ -272,7 +258,7 @@ int msm_dedrift_group_stats(msm_dedrift *d, double percentile, double *mean, dou
     if (!(percentile >= 0.0 && percentile <= 100.0)) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats: percentile %g (0 .. 100)", percentile);
     for (int s = 0; s < d->S; ++s)
         if (!d->have[s]) return fail(MSM_ERR_STATE, "msm_dedrift_group_stats: subject %d has no resampled maps yet", s);
-    return group_stats(d, percentile, mean, stdev, cc, dice);
+    return group_stats(d, "msm_dedrift_group_stats", nullptr, d->S, {}, false, percentile, mean, stdev, cc, dice, nullptr, nullptr);
 }
 
 int msm_dedrift_set_warp(msm_dedrift *d, const double *warp_xyz) {
@@ -304,7 +290,7 @@ int msm_dedrift_group_stats_select(msm_dedrift *d, const int32_t *subjects, int3
             if (mask[v] > 0) kept.push_back(v);  // a NaN is not kept
         if (kept.empty()) return fail(MSM_ERR_INVALID, "msm_dedrift_group_stats_select: the mask keeps no vertex");
     }
-    return group_stats_select(d, subjects, n, kept, mask != nullptr, percentile, mean, stdev, cc, dice, cc_mean, dice_mean);
+    return group_stats(d, "msm_dedrift_group_stats_select", subjects, n, kept, mask != nullptr, percentile, mean, stdev, cc, dice, cc_mean, dice_mean);
 }
 
 }  // extern "C"

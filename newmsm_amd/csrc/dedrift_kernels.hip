@@ -8,50 +8,37 @@
 //                         the box's midpoint and scaled to radius 100.
 //   k_vertex_distortion   one lane per vertex: J and R of triangle_strain (strain_device.hpp) for each incident triangle in trID order, the plain mean
 //                         of log2 J and log2 R.
-//   k_dedrift_moments     one lane per map element: mean over the subjects, then the population standard deviation about it, both in subject order.
-//   k_dedrift_map_stats   one workgroup per map: its mean and the root of its summed squared deviations (a fixed 256-leaf tree each).
-//   k_dedrift_pair_cc     one workgroup per (pair, feature): the sum of products of deviations over the same tree, divided by the two roots.
-//   k_dedrift_masks       one workgroup per map: the two order statistics numpy.percentile interpolates between, by a radix select over an
-//                         order-preserving integer key (8 passes of 8 bits, integer LDS counters); the threshold; the mask x > threshold as one
-//                         ballot word per 64 vertices; its population count.
-//   k_dedrift_pair_dice   one wavefront per (pair, feature): popcount of the ANDed masks.  Integer work: exact.
-// The same figures over a list of the resident subjects and the template vertices a mask keeps (msm_dedrift_group_stats_select):
-//   k_dedrift_moments_list   k_dedrift_moments with subject s read through the list.
-//   k_dedrift_map_stats_sel  k_dedrift_map_stats and
-//   k_dedrift_masks_sel      k_dedrift_masks for the listed maps, over the kept vertices only: the histogram counts kept keys, order statistics and
-//                            the interpolation take K = the kept count, bit j of a map's mask belongs to the j-th kept vertex.
-//   k_dedrift_tile_cc        one workgroup per (tile of 8 x 8 listed subjects, feature): a lane loads one vertex of the tile's 16 map rows and feeds
-//                            all 64 pairs from it, so a map row is read once per tile and not once per pair; the 64 sums of a lane are reduced over
-//                            block_sum's tree, eight side by side.  The tile comes from the grid's coordinates (the lower triangle's workgroups
-//                            leave at once): no search for the pair.
-//   k_dedrift_tile_dice      the same tiling over the mask words: AND + popcount, integer sums over the same tree.
-//   k_dedrift_pair_mean      one workgroup per matrix: the sum over the upper triangle (lane t takes the columns i + 1 + t, + 256, ... of every row
-//                            i, rows ascending; block_sum), divided by the number of pairs; NaN for a single subject.
+// The group statistics, over a list of the resident subjects (nullptr: all of them in order) and the template vertices a mask keeps (nullptr: all K = Vt
+// of them); per-map results and the matrices are indexed by list position:
+//   k_dedrift_moments     one lane per map element: mean over the listed subjects, then the population standard deviation about it, both in list order.
+//   k_dedrift_map_stats   one workgroup per listed map: its mean and the root of its summed squared deviations over the kept vertices (a fixed 256-leaf
+//                         tree each, reduce_device.hpp: block_sum).
+//   k_dedrift_masks       one workgroup per listed map: the two order statistics numpy.percentile interpolates between, by a radix select over an
+//                         order-preserving integer key (8 passes of 8 bits, integer LDS counters; the histogram counts kept keys, order statistics and
+//                         the interpolation take K); the threshold; the mask x > threshold as one ballot word per 64 kept vertices (bit j of a map's mask
+//                         belongs to the j-th kept vertex); its population count.
+//   k_dedrift_tile_cc     one workgroup per (tile of 8 x 8 listed subjects, feature): a lane loads one vertex of the tile's 16 map rows and feeds all 64
+//                         pairs from it, so a map row is read once per tile and not once per pair; the 64 sums of a lane are reduced over block_sum's
+//                         tree, eight side by side (tile_sums), and divided by the two roots.  The tile comes from the grid's coordinates (the lower
+//                         triangle's workgroups leave at once): no search for the pair.
+//   k_dedrift_tile_dice   the same tiling over the mask words: AND + popcount, integer sums over the same tree.  Integer work: exact.
+//   k_dedrift_pair_cc     for a small whole set without a mask (dedrift.cpp: kPerPairMax), where one or three tiles leave the device idle: one workgroup
+//                         per (pair, feature), the sum of products of deviations over the same tree, divided by the two roots: the tile kernel's bits.
+//   k_dedrift_pair_dice   its companion: one wavefront per (pair, feature), popcount of the ANDed masks.
+//   k_dedrift_pair_mean   one workgroup per matrix: the sum over the upper triangle (lane t takes the columns i + 1 + t, + 256, ... of every row i, rows
+//                         ascending; block_sum), divided by the number of pairs; NaN for a single subject.
 //
 // No floating-point atomics anywhere: every floating-point sum has a fixed shape, two runs give the same bits.
 #include "dedrift.hpp"
+#include "reduce_device.hpp"
 #include "strain_device.hpp"
 
 namespace msm {
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kSumBlock;
 constexpr int kWide = 1024;
-
-// the sum of one value per lane of a kBlock-wide workgroup, as a fixed binary tree over LDS (every lane gets it)
-__device__ __forceinline__ double block_sum(double v, double *lds) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (t < s) lds[t] += lds[t + s];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
-}
 
 __global__ __launch_bounds__(kBlock) void k_dedrift_accumulate(const int32_t *__restrict__ vid, const double *__restrict__ w, int Vt,
                                                                const double *__restrict__ m, int Vs, double *__restrict__ sum,
@@ -141,32 +128,19 @@ __global__ __launch_bounds__(kBlock) void k_vertex_distortion(const double *__re
     out[(size_t)V + v] = n > 0 ? sr / n : 0.0;
 }
 
-__global__ __launch_bounds__(kBlock) void k_dedrift_moments(const double *__restrict__ maps, int S, size_t n, double *__restrict__ mean,
-                                                            double *__restrict__ sd) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double a = 0.0;
-    for (int s = 0; s < S; ++s) a += maps[(size_t)s * n + i];
-    const double mu = a / S;
-    double q = 0.0;
-    for (int s = 0; s < S; ++s) {
-        const double d = maps[(size_t)s * n + i] - mu;
-        q += d * d;
-    }
-    mean[i] = mu;
-    sd[i] = sqrt(q / S);
-}
+// the group statistics read the resident maps through a list of subjects: position a is subject list[a], or subject a where list is nullptr
+__device__ __forceinline__ int listed(const int32_t *list, int a) { return list ? list[a] : a; }
 
-__global__ __launch_bounds__(kBlock) void k_dedrift_moments_list(const double *__restrict__ maps, const int32_t *__restrict__ list, int S, size_t n,
-                                                                 double *__restrict__ mean, double *__restrict__ sd) {
+__global__ __launch_bounds__(kBlock) void k_dedrift_moments(const double *__restrict__ maps, const int32_t *__restrict__ list, int S, size_t n,
+                                                            double *__restrict__ mean, double *__restrict__ sd) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double a = 0.0;
-    for (int s = 0; s < S; ++s) a += maps[(size_t)list[s] * n + i];
+    for (int s = 0; s < S; ++s) a += maps[(size_t)listed(list, s) * n + i];
     const double mu = a / S;
     double q = 0.0;
     for (int s = 0; s < S; ++s) {
-        const double d = maps[(size_t)list[s] * n + i] - mu;
+        const double d = maps[(size_t)listed(list, s) * n + i] - mu;
         q += d * d;
     }
     mean[i] = mu;
@@ -194,56 +168,17 @@ __device__ __forceinline__ void map_mean_root(const X x, int n, double *lds, dou
     root = sqrt(block_sum(q, lds));
 }
 
-__global__ __launch_bounds__(kBlock) void k_dedrift_map_stats(const double *__restrict__ maps, int Vt, double *__restrict__ stats) {
-    __shared__ double lds[kBlock];
-    double mu, root;
-    map_mean_root(maps + (size_t)blockIdx.x * Vt, Vt, lds, mu, root);
-    if (threadIdx.x == 0) stats[2 * (size_t)blockIdx.x] = mu, stats[2 * (size_t)blockIdx.x + 1] = root;
-}
-
 // workgroup a * D + d: row d of listed subject a, over the K kept vertices (kept == nullptr: all Vt = K of them)
-__global__ __launch_bounds__(kBlock) void k_dedrift_map_stats_sel(const double *__restrict__ maps, const int32_t *__restrict__ list, int D, int Vt,
-                                                                  const int32_t *__restrict__ kept, int K, double *__restrict__ stats) {
+__global__ __launch_bounds__(kBlock) void k_dedrift_map_stats(const double *__restrict__ maps, const int32_t *__restrict__ list, int D, int Vt,
+                                                              const int32_t *__restrict__ kept, int K, double *__restrict__ stats) {
     __shared__ double lds[kBlock];
-    const double *x = maps + ((size_t)list[blockIdx.x / D] * D + blockIdx.x % D) * Vt;
+    const double *x = maps + ((size_t)listed(list, blockIdx.x / D) * D + blockIdx.x % D) * Vt;
     double mu, root;
     if (kept)
         map_mean_root(KeptRow{x, kept}, K, lds, mu, root);
     else
         map_mean_root(x, K, lds, mu, root);
     if (threadIdx.x == 0) stats[2 * (size_t)blockIdx.x] = mu, stats[2 * (size_t)blockIdx.x + 1] = root;
-}
-
-// pair p of the list (0,1) (0,2) ... (0,S-1) (1,2) ...
-__device__ __forceinline__ void pair_of(int p, int S, int &i, int &j) {
-    i = 0;
-    while (p >= S - 1 - i) p -= S - 1 - i, ++i;
-    j = i + 1 + p;
-}
-
-__global__ __launch_bounds__(kBlock) void k_dedrift_pair_cc(const double *__restrict__ maps, int S, int D, int Vt, const double *__restrict__ stats,
-                                                            double *__restrict__ cc) {
-    __shared__ double lds[kBlock];
-    const int d = blockIdx.y, npairs = S * (S - 1) / 2;
-    if ((int)blockIdx.x >= npairs) {  // the S workgroups after the pairs: the diagonal
-        const int s = blockIdx.x - npairs;
-        if (threadIdx.x == 0) cc[((size_t)d * S + s) * S + s] = 1.0;
-        return;
-    }
-    int i, j;
-    pair_of(blockIdx.x, S, i, j);
-    const size_t mi = (size_t)i * D + d, mj = (size_t)j * D + d;
-    const double *x = maps + mi * Vt, *y = maps + mj * Vt;
-    const double mx = stats[2 * mi], my = stats[2 * mj];
-    double a = 0.0;
-    for (int k = threadIdx.x; k < Vt; k += kBlock) a += (x[k] - mx) * (y[k] - my);
-    const double dot = block_sum(a, lds);
-    if (threadIdx.x == 0) {
-        const double r = dot / (stats[2 * mi + 1] * stats[2 * mj + 1]);
-        double *out = cc + (size_t)d * S * S;
-        out[(size_t)i * S + j] = r;
-        out[(size_t)j * S + i] = r;
-    }
 }
 
 // an integer key with the order of the doubles (negative values: all bits flipped; others: the sign bit set)
@@ -327,20 +262,49 @@ __device__ __forceinline__ void percentile_mask(const X x, int n, int k, double 
     if (t == 0) thr_out[out] = thr, count[out] = s_cnt;
 }
 
-__global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restrict__ maps, int Vt, int k, double gamma, double *__restrict__ thr_out,
-                                                         unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
-    percentile_mask(maps + (size_t)blockIdx.x * Vt, Vt, k, gamma, blockIdx.x, thr_out, bits, words, count);
-}
-
 // workgroup a * D + d: row d of listed subject a, over the K kept vertices (kept == nullptr: all Vt = K of them); words = ceil(K / 64)
-__global__ __launch_bounds__(kWide) void k_dedrift_masks_sel(const double *__restrict__ maps, const int32_t *__restrict__ list, int D, int Vt,
-                                                             const int32_t *__restrict__ kept, int K, int k, double gamma, double *__restrict__ thr_out,
-                                                             unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
-    const double *x = maps + ((size_t)list[blockIdx.x / D] * D + blockIdx.x % D) * Vt;
+__global__ __launch_bounds__(kWide) void k_dedrift_masks(const double *__restrict__ maps, const int32_t *__restrict__ list, int D, int Vt,
+                                                         const int32_t *__restrict__ kept, int K, int k, double gamma, double *__restrict__ thr_out,
+                                                         unsigned long long *__restrict__ bits, int words, int32_t *__restrict__ count) {
+    const double *x = maps + ((size_t)listed(list, blockIdx.x / D) * D + blockIdx.x % D) * Vt;
     if (kept)
         percentile_mask(KeptRow{x, kept}, K, k, gamma, blockIdx.x, thr_out, bits, words, count);
     else
         percentile_mask(x, K, k, gamma, blockIdx.x, thr_out, bits, words, count);
+}
+
+// --- the whole set without a mask, up to dedrift.cpp's kPerPairMax subjects: one workgroup per pair, which a few pairs finish sooner than a tile does.
+// The same sums over the same tree as the tile kernels: the same bits.
+// pair p of the list (0,1) (0,2) ... (0,S-1) (1,2) ...
+__device__ __forceinline__ void pair_of(int p, int S, int &i, int &j) {
+    i = 0;
+    while (p >= S - 1 - i) p -= S - 1 - i, ++i;
+    j = i + 1 + p;
+}
+
+__global__ __launch_bounds__(kBlock) void k_dedrift_pair_cc(const double *__restrict__ maps, int S, int D, int Vt, const double *__restrict__ stats,
+                                                            double *__restrict__ cc) {
+    __shared__ double lds[kBlock];
+    const int d = blockIdx.y, npairs = S * (S - 1) / 2;
+    if ((int)blockIdx.x >= npairs) {  // the S workgroups after the pairs: the diagonal
+        const int s = blockIdx.x - npairs;
+        if (threadIdx.x == 0) cc[((size_t)d * S + s) * S + s] = 1.0;
+        return;
+    }
+    int i, j;
+    pair_of(blockIdx.x, S, i, j);
+    const size_t mi = (size_t)i * D + d, mj = (size_t)j * D + d;
+    const double *x = maps + mi * Vt, *y = maps + mj * Vt;
+    const double mx = stats[2 * mi], my = stats[2 * mj];
+    double a = 0.0;
+    for (int k = threadIdx.x; k < Vt; k += kBlock) a += (x[k] - mx) * (y[k] - my);
+    const double dot = block_sum(a, lds);
+    if (threadIdx.x == 0) {
+        const double r = dot / (stats[2 * mi + 1] * stats[2 * mj + 1]);
+        double *out = cc + (size_t)d * S * S;
+        out[(size_t)i * S + j] = r;
+        out[(size_t)j * S + i] = r;
+    }
 }
 
 __global__ __launch_bounds__(64) void k_dedrift_pair_dice(const unsigned long long *__restrict__ bits, const int32_t *__restrict__ count, int S, int D,
@@ -371,25 +335,6 @@ __global__ __launch_bounds__(64) void k_dedrift_pair_dice(const unsigned long lo
 
 constexpr int kTile = 8;  // listed subjects along each side of a pair tile
 
-// kTile sums of one value per lane each, side by side over block_sum's tree; lane b < kTile returns sum b (the other lanes' value is not used)
-template <class T>
-__device__ __forceinline__ T tile_sums(const T (&v)[kTile], T (*lds)[kBlock]) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int b = 0; b < kTile; ++b) lds[b][t] = v[b];
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int b = 0; b < kTile; ++b) lds[b][t] += lds[b][t + s];
-        }
-        __syncthreads();
-    }
-    const T r = lds[t < kTile ? t : 0][0];
-    __syncthreads();
-    return r;
-}
-
 // workgroup (tj, ti, d), ti <= tj: the pairs of the listed subjects ti * 8 + a and tj * 8 + b of feature d.  A position past the list's end reads
 // the list's last subject and writes nothing.  stats is indexed by list position.
 __global__ __launch_bounds__(kBlock) void k_dedrift_tile_cc(const double *__restrict__ maps, const int32_t *__restrict__ list, int n, int D, int Vt,
@@ -403,8 +348,8 @@ __global__ __launch_bounds__(kBlock) void k_dedrift_tile_cc(const double *__rest
 #pragma unroll
     for (int a = 0; a < kTile; ++a) {
         const int ia = min(ti * kTile + a, n - 1), ib = min(tj * kTile + a, n - 1);
-        xr[a] = maps + ((size_t)list[ia] * D + d) * Vt, mr[a] = stats[2 * ((size_t)ia * D + d)];
-        xc[a] = maps + ((size_t)list[ib] * D + d) * Vt, mc[a] = stats[2 * ((size_t)ib * D + d)];
+        xr[a] = maps + ((size_t)listed(list, ia) * D + d) * Vt, mr[a] = stats[2 * ((size_t)ia * D + d)];
+        xc[a] = maps + ((size_t)listed(list, ib) * D + d) * Vt, mc[a] = stats[2 * ((size_t)ib * D + d)];
     }
     double acc[kTile][kTile];
 #pragma unroll
@@ -508,16 +453,22 @@ int launch_vertex_distortion(msm_ctx *ctx, const double *d_m, const double *d_c,
     return MSM_OK;
 }
 
-int launch_dedrift_moments(msm_ctx *ctx, const double *d_maps, int S, size_t n, double *d_mean, double *d_sd) {
-    if (n == 0) return MSM_OK;
-    hipLaunchKernelGGL(k_dedrift_moments, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, d_maps, S, n, d_mean, d_sd);
+int launch_dedrift_moments(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, size_t nmap, double *d_mean, double *d_sd) {
+    if (nmap == 0) return MSM_OK;
+    hipLaunchKernelGGL(k_dedrift_moments, dim3((unsigned)((nmap + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, d_maps, d_list, n, nmap, d_mean, d_sd);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }
 
-int launch_dedrift_map_stats(msm_ctx *ctx, const double *d_maps, int nmaps, int Vt, double *d_stats) {
-    if (nmaps <= 0) return MSM_OK;
-    hipLaunchKernelGGL(k_dedrift_map_stats, dim3(nmaps), dim3(kBlock), 0, ctx->stream, d_maps, Vt, d_stats);
+int launch_dedrift_map_stats(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K, double *d_stats) {
+    hipLaunchKernelGGL(k_dedrift_map_stats, dim3(n * D), dim3(kBlock), 0, ctx->stream, d_maps, d_list, D, Vt, d_kept, K, d_stats);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_dedrift_masks(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K, int k, double gamma,
+                         double *d_thr, unsigned long long *d_bits, int words, int32_t *d_count) {
+    hipLaunchKernelGGL(k_dedrift_masks, dim3(n * D), dim3(kWide), 0, ctx->stream, d_maps, d_list, D, Vt, d_kept, K, k, gamma, d_thr, d_bits, words, d_count);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }
@@ -530,40 +481,9 @@ int launch_dedrift_pair_cc(msm_ctx *ctx, const double *d_maps, int S, int D, int
     return MSM_OK;
 }
 
-int launch_dedrift_masks(msm_ctx *ctx, const double *d_maps, int nmaps, int Vt, int k, double gamma, double *d_thr, unsigned long long *d_bits, int words,
-                         int32_t *d_count) {
-    if (nmaps <= 0) return MSM_OK;
-    hipLaunchKernelGGL(k_dedrift_masks, dim3(nmaps), dim3(kWide), 0, ctx->stream, d_maps, Vt, k, gamma, d_thr, d_bits, words, d_count);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
-}
-
 int launch_dedrift_pair_dice(msm_ctx *ctx, const unsigned long long *d_bits, const int32_t *d_count, int S, int D, int words, double *d_dice) {
     const int npairs = S * (S - 1) / 2;
     hipLaunchKernelGGL(k_dedrift_pair_dice, dim3(npairs + S, D), dim3(64), 0, ctx->stream, d_bits, d_count, S, D, words, d_dice);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
-}
-
-int launch_dedrift_moments_list(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, size_t nmap, double *d_mean, double *d_sd) {
-    if (nmap == 0) return MSM_OK;
-    hipLaunchKernelGGL(k_dedrift_moments_list, dim3((unsigned)((nmap + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, d_maps, d_list, n, nmap, d_mean,
-                       d_sd);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
-}
-
-int launch_dedrift_map_stats_sel(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K,
-                                 double *d_stats) {
-    hipLaunchKernelGGL(k_dedrift_map_stats_sel, dim3(n * D), dim3(kBlock), 0, ctx->stream, d_maps, d_list, D, Vt, d_kept, K, d_stats);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
-}
-
-int launch_dedrift_masks_sel(msm_ctx *ctx, const double *d_maps, const int32_t *d_list, int n, int D, int Vt, const int32_t *d_kept, int K, int k,
-                             double gamma, double *d_thr, unsigned long long *d_bits, int words, int32_t *d_count) {
-    hipLaunchKernelGGL(k_dedrift_masks_sel, dim3(n * D), dim3(kWide), 0, ctx->stream, d_maps, d_list, D, Vt, d_kept, K, k, gamma, d_thr, d_bits, words,
-                       d_count);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import oracle as O
 from tests import dedrift_literal as L
+from tests import hierarchy_literal as H
 
 pytestmark = pytest.mark.gpu
 
@@ -120,6 +121,34 @@ def test_handle_reset_and_call_order(ctx):
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
     assert all(np.array_equal(x, y) for x, y in zip(runs[0][2], runs[1][2]))
     d.close()
+
+
+@pytest.mark.parametrize("S", [1, 8, 9, 17, 65])
+def test_group_stats_across_the_pair_tiles(ctx, S):
+    """group_stats(75) against the restatement with every subject listed and no mask, on the ico3 template (642 vertices: the last ballot word is
+    partial), D = 2: a single subject, exactly one tile of 8 x 8 subjects, one past a tile, three tiles with a ragged edge -- sets this small go
+    through the per-pair kernels -- and 65 subjects, one past the size up to which they do: nine tiles a side with a ragged edge, read without a list.
+    The select over the whole set, which takes the tile kernels at any size, gives the same bits"""
+    import newmsm_amd as M
+    from newmsm_amd import dedrift
+
+    txyz, ttri = O.icosphere(3)
+    maps = [L.smooth_data(txyz, 2, s) for s in range(S)]
+    assert H.threshold_gaps(maps, None, 75) > 0, "a value ties with its percentile threshold"
+    want_mean, want_stdev, want_cc, want_dice = H.select_stats(maps, None, 75)[:4]
+    tmpl = M.Mesh(ctx, txyz, ttri)
+    d = dedrift.Dedrift(ctx, tmpl, S)
+    for s, m in enumerate(maps):
+        d.set_map(s, m)
+    mean, stdev, cc, dice = d.group_stats(75)
+    tiled = d.group_stats_select(list(range(S)), None, 75)
+    d.close()
+    tmpl.close()
+    assert close_rel(mean, want_mean, 1e-12) and close_rel(stdev, want_stdev, 1e-12)
+    assert np.abs(cc - want_cc).max() <= 1e-9
+    assert np.array_equal(cc[:, range(S), range(S)], np.ones((2, S)))
+    assert np.array_equal(dice, want_dice)
+    assert all(np.array_equal(a, b) for a, b in zip(tiled[:4], (mean, stdev, cc, dice)))
 
 
 def test_group_run_warps_at_ico6(ctx):

@@ -100,7 +100,7 @@ def test_the_whole_set_without_a_mask_is_group_stats(nine_maps):
     mean, stdev, cc, dice = d.group_stats(75)
     got = d.group_stats_select(list(range(9)), None, 75)
     assert np.array_equal(got[0], mean) and np.array_equal(got[1], stdev)  # the same arithmetic
-    assert np.abs(got[2] - cc).max() <= 1e-9
+    assert np.array_equal(got[2], cc)
     assert np.array_equal(got[3], dice)
     assert H.threshold_gaps(maps, None, 75) > 0
     compare_stats(dict(zip(KEYS, got)), literal_select(maps, list(range(9)), None, 75), "whole set")

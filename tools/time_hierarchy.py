@@ -1,15 +1,17 @@
-"""Times the hierarchy stage on the GPU: msm_dedrift_group_stats_select (the tiled pair kernels) against msm_dedrift_group_stats (one workgroup per pair)
-in the same run, the select under a mask and over a part of the resident set, and one hierarchy.merge_groups stage by stage.
+"""Times the hierarchy stage on the GPU: msm_dedrift_group_stats and msm_dedrift_group_stats_select over the whole set (one path: the select uploads
+a list, group_stats does not) in the same run, the select under a mask and over a part of the resident set, and one hierarchy.merge_groups stage by stage.
 
-    python tools/time_hierarchy.py [--order 6] [--rows 2] [--runs 10] [--warmup 3] [--out profiles/hierarchy_time.json]
+    python tools/time_hierarchy.py [--order 6] [--rows 2] [--sizes 64,256] [--runs 10] [--warmup 3] [--out profiles/hierarchy_time.json]
     python tools/time_hierarchy.py --once      one group_stats and one select at S = 256 only (for `rocprofv3 --kernel-trace --stats -- python ... --once`)
 
-(a) S = 64 and S = 256 synthetic maps through set_map: group_stats, and the select with every subject listed and no mask, alternating.  The two are
-    compared before a time is reported: mean and stdev bit-equal, cc to 1e-9 absolute, dice exactly.
-(b) at S = 256: the select under a mask that keeps about 90 % of the vertices, and with a 32-subject list.
+(a) for every S of --sizes, S synthetic maps through set_map: group_stats, the select with every subject listed and no mask, and group_stats a second
+    time (the same call twice: what the machine's noise does to a ratio), taking turns within every round.  The two entry points are compared before a
+    time is reported: every array bit-equal.
+(b) at S = 256, when it is among the sizes: the select under a mask that keeps about 90 % of the vertices, and with a 32-subject list.
 (c) one merge_groups of 2 x 32 subjects, the time of every call of its ops object summed per kind.
 Every timed call is complete on return (host arrays), so the host clock around it measures it.  Reported: the median of --runs after --warmup, with the
-fastest and the slowest run.  Prints one JSON line; --out also writes it to a file."""
+fastest and the slowest run; for (a) also the median and the quartiles of the ratios select / group_stats and group_stats again / group_stats, round by
+round.  Prints one JSON line; --out also writes it to a file."""
 import argparse
 import json
 import os
@@ -68,6 +70,12 @@ def figure(ms):
     return dict(median_ms=float(np.median(ms)), min_ms=float(np.min(ms)), max_ms=float(np.max(ms)))
 
 
+def spread(num, den):
+    """the ratio of two legs round by round: its median and quartiles"""
+    q1, med, q3 = np.percentile([x / y for x, y in zip(num, den)], [25, 50, 75])
+    return dict(median=float(med), q1=float(q1), q3=float(q3))
+
+
 def resident(ctx, tmpl, maps):
     d = dedrift.Dedrift(ctx, tmpl, len(maps))
     for s, m in enumerate(maps):
@@ -79,11 +87,9 @@ def assert_agreement(d, S):
     mean, stdev, cc, dice = d.group_stats(75.0)
     got = d.group_stats_select(list(range(S)), None, 75.0)
     assert np.array_equal(got[0], mean) and np.array_equal(got[1], stdev), "mean / stdev differ"
-    err = float(np.abs(got[2] - cc).max())
-    assert err <= 1e-9, "cc differs by %g" % err
+    assert np.array_equal(got[2], cc), "cc differs by %g" % float(np.abs(got[2] - cc).max())
     assert np.array_equal(got[3], dice), "dice differs"
     assert np.allclose(got[4], dedrift.pair_means(cc), rtol=0, atol=1e-9) and np.allclose(got[5], dedrift.pair_means(dice), rtol=1e-12, atol=0)
-    return err
 
 
 class ClockedOps(dedrift.ProductOps):
@@ -120,6 +126,7 @@ def main(argv):
     ap = argparse.ArgumentParser(prog="time_hierarchy.py")
     ap.add_argument("--order", type=int, default=6)
     ap.add_argument("--rows", type=int, default=2)
+    ap.add_argument("--sizes", default="64,256", help="the numbers of subjects of leg (a)")
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--once", action="store_true")
@@ -137,14 +144,15 @@ def main(argv):
         d.close()
         return 0
     result = dict(order=a.order, vertices=V, rows=D, runs=a.runs, warmup=a.warmup, whole_set={}, part={}, merge={})
-    for S in (64, 256):
+    for S in [int(x) for x in a.sizes.split(",")]:
         d = resident(ctx, tmpl, synthetic_maps(xyz, S, D))
-        err = assert_agreement(d, S)
+        assert_agreement(d, S)
         everyone = list(range(S))
-        t = alternating(dict(group_stats=lambda: d.group_stats(75.0), select=lambda: d.group_stats_select(everyone, None, 75.0)), a.runs, a.warmup)
-        ratio = [g / s for g, s in zip(t["group_stats"], t["select"])]
-        result["whole_set"][str(S)] = dict(group_stats=figure(t["group_stats"]), select=figure(t["select"]), cc_max_abs_diff=err,
-                                           group_stats_over_select=dict(median=float(np.median(ratio)), min=float(np.min(ratio)), max=float(np.max(ratio))))
+        t = alternating(dict(group_stats=lambda: d.group_stats(75.0), select=lambda: d.group_stats_select(everyone, None, 75.0),
+                             group_stats_again=lambda: d.group_stats(75.0)), a.runs, a.warmup)
+        result["whole_set"][str(S)] = dict(group_stats=figure(t["group_stats"]), select=figure(t["select"]), group_stats_again=figure(t["group_stats_again"]),
+                                           select_over_group_stats=spread(t["select"], t["group_stats"]),
+                                           again_over_group_stats=spread(t["group_stats_again"], t["group_stats"]))
         if S == 256:
             mask = (np.random.default_rng(1).uniform(size=V) < 0.9).astype(np.float64)
             some = [int(s) for s in np.random.default_rng(2).choice(S, 32, replace=False)]
