@@ -114,6 +114,14 @@ int msm_octree_signature(const double *xyz, const int32_t *tri, int32_t V, int32
  * [4] violations (must be 0) [5] triangles the table cannot use [6] triangles with exclusion boxes [7] simple surface [8] exclusion boxes
  * checked one by one (the centre of the leaf a box stands for must be refused) [9] sampled points refused by the boxes alone */
 int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[10]);
+/* testing hook, host only: the first-candidate hints of the direction table's cells (which of a cell's candidates a kernel tries first, by sub-cell),
+ * at nsamples random directions on the radius shell; a point's triangle is the one the first pass of Octree::get_closest_triangle returns, found as
+ * msm_ray_table_check finds it.  report: [0] points [1] points whose triangle is the hinted first candidate [2] points whose triangle is the first
+ * stored candidate, hints ignored [3] points whose triangle is anywhere in the cell's list [4] cells whose decoded candidates differ from the stored
+ * ones (must be 0) [5] cells [6] cells with more than four candidates [7] sub-cells per cell axis.  cells: NULL, or room for cells_cap words
+ * (4 x [5] are needed) that receive the cell array as stored. */
+int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
+                       int64_t cells_cap);
 
 /* ------------------------------------------------------------------------------------------------
  * context: one per GPU

@@ -142,6 +142,20 @@ def ray_table_check(xyz, tri, nsamples=20000, seed=1):
     return dict(points=rep[0], by_float=rep[1], by_fp64=rep[2], open=rep[3], violations=rep[4], unusable=rep[5], with_exclusions=rep[6], simple=bool(rep[7]), boxes_checked=rep[8], refused_by_boxes=rep[9])
 
 
+def ray_hint_check(xyz, tri, nsamples=20000, seed=1, return_cells=False):
+    """[host] how often the direction table's first candidate is the answer, with and without the cells' sub-cell hints, and that the hints leave
+    every cell's candidates alone (testing hook, msm_ray_hint_check).  return_cells: also the cell array as stored, (cells, 4) int32."""
+    x, px = _soa(xyz)
+    t, pt = _tri_soa(tri)
+    rep = (C.c_int64 * 8)()
+    cells = np.zeros((6 * 512 * 512, 4), dtype=np.int32) if return_cells else None  # (the largest table build_ray_table makes)
+    check(lib().msm_ray_hint_check(px, pt, x.shape[1], t.shape[1], nsamples, seed, rep, cells.ctypes.data_as(c_ip) if return_cells else None, cells.size if return_cells else 0))
+    out = dict(points=rep[0], hinted=rep[1], unhinted=rep[2], listed=rep[3], cells_changed=rep[4], cells=rep[5], cells_with_more=rep[6], subcells=rep[7])
+    if return_cells:
+        out["cell_array"] = cells[: rep[5]].copy()
+    return out
+
+
 def estimate_triplets(tri):
     t, pt = _tri_soa(tri)
     out = np.zeros((t.shape[1], 3), dtype=np.int32)

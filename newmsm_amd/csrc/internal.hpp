@@ -64,6 +64,20 @@ static_assert(sizeof(TriRec) == 128, "TriRec must be 128 bytes");
 // (kernels.hip: k_build_raytri).
 constexpr int kRayPieces = 9;
 
+// First-candidate hints of a direction cell.  A cell is cut into kRayHintK x kRayHintK sub-cells, and two bits per sub-cell
+// say which of the candidates stored in the cell itself (x, y, z, and w when it is an id) to try first: the one whose
+// gnomonic triangle holds the sub-cell's centre, 0 = the stored order.  They ride in the top 6 bits of x, y, z -- word
+// su (x, y, z for su = 0, 1, 2), bits 26 + 2 sv -- above a 26-bit two's-complement id (-1 = none; w keeps all 32 bits
+// for an id, -1 or the ray_more reference).  The order of trial cannot change a result: at most one listed candidate
+// passes the acceptance test (octree.cpp).  kRayHintK = 1: no hints are written and none are read.
+#ifndef MSM_RAY_HINT_K
+#define MSM_RAY_HINT_K 3
+#endif
+constexpr int kRayHintK = MSM_RAY_HINT_K;
+static_assert(kRayHintK >= 1 && kRayHintK <= 3, "two bits per sub-cell, three sub-cells per word, three words");
+constexpr int kRayIdBits = 26;
+constexpr int kRayMaxTris = 1 << (kRayIdBits - 1);  // a mesh with more triangles gets no table (build_ray_table)
+
 // Direction (ray) table of a simple surface (octree.cpp: build_ray_table), the host side; G == 0 when absent.
 struct RayTable {
     // closed, consistently oriented, star-shaped about the origin, covering the sphere exactly once: every ray from

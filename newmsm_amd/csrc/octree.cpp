@@ -21,6 +21,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <unordered_map>
 
@@ -325,10 +326,38 @@ bool lacking_leaves(const FlatOctree &o, int n, const double lo[3], const double
 //                on a leaf boundary with 2 x 2 leaves beyond it -- and every sample in them went to the complete search.)
 // Record layout (three float4 per triangle): {n0, thr} {n1, bits of the ray_excl index or -1} {n2, 0}.
 // The cube-map cells only propose candidates, likeliest first: {c0,c1,c2,c3}, or {c0,c1,c2,-2-k} with c3..c6 in
-// ray_more[k]; a miss just means the complete search.
+// ray_more[k]; a miss just means the complete search.  The top bits of c0..c2 say which candidate to try first in each
+// sub-cell of the cell (internal.hpp: kRayHintK; search_device.hpp: ray_cell_of hands the cell out in that order).
 // ------------------------------------------------------------------------------------------------
 constexpr double kRayShell = 1e-4;
 constexpr int kRayExclMax = 7;
+
+// A triangle's gnomonic image on cube face f = 2*axis + (negative side) -- (u, v) = the two other components over |major
+// component| -- and its edge functions, oriented so that the third vertex is on the positive side.
+struct FaceTri {
+    double pu[3], pv[3], ex[3], ey[3], ox[3], oy[3], sg[3];
+    bool project(const V3 v[3], const double ln[3], int f) {  // false: a vertex is not well in front of the face
+        const int a = f >> 1, bb = (a + 1) % 3, cc = (a + 2) % 3;
+        const double sgn = (f & 1) ? -1.0 : 1.0;
+        for (int k = 0; k < 3; ++k) {
+            const double c[3] = {v[k].x, v[k].y, v[k].z};
+            const double w = sgn * c[a];
+            if (!(w > 0.05 * ln[k])) return false;
+            pu[k] = c[bb] / w;
+            pv[k] = c[cc] / w;
+        }
+        return true;
+    }
+    void edges() {
+        for (int k = 0; k < 3; ++k) {
+            const int p = (k + 1) % 3, q = (k + 2) % 3;
+            ex[k] = pu[q] - pu[p], ey[k] = pv[q] - pv[p], ox[k] = pu[p], oy[k] = pv[p];
+            sg[k] = (ex[k] * (pv[k] - oy[k]) - ey[k] * (pu[k] - ox[k])) >= 0 ? 1.0 : -1.0;
+        }
+    }
+    double E(int k, double x, double y) const { return sg[k] * (ex[k] * (y - oy[k]) - ey[k] * (x - ox[k])); }
+    bool holds(double x, double y) const { return E(0, x, y) >= 0 && E(1, x, y) >= 0 && E(2, x, y) >= 0; }
+};
 
 }  // namespace
 
@@ -340,6 +369,7 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
     out.rays.simple = simple_star_surface(xyz, tri, V, T);
     const char *no_table = std::getenv("MSMHIP_DISABLE_RAYTABLE");  // testing: force the complete search everywhere
     if (!out.rays.simple || (no_table && no_table[0] == '1')) return;
+    if (kRayHintK > 1 && T > kRayMaxTris) return;  // ids beyond the cell's id field: no table, the complete search everywhere
     TICK("simple");
     const std::vector<double> margin = safe_margins(xyz, tri, V, T);
     TICK("margins");
@@ -471,43 +501,23 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
         const V3 v[3] = {vtx(xyz, V, tri[t]), vtx(xyz, V, tri[T + t]), vtx(xyz, V, tri[2 * T + t])};
         const double ln[3] = {norm(v[0]), norm(v[1]), norm(v[2])};
         for (int f = 0; f < 6; ++f) {
-            const int a = f >> 1, bb = (a + 1) % 3, cc = (a + 2) % 3;
-            const double sgn = (f & 1) ? -1.0 : 1.0;
-            double pu[3], pv[3];
-            bool front = true;
-            for (int k = 0; k < 3; ++k) {
-                const double c[3] = {v[k].x, v[k].y, v[k].z};
-                const double w = sgn * c[a];
-                if (!(w > 0.05 * ln[k])) {
-                    front = false;
-                    break;
-                }
-                pu[k] = c[bb] / w;
-                pv[k] = c[cc] / w;
-            }
-            if (!front) continue;
+            FaceTri ft;
+            if (!ft.project(v, ln, f)) continue;
+            const double *pu = ft.pu, *pv = ft.pv;
             const double umin = std::fmin(pu[0], std::fmin(pu[1], pu[2])) - m, umax = std::fmax(pu[0], std::fmax(pu[1], pu[2])) + m;
             const double vmin = std::fmin(pv[0], std::fmin(pv[1], pv[2])) - m, vmax = std::fmax(pv[0], std::fmax(pv[1], pv[2])) + m;
             if (umax < -1 || umin > 1 || vmax < -1 || vmin > 1) continue;
             auto cellof = [&](double x) { return std::max(0, std::min(G - 1, (int)std::floor((x + 1) * 0.5 * G))); };
             const int iu0 = cellof(umin), iu1 = cellof(umax), iv0 = cellof(vmin), iv1 = cellof(vmax);
             const double gu = (pu[0] + pu[1] + pu[2]) / 3, gv = (pv[0] + pv[1] + pv[2]) / 3;
-            // edge functions, oriented so that the third vertex is on the positive side
-            double ex[3], ey[3], ox[3], oy[3], sg[3];
-            for (int k = 0; k < 3; ++k) {
-                const int p = (k + 1) % 3, q = (k + 2) % 3;
-                ex[k] = pu[q] - pu[p], ey[k] = pv[q] - pv[p], ox[k] = pu[p], oy[k] = pv[p];
-                sg[k] = (ex[k] * (pv[k] - oy[k]) - ey[k] * (pu[k] - ox[k])) >= 0 ? 1.0 : -1.0;
-            }
+            ft.edges();
             for (int iu = iu0; iu <= iu1; ++iu)
                 for (int iv = iv0; iv <= iv1; ++iv) {
                     const double x0 = -1 + 2.0 * iu / G - m, x1 = -1 + 2.0 * (iu + 1) / G + m;
                     const double y0 = -1 + 2.0 * iv / G - m, y1 = -1 + 2.0 * (iv + 1) / G + m;
                     bool sep = false;  // a triangle edge with the whole (grown) cell strictly outside
-                    for (int k = 0; k < 3 && !sep; ++k) {
-                        auto E = [&](double x, double y) { return sg[k] * (ex[k] * (y - oy[k]) - ey[k] * (x - ox[k])); };
-                        sep = E(x0, y0) < 0 && E(x1, y0) < 0 && E(x0, y1) < 0 && E(x1, y1) < 0;
-                    }
+                    for (int k = 0; k < 3 && !sep; ++k)
+                        sep = ft.E(k, x0, y0) < 0 && ft.E(k, x1, y0) < 0 && ft.E(k, x0, y1) < 0 && ft.E(k, x1, y1) < 0;
                     if (sep) continue;
                     const double cu = 0.5 * (x0 + x1) - gu, cv = 0.5 * (y0 + y1) - gv;
                     const size_t cell = ((size_t)f * G + iu) * G + iv;
@@ -552,6 +562,51 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
         }
     }
     TICK("cells");
+    // first-candidate hints (internal.hpp: kRayHintK): per sub-cell, the first of the candidates stored in the cell itself whose
+    // image on the face holds the sub-cell's centre; none: 0, the ranked order.  Cell by cell, from the cell's own content only.
+    if (kRayHintK > 1) {
+        parallel_chunks((int)ncell, workers, [&](int, int c_begin, int c_end) {
+            for (int c = c_begin; c < c_end; ++c) {
+                int4 &cell = out.rays.cell[c];
+                const int f = c / (G * G), iu = (c / G) % G, iv = c % G;
+                const int ids[4] = {cell.x, cell.y, cell.z, cell.w};
+                FaceTri ft[4];
+                int state[4] = {0, 0, 0, 0};  // 0: not set up yet, 1: usable, -1: not a candidate of this cell
+                auto holds = [&](int j, double x, double y) {
+                    if (state[j] == 0) {
+                        const int t = ids[j];
+                        state[j] = -1;
+                        if (t >= 0) {  // (a negative w: no candidate, or the ray_more reference)
+                            const V3 v[3] = {vtx(xyz, V, tri[t]), vtx(xyz, V, tri[T + t]), vtx(xyz, V, tri[2 * (size_t)T + t])};
+                            const double ln[3] = {0.0, 0.0, 0.0};  // (the rasteriser found it on this face: it is in front)
+                            if (ft[j].project(v, ln, f)) {
+                                ft[j].edges();
+                                state[j] = 1;
+                            }
+                        }
+                    }
+                    return state[j] > 0 && ft[j].holds(x, y);
+                };
+                uint32_t bits[3] = {0u, 0u, 0u};
+                for (int su = 0; su < kRayHintK && ids[1] >= 0; ++su)  // (a single candidate: nothing to choose)
+                    for (int sv = 0; sv < kRayHintK; ++sv) {
+                        const double x = -1 + 2.0 * (iu + (su + 0.5) / kRayHintK) / G, y = -1 + 2.0 * (iv + (sv + 0.5) / kRayHintK) / G;
+                        uint32_t h = 0;
+                        for (int j = 0; j < 4; ++j)
+                            if (holds(j, x, y)) {
+                                h = (uint32_t)j;
+                                break;
+                            }
+                        bits[su] |= h << (kRayIdBits + 2 * sv);
+                    }
+                const uint32_t idmask = (1u << kRayIdBits) - 1u;
+                cell.x = (int32_t)(((uint32_t)cell.x & idmask) | bits[0]);
+                cell.y = (int32_t)(((uint32_t)cell.y & idmask) | bits[1]);
+                cell.z = (int32_t)(((uint32_t)cell.z & idmask) | bits[2]);
+            }
+        });
+        TICK("hints");
+    }
 }
 
 namespace {
@@ -887,6 +942,98 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
         if (by_float) ++report[1];
         else if (by_fp64) ++report[2];
         else ++report[3];
+    }
+    return MSM_OK;
+}
+
+// Testing hook, host only: what the first-candidate hints of the direction cells (internal.hpp: kRayHintK) are worth, and that they leave the
+// candidates alone.  `nsamples` random directions on the radius shell; a point's triangle is the one the reference's first pass returns, found as
+// msm_ray_table_check finds it (the only listed triangle of the point's leaf that passes the inside test; a point without one counts in [0] only).
+// report: [0] points, [1] points whose triangle is ray_cell_of(...).x, [2] points whose triangle is the cell's first stored candidate (hints ignored),
+// [3] points whose triangle is anywhere in the cell's list (ray_more included), [4] CELLS WHOSE DECODED CANDIDATES DIFFER FROM THE STORED ONES in some
+// sub-cell (must be 0: the same ids, the others in their stored order, a ray_more reference where it was, a first candidate whenever there is one),
+// [5] cells, [6] cells that use ray_more, [7] kRayHintK.  cells (may be NULL): the cell array as stored, 4 x [5] words, when cells_cap holds it.
+extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
+                                  int64_t cells_cap) {
+    using namespace msm;
+    if (!xyz || !tri || !report || V <= 0 || T <= 0 || nsamples < 0) return fail(MSM_ERR_INVALID, "msm_ray_hint_check: bad arguments");
+    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
+        if (tri[i] < 0 || tri[i] >= V) return fail(MSM_ERR_INVALID, "msm_ray_hint_check: triangle vertex id %d out of range [0,%d)", tri[i], V);
+    FlatOctree o;
+    build_octree(xyz, tri, V, T, o);
+    build_ray_table(xyz, tri, V, T, o);
+    for (int k = 0; k < 8; ++k) report[k] = 0;
+    report[7] = kRayHintK;
+    if (o.rays.G <= 0) return MSM_OK;
+    const size_t ncell = o.rays.cell.size();
+    report[5] = (int64_t)ncell;
+    if (cells) {
+        if (cells_cap < 4 * (int64_t)ncell) return fail(MSM_ERR_INVALID, "msm_ray_hint_check: room for %lld words, the cells have %lld", (long long)cells_cap, (long long)(4 * ncell));
+        std::memcpy(cells, o.rays.cell.data(), ncell * sizeof(int4));
+    }
+    for (size_t c = 0; c < ncell; ++c) {
+        const int4 raw = o.rays.cell[c], ids = ray_cell_ids(raw);
+        if (ids.x >= 0 && ids.w < -1) ++report[6];
+        const int stored[4] = {ids.x, ids.y, ids.z, ids.w};
+        bool same = true;
+        for (int k = 0; k < 4; ++k) same = same && stored[k] < T && (stored[k] >= -1 || (k == 3 && -2 - stored[k] < (int)o.rays.more.size()));
+        for (int su = 0; su < kRayHintK && same; ++su)
+            for (int sv = 0; sv < kRayHintK && same; ++sv) {
+                const int h = ray_cell_hint(raw, su, sv);
+                const int4 d = ray_cell_first(raw, h);
+                const int got[4] = {d.x, d.y, d.z, d.w};
+                same = got[0] == stored[h] && (stored[0] < 0 || got[0] >= 0);
+                for (int k = 0, j = 1; k < 4; ++k)  // the others behind it, in their stored order
+                    if (k != h) same = same && got[j++] == stored[k];
+            }
+        if (!same) ++report[4];
+    }
+    DevTree dt{};
+    dt.ray_G = o.rays.G;
+    dt.ray_cell = o.rays.cell.data();
+    dt.ray_more = o.rays.more.data();
+    dt.ray_excl = o.rays.excl.data();
+    dt.ray_r2lo = o.rays.r2lo, dt.ray_r2hi = o.rays.r2hi;
+    uint64_t rs = seed * 6364136223846793005ull + 1442695040888963407ull;
+    auto rnd = [&]() {  // uniform in [0, 1)
+        rs = rs * 6364136223846793005ull + 1442695040888963407ull;
+        return (double)(rs >> 11) * (1.0 / 9007199254740992.0);
+    };
+    auto vert = [&](int t, int k) { return vtx(xyz, V, tri[(size_t)k * T + t]); };
+    for (int it = 0; it < nsamples; ++it) {
+        V3 p;
+        do p = mk(2 * rnd() - 1, 2 * rnd() - 1, 2 * rnd() - 1);
+        while (!(norm(p) > 0.1 && norm(p) <= 1.0));
+        p = scale(normalized(p), kRad);
+        ++report[0];
+        int n = 0;  // the reference's first pass: descend to the leaf, every listed triangle through the inside test
+        while (o.node[n].x >= 0) {
+            const double4 b = o.nodebox[n];
+            const double mx = (b.x + (b.x + b.w)) / 2.0, my = (b.y + (b.y + b.w)) / 2.0, mz = (b.z + (b.z + b.w)) / 2.0;
+            n = o.node[n].x + 4 * (!(p.x < mx)) + 2 * (!(p.y < my)) + (!(p.z < mz));
+        }
+        int answer = -1, nhits = 0;
+        for (int e = 0; e < -o.node[n].x - 1; ++e) {
+            const int t = o.leaf_tri[o.node[n].y + e];
+            const V3 a = vert(t, 0), b = vert(t, 1), c = vert(t, 2);
+            if (point_in_triangle(project_point(p, a, b, c), a, b, c)) answer = t, ++nhits;
+        }
+        if (nhits != 1) continue;
+        float fx, fy, fz;
+        size_t at;
+        int su, sv;
+        if (!ray_cell_at(dt, p, fx, fy, fz, at, su, sv)) continue;
+        const int4 first = ray_cell_of(dt, p, fx, fy, fz), ids = ray_cell_ids(o.rays.cell[at]);
+        if (first.x == answer) ++report[1];
+        if (ids.x == answer) ++report[2];
+        int4 more = make_int4(ids.w, -1, -1, -1);
+        if (ids.x >= 0 && ids.w < -1) more = o.rays.more[-2 - ids.w];
+        const int list[7] = {ids.x, ids.y, ids.z, more.x, more.y, more.z, more.w};
+        for (int k = 0; k < 7; ++k)
+            if (list[k] == answer) {
+                ++report[3];
+                break;
+            }
     }
     return MSM_OK;
 }

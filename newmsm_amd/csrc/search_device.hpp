@@ -57,10 +57,28 @@ MSM_HD float ray_rsqrt(float x) {
     return 1.0f / sqrtf(x);
 #endif
 }
-MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, float &fz) {
+// A stored cell (internal.hpp: kRayHintK): its ids in the stored order, the hint of one of its sub-cells, and the
+// cell as the kernels take it -- candidate h first, the others behind it in their stored order.
+MSM_HD int ray_cell_id(int word) { return (int)((unsigned)word << (32 - kRayIdBits)) >> (32 - kRayIdBits); }
+MSM_HD int4 ray_cell_ids(const int4 &raw) {
+    if (kRayHintK == 1) return raw;
+    return make_int4(ray_cell_id(raw.x), ray_cell_id(raw.y), ray_cell_id(raw.z), raw.w);
+}
+MSM_HD int ray_cell_hint(const int4 &raw, int su, int sv) {
+    if (kRayHintK == 1) return 0;
+    const unsigned word = (unsigned)(su == 0 ? raw.x : (su == 1 ? raw.y : raw.z));
+    return (int)((word >> (kRayIdBits + 2 * sv)) & 3u);
+}
+MSM_HD int4 ray_cell_first(const int4 &raw, int h) {
+    const int4 c = ray_cell_ids(raw);
+    if (kRayHintK == 1) return c;
+    return make_int4(h == 0 ? c.x : (h == 1 ? c.y : (h == 2 ? c.z : c.w)), h >= 1 ? c.x : c.y, h >= 2 ? c.y : c.z, h == 3 ? c.z : c.w);
+}
+// the cell of p and the sub-cell of p in it; false when p is off the shell (fx = fy = fz = 0 then)
+MSM_HD bool ray_cell_at(const DevTree &T, const V3 &p, float &fx, float &fy, float &fz, size_t &at, int &su, int &sv) {
     const double r2 = p.x * p.x + p.y * p.y + p.z * p.z;
     fx = fy = fz = 0.f;
-    if (!(r2 >= T.ray_r2lo && r2 <= T.ray_r2hi)) return make_int4(-1, -1, -1, -1);
+    if (!(r2 >= T.ray_r2lo && r2 <= T.ray_r2hi)) return false;
     const float qx = (float)p.x, qy = (float)p.y, qz = (float)p.z;
     const float inv = ray_rsqrt(qx * qx + qy * qy + qz * qz);
     fx = qx * inv, fy = qy * inv, fz = qz * inv;
@@ -76,9 +94,31 @@ MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, flo
     }
     const float iw = 1.0f / w, half = 0.5f * (float)T.ray_G;
     const int G = T.ray_G;
-    const int iu = ray_clamp((int)((u * iw + 1.0f) * half), G - 1);
-    const int iv = ray_clamp((int)((v * iw + 1.0f) * half), G - 1);
-    return T.ray_cell[((size_t)face * G + iu) * G + iv];
+    const float gu = (u * iw + 1.0f) * half, gv = (v * iw + 1.0f) * half;
+    const int iu = ray_clamp((int)gu, G - 1);
+    const int iv = ray_clamp((int)gv, G - 1);
+    su = ray_clamp((int)((gu - (float)iu) * (float)kRayHintK), kRayHintK - 1);  // (gu - iu is exact; the clamp is for the rim of a face)
+    sv = ray_clamp((int)((gv - (float)iv) * (float)kRayHintK), kRayHintK - 1);
+    at = ((size_t)face * G + iu) * G + iv;
+    return true;
+}
+MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, float &fz) {
+    size_t at;
+    int su, sv;
+    if (!ray_cell_at(T, p, fx, fy, fz, at, su, sv)) return make_int4(-1, -1, -1, -1);
+    const int4 raw = T.ray_cell[at];
+    int4 c = ray_cell_first(raw, ray_cell_hint(raw, su, sv));
+#ifdef __HIP_DEVICE_COMPILE__
+    // the decoded cell in one register quadruple, as the load delivered it before there were hints: without this the allocator
+    // scatters the four ids and k_unary_rays needs 74 registers instead of 72, which is a wavefront per SIMD
+    if (kRayHintK > 1) {
+        typedef int v4i __attribute__((ext_vector_type(4)));
+        v4i q = {c.x, c.y, c.z, c.w};
+        asm volatile("" : "+v"(q));
+        c = make_int4(q.x, q.y, q.z, q.w);
+    }
+#endif
+    return c;
 }
 
 // the acceptance test of one candidate: all three edge-plane products at or above the triangle's threshold (e0.w)

@@ -378,7 +378,8 @@ __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
 //
 // The kernel is bound by the vector L1's line-lookup rate (one 128-byte line per cycle per CU: a load whose 64
 // lanes hit 64 different lines costs 64 cycles, whatever its width), not by HBM or the ALUs: about 13 line
-// lookups per sample (cell 1, edge planes 3, vertices + features 6, retries) = 4.1e7 per table, 161 k cycles per CU.
+// lookups per sample (cell 1, edge planes 3, vertices + features 6, retries) = 4.1e7 per table, 161 k cycles per CU,
+// before the cells named their first candidate by sub-cell; DESIGN.md section 5.2 has the counters with and without the hints.
 // Two variants in which the wavefront fetches the 64 records as a team (lane j of load k reads piece (64k+j) % 9 of
 // the record of lane (64k+j) / 9, straight into LDS with global_load_lds_dwordx4) halved the lookups, but at 9 KB of
 // LDS per wavefront they cut the occupancy to 3 waves per SIMD and lengthen the dependent chain (shuffle -> load ->
@@ -430,8 +431,9 @@ __global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
         }
         if (act) {
             if (c.x >= 0) {
-                // the first candidate is the answer three times out of four: its vertices are requested together with
-                // its edge planes, so a settled sample costs two dependent loads after the cell
+                // the first candidate -- the one the cell's hint names for this sub-cell (ray_cell_of) -- is the answer nine times
+                // out of ten (three out of four for the best-ranked candidate of the whole cell): its vertices are requested
+                // together with its edge planes, so a settled sample costs two dependent loads after the cell
                 const float4 *rec = a.tree.ray_tri + (size_t)kRayPieces * c.x;
                 const float4 e0 = rec[0], e1 = rec[1], e2 = rec[2];
                 const double2 *dv = reinterpret_cast<const double2 *>(rec + 3);
@@ -443,7 +445,7 @@ __global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
                     t = -1;
                     int4 mo = make_int4(c.w, -1, -1, -1);
                     if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
-                    // a real loop, not unrolled: this path is taken by one lane in four and must not cost registers
+                    // a real loop, not unrolled: this path is taken by one lane in ten and must not cost registers
 #pragma unroll 1
                     for (int k = 0; k < 6 && t < 0; ++k) {
                         const int ck = k == 0 ? c.y : (k == 1 ? c.z : (k == 2 ? mo.x : (k == 3 ? mo.y : (k == 4 ? mo.z : mo.w))));
