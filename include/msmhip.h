@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 11  /* 11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 11  /* 11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -243,6 +243,44 @@ int msm_nearest_neighbour(msm_mesh *orig, const double *data, int32_t D, const d
 /* [host] create_exclusion R/mesh.cpp:1257-1273: excl[i] = 1 when some feature of vertex i lies outside [thrl - EPSILON,
  * thru + EPSILON], else 0 (as written in the reference: the mask marks the vertices to cut with 1).  data D x V. */
 int msm_create_exclusion(const double *data, int32_t D, int32_t V, double thrl, double thru, double *excl);
+
+/* ------------------------------------------------------------------------------------------------
+ * resampling plan: the weights of one (in_mesh -> new_mesh) pair built once and applied to any number of maps.  Replaces the bodies of the
+ * reference's resampler programs (R/../demo: metric-resample, NN-resample, surface-resample) and of `wb_command -metric-resample` /
+ * `-label-resample` in its scripts (gMSM_scripts/run_gMSM.sh:95), which rebuild two octrees and the weights for every file.
+ * A plan is a SNAPSHOT: it owns device copies of its rows (and of excl), so later calls on the context, msm_mesh_update_coords on either mesh or
+ * destroying either mesh do not change what it does.  It belongs to in_mesh's context: destroy it before that context.
+ * Data and results are D x V row-major (one map after another); D is 64-bit.
+ * Arithmetic of an apply, for row k and map d: acc = 0.0; for the row's entries in stored order, skipping col < 0 and, with a mask, excl[col] == 0:
+ * acc += (double)data[d][col] * val (FP64, product and sum rounded separately).  MSM_F64 stores acc, MSM_F32 stores (float)acc (one rounding to nearest
+ * even); a row without kept entries gives 0.  Two runs give the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct msm_resample_plan msm_resample_plan;
+#define MSM_RESAMPLE_ADAP_BARY   0  /* Resampler::get_adaptive_barycentric_weights, R/resampler.cpp:72-140: metric_resample's rows */
+#define MSM_RESAMPLE_BARYCENTRIC 1  /* get_barycentric_weights :142-167 of new_mesh's vertices on in_mesh, ascending ids: surface_resample's rows (:284-302) */
+#define MSM_RESAMPLE_NEAREST     2  /* nearest_neighbour_interpolation :232-258: one entry of weight 1 per row */
+#define MSM_F64 0
+#define MSM_F32 1
+/* excl: V(in_mesh) values (the EXCL mesh's data, 0 = excluded) or NULL.  NULL on failure (msm_last_error): meshes of different contexts, an unknown
+ * method, a failed search (MSM_ERR_OUTSIDE / MSM_ERR_NOTFOUND, as msm_metric_resample fails). */
+msm_resample_plan *msm_resample_plan_create(msm_mesh *in_mesh, msm_mesh *new_mesh, int method, const double *excl);
+void msm_resample_plan_destroy(msm_resample_plan *p);
+/* [host] any pointer may be NULL */
+int  msm_resample_plan_sizes(const msm_resample_plan *p, int32_t *V_in, int32_t *V_out, int64_t *nnz, int32_t *longest_row);
+/* the rows as CSR (row_ptr: V_out + 1; col / val: nnz entries, cap = their capacity; any of the three may be NULL), read back from the device */
+int  msm_resample_plan_weights(msm_resample_plan *p, int32_t *row_ptr, int32_t *col, double *val, int64_t cap);
+/* data: D x V_in host array of dtype (MSM_F64: double, MSM_F32: float); out: D x V_out of the same type.  excl_out (optional, V_out): the resampled
+ * mask of a plan with excl (:54-67; NEAREST: the mask at the closest vertex, :244-249), zeros for a plan without.  The maps travel through the context's
+ * pinned staging blocks in slabs of a fixed device budget (64 MiB of maps; MSMHIP_PLAN_CHUNK_KB overrides), whatever D is.  D == 0: nothing is done. */
+int  msm_resample_plan_apply(msm_resample_plan *p, const void *data, int dtype, int64_t D, void *out, double *excl_out);
+/* the same for the caller's DEVICE arrays, read and written on the context's stream under the stream contract above (msm_ctx_wait_stream orders the
+ * caller's pending work before the call; the context's stream is synchronised before it returns).  No mask output. */
+int  msm_resample_plan_apply_dev(msm_resample_plan *p, const void *data_dev, int dtype, int64_t D, void *out_dev);
+/* Integer keys (a parcellation) through the plan's rows: the largest-summed-weight vote `wb_command -label-resample ADAP_BARY_AREA` stands for (the
+ * reference itself has nearest-vertex only).  For row k and every distinct key among its kept entries: the sum of val over the entries holding that
+ * key, in stored order from 0.0; the largest sum wins, an exact tie goes to the smallest key, a row without kept entries gets `unassigned`
+ * (tests/resample_literal.py).  labels: D x V_in, out: D x V_out. */
+int  msm_resample_plan_apply_labels(msm_resample_plan *p, const int32_t *labels, int64_t D, int32_t unassigned, int32_t *out);
 
 /* ------------------------------------------------------------------------------------------------
  * the callers' side of one iteration (run_discrete_opt, M/mesh_registration.cpp:164-232): what sits between two

@@ -229,6 +229,65 @@ inline Matrix metric_resample(Mesh &in_mesh, const Matrix &data, Mesh &ref, std:
     if (EXCL) *EXCL = eo;  // the reference writes the resampled mask back (:66)
     return out;
 }
+// msm_resample_plan: the rows of one (in_mesh -> new_mesh) resampling built once and applied to any number of maps -- what the bodies of the reference's
+// resampler programs (metric-resample, NN-resample, surface-resample) turn into when one sphere.reg carries many files.  A snapshot: it outlives both
+// meshes and does not follow their coordinates; destroy it before its context.
+class ResamplePlan {
+public:
+    ResamplePlan(Mesh &in_mesh, Mesh &new_mesh, int method = MSM_RESAMPLE_ADAP_BARY, const std::vector<double> *excl = nullptr)
+        : h_(msm_resample_plan_create(in_mesh.handle(), new_mesh.handle(), method, excl ? excl->data() : nullptr)), masked_(excl != nullptr) {
+        if (!h_) throw Error(MSM_ERR_INVALID, msm_last_error());
+        check(msm_resample_plan_sizes(h_, &V_in_, &V_out_, &nnz_, &longest_));
+    }
+    ~ResamplePlan() { msm_resample_plan_destroy(h_); }
+    ResamplePlan(const ResamplePlan &) = delete;
+    ResamplePlan &operator=(const ResamplePlan &) = delete;
+    int nvertices_in() const { return V_in_; }
+    int nvertices_out() const { return V_out_; }
+    int64_t nnz() const { return nnz_; }
+    int longest_row() const { return longest_; }
+    SparseWeights weights() {
+        SparseWeights w;
+        w.row_ptr.resize((size_t)V_out_ + 1);
+        w.col.resize((size_t)nnz_);
+        w.val.resize((size_t)nnz_);
+        check(msm_resample_plan_weights(h_, w.row_ptr.data(), w.col.data(), w.val.data(), nnz_));
+        return w;
+    }
+    // data: D x V_in, out: D x V_out, both row-major and of one type; excl_out (optional, V_out): the resampled mask of a plan with excl
+    void apply(const double *data, int64_t D, double *out, double *excl_out = nullptr) { check(msm_resample_plan_apply(h_, data, MSM_F64, D, out, excl_out)); }
+    void apply(const float *data, int64_t D, float *out, double *excl_out = nullptr) { check(msm_resample_plan_apply(h_, data, MSM_F32, D, out, excl_out)); }
+    Matrix apply(const Matrix &data, std::vector<double> *EXCL = nullptr) {
+        const int64_t D = (int64_t)(data.size() / (size_t)V_in_);
+        Matrix out((size_t)D * (size_t)V_out_);
+        if (EXCL) EXCL->assign((size_t)V_out_, 0.0);
+        apply(data.data(), D, out.data(), EXCL ? EXCL->data() : nullptr);
+        return out;
+    }
+    std::vector<float> apply(const std::vector<float> &data) {
+        const int64_t D = (int64_t)(data.size() / (size_t)V_in_);
+        std::vector<float> out((size_t)D * (size_t)V_out_);
+        apply(data.data(), D, out.data());
+        return out;
+    }
+    // the caller's device arrays under the stream contract of msmhip.h (dtype MSM_F64 / MSM_F32)
+    void apply_dev(const void *data_dev, int dtype, int64_t D, void *out_dev) { check(msm_resample_plan_apply_dev(h_, data_dev, dtype, D, out_dev)); }
+    // integer keys by the largest-summed-weight vote (msmhip.h); labels D x V_in -> D x V_out
+    std::vector<int32_t> apply_labels(const std::vector<int32_t> &labels, int32_t unassigned = 0) {
+        const int64_t D = (int64_t)(labels.size() / (size_t)V_in_);
+        std::vector<int32_t> out((size_t)D * (size_t)V_out_);
+        check(msm_resample_plan_apply_labels(h_, labels.data(), D, unassigned, out.data()));
+        return out;
+    }
+    bool masked() const { return masked_; }
+    msm_resample_plan *handle() const { return h_; }
+
+private:
+    msm_resample_plan *h_;
+    bool masked_;
+    int32_t V_in_ = 0, V_out_ = 0, longest_ = 0;
+    int64_t nnz_ = 0;
+};
 // surface_resample (R/resampler.cpp:284-302) / project_anatomical_mesh (:260-282): the coordinates `coords` given on the vertices of `from`, carried to
 // the points q by barycentric weights
 inline Points barycentric_coords_resample(Mesh &from, const Points &coords, const Points &q) {

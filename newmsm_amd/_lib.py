@@ -89,6 +89,13 @@ SIGNATURES = {
     "msm_adaptive_barycentric_weights": (C.c_int, [_VP, _VP, c_dp, c_ip, c_ip, c_dp, C.c_int64, c_lp]),
     "msm_metric_resample": (C.c_int, [_VP, c_dp, C.c_int32, _VP, c_dp, c_dp, c_dp]),
     "msm_create_exclusion": (C.c_int, [c_dp, C.c_int32, C.c_int32, C.c_double, C.c_double, c_dp]),
+    "msm_resample_plan_create": (_VP, [_VP, _VP, C.c_int, c_dp]),
+    "msm_resample_plan_destroy": (None, [_VP]),
+    "msm_resample_plan_sizes": (C.c_int, [_VP, c_ip, c_ip, c_lp, c_ip]),
+    "msm_resample_plan_weights": (C.c_int, [_VP, c_ip, c_ip, c_dp, C.c_int64]),
+    "msm_resample_plan_apply": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, _VP, c_dp]),
+    "msm_resample_plan_apply_dev": (C.c_int, [_VP, _VP, C.c_int, C.c_int64, _VP]),
+    "msm_resample_plan_apply_labels": (C.c_int, [_VP, c_ip, C.c_int64, C.c_int32, c_ip]),
     "msm_sphere_project_warp": (C.c_int, [_VP, c_dp, c_dp, C.c_int32]),
     "msm_mesh_sphere_project_warp": (C.c_int, [_VP, _VP, c_dp]),
     "msm_barycentric_coords_resample": (C.c_int, [_VP, c_dp, c_dp, C.c_int32, c_dp]),

@@ -387,6 +387,109 @@ def metric_resample(in_mesh, data, new_mesh, excl=None, out=None):
     return out, eo
 
 
+RESAMPLE_METHODS = dict(adap_bary=0, barycentric=1, nearest=2)
+PLAN_DTYPES = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}  # MSM_F64, MSM_F32
+PLAN_TILE = 64  # maps per tile of an apply (kPlanTile, csrc/resample_plan.hpp): a ragged tile takes the same kernels with lanes masked
+
+
+class ResamplePlan:
+    """msm_resample_plan: the rows of one (in_mesh -> new_mesh) resampling built once and applied to any number of maps.  A snapshot: later calls on the
+    context, set_coords on either mesh or closing either mesh do not change what it does.  method: adap_bary (metric_resample's rows), barycentric
+    (surface_resample's) or nearest; excl: the EXCL mesh's values on in_mesh (0 = excluded) or None."""
+
+    def __init__(self, in_mesh, new_mesh, method="adap_bary", excl=None):
+        if method not in RESAMPLE_METHODS:
+            raise ValueError("unknown resampling method %r (one of %s)" % (method, ", ".join(sorted(RESAMPLE_METHODS))))
+        self.ctx = in_mesh.ctx
+        self.method = method
+        self.masked = excl is not None
+        if self.masked:
+            e, pe = _d(np.asarray(excl).reshape(-1))
+            if e.shape[0] != in_mesh.V:
+                raise ValueError("excl has %d values, the mesh %d vertices" % (e.shape[0], in_mesh.V))
+        else:
+            pe = None
+        self.h = lib().msm_resample_plan_create(in_mesh.h, new_mesh.h, RESAMPLE_METHODS[method], pe)
+        if not self.h:
+            raise MsmError(-1, lib().msm_last_error().decode())
+        self.V_in, self.V_out, self.nnz, self.longest_row = self.sizes()
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            lib().msm_resample_plan_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def sizes(self):
+        """(V_in, V_out, nnz, longest row)"""
+        vi, vo, lr, nnz = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        check(lib().msm_resample_plan_sizes(self.h, C.byref(vi), C.byref(vo), C.byref(nnz), C.byref(lr)))
+        return vi.value, vo.value, nnz.value, lr.value
+
+    def weights(self):
+        """the rows as CSR (row_ptr, col, val), read back from the device"""
+        rp = np.zeros(self.V_out + 1, dtype=np.int32)
+        col = np.zeros(self.nnz, dtype=np.int32)
+        val = np.zeros(self.nnz)
+        check(lib().msm_resample_plan_weights(self.h, rp.ctypes.data_as(c_ip), col.ctypes.data_as(c_ip), val.ctypes.data_as(c_dp), self.nnz))
+        return rp, col, val
+
+    def apply(self, data, out=None):
+        """D x V_in float32 or float64 -> D x V_out of the same dtype; (out, resampled mask) when the plan has a mask"""
+        d = np.asarray(data)
+        if d.dtype not in PLAN_DTYPES:
+            raise TypeError("ResamplePlan.apply takes float32 or float64 data, not %s" % d.dtype)
+        d = np.ascontiguousarray(np.atleast_2d(d))
+        if d.shape[1] != self.V_in:
+            raise ValueError("data has %d columns, the plan's source %d vertices" % (d.shape[1], self.V_in))
+        D = d.shape[0]
+        if out is None:
+            out = np.zeros((D, self.V_out), dtype=d.dtype)
+        assert out.shape == (D, self.V_out) and out.flags.c_contiguous and out.dtype == d.dtype
+        eo = np.zeros(self.V_out) if self.masked else None
+        check(lib().msm_resample_plan_apply(self.h, d.ctypes.data, PLAN_DTYPES[d.dtype], D, out.ctypes.data, eo.ctypes.data_as(c_dp) if self.masked else None))
+        return (out, eo) if self.masked else out
+
+    def apply_dev(self, data, out=None, D=None, dtype=None):
+        """The same on DEVICE memory.  data / out: torch tensors on the context's GPU (D x V_in / D x V_out, contiguous, float32 or float64; out is made when
+        None), or integer device addresses with D and dtype given.  The caller orders its pending work with Context.wait_stream; complete on return."""
+        if hasattr(data, "data_ptr"):
+            import torch
+
+            names = {torch.float64: np.float64, torch.float32: np.float32}
+            if data.dtype not in names:
+                raise TypeError("ResamplePlan.apply_dev takes float32 or float64 tensors, not %s" % data.dtype)
+            t = data.reshape(-1, self.V_in)
+            assert t.is_contiguous() and t.is_cuda
+            D, dtype = t.shape[0], names[t.dtype]
+            if out is None:
+                out = torch.empty((D, self.V_out), dtype=t.dtype, device=t.device)
+            assert out.is_contiguous() and out.dtype == t.dtype and tuple(out.shape) == (D, self.V_out)
+            src, dst = t.data_ptr(), out.data_ptr()
+        else:
+            if D is None or dtype is None or out is None:
+                raise ValueError("device addresses need out, D and dtype")
+            src, dst = int(data), int(out.data_ptr() if hasattr(out, "data_ptr") else out)
+        if np.dtype(dtype) not in PLAN_DTYPES:
+            raise TypeError("ResamplePlan.apply_dev takes float32 or float64 data, not %s" % np.dtype(dtype))
+        check(lib().msm_resample_plan_apply_dev(self.h, src or None, PLAN_DTYPES[np.dtype(dtype)], int(D), dst or None))
+        return out
+
+    def apply_labels(self, labels, unassigned=0):
+        """D x V_in integer keys -> D x V_out int32 by the largest-summed-weight vote (msmhip.h); rows without kept entries get `unassigned`"""
+        l = np.asarray(labels)
+        if not np.issubdtype(l.dtype, np.integer):
+            raise TypeError("ResamplePlan.apply_labels takes integer keys, not %s" % l.dtype)
+        l, pl = _i(np.atleast_2d(l))
+        if l.shape[1] != self.V_in:
+            raise ValueError("labels have %d columns, the plan's source %d vertices" % (l.shape[1], self.V_in))
+        out = np.zeros((l.shape[0], self.V_out), dtype=np.int32)
+        check(lib().msm_resample_plan_apply_labels(self.h, pl, l.shape[0], int(unassigned), out.ctypes.data_as(c_ip)))
+        return out
+
+
 def create_exclusion(data, thrl, thru):
     """create_exclusion (R/mesh.cpp:1257-1273) of a D x V matrix"""
     d, pd = _d(np.atleast_2d(data))

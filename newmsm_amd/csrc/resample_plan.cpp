@@ -1,0 +1,329 @@
+// resample_plan.cpp -- msm_resample_plan_*: the rows of one (in_mesh -> new_mesh) resampling built once, kept in HBM and applied to any number of maps.
+// The rows come from the paths the library already has (adaptive_weights_dev / adaptive_weights, launch_query, launch_closest_vertex: api.cpp,
+// kernels.hip); what is new is the ownership (a snapshot: nothing here points back into a mesh or into context scratch) and the apply
+// (resample_plan_kernels.hip).  Host arrays travel in slabs through the context's pinned staging blocks (stager.cpp): the device never holds more than
+// the slab budget of maps, whatever D is.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "kernels.hpp"
+#include "resample_plan.hpp"
+
+using namespace msm;
+
+namespace msm {
+int adaptive_weights(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *excl, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col,
+                     std::vector<double> &val);  // api.cpp
+}
+
+struct msm_resample_plan {
+    msm_ctx *ctx = nullptr;
+    int nOld = 0, nNew = 0, method = 0, longest = 0;
+    int64_t nnz = 0;
+    bool masked = false;
+    DevBuf<int32_t> row_ptr, col;   // nNew + 1, nnz
+    DevBuf<double> val, excl;       // nnz, nOld (masked plans)
+    std::vector<double> excl_out;   // masked plans: the resampled mask (it depends on the rows and the mask only)
+    DevBuf<char> in, out, tin, tout;  // grow-only scratch of the applies: a slab of maps in and out, one tile in vertex-major order in and out
+    hipEvent_t ev = nullptr;        // behind a slab's download: its delivery waits for this, not for the stream
+
+    PlanRows rows() const {
+        PlanRows r;
+        r.nOld = nOld, r.nNew = nNew, r.row_ptr = row_ptr.p, r.col = col.p, r.val = val.p, r.excl = masked ? excl.p : nullptr;
+        return r;
+    }
+};
+
+namespace {
+
+// The slab budget: bytes of maps (input and result together) the device holds at a time.  Two tiles of kPlanTile maps in vertex-major order come on top.
+constexpr size_t kPlanBudgetDefault = (size_t)64 << 20;
+size_t plan_budget() {
+    const char *e = std::getenv("MSMHIP_PLAN_CHUNK_KB");
+    const long long kb = e ? std::atoll(e) : 0;
+    return kb > 0 ? (size_t)kb << 10 : kPlanBudgetDefault;
+}
+// maps per slab for elements of es bytes: what the budget holds, whole tiles when it holds more than one
+int64_t slab_maps(const msm_resample_plan *p, size_t es, int64_t D) {
+    const size_t per_map = ((size_t)p->nOld + (size_t)p->nNew) * es;
+    int64_t s = per_map ? (int64_t)(plan_budget() / per_map) : D;
+    s = std::max<int64_t>(1, std::min(s, D));
+    if (s > kPlanTile) s -= s % kPlanTile;
+    return s;
+}
+
+// a std::map<int, double> holding the three weights of one query: ascending key, later writes win (R/resampler.cpp:150-166 read at :296-297)
+int sorted_triple(const int *vid, const double *w, size_t stride, size_t k, int32_t key[3], double wt[3]) {
+    int n = 0;
+    for (int j = 0; j < 3; ++j) {
+        const int32_t id = vid[j * stride + k];
+        const double x = w[j * stride + k];
+        int pos = 0;
+        while (pos < n && key[pos] < id) ++pos;
+        if (pos < n && key[pos] == id) {
+            wt[pos] = x;
+            continue;
+        }
+        for (int s = n; s > pos; --s) key[s] = key[s - 1], wt[s] = wt[s - 1];
+        key[pos] = id, wt[pos] = x;
+        ++n;
+    }
+    return n;
+}
+
+int upload_rows(msm_resample_plan *p, const std::vector<int32_t> &rp, const std::vector<int32_t> &c, const std::vector<double> &v) {
+    msm_ctx *ctx = p->ctx;
+    p->nnz = (int64_t)c.size();
+    if (p->row_ptr.ensure(rp.size(), true) || p->col.ensure(std::max<size_t>(c.size(), 1), true) || p->val.ensure(std::max<size_t>(v.size(), 1), true))
+        return stage_alloc_failed(12 * c.size());
+    MSM_TRY(stage_h2d(ctx, p->row_ptr.p, rp.data(), sizeof(int32_t) * rp.size()));
+    MSM_TRY(stage_h2d(ctx, p->col.p, c.data(), sizeof(int32_t) * c.size()));
+    MSM_TRY(stage_h2d(ctx, p->val.p, v.data(), sizeof(double) * v.size()));
+    for (size_t k = 0; k + 1 < rp.size(); ++k) p->longest = std::max(p->longest, rp[k + 1] - rp[k]);
+    return MSM_OK;
+}
+
+int build(msm_resample_plan *p, msm_mesh *in_mesh, msm_mesh *new_mesh, const double *excl) {
+    msm_ctx *ctx = p->ctx;
+    const int nOld = p->nOld, nNew = p->nNew;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    MSM_HIP(hipEventCreateWithFlags(&p->ev, hipEventDisableTiming));
+    std::vector<int32_t> rp, c;
+    std::vector<double> v;
+    if (p->method == MSM_RESAMPLE_ADAP_BARY && !excl) {
+        // searches and list surgery on the device; the rows leave the context's scratch with three device-to-device copies
+        AdaptiveDev w;
+        MSM_TRY(adaptive_weights_dev(in_mesh, new_mesh, w));
+        rp.resize((size_t)nNew + 1);
+        MSM_TRY(stage_d2h(ctx, rp.data(), w.row_ptr, sizeof(int32_t) * rp.size()));
+        MSM_TRY(ctx_sync(ctx));
+        p->nnz = rp.back();
+        const size_t nnz = (size_t)p->nnz;
+        if (p->row_ptr.ensure(rp.size(), true) || p->col.ensure(std::max<size_t>(nnz, 1), true) || p->val.ensure(std::max<size_t>(nnz, 1), true))
+            return stage_alloc_failed(12 * nnz);
+        MSM_HIP(hipMemcpyAsync(p->row_ptr.p, w.row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToDevice, ctx->stream));
+        if (nnz) {
+            MSM_HIP(hipMemcpyAsync(p->col.p, w.col, sizeof(int32_t) * nnz, hipMemcpyDeviceToDevice, ctx->stream));
+            MSM_HIP(hipMemcpyAsync(p->val.p, w.val, sizeof(double) * nnz, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        for (int k = 0; k < nNew; ++k) p->longest = std::max(p->longest, rp[(size_t)k + 1] - rp[(size_t)k]);
+        return ctx_sync(ctx);
+    }
+    if (p->method == MSM_RESAMPLE_ADAP_BARY) {
+        MSM_TRY(adaptive_weights(in_mesh, new_mesh, excl, rp, c, v));  // the searches on the GPU, the surgery with its mask on the host
+    } else {
+        MSM_TRY(ensure_tree(in_mesh));
+        rp.resize((size_t)nNew + 1);
+        if (p->method == MSM_RESAMPLE_BARYCENTRIC) {
+            DevBuf<int> dvid;
+            DevBuf<double> dw;
+            std::vector<int> vid(3 * (size_t)nNew);
+            std::vector<double> w(3 * (size_t)nNew);
+            if (dvid.ensure(vid.size() + 1) || dw.ensure(w.size() + 1)) return stage_alloc_failed(36 * (size_t)nNew);
+            MSM_TRY(launch_query(ctx, dev_tree(in_mesh), new_mesh->d_xyz.p, nNew, nullptr, dvid.p, dw.p, MSM_WEIGHTS_PROJECTED));
+            MSM_TRY(dvid.download(vid.data(), vid.size(), ctx));
+            MSM_TRY(dw.download(w.data(), w.size(), ctx));
+            MSM_TRY(check_status(ctx, "msm_resample_plan_create (barycentric)"));
+            for (int k = 0; k < nNew; ++k) {
+                int32_t key[3];
+                double wt[3];
+                const int n = sorted_triple(vid.data(), w.data(), (size_t)nNew, (size_t)k, key, wt);
+                rp[(size_t)k] = (int32_t)c.size();
+                c.insert(c.end(), key, key + n);
+                v.insert(v.end(), wt, wt + n);
+            }
+        } else {
+            DevBuf<int> dcv;
+            std::vector<int> cv((size_t)nNew);
+            if (dcv.ensure(cv.size() + 1)) return stage_alloc_failed(4 * (size_t)nNew);
+            MSM_TRY(launch_closest_vertex(ctx, dev_tree(in_mesh), new_mesh->d_xyz.p, nNew, dcv.p));
+            MSM_TRY(dcv.download(cv.data(), cv.size(), ctx));
+            MSM_TRY(check_status(ctx, "msm_resample_plan_create (nearest)"));
+            for (int k = 0; k < nNew; ++k) rp[(size_t)k] = k;
+            c.assign(cv.begin(), cv.end());
+            v.assign((size_t)nNew, 1.0);
+        }
+        rp[(size_t)nNew] = (int32_t)c.size();
+    }
+    MSM_TRY(upload_rows(p, rp, c, v));
+    if (excl) {
+        p->masked = true;
+        MSM_TRY(p->excl.upload(excl, (size_t)nOld, ctx));
+        p->excl_out.assign((size_t)nNew, 0.0);
+        for (int k = 0; k < nNew; ++k) {  // barycentric_data_interpolation on the mask itself, R/resampler.cpp:54-67
+            double acc = 0.0;
+            for (int e = rp[(size_t)k]; e < rp[(size_t)k + 1]; ++e)
+                if (c[(size_t)e] >= 0 && excl[c[(size_t)e]] != 0) acc += excl[c[(size_t)e]] * v[(size_t)e];
+            p->excl_out[(size_t)k] = acc;
+        }
+    }
+    return ctx_sync(ctx);
+}
+
+template <typename T>
+int tiles(msm_resample_plan *p, const T *d_data, int64_t D, T *d_out) {
+    const PlanRows r = p->rows();
+    for (int64_t d0 = 0; d0 < D; d0 += kPlanTile) {
+        const int nd = (int)std::min<int64_t>(kPlanTile, D - d0);
+        MSM_TRY(launch_plan_tile<T>(p->ctx, r, d_data + (size_t)d0 * (size_t)p->nOld, nd, (T *)p->tin.p, (T *)p->tout.p, d_out + (size_t)d0 * (size_t)p->nNew));
+    }
+    return MSM_OK;
+}
+
+int ensure_tiles(msm_resample_plan *p, size_t es) {
+    if (p->tin.ensure(std::max<size_t>((size_t)p->nOld, 1) * kPlanTile * es) || p->tout.ensure(std::max<size_t>((size_t)p->nNew, 1) * kPlanTile * es))
+        return stage_alloc_failed(((size_t)p->nOld + (size_t)p->nNew) * kPlanTile * es);
+    return MSM_OK;
+}
+
+int check_apply(const msm_resample_plan *p, const void *data, int dtype, int64_t D, const void *out, const char *what) {
+    if (!p) return fail(MSM_ERR_INVALID, "%s: null plan", what);
+    if (dtype != MSM_F64 && dtype != MSM_F32) return fail(MSM_ERR_INVALID, "%s: unknown dtype %d (MSM_F64 = 0, MSM_F32 = 1)", what, dtype);
+    if (D < 0) return fail(MSM_ERR_INVALID, "%s: D = %lld maps", what, (long long)D);
+    if (D > 0 && (!data || !out)) return fail(MSM_ERR_INVALID, "%s: null array with D = %lld", what, (long long)D);
+    return MSM_OK;
+}
+
+// host arrays, slab by slab.  While the GPU works on slab i the host fills the staging block of slab i + 1 and hands slab i - 1's result to the caller;
+// the copies and kernels themselves run in order on the context's one stream (a staged download is delivered from the thread that queued it, after an
+// event behind it: stager.cpp).
+template <typename T>
+int apply_host(msm_resample_plan *p, const T *data, int64_t D, T *out) {
+    msm_ctx *ctx = p->ctx;
+    const size_t nOld = (size_t)p->nOld, nNew = (size_t)p->nNew;
+    const int64_t S = slab_maps(p, sizeof(T), D);
+    MSM_TRY(ensure_tiles(p, sizeof(T)));
+    if (p->in.ensure(std::max<size_t>((size_t)S * nOld, 1) * sizeof(T)) || p->out.ensure(std::max<size_t>((size_t)S * nNew, 1) * sizeof(T)))
+        return stage_alloc_failed((size_t)S * (nOld + nNew) * sizeof(T));
+    bool pending = false;
+    for (int64_t d0 = 0; d0 < D; d0 += S) {
+        const int64_t n = std::min(S, D - d0);
+        MSM_TRY(stage_h2d(ctx, p->in.p, data + (size_t)d0 * nOld, (size_t)n * nOld * sizeof(T)));
+        MSM_TRY(tiles<T>(p, (const T *)p->in.p, n, (T *)p->out.p));
+        if (pending) {  // the previous slab's download has been queued before this slab's kernels
+            MSM_HIP(hipEventSynchronize(p->ev));
+            stage_deliver(ctx);
+        }
+        MSM_TRY(stage_d2h(ctx, out + (size_t)d0 * nNew, p->out.p, (size_t)n * nNew * sizeof(T)));
+        MSM_HIP(hipEventRecord(p->ev, ctx->stream));
+        pending = true;
+    }
+    return ctx_sync(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+msm_resample_plan *msm_resample_plan_create(msm_mesh *in_mesh, msm_mesh *new_mesh, int method, const double *excl) {
+    if (!in_mesh || !new_mesh) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create: null mesh");
+        return nullptr;
+    }
+    if (in_mesh->ctx != new_mesh->ctx) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create: the two meshes belong to different contexts");
+        return nullptr;
+    }
+    if (method != MSM_RESAMPLE_ADAP_BARY && method != MSM_RESAMPLE_BARYCENTRIC && method != MSM_RESAMPLE_NEAREST) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create: unknown method %d (ADAP_BARY = 0, BARYCENTRIC = 1, NEAREST = 2)", method);
+        return nullptr;
+    }
+    msm_resample_plan *p = new (std::nothrow) msm_resample_plan();
+    if (!p) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create: out of memory");
+        return nullptr;
+    }
+    p->ctx = in_mesh->ctx;
+    p->nOld = in_mesh->V, p->nNew = new_mesh->V, p->method = method;
+    int st;
+    try {
+        st = build(p, in_mesh, new_mesh, excl);
+    } catch (const std::exception &e) {
+        st = fail(MSM_ERR_INVALID, "msm_resample_plan_create: %s", e.what());
+    }
+    if (st) {
+        msm_resample_plan_destroy(p);
+        return nullptr;
+    }
+    return p;
+}
+
+void msm_resample_plan_destroy(msm_resample_plan *p) {
+    if (!p) return;
+    (void)hipSetDevice(p->ctx->device);
+    if (p->ev) (void)hipEventDestroy(p->ev);
+    delete p;  // the buffers go back to the pool, which waits for work that may still use them
+}
+
+int msm_resample_plan_sizes(const msm_resample_plan *p, int32_t *V_in, int32_t *V_out, int64_t *nnz, int32_t *longest_row) {
+    if (!p) return fail(MSM_ERR_INVALID, "msm_resample_plan_sizes: null plan");
+    if (V_in) *V_in = p->nOld;
+    if (V_out) *V_out = p->nNew;
+    if (nnz) *nnz = p->nnz;
+    if (longest_row) *longest_row = p->longest;
+    return MSM_OK;
+}
+
+int msm_resample_plan_weights(msm_resample_plan *p, int32_t *row_ptr, int32_t *col, double *val, int64_t cap) {
+    if (!p) return fail(MSM_ERR_INVALID, "msm_resample_plan_weights: null plan");
+    if ((col || val) && cap < p->nnz) return fail(MSM_ERR_INVALID, "msm_resample_plan_weights: the plan has %lld entries, the arrays hold %lld", (long long)p->nnz, (long long)cap);
+    msm_ctx *ctx = p->ctx;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    if (row_ptr) MSM_TRY(p->row_ptr.download(row_ptr, (size_t)p->nNew + 1, ctx));
+    if (col) MSM_TRY(p->col.download(col, (size_t)p->nnz, ctx));
+    if (val) MSM_TRY(p->val.download(val, (size_t)p->nnz, ctx));
+    return ctx_sync(ctx);
+}
+
+int msm_resample_plan_apply(msm_resample_plan *p, const void *data, int dtype, int64_t D, void *out, double *excl_out) {
+    MSM_TRY(check_apply(p, data, dtype, D, out, "msm_resample_plan_apply"));
+    if (excl_out) {
+        if (p->masked) std::copy(p->excl_out.begin(), p->excl_out.end(), excl_out);
+        else std::fill(excl_out, excl_out + p->nNew, 0.0);
+    }
+    if (D == 0) return MSM_OK;
+    MSM_HIP(hipSetDevice(p->ctx->device));
+    MSM_TRY(drop_ctx_pending(p->ctx));
+    return dtype == MSM_F32 ? apply_host<float>(p, (const float *)data, D, (float *)out) : apply_host<double>(p, (const double *)data, D, (double *)out);
+}
+
+int msm_resample_plan_apply_dev(msm_resample_plan *p, const void *data_dev, int dtype, int64_t D, void *out_dev) {
+    MSM_TRY(check_apply(p, data_dev, dtype, D, out_dev, "msm_resample_plan_apply_dev"));
+    if (D == 0) return MSM_OK;
+    MSM_HIP(hipSetDevice(p->ctx->device));
+    MSM_TRY(drop_ctx_pending(p->ctx));
+    MSM_TRY(ensure_tiles(p, dtype == MSM_F32 ? sizeof(float) : sizeof(double)));
+    if (dtype == MSM_F32) MSM_TRY(tiles<float>(p, (const float *)data_dev, D, (float *)out_dev));
+    else MSM_TRY(tiles<double>(p, (const double *)data_dev, D, (double *)out_dev));
+    return ctx_sync(p->ctx);  // the caller's buffers are free for any stream on return (the stream contract, msmhip.h)
+}
+
+int msm_resample_plan_apply_labels(msm_resample_plan *p, const int32_t *labels, int64_t D, int32_t unassigned, int32_t *out) {
+    if (!p) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: null plan");
+    if (D < 0) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: D = %lld rows", (long long)D);
+    if (D > 0 && (!labels || !out)) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: null array with D = %lld", (long long)D);
+    if (D == 0) return MSM_OK;
+    msm_ctx *ctx = p->ctx;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    const size_t nOld = (size_t)p->nOld, nNew = (size_t)p->nNew;
+    int64_t S = slab_maps(p, sizeof(int32_t), D);
+    S = std::max<int64_t>(1, std::min<int64_t>(S, ((int64_t)1 << 33) / std::max<int64_t>(p->nNew, 1)));  // 16 lanes per (row, vertex): a launch's grid stays inside 31 bits
+    if (p->in.ensure(std::max<size_t>((size_t)S * nOld, 1) * sizeof(int32_t)) || p->out.ensure(std::max<size_t>((size_t)S * nNew, 1) * sizeof(int32_t)))
+        return stage_alloc_failed((size_t)S * (nOld + nNew) * sizeof(int32_t));
+    for (int64_t d0 = 0; d0 < D; d0 += S) {
+        const int64_t n = std::min(S, D - d0);
+        MSM_TRY(stage_h2d(ctx, p->in.p, labels + (size_t)d0 * nOld, (size_t)n * nOld * sizeof(int32_t)));
+        MSM_TRY(launch_plan_labels(ctx, p->rows(), (const int32_t *)p->in.p, (int)n, unassigned, (int32_t *)p->out.p));
+        MSM_TRY(stage_d2h(ctx, out + (size_t)d0 * nNew, p->out.p, (size_t)n * nNew * sizeof(int32_t)));
+        MSM_TRY(ctx_sync(ctx));
+    }
+    return MSM_OK;
+}
+
+}  // extern "C"

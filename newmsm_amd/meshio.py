@@ -5,6 +5,8 @@
   NIFTI_INTENT_TRIANGLE array (int32, T x 3); a metric file holds one float32 array of N values per feature; files are
   written GZipBase64Binary, row-major, little-endian.  The reader also accepts ASCII and Base64Binary encodings, big-endian
   data, column-major arrays and the other numeric GIFTI datatypes.
+* GIFTI label files (`.label.gii`): int32 NIFTI_INTENT_LABEL arrays of keys, one per row, and the file's `<LabelTable>` element, which is carried
+  through as text and never interpreted (`load_label` / `save_label`).
 * FreeSurfer ASCII (`.asc`) as `Mesh::load_ascii` reads it (R/mesh.cpp:455-515): "#!ascii" header, "NVertices NFaces", then
   "x y z value" per vertex and "a b c value" per face.
 
@@ -13,6 +15,7 @@ specification and the reference's call sites.  Host-side only (numpy + the stand
 as float64 arrays holding the float32 values of the file, which is what Mpoint receives in the reference.
 """
 import base64
+import re
 import sys
 import xml.etree.ElementTree as ET
 import zlib
@@ -86,9 +89,9 @@ def _encode_array(intent, a, with_coordsys=False):
     return "\n".join(out)
 
 
-def _write_gifti(path, arrays):
+def _write_gifti(path, arrays, label_table=None):
     body = ['<?xml version="1.0" encoding="UTF-8"?>', '<!DOCTYPE GIFTI SYSTEM "http://www.nitrc.org/frs/download.php/115/gifti.dtd">',
-            '<GIFTI Version="1.0" NumberOfDataArrays="%d">' % len(arrays), "   <MetaData/>", "   <LabelTable/>"]
+            '<GIFTI Version="1.0" NumberOfDataArrays="%d">' % len(arrays), "   <MetaData/>", "   " + (label_table or "<LabelTable/>")]
     body += arrays + ["</GIFTI>", ""]
     with open(path, "w") as f:
         f.write("\n".join(body))
@@ -122,11 +125,12 @@ def save_surface(path, xyz, tri):
     _write_gifti(path, [_encode_array("NIFTI_INTENT_POINTSET", xyz, True), _encode_array("NIFTI_INTENT_TRIANGLE", tri, True)])
 
 
-def load_metric(path, nvertices=None):
-    """D x V float64 matrix of a .func.gii / .shape.gii (one array per feature) or of the value column of an .asc file."""
+def load_metric(path, nvertices=None, dtype=np.float64):
+    """D x V matrix (float64 unless dtype says float32: the file's own bits, for a consumer that takes them as they are) of a .func.gii / .shape.gii
+    (one array per feature) or of the value column of an .asc file."""
     if str(path).endswith(".asc"):
         _, _, val = _read_ascii(path)
-        return val[None, :]
+        return val[None, :].astype(dtype, copy=False)
     rows = []
     for intent, a in read_gifti(path):
         if intent in ("NIFTI_INTENT_POINTSET", "NIFTI_INTENT_TRIANGLE"):
@@ -134,7 +138,7 @@ def load_metric(path, nvertices=None):
         a = a.reshape(a.shape[0], -1)
         if nvertices is not None and a.shape[0] != nvertices:
             raise MeshIOError(" mismatch between data and surface dimensions")  # R/mesh.cpp:392
-        rows += [a[:, k].astype(np.float64) for k in range(a.shape[1])]
+        rows += [a[:, k].astype(dtype) for k in range(a.shape[1])]
     if not rows:
         raise MeshIOError("GIFTI: %s holds no data arrays" % path)
     if len({len(r) for r in rows}) != 1:
@@ -146,6 +150,32 @@ def save_metric(path, data):
     """save_gifti for a '.func' / '.shape' file: one float32 NIFTI_INTENT_NONE array per feature row."""
     data = np.atleast_2d(np.asarray(data, dtype=np.float32))
     _write_gifti(path, [_encode_array("NIFTI_INTENT_NONE", row) for row in data])
+
+
+_LABEL_TABLE = re.compile(r"<LabelTable\s*/>|<LabelTable[\s>].*?</LabelTable>", re.S)
+
+
+def load_label(path):
+    """(D x V int32 keys, the file's <LabelTable> element as text) of a .label.gii: one row per NIFTI_INTENT_LABEL array (a file without that intent
+    gives its integer arrays).  The table is not interpreted: save_label writes it back verbatim."""
+    arrays = read_gifti(path)
+    rows = [a for i, a in arrays if i == "NIFTI_INTENT_LABEL"] or [a for i, a in arrays if np.issubdtype(a.dtype, np.integer) and i != "NIFTI_INTENT_TRIANGLE"]
+    if not rows:
+        raise MeshIOError("GIFTI: %s holds no label arrays" % path)
+    rows = [a.reshape(-1).astype(np.int32) for a in rows]
+    if len({len(r) for r in rows}) != 1:
+        raise MeshIOError(" mismatch between data and surface dimensions")
+    with open(path, encoding="utf-8") as f:
+        m = _LABEL_TABLE.search(f.read())
+    return np.stack(rows), (m.group(0) if m else "<LabelTable/>")
+
+
+def save_label(path, labels, label_table_xml="<LabelTable/>"):
+    """a .label.gii: one int32 NIFTI_INTENT_LABEL array per row of keys, label_table_xml (a whole <LabelTable> element) as given"""
+    if not _LABEL_TABLE.fullmatch(label_table_xml.strip()):
+        raise MeshIOError("GIFTI: a label table is one <LabelTable> element")
+    labels = np.atleast_2d(np.asarray(labels, dtype=np.int32))
+    _write_gifti(path, [_encode_array("NIFTI_INTENT_LABEL", row) for row in labels], label_table_xml.strip())
 
 
 # ------------------------------------------------------------------------------------------------ FreeSurfer ASCII
