@@ -138,6 +138,7 @@ SIGNATURES = {
     "msm_cost_enable_timing": (C.c_int, [_VP, C.c_int]),
     "msm_cost_kernel_times": (C.c_int, [_VP, c_dp, C.c_int32, c_ip]),
     "msm_cost_counters": (C.c_int, [_VP, c_lp]),
+    "msm_cost_routes": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "msm_group_create": (_VP, [_VP, C.POINTER(GroupParams), C.c_int32]),
     "msm_group_fusion_move": (C.c_int, [_VP, c_ip, C.c_int32, c_dp, c_dp]),
     "msm_group_destroy": (None, [_VP]),

@@ -362,25 +362,34 @@ int launch_triplet_batch(msm_ctx *ctx, const CliqueArgs &a, const int *qt, const
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }
-int launch_triplet_octets(msm_ctx *ctx, const CliqueArgs &a, const int *labeling, int label, double *out) {
+int launch_triplet_octets(msm_ctx *ctx, const CliqueArgs &a, const int *labeling, int label, double *out, int *route) {
     if (a.T <= 0) return MSM_OK;
+    int chosen;
     if (is_ho(a) && a.ho_vals && a.tree.simple && a.tree.ray_G > 0 && a.rmode != 4 && a.rmode != 5) {
         const int per = 256 / kOctLanes;
         const bool mv8 = a.kind == MSM_COST_HO_MULTIVARIATE && a.sfeat_vm && a.D >= 12 && a.D <= kMvLanes * kMvKeep && (a.simmeasure == 1 || a.simmeasure == 2);
         auto grid8 = [](int evals, int per_block) { return dim3((unsigned)(8 * (((evals + per_block - 1) / per_block + 7) / 8))); };  // 8 x blocks per XCD
-        if (mv8) hipLaunchKernelGGL(k_ho_octets_sample_mv8, grid8(8 * a.T, 32), dim3(256), 0, ctx->stream, a, labeling, label);
-        else hipLaunchKernelGGL(k_ho_octets_sample, grid8(8 * a.T, per), dim3(256), 0, ctx->stream, a, labeling, label);
+        if (mv8) {
+            chosen = MSM_MOVE_OCTETS_SAMPLE_MV8;
+            hipLaunchKernelGGL(k_ho_octets_sample_mv8, grid8(8 * a.T, 32), dim3(256), 0, ctx->stream, a, labeling, label);
+        } else {
+            chosen = MSM_MOVE_OCTETS_SAMPLE;
+            hipLaunchKernelGGL(k_ho_octets_sample, grid8(8 * a.T, per), dim3(256), 0, ctx->stream, a, labeling, label);
+        }
         MSM_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_ho_octets_fix, dim3(64), dim3(256), 0, ctx->stream, a, labeling, label);
         MSM_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_ho_octets_reduce, grid8(8 * a.T, 128), dim3(128), 0, ctx->stream, a, labeling, label, out);
-    } else if (is_ho(a))
+    } else if (is_ho(a)) {
+        chosen = MSM_MOVE_OCTETS_HO;
         MSM_HO_LAUNCH(k_triplet_octets_ho, (size_t)8 * a.T, a, labeling, label, out);
-    else {
+    } else {
+        chosen = MSM_MOVE_STRAIN;
         if (a.rmode == 4 || a.rmode == 5) hipLaunchKernelGGL(k_triplet_octets<true>, dim3((8 * a.T + 127) / 128), dim3(128), 0, ctx->stream, a, labeling, label, out);
         else hipLaunchKernelGGL(k_triplet_octets<false>, dim3((8 * a.T + 127) / 128), dim3(128), 0, ctx->stream, a, labeling, label, out);
     }
     MSM_HIP(hipGetLastError());
+    if (route) *route = chosen;
     return MSM_OK;
 }
 int launch_triplet_octets_packed(msm_ctx *ctx, const CliqueArgs &a, const MoveLabels &lab, int label, double *out, int *host_flag) {

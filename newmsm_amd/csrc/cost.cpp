@@ -259,6 +259,7 @@ int ensure_unary_table(msm_cost *c) {
     u.fix_cnt = c->d_fix_count.p;
     u.fix_off = c->d_fix_off.p;
     u.redo_list = c->d_queues.p;
+    u.route = &c->route_unary;
     if (c->timing) {
         u.ev_start = c->ev0[c->ev_next];
         u.ev_stop = c->ev1[c->ev_next];
@@ -662,6 +663,18 @@ int msm_cost_kernel_times(msm_cost *c, double *ms, int32_t cap, int32_t *n) {
         ms[k] = f;
     }
     *n = cnt;
+    return MSM_OK;
+}
+
+int msm_cost_routes(msm_cost *c, int32_t routes[8]) {
+    if (!c || !routes) return fail(MSM_ERR_INVALID, "msm_cost_routes: null argument");
+    for (int i = 0; i < 8; ++i) routes[i] = 0;
+    routes[MSM_ROUTE_UNARY] = c->route_unary;
+    routes[MSM_ROUTE_MOVE] = c->route_move;
+    routes[MSM_ROUTE_MOVE_NBLK] = c->move_nblk;
+    routes[MSM_ROUTE_MOVE_CAP] = c->move_cap;
+    routes[MSM_ROUTE_MOVE_MAXTRI] = c->move_maxtri;
+    routes[MSM_ROUTE_MOVE_TAILS] = (int32_t)std::min<int64_t>(c->move_tails, INT32_MAX);
     return MSM_OK;
 }
 

@@ -191,8 +191,9 @@ int ensure_move(msm_cost *c, const CliqueArgs &a) {
             max_slots = 8 * t;
             break;
         }
-    int slots = 0, nt = 0, cap = max_slots, first = 0;
+    int slots = 0, nt = 0, cap = max_slots, first = 0, most_tris = 0;
     auto close = [&](int t_end) {
+        most_tris = std::max(most_tris, nt);
         if (nt > 0) blk.push_back(make_int4(first, nt, c->pptr[first], c->pptr[t_end] - c->pptr[first]));
         first = t_end;
         slots = nt = 0;
@@ -222,6 +223,7 @@ int ensure_move(msm_cost *c, const CliqueArgs &a) {
     MSM_TRY(ctx_sync(ctx));  // blk is a local
     c->move_nblk = (int)blk.size();
     c->move_cap = cap;
+    c->move_maxtri = most_tris;
     c->move_valid = true;
     return MSM_OK;
 }
@@ -376,7 +378,7 @@ static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling,
         c->ev_next = (c->ev_next + 1) % (int)c->ev0.size();
         c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
     }
-    st = launch_move(ctx, a, m, packed ? &lab : nullptr, e0, e1);
+    st = launch_move(ctx, a, m, packed ? &lab : nullptr, e0, e1, &c->route_move);
     if (st) return st;
     if (staged_copy) MSM_HIP(hipMemcpyAsync((char *)pin + in_pad, out_dev, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     c->counters[2] += (int64_t)(single ? 1 : 8) * a.T;
@@ -438,6 +440,7 @@ static int packed_strain_move(msm_cost *c, const CliqueArgs &a, const int32_t *l
     }
     int st = launch_triplet_octets_packed(ctx, a, lab, label, out_dev, ctx->d_flag_map);
     if (st) return st;
+    c->route_move = MSM_MOVE_STRAIN;  // that launcher has one kernel
     if (e1) MSM_HIP(hipEventRecord(e1, ctx->stream));
     c->counters[2] += (int64_t)8 * a.T;
     if (queue_only) {
@@ -549,7 +552,7 @@ static int triplet_octets_impl(msm_cost *c, const int32_t *labeling, int32_t lab
         c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
         MSM_HIP(hipEventRecord(g0, ctx->stream));
     }
-    st = launch_triplet_octets(ctx, a, c->d_labeling.p, label, c->d_clique_out.p);
+    st = launch_triplet_octets(ctx, a, c->d_labeling.p, label, c->d_clique_out.p, &c->route_move);
     if (st) return st;
     if (g1) MSM_HIP(hipEventRecord(g1, ctx->stream));
     MSM_HIP(hipMemcpyAsync((char *)pin + in_pad, c->d_clique_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -60,6 +60,8 @@ struct msm_cost {
     int64_t prefetch_hits = 0, prefetch_drops = 0;
     DevBuf<unsigned> d_defer_list, d_defer_cnt;
     int move_nblk = 0, move_cap = 0, move_parity = 0;
+    int move_maxtri = 0;                  // most control triangles in one workgroup of the fused move
+    int route_unary = 0, route_move = 0;  // msm_cost_routes: MSM_UNARY_* / MSM_MOVE_* as the launchers reported them
     bool move_valid = false;
     // get_source_data products
     bool have_source = false;

@@ -121,6 +121,7 @@ struct UnaryLaunch {
     const unsigned int *fix_off;   // unary_fix_segments() + 1 offsets from unary_fix_offsets()
     int *redo_list;                // N ints
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // optional: recorded around the samples kernel
+    int *route = nullptr;          // optional: the launcher writes the MSM_UNARY_* value of the reduction kernel it chose
 };
 int unary_nsplit(int L, int pmax);
 int unary_fix_segments();
@@ -216,11 +217,12 @@ struct MoveArgs {
 // launch_move runs the main kernel; the host launches the tail (launch_move_tail) only when host_flags[1] was set
 int launch_move_prepare(msm_ctx *ctx, const CliqueArgs &a, int nslots, int *slot_tri, double *slot_w, double *slot_sf, double *slot_cw, double *slot_wda,
                         double *tri_frame, double *tri_stat);
-int launch_move(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *labels, hipEvent_t ev_start, hipEvent_t ev_stop);
+// *route (optional): the MSM_MOVE_* value of the kernel the launcher chose
+int launch_move(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *labels, hipEvent_t ev_start, hipEvent_t ev_stop, int *route = nullptr);
 int launch_move_tail(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *labels);
 
 int launch_triplet_batch(msm_ctx *ctx, const CliqueArgs &a, const int *qt, const int *qa, const int *qb, const int *qc, int n, double *out);
-int launch_triplet_octets(msm_ctx *ctx, const CliqueArgs &a, const int *labeling, int label, double *out);
+int launch_triplet_octets(msm_ctx *ctx, const CliqueArgs &a, const int *labeling, int label, double *out, int *route = nullptr);
 struct MoveLabels;
 // the strain-only classes: labeling in the kernel arguments, costs to `out` (device or mapped host memory), raised statuses to host_flag
 int launch_triplet_octets_packed(msm_ctx *ctx, const CliqueArgs &a, const MoveLabels &lab, int label, double *out, int *host_flag);

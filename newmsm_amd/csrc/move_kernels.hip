@@ -515,7 +515,7 @@ static int move_mode(const CliqueArgs &a) {
 }
 static MoveLabels g_no_labels;  // handed over (and never read) when the labeling comes as a device array
 
-int launch_move(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *labels, hipEvent_t ev_start, hipEvent_t ev_stop) {
+int launch_move(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *labels, hipEvent_t ev_start, hipEvent_t ev_stop, int *route) {
     if (a.T <= 0 || m.nblk <= 0) return MSM_OK;
     const int mode = move_mode(a);
     // 256 threads and two rounds of samples per workgroup.  Measured alternatives (D = 1 / D = 32 kernel time against 32 / 95 us):
@@ -540,6 +540,7 @@ int launch_move(msm_ctx *ctx, const CliqueArgs &a, const MoveArgs &m, const Move
     else MSM_MOVE_LAUNCH(false);
 #undef MSM_MOVE_LAUNCH
     MSM_HIP(hipGetLastError());
+    if (route) *route = MSM_MOVE_FUSED_0 + mode;  // the launch above switches on this very value
     if (ev_stop) MSM_HIP(hipEventRecord(ev_stop, ctx->stream));
     return MSM_OK;
 }

@@ -1178,6 +1178,7 @@ int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u) {
     r.U = u.U;
     r.redo_list = u.redo_list;
     r.redo_count = u.fix_cnt;
+    if (u.route) *u.route = dice ? MSM_UNARY_UNIVARIATE : MSM_UNARY_FLAT;
     if (uses_ray_table(u.tree) && dice) {
         // the rank-counting DICE reduction is the wavefront-per-label kernel; all control points
         r.redo_list = nullptr;
@@ -1234,9 +1235,18 @@ int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWei
         m.stri = w.stri, m.sw3 = w.sw3;
         m.simmeasure = u.simmeasure;
         m.U = u.U;
-        if (!patchwise) hipLaunchKernelGGL(k_unary_reduce_mv8, dim3(u.N), dim3(256), 0, ctx->stream, m);
-        else if (u.D <= 32) hipLaunchKernelGGL(k_unary_reduce_pw8<4>, dim3(u.N), dim3(256), 0, ctx->stream, m);
-        else hipLaunchKernelGGL(k_unary_reduce_pw8<8>, dim3(u.N), dim3(256), 0, ctx->stream, m);
+        int route;
+        if (!patchwise) {
+            route = MSM_UNARY_MV8;
+            hipLaunchKernelGGL(k_unary_reduce_mv8, dim3(u.N), dim3(256), 0, ctx->stream, m);
+        } else if (u.D <= 32) {
+            route = MSM_UNARY_PW8_4;
+            hipLaunchKernelGGL(k_unary_reduce_pw8<4>, dim3(u.N), dim3(256), 0, ctx->stream, m);
+        } else {
+            route = MSM_UNARY_PW8_8;
+            hipLaunchKernelGGL(k_unary_reduce_pw8<8>, dim3(u.N), dim3(256), 0, ctx->stream, m);
+        }
+        if (u.route) *u.route = route;
     } else {
         size_t flds = (dice && patchwise) ? sizeof(double) * 8 * (size_t)u.pmax : 0;
         int threads = 256;
@@ -1247,6 +1257,7 @@ int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWei
         if (flds > 160 * 1024) return fail(MSM_ERR_CAPACITY, "a patch of %d points does not fit in LDS (patchwise DICE)", u.pmax);
         if (flds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_unary_reduce_features), hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
         hipLaunchKernelGGL(k_unary_reduce_features, dim3(u.N), dim3(threads), flds, ctx->stream, r);
+        if (u.route) *u.route = MSM_UNARY_FEATURES;
     }
     MSM_HIP(hipGetLastError());
     MSM_HIP(hipMemsetAsync(u.fix_cnt, 0, unary_fix_counter_words() * sizeof(unsigned), ctx->stream));  // counters are zero between launches

@@ -62,6 +62,51 @@ def oracle_anatomy_by_queries(cp_order=2, anat_order=4):
     return cxyz, ctri, axyz, atri, w_ptr, w_cp, w_val, face_ptr, face_idx
 
 
+# ---- the triclique classes' fusion move against the oracle (tests/test_gpu_hot_configs.py, tests/test_gpu_feature_widths.py)
+MOVE_RTOL, MOVE_ATOL = 1e-9, 1e-11
+HCP = dict(rmode=3, mu=0.4, kappa=1.6, k_exp=2.0, rexp=2.0)  # --shearmod --bulkmod --k_exponent --regexp of the two configs
+
+
+def close(got, want):
+    return np.allclose(got, want, rtol=MOVE_RTOL, atol=MOVE_ATOL, equal_nan=True)
+
+
+def move_labelings(cf, seed):
+    """two labelings a fusion sweep meets: all control points still on the centre label, and a mixed one"""
+    rng = np.random.default_rng(seed)
+    return [(np.zeros(cf.N, dtype=np.int32), int(rng.integers(1, cf.L))), (rng.integers(0, cf.L, cf.N).astype(np.int32), int(rng.integers(0, cf.L)))]
+
+
+def check_moves(cf, oc, triplets, seed, full):
+    """tripletOctets vs Fusion.h:188-195 replayed on the oracle: every triplet (full) or >= 200 of them, all 8 combinations"""
+    for labeling, label in move_labelings(cf, seed):
+        E = cf.tripletOctets(labeling, label)
+        assert E.shape == (cf.T, 8) and np.isfinite(E).all()
+        if full:
+            want = oc.triplet_octets(labeling, label, threads=8)
+            assert close(E, want), np.abs(E - want).max()
+            folded = want >= 1e6 * oc.params.lambda_
+            assert np.array_equal(E >= 1e6 * oc.params.lambda_, folded)
+        else:
+            rng = np.random.default_rng(seed + 1)
+            for t in rng.choice(cf.T, 240, replace=False):
+                ids = triplets[t]
+                for k in range(8):
+                    lab = [label if k >> (2 - j) & 1 else int(labeling[ids[j]]) for j in range(3)]
+                    w = oc.triplet(int(t), *lab)
+                    assert abs(E[t, k] - w) <= MOVE_ATOL + MOVE_RTOL * abs(w), (t, k, E[t, k], w)
+
+
+def ho_pair(ctx, inp, kind, lam):
+    from newmsm_amd import problem
+
+    cf, keep = problem.build_cost(ctx, inp, kind=kind, lambda_=lam, **HCP)
+    cf.get_source_data()
+    oc = oracle_cost(inp, kind, lambda_=lam, **HCP)
+    oc.get_source_data()
+    return cf, oc, keep
+
+
 ORACLE_THREADS = int(os.environ.get("MSM_ORACLE_THREADS", "8"))  # OpenMP threads of the oracle's table / octet evaluations
 
 

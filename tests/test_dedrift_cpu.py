@@ -26,7 +26,7 @@ def test_bindings_exist(built):
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES, name
         assert hasattr(lib, name), name
-    assert lib.msm_abi_version() == 11
+    assert lib.msm_abi_version() == 12
     for name in ("dedrift_group", "pairwise_stats", "ProductOps", "Dedrift", "format_stats", "distortion_summary"):
         assert hasattr(dedrift, name), name
 

@@ -15,49 +15,10 @@ import pytest
 
 import newmsm_amd as M
 from newmsm_amd import problem
-from tests.helpers import oracle_cost
+from tests.helpers import HCP, check_moves, close, ho_pair, move_labelings, oracle_cost
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-9, 1e-11
-HCP = dict(rmode=3, mu=0.4, kappa=1.6, k_exp=2.0, rexp=2.0)  # --shearmod --bulkmod --k_exponent --regexp of the two configs
-
-
-def close(got, want):
-    return np.allclose(got, want, rtol=RTOL, atol=ATOL, equal_nan=True)
-
-
-def move_labelings(cf, seed):
-    """two labelings a fusion sweep meets: all control points still on the centre label, and a mixed one"""
-    rng = np.random.default_rng(seed)
-    return [(np.zeros(cf.N, dtype=np.int32), int(rng.integers(1, cf.L))), (rng.integers(0, cf.L, cf.N).astype(np.int32), int(rng.integers(0, cf.L)))]
-
-
-def check_moves(cf, oc, triplets, seed, full):
-    """tripletOctets vs Fusion.h:188-195 replayed on the oracle: every triplet (full) or >= 200 of them, all 8 combinations"""
-    for labeling, label in move_labelings(cf, seed):
-        E = cf.tripletOctets(labeling, label)
-        assert E.shape == (cf.T, 8) and np.isfinite(E).all()
-        if full:
-            want = oc.triplet_octets(labeling, label, threads=8)
-            assert close(E, want), np.abs(E - want).max()
-            folded = want >= 1e6 * oc.params.lambda_
-            assert np.array_equal(E >= 1e6 * oc.params.lambda_, folded)
-        else:
-            rng = np.random.default_rng(seed + 1)
-            for t in rng.choice(cf.T, 240, replace=False):
-                ids = triplets[t]
-                for k in range(8):
-                    lab = [label if k >> (2 - j) & 1 else int(labeling[ids[j]]) for j in range(3)]
-                    w = oc.triplet(int(t), *lab)
-                    assert abs(E[t, k] - w) <= ATOL + RTOL * abs(w), (t, k, E[t, k], w)
-
-
-def ho_pair(ctx, inp, kind, lam):
-    cf, keep = problem.build_cost(ctx, inp, kind=kind, lambda_=lam, **HCP)
-    cf.get_source_data()
-    oc = oracle_cost(inp, kind, lambda_=lam, **HCP)
-    oc.get_source_data()
-    return cf, oc, keep
 
 
 @pytest.mark.parametrize("search", ["raytable", "complete"])

@@ -50,7 +50,7 @@ def test_bindings_exist(built):
     lib = M.lib()
     for name in ("msm_dedrift_set_warp", "msm_dedrift_group_stats_select"):
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.msm_abi_version() == 11
+    assert lib.msm_abi_version() == 12
     for name in ("set_warp", "group_stats_select"):
         assert hasattr(dedrift.Dedrift, name) and hasattr(dedrift.ProductOps, name), name
     assert hasattr(hierarchy, "merge_groups")
