@@ -7,8 +7,10 @@ import numpy as np
 import newmsm_amd as M
 from newmsm_amd import problem
 from tests.helpers import oracle_cost
+import similarity_edge_cases as edges  # (the script's directory is on sys.path)
 ctx = M.Context(0)
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 7)
+edge_rng = np.random.default_rng([int(sys.argv[1]) if len(sys.argv) > 1 else 7, 1])  # a stream of its own: a seed draws the configurations it always drew
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 bad = 0
 t0 = time.time()
@@ -26,11 +28,16 @@ for k in range(n):
     elif shape == 2: kw["target_radial"] = float(10 ** rng.uniform(-5, -2.5))
     elif shape == 3: kw["target_noise"] = float(rng.uniform(0.1, 1.0))
     sim = int(rng.choice([1, 2, 4, 5]))
+    edge = int(edge_rng.integers(0, 4))  # 1: both feature sets exactly 0 on a cap; 2: the cap, and weights from {0, 0.5, 1} (tests/similarity_edge_cases.py)
     try:
         inp = problem.pairwise_inputs(data_order, cp_order, D=D, **kw)
+        if edge in (1, 2): inp = edges.cap(inp)
         cf, keep = problem.build_cost(ctx, inp, kind=kind, simmeasure=sim, rmode=rmode, lambda_=lam)
-        cf.get_source_data()
         oc = oracle_cost(inp, kind, simmeasure=sim, rmode=rmode, lambda_=lam)
+        if edge == 2:
+            w = edges.zero_weights(inp, seed=k)
+            cf.set_dataaffintyweighting(w); oc.set_cfweight(w)
+        cf.get_source_data()
         if rmode != 1: oc.set_pairs(np.zeros((0, 2), dtype=np.int32))   # the model holds pairs or triplets, never both (M/DiscreteModel.cpp:99-102)
         else: oc.set_triplets(np.zeros((0, 3), dtype=np.int32))
         oc.get_source_data()
@@ -71,7 +78,7 @@ for k in range(n):
         print("   (error: %s)" % str(e)[:80])
     if not ok:
         bad += 1
-        print("MISMATCH", k, kind, D, sim, data_order, cp_order, kw, flush=True)
+        print("MISMATCH", k, kind, D, sim, data_order, cp_order, "edge", edge, kw, flush=True)
     else:
-        print("ok", k, kind, D, sim, data_order, cp_order, shape, flush=True)
+        print("ok", k, kind, D, sim, data_order, cp_order, shape, edge, flush=True)
 print("fuzz: %d configs, %d mismatches, %.0f s" % (n, bad, time.time() - t0))
