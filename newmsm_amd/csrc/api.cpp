@@ -1,5 +1,5 @@
-// api.cpp -- C ABI of libmsmhip (include/msmhip.h): contexts, meshes and the resampler entry points.
-// The cost-function entry points live in cost.cpp.
+// api.cpp -- C ABI of libmsmhip (include/msmhip.h): contexts, meshes, trees and queries.
+// The cost-function entry points live in cost.cpp, the resampler's in resample.cpp.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -379,10 +379,6 @@ static hipError_t ctx_scratch(msm_ctx *ctx, int slot, size_t bytes, void **out) 
 }
 
 constexpr int kRayQueryMin = 4096;  // queries from which a target's direction table is used by the plain search entry points (kernels.hip: launch_query_rays)
-int query_host(msm_mesh *target, const double *q, int N, int *tri_id, int *vid, double *w, int mode, const char *what, const double *q_on_device = nullptr);
-
-// q_on_device (optional): the same 3 x N points already in HBM (the vertices of a mesh handle of this context); the host copy
-// then stays where it is
 int query_host(msm_mesh *target, const double *q, int N, int *tri_id, int *vid, double *w, int mode, const char *what, const double *q_on_device) {
     msm_ctx *ctx = target->ctx;
     int st = ensure_tree(target);
@@ -460,60 +456,6 @@ int query_host(msm_mesh *target, const double *q, int N, int *tri_id, int *vid, 
     return st;
 }
 
-// compute_vertex_area for every vertex (R/mesh.cpp:1275-1283): mean area of the adjacent faces, in trID order
-void vertex_areas_of(const double *xyz, const int32_t *tri, int V, int T, const Adjacency &a, std::vector<double> &area) {
-    std::vector<double> ta(T);
-    auto pt = [&](int i) { return mk(xyz[i], xyz[V + i], xyz[2 * V + i]); };
-    for (int t = 0; t < T; ++t) ta[t] = tri_area(pt(tri[t]), pt(tri[T + t]), pt(tri[2 * T + t]));
-    area.resize(V);
-    for (int v = 0; v < V; ++v) {
-        double sum = 0;
-        for (int j = a.tid_ptr[v]; j < a.tid_ptr[v + 1]; ++j) sum += ta[a.tid[j]];
-        area[v] = sum / (a.tid_ptr[v + 1] - a.tid_ptr[v]);
-    }
-}
-
-int vertex_areas(msm_mesh *m, std::vector<double> &area) {
-    vertex_areas_of(m->xyz.data(), m->tri.data(), m->V, m->T, mesh_adjacency(m), area);
-    return MSM_OK;
-}
-
-// Resampler::get_adaptive_barycentric_weights, R/resampler.cpp:72-140, the variant with an exclusion mask (or meshes of two
-// contexts), in two halves: the 2 x N nearest-triangle queries run on the GPU (adaptive_queries); the list
-// surgery (transpose, pick, area correction) is done on the host in the reference's serial order so that every sum has the
-// same operand order (adaptive_surgery: touches no handle, so callers may run several of them on worker threads).  Without a
-// mask everything runs on the device: adaptive_weights_dev below.
-int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, AdaptiveQueries &q) {
-    const int nOld = in_mesh->V, nNew = new_mesh->V;
-    q.fvid.resize(3 * (size_t)nNew);
-    q.rvid.resize(3 * (size_t)nOld);
-    q.fw.resize(3 * (size_t)nNew);
-    q.rw.resize(3 * (size_t)nOld);
-    // the query points are the other mesh's vertices, which its handle keeps in HBM (same context, same stream)
-    const bool same_ctx = in_mesh->ctx == new_mesh->ctx;
-    int st = query_host(in_mesh, new_mesh->xyz.data(), nNew, nullptr, q.fvid.data(), q.fw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (forward)",
-                        same_ctx ? new_mesh->d_xyz.p : nullptr);
-    if (st) return st;
-    st = query_host(new_mesh, in_mesh->xyz.data(), nOld, nullptr, q.rvid.data(), q.rw.data(), MSM_WEIGHTS_PROJECTED, "adaptive weights (reverse)",
-                        same_ctx ? in_mesh->d_xyz.p : nullptr);
-    if (st) return st;
-    q.closest.clear();
-    if (with_closest) {
-        q.closest.resize(nNew);
-        msm_ctx *ctx = in_mesh->ctx;
-        DevBuf<double> dq;
-        DevBuf<int> dout;
-        MSM_TRY(dq.upload(new_mesh->xyz.data(), 3 * (size_t)nNew, ctx));
-        MSM_HIP(dout.ensure(nNew));
-        st = launch_closest_vertex(ctx, dev_tree(in_mesh), dq.p, nNew, dout.p);
-        if (st) return st;
-        MSM_TRY(dout.download(q.closest.data(), nNew, ctx));
-        st = check_status(ctx, "adaptive weights (exclusion)");
-        if (st) return st;
-    }
-    return MSM_OK;
-}
-
 int ensure_adjacency_dev(msm_mesh *m) {
     if (m->d_tid_ptr.p) return MSM_OK;
     msm_ctx *ctx = m->ctx;
@@ -527,190 +469,6 @@ int ensure_adjacency_dev(msm_mesh *m) {
     MSM_TRY(upload_staged(ctx, m->d_tid.p, adj.tid.data(), sizeof(int32_t) * adj.tid.size()));
     MSM_TRY(ctx_sync(ctx));
     return MSM_OK;
-}
-
-namespace {
-struct ResampleScratch {
-    DevBuf<int> fvid, rvid, counters, rkey, ckey, row_ptr, col, tkey, scan_tmp;  // counters: roff | rfill | coff | cfill | long_flag, zeroed together
-    DevBuf<double> fw, rw, oldA, newA, ta, rwt, cval, correction, val, data, out, tval;
-};
-ResampleScratch &resample_scratch(msm_ctx *ctx) {
-    if (!ctx->resample_scratch) ctx->resample_scratch = std::shared_ptr<void>(new ResampleScratch(), [](void *p) { delete static_cast<ResampleScratch *>(p); });
-    return *static_cast<ResampleScratch *>(ctx->resample_scratch.get());
-}
-}  // namespace
-
-int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check) {
-    // Everything is queued on in_mesh's context.  new_mesh may belong to another context of the same GPU (the fallback mesh of the
-    // gMSM set-up against the group's template) if its tree and adjacency are complete and synchronised: they are only read.
-    const bool foreign = in_mesh->ctx != new_mesh->ctx;
-    if (foreign && (in_mesh->ctx->device != new_mesh->ctx->device || !new_mesh->tree_valid || !new_mesh->d_tid_ptr.p))
-        return fail(MSM_ERR_INVALID, "adaptive weights: the two meshes belong to different contexts");
-    msm_ctx *ctx = in_mesh->ctx;
-    const int nOld = in_mesh->V, nNew = new_mesh->V;
-    int st = foreign ? ensure_tree(in_mesh) : ensure_tree_pair(in_mesh, new_mesh);
-    if (st) return st;
-    if ((st = ensure_adjacency_dev(in_mesh)) || (st = ensure_adjacency_dev(new_mesh))) return st;
-    ResampleScratch &s = resample_scratch(ctx);
-    const size_t cap = 3 * (size_t)nNew + 3 * (size_t)nOld;
-    MSM_HIP(s.fvid.ensure(3 * (size_t)nNew));
-    MSM_HIP(s.fw.ensure(3 * (size_t)nNew));
-    MSM_HIP(s.rvid.ensure(3 * (size_t)nOld));
-    MSM_HIP(s.rw.ensure(3 * (size_t)nOld));
-    MSM_HIP(s.oldA.ensure(nOld));
-    MSM_HIP(s.newA.ensure(nNew));
-    MSM_HIP(s.ta.ensure((size_t)std::max(in_mesh->T, new_mesh->T)));
-    MSM_HIP(s.counters.ensure(2 * (size_t)nNew + 2 * (size_t)nOld + 4));
-    MSM_HIP(s.rkey.ensure(3 * (size_t)nOld));
-    MSM_HIP(s.rwt.ensure(3 * (size_t)nOld));
-    MSM_HIP(s.ckey.ensure(cap));
-    MSM_HIP(s.cval.ensure(cap));
-    MSM_HIP(s.correction.ensure(nOld));
-    MSM_HIP(s.row_ptr.ensure((size_t)nNew + 1));
-    MSM_HIP(s.col.ensure(cap));
-    MSM_HIP(s.val.ensure(cap));
-    MSM_HIP(s.tkey.ensure(cap));
-    MSM_HIP(s.scan_tmp.ensure((size_t)std::max(nNew, nOld) / 4096 + 2));
-    MSM_HIP(s.tval.ensure(cap));
-    // forward: the new mesh's vertices in the old mesh's tree; reverse: the old vertices in the new mesh's tree (:74-78)
-    st = launch_query(ctx, dev_tree(in_mesh), new_mesh->d_xyz.p, nNew, nullptr, s.fvid.p, s.fw.p, MSM_WEIGHTS_PROJECTED);
-    if (st) return st;
-    st = launch_query(ctx, dev_tree(new_mesh), in_mesh->d_xyz.p, nOld, nullptr, s.rvid.p, s.rw.p, MSM_WEIGHTS_PROJECTED);
-    if (st) return st;
-    st = launch_vertex_areas(ctx, in_mesh->d_xyz.p, nOld, in_mesh->d_tri.p, in_mesh->T, in_mesh->d_tid_ptr.p, in_mesh->d_tid.p, s.ta.p, s.oldA.p);
-    if (st) return st;
-    st = launch_vertex_areas(ctx, new_mesh->d_xyz.p, nNew, new_mesh->d_tri.p, new_mesh->T, new_mesh->d_tid_ptr.p, new_mesh->d_tid.p, s.ta.p, s.newA.p);
-    if (st) return st;
-    AdaptiveDevArgs a;
-    a.nOld = nOld, a.nNew = nNew;
-    a.fvid = s.fvid.p, a.rvid = s.rvid.p, a.fw = s.fw.p, a.rw = s.rw.p, a.oldA = s.oldA.p, a.newA = s.newA.p;
-    a.roff = s.counters.p, a.rfill = a.roff + nNew + 1, a.coff = a.rfill + nNew, a.cfill = a.coff + nOld + 1, a.long_flag = a.cfill + nOld;
-    a.rkey = s.rkey.p, a.rwt = s.rwt.p;
-    a.ckey = s.ckey.p, a.cval = s.cval.p, a.correction = s.correction.p;
-    a.row_ptr = s.row_ptr.p, a.col = s.col.p, a.val = s.val.p, a.tkey = s.tkey.p, a.tval = s.tval.p, a.scan_tmp = s.scan_tmp.p;
-    st = launch_adaptive_surgery(ctx, a);
-    if (st) return st;
-    if (check) {
-        st = check_status(ctx, "adaptive weights");  // a failed search in either direction (synchronises)
-        if (st) return st;
-    }
-    out.nOld = nOld, out.nNew = nNew, out.row_ptr = s.row_ptr.p, out.col = s.col.p, out.val = s.val.p;
-    return MSM_OK;
-}
-
-int apply_weights_dev(msm_ctx *ctx, const AdaptiveDev &w, const double *d_data, int D, double *d_out) {
-    return launch_apply_rows(ctx, w.nNew, w.nOld, D, w.row_ptr, w.col, w.val, d_data, d_out);
-}
-
-// weights as host CSR through the device surgery (no exclusion mask)
-static int adaptive_weights_via_device(msm_mesh *in_mesh, msm_mesh *new_mesh, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col, std::vector<double> &val) {
-    AdaptiveDev w;
-    int st = adaptive_weights_dev(in_mesh, new_mesh, w);
-    if (st) return st;
-    msm_ctx *ctx = in_mesh->ctx;
-    row_ptr.resize((size_t)w.nNew + 1);
-    MSM_TRY(stage_d2h(ctx, row_ptr.data(), w.row_ptr, sizeof(int32_t) * row_ptr.size()));
-    MSM_TRY(ctx_sync(ctx));
-    const size_t nnz = (size_t)row_ptr.back();
-    col.resize(nnz);
-    val.resize(nnz);
-    if (nnz) {
-        MSM_TRY(stage_d2h(ctx, col.data(), w.col, sizeof(int32_t) * nnz));
-        MSM_TRY(stage_d2h(ctx, val.data(), w.val, sizeof(double) * nnz));
-        MSM_TRY(ctx_sync(ctx));
-    }
-    return MSM_OK;
-}
-
-int adaptive_weights(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *excl, std::vector<int32_t> &row_ptr,
-                     std::vector<int32_t> &col, std::vector<double> &val) {
-    if (!excl && in_mesh->ctx == new_mesh->ctx) return adaptive_weights_via_device(in_mesh, new_mesh, row_ptr, col, val);
-    AdaptiveQueries q;
-    int st = adaptive_queries(in_mesh, new_mesh, excl != nullptr, q);
-    if (st) return st;
-    std::vector<double> oldA, newA;
-    vertex_areas(in_mesh, oldA);
-    vertex_areas(new_mesh, newA);
-    adaptive_surgery(q, in_mesh->V, new_mesh->V, oldA, newA, excl, row_ptr, col, val);
-    return MSM_OK;
-}
-
-void adaptive_surgery(const AdaptiveQueries &q, int nOld, int nNew, const std::vector<double> &oldA, const std::vector<double> &newA,
-                      const double *excl, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col, std::vector<double> &val) {
-    const std::vector<int> &fvid = q.fvid, &rvid = q.rvid, &closest = q.closest;
-    const std::vector<double> &fw = q.fw, &rw = q.rw;
-    struct Entry {
-        int32_t key;
-        double w;
-    };
-    // a std::map<int,double> holding the three weights of one query: ascending key, later writes win
-    auto small_map = [](const int *vid, const double *w, int stride, int k, Entry out[3]) {
-        int n = 0;
-        for (int j = 0; j < 3; ++j) {
-            const int32_t key = vid[j * stride + k];
-            const double wt = w[j * stride + k];
-            int pos = 0;
-            while (pos < n && out[pos].key < key) ++pos;
-            if (pos < n && out[pos].key == key) {
-                out[pos].w = wt;
-                continue;
-            }
-            for (int q = n; q > pos; --q) out[q] = out[q - 1];
-            out[pos] = Entry{key, wt};
-            ++n;
-        }
-        return n;
-    };
-    // reverse lists transposed: for each new vertex the old vertices whose triangle contains it (:91-97);
-    // old vertices are visited in ascending order, so each list is already sorted by key
-    std::vector<int32_t> rcount(nNew + 1, 0);
-    for (int o = 0; o < nOld; ++o) {
-        Entry e[3];
-        const int n = small_map(rvid.data(), rw.data(), nOld, o, e);
-        for (int j = 0; j < n; ++j) rcount[e[j].key + 1]++;
-    }
-    for (int k = 0; k < nNew; ++k) rcount[k + 1] += rcount[k];
-    std::vector<Entry> rlist(rcount[nNew]);
-    {
-        std::vector<int32_t> fill(rcount.begin(), rcount.end() - 1);
-        for (int o = 0; o < nOld; ++o) {
-            Entry e[3];
-            const int n = small_map(rvid.data(), rw.data(), nOld, o, e);
-            for (int j = 0; j < n; ++j) rlist[fill[e[j].key]++] = Entry{o, e[j].w};
-        }
-    }
-    row_ptr.assign(nNew + 1, 0);
-    col.clear();
-    val.clear();
-    std::vector<double> correction(nOld, 0.0);
-    std::vector<char> active(nNew, 0);
-    for (int k = 0; k < nNew; ++k) {  // :99-118
-        row_ptr[k] = (int32_t)col.size();
-        if (excl && !(closest[k] >= 0 && excl[closest[k]] != 0)) continue;
-        active[k] = 1;
-        Entry f[3];
-        const int nf = small_map(fvid.data(), fw.data(), nNew, k, f);
-        const int nr = rcount[k + 1] - rcount[k];
-        const Entry *src = (nr <= nf) ? f : &rlist[rcount[k]];
-        const int n = (nr <= nf) ? nf : nr;
-        for (int j = 0; j < n; ++j) {
-            const double wgt = src[j].w * newA[k];
-            col.push_back(src[j].key);
-            val.push_back(wgt);
-            correction[src[j].key] += wgt;
-        }
-    }
-    row_ptr[nNew] = (int32_t)col.size();
-    for (int k = 0; k < nNew; ++k) {  // :120-137
-        if (!active[k]) continue;
-        double wsum = 0.0;
-        for (int e = row_ptr[k]; e < row_ptr[k + 1]; ++e) {
-            val[e] *= oldA[col[e]] / correction[col[e]];
-            wsum += val[e];
-        }
-        if (wsum != 0.0)
-            for (int e = row_ptr[k]; e < row_ptr[k + 1]; ++e) val[e] /= wsum;
-    }
 }
 
 }  // namespace msm
@@ -1107,88 +865,6 @@ int msm_closest_vertex(msm_mesh *target, const double *q, int32_t N, int32_t *v_
     st = check_status(ctx, "msm_closest_vertex");
     std::memcpy(v_id, (char *)pin + pq, bo);
     return st;
-}
-
-int msm_adaptive_barycentric_weights(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *excl, int32_t *row_ptr, int32_t *col, double *val,
-                                     int64_t cap, int64_t *nnz) {
-    if (!in_mesh || !new_mesh) return fail(MSM_ERR_INVALID, "msm_adaptive_barycentric_weights: null mesh");
-    std::vector<int32_t> rp, c;
-    std::vector<double> v;
-    int st = adaptive_weights(in_mesh, new_mesh, excl, rp, c, v);
-    if (st) return st;
-    if (nnz) *nnz = (int64_t)c.size();
-    if (!col) return MSM_OK;
-    if ((int64_t)c.size() > cap) return fail(MSM_ERR_CAPACITY, "weights need %zu entries, buffer holds %lld", c.size(), (long long)cap);
-    if (row_ptr) std::copy(rp.begin(), rp.end(), row_ptr);
-    std::copy(c.begin(), c.end(), col);
-    if (val) std::copy(v.begin(), v.end(), val);
-    return MSM_OK;
-}
-
-int msm_metric_resample(msm_mesh *in_mesh, const double *data, int32_t D, msm_mesh *new_mesh, const double *excl, double *out, double *excl_out) {
-    if (!in_mesh || !new_mesh || !data || !out || D <= 0) return fail(MSM_ERR_INVALID, "msm_metric_resample: bad arguments");
-    if (!excl && !excl_out && in_mesh->ctx == new_mesh->ctx) {
-        // queries, list surgery and the weighted sums on the device; only the data go up and the resampled data come back
-        msm_ctx *ctx = in_mesh->ctx;
-        AdaptiveDev w;
-        int st = adaptive_weights_dev(in_mesh, new_mesh, w);
-        if (st) return st;
-        ResampleScratch &s = resample_scratch(ctx);
-        const size_t nin = (size_t)D * in_mesh->V, nout = (size_t)D * new_mesh->V;
-        MSM_HIP(s.data.ensure(nin));
-        MSM_HIP(s.out.ensure(nout));
-        st = upload_staged(ctx, s.data.p, data, sizeof(double) * nin);
-        if (st) return st;
-        st = apply_weights_dev(ctx, w, s.data.p, D, s.out.p);
-        if (st) return st;
-        if (ctx_mapped(ctx, out, sizeof(double) * nout)) {  // the caller's array is pinned for this context: one copy command, no memcpy
-            MSM_HIP(hipMemcpyAsync(out, s.out.p, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
-            MSM_TRY(ctx_sync(ctx));
-            return MSM_OK;
-        }
-        void *pin = nullptr;
-        st = ctx_io_pinned(ctx, sizeof(double) * nout, &pin);
-        if (st) return st;
-        MSM_HIP(hipMemcpyAsync(pin, s.out.p, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
-        MSM_TRY(ctx_sync(ctx));
-        std::memcpy(out, pin, sizeof(double) * nout);
-        return MSM_OK;
-    }
-    std::vector<int32_t> rp, c;
-    std::vector<double> v;
-    int st = adaptive_weights(in_mesh, new_mesh, excl, rp, c, v);
-    if (st) return st;
-    const int Vin = in_mesh->V, Vn = new_mesh->V;
-    for (int d = 0; d < D; ++d)  // barycentric_data_interpolation, R/resampler.cpp:40-52
-        for (int k = 0; k < Vn; ++k) {
-            double acc = 0.0;
-            for (int e = rp[k]; e < rp[k + 1]; ++e)
-                if (!excl || excl[c[e]] != 0) acc += data[(size_t)d * Vin + c[e]] * v[e];
-            out[(size_t)d * Vn + k] = acc;
-        }
-    if (excl && excl_out)  // :54-67
-        for (int k = 0; k < Vn; ++k) {
-            double acc = 0.0;
-            for (int e = rp[k]; e < rp[k + 1]; ++e)
-                if (excl[c[e]] != 0) acc += excl[c[e]] * v[e];
-            excl_out[k] = acc;
-        }
-    return MSM_OK;
-}
-
-int msm_create_exclusion(const double *data, int32_t D, int32_t V, double thrl, double thru, double *excl) {
-    if (!data || !excl || D < 0 || V < 0) return fail(MSM_ERR_INVALID, "msm_create_exclusion: bad arguments");
-    for (int i = 0; i < V; ++i) {
-        excl[i] = 0.0;
-        for (int d = 0; d < D; ++d) {
-            const double x = data[(size_t)d * V + i];
-            if (!(x >= (thrl - kEps) && x <= (thru + kEps))) {
-                excl[i] = 1.0;
-                break;
-            }
-        }
-    }
-    return MSM_OK;
 }
 
 // shared by the coordinate-resampling entry points: out = sum_j w_j * coords[v_j], ids in ascending order

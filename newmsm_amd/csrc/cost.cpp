@@ -13,6 +13,7 @@
 
 #include "cost_internal.hpp"
 #include "host_parallel.hpp"
+#include "resample.hpp"
 
 using namespace msm;
 

@@ -111,8 +111,6 @@ struct msm_cost {
 
 
 namespace msm {
-int query_host(msm_mesh *target, const double *q, int N, int *tri_id, int *vid, double *w, int mode, const char *what, const double *q_on_device = nullptr);
-const Adjacency &mesh_adjacency(msm_mesh *m);
 // (re)computes the per (control point, label) rotation matrices and moved control points if stale
 int ensure_label_rotations(msm_cost *c);
 int drop_pending_move(msm_cost *c);  // cost_cliques.cpp: waits for and discards a label step queued by msm_cost_triplet_octets_prefetch that nobody took

@@ -8,6 +8,7 @@
 
 #include "dedrift.hpp"
 #include "kernels.hpp"
+#include "resample.hpp"
 
 using namespace msm;
 

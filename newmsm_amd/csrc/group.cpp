@@ -23,6 +23,7 @@
 #include "devbuf.hpp"
 #include "host_parallel.hpp"
 #include "kernels.hpp"
+#include "resample.hpp"
 
 using namespace msm;
 
@@ -97,8 +98,8 @@ struct msm_group {
     // the per-label remainder of a subject's set-up with the label as the second grid dimension of every launch (stage_batch)
     struct Batch {
         msm_ctx *ctx = nullptr;  // a stream of its own: runs beside the main stream's preparation of the next subject
-        DevBuf<int> fvid, rvid, roff, rfill, rkey, coff, cfill, ckey, row_ptr, col, tkey, scan_tmp, long_flag, open;
-        DevBuf<double> fw, rw, oldA, newA, ta, rwt, cval, correction, val, tval;
+        SurgeryScratch surgery;  // of the L problems of one subject
+        DevBuf<int> open;
         DevBuf<int2> info[2];
     };
     // One set-up pipeline: a main stream (rotations, forest of the next subject), a batch stream (the per-label work and the patch lists of the
@@ -860,32 +861,10 @@ static int stage_batch(msm_group *g, int s, msm_group::Stage &b, int which, msm_
     const int L = g->L, D = g->D;
     msm_mesh *dm = g->data[s], *tm = g->tmpl;
     const int V = dm->V, T = dm->T, Vt = tm->V, Tt = tm->T;
-    const size_t LV = (size_t)L * V, LVt = (size_t)L * Vt, cap = 3 * (size_t)Vt + 3 * (size_t)V;
+    const size_t LV = (size_t)L * V, LVt = (size_t)L * Vt;
     int st = MSM_OK;  // (the data mesh's adjacency lists are on the device: group_setup_pipeline saw to it before the pipelines started)
-    const size_t nscan = (size_t)std::max(V, Vt) / 4096 + 2;
-    MSM_HIP(w.fvid.ensure(3 * LVt));
-    MSM_HIP(w.fw.ensure(3 * LVt));
-    MSM_HIP(w.rvid.ensure(3 * LV));
-    MSM_HIP(w.rw.ensure(3 * LV));
-    MSM_HIP(w.oldA.ensure(LV));
-    MSM_HIP(w.newA.ensure(Vt));
-    MSM_HIP(w.ta.ensure((size_t)L * std::max(T, Tt)));
-    MSM_HIP(w.roff.ensure((size_t)L * (Vt + 1)));
-    MSM_HIP(w.rfill.ensure(LVt));
-    MSM_HIP(w.rkey.ensure(3 * LV));
-    MSM_HIP(w.rwt.ensure(3 * LV));
-    MSM_HIP(w.coff.ensure((size_t)L * (V + 1)));
-    MSM_HIP(w.cfill.ensure(LV));
-    MSM_HIP(w.ckey.ensure(L * cap));
-    MSM_HIP(w.cval.ensure(L * cap));
-    MSM_HIP(w.correction.ensure(LV));
-    MSM_HIP(w.row_ptr.ensure((size_t)L * (Vt + 1)));
-    MSM_HIP(w.col.ensure(L * cap));
-    MSM_HIP(w.val.ensure(L * cap));
-    MSM_HIP(w.tkey.ensure(L * cap));
-    MSM_HIP(w.tval.ensure(L * cap));
-    MSM_HIP(w.scan_tmp.ensure((size_t)L * nscan));
-    MSM_HIP(w.long_flag.ensure(2 * (size_t)L));
+    SurgeryScratch &sc = w.surgery;
+    MSM_TRY(sc.ensure(V, Vt, T, Tt, L));
     std::vector<int2> info(L);
     for (int l = 0; l < L; ++l) info[l] = make_int2(b.forest.info[l].nnodes, b.forest.info[l].grid_depth);
     MSM_HIP(w.info[which].ensure(L));
@@ -897,27 +876,16 @@ static int stage_batch(msm_group *g, int s, msm_group::Stage &b, int which, msm_
     fd.s_node = b.forest.s_node, fd.s_leaf = b.forest.s_leaf, fd.s_rec = b.forest.s_rec, fd.s_grid = b.forest.s_grid;
     fd.info = w.info[which].p;
     // forward: the template's vertices in every label's tree; reverse: every label's vertices in the template's tree (:74-78)
-    st = launch_query_forest(ctx, fd, L, tm->d_xyz.p, Vt, w.fvid.p, w.fw.p, LVt);
+    st = launch_query_forest(ctx, fd, L, tm->d_xyz.p, Vt, sc.fvid.p, sc.fw.p, LVt);
     if (st) return st;
     MSM_HIP(w.open.ensure(LV + 1));
-    st = launch_query_rays(ctx, dev_tree(tm), b.d_rot.p, (int)LV, nullptr, w.rvid.p, w.rw.p, MSM_WEIGHTS_PROJECTED, w.open.p);  // (the template's direction table: group_setup_pipeline)
+    st = launch_query_rays(ctx, dev_tree(tm), b.d_rot.p, (int)LV, nullptr, sc.rvid.p, sc.rw.p, MSM_WEIGHTS_PROJECTED, w.open.p);  // (the template's direction table: group_setup_pipeline)
     if (st) return st;
-    st = launch_vertex_areas_batch(ctx, b.d_rot.p, LV, (size_t)V, V, dm->d_tri.p, T, dm->d_tid_ptr.p, dm->d_tid.p, L, w.ta.p, w.oldA.p);
+    st = launch_vertex_areas_batch(ctx, b.d_rot.p, LV, (size_t)V, V, dm->d_tri.p, T, dm->d_tid_ptr.p, dm->d_tid.p, L, sc.ta.p, sc.oldA.p);
     if (st) return st;
-    st = launch_vertex_areas_batch(ctx, tm->d_xyz.p, (size_t)Vt, 0, Vt, tm->d_tri.p, Tt, tm->d_tid_ptr.p, tm->d_tid.p, 1, w.ta.p, w.newA.p);
+    st = launch_vertex_areas_batch(ctx, tm->d_xyz.p, (size_t)Vt, 0, Vt, tm->d_tri.p, Tt, tm->d_tid_ptr.p, tm->d_tid.p, 1, sc.ta.p, sc.newA.p);
     if (st) return st;
-    AdaptiveDevArgs a;
-    a.nOld = V, a.nNew = Vt;
-    a.fvid = w.fvid.p, a.fw = w.fw.p, a.rvid = w.rvid.p, a.rw = w.rw.p, a.oldA = w.oldA.p, a.newA = w.newA.p;
-    a.roff = w.roff.p, a.rfill = w.rfill.p, a.rkey = w.rkey.p, a.rwt = w.rwt.p;
-    a.coff = w.coff.p, a.cfill = w.cfill.p, a.ckey = w.ckey.p, a.cval = w.cval.p, a.correction = w.correction.p;
-    a.scan_tmp = w.scan_tmp.p, a.long_flag = w.long_flag.p, a.tkey = w.tkey.p, a.tval = w.tval.p;
-    a.row_ptr = w.row_ptr.p, a.col = w.col.p, a.val = w.val.p;
-    a.B = L;
-    a.fstride = LVt, a.rstride = LV;
-    a.s_f = (size_t)Vt, a.s_r = (size_t)V, a.s_oldA = (size_t)V, a.s_newA = 0;
-    a.s_roff = (size_t)Vt + 1, a.s_rfill = (size_t)Vt, a.s_r3 = 3 * (size_t)V;
-    a.s_coff = (size_t)V + 1, a.s_cfill = (size_t)V, a.s_cap = cap, a.s_corr = (size_t)V, a.s_rowptr = (size_t)Vt + 1, a.s_scan = nscan;
+    const AdaptiveDevArgs a = sc.args(V, Vt, L);
     st = launch_adaptive_surgery(ctx, a);
     if (st) return st;
     st = launch_apply_rows_batch(ctx, a, D, b.d_feat.p, g->Fslab[s]->p, (size_t)D * Vt);

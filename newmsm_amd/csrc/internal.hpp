@@ -173,7 +173,7 @@ struct msm_ctx {
     // a mapped pinned word kernels of the per-label-step calls store a raised status into (no status copy on their fast path)
     int *h_flag = nullptr;
     int *d_flag_map = nullptr;  // its device address
-    std::shared_ptr<void> resample_scratch;  // api.cpp: device buffers of adaptive_weights_dev, kept between calls
+    std::shared_ptr<void> resample_scratch;  // resample.cpp: device buffers of adaptive_weights_dev and msm_metric_resample, kept between calls
     std::shared_ptr<void> histmatch_scratch;  // histmatch.cpp: device buffers of msm_histogram_match, kept between calls
     std::shared_ptr<void> cohort_scratch;     // cohort.cpp: device buffers of msm_surface_distortion and msm_abs_summary, kept between calls
     // msm_ctx_time_queries: events around the search kernel of the host-array query entry points
@@ -240,29 +240,14 @@ struct msm_mesh {
 };
 
 namespace msm {
-// Resampler::get_adaptive_barycentric_weights in two halves (api.cpp)
-struct AdaptiveQueries {
-    std::vector<int> fvid, rvid, closest;  // forward (new -> old) and reverse (old -> new) hit-triangle vertex ids, 3 x N SoA
-    std::vector<double> fw, rw;            // and their projected barycentric weights
-};
-// directions: 1 forward (new -> old), 2 reverse (old -> new), 3 both
-int adaptive_queries(msm_mesh *in_mesh, msm_mesh *new_mesh, bool with_closest, AdaptiveQueries &q);
-// The same weights with queries AND list surgery on the device (resample_kernels.hip; no exclusion mask): the CSR stays in HBM.
-struct AdaptiveDev {
-    int nOld = 0, nNew = 0;
-    const int *row_ptr = nullptr, *col = nullptr;  // device; valid until the next adaptive_weights_dev on this context
-    const double *val = nullptr;
-};
-int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check = true);  // check = false: the caller checks the status word
-// out (device, D x V(new)) = the weights applied to d_data (device, D x V(in)): barycentric_data_interpolation R/resampler.cpp:40-52
-int apply_weights_dev(msm_ctx *ctx, const AdaptiveDev &w, const double *d_data, int D, double *d_out);
 int ensure_adjacency_dev(msm_mesh *m);  // Mpoint::trID lists as CSR in HBM (d_tid_ptr / d_tid), and d_fold
+const Adjacency &mesh_adjacency(msm_mesh *m);  // the host's lists, built on first use
 // the host copy of the coordinates follows the device when they were last written there (msm_mesh::host_xyz_stale); fetched on via's stream
 int refresh_host_xyz(msm_mesh *m, msm_ctx *via);
 int ensure_tree_pair(msm_mesh *a, msm_mesh *b);  // both trees; a host build of one runs while the GPU builds the other
-void adaptive_surgery(const AdaptiveQueries &q, int nOld, int nNew, const std::vector<double> &oldA, const std::vector<double> &newA,
-                      const double *excl, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col, std::vector<double> &val);
-void vertex_areas_of(const double *xyz, const int32_t *tri, int V, int T, const Adjacency &a, std::vector<double> &area);
+// get_barycentric_weights on the device for host-resident query points; q_on_device (optional): the same 3 x N points already in HBM (the vertices
+// of a mesh handle of this context); the host copy then stays where it is
+int query_host(msm_mesh *target, const double *q, int N, int *tri_id, int *vid, double *w, int mode, const char *what, const double *q_on_device = nullptr);
 int ensure_tree(msm_mesh *m);  // build + upload the search structure if stale
 // octree_kernels.hip: the same tree built in HBM from the mesh's device coordinates (MSM_ERR_CAPACITY: use the host build)
 int gpu_build_octree(msm_mesh *m, const std::function<void()> *overlap = nullptr);

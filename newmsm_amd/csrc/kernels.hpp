@@ -1,4 +1,4 @@
-// kernels.hpp -- launch wrappers implemented in kernels.hip (device pointers only).
+// kernels.hpp -- launch wrappers implemented in the *_kernels.hip files (device pointers only); the resampler's are in resample.hpp.
 #pragma once
 
 #include "internal.hpp"
@@ -15,39 +15,6 @@ int launch_build_recs(msm_ctx *ctx, const double *d_xyz, int V, const int32_t *d
 int launch_build_recs_forest(msm_ctx *ctx, const double *d_xyz, size_t comp_stride, size_t tree_stride, const int32_t *d_tri, int T, int B, TriRec *d_rec, float4 *d_tcone,
                              size_t s_rec, const int32_t *d_leaf_tri, float4 *d_cone, size_t s_leaf, const int *d_entries, size_t entries_stride);
 int launch_build_raytri(msm_ctx *ctx, const TriRec *d_rec, const float4 *d_edge, int T, const double *d_feat1, int D, float4 *d_out);
-// ---- adaptive barycentric weights on the device (resample_kernels.hip): Resampler::get_adaptive_barycentric_weights R/resampler.cpp:72-140
-struct AdaptiveDevArgs {
-    int nOld, nNew;
-    const int *fvid, *rvid;        // forward (new -> old) / reverse (old -> new) hit-triangle vertex ids, 3 x N SoA
-    const double *fw, *rw;         // their projected barycentric weights
-    const double *oldA, *newA;     // vertex areas
-    int *roff, *rfill, *rkey;      // transposed reverse lists: offsets (nNew + 1), fill counters (nNew), old vertex ids (3 nOld)
-    double *rwt;
-    int *coff, *cfill, *ckey;      // columns of the result: offsets (nOld + 1), fill counters (nOld), new vertex ids (3 nNew + 3 nOld)
-    double *cval, *correction;     // (nOld)
-    int *scan_tmp;                 // scratch of the prefix sums, max(nNew, nOld) / 4096 + 2
-    int *long_flag;                // 2 per problem: does any transposed reverse list / any column exceed the short sort's limit?
-    int *tkey;                     // scratch of the long-list sort, 3 nNew + 3 nOld
-    double *tval;
-    int *row_ptr, *col;            // the result as CSR: nNew + 1, 3 nNew + 3 nOld
-    double *val;
-    // B problems at once (gMSM: a subject's data mesh rotated to every label against the one template): problem b = blockIdx.y of
-    // every launch uses the arrays b * stride elements further on.  fstride / rstride: distance between the three components of
-    // fvid / fw and rvid / rw (nNew and nOld for one problem).  All strides 0 and B = 1 for one problem.
-    int B = 1;
-    size_t fstride = 0, rstride = 0;
-    size_t s_f = 0, s_r = 0, s_oldA = 0, s_newA = 0, s_roff = 0, s_rfill = 0, s_r3 = 0, s_coff = 0, s_cfill = 0, s_cap = 0, s_corr = 0, s_rowptr = 0, s_scan = 0;
-};
-// vertex areas of B coordinate sets over one triangle list: component c of vertex i of set b at xyz[c * comp + b * set + i];
-// ta: scratch, B x T; area: B x V
-int launch_vertex_areas_batch(msm_ctx *ctx, const double *d_xyz, size_t comp, size_t set, int V, const int32_t *d_tri, int T, const int32_t *d_tid_ptr, const int32_t *d_tid,
-                              int B, double *d_ta, double *d_area);
-// out[b][d][k] = problem b's weights applied to data (D x nOld, shared by the problems); out: B blocks of out_stride doubles
-int launch_apply_rows_batch(msm_ctx *ctx, const AdaptiveDevArgs &a, int D, const double *d_data, double *d_out, size_t out_stride);
-int launch_vertex_areas(msm_ctx *ctx, const double *d_xyz, int V, const int32_t *d_tri, int T, const int32_t *d_tid_ptr, const int32_t *d_tid, double *d_ta,
-                        double *d_area);
-int launch_adaptive_surgery(msm_ctx *ctx, const AdaptiveDevArgs &a);
-int launch_apply_rows(msm_ctx *ctx, int nNew, int nOld, int D, const int *row_ptr, const int *col, const double *val, const double *d_data, double *d_out);
 // n doubles from device memory into mapped pinned host memory, and the context's status word into flags_mapped[0] when it is set
 int launch_copy_to_mapped(msm_ctx *ctx, const double *d_src, double *mapped_dst, size_t n, int *flags_mapped);
 int launch_query(msm_ctx *ctx, const DevTree &T, const double *d_q, int N, int *d_tri, int *d_vid, double *d_w, int mode);

@@ -12,10 +12,6 @@
 
 using namespace msm;
 
-namespace msm {
-const Adjacency &mesh_adjacency(msm_mesh *m);
-}
-
 namespace {
 
 struct FoldMesh {

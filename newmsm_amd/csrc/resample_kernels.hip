@@ -13,41 +13,17 @@
 //   row sums                   a thread per row, in entry (= key) order.
 // So every floating-point sum has the reference's operand order and the weights are bit-identical to the host surgery's
 // (tests/test_gpu_search.py, tests/fuzz_resample.py compare them with the oracle bit for bit).  The exclusion-mask variant keeps
-// the host path (api.cpp: adaptive_surgery).
+// the host path (resample.cpp: adaptive_surgery).
 #include <climits>
 #include <algorithm>
 
 #include "devbuf.hpp"
 #include "kernels.hpp"
+#include "resample.hpp"
 
 namespace msm {
 
 namespace {
-
-struct Entry {
-    int key;
-    double w;
-};
-
-// a std::map<int,double> holding the three weights of one query: ascending key, later writes win
-__device__ __forceinline__ int small_map(const int *__restrict__ vid, const double *__restrict__ w, int stride, int k, Entry out[3]) {
-    int n = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int key = vid[(size_t)j * stride + k];
-        const double wt = w[(size_t)j * stride + k];
-        int pos = 0;
-        while (pos < n && out[pos].key < key) ++pos;
-        if (pos < n && out[pos].key == key) {
-            out[pos].w = wt;
-            continue;
-        }
-        for (int q = n; q > pos; --q) out[q] = out[q - 1];
-        out[pos] = Entry{key, wt};
-        ++n;
-    }
-    return n;
-}
 
 // component c of vertex i of coordinate set blockIdx.y at xyz[c * comp + blockIdx.y * set + i] (one mesh: comp = V, set = 0)
 __global__ __launch_bounds__(256) void k_tri_areas(const double *__restrict__ xyz, size_t comp, size_t set, const int32_t *__restrict__ tri, int T, double *__restrict__ ta) {
@@ -143,7 +119,7 @@ __global__ __launch_bounds__(256) void k_rev_count(AdaptiveDevArgs a) {
     a = problem_view(a);
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= a.nOld) return;
-    Entry e[3];
+    WeightEntry e[3];
     const int n = small_map(a.rvid, a.rw, (int)a.rstride, o, e);
     for (int j = 0; j < n; ++j)
         if (e[j].key >= 0) atomicAdd(&a.roff[e[j].key], 1);
@@ -152,7 +128,7 @@ __global__ __launch_bounds__(256) void k_rev_fill(AdaptiveDevArgs a) {
     a = problem_view(a);
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= a.nOld) return;
-    Entry e[3];
+    WeightEntry e[3];
     const int n = small_map(a.rvid, a.rw, (int)a.rstride, o, e);
     for (int j = 0; j < n; ++j) {
         if (e[j].key < 0) continue;
@@ -230,7 +206,7 @@ __global__ __launch_bounds__(256) void k_row_len(AdaptiveDevArgs a) {
     a = problem_view(a);
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.nNew) return;
-    Entry f[3];
+    WeightEntry f[3];
     const int nf = small_map(a.fvid, a.fw, (int)a.fstride, k, f), nr = a.roff[k + 1] - a.roff[k];
     a.row_ptr[k] = nr <= nf ? nf : nr;
 }
@@ -245,7 +221,7 @@ __global__ __launch_bounds__(256) void k_row_write(AdaptiveDevArgs a) {
     a = problem_view(a);
     const int gid = blockIdx.x * blockDim.x + threadIdx.x, k = gid / LPR, sub = gid % LPR;
     if (k >= a.nNew) return;
-    Entry f[3];
+    WeightEntry f[3];
     const int nf = small_map(a.fvid, a.fw, (int)a.fstride, k, f), nr = a.roff[k + 1] - a.roff[k];
     const int n = nr <= nf ? nf : nr, at = a.row_ptr[k];
     const double area = a.newA[k];
@@ -401,30 +377,13 @@ static int lanes_per_row(double len) { return len <= 6.0 ? 1 : (len <= 96.0 ? 8 
         else MSM_LAUNCH2D(kernel<1>, (size_t)(n), B, __VA_ARGS__);            \
     } while (0)
 
-int launch_adaptive_surgery(msm_ctx *ctx, const AdaptiveDevArgs &arg) {
-    AdaptiveDevArgs a = arg;
+// a: from SurgeryScratch::args, nothing else -- the clear below relies on its one-block layout of the counters
+int launch_adaptive_surgery(msm_ctx *ctx, const AdaptiveDevArgs &a) {
     const int nOld = a.nOld, nNew = a.nNew, B = std::max(a.B, 1);
-    if (a.fstride == 0) a.fstride = (size_t)nNew;
-    if (a.rstride == 0) a.rstride = (size_t)nOld;
     // rows: the forward list (3) or the transposed reverse list (3 nOld / nNew on average); columns: 3 nNew / nOld or the reverse list's 3
     const int row_lpr = lanes_per_row(3.0 * nOld / std::max(nNew, 1)), col_lpr = lanes_per_row(3.0 * nNew / std::max(nOld, 1));
-    if (B == 1) {
-        if (a.rfill == a.roff + nNew + 1 && a.coff == a.rfill + nNew && a.cfill == a.coff + nOld + 1 && a.long_flag == a.cfill + nOld) {
-            MSM_HIP(hipMemsetAsync(a.roff, 0, sizeof(int) * (2 * (size_t)nNew + 2 * (size_t)nOld + 4), ctx->stream));  // one block (adaptive_weights_dev)
-        } else {
-            MSM_HIP(hipMemsetAsync(a.roff, 0, sizeof(int) * ((size_t)nNew + 1), ctx->stream));
-            MSM_HIP(hipMemsetAsync(a.rfill, 0, sizeof(int) * (size_t)nNew, ctx->stream));
-            MSM_HIP(hipMemsetAsync(a.coff, 0, sizeof(int) * ((size_t)nOld + 1), ctx->stream));
-            MSM_HIP(hipMemsetAsync(a.cfill, 0, sizeof(int) * (size_t)nOld, ctx->stream));
-            MSM_HIP(hipMemsetAsync(a.long_flag, 0, sizeof(int) * 2, ctx->stream));
-        }
-    } else {  // the problems' arrays lie one after the other
-        MSM_HIP(hipMemsetAsync(a.roff, 0, sizeof(int) * a.s_roff * B, ctx->stream));
-        MSM_HIP(hipMemsetAsync(a.rfill, 0, sizeof(int) * a.s_rfill * B, ctx->stream));
-        MSM_HIP(hipMemsetAsync(a.coff, 0, sizeof(int) * a.s_coff * B, ctx->stream));
-        MSM_HIP(hipMemsetAsync(a.cfill, 0, sizeof(int) * a.s_cfill * B, ctx->stream));
-        MSM_HIP(hipMemsetAsync(a.long_flag, 0, sizeof(int) * 2 * (size_t)B, ctx->stream));
-    }
+    // roff | rfill | coff | cfill | long_flag of the B problems
+    MSM_HIP(hipMemsetAsync(a.roff, 0, sizeof(int) * (size_t)B * (2 * (size_t)nNew + 2 * (size_t)nOld + 4), ctx->stream));
     MSM_LAUNCH2D(k_rev_count, nOld, B, a);
     scan_excl(ctx, a.roff, nNew, a.scan_tmp, B, a.s_roff, a.s_scan);
     MSM_LAUNCH2D(k_rev_fill, nOld, B, a);

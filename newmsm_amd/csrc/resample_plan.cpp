@@ -1,5 +1,5 @@
 // resample_plan.cpp -- msm_resample_plan_*: the rows of one (in_mesh -> new_mesh) resampling built once, kept in HBM and applied to any number of maps.
-// The rows come from the paths the library already has (adaptive_weights_dev / adaptive_weights, launch_query, launch_closest_vertex: api.cpp,
+// The rows come from the paths the library already has (adaptive_weights_dev / adaptive_weights, launch_query, launch_closest_vertex: resample.cpp,
 // kernels.hip); what is new is the ownership (a snapshot: nothing here points back into a mesh or into context scratch) and the apply
 // (resample_plan_kernels.hip).  Host arrays travel in slabs through the context's pinned staging blocks (stager.cpp): the device never holds more than
 // the slab budget of maps, whatever D is.
@@ -10,14 +10,10 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "resample.hpp"
 #include "resample_plan.hpp"
 
 using namespace msm;
-
-namespace msm {
-int adaptive_weights(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *excl, std::vector<int32_t> &row_ptr, std::vector<int32_t> &col,
-                     std::vector<double> &val);  // api.cpp
-}
 
 struct msm_resample_plan {
     msm_ctx *ctx = nullptr;
@@ -55,25 +51,6 @@ int64_t slab_maps(const msm_resample_plan *p, size_t es, int64_t D) {
     return s;
 }
 
-// a std::map<int, double> holding the three weights of one query: ascending key, later writes win (R/resampler.cpp:150-166 read at :296-297)
-int sorted_triple(const int *vid, const double *w, size_t stride, size_t k, int32_t key[3], double wt[3]) {
-    int n = 0;
-    for (int j = 0; j < 3; ++j) {
-        const int32_t id = vid[j * stride + k];
-        const double x = w[j * stride + k];
-        int pos = 0;
-        while (pos < n && key[pos] < id) ++pos;
-        if (pos < n && key[pos] == id) {
-            wt[pos] = x;
-            continue;
-        }
-        for (int s = n; s > pos; --s) key[s] = key[s - 1], wt[s] = wt[s - 1];
-        key[pos] = id, wt[pos] = x;
-        ++n;
-    }
-    return n;
-}
-
 int upload_rows(msm_resample_plan *p, const std::vector<int32_t> &rp, const std::vector<int32_t> &c, const std::vector<double> &v) {
     msm_ctx *ctx = p->ctx;
     p->nnz = (int64_t)c.size();
@@ -98,11 +75,9 @@ int build(msm_resample_plan *p, msm_mesh *in_mesh, msm_mesh *new_mesh, const dou
         // searches and list surgery on the device; the rows leave the context's scratch with three device-to-device copies
         AdaptiveDev w;
         MSM_TRY(adaptive_weights_dev(in_mesh, new_mesh, w));
-        rp.resize((size_t)nNew + 1);
-        MSM_TRY(stage_d2h(ctx, rp.data(), w.row_ptr, sizeof(int32_t) * rp.size()));
-        MSM_TRY(ctx_sync(ctx));
-        p->nnz = rp.back();
-        const size_t nnz = (size_t)p->nnz;
+        size_t nnz = 0;
+        MSM_TRY(fetch_row_ptr(ctx, w, rp, nnz));
+        p->nnz = (int64_t)nnz;
         if (p->row_ptr.ensure(rp.size(), true) || p->col.ensure(std::max<size_t>(nnz, 1), true) || p->val.ensure(std::max<size_t>(nnz, 1), true))
             return stage_alloc_failed(12 * nnz);
         MSM_HIP(hipMemcpyAsync(p->row_ptr.p, w.row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToDevice, ctx->stream));
@@ -129,12 +104,10 @@ int build(msm_resample_plan *p, msm_mesh *in_mesh, msm_mesh *new_mesh, const dou
             MSM_TRY(dw.download(w.data(), w.size(), ctx));
             MSM_TRY(check_status(ctx, "msm_resample_plan_create (barycentric)"));
             for (int k = 0; k < nNew; ++k) {
-                int32_t key[3];
-                double wt[3];
-                const int n = sorted_triple(vid.data(), w.data(), (size_t)nNew, (size_t)k, key, wt);
+                WeightEntry e[3];  // R/resampler.cpp:150-166 read at :296-297
+                const int n = small_map(vid.data(), w.data(), nNew, k, e);
                 rp[(size_t)k] = (int32_t)c.size();
-                c.insert(c.end(), key, key + n);
-                v.insert(v.end(), wt, wt + n);
+                for (int j = 0; j < n; ++j) c.push_back(e[j].key), v.push_back(e[j].w);
             }
         } else {
             DevBuf<int> dcv;
@@ -154,12 +127,7 @@ int build(msm_resample_plan *p, msm_mesh *in_mesh, msm_mesh *new_mesh, const dou
         p->masked = true;
         MSM_TRY(p->excl.upload(excl, (size_t)nOld, ctx));
         p->excl_out.assign((size_t)nNew, 0.0);
-        for (int k = 0; k < nNew; ++k) {  // barycentric_data_interpolation on the mask itself, R/resampler.cpp:54-67
-            double acc = 0.0;
-            for (int e = rp[(size_t)k]; e < rp[(size_t)k + 1]; ++e)
-                if (c[(size_t)e] >= 0 && excl[c[(size_t)e]] != 0) acc += excl[c[(size_t)e]] * v[(size_t)e];
-            p->excl_out[(size_t)k] = acc;
-        }
+        resampled_mask(rp, c, v, excl, p->excl_out.data());
     }
     return ctx_sync(ctx);
 }

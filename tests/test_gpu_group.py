@@ -21,7 +21,8 @@ def folded(xyz, scale=20.0, seed=5):
     return x / np.linalg.norm(x, axis=1, keepdims=True) * 100.0
 
 
-def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile=0.75, subject_orders=None, label_order_offset=2, fold=()):
+def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile=0.75, subject_orders=None, label_order_offset=2, fold=(), who=None):
+    who = list(range(S)) if who is None else who  # the synthetic subject in each slot
     dxyz, dtri = M.make_mesh_from_icosa(data_order)
     cxyz, ctri = M.make_mesh_from_icosa(cp_order)
     txyz, ttri = dxyz, dtri  # template space = a regular sphere at data resolution
@@ -38,13 +39,13 @@ def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile
     og.set_controlgrid(O.Mesh(cxyz, ctri))
     keep = [tm, otm]
     txyz0, ttri0 = dxyz, dtri
-    for s in range(S):
+    for s, i in enumerate(who):
         if subject_orders is not None:  # subjects on data meshes of their own (different sizes: the set-up's scratch meshes follow)
-            dxyz, dtri = (txyz0, ttri0) if subject_orders[s] == data_order else M.make_mesh_from_icosa(subject_orders[s])
-        sph = synthetic.known_warp(dxyz, seed=40 + s, rot_deg=1.0 + s, amp=0.5)   # this subject's registered sphere so far
-        if s in fold:
+            dxyz, dtri = (txyz0, ttri0) if subject_orders[i] == data_order else M.make_mesh_from_icosa(subject_orders[i])
+        sph = synthetic.known_warp(dxyz, seed=40 + i, rot_deg=1.0 + i, amp=0.5)   # this subject's registered sphere so far
+        if i in fold:
             sph = folded(sph)
-        feat = synthetic.features(synthetic.known_warp(dxyz, seed=90 + s, rot_deg=2.0, amp=1.0), D, seed=5)
+        feat = synthetic.features(synthetic.known_warp(dxyz, seed=90 + i, rot_deg=2.0, amp=1.0), D, seed=5)
         regular = M.Mesh(ctx, dxyz, dtri)
         g.reset_meshspace(s, regular, feat)        # first call: _ORIG_MESHES = the regular sphere
         regular.set_coords(sph)
@@ -53,7 +54,7 @@ def build(ctx, S=3, data_order=4, cp_order=2, D=2, mask=False, sim=2, percentile
         og.set_subject(s, om, feat)
         om.set_coords(sph)
         og.set_subject(s, om, feat)
-        cp_s = synthetic.known_warp(cxyz, seed=40 + s, rot_deg=1.0 + s, amp=0.5)
+        cp_s = synthetic.known_warp(cxyz, seed=40 + i, rot_deg=1.0 + i, amp=0.5)
         g.reset_CPgrid(s, cp_s)
         og.reset_cpgrid(s, cp_s)
         keep += [regular, om]
@@ -113,6 +114,26 @@ def test_group_subjects_on_different_data_meshes(ctx, fold):
     got, want = g.computePairwiseCost(p, la, lb), np.array([og.pairwise(*q) for q in zip(p, la, lb)])
     both = np.isnan(want) & np.isnan(got)
     assert np.allclose(got[~both], want[~both], rtol=RTOL, atol=ATOL)
+
+
+def test_group_setup_does_not_depend_on_the_order_of_differently_sized_subjects(ctx):
+    """Two subjects on data meshes of different sizes (ico3 and ico2; template ico2, control grid ico1) share the set-up's batch scratch: set up
+    as (A, B) it grows for A and serves B oversized, as (B, A) it grows twice.  Either way a subject's resampled features and patch lists are the
+    same bits, and they are the oracle's (whose group takes a mesh per subject)."""
+    kw = dict(S=2, data_order=2, cp_order=1, D=2, subject_orders=[3, 2])
+    g1, og1, keep1 = build(ctx, **kw)
+    g2, og2, keep2 = build(ctx, who=[1, 0], **kw)
+    assert g1.L == g2.L
+    for i in range(2):
+        (F1, pp1, pi1), (F2, pp2, pi2) = g1.export_subject(i), g2.export_subject(1 - i)
+        assert np.array_equal(F1.view(np.uint64), F2.view(np.uint64)) and np.array_equal(pp1, pp2) and np.array_equal(pi1, pi2)
+    rng = np.random.default_rng(5)
+    for g, og in ((g1, og1), (g2, og2)):
+        for s, v, l in zip(rng.integers(0, 2, 30), rng.integers(0, 42, 30), rng.integers(0, g.L, 30)):
+            ids, data = g.patch(s, v, l)
+            oids, odata = og.patch(s, v, l)
+            assert np.array_equal(ids, oids)
+            assert np.allclose(data, odata, rtol=1e-10, atol=1e-11)
 
 
 @pytest.mark.parametrize("lanes", [None, 16, 32])

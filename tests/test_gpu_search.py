@@ -182,6 +182,28 @@ def test_adaptive_weights_long_lists_bit_exact(ctx, oin, onew):
     assert np.array_equal(M.metric_resample(min_, data, mnew), O.metric_resample(O.Mesh(xin, tin), data, O.Mesh(xnew, tnew)))
 
 
+def test_adaptive_weights_reuse_one_scratch_across_sizes(built):
+    """One context, so one scratch of the device surgery, through pairs whose sizes go up and down: ico3 -> ico1 (long transposed lists, large
+    nOld), ico1 -> ico3 (the scratch now larger than needed in one dimension and grown in the other), warped ico2 -> ico2; then all three again
+    with every buffer oversized.  The arrays' strides and the counters' layout come from the sizes of the call, not from what the buffers hold:
+    every result has the oracle's CSR and bits."""
+    own, cases = M.Context(0), []  # (a scratch that has seen nothing larger)
+    try:
+        for oin, onew in [(3, 1), (1, 3), (2, 2)]:
+            xin, tin = M.make_mesh_from_icosa(oin)
+            xnew, tnew = M.make_mesh_from_icosa(onew)
+            xin = synthetic.known_warp(xin, seed=21, rot_deg=5.0, amp=1.0)
+            cases.append((M.Mesh(own, xin, tin), M.Mesh(own, xnew, tnew), O.adaptive_barycentric_weights(O.Mesh(xin, tin), O.Mesh(xnew, tnew))))
+        for _ in range(2):
+            for min_, mnew, (orp, ocol, oval) in cases:
+                rp, col, val = M.get_adaptive_barycentric_weights(min_, mnew)
+                assert np.array_equal(rp, orp) and np.array_equal(col, ocol) and np.array_equal(val.view(np.uint64), oval.view(np.uint64))
+    finally:
+        for min_, mnew, _ in cases:
+            min_.close(), mnew.close()
+        own.close()
+
+
 def test_adaptive_weights_with_exclusion(ctx):
     xin, tin = M.make_mesh_from_icosa(4)
     xnew, tnew = M.make_mesh_from_icosa(3)
