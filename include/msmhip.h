@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 12  /* 12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 12  /* 12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -428,13 +428,17 @@ int msm_cost_counters(msm_cost *c, int64_t counters[4]);
  * device).  routes[MSM_ROUTE_UNARY]: the reduction kernel of the last unary table; routes[MSM_ROUTE_MOVE]: the route of the last triclique label step
  * (msm_cost_triplet_octets, or the single-combination move of msm_cost_total); routes[MSM_ROUTE_MOVE_NBLK / _CAP / _MAXTRI]: workgroups of the fused
  * move, bin slots one of them holds at most, and the largest number of control triangles in one (0 until a fused move has run);
- * routes[MSM_ROUTE_MOVE_TAILS]: moves that needed the tail kernel since creation (saturating).  routes[6], routes[7]: 0 (reserved). */
+ * routes[MSM_ROUTE_MOVE_TAILS]: moves that needed the tail kernel since creation (saturating); routes[MSM_ROUTE_MOVE_DEFERRED]: evaluations (of the
+ * move's 8 x T, or T in msm_cost_total) that the last fused move handed to the tail kernel, 0 when it launched none -- read back (four bytes) behind the
+ * tail kernel only, so a move that needs no tail pays nothing; samples settled by the leaf search inside the main kernel are not counted.  routes[7]: 0
+ * (reserved). */
 #define MSM_ROUTE_UNARY 0
 #define MSM_ROUTE_MOVE 1
 #define MSM_ROUTE_MOVE_NBLK 2
 #define MSM_ROUTE_MOVE_CAP 3
 #define MSM_ROUTE_MOVE_MAXTRI 4
 #define MSM_ROUTE_MOVE_TAILS 5
+#define MSM_ROUTE_MOVE_DEFERRED 6
 #define MSM_UNARY_NONE 0        /* no unary table yet (the triclique classes' table is all zeros: no kernel) */
 #define MSM_UNARY_UNIVARIATE 1  /* k_unary_reduce_univariate (DICE measures of the univariate class) */
 #define MSM_UNARY_FLAT 2        /* k_unary_reduce_flat */

@@ -909,10 +909,11 @@ class DiscreteCostFunction:
         """msm_cost_routes: which kernels this cost function ran, as the launchers recorded them.  unary: the reduction kernel of the last unary
         table (UNARY_ROUTES); move: the route of the last triclique label step (MOVE_ROUTES: fusedM = k_ho_move<., M>, octets_* = the three-kernel
         path with that sampling kernel, octets_ho = k_triplet_octets_ho); move_nblk / move_cap / move_maxtri: workgroups of the fused move, bin slots
-        and control triangles one of them holds at most; move_tails: moves that needed the tail kernel, since creation."""
+        and control triangles one of them holds at most; move_tails: moves that needed the tail kernel, since creation; move_deferred: evaluations the last fused
+        move handed to the tail kernel (0 when it launched none)."""
         r = (C.c_int32 * 8)()
         check(lib().msm_cost_routes(self.h, r))
-        return dict(unary=self.UNARY_ROUTES[r[0]], move=self.MOVE_ROUTES[r[1]], move_nblk=r[2], move_cap=r[3], move_maxtri=r[4], move_tails=r[5])
+        return dict(unary=self.UNARY_ROUTES[r[0]], move=self.MOVE_ROUTES[r[1]], move_nblk=r[2], move_cap=r[3], move_maxtri=r[4], move_tails=r[5], move_deferred=r[6])
 
 
 # ------------------------------------------------------------------ groupwise (gMSM)

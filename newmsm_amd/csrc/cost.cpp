@@ -676,6 +676,7 @@ int msm_cost_routes(msm_cost *c, int32_t routes[8]) {
     routes[MSM_ROUTE_MOVE_CAP] = c->move_cap;
     routes[MSM_ROUTE_MOVE_MAXTRI] = c->move_maxtri;
     routes[MSM_ROUTE_MOVE_TAILS] = (int32_t)std::min<int64_t>(c->move_tails, INT32_MAX);
+    routes[MSM_ROUTE_MOVE_DEFERRED] = c->move_deferred;
     return MSM_OK;
 }
 

@@ -406,6 +406,7 @@ static int fused_move_finish(msm_cost *c, const CliqueArgs &a, const MoveArgs &m
     msm_ctx *ctx = c->ctx;
     int st;
     volatile int *flags = ctx->h_flag;
+    c->move_deferred = 0;
     if (flags[1] != 0) {  // rare: some evaluations need the complete search (sibling leaves, nearest vertex)
         flags[1] = 0;
         st = launch_move_tail(ctx, a, m, lab);
@@ -413,6 +414,10 @@ static int fused_move_finish(msm_cost *c, const CliqueArgs &a, const MoveArgs &m
         if (staged_copy) MSM_HIP(hipMemcpyAsync((char *)pin + in_pad, out_dev, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
         MSM_TRY(ctx_sync(ctx));
         c->move_tails++;
+        unsigned listed = 0;  // how many evaluations the tail kernel took (msm_cost_routes): this move's counter stays until the next move but one clears it
+        MSM_TRY(stage_d2h(ctx, &listed, m.defer_cnt + m.parity, sizeof listed));
+        MSM_TRY(ctx_sync(ctx));
+        c->move_deferred = (int32_t)std::min<unsigned>(listed, (unsigned)INT32_MAX);
     }
     st = MSM_OK;
     if (flags[0] != 0) {

@@ -44,6 +44,7 @@ struct msm_cost {
     DevBuf<int4> d_blk;
     DevBuf<double> d_slot_w, d_slot_sf, d_slot_cw, d_slot_wda, d_tri_frame, d_tri_stat;
     int64_t move_tails = 0;  // moves that needed the tail kernel
+    int32_t move_deferred = 0;  // evaluations the last fused move handed to the tail kernel (0: it launched none)
     // msm_cost_triplet_octets_prefetch: a label step queued ahead of its msm_cost_triplet_octets call (the optimiser's host-side solve of the previous
     // step runs meanwhile); taken by the call that asks for exactly this (labeling, label, E), dropped by any other entry point of this cost function
     struct PendingMove {

@@ -230,15 +230,18 @@ def test_three_kernel_path_at_every_width(ctx, D, rows):
 # ------------------------------------------------------------------ the move's tail kernel
 def test_fused_move_star_shaped_target_d34(ctx):
     """a star-shaped target (vertices moved radially by 3e-3, the shape test_non_spherical_star_shaped_targets uses to defeat leaf
-    membership): one move with 34 rows; where the oracle is finite the result matches.  On this target some open samples find no candidate in
-    their octree leaf, so the move hands their evaluations to k_ho_move_tail: the one test of the suite that runs the tail kernel."""
+    membership): one move with 34 rows, every entry against the oracle (finite everywhere on this input: tests/test_move_fallbacks_cpu.py).  On
+    this target some open samples find no candidate in their octree leaf, so the move hands their evaluations (49 of 10 240, measured) to
+    k_ho_move_tail.  tests/test_gpu_move_fallbacks.py runs the tail kernel on every route."""
     inp = inputs(5, 3, 34, target_radial=3e-3)
     cf, oc, _ = ho(ctx, inp)
     labeling, label = move_labelings(cf, 534)[1]
-    assert cf.routes()["move_tails"] == 0
-    E, want = cf.tripletOctets(labeling, label), oc.triplet_octets(labeling, label, threads=8)
-    both = np.isfinite(want)
-    assert both.mean() > 0.9 and np.isfinite(E[both]).all()
-    assert np.allclose(E[both], want[both], rtol=RTOL, atol=ATOL), np.abs(E[both] - want[both]).max()
     r = cf.routes()
-    assert r["move"] == "fused2" and r["move_tails"] == 1
+    assert r["move_tails"] == 0 and r["move_deferred"] == 0
+    E, want = cf.tripletOctets(labeling, label), oc.triplet_octets(labeling, label, threads=8)
+    assert np.isfinite(want).all() and np.isfinite(E).all()
+    assert close(E, want), np.abs(E - want).max()
+    folded = want >= 1e6 * LAMBDA
+    assert np.array_equal(E >= 1e6 * LAMBDA, folded) and folded.mean() <= MAX_FOLDED
+    r = cf.routes()
+    assert r["move"] == "fused2" and r["move_tails"] == 1 and r["move_deferred"] > 0
