@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 12  /* 12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 12  /* 12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -259,16 +259,32 @@ typedef struct msm_resample_plan msm_resample_plan;
 #define MSM_RESAMPLE_ADAP_BARY   0  /* Resampler::get_adaptive_barycentric_weights, R/resampler.cpp:72-140: metric_resample's rows */
 #define MSM_RESAMPLE_BARYCENTRIC 1  /* get_barycentric_weights :142-167 of new_mesh's vertices on in_mesh, ascending ids: surface_resample's rows (:284-302) */
 #define MSM_RESAMPLE_NEAREST     2  /* nearest_neighbour_interpolation :232-258: one entry of weight 1 per row */
+#define MSM_RESAMPLE_SMOOTH      3  /* smooth_data R/resampler.cpp:168-230: only through msm_resample_plan_create_smooth */
 #define MSM_F64 0
 #define MSM_F32 1
 /* excl: V(in_mesh) values (the EXCL mesh's data, 0 = excluded) or NULL.  NULL on failure (msm_last_error): meshes of different contexts, an unknown
  * method, a failed search (MSM_ERR_OUTSIDE / MSM_ERR_NOTFOUND, as msm_metric_resample fails). */
 msm_resample_plan *msm_resample_plan_create(msm_mesh *in_mesh, msm_mesh *new_mesh, int method, const double *excl);
+/* Gaussian smoothing (msm_smooth_data above, with its arguments and its indexing) as a plan: the neighbourhood sweep runs once, on the device, and the
+ * rows stay in HBM.  V_in = V(orig), V_out = V(sphlow).  Row i: c = the vertex of orig closest to sphlow's vertex i; the entries are the vertices n of
+ * sphlow with (unit[n] | unit[c]) >= cos(4 asin(sigma / 2R)) in ascending n, val = gain * exp(-(g * g) / (2 sigma^2)) with
+ * g = 2R asin(|unit[c] - unit[n]| / 2R), gain = 1 / sqrt(2 pi sigma^2), multiplied by excl[n] when excl (V(orig) values) is given: the mask is part of
+ * the stored weights, an apply skips nothing.  Per row, summed in stored order from 0.0: the divisor SUM of the stored weights, and with a mask
+ * excl_out = SUM / (the sum of the unmasked weights), 0 where that is 0.  A centre with excl[c] <= 0 gives an empty row, divisor 0, excl_out 0.
+ * An apply sums acc += (double)data[d][col] * val in stored order as every plan does and then, where the row's divisor is not 0.0, stores
+ * acc / divisor (one FP64 division): msm_smooth_data's arithmetic -- an MSM_F64 apply gives its bits, a NaN that meets a zero weight included.
+ * msm_resample_plan_apply hands out excl_out for a plan with excl; msm_resample_plan_apply_labels refuses a smoothing plan (MSM_ERR_INVALID).
+ * NULL on failure: sigma <= 0, V(orig) < V(sphlow), meshes of different contexts, more than INT32_MAX entries (a large sigma on ico7).
+ * msm_resample_plan_create refuses MSM_RESAMPLE_SMOOTH as an unknown method: it has no sigma. */
+msm_resample_plan *msm_resample_plan_create_smooth(msm_mesh *orig, msm_mesh *sphlow, double sigma, const double *excl);
 void msm_resample_plan_destroy(msm_resample_plan *p);
 /* [host] any pointer may be NULL */
 int  msm_resample_plan_sizes(const msm_resample_plan *p, int32_t *V_in, int32_t *V_out, int64_t *nnz, int32_t *longest_row);
 /* the rows as CSR (row_ptr: V_out + 1; col / val: nnz entries, cap = their capacity; any of the three may be NULL), read back from the device */
 int  msm_resample_plan_weights(msm_resample_plan *p, int32_t *row_ptr, int32_t *col, double *val, int64_t cap);
+/* div: V_out values, the divisor of every row.  0.0 means "not divided": every row of the three resampling methods, and the rows of a smoothing plan
+ * whose weights sum to 0 */
+int  msm_resample_plan_divisors(msm_resample_plan *p, double *div);
 /* data: D x V_in host array of dtype (MSM_F64: double, MSM_F32: float); out: D x V_out of the same type.  excl_out (optional, V_out): the resampled
  * mask of a plan with excl (:54-67; NEAREST: the mask at the closest vertex, :244-249), zeros for a plan without.  The maps travel through the context's
  * pinned staging blocks in slabs of a fixed device budget (64 MiB of maps; MSMHIP_PLAN_CHUNK_KB overrides), whatever D is.  D == 0: nothing is done. */

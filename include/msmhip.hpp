@@ -239,7 +239,13 @@ public:
         if (!h_) throw Error(MSM_ERR_INVALID, msm_last_error());
         check(msm_resample_plan_sizes(h_, &V_in_, &V_out_, &nnz_, &longest_));
     }
+    // smooth_data(orig, ., sphLow, sigma, excl) (R/resampler.cpp:168-230) as a plan: msm_resample_plan_create_smooth.  The sweep over the neighbourhoods
+    // runs once; apply() then smooths any number of maps (a Matrix apply gives smooth_data's bits) and hands out the smoothed mask when excl was given.
+    static ResamplePlan smoothing(Mesh &orig, Mesh &sphLow, double sigma, const std::vector<double> *excl = nullptr) {
+        return ResamplePlan(msm_resample_plan_create_smooth(orig.handle(), sphLow.handle(), sigma, excl ? excl->data() : nullptr), excl != nullptr);
+    }
     ~ResamplePlan() { msm_resample_plan_destroy(h_); }
+    ResamplePlan(ResamplePlan &&o) noexcept : h_(o.h_), masked_(o.masked_), V_in_(o.V_in_), V_out_(o.V_out_), longest_(o.longest_), nnz_(o.nnz_) { o.h_ = nullptr; }
     ResamplePlan(const ResamplePlan &) = delete;
     ResamplePlan &operator=(const ResamplePlan &) = delete;
     int nvertices_in() const { return V_in_; }
@@ -253,6 +259,12 @@ public:
         w.val.resize((size_t)nnz_);
         check(msm_resample_plan_weights(h_, w.row_ptr.data(), w.col.data(), w.val.data(), nnz_));
         return w;
+    }
+    // what an apply divides each row's sum by; 0.0 = not divided (every row of the resampling methods)
+    std::vector<double> divisors() {
+        std::vector<double> div((size_t)V_out_);
+        check(msm_resample_plan_divisors(h_, div.data()));
+        return div;
     }
     // data: D x V_in, out: D x V_out, both row-major and of one type; excl_out (optional, V_out): the resampled mask of a plan with excl
     void apply(const double *data, int64_t D, double *out, double *excl_out = nullptr) { check(msm_resample_plan_apply(h_, data, MSM_F64, D, out, excl_out)); }
@@ -283,6 +295,10 @@ public:
     msm_resample_plan *handle() const { return h_; }
 
 private:
+    ResamplePlan(msm_resample_plan *h, bool masked) : h_(h), masked_(masked) {
+        if (!h_) throw Error(MSM_ERR_INVALID, msm_last_error());
+        check(msm_resample_plan_sizes(h_, &V_in_, &V_out_, &nnz_, &longest_));
+    }
     msm_resample_plan *h_;
     bool masked_;
     int32_t V_in_ = 0, V_out_ = 0, longest_ = 0;

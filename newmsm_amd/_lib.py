@@ -90,6 +90,8 @@ SIGNATURES = {
     "msm_metric_resample": (C.c_int, [_VP, c_dp, C.c_int32, _VP, c_dp, c_dp, c_dp]),
     "msm_create_exclusion": (C.c_int, [c_dp, C.c_int32, C.c_int32, C.c_double, C.c_double, c_dp]),
     "msm_resample_plan_create": (_VP, [_VP, _VP, C.c_int, c_dp]),
+    "msm_resample_plan_create_smooth": (_VP, [_VP, _VP, C.c_double, c_dp]),
+    "msm_resample_plan_divisors": (C.c_int, [_VP, c_dp]),
     "msm_resample_plan_destroy": (None, [_VP]),
     "msm_resample_plan_sizes": (C.c_int, [_VP, c_ip, c_ip, c_lp, c_ip]),
     "msm_resample_plan_weights": (C.c_int, [_VP, c_ip, c_ip, c_dp, C.c_int64]),

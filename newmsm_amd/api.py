@@ -395,7 +395,8 @@ PLAN_TILE = 64  # maps per tile of an apply (kPlanTile, csrc/resample_plan.hpp):
 class ResamplePlan:
     """msm_resample_plan: the rows of one (in_mesh -> new_mesh) resampling built once and applied to any number of maps.  A snapshot: later calls on the
     context, set_coords on either mesh or closing either mesh do not change what it does.  method: adap_bary (metric_resample's rows), barycentric
-    (surface_resample's) or nearest; excl: the EXCL mesh's values on in_mesh (0 = excluded) or None."""
+    (surface_resample's) or nearest; excl: the EXCL mesh's values on in_mesh (0 = excluded) or None.  ResamplePlan.smoothing(...) makes the fourth kind:
+    smooth_data's Gaussian rows."""
 
     def __init__(self, in_mesh, new_mesh, method="adap_bary", excl=None):
         if method not in RESAMPLE_METHODS:
@@ -413,6 +414,27 @@ class ResamplePlan:
         if not self.h:
             raise MsmError(-1, lib().msm_last_error().decode())
         self.V_in, self.V_out, self.nnz, self.longest_row = self.sizes()
+
+    @classmethod
+    def smoothing(cls, orig_mesh, sph_low, sigma, excl=None):
+        """msm_resample_plan_create_smooth: smooth_data(orig_mesh, ., sph_low, sigma, excl) as a plan -- the neighbourhood sweep runs once, apply then
+        smooths any number of float32 / float64 maps and returns (out, smoothed mask) when excl was given.  A float64 apply gives smooth_data's bits."""
+        self = cls.__new__(cls)
+        self.ctx = orig_mesh.ctx
+        self.method = "smoothing"
+        self.masked = excl is not None
+        self.h = None
+        if self.masked:
+            e, pe = _d(np.asarray(excl).reshape(-1))
+            if e.shape[0] != orig_mesh.V:
+                raise ValueError("excl has %d values, the mesh %d vertices" % (e.shape[0], orig_mesh.V))
+        else:
+            pe = None
+        self.h = lib().msm_resample_plan_create_smooth(orig_mesh.h, sph_low.h, float(sigma), pe)
+        if not self.h:
+            raise MsmError(-1, lib().msm_last_error().decode())
+        self.V_in, self.V_out, self.nnz, self.longest_row = self.sizes()
+        return self
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -435,6 +457,12 @@ class ResamplePlan:
         val = np.zeros(self.nnz)
         check(lib().msm_resample_plan_weights(self.h, rp.ctypes.data_as(c_ip), col.ctypes.data_as(c_ip), val.ctypes.data_as(c_dp), self.nnz))
         return rp, col, val
+
+    def divisors(self):
+        """V_out values: what an apply divides each row's sum by; 0.0 = not divided (every row of the resampling methods)"""
+        div = np.zeros(self.V_out)
+        check(lib().msm_resample_plan_divisors(self.h, div.ctypes.data_as(c_dp)))
+        return div
 
     def apply(self, data, out=None):
         """D x V_in float32 or float64 -> D x V_out of the same dtype; (out, resampled mask) when the plan has a mask"""
@@ -479,6 +507,8 @@ class ResamplePlan:
 
     def apply_labels(self, labels, unassigned=0):
         """D x V_in integer keys -> D x V_out int32 by the largest-summed-weight vote (msmhip.h); rows without kept entries get `unassigned`"""
+        if self.method == "smoothing":
+            raise ValueError("a smoothing plan takes no labels")
         l = np.asarray(labels)
         if not np.issubdtype(l.dtype, np.integer):
             raise TypeError("ResamplePlan.apply_labels takes integer keys, not %s" % l.dtype)

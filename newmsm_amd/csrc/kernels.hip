@@ -9,6 +9,7 @@
 
 #include "kernels.hpp"
 #include "search_device.hpp"
+#include "smooth_device.hpp"
 
 namespace msm {
 
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(256) void k_smooth(const double *__restrict__ unit,
     for (int d = lane; d < D; d += 64) out[(size_t)d * N + i] = 0.0;
     if (excl && !(excl[c] > 0)) return;  // :200: excluded centre: data stays 0
     const V3 ref = mk(unit[c], unit[N + c], unit[2 * N + c]);
-    const double gain = 1 / sqrt(2 * M_PI * sigma * sigma);
+    const double gain = smooth_gain(sigma);
     double SUM = 0.0, excl_sum = 0.0;
     double acc = 0.0;  // lane d < D accumulates feature d (more than 64 features: extra passes below)
     int count = 0;     // members in the LDS list (wavefront-uniform)
@@ -477,8 +478,7 @@ __global__ __launch_bounds__(256) void k_smooth(const double *__restrict__ unit,
     for (int c0 = 0; c0 < nchunks; c0 += 64) {
         bool cand = false;
         if (c0 + lane < nchunks) {
-            const double4 b = cb[c0 + lane];
-            cand = !(b.x * ref.x + b.y * ref.y + b.z * ref.z + b.w < cosang);
+            cand = smooth_chunk_candidate(cb[c0 + lane], ref, cosang);
         }
         unsigned long long todo = __ballot(cand);
         while (todo) {
@@ -489,18 +489,17 @@ __global__ __launch_bounds__(256) void k_smooth(const double *__restrict__ unit,
             double chord = 0.0;
             if (n < N) {
                 const V3 a = mk(unit[n], unit[N + n], unit[2 * N + n]);
-                in = dot(a, ref) >= cosang;
-                if (in) chord = norm(sub(ref, a));
+                in = smooth_member(a, ref, cosang);
+                if (in) chord = smooth_chord(ref, a);
             }
             const unsigned long long bal = __ballot(in);
             if (!bal) continue;
             const int add = __popcll(bal);
             if (count + add > kSmoothList) flush();
             if (in) {
-                const double g = 2 * kRad * asin(chord / (2 * kRad));
                 const int at = count + __popcll(bal & ((1ull << lane) - 1ull));
                 ln[at] = n;
-                lw[at] = gain * exp(-(g * g) / (2 * sigma * sigma));
+                lw[at] = smooth_weight(chord, gain, sigma);
             }
             count += add;
         }
@@ -514,8 +513,7 @@ __global__ __launch_bounds__(256) void k_smooth(const double *__restrict__ unit,
     }
 }
 
-int launch_smooth(msm_ctx *ctx, const double *d_xyz, int N, double *d_unit, const int *d_cv, const double *d_data, int Vorig, int D, double sigma,
-                  double cosang, const double *d_excl, double *d_out, double *d_excl_out) {
+int launch_smooth_prepare(msm_ctx *ctx, const double *d_xyz, int N, double *d_unit) {
     if (N <= 0) return MSM_OK;
     hipLaunchKernelGGL(k_unit_vectors, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, d_xyz, N, d_unit);
     MSM_HIP(hipGetLastError());
@@ -523,6 +521,14 @@ int launch_smooth(msm_ctx *ctx, const double *d_xyz, int N, double *d_unit, cons
     double4 *cb = reinterpret_cast<double4 *>(d_unit + smooth_bounds_offset(N));
     hipLaunchKernelGGL(k_chunk_bounds, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, d_unit, N, cb);
     MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_smooth(msm_ctx *ctx, const double *d_xyz, int N, double *d_unit, const int *d_cv, const double *d_data, int Vorig, int D, double sigma,
+                  double cosang, const double *d_excl, double *d_out, double *d_excl_out) {
+    if (N <= 0) return MSM_OK;
+    MSM_TRY(launch_smooth_prepare(ctx, d_xyz, N, d_unit));
+    const double4 *cb = reinterpret_cast<const double4 *>(d_unit + smooth_bounds_offset(N));
     hipLaunchKernelGGL(k_smooth, dim3((N + 3) / 4), dim3(256), 0, ctx->stream, d_unit, N, d_cv, d_data, Vorig, D, sigma, cosang, d_excl, d_out,
                        d_excl_out, cb, ctx->d_status);
     MSM_HIP(hipGetLastError());

@@ -28,6 +28,8 @@ int query_lanes(long long N);  // lanes per query of the search kernels for a la
 // d_unit of launch_smooth holds smooth_scratch_doubles(N) doubles: the unit vectors and, from smooth_bounds_offset(N), a bounding ball per 64 of them
 inline size_t smooth_bounds_offset(int N) { return ((size_t)3 * N + 3) / 4 * 4; }
 inline size_t smooth_scratch_doubles(int N) { return smooth_bounds_offset(N) + 4 * (((size_t)N + 63) / 64) + 4; }
+// the first two steps alone (k_unit_vectors, k_chunk_bounds): what launch_smooth and the row builder of a smoothing plan (smooth_plan_kernels.hip) sweep
+int launch_smooth_prepare(msm_ctx *ctx, const double *d_xyz, int N, double *d_unit);
 int launch_smooth(msm_ctx *ctx, const double *d_xyz, int N, double *d_unit, const int *d_cv, const double *d_data, int Vorig, int D, double sigma,
                   double cosang, const double *d_excl, double *d_out, double *d_excl_out);
 // check_for_intersections (M/reg_tools.cpp:118-129) of every vertex: fold[0] += folded, fold[1] += vertices without a triangle, fold[2 + v] = folded

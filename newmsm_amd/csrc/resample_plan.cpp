@@ -3,7 +3,11 @@
 // kernels.hip); what is new is the ownership (a snapshot: nothing here points back into a mesh or into context scratch) and the apply
 // (resample_plan_kernels.hip).  Host arrays travel in slabs through the context's pinned staging blocks (stager.cpp): the device never holds more than
 // the slab budget of maps, whatever D is.
+// A smoothing plan (msm_resample_plan_create_smooth) is the fourth kind of row: smooth_data's neighbourhoods, built on the device and never seen by the
+// host (smooth_plan_kernels.hip), with a divisor per row that the apply divides by.
 #include <algorithm>
+#include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -22,13 +26,15 @@ struct msm_resample_plan {
     bool masked = false;
     DevBuf<int32_t> row_ptr, col;   // nNew + 1, nnz
     DevBuf<double> val, excl;       // nnz, nOld (masked plans)
-    std::vector<double> excl_out;   // masked plans: the resampled mask (it depends on the rows and the mask only)
+    DevBuf<double> div;             // nNew (smoothing plans): the sum of a row's weights, 0.0 where the row is not divided
+    std::vector<double> excl_out;   // masked plans: the resampled / smoothed mask (it depends on the rows and the mask only)
     DevBuf<char> in, out, tin, tout;  // grow-only scratch of the applies: a slab of maps in and out, one tile in vertex-major order in and out
     hipEvent_t ev = nullptr;        // behind a slab's download: its delivery waits for this, not for the stream
 
     PlanRows rows() const {
         PlanRows r;
         r.nOld = nOld, r.nNew = nNew, r.row_ptr = row_ptr.p, r.col = col.p, r.val = val.p, r.excl = masked ? excl.p : nullptr;
+        r.row_div = method == MSM_RESAMPLE_SMOOTH ? div.p : nullptr;
         return r;
     }
 };
@@ -132,6 +138,46 @@ int build(msm_resample_plan *p, msm_mesh *in_mesh, msm_mesh *new_mesh, const dou
     return ctx_sync(ctx);
 }
 
+// The rows of smooth_data(orig, sphlow, sigma, excl), R/resampler.cpp:168-230, with msm_smooth_data's indexing (api.cpp).  The mask is part of the stored
+// weights, so the plan keeps none for its applies (masked stays false) and only hands out the smoothed mask.
+int build_smooth(msm_resample_plan *p, msm_mesh *orig, msm_mesh *sphlow, double sigma, const double *excl) {
+    msm_ctx *ctx = p->ctx;
+    const int N = p->nNew;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    MSM_HIP(hipEventCreateWithFlags(&p->ev, hipEventDisableTiming));
+    MSM_TRY(ensure_tree(orig));
+    DevBuf<int> dcv, dtmp;
+    DevBuf<double> dunit, dexcl, dexo;
+    if (dcv.ensure((size_t)N + 1) || dunit.ensure(smooth_scratch_doubles(N)) || dtmp.ensure((size_t)N / 4096 + 2) || p->row_ptr.ensure((size_t)N + 1, true) ||
+        p->div.ensure(std::max<size_t>((size_t)N, 1), true) || (excl && dexo.ensure(std::max<size_t>((size_t)N, 1))))
+        return stage_alloc_failed(sizeof(double) * smooth_scratch_doubles(N) + 16 * (size_t)N);
+    MSM_TRY(launch_closest_vertex(ctx, dev_tree(orig), sphlow->d_xyz.p, N, dcv.p));  // Octree(orig).get_closest_vertex_ID(ci), :182
+    MSM_TRY(launch_smooth_prepare(ctx, sphlow->d_xyz.p, N, dunit.p));
+    if (excl) MSM_TRY(dexcl.upload(excl, (size_t)p->nOld, ctx));
+    const double ang = 4 * asin(sigma / (2 * kRad));  // :175, with the host's libm like the reference
+    const SmoothRows s{dunit.p, reinterpret_cast<const double4 *>(dunit.p + smooth_bounds_offset(N)), dcv.p, excl ? dexcl.p : nullptr, N, sigma, cos(ang)};
+    MSM_TRY(launch_smooth_plan_count(ctx, s, p->row_ptr.p));
+    // the lengths come down once; their sum is taken in 64 bits before anything is sized by it
+    std::vector<int32_t> len((size_t)N);
+    MSM_TRY(p->row_ptr.download(len.data(), (size_t)N, ctx));
+    MSM_TRY(check_status(ctx, "msm_resample_plan_create_smooth"));
+    int64_t nnz = 0;
+    for (int32_t l : len) nnz += l, p->longest = std::max(p->longest, (int)l);
+    if (nnz > (int64_t)INT32_MAX)
+        return fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: nnz = %lld entries (%d rows, the longest of %d) do not fit the plan's 32-bit row offsets", (long long)nnz,
+                    N, p->longest);
+    p->nnz = nnz;
+    if (p->col.ensure(std::max<size_t>((size_t)nnz, 1), true) || p->val.ensure(std::max<size_t>((size_t)nnz, 1), true)) return stage_alloc_failed(12 * (size_t)nnz);
+    MSM_TRY(launch_scan_exclusive(ctx, p->row_ptr.p, N, dtmp.p));
+    MSM_TRY(launch_smooth_plan_fill(ctx, s, p->row_ptr.p, p->col.p, p->val.p, p->div.p, excl ? dexo.p : nullptr));
+    if (excl) {
+        p->excl_out.assign((size_t)N, 0.0);
+        MSM_TRY(dexo.download(p->excl_out.data(), (size_t)N, ctx));
+    }
+    return check_status(ctx, "msm_resample_plan_create_smooth");
+}
+
 template <typename T>
 int tiles(msm_resample_plan *p, const T *d_data, int64_t D, T *d_out) {
     const PlanRows r = p->rows();
@@ -220,6 +266,44 @@ msm_resample_plan *msm_resample_plan_create(msm_mesh *in_mesh, msm_mesh *new_mes
     return p;
 }
 
+msm_resample_plan *msm_resample_plan_create_smooth(msm_mesh *orig, msm_mesh *sphlow, double sigma, const double *excl) {
+    if (!orig || !sphlow) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: null mesh");
+        return nullptr;
+    }
+    if (orig->ctx != sphlow->ctx) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: the two meshes belong to different contexts");
+        return nullptr;
+    }
+    if (!(sigma > 0)) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: sigma = %g, a positive width is needed", sigma);
+        return nullptr;
+    }
+    // the reference reads orig's data and the exclusion mask with sphLow's vertex ids (R/resampler.cpp:193-210)
+    if (orig->V < sphlow->V) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: the data mesh has %d vertices, the sphere %d", orig->V, sphlow->V);
+        return nullptr;
+    }
+    msm_resample_plan *p = new (std::nothrow) msm_resample_plan();
+    if (!p) {
+        fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: out of memory");
+        return nullptr;
+    }
+    p->ctx = orig->ctx;
+    p->nOld = orig->V, p->nNew = sphlow->V, p->method = MSM_RESAMPLE_SMOOTH;
+    int st;
+    try {
+        st = build_smooth(p, orig, sphlow, sigma, excl);
+    } catch (const std::exception &e) {
+        st = fail(MSM_ERR_INVALID, "msm_resample_plan_create_smooth: %s", e.what());
+    }
+    if (st) {
+        msm_resample_plan_destroy(p);
+        return nullptr;
+    }
+    return p;
+}
+
 void msm_resample_plan_destroy(msm_resample_plan *p) {
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
@@ -248,10 +332,23 @@ int msm_resample_plan_weights(msm_resample_plan *p, int32_t *row_ptr, int32_t *c
     return ctx_sync(ctx);
 }
 
+int msm_resample_plan_divisors(msm_resample_plan *p, double *div) {
+    if (!p || !div) return fail(MSM_ERR_INVALID, "msm_resample_plan_divisors: null %s", p ? "array" : "plan");
+    if (p->method != MSM_RESAMPLE_SMOOTH) {  // the other methods' rows are not divided
+        std::fill(div, div + p->nNew, 0.0);
+        return MSM_OK;
+    }
+    msm_ctx *ctx = p->ctx;
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    MSM_TRY(p->div.download(div, (size_t)p->nNew, ctx));
+    return ctx_sync(ctx);
+}
+
 int msm_resample_plan_apply(msm_resample_plan *p, const void *data, int dtype, int64_t D, void *out, double *excl_out) {
     MSM_TRY(check_apply(p, data, dtype, D, out, "msm_resample_plan_apply"));
     if (excl_out) {
-        if (p->masked) std::copy(p->excl_out.begin(), p->excl_out.end(), excl_out);
+        if (!p->excl_out.empty()) std::copy(p->excl_out.begin(), p->excl_out.end(), excl_out);
         else std::fill(excl_out, excl_out + p->nNew, 0.0);
     }
     if (D == 0) return MSM_OK;
@@ -274,6 +371,7 @@ int msm_resample_plan_apply_dev(msm_resample_plan *p, const void *data_dev, int 
 int msm_resample_plan_apply_labels(msm_resample_plan *p, const int32_t *labels, int64_t D, int32_t unassigned, int32_t *out) {
     if (!p) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: null plan");
     if (D < 0) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: D = %lld rows", (long long)D);
+    if (p->method == MSM_RESAMPLE_SMOOTH) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: a smoothing plan takes no labels (a Gaussian vote is not defined)");
     if (D > 0 && (!labels || !out)) return fail(MSM_ERR_INVALID, "msm_resample_plan_apply_labels: null array with D = %lld", (long long)D);
     if (D == 0) return MSM_OK;
     msm_ctx *ctx = p->ctx;

@@ -10,7 +10,7 @@
 // The alternative -- a lane group per row with kPlanTile accumulators in registers reading data[(d0 + j) * nOld + col] from the map-major tile -- saves the
 // two transposes and turns every entry into kPlanTile scattered look-ups again.
 // Arithmetic (msmhip.h): acc = 0.0, acc += (double)x * val per kept entry in stored order, product and sum rounded separately (-ffp-contract=off), the
-// result stored as T.  No atomics: two runs give the same bits.
+// result stored as T.  A smoothing plan's rows (smooth_plan_kernels.hip) divide the sum by the row's divisor first.  No atomics: two runs give the same bits.
 #include "resample_plan.hpp"
 
 namespace msm {
@@ -53,8 +53,9 @@ __global__ __launch_bounds__(256) void k_plan_tile_out(const T *__restrict__ src
     }
 }
 
-// one wavefront per output row; tin: nOld x TD, tout: nNew x TD
-template <typename T>
+// one wavefront per output row; tin: nOld x TD, tout: nNew x TD.  Div: a smoothing plan's rows, whose sum is divided by the row's divisor where that is
+// not 0.0 (one FP64 division, k_smooth's; kernels.hip) -- a compile-time variant, so the other methods run the code they ran before there was one
+template <typename T, bool Div>
 __global__ __launch_bounds__(256) void k_plan_rows(PlanRows p, int nd, const T *__restrict__ tin, T *__restrict__ tout) {
     const int lane = threadIdx.x & 63;
     const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -86,6 +87,10 @@ __global__ __launch_bounds__(256) void k_plan_rows(PlanRows p, int nd, const T *
         if (!(c >= 0 && c < p.nOld && (!p.excl || p.excl[c] != 0.0))) continue;
         const double x = live ? (double)tin[(size_t)c * TD + lane] : 0.0;
         acc += x * w;
+    }
+    if constexpr (Div) {
+        const double dv = p.row_div[k];
+        if (dv != 0.0) acc = acc / dv;
     }
     if (live) tout[(size_t)k * TD + lane] = (T)acc;
 }
@@ -140,7 +145,8 @@ int launch_plan_tile(msm_ctx *ctx, const PlanRows &r, const T *d_data, int nd, T
     if (nd <= 0 || r.nNew <= 0) return MSM_OK;
     if (nd > TD) return fail(MSM_ERR_INVALID, "resampling plan: a tile holds %d maps, %d asked for", TD, nd);
     if (r.nOld > 0) hipLaunchKernelGGL(k_plan_tile_in<T>, dim3((unsigned)((r.nOld + TD - 1) / TD)), dim3(256), 0, ctx->stream, d_data, nd, r.nOld, d_tin);
-    hipLaunchKernelGGL(k_plan_rows<T>, dim3((unsigned)((r.nNew + 3) / 4)), dim3(256), 0, ctx->stream, r, nd, (const T *)d_tin, d_tout);
+    if (r.row_div) hipLaunchKernelGGL((k_plan_rows<T, true>), dim3((unsigned)((r.nNew + 3) / 4)), dim3(256), 0, ctx->stream, r, nd, (const T *)d_tin, d_tout);
+    else hipLaunchKernelGGL((k_plan_rows<T, false>), dim3((unsigned)((r.nNew + 3) / 4)), dim3(256), 0, ctx->stream, r, nd, (const T *)d_tin, d_tout);
     hipLaunchKernelGGL(k_plan_tile_out<T>, dim3((unsigned)((r.nNew + TD - 1) / TD)), dim3(256), 0, ctx->stream, (const T *)d_tout, nd, r.nNew, d_out);
     MSM_HIP(hipGetLastError());
     return MSM_OK;

@@ -18,6 +18,9 @@ ADDITIONS to the programs (the three resampling subcommands):
     --method=adap_bary|barycentric|nearest   the plan's rows (default: the program's own)
     --excl_thr=lo,hi      create_exclusion (R/mesh.cpp:1257-1273) on the first input masks the resampling, as save_transformed_data does
                           (M/mesh_registration.cpp:371-383)
+and to `smoothing`: --metric_in may be repeated as well -- all files go through ONE smoothing plan (the neighbourhood sweep runs once; each output gets
+-<stem of its input> before -smoothed_data) -- and --excl_thr masks the smoothing by the first input (smooth_data's EXCL argument).  The files' float32
+values are smoothed with FP64 sums and rounded once, which is what one input without a mask has always given.
 
 After a registration, everything else the subject has follows its sphere.reg in one call:
     python tools/resample_files.py metric-resample --current_sphere=PREFIX.sphere.reg.surf.gii --new_sphere=ref.sphere.surf.gii \\
@@ -57,6 +60,8 @@ def parser(program):
             ap.add_argument("--sigma", type=float, help="sigma parameter of smoothing (e.g. 0.5)")
         else:
             ap.add_argument("--" + name)
+    if program == "smoothing":
+        ap.add_argument("--excl_thr", help="addition: lo,hi -- create_exclusion on the first input masks the smoothing")
     if rows:
         ap.add_argument("--new_sphere", help="addition: a target sphere file in place of --ico")
         ap.add_argument("--method", choices=METHODS, default=rows, help="addition: the rows of the plan")
@@ -145,9 +150,17 @@ def run(program, opt):
     sxyz = true_rescale(sxyz)
     source = M.Mesh(ctx, sxyz, stri)
     if program == "smoothing":
-        data = meshio.load_metric(opt.metric_in[0], nvertices=len(sxyz))
-        written.append(gifti_name(opt.output + "-smoothed_data.func"))
-        meshio.save_metric(written[-1], M.smooth_data(source, data, source, opt.sigma))
+        excl = None
+        if opt.excl_thr is not None:
+            excl = M.create_exclusion(meshio.load_metric(opt.metric_in[0], nvertices=len(sxyz)), opt.excl_thr[0], opt.excl_thr[1])
+        plan = M.ResamplePlan.smoothing(source, source, opt.sigma, excl)  # ONE sweep for every input
+        for path in opt.metric_in:
+            data = meshio.load_metric(path, nvertices=len(sxyz), dtype=np.float32)  # the file's own floats; the sums run in FP64 and are rounded once
+            tag = "-" + stem(path) if len(opt.metric_in) > 1 else ""
+            written.append(gifti_name(opt.output + tag + "-smoothed_data.func"))
+            out = plan.apply(data)
+            meshio.save_metric(written[-1], out[0] if excl is not None else out)
+        plan.close()
         return written
     if opt.new_sphere is not None:
         txyz, ttri = meshio.load_surface(opt.new_sphere)
