@@ -472,6 +472,43 @@ int msm_cost_counters(msm_cost *c, int64_t counters[4]);
 #define MSM_MOVE_OCTETS_HO 7          /* k_triplet_octets_ho: the general on-demand kernel */
 #define MSM_MOVE_STRAIN 8             /* the strain-only classes: k_triplet_octets / k_triplet_octets_packed */
 int msm_cost_routes(msm_cost *c, int32_t routes[8]);
+/* The launch plan of a unary table: every decision of the launch that depends on the largest patch pmax (a coarse control grid under a fine data
+ * grid gives patches of thousands of points), taken by one host function that the launchers act on.  plan[MSM_PLAN_NSPLIT]: workgroups (label
+ * ranges) per control point, 1 <= nsplit <= L; plan[MSM_PLAN_SAMPLER]: MSM_SAMPLER_RAYS (k_unary_rays, targets with a direction table) or
+ * MSM_SAMPLER_SAMPLES (k_unary_samples, the complete search); plan[MSM_PLAN_SAMPLER_LDS]: its dynamic LDS in bytes; plan[MSM_PLAN_REDUCE]: the
+ * reduction kernel, MSM_UNARY_*; plan[MSM_PLAN_REDUCE_LDS] / [MSM_PLAN_REDUCE_THREADS]: its dynamic LDS in bytes and its workgroup size;
+ * plan[MSM_PLAN_REFUSED]: 0, or which kernel's LDS exceeds the 160 KB of a workgroup (MSM_PLAN_REFUSED_*) -- such a table fails with
+ * MSM_ERR_CAPACITY and a message that names the patch size before anything is launched, and the cost function stays usable;
+ * plan[MSM_PLAN_PMAX]: the pmax the plan was made for.  Byte counts saturate at INT32_MAX.
+ *   msm_unary_launch_plan   the plan for (kind MSM_COST_UNIVARIATE / _MULTIVARIATE / _PATCHWISE, simmeasure, D, L, pmax, ray_table != 0): pure host
+ *                           arithmetic, no context, no device.
+ *   msm_cost_unary_launch   the plan of this cost function's last unary table, refused ones included (all zero but nsplit = 1, threads = 256
+ *                           before the first); host bookkeeping only, as msm_cost_routes.
+ *   msm_unary_launch_order  the order in which the unary kernels take the control points (cp_xyz: 3 x N): Morton order of their positions.
+ *   msm_unary_fix_offsets   the MSM_UNARY_FIX_SEGMENTS + 1 offsets of the fix-up list's segments for patches pptr (N + 1) and that order: workgroup b of
+ *                           the sampling kernel appends to segment b % MSM_UNARY_FIX_SEGMENTS, which holds all samples of its workgroups; the last
+ *                           offset is L * pptr[N] (saturating at 2^32 - 1).
+ *   msm_cost_unary_fix_counters  counts[0]: the redo counter, counts[1 + s]: the fill of fix-up segment s, read back from the device after the
+ *                           queued work (a synchronising call for tests: every unary table leaves all MSM_UNARY_FIX_SEGMENTS + 1 of them zero). */
+#define MSM_PLAN_NSPLIT 0
+#define MSM_PLAN_SAMPLER 1
+#define MSM_PLAN_SAMPLER_LDS 2
+#define MSM_PLAN_REDUCE 3
+#define MSM_PLAN_REDUCE_LDS 4
+#define MSM_PLAN_REDUCE_THREADS 5
+#define MSM_PLAN_REFUSED 6
+#define MSM_PLAN_PMAX 7
+#define MSM_SAMPLER_NONE 0
+#define MSM_SAMPLER_SAMPLES 1
+#define MSM_SAMPLER_RAYS 2
+#define MSM_PLAN_REFUSED_SAMPLER 1
+#define MSM_PLAN_REFUSED_REDUCTION 2
+#define MSM_UNARY_FIX_SEGMENTS 64
+int msm_unary_launch_plan(int32_t kind, int32_t simmeasure, int32_t D, int32_t L, int32_t pmax, int32_t ray_table, int32_t plan[8]);
+int msm_cost_unary_launch(msm_cost *c, int32_t plan[8]);
+int msm_cost_unary_fix_counters(msm_cost *c, uint32_t *counts);
+int msm_unary_launch_order(const double *cp_xyz, int32_t N, int32_t *order);
+int msm_unary_fix_offsets(int32_t N, int32_t L, int32_t pmax, const int32_t *pptr, const int32_t *order, uint32_t *off);
 
 /* ------------------------------------------------------------------------------------------------
  * groupwise registration (gMSM).  Replaces DiscreteGroupModel::setupCostFunction and its helpers

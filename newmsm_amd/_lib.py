@@ -141,6 +141,11 @@ SIGNATURES = {
     "msm_cost_kernel_times": (C.c_int, [_VP, c_dp, C.c_int32, c_ip]),
     "msm_cost_counters": (C.c_int, [_VP, c_lp]),
     "msm_cost_routes": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "msm_unary_launch_plan": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)]),
+    "msm_cost_unary_launch": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "msm_cost_unary_fix_counters": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
+    "msm_unary_launch_order": (C.c_int, [c_dp, C.c_int32, c_ip]),
+    "msm_unary_fix_offsets": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, C.POINTER(C.c_uint32)]),
     "msm_group_create": (_VP, [_VP, C.POINTER(GroupParams), C.c_int32]),
     "msm_group_fusion_move": (C.c_int, [_VP, c_ip, C.c_int32, c_dp, c_dp]),
     "msm_group_destroy": (None, [_VP]),

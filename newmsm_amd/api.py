@@ -945,6 +945,52 @@ class DiscreteCostFunction:
         check(lib().msm_cost_routes(self.h, r))
         return dict(unary=self.UNARY_ROUTES[r[0]], move=self.MOVE_ROUTES[r[1]], move_nblk=r[2], move_cap=r[3], move_maxtri=r[4], move_tails=r[5], move_deferred=r[6])
 
+    SAMPLERS = ("none", "samples", "rays")  # MSM_SAMPLER_* of include/msmhip.h
+    REFUSALS = ("", "sampler", "reduction")  # MSM_PLAN_REFUSED_*
+
+    @classmethod
+    def _plan(cls, p):
+        return dict(nsplit=p[0], sampler=cls.SAMPLERS[p[1]], sampler_lds=p[2], reduce=cls.UNARY_ROUTES[p[3]], reduce_lds=p[4], reduce_threads=p[5],
+                    refused=cls.REFUSALS[p[6]], pmax=p[7])
+
+    def unary_launch(self):
+        """msm_cost_unary_launch: the launch plan of the last unary table as its launchers acted on it (a refused one included): nsplit (workgroups
+        per control point), sampler ("rays" / "samples") and sampler_lds (bytes of dynamic LDS), reduce (UNARY_ROUTES) with reduce_lds and
+        reduce_threads, refused ("" / "sampler" / "reduction": that kernel's LDS does not fit a workgroup), pmax (the largest patch)."""
+        p = (C.c_int32 * 8)()
+        check(lib().msm_cost_unary_launch(self.h, p))
+        return self._plan(p)
+
+    def unary_fix_counters(self):
+        """msm_cost_unary_fix_counters: the redo counter and the 64 fix-up segment counters, read back after the queued work; all zero between tables"""
+        n = (C.c_uint32 * 65)()
+        check(lib().msm_cost_unary_fix_counters(self.h, n))
+        return np.array(n[:], dtype=np.int64)
+
+
+def unary_launch_plan(kind, simmeasure, D, L, pmax, ray_table):
+    """msm_unary_launch_plan: what a unary table of these sizes would do (DiscreteCostFunction.unary_launch's fields); host arithmetic, no GPU."""
+    p = (C.c_int32 * 8)()
+    check(lib().msm_unary_launch_plan(KINDS[kind] if isinstance(kind, str) else int(kind), simmeasure, D, L, pmax, int(bool(ray_table)), p))
+    return DiscreteCostFunction._plan(p)
+
+
+def unary_launch_order(cp_xyz):
+    """msm_unary_launch_order: the order in which the unary kernels take the control points cp_xyz (N x 3)"""
+    cp = np.ascontiguousarray(np.asarray(cp_xyz, dtype=np.float64).T)
+    order = np.zeros(cp.shape[1], dtype=np.int32)
+    check(lib().msm_unary_launch_order(cp.ctypes.data_as(c_dp), cp.shape[1], order.ctypes.data_as(c_ip)))
+    return order
+
+
+def unary_fix_offsets(L, pmax, pptr, order):
+    """msm_unary_fix_offsets: the 65 segment offsets of the unary kernels' fix-up list for the patches pptr (N + 1) taken in `order`"""
+    pptr = np.ascontiguousarray(pptr, dtype=np.int32)
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    off = np.zeros(65, dtype=np.uint32)
+    check(lib().msm_unary_fix_offsets(len(order), L, pmax, pptr.ctypes.data_as(c_ip), order.ctypes.data_as(c_ip), off.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return off
+
 
 # ------------------------------------------------------------------ groupwise (gMSM)
 class DiscreteGroupCostFunction:

@@ -198,6 +198,30 @@ int resample_weights(msm_cost *c) {
     return MSM_OK;
 }
 
+// Launch order of the control points in the unary kernels: Morton order of their positions (cp: 3 x N)
+static void unary_launch_order(const double *cp, int N, std::vector<int32_t> &order) {
+    auto spread = [](uint32_t v) {  // 10 bits -> every third bit
+        v &= 0x3ff;
+        v = (v | (v << 16)) & 0x030000ff;
+        v = (v | (v << 8)) & 0x0300f00f;
+        v = (v | (v << 4)) & 0x030c30c3;
+        v = (v | (v << 2)) & 0x09249249;
+        return v;
+    };
+    std::vector<std::pair<uint32_t, int32_t>> key(N);
+    for (int i = 0; i < N; ++i) {
+        uint32_t q[3];
+        for (int a = 0; a < 3; ++a) {
+            const double u = (cp[(size_t)a * N + i] + kBounds) / (2 * kBounds);
+            q[a] = (uint32_t)std::max(0.0, std::min(1023.0, u == u ? u * 1024.0 : 0.0));
+        }
+        key[i] = {spread(q[0]) << 2 | spread(q[1]) << 1 | spread(q[2]), i};
+    }
+    std::sort(key.begin(), key.end());
+    order.resize(N);
+    for (int i = 0; i < N; ++i) order[i] = key[i].second;
+}
+
 int ensure_unary_table(msm_cost *c) {
     if (c->table_valid) return MSM_OK;
     int st = need(c, c->have_source, "get_source_data()");
@@ -218,6 +242,11 @@ int ensure_unary_table(msm_cost *c) {
     if (st) return st;
     UnaryLaunch u;
     u.tree = dev_tree(c->target);
+    // what the launch will do is decided, recorded and -- where a patch does not fit in LDS -- refused here, before anything is queued
+    c->unary_plan = unary_plan(c->p.kind, c->p.simmeasure, c->D, c->L, c->pmax, unary_uses_ray_table(u.tree));
+    c->unary_plan_pmax = c->pmax;
+    u.plan = &c->unary_plan;
+    MSM_TRY(unary_plan_refusal(c->unary_plan, c->pmax));
     u.tfeat = c->target->d_feat.p;
     u.D = c->D;
     u.N = N;
@@ -252,7 +281,7 @@ int ensure_unary_table(msm_cost *c) {
         MSM_TRY(ctx_sync(ctx));
         c->fix_off_valid = true;
     }
-    MSM_HIP(c->d_queues.ensure(N));
+    MSM_HIP(c->d_queues.ensure((size_t)N * c->unary_plan.nsplit));  // every workgroup of a control point may list it for the redo
     u.ntri = c->target->T;
     u.tval = c->d_tval.p;
     u.fix_list = c->d_fix_list.p;
@@ -519,28 +548,7 @@ int msm_cost_get_source_data(msm_cost *c) {
         // Launch order of the control points in the unary kernels: Morton order of their positions, so that the
         // contiguous share of each XCD (kernels map blockIdx % 8 to a range of this list) is one region of the sphere
         // and that XCD's L2 only has to hold the matching part of the target.
-        const int N = c->cpgrid->V;
-        const double *cp = c->cpgrid->xyz.data();
-        auto spread = [](uint32_t v) {  // 10 bits -> every third bit
-            v &= 0x3ff;
-            v = (v | (v << 16)) & 0x030000ff;
-            v = (v | (v << 8)) & 0x0300f00f;
-            v = (v | (v << 4)) & 0x030c30c3;
-            v = (v | (v << 2)) & 0x09249249;
-            return v;
-        };
-        std::vector<std::pair<uint32_t, int32_t>> key(N);
-        for (int i = 0; i < N; ++i) {
-            uint32_t q[3];
-            for (int a = 0; a < 3; ++a) {
-                const double u = (cp[(size_t)a * N + i] + kBounds) / (2 * kBounds);
-                q[a] = (uint32_t)std::max(0.0, std::min(1023.0, u == u ? u * 1024.0 : 0.0));
-            }
-            key[i] = {spread(q[0]) << 2 | spread(q[1]) << 1 | spread(q[2]), i};
-        }
-        std::sort(key.begin(), key.end());
-        c->order.resize(N);
-        for (int i = 0; i < N; ++i) c->order[i] = key[i].second;
+        unary_launch_order(c->cpgrid->xyz.data(), c->cpgrid->V, c->order);
         MSM_TRY(c->d_order.upload(c->order.data(), c->order.size(), ctx));
         c->fix_off_valid = false;
     }
@@ -677,6 +685,62 @@ int msm_cost_routes(msm_cost *c, int32_t routes[8]) {
     routes[MSM_ROUTE_MOVE_MAXTRI] = c->move_maxtri;
     routes[MSM_ROUTE_MOVE_TAILS] = (int32_t)std::min<int64_t>(c->move_tails, INT32_MAX);
     routes[MSM_ROUTE_MOVE_DEFERRED] = c->move_deferred;
+    return MSM_OK;
+}
+
+static int32_t sat32(size_t v) { return (int32_t)std::min<size_t>(v, INT32_MAX); }
+static void plan_words(const msm::UnaryPlan &p, int pmax, int32_t plan[8]) {
+    plan[MSM_PLAN_NSPLIT] = p.nsplit;
+    plan[MSM_PLAN_SAMPLER] = p.sampler;
+    plan[MSM_PLAN_SAMPLER_LDS] = sat32(p.sampler_lds);
+    plan[MSM_PLAN_REDUCE] = p.reduce;
+    plan[MSM_PLAN_REDUCE_LDS] = sat32(p.reduce_lds);
+    plan[MSM_PLAN_REDUCE_THREADS] = p.reduce_threads;
+    plan[MSM_PLAN_REFUSED] = p.refused;
+    plan[MSM_PLAN_PMAX] = pmax;
+}
+
+int msm_unary_launch_plan(int32_t kind, int32_t simmeasure, int32_t D, int32_t L, int32_t pmax, int32_t ray_table, int32_t plan[8]) {
+    if (!plan || kind < MSM_COST_UNIVARIATE || kind > MSM_COST_PATCHWISE || D < 1 || L < 1 || pmax < 0)
+        return fail(MSM_ERR_INVALID, "msm_unary_launch_plan: bad arguments");
+    plan_words(unary_plan(kind, simmeasure, D, L, pmax, ray_table != 0), pmax, plan);
+    return MSM_OK;
+}
+
+int msm_unary_fix_offsets(int32_t N, int32_t L, int32_t pmax, const int32_t *pptr, const int32_t *order, uint32_t *off) {
+    if (!pptr || !order || !off || N < 1 || L < 1 || pmax < 0) return fail(MSM_ERR_INVALID, "msm_unary_fix_offsets: bad arguments");
+    for (int i = 0; i < N; ++i)
+        if (order[i] < 0 || order[i] >= N || pptr[i + 1] < pptr[i]) return fail(MSM_ERR_INVALID, "msm_unary_fix_offsets: order is no list of control points, or pptr decreases");
+    std::vector<uint32_t> v;
+    unary_fix_offsets(N, L, pmax, pptr, order, v);
+    std::copy(v.begin(), v.end(), off);
+    return MSM_OK;
+}
+
+int msm_cost_unary_launch(msm_cost *c, int32_t plan[8]) {
+    if (!c || !plan) return fail(MSM_ERR_INVALID, "msm_cost_unary_launch: null argument");
+    plan_words(c->unary_plan, c->unary_plan_pmax, plan);
+    return MSM_OK;
+}
+
+int msm_cost_unary_fix_counters(msm_cost *c, uint32_t *counts) {
+    if (!c || !counts) return fail(MSM_ERR_INVALID, "msm_cost_unary_fix_counters: null argument");
+    MSM_TRY(drop_ctx_pending(c->ctx));
+    const int nseg = unary_fix_segments(), stride = (int)(unary_fix_counter_words() / (size_t)(nseg + 1));
+    for (int s = 0; s <= nseg; ++s) counts[s] = 0;
+    if (!c->d_fix_count.p) return MSM_OK;  // no table yet
+    std::vector<unsigned int> words(unary_fix_counter_words());
+    MSM_TRY(c->d_fix_count.download(words.data(), words.size(), c->ctx));
+    MSM_TRY(ctx_sync(c->ctx));
+    for (int s = 0; s <= nseg; ++s) counts[s] = words[(size_t)stride * s];
+    return MSM_OK;
+}
+
+int msm_unary_launch_order(const double *cp_xyz, int32_t N, int32_t *order) {
+    if (!cp_xyz || !order || N < 1) return fail(MSM_ERR_INVALID, "msm_unary_launch_order: bad arguments");
+    std::vector<int32_t> v;
+    unary_launch_order(cp_xyz, N, v);
+    std::copy(v.begin(), v.end(), order);
     return MSM_OK;
 }
 

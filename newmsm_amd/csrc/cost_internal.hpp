@@ -63,6 +63,8 @@ struct msm_cost {
     int move_nblk = 0, move_cap = 0, move_parity = 0;
     int move_maxtri = 0;                  // most control triangles in one workgroup of the fused move
     int route_unary = 0, route_move = 0;  // msm_cost_routes: MSM_UNARY_* / MSM_MOVE_* as the launchers reported them
+    msm::UnaryPlan unary_plan;            // msm_cost_unary_launch: the plan of the last unary table (refused ones included)
+    int unary_plan_pmax = 0;
     bool move_valid = false;
     // get_source_data products
     bool have_source = false;

@@ -59,6 +59,21 @@ int launch_scan_exclusive(msm_ctx *ctx, int *d_data, int n, int *d_tmp);
 int launch_label_rotations(msm_ctx *ctx, const double *d_cp, int N, const double *d_rot, const double *d_labels, int L, double *d_rnl,
                            double *d_moved);
 
+// What a unary-table launch does for (cost kind, similarity, D, L, largest patch, sampler): unary_plan() takes every decision that depends on the
+// largest patch, the launchers act on the plan they are handed (UnaryLaunch::plan) and msm_unary_launch_plan shows it to the tests.
+struct UnaryPlan {
+    int nsplit = 1;              // workgroups (label ranges) per control point
+    int sampler = 0;             // MSM_SAMPLER_*
+    size_t sampler_lds = 0;      // dynamic LDS of the sampling kernel, bytes
+    int reduce = 0;              // MSM_UNARY_*: the reduction kernel
+    size_t reduce_lds = 0;       // its dynamic LDS, bytes
+    int reduce_threads = 256;    // its workgroup size
+    int refused = 0;             // MSM_PLAN_REFUSED_*: a kernel's LDS does not fit a workgroup; nothing is launched
+};
+UnaryPlan unary_plan(int kind, int simmeasure, int D, int L, int pmax, bool ray_table);
+int unary_plan_refusal(const UnaryPlan &p, int pmax);  // MSM_OK, or MSM_ERR_CAPACITY with the message that names the patch size
+bool unary_uses_ray_table(const DevTree &t);
+
 struct UnaryLaunch {
     DevTree tree;
     const double *tfeat;   // target features, V x D vertex-major
@@ -88,9 +103,10 @@ struct UnaryLaunch {
     double *fix_pt;                // three doubles per slot
     unsigned int *fix_cnt;         // unary_fix_counter_words() words (zeroed by the launch)
     const unsigned int *fix_off;   // unary_fix_segments() + 1 offsets from unary_fix_offsets()
-    int *redo_list;                // N ints
+    int *redo_list;                // N * plan->nsplit ints: every workgroup of a control point may list it
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // optional: recorded around the samples kernel
     int *route = nullptr;          // optional: the launcher writes the MSM_UNARY_* value of the reduction kernel it chose
+    const UnaryPlan *plan = nullptr;  // unary_plan() for this launch
 };
 int unary_nsplit(int L, int pmax);
 int unary_fix_segments();

@@ -36,7 +36,8 @@ namespace msm {
 
 namespace {
 
-constexpr int kFixSegs = 64;       // segments of the fix-up list (see SamplesArgs)
+constexpr int kFixSegs = MSM_UNARY_FIX_SEGMENTS;  // segments of the fix-up list (see SamplesArgs); k_unary_fixup scans them with one wavefront
+static_assert(kFixSegs == 64, "k_unary_fixup's prefix sum is one wavefront wide");
 constexpr int kCntStride = 32;     // counters sit 128 bytes apart
 constexpr int kChunk = 768;       // samples per LDS pass (3 rounds of 256 lanes)
 constexpr int kQueueCap = 3072;   // (sample, triangle) pairs per pass
@@ -1066,6 +1067,11 @@ static size_t samples_lds(int pmax, int L, int nsplit) {
     const size_t lper = (size_t)(L + nsplit - 1) / nsplit;
     return sizeof(double) * (5 * (size_t)pmax + 9 * (size_t)L + lper * pmax) + sizeof(unsigned) * kQueueCap + sizeof(int) * 2 * kChunk;
 }
+// dynamic LDS of k_unary_rays: patch coordinates, rotations, and the list of samples the table could not settle
+static size_t rays_lds(int pmax, int L, int nsplit) {
+    const size_t lper = (size_t)(L + nsplit - 1) / nsplit;
+    return sizeof(double) * (3 * (size_t)pmax + 9 * (size_t)L) + sizeof(int) * (lper * pmax + 4) + 16;
+}
 
 // Workgroups per control point: enough that one workgroup's samples are about one LDS pass (at most 4 for that
 // reason), and more when the patch is so large (coarse control grid under a fine data grid) that the per-label target
@@ -1075,6 +1081,57 @@ int unary_nsplit(int L, int pmax) {
     while (n < L && samples_lds(pmax, L, n) > 64 * 1024) ++n;
     return std::min(n, std::max(L, 1));
 }
+
+// Every decision of a unary-table launch that depends on the largest patch, in one place: the launchers below act on
+// this plan and on nothing else, and msm_unary_launch_plan hands it to the tests.  A workgroup of gfx950 can address
+// 160 KB of LDS, static variables included; above 64 KB of dynamic LDS a kernel needs its attribute raised first.
+// A plan whose sampler or reduction does not fit is refused before anything is launched.
+constexpr size_t kLdsWorkgroup = 160 * 1024, kLdsDefault = 64 * 1024;
+constexpr size_t kStaticSampler = 16;  // k_unary_samples: s_qn, s_ndefer; k_unary_rays: s_nleft, s_base
+constexpr size_t kStaticFlat = 32;     // k_unary_reduce_flat: s_stat[3]
+
+UnaryPlan unary_plan(int kind, int simmeasure, int D, int L, int pmax, bool ray_table) {
+    UnaryPlan p;
+    const bool dice = simmeasure == 4 || simmeasure == 5;
+    p.nsplit = unary_nsplit(L, pmax);
+    p.sampler = ray_table ? MSM_SAMPLER_RAYS : MSM_SAMPLER_SAMPLES;
+    p.sampler_lds = ray_table ? rays_lds(pmax, L, p.nsplit) : samples_lds(pmax, L, p.nsplit);
+    if (p.sampler_lds + kStaticSampler > kLdsWorkgroup) p.refused = MSM_PLAN_REFUSED_SAMPLER;
+    size_t stat = 0;
+    if (kind == MSM_COST_UNIVARIATE) {
+        // Correlation / SSD: both samplers only fill tval and k_unary_reduce_flat reduces it.  DICE: the wavefront-per-label kernel, over
+        // all control points behind the ray sampler, over the redo list behind the complete sampler (which reduces the rest itself)
+        p.reduce = dice ? MSM_UNARY_UNIVARIATE : MSM_UNARY_FLAT;
+        p.reduce_lds = sizeof(double) * 2 * (size_t)pmax;
+        stat = dice ? 0 : kStaticFlat;
+    } else if (!dice && D >= 12 && D <= kMvLanes * kMvKeep) {  // few dimensions: a lane per point wastes less
+        p.reduce = kind == MSM_COST_MULTIVARIATE ? MSM_UNARY_MV8 : (D <= 32 ? MSM_UNARY_PW8_4 : MSM_UNARY_PW8_8);
+    } else {
+        p.reduce = MSM_UNARY_FEATURES;
+        p.reduce_lds = (dice && kind == MSM_COST_PATCHWISE) ? sizeof(double) * 8 * (size_t)pmax : 0;  // two patches per wavefront
+        if (p.reduce_lds > kLdsWorkgroup) {  // one wavefront per control point: a quarter of the LDS
+            p.reduce_lds /= 4;
+            p.reduce_threads = 64;
+        }
+    }
+    if (!p.refused && p.reduce_lds + stat > kLdsWorkgroup) p.refused = MSM_PLAN_REFUSED_REDUCTION;
+    return p;
+}
+
+int unary_plan_refusal(const UnaryPlan &p, int pmax) {
+    if (!p.refused) return MSM_OK;
+    if (p.refused == MSM_PLAN_REFUSED_SAMPLER)
+        return fail(MSM_ERR_CAPACITY, "a patch of %d points does not fit in LDS (%s, %zu bytes)", pmax, p.sampler == MSM_SAMPLER_RAYS ? "k_unary_rays" : "k_unary_samples", p.sampler_lds);
+    return fail(MSM_ERR_CAPACITY, "a patch of %d points does not fit in LDS (reduction, %zu bytes)", pmax, p.reduce_lds);
+}
+
+// dynamic LDS beyond the default limit: the kernel's attribute first (the plan has checked that it fits a workgroup)
+template <class K>
+static int allow_lds(K kernel, size_t lds) {
+    if (lds > kLdsDefault) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MSM_OK;
+}
+
 int unary_fix_segments() { return kFixSegs; }
 size_t unary_fix_counter_words() { return (size_t)kCntStride * (1 + kFixSegs); }
 // samples of workgroup `block` of the unary sample kernels (the mapping at the top of k_unary_samples / k_unary_rays)
@@ -1095,9 +1152,9 @@ void unary_fix_offsets(int N, int L, int pmax, const int32_t *pptr, const int32_
     for (int s = 0; s < kFixSegs; ++s) off[s + 1] = (uint32_t)std::min<uint64_t>(0xffffffffull, off[s] + size[s]);
 }
 
-static bool uses_ray_table(const DevTree &t) { return t.simple && t.ray_G > 0 && t.ray_cell && t.ray_tri; }
+bool unary_uses_ray_table(const DevTree &t) { return t.simple && t.ray_G > 0 && t.ray_cell && t.ray_tri; }
 
-static int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWeightsScratch *w, SamplesArgs &a, bool fused_reduction = false) {
+static int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, const UnaryWeightsScratch *w, SamplesArgs &a, bool fused_reduction = false) {
     if (u.tree.nnodes <= 0 || !u.tree.mask) return fail(MSM_ERR_STATE, "target search structure missing");
     a.tree = u.tree;
     a.tfeat = u.tfeat;
@@ -1128,22 +1185,16 @@ static int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWeights
     a.redo_count = u.fix_cnt;
     a.status = ctx->d_status;
     if (u.ntri >= (1 << kTriBits)) return fail(MSM_ERR_CAPACITY, "target mesh has %d triangles; the sample queue packs ids in %d bits", u.ntri, kTriBits);
-    a.nsplit = unary_nsplit(u.L, u.pmax);
-    const size_t lds = samples_lds(u.pmax, u.L, a.nsplit);
-    if (!uses_ray_table(u.tree) && lds > 64 * 1024) {
-        if (lds > 160 * 1024) return fail(MSM_ERR_CAPACITY, "a patch of %d points does not fit in LDS", u.pmax);
-        MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_unary_samples), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    a.nsplit = plan.nsplit;
+    const bool rays = plan.sampler == MSM_SAMPLER_RAYS;
+    MSM_TRY(rays ? allow_lds(k_unary_rays, plan.sampler_lds) : allow_lds(k_unary_samples, plan.sampler_lds));
     const int blocks = a.nsplit * 8 * ((u.N + 7) / 8);
     if (u.ev_start) MSM_HIP(hipEventRecord(u.ev_start, ctx->stream));
-    if (uses_ray_table(u.tree)) {
+    if (rays) {
         a.U = nullptr;  // the reduction is a kernel of its own on this path
-        const int lper = (u.L + a.nsplit - 1) / a.nsplit;
-        const size_t rays_lds = sizeof(double) * (3 * (size_t)u.pmax + 9 * (size_t)u.L) + sizeof(int) * ((size_t)lper * u.pmax + 4) + 16;
-        if (rays_lds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_unary_rays), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rays_lds));
-        hipLaunchKernelGGL(k_unary_rays, dim3(blocks), dim3(256), rays_lds, ctx->stream, a);
+        hipLaunchKernelGGL(k_unary_rays, dim3(blocks), dim3(256), plan.sampler_lds, ctx->stream, a);
     } else {
-        hipLaunchKernelGGL(k_unary_samples, dim3(blocks), dim3(256), lds, ctx->stream, a);
+        hipLaunchKernelGGL(k_unary_samples, dim3(blocks), dim3(256), plan.sampler_lds, ctx->stream, a);
     }
     MSM_HIP(hipGetLastError());
     if (u.ev_stop) MSM_HIP(hipEventRecord(u.ev_stop, ctx->stream));
@@ -1155,10 +1206,14 @@ static int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWeights
 int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u) {
     SamplesArgs a;
     const bool dice = u.simmeasure == 4 || u.simmeasure == 5;
+    if (!u.plan) return fail(MSM_ERR_STATE, "launch_unary_univariate: no launch plan");
+    const UnaryPlan &plan = *u.plan;
+    MSM_TRY(unary_plan_refusal(plan, u.pmax));
     // Correlation / SSD: both search paths only fill tval and one kernel reduces it, so the table does not depend on
     // which of them ran (the ray table of a target arrives in the background, api.cpp: ensure_rays).  DICE costs are
     // ratios of counts -- the same from any summation order -- and keep the reduction fused into the general kernel.
-    int st = launch_samples(ctx, u, nullptr, a, dice);
+    MSM_TRY(dice ? allow_lds(k_unary_reduce_univariate, plan.reduce_lds) : allow_lds(k_unary_reduce_flat, plan.reduce_lds));
+    int st = launch_samples(ctx, u, plan, nullptr, a, dice);
     if (st) return st;
     // control points that had deferred samples are reduced now that the fix-up kernel has filled them in
     ReduceArgs r;
@@ -1178,19 +1233,19 @@ int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u) {
     r.U = u.U;
     r.redo_list = u.redo_list;
     r.redo_count = u.fix_cnt;
-    if (u.route) *u.route = dice ? MSM_UNARY_UNIVARIATE : MSM_UNARY_FLAT;
-    if (uses_ray_table(u.tree) && dice) {
+    if (u.route) *u.route = plan.reduce;
+    if (plan.sampler == MSM_SAMPLER_RAYS && dice) {
         // the rank-counting DICE reduction is the wavefront-per-label kernel; all control points
         r.redo_list = nullptr;
         r.redo_count = nullptr;
-        hipLaunchKernelGGL(k_unary_reduce_univariate, dim3(std::min(u.N, 2048)), dim3(256), sizeof(double) * 2 * (size_t)u.pmax, ctx->stream, r);
+        hipLaunchKernelGGL(k_unary_reduce_univariate, dim3(std::min(u.N, 2048)), dim3(256), plan.reduce_lds, ctx->stream, r);
         MSM_HIP(hipMemsetAsync(u.fix_cnt, 0, unary_fix_counter_words() * sizeof(unsigned), ctx->stream));
     } else if (!dice) {
         r.redo_list = u.order;  // all control points, in launch order
-        hipLaunchKernelGGL(k_unary_reduce_flat, dim3(u.N), dim3(256), sizeof(double) * 2 * (size_t)u.pmax, ctx->stream, r, u.fix_cnt,
+        hipLaunchKernelGGL(k_unary_reduce_flat, dim3(u.N), dim3(256), plan.reduce_lds, ctx->stream, r, u.fix_cnt,
                            (int)unary_fix_counter_words());
     } else {
-        hipLaunchKernelGGL(k_unary_reduce_univariate, dim3(64), dim3(256), sizeof(double) * 2 * (size_t)u.pmax, ctx->stream, r);
+        hipLaunchKernelGGL(k_unary_reduce_univariate, dim3(64), dim3(256), plan.reduce_lds, ctx->stream, r);
         MSM_HIP(hipMemsetAsync(u.fix_cnt, 0, unary_fix_counter_words() * sizeof(unsigned), ctx->stream));  // counters are zero between launches
     }
     MSM_HIP(hipGetLastError());
@@ -1199,7 +1254,12 @@ int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u) {
 
 int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWeightsScratch &w, bool patchwise) {
     SamplesArgs a;
-    int st = launch_samples(ctx, u, &w, a);
+    if (!u.plan) return fail(MSM_ERR_STATE, "launch_unary_multivariate: no launch plan");
+    const UnaryPlan &plan = *u.plan;
+    MSM_TRY(unary_plan_refusal(plan, u.pmax));
+    if (plan.reduce != MSM_UNARY_FEATURES && !u.sfeat_vm) return fail(MSM_ERR_STATE, "vertex-major features missing");
+    if (plan.reduce == MSM_UNARY_FEATURES) MSM_TRY(allow_lds(k_unary_reduce_features, plan.reduce_lds));
+    int st = launch_samples(ctx, u, plan, &w, a);
     if (st) return st;
     ReduceMvArgs r;
     r.N = u.N;
@@ -1221,8 +1281,7 @@ int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWei
     r.pmax = u.pmax;
     r.percentile = u.percentile;
     r.U = u.U;
-    const bool dice = u.simmeasure == 4 || u.simmeasure == 5;
-    if (!dice && u.D >= 12 && u.D <= kMvLanes * kMvKeep && u.sfeat_vm) {  // few dimensions: a lane per point wastes less
+    if (plan.reduce != MSM_UNARY_FEATURES) {
         ReduceMv8Args m;
         m.N = u.N, m.L = u.L, m.Nsrc = u.Nsrc, m.D = u.D;
         m.tfeat = u.tfeat;
@@ -1235,30 +1294,17 @@ int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWei
         m.stri = w.stri, m.sw3 = w.sw3;
         m.simmeasure = u.simmeasure;
         m.U = u.U;
-        int route;
-        if (!patchwise) {
-            route = MSM_UNARY_MV8;
+        if (plan.reduce == MSM_UNARY_MV8) {
             hipLaunchKernelGGL(k_unary_reduce_mv8, dim3(u.N), dim3(256), 0, ctx->stream, m);
-        } else if (u.D <= 32) {
-            route = MSM_UNARY_PW8_4;
+        } else if (plan.reduce == MSM_UNARY_PW8_4) {
             hipLaunchKernelGGL(k_unary_reduce_pw8<4>, dim3(u.N), dim3(256), 0, ctx->stream, m);
         } else {
-            route = MSM_UNARY_PW8_8;
             hipLaunchKernelGGL(k_unary_reduce_pw8<8>, dim3(u.N), dim3(256), 0, ctx->stream, m);
         }
-        if (u.route) *u.route = route;
     } else {
-        size_t flds = (dice && patchwise) ? sizeof(double) * 8 * (size_t)u.pmax : 0;
-        int threads = 256;
-        if (flds > 160 * 1024) {  // one wavefront per control point: a quarter of the LDS
-            flds /= 4;
-            threads = 64;
-        }
-        if (flds > 160 * 1024) return fail(MSM_ERR_CAPACITY, "a patch of %d points does not fit in LDS (patchwise DICE)", u.pmax);
-        if (flds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_unary_reduce_features), hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-        hipLaunchKernelGGL(k_unary_reduce_features, dim3(u.N), dim3(threads), flds, ctx->stream, r);
-        if (u.route) *u.route = MSM_UNARY_FEATURES;
+        hipLaunchKernelGGL(k_unary_reduce_features, dim3(u.N), dim3(plan.reduce_threads), plan.reduce_lds, ctx->stream, r);
     }
+    if (u.route) *u.route = plan.reduce;
     MSM_HIP(hipGetLastError());
     MSM_HIP(hipMemsetAsync(u.fix_cnt, 0, unary_fix_counter_words() * sizeof(unsigned), ctx->stream));  // counters are zero between launches
     return MSM_OK;
