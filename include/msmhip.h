@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 12  /* 12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 12  /* 12: msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise / msm_mcmc_gpu_stats / msm_mcmc_proposals / msm_mcmc_schedule added (the Monte Carlo optimiser's sweeps on the GPU; additive, the version stays).  12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -326,6 +326,23 @@ int msm_histogram_match(msm_ctx *ctx, int32_t n_src, int32_t D, int32_t Vs, cons
  * combinations.  labeling (N) is read and updated.  The energy the reference returns is msm_cost_total(labeling). */
 int msm_mcmc_optimise(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
                       int32_t iters, uint64_t seed, int32_t *labeling);
+/* MCMC::optimise M/mcmc_opt.h:31-134 with the sweeps on the GPU: the labelling msm_mcmc_optimise gives for the same arguments, bit for bit.  The host
+ * tables are uploaded through the context's staging blocks; one workgroup walks the triplets level by level (a triplet's level is one above the highest
+ * level of the earlier triplets that share a node with it, so the triplets of a level are independent) with the labelling in LDS, and takes its
+ * proposals from the host's own stream (std::mt19937 + std::geometric_distribution, drawn chunk by chunk while the device works on the chunk before;
+ * MSMHIP_MCMC_CHUNK_SWEEPS sets the sweeps per chunk).  Argument checks and messages are msm_mcmc_optimise's; additionally L > 65535 is refused
+ * (MSM_ERR_INVALID) and N > 80000 (the labelling does not fit a workgroup's LDS: MSM_ERR_CAPACITY).  iters == 0 or T == 0 leave the labelling as it is. */
+int msm_mcmc_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                          double mcparam, int32_t iters, uint64_t seed, int32_t *labeling);
+/* What the last msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise on the context did: stats[0] ms in the sweep kernels (HIP events), [1] levels walked,
+ * [2] ms the host spent drawing proposals, [3] chunks, [4] levels of one sweep, [5] the widest level. */
+int msm_mcmc_gpu_stats(msm_ctx *ctx, double stats[6]);
+/* [host] The proposal stream both optimisers consume: out[s * T + t] is the label proposed to triplet t in sweep s (sweeps x T values), drawn in chunks of
+ * chunk_sweeps whole sweeps (<= 0: one chunk); the stream does not depend on the chunking.  L > 65535: MSM_ERR_INVALID. */
+int msm_mcmc_proposals(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, int32_t chunk_sweeps, uint16_t *out);
+/* [host] The level schedule of a triplet list (any list with nodes in [0, N)): level[t] (0-based), order (the T triplets by level, ascending within a
+ * level), level_off (offsets into order; room for T + 1), *levels.  level / order / level_off may be NULL. */
+int msm_mcmc_schedule(const int32_t *triplets, int32_t N, int32_t T, int32_t *level, int32_t *order, int32_t *level_off, int32_t *levels);
 /* [host] A STAND-IN for the binary solve of one label step of Fusion::optimize (I/Fusion/Fusion.h:198-229 hands the step to ELC's
  * reduction + FastPD, which are licence-restricted and FSL-bound: not reproduced).  Iterated conditional modes over x in {0,1}^N
  * (0: the node keeps its label, 1: it takes the proposed one) for
@@ -430,6 +447,10 @@ int msm_cost_pairwise_table(msm_cost *c, double *paircosts);
 /* computeTripletCosts M/DiscreteCostFunction.cpp:245-253 (the MCMC optimiser's table, M/mcmc_opt.h:58): tcosts[((t - t0)*L + a)*L*L + b*L + c]
  * for the triplets t0 <= t < t1 (the whole table is T * L^3 doubles, 281 MB at ico4 / 19 labels: fetch it in ranges) */
 int msm_cost_triplet_table(msm_cost *c, int32_t t0, int32_t t1, double *tcosts);
+/* computeUnaryCosts + computeTripletCosts + MCMC::optimise (M/mcmc_opt.h:31-134) over the cost function's own tables, which never leave the device: the
+ * unary table's kernels and the triplet-table kernels fill device buffers (T * L^3 doubles for the latter), then the sweeps of msm_mcmc_optimise_gpu run
+ * there.  The labelling (N, read and updated) is the one msm_cost_unary_table + msm_cost_triplet_table(0, T) + msm_mcmc_optimise give, bit for bit. */
+int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t seed, int32_t *labeling);
 /* evaluateTotalCostSum :55-77: parts = {unary, pairwise, triplet} sums in the reference's serial order */
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]);
 /* Optional HIP-event timing of the sampling kernel (k_unary_rays or k_unary_samples) of each unary-table launch, recorded on the

@@ -447,6 +447,12 @@ inline void mcmc_optimise(const Matrix &unary_costs, const Matrix &tcosts, const
     check(msm_mcmc_optimise(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), dist_param,
                             mciters, seed, labeling.data()));
 }
+// the same with the sweeps on the GPU (msm_mcmc_optimise_gpu: the tables are uploaded, one workgroup walks the triplets level by level): the same labeling
+inline void mcmc_optimise_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
+                              double dist_param, int mciters, uint64_t seed, std::vector<int32_t> &labeling) {
+    check(msm_mcmc_optimise_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
+                                dist_param, mciters, seed, labeling.data()));
+}
 
 // The stand-in for the binary solve of one label step of Fusion::optimize (msm_fusion_icm_step: iterated conditional modes, NOT ELC +
 // FastPD): x[node] = 1 where the proposed label is taken.  unary2 N x 2 (may be empty: no unary costs), quads P x 4, octets T x 8.
@@ -552,6 +558,11 @@ public:
         std::vector<double> tcosts((size_t)T_ * L_ * L_ * L_);
         if (!tcosts.empty()) check(msm_cost_triplet_table(h_, 0, T_, tcosts.data()));
         return tcosts;
+    }
+    // computeUnaryCosts + computeTripletCosts + MCMC::optimise with both tables staying on the device (msm_cost_mcmc_optimise): the labeling
+    // computeUnaryCosts() + computeTripletCosts() + mcmc_optimise give, bit for bit
+    void mcmc_optimise(double dist_param, int mciters, uint64_t seed, std::vector<int32_t> &labeling) {
+        check(msm_cost_mcmc_optimise(h_, dist_param, mciters, seed, labeling.data()));
     }
     // the batched forms the optimisers' loops collapse to (I/Fusion/Fusion.h:138-196)
     std::vector<double> computeTripletCost(const std::vector<int32_t> &t, const std::vector<int32_t> &a, const std::vector<int32_t> &b,

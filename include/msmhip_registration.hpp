@@ -57,6 +57,9 @@ struct LevelOptions {
     // licence-restricted binary solve (msm_fusion_icm_step, icm_passes passes): the path is exercised as HOCR would, the result is not HOCR's
     bool fusion = false;
     int icm_passes = 5;
+    // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
+    // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
+    bool mcmc_gpu = false;
     // true: --regoption=1 as --dopt=FastPD drives it (M/mesh_registration.cpp:182-188): the model lists pairs instead of triplets, per iteration
     // computeUnaryCosts + computePairwiseCosts, then a stand-in for FPD::FastPD(model, 100) (msm_pairwise_icm)
     bool pairwise = false;
@@ -173,7 +176,8 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
         if (o.pairwise) costfct.setPairs(pairs);
         else costfct.setTriplets(triplets);
         ++m_iter;
-        PhaseClock::timed(clock, "unary_table", [&] { costfct.computeUnaryCosts(); });
+        const bool mcmc_gpu = o.mcmc_gpu && !o.fusion && !o.pairwise;
+        if (!mcmc_gpu) PhaseClock::timed(clock, "unary_table", [&] { costfct.computeUnaryCosts(); });
         std::vector<int32_t> labeling((size_t)N, 0);  // resetLabeling
         const int L = (int)(labels.size() / 3), T = (int)(triplets.size() / 3);
         if (o.fusion) {  // ---- Fusion::optimize: two sweeps over the labels, a fusion move per label step
@@ -217,6 +221,8 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
         } else if (o.pairwise) {  // ---- FastPD: computeUnaryCosts, computePairwiseCosts, the solve
             PhaseClock::timed(clock, "pairwise_table", [&] { costfct.computePairwiseCosts(); });
             PhaseClock::timed(clock, "optimiser", [&] { pairwise_icm(costfct.unarycosts, costfct.paircosts, pairs, N, L, labeling, 100); });
+        } else if (mcmc_gpu) {  // ---- MCMC with the tables and the sweeps on the device: the labeling of the branch below
+            PhaseClock::timed(clock, "optimiser", [&] { costfct.mcmc_optimise(o.mcparam, o.mciters, o.seed + (uint64_t)it, labeling); });
         } else {  // ---- MCMC: computeUnaryCosts, computeTripletCosts, optimise
             const std::vector<double> tcosts = PhaseClock::timed(clock, "triplet_table", [&] { return costfct.computeTripletCosts(); });
             PhaseClock::timed(clock, "optimiser", [&] { mcmc_optimise(costfct.unarycosts, tcosts, triplets, N, L, o.mcparam, o.mciters, o.seed + (uint64_t)it, labeling); });

@@ -677,6 +677,44 @@ def mcmc_optimise(unary, tcosts, triplets, labeling, mcparam=0.8, iters=100, see
     return lab
 
 
+def mcmc_optimise_gpu(ctx, unary, tcosts, triplets, labeling, mcparam=0.8, iters=100, seed=0):
+    """msm_mcmc_optimise_gpu: mcmc_optimise with the sweeps on the GPU (one workgroup walks the triplets level by level, the proposals come from the
+    host's own stream); the labeling mcmc_optimise returns for the same arguments, bit for bit."""
+    U, pu = _d(unary)
+    L, N = U.shape
+    tc, ptc = _d(tcosts)
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    T = tr.shape[0]
+    assert tc.size == T * L ** 3
+    lab = np.array(labeling, dtype=np.int32)
+    check(lib().msm_mcmc_optimise_gpu(ctx.h, pu, ptc, tr.ctypes.data_as(c_ip), N, L, T, float(mcparam), int(iters), int(seed), lab.ctypes.data_as(c_ip)))
+    return lab
+
+
+def mcmc_gpu_stats(ctx):
+    """msm_mcmc_gpu_stats of the context's last GPU sweeps: dict(kernel_ms, levels, draw_ms, chunks, levels_per_sweep, widest_level)"""
+    s = np.zeros(6)
+    check(lib().msm_mcmc_gpu_stats(ctx.h, s.ctypes.data_as(c_dp)))
+    return dict(kernel_ms=s[0], levels=int(s[1]), draw_ms=s[2], chunks=int(s[3]), levels_per_sweep=int(s[4]), widest_level=int(s[5]))
+
+
+def mcmc_proposals(L, mcparam, seed, T, sweeps, chunk_sweeps=0):
+    """msm_mcmc_proposals: the labels MCMC::optimise proposes, (sweeps, T) uint16 in visit order, drawn in chunks of chunk_sweeps sweeps"""
+    out = np.zeros((int(sweeps), int(T)), dtype=np.uint16)
+    check(lib().msm_mcmc_proposals(int(L), float(mcparam), int(seed), int(T), int(sweeps), int(chunk_sweeps), out.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return out
+
+
+def mcmc_schedule(triplets, N):
+    """msm_mcmc_schedule: (level per triplet, the triplets by level, level offsets) of the GPU sweeps' level schedule"""
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    T = tr.shape[0]
+    level, order, off = np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32), np.zeros(T + 1, dtype=np.int32)
+    n = C.c_int32()
+    check(lib().msm_mcmc_schedule(tr.ctypes.data_as(c_ip), int(N), T, level.ctypes.data_as(c_ip), order.ctypes.data_as(c_ip), off.ctypes.data_as(c_ip), C.byref(n)))
+    return level, order, off[: n.value + 1]
+
+
 def fusion_icm_step(unary2, octets, triplets, passes=5, quads=None, pairs=None):
     """msm_fusion_icm_step: the stand-in binary solve of one label step (iterated conditional modes; NOT ELC + FastPD).  unary2 N x 2
     (current, proposed) or an int N (no unary costs), octets T x 8 / quads P x 4 as tripletOctets / fusionMove return them; returns x (N):
@@ -897,6 +935,14 @@ class DiscreteCostFunction:
                 out = self._keep["tcosts"] = np.empty(shape)
         check(lib().msm_cost_triplet_table(self.h, int(t0), int(t1), out.ctypes.data_as(c_dp)))
         return out
+
+    def mcmc_optimise(self, labeling, mcparam=0.8, iters=100, seed=0):
+        """msm_cost_mcmc_optimise: computeUnaryCosts + computeTripletCosts + MCMC::optimise with both tables staying on the device; the labeling
+        computeUnaryCosts() + computeTripletCosts() + api.mcmc_optimise give, bit for bit"""
+        lab = np.array(labeling, dtype=np.int32)
+        assert lab.shape == (self.N,)
+        check(lib().msm_cost_mcmc_optimise(self.h, float(mcparam), int(iters), int(seed), lab.ctypes.data_as(c_ip)))
+        return lab
 
     def computePairwiseCost(self, pair, la, lb):
         p, pp = _i(np.atleast_1d(pair))

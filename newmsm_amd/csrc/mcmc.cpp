@@ -1,0 +1,199 @@
+// mcmc.cpp -- the host side of the Monte Carlo optimiser's GPU sweeps (mcmc.hpp; kernel: mcmc_kernels.hip): the level schedule, the
+// proposal stream in chunks of whole sweeps, and the loop that draws chunk k + 1 while the device walks chunk k.
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+
+#include "mcmc.hpp"
+
+using namespace msm;
+
+namespace msm {
+
+int mcmc_check_arguments(const int32_t *triplets, int N, int L, int T, double mcparam, const int32_t *labeling) {
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    for (int i = 0; i < N; ++i)
+        if (labeling[i] < 0 || labeling[i] >= L) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: label of node %d out of range", i);
+    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
+        if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
+    return MSM_OK;
+}
+
+}  // namespace msm
+
+namespace {
+
+struct McmcScratch {
+    DevBuf<double> U, tc;  // the host tables of msm_mcmc_optimise_gpu
+    DevBuf<int4> sched;
+    DevBuf<int32_t> level_off, labeling;
+    DevBuf<uint16_t> prop;
+    std::vector<hipEvent_t> ev;  // a pair per chunk
+    double stats[6] = {0, 0, 0, 0, 0, 0};
+    ~McmcScratch() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+
+McmcScratch &mcmc_scratch(msm_ctx *ctx) {
+    if (!ctx->mcmc_scratch) ctx->mcmc_scratch = std::shared_ptr<void>(new McmcScratch(), [](void *p) { delete static_cast<McmcScratch *>(p); });
+    return *static_cast<McmcScratch *>(ctx->mcmc_scratch.get());
+}
+
+// sweeps per chunk: MSMHIP_MCMC_CHUNK_SWEEPS, or as many as make half a million proposals (1 MB).  The host draws about as fast as the device walks
+// (DESIGN.md 5.16), so the device idles for as long as the first chunk takes to draw: at 4 MB that was a sixth of a 2 000-sweep run at ico4.
+int chunk_sweeps(int T, int iters) {
+    long n = 0;
+    if (const char *e = std::getenv("MSMHIP_MCMC_CHUNK_SWEEPS")) n = std::atol(e);
+    if (n <= 0) n = ((long)1 << 19) / std::max(T, 1);
+    n = std::min(n, ((long)1 << 30) / std::max(T, 1));  // (a chunk is at most 2 GB of proposals, whatever the environment says)
+    return (int)std::max(1L, std::min(n, (long)iters));
+}
+
+// host -> device through the staging blocks in pieces (a table of 281 MB must not ask for one staging block of its size)
+int upload_in_pieces(msm_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    const size_t piece = (size_t)16 << 20;
+    for (size_t off = 0; off < bytes; off += piece)
+        MSM_TRY(stage_h2d(ctx, (char *)dst + off, (const char *)src + off, std::min(piece, bytes - off)));
+    return MSM_OK;
+}
+
+}  // namespace
+
+namespace msm {
+
+int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
+                    int32_t *labeling) {
+    if (iters <= 0 || T <= 0) return MSM_OK;
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
+    McmcScratch &s = mcmc_scratch(ctx);
+    McmcSchedule sch;
+    mcmc_build_schedule(triplets, N, T, sch);
+    std::vector<int4> rec((size_t)T);
+    std::vector<int32_t> pos((size_t)T);  // where triplet t stands in the schedule
+    for (int i = 0; i < T; ++i) {
+        const int t = sch.order[(size_t)i];
+        rec[(size_t)i] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
+        pos[(size_t)t] = i;
+    }
+    const int chunk = chunk_sweeps(T, iters);
+    const int chunks = (iters + chunk - 1) / chunk;
+    MSM_TRY(s.sched.upload_vec(rec, ctx));
+    MSM_TRY(s.level_off.upload_vec(sch.level_off, ctx));
+    MSM_TRY(s.labeling.upload(labeling, (size_t)N, ctx));
+    if (s.prop.ensure((size_t)chunk * T) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * (size_t)chunk * T);
+    while (s.ev.size() < 2 * (size_t)chunks) {
+        hipEvent_t e;
+        MSM_HIP(hipEventCreate(&e));
+        s.ev.push_back(e);
+    }
+    McmcArgs a;
+    a.U = d_U;
+    a.tc = d_tc;
+    a.sched = s.sched.p;
+    a.level_off = s.level_off.p;
+    a.prop = s.prop.p;
+    a.labeling = s.labeling.p;
+    a.N = N;
+    a.L = L;
+    a.T = T;
+    a.levels = sch.levels();
+    a.status = ctx->d_status;
+    McmcProposals proposals(seed, mcparam, L);
+    std::vector<uint16_t> buf((size_t)chunk * T);
+    double draw_ms = 0.0;
+    // a chunk in the kernel's order: the stream is drawn in visit order, and the label of triplet t goes to t's place in the schedule
+    auto draw = [&](int sweeps) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int sw = 0; sw < sweeps; ++sw) {
+            uint16_t *row = buf.data() + (size_t)sw * T;
+            for (int t = 0; t < T; ++t) row[(size_t)pos[(size_t)t]] = (uint16_t)proposals.next();
+        }
+        draw_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    draw(std::min(chunk, iters));
+    for (int k = 0, done = 0; k < chunks; ++k) {
+        const int sweeps = std::min(chunk, iters - done);
+        // behind the previous chunk's kernel on the stream: the one device buffer is free when this copy runs; buf is consumed on return
+        MSM_TRY(stage_h2d(ctx, s.prop.p, buf.data(), sizeof(uint16_t) * (size_t)sweeps * T));
+        a.sweeps = sweeps;
+        MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
+        MSM_TRY(launch_mcmc_sweeps(ctx, a));
+        MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
+        done += sweeps;
+        if (done < iters) draw(std::min(chunk, iters - done));  // while the device walks chunk k
+    }
+    MSM_TRY(s.labeling.download(labeling, (size_t)N, ctx));
+    MSM_TRY(check_status(ctx, "msm_mcmc_optimise_gpu"));
+    double kernel_ms = 0.0;
+    for (int k = 0; k < chunks; ++k) {
+        float ms = 0.f;
+        MSM_HIP(hipEventElapsedTime(&ms, s.ev[2 * (size_t)k], s.ev[2 * (size_t)k + 1]));
+        kernel_ms += ms;
+    }
+    s.stats[0] = kernel_ms;
+    s.stats[1] = (double)iters * sch.levels();
+    s.stats[2] = draw_ms;
+    s.stats[3] = chunks;
+    s.stats[4] = sch.levels();
+    s.stats[5] = sch.widest();
+    return MSM_OK;
+}
+
+}  // namespace msm
+
+extern "C" {
+
+int msm_mcmc_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
+                          int32_t iters, uint64_t seed, int32_t *labeling) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: null context");
+    if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
+    MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
+    if (iters == 0 || T == 0) return MSM_OK;
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    McmcScratch &s = mcmc_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L;
+    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
+    if (s.tc.ensure(ntc) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
+    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
+    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
+    return mcmc_run_device(ctx, s.U.p, s.tc.p, triplets, N, L, T, mcparam, iters, seed, labeling);
+}
+
+int msm_mcmc_gpu_stats(msm_ctx *ctx, double stats[6]) {
+    if (!ctx || !stats) return fail(MSM_ERR_INVALID, "msm_mcmc_gpu_stats: null argument");
+    std::memcpy(stats, mcmc_scratch(ctx).stats, sizeof(double) * 6);
+    return MSM_OK;
+}
+
+int msm_mcmc_proposals(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, int32_t chunk_sweeps, uint16_t *out) {
+    if (!out || L <= 0 || T < 0 || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals: bad arguments");
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    McmcProposals proposals(seed, mcparam, L);
+    const int chunk = chunk_sweeps > 0 ? chunk_sweeps : std::max(sweeps, 1);
+    for (int done = 0; done < sweeps; done += chunk) {
+        const int n = std::min(chunk, sweeps - done);
+        proposals.fill(out + (size_t)done * T, (size_t)n * T);
+    }
+    return MSM_OK;
+}
+
+int msm_mcmc_schedule(const int32_t *triplets, int32_t N, int32_t T, int32_t *level, int32_t *order, int32_t *level_off, int32_t *levels) {
+    if (N <= 0 || T < 0 || (T > 0 && !triplets)) return fail(MSM_ERR_INVALID, "msm_mcmc_schedule: bad arguments");
+    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
+        if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
+    McmcSchedule s;
+    mcmc_build_schedule(triplets, N, T, s);
+    if (level) std::copy(s.level.begin(), s.level.end(), level);
+    if (order) std::copy(s.order.begin(), s.order.end(), order);
+    if (level_off) std::copy(s.level_off.begin(), s.level_off.end(), level_off);
+    if (levels) *levels = s.levels();
+    return MSM_OK;
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 #include "devbuf.hpp"
 #include "host_parallel.hpp"
 #include "kernels.hpp"
+#include "mcmc.hpp"
 
 using namespace msm;
 
@@ -151,19 +152,13 @@ int msm_variance_normalise(double *data, int32_t D, int32_t V, const double *exc
 int msm_mcmc_optimise(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
                       int32_t iters, uint64_t seed, int32_t *labeling) {
     if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
-    for (int i = 0; i < N; ++i)
-        if (labeling[i] < 0 || labeling[i] >= L) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: label of node %d out of range", i);
-    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
-        if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
-    std::mt19937 gen((std::mt19937::result_type)seed);
-    std::geometric_distribution<> distribution(mcparam);
+    MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
+    McmcProposals proposals(seed, mcparam, L);  // the stream the GPU sweeps consume too (mcmc.hpp)
     const size_t L2 = (size_t)L * L, L3 = L2 * L;
     double costs[8];
     for (int i = 0; i < iters; ++i)
         for (int t = 0; t < T; ++t) {
-            int label;
-            do { label = distribution(gen); } while (label >= L);
+            const int label = proposals.next();
             const int node[3] = {triplets[3 * t], triplets[3 * t + 1], triplets[3 * t + 2]};
             const int cur[3] = {labeling[node[0]], labeling[node[1]], labeling[node[2]]};
             const double *tc = tcosts + (size_t)t * L3;

@@ -27,8 +27,11 @@ EXCL_WITH_WEIGHTINGS = ("--excl together with --inweight and --refweight is not 
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, mcmc_gpu=False):
+        """mcmc_gpu: the MCMC branch of run_discrete_level leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead
+        of fetching them for the host optimiser -- the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)"""
         self.ctx = ctx
+        self.mcmc_gpu = bool(mcmc_gpu)
 
     # --- meshes
     def icosphere(self, order):
@@ -227,6 +230,9 @@ class _ProductCost:
         """the NEXT triplet_octets call will ask for (labeling, label) unless the solve in between changes a label: let its kernel run meanwhile
         (msm_cost_triplet_octets_prefetch into the buffer that call will use)"""
         self.cf.prefetchTripletOctets(labeling, label, self._octet_buffers()[self._turn])
+
+    def mcmc_optimise(self, labeling, mcparam, iters, seed):
+        return self.cf.mcmc_optimise(labeling, mcparam=mcparam, iters=iters, seed=seed)
 
     def total(self, labeling):
         return self.cf.evaluateTotalCostSum(labeling)[0]
@@ -475,7 +481,8 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
         else:
             cost.set_triplets(triplets)
         m_iter += 1
-        unary = timed("unary_table", cost.unary_table)
+        mcmc_gpu = optimiser == "mcmc" and getattr(ops, "mcmc_gpu", False)  # both tables stay on the device (msm_cost_mcmc_optimise)
+        unary = None if mcmc_gpu else timed("unary_table", cost.unary_table)
         labeling = np.zeros(len(cp_xyz), dtype=np.int32)  # resetLabeling
         if optimiser == "fusion":  # --- Fusion::optimize: computeUnaryCosts, then per label step the 8 T combinations
             nodes = np.arange(len(cp_xyz))
@@ -499,6 +506,8 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
         elif pairwise:  # --- FastPD: computeUnaryCosts, computePairwiseCosts, FPD::FastPD(model, 100) (M/mesh_registration.cpp:182-188)
             paircosts = timed("pairwise_table", cost.pairwise_table)
             labeling = timed("optimiser", ops.pairwise_solve, unary, paircosts, pairs, 100)
+        elif mcmc_gpu:  # --- MCMC with the tables and the sweeps on the device: the labeling of the branch below, bit for bit
+            labeling = timed("optimiser", cost.mcmc_optimise, labeling, mcparam, mciters, seed + it)
         else:  # --- MCMC: computeUnaryCosts, computeTripletCosts, optimise
             tcosts = timed("triplet_table", cost.triplet_table)
             labeling = timed("optimiser", ops.mcmc, unary, tcosts, triplets, labeling, mcparam, mciters, seed + it)

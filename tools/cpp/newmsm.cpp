@@ -199,7 +199,11 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const bool rigid = rigid_env && std::string(rigid_env) == "on";
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
     IntensityNorm inorm;  // --IN / --INc: taken when MSMHIP_HISTMATCH=on, refused otherwise
-    const std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr);
+    std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr);
+    const char *mcmc_env = std::getenv("MSMHIP_MCMC");  // "gpu": the --dopt=MCMC levels keep both cost tables on the device and run the sweeps there
+    const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
+    if (mcmc_gpu)
+        for (LevelSpec &lv : levels) lv.options.mcmc_gpu = true;
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
@@ -221,6 +225,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     Context ctx(device);
     if (o.has("verbose"))
         std::cout << "This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
+    if (o.has("verbose") && mcmc_gpu) std::cout << "MCMC sweeps on the GPU." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,
                                                     anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr,
                                                     o.get("trans").empty() ? nullptr : &trans, excl, inorm);

@@ -127,6 +127,11 @@ def histmatch_enabled():
     return os.environ.get("MSMHIP_HISTMATCH", "") == "on"
 
 
+def mcmc_gpu_enabled():
+    """MSMHIP_MCMC=gpu: the --dopt=MCMC levels keep both cost tables on the device and run the optimiser's sweeps there (the same labelings)"""
+    return os.environ.get("MSMHIP_MCMC", "") == "gpu"
+
+
 def discrete_levels(cfg, D, anat=False, groupwise=False):
     levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
                                                         **(dict(histmatch=True) if histmatch_enabled() else {}))
@@ -215,7 +220,9 @@ def main(argv):
     ctx = M.Context(a.device)
     if a.verbose:
         print("This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+        if mcmc_gpu_enabled():
+            print("MCMC sweeps on the GPU.")
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled()), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])

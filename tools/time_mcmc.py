@@ -1,0 +1,119 @@
+"""tools/time_mcmc.py [--sweeps N] [--repeats R] [--out FILE] -- the Monte Carlo optimiser (MCMC::optimise, M/mcmc_opt.h:31-134) on the host against its
+sweeps on the MI355X, over the unary and triplet tables of BASELINE config 2 (pairwise sulc, ico6 data, ico4 control grid, 19 labels) and of an ico3
+control grid.  In one process, alternating: the host path (msm_cost_unary_table + msm_cost_triplet_table into pinned memory + msm_mcmc_optimise) and
+msm_cost_mcmc_optimise (both tables stay on the device).  A time is reported only when the two labellings are equal.  Per grid, medians of the repeats with
+min and max: ms per sweep either way, us per level by the HIP events around the sweep kernels, the proposal stream's draws per second on the host alone,
+the time the host path spends computing and fetching the triplet table, and the time the device path spends on its two tables.  Prints one JSON object."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import newmsm_amd as M  # noqa: E402
+from newmsm_amd import api, problem  # noqa: E402
+
+
+def spread(values):
+    v = sorted(values)
+    return dict(median=v[len(v) // 2], min=v[0], max=v[-1])
+
+
+def measure(ctx, cp_order, sweeps, repeats, mcparam, seed):
+    inp = problem.pairwise_inputs(6, cp_order, D=1)
+    cf, keep = problem.build_cost(ctx, inp, kind="univariate")
+    cf.get_source_data()
+    keep["target"].prepare_search(wait=True)
+    triplets = inp["triplets"]
+    start = np.zeros(cf.N, dtype=np.int32)
+    kw = dict(mcparam=mcparam, seed=seed)
+
+    def host(iters):
+        t0 = time.perf_counter()
+        U = cf.computeUnaryCosts()
+        t1 = time.perf_counter()
+        tc = cf.computeTripletCosts(pinned=True)
+        t2 = time.perf_counter()
+        lab = api.mcmc_optimise(U, tc, triplets, start, iters=iters, **kw)
+        t3 = time.perf_counter()
+        return lab, dict(unary_ms=(t1 - t0) * 1e3, triplet_fetch_ms=(t2 - t1) * 1e3, sweeps_ms=(t3 - t2) * 1e3, total_ms=(t3 - t0) * 1e3)
+
+    def device(iters):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        lab = cf.mcmc_optimise(start, iters=iters, **kw)
+        t1 = time.perf_counter()
+        return lab, dict(total_ms=(t1 - t0) * 1e3, **api.mcmc_gpu_stats(ctx))
+
+    for _ in range(2):  # warm-up of every shape the timed window uses: code objects, staging blocks, the pinned table buffer
+        host(20), device(20)
+    runs_h, runs_d, tables_ms, equal = [], [], [], True
+    for _ in range(repeats):
+        lab_h, h = host(sweeps)
+        lab_d, d = device(sweeps)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        cf.mcmc_optimise(start, iters=0, **kw)  # the two tables alone: no sweep is run
+        tables_ms.append((time.perf_counter() - t0) * 1e3)
+        equal = equal and np.array_equal(lab_h, lab_d)
+        runs_h.append(h), runs_d.append(d)
+    draws = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        api.mcmc_proposals(cf.L, mcparam, seed, cf.T, sweeps)
+        draws.append(sweeps * cf.T / (time.perf_counter() - t0))
+    out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, sweeps=sweeps, repeats=repeats, mcparam=mcparam, triplet_table_MB=cf.T * cf.L ** 3 * 8 / 1e6,
+               labellings_equal=bool(equal), labels_in_result=int(len(np.unique(lab_h))), levels_per_sweep=runs_d[0]["levels_per_sweep"],
+               widest_level=runs_d[0]["widest_level"], chunks=runs_d[0]["chunks"])
+    cf.close()
+    if not equal:
+        return out  # no time is reported for a result that is not the host's
+    out.update(
+        host_ms_per_sweep=spread([r["sweeps_ms"] / sweeps for r in runs_h]),
+        host_triplet_table_fetch_ms=spread([r["triplet_fetch_ms"] for r in runs_h]),
+        host_unary_table_ms=spread([r["unary_ms"] for r in runs_h]),
+        host_total_ms=spread([r["total_ms"] for r in runs_h]),
+        gpu_ms_per_sweep=spread([(r["total_ms"] - t) / sweeps for r, t in zip(runs_d, tables_ms)]),
+        gpu_kernel_ms_per_sweep=spread([r["kernel_ms"] / sweeps for r in runs_d]),
+        gpu_us_per_level=spread([1e3 * r["kernel_ms"] / r["levels"] for r in runs_d]),
+        gpu_draw_ms_per_sweep=spread([r["draw_ms"] / sweeps for r in runs_d]),
+        gpu_tables_ms=spread(tables_ms),
+        gpu_total_ms=spread([r["total_ms"] for r in runs_d]),
+        proposal_draws_per_s=spread(draws),
+    )
+    # "faster" only where the slower path's fastest run is above the faster path's slowest
+    out["gpu_faster_total"] = out["gpu_total_ms"]["max"] < out["host_total_ms"]["min"]
+    out["gpu_faster_sweeps"] = out["gpu_ms_per_sweep"]["max"] < out["host_ms_per_sweep"]["min"]
+    bounds = dict(levels=out["gpu_kernel_ms_per_sweep"]["median"], proposals=out["gpu_draw_ms_per_sweep"]["median"], tables=out["gpu_tables_ms"]["median"] / sweeps)
+    out["gpu_bound_by"] = max(bounds, key=bounds.get)
+    # arithmetic, not a measurement: the reference's default --mciters=100000 at the per-sweep figures above
+    out["arithmetic_s_per_100000_sweeps"] = dict(host=out["host_ms_per_sweep"]["median"] * 100, gpu=out["gpu_ms_per_sweep"]["median"] * 100)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sweeps", type=int, default=2000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--mcparam", type=float, default=0.8)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if M.device_count() < 1:
+        raise SystemExit("time_mcmc.py: no HIP device is visible (nothing is measured without one)")
+    ctx = M.Context(0)
+    result = dict(tool="tools/time_mcmc.py", grids=[measure(ctx, cp, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
+    ctx.close()
+    text = json.dumps(result, indent=1)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
