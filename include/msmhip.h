@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 12  /* 12: msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise / msm_mcmc_gpu_stats / msm_mcmc_proposals / msm_mcmc_schedule added (the Monte Carlo optimiser's sweeps on the GPU; additive, the version stays).  12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 12  /* 12: msm_group_pair_route / msm_group_pair_launch added (which path of the pair-cost kernel a query takes, and what the group's launch was decided to be; additive, the version stays).  12: msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise / msm_mcmc_gpu_stats / msm_mcmc_proposals / msm_mcmc_schedule added (the Monte Carlo optimiser's sweeps on the GPU; additive, the version stays).  12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -624,6 +624,33 @@ int msm_group_fusion_move_dev(msm_group *g, const int32_t *labeling, int32_t lab
  * step's GPU time in milliseconds (-1 when none was timed). */
 int msm_group_time_moves(msm_group *g, int enable);
 int msm_group_move_kernels_ms(msm_group *g, double *ms);
+/* What the pair-cost kernel (k_group_pairwise) does with a query, for the tests that steer it.
+ *   msm_group_pair_route   the code path of ONE query whose patches hold cntA and cntB entries, with D feature rows, the measure and `lanes` lanes per query
+ *                          (16 or 32 for SSD / correlation, 64 for DICE / genDICE) -- the function the kernel itself calls; pure host arithmetic, no
+ *                          context, no device.  route[MSM_PAIR_ROUTE_FAST]: everything in registers, else the general path; [_PADDED]: the length B's
+ *                          list is padded to in LDS (64 / 128 / 256; 0 when it is not staged); [_STAGED]: B's ids in LDS, else read from memory;
+ *                          [_BEYOND]: general path with entries of A past the 64 rounds x lanes membership bits, looked up again in every pass.
+ *   msm_group_pair_launch  what msm_group_finalize decided for this group and what a pair evaluation would be handed NOW; host bookkeeping, no kernel and
+ *                          no synchronisation.  out[MSM_PAIR_LAUNCH_LANES]: lanes per query; [_PATCH_MAX]: the largest patch; [_NPATCH] / [_NSMALL]: the
+ *                          patches counted and those of at most 80 entries (16 lanes when 10 nsmall >= 9 npatch, unless MSMHIP_GROUP_PAIR_LANES says
+ *                          otherwise); [_DICE_LDS]: static plus dynamic LDS bytes of the DICE launch (0 for the other measures); [_DICE_FIT]: 0 it runs
+ *                          as it is, 1 the kernel's attribute is raised first (more than 64 KB), 2 refused (more than 160 KB: every pair evaluation fails
+ *                          with MSM_ERR_CAPACITY before anything is queued, the group stays usable otherwise); [_PVAL] / [_DIR]: whether the value copies
+ *                          and the patch directory serve the WHOLE pair list (a group with imported subjects builds them at its first label step). */
+#define MSM_PAIR_ROUTE_FAST 0
+#define MSM_PAIR_ROUTE_PADDED 1
+#define MSM_PAIR_ROUTE_STAGED 2
+#define MSM_PAIR_ROUTE_BEYOND 3
+#define MSM_PAIR_LAUNCH_LANES 0
+#define MSM_PAIR_LAUNCH_PATCH_MAX 1
+#define MSM_PAIR_LAUNCH_NPATCH 2
+#define MSM_PAIR_LAUNCH_NSMALL 3
+#define MSM_PAIR_LAUNCH_DICE_LDS 4
+#define MSM_PAIR_LAUNCH_DICE_FIT 5
+#define MSM_PAIR_LAUNCH_PVAL 6
+#define MSM_PAIR_LAUNCH_DIR 7
+int msm_group_pair_route(int32_t cntA, int32_t cntB, int32_t D, int32_t simmeasure, int32_t lanes, int32_t route[4]);
+int msm_group_pair_launch(msm_group *g, int64_t out[8]);
 
 
 /* ------------------------------------------------------------------------------------------------

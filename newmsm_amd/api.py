@@ -1225,6 +1225,26 @@ class DiscreteGroupCostFunction:
         check(lib().msm_group_pairwise_batch(self.h, pp, pa, pb, len(p), out.ctypes.data_as(c_dp)))
         return out
 
+    PAIR_ROUTES = ("fast64", "fast128", "fast256", "staged", "staged_beyond", "unstaged", "unstaged_beyond")
+    DICE_FIT = ("default", "attribute", "refused")
+
+    @staticmethod
+    def pair_route(cntA, cntB, D, simmeasure, lanes):
+        """msm_group_pair_route: the path k_group_pairwise takes for a query over patches of cntA and cntB entries (the function the kernel calls; host
+        arithmetic, no GPU): dict(fast, padded, staged, beyond, name), name one of PAIR_ROUTES"""
+        r = (C.c_int32 * 4)()
+        check(lib().msm_group_pair_route(int(cntA), int(cntB), int(D), int(simmeasure), int(lanes), r))
+        fast, padded, staged, beyond = bool(r[0]), int(r[1]), bool(r[2]), bool(r[3])
+        name = "fast%d" % padded if fast else ("staged" if staged else "unstaged") + ("_beyond" if beyond else "")
+        return dict(fast=fast, padded=padded, staged=staged, beyond=beyond, name=name)
+
+    def pair_launch(self):
+        """msm_group_pair_launch: what finalize() decided for this group's pair costs and what an evaluation would be handed now (host bookkeeping)"""
+        o = (C.c_int64 * 8)()
+        check(lib().msm_group_pair_launch(self.h, o))
+        return dict(lanes=int(o[0]), patch_max=int(o[1]), npatch=int(o[2]), nsmall=int(o[3]), dice_lds=int(o[4]), dice_fit=self.DICE_FIT[o[5]], pval=bool(o[6]),
+                    dir=bool(o[7]))
+
     def computeTripletCost(self, t, la, lb, lc):
         t_, pt = _i(np.atleast_1d(t))
         a, pa = _i(np.atleast_1d(la))

@@ -37,6 +37,7 @@ struct msm_group {
     bool rgrid_valid = false;  // the longest patch index list of a subject so far: the next one's is compacted before the look at its counts
     int patch_max = 0;  // largest patch of any subject (msm_group_finalize)
     int pair_lanes = 32;  // lanes per query of k_group_pairwise: 16 when nearly all patches fit a quarter wavefront's registers (msm_group_finalize)
+    int64_t npatch = 0, nsmall = 0;  // the patches msm_group_finalize counted, and those of at most kPairSmallPatch entries (msm_group_pair_launch)
     msm_group_params p{};
     int S = 0;
     msm_mesh *tmpl = nullptr;
@@ -138,6 +139,7 @@ struct msm_group {
     DevBuf<double> d_cp_soa, d_rot, d_spacing, d_labels3;  // control points by component; ROT per node; spacing per node; labels 3 x L
     DevBuf<int2> d_forest_info;
     int64_t npairs = 0;                  // N * S * (S - 1) / 2; the host copy of the list (pairs) is fetched when asked for
+    bool pval_serves_all() const { return pval_ready && pval_p0 == 0 && pval_p1 == npairs; }  // pval / dir cover every pair: batch evaluations may use them
     bool moved_on_host = false;          // g->moved mirrors d_moved (fetched for the rare host decisions of subject_patches)
     // the (current, current) pair costs of the last label step and the labeling they were computed for (GroupArgs::move_e00)
     DevBuf<double> d_e00;
@@ -335,7 +337,7 @@ int group_args(msm_group *g, GroupArgs &a) {
     a.pptr = g->d_pptrp.p;
     a.pidx = g->d_pidxp.p;
     a.F = g->d_Fp.p;
-    const bool pval_all = g->pval_ready && g->pval_p0 == 0 && g->pval_p1 == g->npairs;  // (a slice's copies serve that slice's label steps only: group_move_compute)
+    const bool pval_all = g->pval_serves_all();  // (a slice's copies serve that slice's label steps only: group_move_compute)
     a.pval = pval_all ? const_cast<const double *const *>(g->d_pvalp.p) : nullptr;
     a.dir = pval_all ? g->d_patch_dir.p : nullptr;
     a.mask = g->mask.empty() ? nullptr : g->d_mask.p;
@@ -362,6 +364,13 @@ int group_args(msm_group *g, GroupArgs &a) {
     a.patch_cap = g->patch_max;
     a.pair_lanes = g->pair_lanes;
     a.status = g->ctx->d_status;
+    return MSM_OK;
+}
+
+// a DICE group whose largest patch does not fit the pair kernel's LDS: said before a pair evaluation queues anything (launch_group_pairwise would say it too)
+int pair_refusal(const msm_group *g) {
+    if ((g->p.simmeasure == 4 || g->p.simmeasure == 5) && group_dice_lds(g->patch_max, nullptr, nullptr) == 2)
+        return fail(MSM_ERR_CAPACITY, "group patch of %d entries does not fit in LDS", g->patch_max);
     return MSM_OK;
 }
 
@@ -1396,6 +1405,7 @@ int msm_group_finalize(msm_group *g) {
     // a quarter wavefront per pair cost when (nearly) all patches fit its registers: four queries share a wavefront's instruction stream and latency
     // instead of two (label step 12.5 -> 9.5 ms at ico6 / ico4, patches of ~65 entries); the others take the general path, at half the lanes
     g->pair_lanes = (npatch > 0 && 10 * nsmall >= 9 * npatch) ? 16 : 32;
+    g->npatch = npatch, g->nsmall = nsmall;
     if (const char *e = std::getenv("MSMHIP_GROUP_PAIR_LANES")) g->pair_lanes = std::atoi(e) == 16 ? 16 : 32;
     // The patch entries' values beside their ids (GroupArgs::pval), for the register path of k_group_pairwise (D <= 2): one launch over all subjects, whether
     // they were set up here or imported -- 3.2 GB written at S = 64, ico6 / ico4 (0.5 ms), and the label steps' value gathers by vertex id become a coalesced
@@ -1431,6 +1441,33 @@ int msm_group_finalize(msm_group *g) {
         fprintf(stderr, "  group patches: %lld, %.1f %% of them with at most %d entries, largest %d -> %d lanes per pair cost\n", (long long)npatch,
                 npatch ? 100.0 * (double)nsmall / (double)npatch : 0.0, kPairSmallPatch, g->patch_max, g->pair_lanes);
     g->ready = true;
+    return MSM_OK;
+}
+
+int msm_group_pair_route(int32_t cntA, int32_t cntB, int32_t D, int32_t simmeasure, int32_t lanes, int32_t route[4]) {
+    if (!route || cntA < 0 || cntB < 0 || D < 1 || (lanes != 16 && lanes != 32 && lanes != 64) || (simmeasure != 1 && simmeasure != 2 && simmeasure != 4 && simmeasure != 5) ||
+        ((simmeasure == 4 || simmeasure == 5) != (lanes == 64)))
+        return fail(MSM_ERR_INVALID, "msm_group_pair_route: bad arguments");
+    const GroupPairRoute r = group_pair_route(cntA, cntB, D, simmeasure, lanes);
+    route[MSM_PAIR_ROUTE_FAST] = r.fast, route[MSM_PAIR_ROUTE_PADDED] = r.padded, route[MSM_PAIR_ROUTE_STAGED] = r.staged, route[MSM_PAIR_ROUTE_BEYOND] = r.beyond;
+    return MSM_OK;
+}
+
+int msm_group_pair_launch(msm_group *g, int64_t out[8]) {
+    if (!g || !out) return fail(MSM_ERR_INVALID, "msm_group_pair_launch: null argument");
+    if (!g->ready) return fail(MSM_ERR_STATE, "msm_group: msm_group_finalize() must be called first");
+    const bool dice = g->p.simmeasure == 4 || g->p.simmeasure == 5;
+    size_t total = 0;
+    const int fit = dice ? group_dice_lds(g->patch_max, &total, nullptr) : 0;
+    const bool pval_all = g->pval_serves_all();  // what group_args hands the kernel
+    out[MSM_PAIR_LAUNCH_LANES] = dice ? 64 : g->pair_lanes;
+    out[MSM_PAIR_LAUNCH_PATCH_MAX] = g->patch_max;
+    out[MSM_PAIR_LAUNCH_NPATCH] = g->npatch;
+    out[MSM_PAIR_LAUNCH_NSMALL] = g->nsmall;
+    out[MSM_PAIR_LAUNCH_DICE_LDS] = (int64_t)total;
+    out[MSM_PAIR_LAUNCH_DICE_FIT] = fit;
+    out[MSM_PAIR_LAUNCH_PVAL] = pval_all;
+    out[MSM_PAIR_LAUNCH_DIR] = pval_all;
     return MSM_OK;
 }
 
@@ -1516,6 +1553,7 @@ int msm_group_pairwise_batch(msm_group *g, const int32_t *pair, const int32_t *l
     if (n == 0) return MSM_OK;
     GroupArgs a;
     int st = group_args(g, a);
+    if (!st) st = pair_refusal(g);
     if (st) return st;
     const int P = (int)g->npairs;
     for (int i = 0; i < n; ++i)
@@ -1596,6 +1634,7 @@ static int group_move_compute_untimed(msm_group *g, const int32_t *labeling, int
                               double *quads_dev, double *octets_dev, const char *who, const std::function<int(int, int64_t, int64_t)> *after_piece = nullptr) {
     GroupArgs a;
     int st = group_args(g, a);
+    if (!st && pair1 > pair0) st = pair_refusal(g);
     if (st) return st;
     const int nodes = g->S * g->N;
     if (label < 0 || label >= g->L) return fail(MSM_ERR_INVALID, "%s: label %d out of range", who, label);

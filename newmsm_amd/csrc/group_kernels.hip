@@ -87,8 +87,6 @@ __device__ __forceinline__ void half_sums(double (&v)[N], int lane) {
     for (int k = 0; k < N; ++k) v[k] = half_get(y, k);
 }
 
-constexpr int kGroupStage = 256;  // ids of patch B staged in LDS per wavefront
-
 // a pointer the compiler knows to point into device memory (address space 1)
 template <class T>
 using GlobalPtr = const T __attribute__((address_space(1))) *;
@@ -257,17 +255,19 @@ __global__ __launch_bounds__(256) void k_group_pairwise(GroupArgs a, const int *
     __shared__ int s_ids[kPerBlock][kGroupStage + 8];
     int *stage = s_ids[slot];
     // Staged up to the next of 64 / 128 / 256 entries, the tail filled with INT_MAX: the fast path's search then walks a power of two with no bounds to check.
-    const bool staged = cntB <= kGroupStage;
-    const int padded = cntB <= 64 ? 64 : (cntB <= 128 ? 128 : 256);
+    const GroupPairRoute route = group_pair_route(cntA, cntB, a.D, a.simmeasure, kLanes);  // (kernels.hpp: the one place these decisions are taken)
+    static_assert(sizeof(s_ids) == sizeof(int) * kPerBlock * (kGroupStage + 8), "group_dice_lds counts these bytes");
+    const bool staged = route.staged;
+    const int padded = route.padded;
     // The usual case -- patches of up to 5 (4) entries per lane, one or two feature rows, correlation or SSD -- keeps everything in registers (below).  Its
     // loads are requested HERE, all at once and unconditionally (indices clamped into the patch instead of branched around): patch A's ids, patch A's
     // values from the entry-major copy beside them (GroupArgs::pval) and the first 64 ids of patch B.  Round 5: B's ids used to be fetched and written to
     // LDS one round after the other (load, wait, write, four times), and A's ids only after that -- five dependent memory phases in front of the search
     // where one does; A's values were ten gathers by vertex id behind the search.
-    constexpr int kRounds = kLanes == 16 ? kPairSmallPatch / 16 : 4;  // entries per lane kept in registers: patches of up to 80 / 128 entries (6 and 8
+    constexpr int kRounds = group_pair_rounds(kLanes);                // entries per lane kept in registers: patches of up to 80 / 128 entries (6 and 8
                                                                       // rounds of sixteen lanes: 89 / 109 registers, 10.2 / 12.1 ms per label step against 9.5)
     constexpr int kQ = kLanes == 64 ? 32 : kLanes;                    // (the fast path is compiled for 32 and 16 lanes per query)
-    const bool fast = !kDice && staged && cntA <= kRounds * kLanes && a.D <= 2 && a.simmeasure != 4 && a.simmeasure != 5;
+    const bool fast = !kDice && route.fast;
     const bool compact = fast && a.pval != nullptr;
     const GlobalPtr<double> PA = !compact ? GlobalPtr<double>(nullptr) : (a.dir ? dirA : as_global(a.pval[sa]) + (size_t)a.D * ba);
     const GlobalPtr<double> PB = !compact ? GlobalPtr<double>(nullptr) : (a.dir ? dirB : as_global(a.pval[sb]) + (size_t)a.D * bb);
@@ -462,10 +462,10 @@ __global__ __launch_bounds__(256) void k_group_pairwise(GroupArgs a, const int *
     int common = 0;
     for (int r = 0, i = lane; i < cntA; i += kLanes, ++r)
         if (in_b(ia[i])) {
-            if (r < 64) member |= 1ull << r;
+            if (r < kPairMemberRounds) member |= 1ull << r;
             ++common;
         }
-    const auto is_member = [&](int r, int i) { return r < 64 ? (member >> r & 1ull) != 0 : in_b(ia[i]); };
+    const auto is_member = [&](int r, int i) { return r < kPairMemberRounds ? (member >> r & 1ull) != 0 : in_b(ia[i]); };
     if (kDice && cntA > 64 * 64) raise_status(a.status, MSM_ERR_CAPACITY);
     const int ncommon = (int)lanes_sum<kLanes>((double)common);
     double cost = 0.0;
@@ -732,12 +732,26 @@ int launch_group_centres(msm_ctx *ctx, const double *d_moved_subject, const doub
     return MSM_OK;
 }
 
+// A workgroup of gfx950 can address 160 KB of LDS, static variables included; a kernel whose LDS passes 64 KB needs its attribute raised first.  The DICE
+// kernel's four wavefronts each hold two rows of patch_cap doubles beside the staged ids of B (s_ids: 4 224 bytes): 64 patch_cap + 4 224 bytes, so patches of
+// up to 958 entries run as they are, up to 2 494 with the attribute, and a larger one is refused.  The attribute is decided from the SUM: the documented rule
+// bounds static plus dynamic bytes by the opt-in limit, and whether the runtime's default allowance counts the static bytes is not documented -- raising the
+// attribute where only the sum passes 64 KB (959 .. 1 024 entries) is correct under either reading.
+int group_dice_lds(int patch_cap, size_t *total, size_t *dynamic) {
+    constexpr size_t kStatic = sizeof(int) * 4 * (kGroupStage + 8), kLdsWorkgroup = 160 * 1024, kLdsDefault = 64 * 1024;
+    const size_t dyn = sizeof(double) * 4 * 2 * (size_t)std::max(patch_cap, 1);
+    if (total) *total = dyn + kStatic;
+    if (dynamic) *dynamic = dyn;
+    return dyn + kStatic > kLdsWorkgroup ? 2 : (dyn + kStatic > kLdsDefault ? 1 : 0);
+}
+
 int launch_group_pairwise(msm_ctx *ctx, const GroupArgs &a, const int *qp, const int *qa, const int *qb, int n, double *out) {
     if (n <= 0) return MSM_OK;
     if (a.simmeasure == 4 || a.simmeasure == 5) {
-        const size_t lds = sizeof(double) * 4 * 2 * (size_t)std::max(a.patch_cap, 1);  // <= 128 KB: patches hold at most 2048 entries
-        if (lds > 160 * 1024) return fail(MSM_ERR_CAPACITY, "group patch of %d entries does not fit in LDS", a.patch_cap);
-        if (lds > 64 * 1024) MSM_HIP(hipFuncSetAttribute((const void *)k_group_pairwise<true, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        size_t lds = 0;
+        const int fit = group_dice_lds(a.patch_cap, nullptr, &lds);
+        if (fit == 2) return fail(MSM_ERR_CAPACITY, "group patch of %d entries does not fit in LDS", a.patch_cap);
+        if (fit == 1) MSM_HIP(hipFuncSetAttribute((const void *)k_group_pairwise<true, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((k_group_pairwise<true, 64>), dim3((n + 3) / 4), dim3(256), lds, ctx->stream, a, qp, qa, qb, n, out);
     } else {
         // half a wavefront per query: two queries share a wavefront's latency; a quarter when the group's patches are small enough (a.pair_lanes)

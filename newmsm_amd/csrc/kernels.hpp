@@ -277,6 +277,28 @@ struct GroupArgs {
     int pair_lanes;              // 32 or 16 lanes per pair cost (group.cpp: msm_group_finalize)
     int *status;
 };
+// Which of k_group_pairwise's code paths a query takes -- a function of the two patches' lengths, the feature rows, the measure and the lanes per query
+// (16 / 32: GroupArgs::pair_lanes; 64: DICE) and of nothing else.  The kernel calls it, msm_group_pair_route shows it to the tests.
+constexpr int kGroupStage = 256;       // ids of patch B staged in LDS per query
+constexpr int kPairMemberRounds = 64;  // rounds of A's entries whose membership the general path keeps as a bit per lane
+struct GroupPairRoute {
+    int fast;    // everything in registers; else the general path
+    int padded;  // staged: entries the list of B is padded to in LDS (64 / 128 / 256: the length of the fast path's search); else 0
+    int staged;  // B's ids in LDS; else read from memory at every step of the search
+    int beyond;  // general path: A has entries past the membership bits, looked up again in every pass
+};
+__host__ __device__ constexpr int group_pair_rounds(int lanes) { return lanes == 16 ? kPairSmallPatch / 16 : 4; }  // entries per lane the fast path keeps in registers
+__host__ __device__ inline GroupPairRoute group_pair_route(int cntA, int cntB, int D, int simmeasure, int lanes) {
+    GroupPairRoute r;
+    r.staged = cntB <= kGroupStage;
+    r.padded = !r.staged ? 0 : (cntB <= 64 ? 64 : (cntB <= 128 ? 128 : 256));
+    r.fast = (simmeasure == 1 || simmeasure == 2) && lanes <= 32 && r.staged && cntA <= group_pair_rounds(lanes) * lanes && D <= 2;
+    r.beyond = !r.fast && cntA > kPairMemberRounds * lanes;
+    return r;
+}
+// LDS of the DICE launch (k_group_pairwise<true, 64>) for a largest patch of patch_cap entries: *total = the kernel's static variables plus *dynamic, the
+// rows of common entries.  Returns 0: fits the 64 KB a kernel gets as it is; 1: its attribute is raised first; 2: beyond the 160 KB of a workgroup, refused.
+int group_dice_lds(int patch_cap, size_t *total, size_t *dynamic);
 // out[i], out[stride + i], out[2 * stride + i] (stride 0: V)
 int launch_rotate_to_label(msm_ctx *ctx, const double *d_xyz, int V, const double centre[3], const double label[3], double *d_out, size_t stride = 0);
 // all L labels in one launch (out 3 x (L * V), stride = L * V); d_rot9 (optional, V x 9 on the device): the vertices' rotation matrices from the host
