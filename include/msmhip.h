@@ -320,6 +320,22 @@ int msm_variance_normalise(double *data, int32_t D, int32_t V, const double *exc
  * their quantile; the others, and rows without counted values or without a range on either side, stay as they are.  out: n_src x D x Vs (may be src). */
 int msm_histogram_match(msm_ctx *ctx, int32_t n_src, int32_t D, int32_t Vs, const double *src, const double *src_excl, int32_t src_excl_rows,
                         int32_t Vt, const double *ref, const double *ref_excl, int32_t ref_excl_rows, double *out);
+typedef struct msm_level_features_params {
+    int32_t exclude;    /* masks exist: --excl, or the cut of --INc (M/featurespace.cpp:61) */
+    int32_t intensity;  /* --IN / --INc: data set i >= 1 matched to data set 0 (:76-78) */
+    int32_t varnorm;    /* --VN (:81-83) */
+    int32_t reserved;
+    double  thrl, thru; /* --cutthr */
+} msm_level_features_params;
+/* featurespace::initialise (M/featurespace.cpp:39-86) for n data sets on one level grid, in one call: per data set msm_create_exclusion (with
+ * p->exclude), msm_metric_resample onto the grid and msm_smooth_data on the grid (sigma[i] > 0), then over all of them msm_histogram_match of data
+ * sets 1 .. n-1 against data set 0 with the masks as they stand after smoothing (p->intensity, n > 1) and msm_variance_normalise (p->varnorm) -- the
+ * bytes that sequence of entry points gives, with everything but the variance recurrence queued on the device behind one upload per data set and
+ * in front of one download; the masked list surgery runs on the device too.  All meshes belong to one context.
+ * data[i]: D x V(in_mesh[i]) host rows.  sigma[i]: <= 0 means no smoothing.
+ * feat: n x D x V(grid).  mask: n x V(grid), required when p->exclude, else NULL.  A failed search fails the call as msm_metric_resample fails it. */
+int msm_level_features(msm_mesh *grid, int32_t n, msm_mesh *const *in_mesh, const double *const *data, int32_t D, const double *sigma,
+                       const msm_level_features_params *p, double *feat, double *mask);
 /* [host] MCMC::optimise M/mcmc_opt.h:31-134 over the tables of msm_cost_unary_table (L x N) and msm_cost_triplet_table
  * (T x L x L x L): `iters` sweeps over the triplets, each proposing one label drawn from std::geometric_distribution(mcparam)
  * (std::mt19937 seeded with `seed`; the reference seeds from std::random_device) and keeping the cheapest of the eight

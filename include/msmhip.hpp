@@ -417,6 +417,37 @@ inline Matrix histogram_match(Context &ctx, int n_src, int D, int Vs, const Matr
                               ref_excl ? ref_excl->data() : nullptr, ref_rows, out.data()));
     return out;
 }
+// msm_level_features: featurespace::initialise (M/featurespace.cpp:39-86) for n data sets (meshes[i], datas[i]: D x V(meshes[i])) on the level grid in ONE
+// call -- create_exclusion (exclude), metric_resample and smooth_data (sigmas[i] > 0) per data set, then histogram_match of data sets 1.. against data set 0
+// (intensity) and variance_normalise (varnorm): the bytes of those calls one after another.  masks: per data set V(grid) values, empty without exclude.
+struct LevelFeatures {
+    std::vector<Matrix> features;
+    std::vector<std::vector<double>> masks;
+};
+inline LevelFeatures level_features_batch(Mesh &grid, const std::vector<Mesh *> &meshes, const std::vector<const Matrix *> &datas, int D, const std::vector<double> &sigmas,
+                                          bool exclude, bool intensity, bool varnorm, double thrl = 0.0, double thru = 0.0001) {
+    const size_t n = meshes.size(), V = (size_t)grid.nvertices();
+    if (datas.size() != n || sigmas.size() != n) throw Error(MSM_ERR_INVALID, "level_features_batch: as many data sets and sigmas as meshes");
+    std::vector<msm_mesh *> handles;
+    std::vector<const double *> rows;
+    for (size_t i = 0; i < n; ++i) {
+        if (D > 0 && datas[i]->size() != (size_t)D * (size_t)meshes[i]->nvertices()) throw Error(MSM_ERR_INVALID, "level_features_batch: a data set is not D x V(its mesh)");
+        handles.push_back(meshes[i]->handle());
+        rows.push_back(datas[i]->data());
+    }
+    msm_level_features_params p{exclude ? 1 : 0, intensity ? 1 : 0, varnorm ? 1 : 0, 0, thrl, thru};
+    Matrix feat(n * (size_t)std::max(D, 0) * V);
+    std::vector<double> mask(exclude ? n * V : 0);
+    check(msm_level_features(grid.handle(), (int32_t)n, handles.data(), rows.data(), D, sigmas.data(), &p, feat.data(), exclude ? mask.data() : nullptr));
+    LevelFeatures out;
+    out.features.resize(n), out.masks.resize(n);
+    const size_t DV = (size_t)D * V;
+    for (size_t i = 0; i < n; ++i) {
+        out.features[i].assign(feat.begin() + (long)(i * DV), feat.begin() + (long)((i + 1) * DV));
+        if (exclude) out.masks[i].assign(mask.begin() + (long)(i * V), mask.begin() + (long)((i + 1) * V));
+    }
+    return out;
+}
 // msm_surface_distortion: the distortion maps (S x 2 x V: log2 J, log2 R per vertex) of the deformed copies `finals` of one sphere, in one call
 inline Matrix surface_distortion(Context &ctx, const Points &orig_xyz, const Triangles &tri, const std::vector<Points> &finals) {
     const int32_t V = (int32_t)(orig_xyz.size() / 3), T = (int32_t)(tri.size() / 3), S = (int32_t)finals.size();

@@ -20,6 +20,7 @@ struct GroupLevelOptions {
     int icm_passes = 5;      // the stand-in solve
     double labeldist = 0.5;  // _labeldist, M/DiscreteModel.h:167
     GroupParameters cost;    // --simval --lambda --fixnan --shearmod --bulkmod --k_exponent --regexp --cprange --percentile
+    bool features_gpu = false;  // the level's features for all subjects through one msm_level_features call (LevelOptions::features_gpu): the same bytes
 };
 
 struct GroupLevelResult {
@@ -157,7 +158,14 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
         auto [ico_xyz, ico_tri] = make_mesh_from_icosa(lv.data_order);
         Mesh ico(ctx, ico_xyz, ico_tri);
         std::vector<Matrix> feats;
-        if (inorm.on || inorm.cut) {  // resample and smooth only: matching and variance normalisation follow when every subject's data is there
+        if (lv.options.features_gpu) {  // featurespace::initialise over all subjects in one call (msm_level_features): the bytes of the branches below
+            std::vector<Mesh *> ms;
+            std::vector<const Matrix *> ds;
+            for (int s = 0; s < S; ++s) ms.push_back(in_mesh[(size_t)s].get()), ds.push_back(&datas[(size_t)s]);
+            feats = PhaseClock::timed(clock, "level_features", [&] {
+                return level_features_batch(ico, ms, ds, D, std::vector<double>((size_t)S, lv.sigma_in), excl.on || inorm.cut, inorm.on, varnorm, excl.lower, excl.upper);
+            }).features;
+        } else if (inorm.on || inorm.cut) {  // resample and smooth only: matching and variance normalisation follow when every subject's data is there
             Exclusion masked = excl;
             masked.on = excl.on || inorm.cut;
             std::vector<std::vector<double>> masks((size_t)S);

@@ -60,6 +60,9 @@ struct LevelOptions {
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
+    // the level's features for both data sets through one msm_level_features call (level_features_batch: the masked list surgery and create_exclusion on
+    // the device) instead of the chain of calls of level_features / finish_features: the same bytes (what MSMHIP_FEATURES=gpu asks of the executables)
+    bool features_gpu = false;
     // true: --regoption=1 as --dopt=FastPD drives it (M/mesh_registration.cpp:182-188): the model lists pairs instead of triplets, per iteration
     // computeUnaryCosts + computePairwiseCosts, then a stand-in for FPD::FastPD(model, 100) (msm_pairwise_icm)
     bool pairwise = false;
@@ -412,7 +415,28 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
         masked.on = excl.on || (postponed && inorm.cut);
         ReferenceCache::Entry *entry = ref_cache ? &ref_cache->levels[li] : nullptr;
         ++li;
-        for (int k = 0; k < 2; ++k) {
+        bool finish = postponed;
+        if (lv.options.features_gpu) {  // featurespace::initialise in one call (msm_level_features): the bytes of the loop below
+            const auto batch = [&](const std::vector<Mesh *> &m, const std::vector<const Matrix *> &d, const std::vector<double> &s, bool match, bool vn) {
+                return PhaseClock::timed(clock, "level_features", [&] { return level_features_batch(ico, m, d, D, s, masked.on, match, vn, masked.lower, masked.upper); });
+            };
+            if (!entry) {
+                feats = batch({&in_mesh, &ref_mesh}, {&in_data, &ref_data}, {lv.sigma_in, lv.sigma_ref}, inorm.on, varnorm).features;
+                finish = false;
+            } else {  // the input data alone; the reference's from the cache, which one call of its own fills; the tail over the two as below
+                LevelFeatures one = batch({&in_mesh}, {&in_data}, {lv.sigma_in}, false, postponed ? false : varnorm);
+                feats[0] = std::move(one.features[0]), masks[0] = std::move(one.masks[0]);
+                if (entry->filled) {
+                    ++ref_cache->hits;
+                } else {
+                    one = batch({&ref_mesh}, {&ref_data}, {lv.sigma_ref}, false, postponed ? false : varnorm);
+                    entry->features = std::move(one.features[0]), entry->mask = std::move(one.masks[0]), entry->filled = true;
+                    ++ref_cache->fills;
+                }
+                feats[1] = entry->features, masks[1] = entry->mask;
+            }
+        }
+        for (int k = 0; k < 2 && !lv.options.features_gpu; ++k) {
             if (k == 1 && entry && entry->filled) {
                 feats[1] = entry->features, masks[1] = entry->mask;
                 ++ref_cache->hits;
@@ -425,7 +449,7 @@ inline MultiresResult run_multiresolutions(Context &ctx, const Points &in_xyz, c
                 ++ref_cache->fills;
             }
         }
-        if (postponed) finish_features(ctx, feats, masks, masked.on, D, ico.nvertices(), inorm, varnorm, clock);
+        if (finish) finish_features(ctx, feats, masks, masked.on, D, ico.nvertices(), inorm, varnorm, clock);
         // project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         Points sph_in, cp_start, incurrent;
         const Points *moved_in = trans_xyz;

@@ -37,6 +37,10 @@ class CostParams(C.Structure):
                 ("rexp", C.c_double), ("range", C.c_double), ("percentile", C.c_double)]
 
 
+class LevelFeaturesParams(C.Structure):
+    _fields_ = [("exclude", C.c_int32), ("intensity", C.c_int32), ("varnorm", C.c_int32), ("reserved", C.c_int32), ("thrl", C.c_double), ("thru", C.c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/msmhip.h one to one
 _VP = C.c_void_p
 SIGNATURES = {
@@ -106,6 +110,7 @@ SIGNATURES = {
     "msm_mesh_prepare_search": (C.c_int, [_VP, C.c_int, c_ip]),
     "msm_variance_normalise": (C.c_int, [c_dp, C.c_int32, C.c_int32, c_dp]),
     "msm_histogram_match": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp, C.c_int32, C.c_int32, c_dp, c_dp, C.c_int32, c_dp]),
+    "msm_level_features": (C.c_int, [_VP, C.c_int32, C.POINTER(_VP), C.POINTER(c_dp), C.c_int32, c_dp, C.POINTER(LevelFeaturesParams), c_dp, c_dp]),
     "msm_mcmc_optimise": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_uint64, c_ip]),
     "msm_mcmc_optimise_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_uint64, c_ip]),
     "msm_mcmc_gpu_stats": (C.c_int, [_VP, c_dp]),

@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CostParams, MsmError, c_dp, c_ip, c_lp, check, lib
+from ._lib import CostParams, LevelFeaturesParams, MsmError, c_dp, c_ip, c_lp, check, lib
 
 WEIGHTS_PROJECTED = 0
 WEIGHTS_RAW = 1
@@ -637,6 +637,27 @@ def histogram_match(ctx, src, ref, src_excl=None, ref_excl=None):
     out = np.empty(s3.shape)
     check(lib().msm_histogram_match(ctx.h, n, D, Vs, ps, pse, se_rows, r.shape[1], pr, pre, re_rows, out.ctypes.data_as(c_dp)))
     return out.reshape(shape)
+
+
+def level_features(grid, meshes, datas, sigmas, exclude=False, intensity=False, varnorm=False, cutthr=(0.0, 0.0001)):
+    """msm_level_features: featurespace::initialise (M/featurespace.cpp:39-86) for n data sets on the level grid `grid` in ONE call -- per data set
+    create_exclusion (with exclude), metric_resample from its native mesh and smooth_data on the grid (sigmas[i] > 0), then histogram_match of
+    data sets 1.. against data set 0 (intensity) and variance_normalise (varnorm): the bytes of those calls one after another.  meshes: n Mesh
+    handles of grid's context; datas: n matrices D x V(meshes[i]).  Returns (n x D x V(grid) features, n x V(grid) masks or None without exclude)."""
+    n = len(meshes)
+    mats = [_d(np.atleast_2d(d))[0] for d in datas]
+    assert len(mats) == n and len(sigmas) == n
+    D = mats[0].shape[0] if n else 0
+    for m, a in zip(meshes, mats):
+        assert a.shape == (D, m.V), "a data set has shape %s, its mesh %d vertices and the first data set %d rows" % (a.shape, m.V, D)
+    handles = (C.c_void_p * max(n, 1))(*[m.h for m in meshes])
+    rows = (c_dp * max(n, 1))(*[a.ctypes.data_as(c_dp) for a in mats])
+    sg, psg = _d(np.asarray(sigmas, dtype=np.float64).reshape(-1))
+    p = LevelFeaturesParams(int(bool(exclude)), int(bool(intensity)), int(bool(varnorm)), 0, float(cutthr[0]), float(cutthr[1]))
+    feat = np.zeros((n, D, grid.V))
+    mask = np.zeros((n, grid.V)) if exclude else None
+    check(lib().msm_level_features(grid.h, n, handles, rows, D, psg, C.byref(p), feat.ctypes.data_as(c_dp), None if mask is None else mask.ctypes.data_as(c_dp)))
+    return feat, mask
 
 
 def surface_distortion(ctx, orig_xyz, tri, final_xyz):

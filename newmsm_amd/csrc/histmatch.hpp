@@ -26,4 +26,9 @@ int launch_hist_table(msm_ctx *ctx, const HistRows &rows, const unsigned long lo
 // out (n_src x D x Vs) = src with every counted value of a flagged row replaced by its bin's table entry
 int launch_hist_apply(msm_ctx *ctx, const HistRows &rows, const unsigned long long *d_range, const double *d_table, const int32_t *d_flag, double *d_out);
 
+// histmatch.cpp, the device part of msm_histogram_match: the four launches over rows that lie in HBM, with the context's range words, counters, tables and
+// flags (zeroed here); d_out may be rows.src.  Nothing is waited for.  hist_rows_check: the limits of one launch (MSM_ERR_CAPACITY with `who` in the message).
+int hist_rows_check(const char *who, int n_src, int D, int Vs, int Vt);
+int hist_match_dev(msm_ctx *ctx, const HistRows &rows, double *d_out);
+
 }  // namespace msm

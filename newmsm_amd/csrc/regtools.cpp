@@ -10,6 +10,7 @@
 #include "host_parallel.hpp"
 #include "kernels.hpp"
 #include "mcmc.hpp"
+#include "varnorm.hpp"
 
 using namespace msm;
 
@@ -126,25 +127,7 @@ int msm_variance_normalise(double *data, int32_t D, int32_t V, const double *exc
     if (!data || D < 0 || V < 0) return fail(MSM_ERR_INVALID, "msm_variance_normalise: bad arguments");
     // the recurrence of a row is serial (a division per value: 0.4 ms per ico6 row); the rows are independent and run on the host workers
     parallel_chunks(D, D >= 4 ? host_workers() : 1, [&](int, int d_begin, int d_end) {
-    for (int d = d_begin; d < d_end; ++d) {
-        double *row = data + (size_t)d * V;
-        double mean = 0.0, var = 0.0;
-        size_t n = 0;
-        for (int i = 0; i < V; ++i) {
-            if (excl && !(excl[i] > 0.0)) continue;
-            const double delta = row[i] - mean;
-            mean += delta / (double)(n + 1);
-            var += delta * (row[i] - mean);
-            ++n;
-        }
-        var /= (double)(n - 1);  // unsigned, as _data[i].size() - 1 at :829
-        const double sd = std::sqrt(var);
-        for (int i = 0; i < V; ++i) {
-            if (excl && !(excl[i] > 0.0)) continue;
-            row[i] -= mean;
-            if (var > 0.0) row[i] /= sd;
-        }
-    }
+    for (int d = d_begin; d < d_end; ++d) variance_normalise_row(data + (size_t)d * V, V, excl);
     });
     return MSM_OK;
 }

@@ -1,5 +1,6 @@
 // resample.cpp -- the host side of the adaptive-barycentric resampler (resample.hpp): the scratch of the device surgery, the weights of a mesh pair on
 // the device or (with an exclusion mask) through the host surgery, and the entry points msm_adaptive_barycentric_weights / msm_metric_resample.
+// adaptive_weights_dev_masked queues the masked surgery on the device for msm_level_features (features.cpp); the two entry points keep the host surgery.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -180,6 +181,7 @@ void adaptive_surgery(const AdaptiveQueries &q, int nOld, int nNew, const std::v
 struct ResampleScratch {
     SurgeryScratch surgery;
     DevBuf<double> data, out;  // msm_metric_resample: the maps in and out
+    DevBuf<int> closest;       // the masked device surgery: the old vertex closest to every new vertex
 };
 ResampleScratch &resample_scratch(msm_ctx *ctx) {
     if (!ctx->resample_scratch) ctx->resample_scratch = std::shared_ptr<void>(new ResampleScratch(), [](void *p) { delete static_cast<ResampleScratch *>(p); });
@@ -188,7 +190,8 @@ ResampleScratch &resample_scratch(msm_ctx *ctx) {
 
 }  // namespace
 
-int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check) {
+// d_excl: nullptr, or the mask of adaptive_weights_dev_masked
+static int adaptive_weights_queue(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *d_excl, AdaptiveDev &out, bool check) {
     // Everything is queued on in_mesh's context.  new_mesh may belong to another context of the same GPU (the fallback mesh of the
     // gMSM set-up against the group's template) if its tree and adjacency are complete and synchronised: they are only read.
     const bool foreign = in_mesh->ctx != new_mesh->ctx;
@@ -210,13 +213,36 @@ int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out
     if (st) return st;
     st = launch_vertex_areas(ctx, new_mesh->d_xyz.p, nNew, new_mesh->d_tri.p, new_mesh->T, new_mesh->d_tid_ptr.p, new_mesh->d_tid.p, s.ta.p, s.newA.p);
     if (st) return st;
-    st = launch_adaptive_surgery(ctx, s.args(nOld, nNew, 1));
+    AdaptiveDevArgs args = s.args(nOld, nNew, 1);
+    if (d_excl) {  // :101: the old vertex closest to every new vertex decides whether its row takes part
+        DevBuf<int> &closest = resample_scratch(ctx).closest;
+        MSM_HIP(closest.ensure(nNew));
+        st = launch_closest_vertex(ctx, dev_tree(in_mesh), new_mesh->d_xyz.p, nNew, closest.p);
+        if (st) return st;
+        args.closest = closest.p, args.excl = d_excl;
+    }
+    st = launch_adaptive_surgery(ctx, args);
     if (st) return st;
     if (check) {
         st = check_status(ctx, "adaptive weights");  // a failed search in either direction (synchronises)
         if (st) return st;
     }
     out.nOld = nOld, out.nNew = nNew, out.row_ptr = s.row_ptr.p, out.col = s.col.p, out.val = s.val.p;
+    return MSM_OK;
+}
+
+int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check) { return adaptive_weights_queue(in_mesh, new_mesh, nullptr, out, check); }
+
+int adaptive_weights_dev_masked(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *d_excl, AdaptiveDev &out) {
+    if (!d_excl) return fail(MSM_ERR_INVALID, "adaptive weights: the masked surgery needs a mask");
+    if (in_mesh->ctx != new_mesh->ctx) return fail(MSM_ERR_INVALID, "adaptive weights: the two meshes belong to different contexts");
+    return adaptive_weights_queue(in_mesh, new_mesh, d_excl, out, false);
+}
+
+int reserve_surgery_scratch(msm_ctx *ctx, int nOld, int nNew, int Told, int Tnew) {
+    ResampleScratch &s = resample_scratch(ctx);
+    MSM_TRY(s.surgery.ensure(nOld, nNew, Told, Tnew, 1));
+    MSM_HIP(s.closest.ensure(nNew));
     return MSM_OK;
 }
 

@@ -49,6 +49,10 @@ struct AdaptiveDevArgs {
     double *tval;
     int *row_ptr, *col;            // the result as CSR: nNew + 1, 3 nNew + 3 nOld
     double *val;
+    // an exclusion mask (one problem only; msm_level_features): closest[k] = the old vertex closest to new vertex k, excl: the mask on the old mesh
+    // (0 = excluded).  excl == nullptr: no mask, every row takes part
+    const int *closest = nullptr;
+    const double *excl = nullptr;
     // B problems at once (gMSM: a subject's data mesh rotated to every label against the one template): problem b = blockIdx.y of
     // every launch uses the arrays b * stride elements further on.  fstride / rstride: distance between the three components of
     // fvid / fw and rvid / rw (B * nNew and B * nOld).
@@ -74,6 +78,9 @@ int launch_adaptive_surgery(msm_ctx *ctx, const AdaptiveDevArgs &a);  // a: from
 // out[b][d][k] = problem b's weights applied to data (D x nOld, shared by the problems); out: B blocks of out_stride doubles
 int launch_apply_rows_batch(msm_ctx *ctx, const AdaptiveDevArgs &a, int D, const double *d_data, double *d_out, size_t out_stride);
 int launch_apply_rows(msm_ctx *ctx, int nNew, int nOld, int D, const int *row_ptr, const int *col, const double *val, const double *d_data, double *d_out);
+// the same with the old mesh's mask d_excl: excluded columns left out, and d_excl_out (nNew) = the rows applied to the mask itself over the kept columns
+int launch_apply_rows_masked(msm_ctx *ctx, int nNew, int nOld, int D, const int *row_ptr, const int *col, const double *val, const double *d_data,
+                             const double *d_excl, double *d_out, double *d_excl_out);
 
 // ---- the weights of one (in_mesh -> new_mesh) pair (resample.cpp)
 // queries AND list surgery on the device (no exclusion mask): the CSR stays in HBM
@@ -83,6 +90,11 @@ struct AdaptiveDev {
     const double *val = nullptr;
 };
 int adaptive_weights_dev(msm_mesh *in_mesh, msm_mesh *new_mesh, AdaptiveDev &out, bool check = true);  // check = false: the caller checks the status word
+// the same under an exclusion mask that lies in HBM (d_excl: V(in_mesh) values, 0 = excluded): the closest-vertex search and the masked surgery are queued
+// behind the queries, nothing is waited for and the status word is the caller's to check.  Both meshes belong to one context.
+int adaptive_weights_dev_masked(msm_mesh *in_mesh, msm_mesh *new_mesh, const double *d_excl, AdaptiveDev &out);
+// grows the context's surgery scratch to what a pair of these sizes needs, so that a sequence of queued surgeries finds it large enough
+int reserve_surgery_scratch(msm_ctx *ctx, int nOld, int nNew, int Told, int Tnew);
 // out (device, D x V(new)) = the weights applied to d_data (device, D x V(in)): barycentric_data_interpolation R/resampler.cpp:40-52
 int apply_weights_dev(msm_ctx *ctx, const AdaptiveDev &w, const double *d_data, int D, double *d_out);
 // the row offsets of device rows on the host (synchronises) and their last one, the number of entries

@@ -12,8 +12,9 @@
 //                              serially in that order -- the order of the reference's loop over k (:99-118);
 //   row sums                   a thread per row, in entry (= key) order.
 // So every floating-point sum has the reference's operand order and the weights are bit-identical to the host surgery's
-// (tests/test_gpu_search.py, tests/fuzz_resample.py compare them with the oracle bit for bit).  The exclusion-mask variant keeps
-// the host path (resample.cpp: adaptive_surgery).
+// (tests/test_gpu_search.py, tests/fuzz_resample.py compare them with the oracle bit for bit).  Under an exclusion mask the entry points
+// msm_metric_resample / msm_adaptive_barycentric_weights keep the host path (resample.cpp: adaptive_surgery); msm_level_features runs the masked
+// surgery here (row_active: a row whose new vertex lies closest to an excluded old vertex is empty) and the masked sums of k_apply_rows_masked.
 #include <climits>
 #include <algorithm>
 
@@ -201,14 +202,23 @@ __global__ __launch_bounds__(256) void k_sort_long_lists(AdaptiveDevArgs a, int 
         __syncthreads();
     }
 }
+// Does row k take part (:101)?  Without a mask every row does; under one only a new vertex whose closest old vertex is kept -- the others have no
+// entries, so they add nothing to `correction`.  The one definition for k_row_len and k_row_write: a row's length and its entries cannot disagree.
+template <bool MASKED>
+__device__ __forceinline__ bool row_active(const AdaptiveDevArgs &a, int k) {
+    if (!MASKED) return true;
+    const int c = a.closest[k];
+    return c >= 0 && a.excl[c] != 0;
+}
 // :105-109: the forward list unless the transposed reverse list is longer
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_row_len(AdaptiveDevArgs a) {
     a = problem_view(a);
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.nNew) return;
     WeightEntry f[3];
     const int nf = small_map(a.fvid, a.fw, (int)a.fstride, k, f), nr = a.roff[k + 1] - a.roff[k];
-    a.row_ptr[k] = nr <= nf ? nf : nr;
+    a.row_ptr[k] = !row_active<MASKED>(a, k) ? 0 : (nr <= nf ? nf : nr);
 }
 // The four kernels below walk a row (a column) of the result.  With meshes of similar resolution a row has 3 - 6 entries and a thread per
 // row is right; a coarse new mesh under a fine old one (resample_weights of every iteration: ico6 source -> ico4 control grid) has rows of
@@ -216,14 +226,14 @@ __global__ __launch_bounds__(256) void k_row_len(AdaptiveDevArgs a) {
 // (60 - 90 us each at ico6 -> ico4).  LPR = 1, 8 or 64 lanes share a row; where the reference's sum runs over the row in entry order the
 // lanes compute their terms side by side and every lane of the row adds them up in that order (broadcast term by term: same operands,
 // same order, same bits).
-template <int LPR>
+template <int LPR, bool MASKED>
 __global__ __launch_bounds__(256) void k_row_write(AdaptiveDevArgs a) {
     a = problem_view(a);
     const int gid = blockIdx.x * blockDim.x + threadIdx.x, k = gid / LPR, sub = gid % LPR;
     if (k >= a.nNew) return;
     WeightEntry f[3];
     const int nf = small_map(a.fvid, a.fw, (int)a.fstride, k, f), nr = a.roff[k + 1] - a.roff[k];
-    const int n = nr <= nf ? nf : nr, at = a.row_ptr[k];
+    const int n = !row_active<MASKED>(a, k) ? 0 : (nr <= nf ? nf : nr), at = a.row_ptr[k];
     const double area = a.newA[k];
     for (int j = sub; j < n; j += LPR) {
         int key;
@@ -334,6 +344,25 @@ __global__ __launch_bounds__(256) void k_apply_rows(AdaptiveDevArgs a, int D, co
     });
     if (live && sub == 0) out[i] = acc;
 }
+// the same under a mask (:40-67): excluded old vertices are left out of every sum, and row D of the launch is the mask itself resampled --
+// excl_out[k] = sum of excl[col] * val over the kept entries.  One problem.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_apply_rows_masked(AdaptiveDevArgs a, int D, const double *__restrict__ data, const double *__restrict__ excl,
+                                                            double *__restrict__ out, double *__restrict__ excl_out) {
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, i = gid / LPR;
+    const int sub = (int)(gid % LPR);
+    const bool live = i < (size_t)a.nNew * (D + 1);
+    if (LPR == 1 && !live) return;
+    const int d = live ? (int)(i / a.nNew) : 0, k = live ? (int)(i - (size_t)d * a.nNew) : 0;
+    const int b = live ? a.row_ptr[k] : 0, end = live ? a.row_ptr[k + 1] : 0;
+    const double *src = d < D ? data + (size_t)d * a.nOld : excl;
+    const double acc = ordered_sum<LPR>(b, end, sub, [&](int e, bool &ok) {
+        const int c = a.col[e];
+        ok = c >= 0 && excl[c] != 0;
+        return ok ? src[c] * a.val[e] : 0.0;
+    });
+    if (live && sub == 0) (d < D ? out[i] : excl_out[k]) = acc;
+}
 
 }  // namespace
 
@@ -377,6 +406,13 @@ static int lanes_per_row(double len) { return len <= 6.0 ? 1 : (len <= 96.0 ? 8 
         else MSM_LAUNCH2D(kernel<1>, (size_t)(n), B, __VA_ARGS__);            \
     } while (0)
 
+#define MSM_LAUNCH_LPR2(kernel, lpr, flag, n, B, ...)                        \
+    do {                                                                      \
+        if ((lpr) == 64) MSM_LAUNCH2D((kernel<64, flag>), (size_t)(n) * 64, B, __VA_ARGS__); \
+        else if ((lpr) == 8) MSM_LAUNCH2D((kernel<8, flag>), (size_t)(n) * 8, B, __VA_ARGS__); \
+        else MSM_LAUNCH2D((kernel<1, flag>), (size_t)(n), B, __VA_ARGS__);    \
+    } while (0)
+
 // a: from SurgeryScratch::args, nothing else -- the clear below relies on its one-block layout of the counters
 int launch_adaptive_surgery(msm_ctx *ctx, const AdaptiveDevArgs &a) {
     const int nOld = a.nOld, nNew = a.nNew, B = std::max(a.B, 1);
@@ -390,9 +426,13 @@ int launch_adaptive_surgery(msm_ctx *ctx, const AdaptiveDevArgs &a) {
     MSM_LAUNCH2D(k_sort_lists, nNew, B, a, 0);
     // (256 workgroups per problem walk the lists: the usual launch finds no long list, and 2048 x B workgroups that only look at the flag took 26 us to dispatch)
     hipLaunchKernelGGL(k_sort_long_lists, dim3((unsigned)std::min(nNew, B > 1 ? 256 : 2048), (unsigned)B), dim3(256), 0, ctx->stream, a, 0);
-    MSM_LAUNCH2D(k_row_len, nNew, B, a);
+    const bool masked = a.excl != nullptr;  // (one problem: problem_view leaves closest / excl where they are)
+    if (masked && (B != 1 || !a.closest)) return fail(MSM_ERR_INVALID, "adaptive surgery: a mask serves one problem and needs the closest vertices");
+    if (masked) MSM_LAUNCH2D(k_row_len<true>, nNew, B, a);
+    else MSM_LAUNCH2D(k_row_len<false>, nNew, B, a);
     scan_excl(ctx, a.row_ptr, nNew, a.scan_tmp, B, a.s_rowptr, a.s_scan);
-    MSM_LAUNCH_LPR(k_row_write, row_lpr, nNew, B, a);
+    if (masked) MSM_LAUNCH_LPR2(k_row_write, row_lpr, true, nNew, B, a);
+    else MSM_LAUNCH_LPR2(k_row_write, row_lpr, false, nNew, B, a);
     scan_excl(ctx, a.coff, nOld, a.scan_tmp, B, a.s_coff, a.s_scan);
     MSM_LAUNCH_LPR(k_col_fill, row_lpr, nNew, B, a);
     MSM_LAUNCH2D(k_sort_lists, nOld, B, a, 1);
@@ -407,6 +447,17 @@ int launch_apply_rows_batch(msm_ctx *ctx, const AdaptiveDevArgs &a, int D, const
     const size_t total = (size_t)a.nNew * D;
     const int lpr = lanes_per_row(3.0 * a.nOld / std::max(a.nNew, 1));
     MSM_LAUNCH_LPR(k_apply_rows, lpr, total, std::max(a.B, 1), a, D, d_data, d_out, out_stride);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+int launch_apply_rows_masked(msm_ctx *ctx, int nNew, int nOld, int D, const int *row_ptr, const int *col, const double *val, const double *d_data,
+                             const double *d_excl, double *d_out, double *d_excl_out) {
+    AdaptiveDevArgs a{};
+    a.nNew = nNew, a.nOld = nOld, a.B = 1;
+    a.row_ptr = const_cast<int *>(row_ptr), a.col = const_cast<int *>(col), a.val = const_cast<double *>(val);
+    const size_t total = (size_t)nNew * (D + 1);
+    const int lpr = lanes_per_row(3.0 * nOld / std::max(nNew, 1));
+    MSM_LAUNCH_LPR(k_apply_rows_masked, lpr, total, 1, a, D, d_data, d_excl, d_out, d_excl_out);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

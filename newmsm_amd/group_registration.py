@@ -19,11 +19,11 @@ from .registration import ProductOps, apply_labeling, finish_features, level_fea
 
 
 class ProductGroupOps(ProductOps):
-    def __init__(self, ctx, host_rotations=True):
-        """host_rotations (the library's default): the rotation matrices of the data meshes' vertices from the host's libm, as the reference computes them
+    def __init__(self, ctx, host_rotations=True, features_gpu=False):
+        """features_gpu: as ProductOps' (a level's features for all subjects in one msm_level_features call).  host_rotations (the library's default): the rotation matrices of the data meshes' vertices from the host's libm, as the reference computes them
         (DiscreteGroupCostFunction.set_rotation_mode) -- on regular icospheres (template and subjects' spheres alike, as gMSM's scripts set them up) a label
         carries data vertices exactly onto template vertices and the last bits of the rotation decide the resampled values there; False: the device computes them"""
-        super().__init__(ctx)
+        super().__init__(ctx, features_gpu=features_gpu)
         self.host_rotations = host_rotations
 
     def group(self, S, simmeasure, lambda_, fixnan, **params):
@@ -186,7 +186,9 @@ def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, le
         ico_xyz, ico_tri = ops.icosphere(lv["data_order"])
         ico = ops.mesh(ico_xyz, ico_tri)
         feats = []
-        if intensity or cut:
+        if getattr(ops, "features_gpu", False):  # featurespace::initialise over all subjects in one call: the bytes of the branches below
+            feats, _ = timed("level_features", ops.level_features_batch, ico, in_mesh, datas, [lv.get("sigma_in", 0.0)] * S, excl or cut, intensity, varnorm, cutthr)
+        elif intensity or cut:
             prepared = [level_features(ops, timed, in_mesh[s], datas[s], ico, lv.get("sigma_in", 0.0), False, None, excl or cut, cutthr) for s in range(S)]
             feats = finish_features(ops, timed, [p[0] for p in prepared], [p[1] for p in prepared], intensity, varnorm)
         else:

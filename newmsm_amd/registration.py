@@ -27,11 +27,15 @@ EXCL_WITH_WEIGHTINGS = ("--excl together with --inweight and --refweight is not 
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
-    def __init__(self, ctx, mcmc_gpu=False):
-        """mcmc_gpu: the MCMC branch of run_discrete_level leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead
+    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False):
+        """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
+        the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
+        bytes (what MSMHIP_FEATURES=gpu asks of the executables).
+        mcmc_gpu: the MCMC branch of run_discrete_level leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead
         of fetching them for the host optimiser -- the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)"""
         self.ctx = ctx
         self.mcmc_gpu = bool(mcmc_gpu)
+        self.features_gpu = bool(features_gpu)
 
     # --- meshes
     def icosphere(self, order):
@@ -108,6 +112,12 @@ class ProductOps:
         matched copies."""
         out = api.histogram_match(self.ctx, np.stack([np.atleast_2d(s) for s in srcs]), ref, None if src_excls is None else np.stack(src_excls), ref_excl)
         return list(out)
+
+    def level_features_batch(self, ico, meshes, datas, sigmas, exclude, intensity, varnorm, cutthr):
+        """featurespace::initialise for the data sets (meshes[i], datas[i]) on the level grid ico in one call (msm_level_features): what
+        composed_level_features gives over this object's other methods.  Returns (list of D x V(ico) features, list of masks -- None each without exclude)"""
+        feat, mask = api.level_features(ico, meshes, datas, sigmas, exclude=exclude, intensity=intensity, varnorm=varnorm, cutthr=cutthr)
+        return list(feat), ([None] * len(meshes) if mask is None else list(mask))
 
     def nearest_neighbour(self, mesh, data, q_xyz):
         return api.nearest_neighbour_interpolation(mesh, data, q_xyz)
@@ -337,6 +347,36 @@ def finish_features(ops, timed, feats, masks, intensity, varnorm):
     if varnorm:
         feats = [ops.variance_normalise(f) if m is None else ops.variance_normalise(f, excl=m) for f, m in zip(feats, masks)]
     return feats
+
+
+def composed_level_features(ops, timed, ico, meshes, datas, sigmas, exclude, intensity, varnorm, cutthr):
+    """What ops.level_features_batch stands for, spelt out over the separate calls: level_features of every data set without variance normalisation
+    (masks from the cut range when exclude), then finish_features -- matching of data sets 1.. to data set 0 when intensity, variance normalisation of
+    each with its mask when varnorm.  Without intensity that is level_features with varnorm, data set by data set.  Returns (features, masks)."""
+    prepared = [level_features(ops, timed, m, d, ico, s, False, None, exclude, cutthr) for m, d, s in zip(meshes, datas, sigmas)]
+    masks = [p[1] for p in prepared]
+    return finish_features(ops, timed, [p[0] for p in prepared], masks, intensity, varnorm), masks
+
+
+def batched_pair_features(ops, timed, ico, li, lv, in_mesh, in_data, ref_mesh, ref_data, varnorm, excl, cutthr, intensity, cut, ref_cache):
+    """A pairwise level's two feature matrices (input, reference) through ops.level_features_batch: one call over both data sets; with a ReferenceCache
+    one call for the input data, the cache's entry (filled by one call for the reference data, under the key the unbatched loop uses) and
+    finish_features over the two where --IN / --INc postpone the tail."""
+    exclude, postponed = bool(excl or cut), bool(intensity or cut)
+    sig_in, sig_ref = lv.get("sigma_in", 0.0), lv.get("sigma_ref", 0.0)
+    if ref_cache is None:
+        return timed("level_features", ops.level_features_batch, ico, [in_mesh, ref_mesh], [in_data, ref_data], [sig_in, sig_ref], exclude, intensity, varnorm, cutthr)[0]
+    each = False if postponed else varnorm
+
+    def one(mesh, data, sigma):
+        f, m = timed("level_features", ops.level_features_batch, ico, [mesh], [data], [sigma], exclude, False, each, cutthr)
+        return f[0], m[0]
+
+    f_in, m_in = one(in_mesh, in_data, sig_in)
+    key = (li, lv["data_order"], float(sig_ref), bool(each), exclude, tuple(float(c) for c in cutthr))
+    f_ref, m_ref = ref_cache.get(key, lambda: one(ref_mesh, ref_data, sig_ref))
+    feats = [f_in, f_ref]
+    return finish_features(ops, timed, feats, [m_in, m_ref], intensity, varnorm) if postponed else feats
 
 
 def transformed_data(ops, moved_mesh, in_data, ref_mesh, ref_data=None, *, excl=False, cutthr=(0.0, 0.0001), intensity=False):
@@ -607,7 +647,12 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
         ico_xyz, ico_tri = ops.icosphere(lv["data_order"])
         ico = ops.mesh(ico_xyz, ico_tri)
         feats, masks = [], []
-        for mesh, data, sigma, slot in ((in_mesh, in_data, lv.get("sigma_in", 0.0), "in"), (ref_mesh, ref_data, lv.get("sigma_ref", 0.0), "ref")):
+        batched = getattr(ops, "features_gpu", False)  # featurespace::initialise in one call: the bytes of the loop below
+        data_sets = ((in_mesh, in_data, lv.get("sigma_in", 0.0), "in"), (ref_mesh, ref_data, lv.get("sigma_ref", 0.0), "ref"))
+        if batched:
+            feats = batched_pair_features(ops, timed, ico, li, lv, in_mesh, in_data, ref_mesh, ref_data, varnorm, excl, cutthr, intensity, cut, ref_cache)
+            data_sets = ()
+        for mesh, data, sigma, slot in data_sets:
             # (a level's matrices are consumed -- uploaded by the cost function and the target mesh -- before the next level asks for its own: the
             # result slots are reused from level to level)
             if intensity or cut:  # resample and smooth only: matching and variance normalisation follow when both data sets are there
@@ -622,7 +667,7 @@ def _run_levels(ops, clock, timed, in_xyz, in_mesh, ref_mesh, in_data, ref_data,
             if intensity or cut:
                 masks.append(m)
             feats.append(f)
-        if intensity or cut:
+        if (intensity or cut) and not batched:
             feats = finish_features(ops, timed, feats, masks, intensity, varnorm)
         # project_CPgrid: the warp this level starts from, as the input sphere moved through it -- the previous level's, or --trans at the first
         if sph_reg_prev is None:

@@ -182,6 +182,12 @@ bool histmatch_enabled() {
     return env && std::string(env) == "on";
 }
 
+// MSMHIP_FEATURES=gpu: every level's features are prepared through one msm_level_features call; the same files are written
+bool features_gpu_enabled() {
+    const char *env = std::getenv("MSMHIP_FEATURES");
+    return env && std::string(env) == "gpu";
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
     for (const char *flag : {"inmesh", "indata", "refdata"})
         if (o.get(flag).empty()) throw Error(MSM_ERR_INVALID, std::string("newmsm: --") + flag + " is required");
@@ -204,6 +210,8 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
     if (mcmc_gpu)
         for (LevelSpec &lv : levels) lv.options.mcmc_gpu = true;
+    if (features_gpu_enabled())
+        for (LevelSpec &lv : levels) lv.options.features_gpu = true;
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
@@ -226,6 +234,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("verbose"))
         std::cout << "This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     if (o.has("verbose") && mcmc_gpu) std::cout << "MCMC sweeps on the GPU." << std::endl;
+    if (o.has("verbose") && features_gpu_enabled()) std::cout << "Level features in one call on the GPU." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,
                                                     anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr,
                                                     o.get("trans").empty() ? nullptr : &trans, excl, inorm);
@@ -264,8 +273,10 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
     bool varnorm = false;
     IntensityNorm inorm;
-    const std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm, histmatch_enabled() ? &inorm : nullptr);  // refuses AFFINE / RIGID levels and optimisers other than HOCR
+    std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm, histmatch_enabled() ? &inorm : nullptr);  // refuses AFFINE / RIGID levels and optimisers other than HOCR
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
+    if (features_gpu_enabled())
+        for (GroupLevelSpec &lv : levels) lv.options.features_gpu = true;
     std::vector<std::pair<Points, Triangles>> meshes;
     for (size_t k = 0; k < mesh_files.size(); ++k) {
         if (o.has("verbose")) std::cout << "Mesh #" << k << " is " << mesh_files[k] << std::endl;
@@ -292,6 +303,7 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     Context ctx(device);
     if (o.has("verbose"))
         std::cout << "This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
+    if (o.has("verbose") && features_gpu_enabled()) std::cout << "Level features in one call on the GPU." << std::endl;
     const GroupMultiresResult res = run_group_multiresolutions(ctx, meshes, datas, D, txyz, ttri, levels, varnorm, mask.empty() ? nullptr : &mask, nullptr,
                                                                exclusion_from_config(cfg), inorm);
     const Triangles last_tri = make_mesh_from_icosa(levels.back().data_order).second;

@@ -142,6 +142,11 @@ def discrete_levels(cfg, D, anat=False, groupwise=False):
     return levels, run_kw
 
 
+def features_gpu_enabled():
+    """MSMHIP_FEATURES=gpu: every level's features are prepared through one msm_level_features call; the same files are written"""
+    return os.environ.get("MSMHIP_FEATURES", "") == "gpu"
+
+
 def main_groupwise(a, surf_ext, data_ext):
     """CLI/newmsm.cpp:13-27 + Group_Mesh_registration (M/group_mesh_registration.h:46-82, .cpp:26-133)"""
     for flag in ("meshes", "template", "data"):
@@ -173,7 +178,9 @@ def main_groupwise(a, surf_ext, data_ext):
     ctx = M.Context(a.device)
     if a.verbose:
         print("This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
-    regs, level_regs, energies = group_registration.run_group_multiresolution(group_registration.ProductGroupOps(ctx), meshes, datas, txyz, ttri, levels, mask=mask,
+        if features_gpu_enabled():
+            print("Level features in one call on the GPU.")
+    regs, level_regs, energies = group_registration.run_group_multiresolution(group_registration.ProductGroupOps(ctx, features_gpu=features_gpu_enabled()), meshes, datas, txyz, ttri, levels, mask=mask,
                                                                               fixnan=cfg["fixnan"], **run_kw, **config.run_options(cfg))
     last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])[1]
     target = M.Mesh(ctx, txyz, ttri)
@@ -222,7 +229,9 @@ def main(argv):
         print("This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
         if mcmc_gpu_enabled():
             print("MCMC sweeps on the GPU.")
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled()), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+        if features_gpu_enabled():
+            print("Level features in one call on the GPU.")
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled()), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])
