@@ -353,6 +353,28 @@ int msm_mcmc_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcost
 /* What the last msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise on the context did: stats[0] ms in the sweep kernels (HIP events), [1] levels walked,
  * [2] ms the host spent drawing proposals, [3] chunks, [4] levels of one sweep, [5] the widest level. */
 int msm_mcmc_gpu_stats(msm_ctx *ctx, double stats[6]);
+/* K chains of msm_mcmc_optimise_gpu from one start, side by side in one launch per chunk (a workgroup per chain over the same two tables): chain k is
+ * msm_mcmc_optimise(..., seeds[k], ...) bit for bit.  labelings: K x N out (may be NULL); energies: K out (may be NULL); labeling (N): the start in,
+ * chain *best's labelling out (best may be NULL).  The energy of a chain is msm_mcmc_energy of its labelling, *best is msm_mcmc_best of the energies.
+ * 1 <= K <= 256 and seeds given, else MSM_ERR_INVALID; the other checks and messages are msm_mcmc_optimise_gpu's.  iters == 0 or T == 0: every chain
+ * is the start, *best = 0.  The K proposal streams are drawn on up to min(MSMHIP_HOST_THREADS, 16, K) host threads; MSMHIP_MCMC_CHUNK_SWEEPS counts
+ * sweeps per chain (default: half a million proposals per chain, at most 16 MB over all chains).  Afterwards msm_mcmc_gpu_stats gives [0] kernel ms,
+ * [1] levels walked by one chain, [2] wall ms of the threaded draw, [3] chunks, [4] and [5] as before. */
+int msm_mcmc_optimise_chains_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                                 double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings, double *energies,
+                                 int32_t *best);
+/* [host] The same over host tables: K runs of msm_mcmc_optimise from the one start (on the host worker threads), msm_mcmc_energy, msm_mcmc_best. */
+int msm_mcmc_optimise_chains(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
+                             int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best);
+/* [host] The table form of evaluateTotalCostSum (M/DiscreteCostFunction.cpp:55-77): (sum over i < N ascending, from 0.0, of unary[labeling[i] * N + i])
+ * + 0.0 + (sum over t < T ascending, from 0.0, of tcosts[t][la][lb][lc]). */
+int msm_mcmc_energy(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const int32_t *labeling,
+                    double *energy);
+/* [host] std::min_element's rule over K >= 1 energies: the first index no later energy is strictly smaller than (ties go to the lower index, a NaN never
+ * beats anything, nothing beats a NaN in slot 0). */
+int msm_mcmc_best(const double *energies, int32_t K, int32_t *best);
+/* Chains and host draw threads of the last msm_mcmc_optimise*_gpu / msm_cost_mcmc_optimise* call on the context (1 and 1 after a single-chain call). */
+int msm_mcmc_chains_info(msm_ctx *ctx, int32_t *K, int32_t *draw_threads);
 /* [host] The proposal stream both optimisers consume: out[s * T + t] is the label proposed to triplet t in sweep s (sweeps x T values), drawn in chunks of
  * chunk_sweeps whole sweeps (<= 0: one chunk); the stream does not depend on the chunking.  L > 65535: MSM_ERR_INVALID. */
 int msm_mcmc_proposals(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, int32_t chunk_sweeps, uint16_t *out);
@@ -467,6 +489,10 @@ int msm_cost_triplet_table(msm_cost *c, int32_t t0, int32_t t1, double *tcosts);
  * unary table's kernels and the triplet-table kernels fill device buffers (T * L^3 doubles for the latter), then the sweeps of msm_mcmc_optimise_gpu run
  * there.  The labelling (N, read and updated) is the one msm_cost_unary_table + msm_cost_triplet_table(0, T) + msm_mcmc_optimise give, bit for bit. */
 int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t seed, int32_t *labeling);
+/* msm_mcmc_optimise_chains_gpu over the cost function's own device tables, as msm_cost_mcmc_optimise: what msm_cost_unary_table +
+ * msm_cost_triplet_table(0, T) + msm_mcmc_optimise_chains give, bit for bit. */
+int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings,
+                                  double *energies, int32_t *best);
 /* evaluateTotalCostSum :55-77: parts = {unary, pairwise, triplet} sums in the reference's serial order */
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]);
 /* Optional HIP-event timing of the sampling kernel (k_unary_rays or k_unary_samples) of each unary-table launch, recorded on the

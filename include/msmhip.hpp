@@ -484,6 +484,57 @@ inline void mcmc_optimise_gpu(Context &ctx, const Matrix &unary_costs, const Mat
     check(msm_mcmc_optimise_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
                                 dist_param, mciters, seed, labeling.data()));
 }
+// what several chains from one start hand back: labelings chains x N, energies per chain, best by std::min_element's rule
+struct McmcChains {
+    std::vector<int32_t> labelings;
+    std::vector<double> energies;
+    int32_t best = 0;
+};
+// the level loops' seeds of one iteration: chain k takes seed + 1000003 k (chain 0 is the single-chain run's seed)
+inline std::vector<uint64_t> mcmc_chain_seeds(uint64_t seed, int chains) {
+    std::vector<uint64_t> s((size_t)chains);
+    for (int k = 0; k < chains; ++k) s[(size_t)k] = seed + (uint64_t)1000003 * (uint64_t)k;
+    return s;
+}
+// msm_mcmc_energy: the table form of evaluateTotalCostSum -- the unary terms, 0.0 and the triplet terms, each sum serial and ascending from 0.0
+inline double mcmc_energy(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
+                          const std::vector<int32_t> &labeling) {
+    double e = 0.0;
+    check(msm_mcmc_energy(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), labeling.data(), &e));
+    return e;
+}
+// msm_mcmc_best: std::min_element's index over the chains' energies
+inline int mcmc_best(const std::vector<double> &energies) {
+    int32_t best = 0;
+    check(msm_mcmc_best(energies.data(), (int32_t)energies.size(), &best));
+    return best;
+}
+// msm_mcmc_chains_info: {chains, host draw threads} of the context's last GPU sweeps
+inline std::pair<int, int> mcmc_chains_info(Context &ctx) {
+    int32_t chains = 0, threads = 0;
+    check(msm_mcmc_chains_info(ctx.handle(), &chains, &threads));
+    return {chains, threads};
+}
+// msm_mcmc_optimise_chains: seeds.size() runs of mcmc_optimise from the one start; labeling becomes the best chain's
+inline McmcChains mcmc_optimise_chains(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
+                                       double dist_param, int mciters, const std::vector<uint64_t> &seeds, std::vector<int32_t> &labeling) {
+    McmcChains r;
+    r.labelings.assign(seeds.size() * (size_t)num_nodes, 0);
+    r.energies.assign(seeds.size(), 0.0);
+    check(msm_mcmc_optimise_chains(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), dist_param,
+                                   mciters, seeds.data(), (int32_t)seeds.size(), labeling.data(), r.labelings.data(), r.energies.data(), &r.best));
+    return r;
+}
+// the same with every chain's sweeps on the GPU (msm_mcmc_optimise_chains_gpu: a workgroup per chain): the same labelings, energies and best
+inline McmcChains mcmc_optimise_chains_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes,
+                                           int num_labels, double dist_param, int mciters, const std::vector<uint64_t> &seeds, std::vector<int32_t> &labeling) {
+    McmcChains r;
+    r.labelings.assign(seeds.size() * (size_t)num_nodes, 0);
+    r.energies.assign(seeds.size(), 0.0);
+    check(msm_mcmc_optimise_chains_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
+                                       dist_param, mciters, seeds.data(), (int32_t)seeds.size(), labeling.data(), r.labelings.data(), r.energies.data(), &r.best));
+    return r;
+}
 
 // The stand-in for the binary solve of one label step of Fusion::optimize (msm_fusion_icm_step: iterated conditional modes, NOT ELC +
 // FastPD): x[node] = 1 where the proposed label is taken.  unary2 N x 2 (may be empty: no unary costs), quads P x 4, octets T x 8.
@@ -594,6 +645,15 @@ public:
     // computeUnaryCosts() + computeTripletCosts() + mcmc_optimise give, bit for bit
     void mcmc_optimise(double dist_param, int mciters, uint64_t seed, std::vector<int32_t> &labeling) {
         check(msm_cost_mcmc_optimise(h_, dist_param, mciters, seed, labeling.data()));
+    }
+    // the same for seeds.size() chains side by side over the same device tables (msm_cost_mcmc_optimise_chains); labeling becomes the best chain's
+    McmcChains mcmc_optimise_chains(double dist_param, int mciters, const std::vector<uint64_t> &seeds, std::vector<int32_t> &labeling) {
+        McmcChains r;
+        r.labelings.assign(seeds.size() * labeling.size(), 0);
+        r.energies.assign(seeds.size(), 0.0);
+        check(msm_cost_mcmc_optimise_chains(h_, dist_param, mciters, seeds.data(), (int32_t)seeds.size(), labeling.data(), r.labelings.data(), r.energies.data(),
+                                            &r.best));
+        return r;
     }
     // the batched forms the optimisers' loops collapse to (I/Fusion/Fusion.h:138-196)
     std::vector<double> computeTripletCost(const std::vector<int32_t> &t, const std::vector<int32_t> &a, const std::vector<int32_t> &b,

@@ -60,6 +60,9 @@ struct LevelOptions {
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
+    // the MCMC branch runs this many chains per iteration from the one labelling (chain k seeded with seed + it + 1000003 k) and keeps the one with the
+    // lowest energy (msm_cost_mcmc_optimise_chains with mcmc_gpu, msm_mcmc_optimise_chains without: the same labelling); 1: the single run
+    int mcmc_chains = 1;
     // the level's features for both data sets through one msm_level_features call (level_features_batch: the masked list surgery and create_exclusion on
     // the device) instead of the chain of calls of level_features / finish_features: the same bytes (what MSMHIP_FEATURES=gpu asks of the executables)
     bool features_gpu = false;
@@ -225,10 +228,18 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
             PhaseClock::timed(clock, "pairwise_table", [&] { costfct.computePairwiseCosts(); });
             PhaseClock::timed(clock, "optimiser", [&] { pairwise_icm(costfct.unarycosts, costfct.paircosts, pairs, N, L, labeling, 100); });
         } else if (mcmc_gpu) {  // ---- MCMC with the tables and the sweeps on the device: the labeling of the branch below
-            PhaseClock::timed(clock, "optimiser", [&] { costfct.mcmc_optimise(o.mcparam, o.mciters, o.seed + (uint64_t)it, labeling); });
+            if (o.mcmc_chains > 1)
+                PhaseClock::timed(clock, "optimiser", [&] { costfct.mcmc_optimise_chains(o.mcparam, o.mciters, mcmc_chain_seeds(o.seed + (uint64_t)it, o.mcmc_chains), labeling); });
+            else
+                PhaseClock::timed(clock, "optimiser", [&] { costfct.mcmc_optimise(o.mcparam, o.mciters, o.seed + (uint64_t)it, labeling); });
         } else {  // ---- MCMC: computeUnaryCosts, computeTripletCosts, optimise
             const std::vector<double> tcosts = PhaseClock::timed(clock, "triplet_table", [&] { return costfct.computeTripletCosts(); });
-            PhaseClock::timed(clock, "optimiser", [&] { mcmc_optimise(costfct.unarycosts, tcosts, triplets, N, L, o.mcparam, o.mciters, o.seed + (uint64_t)it, labeling); });
+            if (o.mcmc_chains > 1)
+                PhaseClock::timed(clock, "optimiser", [&] {
+                    mcmc_optimise_chains(costfct.unarycosts, tcosts, triplets, N, L, o.mcparam, o.mciters, mcmc_chain_seeds(o.seed + (uint64_t)it, o.mcmc_chains), labeling);
+                });
+            else
+                PhaseClock::timed(clock, "optimiser", [&] { mcmc_optimise(costfct.unarycosts, tcosts, triplets, N, L, o.mcparam, o.mciters, o.seed + (uint64_t)it, labeling); });
         }
         res.energies.push_back(PhaseClock::timed(clock, "total_cost", [&] { return costfct.evaluateTotalCostSum(labeling); }));
         res.labelings.push_back(labeling);

@@ -712,6 +712,86 @@ def mcmc_optimise_gpu(ctx, unary, tcosts, triplets, labeling, mcparam=0.8, iters
     return lab
 
 
+def _chain_args(seeds, N):
+    """(seeds array or None, its pointer or NULL, K, labelings K x N, energies K) of a chains call; seeds=None passes a NULL pointer with K = 1"""
+    c_u64p = C.POINTER(C.c_uint64)
+    if seeds is None:
+        sd, ps, K = None, C.cast(None, c_u64p), 1
+    else:
+        sd = np.ascontiguousarray(np.atleast_1d(seeds), dtype=np.uint64)
+        ps, K = sd.ctypes.data_as(c_u64p), len(sd)
+    return sd, ps, K, np.zeros((K, N), dtype=np.int32), np.zeros(K)
+
+
+def mcmc_optimise_chains(unary, tcosts, triplets, labeling, seeds, mcparam=0.8, iters=100):
+    """msm_mcmc_optimise_chains: len(seeds) runs of mcmc_optimise from the one start; returns (the best chain's labeling, labelings K x N, energies K, best)"""
+    U, pu = _d(unary)
+    L, N = U.shape
+    tc, ptc = _d(tcosts)
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    T = tr.shape[0]
+    assert tc.size == T * L ** 3
+    lab = np.array(labeling, dtype=np.int32)
+    sd, ps, K, labs, E = _chain_args(seeds, N)
+    best = C.c_int32(-1)
+    check(lib().msm_mcmc_optimise_chains(pu, ptc, tr.ctypes.data_as(c_ip), N, L, T, float(mcparam), int(iters), ps, K, lab.ctypes.data_as(c_ip),
+                                         labs.ctypes.data_as(c_ip), E.ctypes.data_as(c_dp), C.byref(best)))
+    return lab, labs, E, best.value
+
+
+def mcmc_optimise_chains_gpu(ctx, unary, tcosts, triplets, labeling, seeds, mcparam=0.8, iters=100):
+    """msm_mcmc_optimise_chains_gpu: mcmc_optimise_chains with every chain's sweeps on the GPU, a workgroup per chain in one launch per chunk; the
+    same labelings, energies and best, bit for bit"""
+    U, pu = _d(unary)
+    L, N = U.shape
+    tc, ptc = _d(tcosts)
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    T = tr.shape[0]
+    assert tc.size == T * L ** 3
+    lab = np.array(labeling, dtype=np.int32)
+    sd, ps, K, labs, E = _chain_args(seeds, N)
+    best = C.c_int32(-1)
+    check(lib().msm_mcmc_optimise_chains_gpu(ctx.h, pu, ptc, tr.ctypes.data_as(c_ip), N, L, T, float(mcparam), int(iters), ps, K, lab.ctypes.data_as(c_ip),
+                                             labs.ctypes.data_as(c_ip), E.ctypes.data_as(c_dp), C.byref(best)))
+    return lab, labs, E, best.value
+
+
+def mcmc_energy(unary, tcosts, triplets, labeling):
+    """msm_mcmc_energy: the table form of evaluateTotalCostSum -- the unary terms, 0.0 and the triplet terms, each sum serial and ascending from 0.0"""
+    U, pu = _d(unary)
+    L, N = U.shape
+    tc, ptc = _d(tcosts)
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    T = tr.shape[0]
+    assert tc.size == T * L ** 3
+    lab = np.ascontiguousarray(labeling, dtype=np.int32)
+    assert lab.shape == (N,)
+    e = C.c_double()
+    check(lib().msm_mcmc_energy(pu, ptc, tr.ctypes.data_as(c_ip), N, L, T, lab.ctypes.data_as(c_ip), C.byref(e)))
+    return e.value
+
+
+def mcmc_best(energies):
+    """msm_mcmc_best: std::min_element's index over the chains' energies (ties to the lower index; a NaN never wins but stays in slot 0)"""
+    E, pe = _d(np.atleast_1d(energies))
+    best = C.c_int32(-1)
+    check(lib().msm_mcmc_best(pe, E.size, C.byref(best)))
+    return best.value
+
+
+def mcmc_chains_info(ctx):
+    """msm_mcmc_chains_info: (chains, host draw threads) of the context's last GPU sweeps"""
+    K, threads = C.c_int32(), C.c_int32()
+    check(lib().msm_mcmc_chains_info(ctx.h, C.byref(K), C.byref(threads)))
+    return K.value, threads.value
+
+
+def chain_seeds(seed, it, chains):
+    """the level loops' seeds of iteration `it`: chain k takes seed + it + 1000003 k (chain 0 is the single-chain run's seed; distinct in their low 32 bits,
+    which is what the engine keeps, for k < 256)"""
+    return [(int(seed) + int(it) + 1000003 * k) & 0xFFFFFFFFFFFFFFFF for k in range(int(chains))]
+
+
 def mcmc_gpu_stats(ctx):
     """msm_mcmc_gpu_stats of the context's last GPU sweeps: dict(kernel_ms, levels, draw_ms, chunks, levels_per_sweep, widest_level)"""
     s = np.zeros(6)
@@ -964,6 +1044,17 @@ class DiscreteCostFunction:
         assert lab.shape == (self.N,)
         check(lib().msm_cost_mcmc_optimise(self.h, float(mcparam), int(iters), int(seed), lab.ctypes.data_as(c_ip)))
         return lab
+
+    def mcmc_optimise_chains(self, labeling, seeds, mcparam=0.8, iters=100):
+        """msm_cost_mcmc_optimise_chains: mcmc_optimise for len(seeds) chains side by side over the same device tables; returns (the best chain's
+        labeling, labelings K x N, energies K, best) -- what the fetched tables and api.mcmc_optimise_chains give, bit for bit"""
+        lab = np.array(labeling, dtype=np.int32)
+        assert lab.shape == (self.N,)
+        sd, ps, K, labs, E = _chain_args(seeds, self.N)
+        best = C.c_int32(-1)
+        check(lib().msm_cost_mcmc_optimise_chains(self.h, float(mcparam), int(iters), ps, K, lab.ctypes.data_as(c_ip), labs.ctypes.data_as(c_ip),
+                                                  E.ctypes.data_as(c_dp), C.byref(best)))
+        return lab, labs, E, best.value
 
     def computePairwiseCost(self, pair, la, lb):
         p, pp = _i(np.atleast_1d(pair))

@@ -643,6 +643,28 @@ int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t 
     return mcmc_run_device(ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seed, labeling);
 }
 
+// the same for K chains from one start (mcmc.cpp: mcmc_run_device_chains); the tables are built once and shared
+int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings,
+                                  double *energies, int32_t *best) {
+    if (!c || !labeling || iters < 0) return fail(MSM_ERR_INVALID, "msm_cost_mcmc_optimise: bad arguments");
+    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mcmc_optimise: meshes, labels and triplets must be set first");
+    MSM_TRY(mcmc_check_chains(seeds, K));
+    MSM_TRY(mcmc_check_arguments(c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), mcparam, labeling));
+    MSM_TRY(msm_cost_unary_table_async(c));
+    MSM_TRY(check_status(c->ctx, "computeUnaryCosts"));
+    CliqueArgs a;
+    MSM_TRY(clique_args(c, true, false, a));
+    msm_ctx *ctx = c->ctx;
+    const int N = a.N, L = a.L, T = a.T;
+    const size_t per = (size_t)L * L * L, total = (size_t)T * per;
+    if (c->d_clique_out.ensure(total ? total : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * total);
+    const int step = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, ((size_t)1 << 31) / per));
+    for (int t0 = 0; t0 < T; t0 += step) MSM_TRY(launch_triplet_table(ctx, a, t0, std::min(T, t0 + step), c->d_clique_out.p + (size_t)t0 * per));
+    c->counters[2] += (int64_t)total;
+    MSM_TRY(check_status(ctx, "computeTripletCosts"));
+    return mcmc_run_device_chains(ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
+}
+
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on
 // the host over device-evaluated terms (N + P + T values), because the order defines the reported energy
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]) {

@@ -1,5 +1,6 @@
 // mcmc.cpp -- the host side of the Monte Carlo optimiser's GPU sweeps (mcmc.hpp; kernel: mcmc_kernels.hip): the level schedule, the
-// proposal stream in chunks of whole sweeps, and the loop that draws chunk k + 1 while the device walks chunk k.
+// proposal stream in chunks of whole sweeps, and the loop that draws chunk k + 1 while the device walks chunk k; the same for several chains from one
+// start (their streams drawn on the host workers, their energies summed here, the best one kept), and the host-only chains, energy and selection.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,12 @@ int mcmc_check_arguments(const int32_t *triplets, int N, int L, int T, double mc
     return MSM_OK;
 }
 
+int mcmc_check_chains(const uint64_t *seeds, int K) {
+    if (K < 1 || K > kMcmcMaxChains) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains: %d chains (1 to %d)", K, kMcmcMaxChains);
+    if (!seeds) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains: null seeds");
+    return MSM_OK;
+}
+
 }  // namespace msm
 
 namespace {
@@ -28,8 +35,10 @@ struct McmcScratch {
     DevBuf<int4> sched;
     DevBuf<int32_t> level_off, labeling;
     DevBuf<uint16_t> prop;
+    DevBuf<double> terms;        // K x (N + T) terms of the chains' energies
     std::vector<hipEvent_t> ev;  // a pair per chunk
     double stats[6] = {0, 0, 0, 0, 0, 0};
+    int chains = 1, draw_threads = 1;  // of the last call
     ~McmcScratch() {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
@@ -138,6 +147,108 @@ int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const i
     s.stats[3] = chunks;
     s.stats[4] = sch.levels();
     s.stats[5] = sch.widest();
+    s.chains = s.draw_threads = 1;
+    return MSM_OK;
+}
+
+int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters,
+                           const uint64_t *seeds, int K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best) {
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
+    McmcScratch &s = mcmc_scratch(ctx);
+    const bool sweep = iters > 0 && T > 0;  // otherwise every chain is the start: only the energies are computed
+    McmcSchedule sch;
+    mcmc_build_schedule(triplets, N, T, sch);
+    std::vector<int4> rec((size_t)T);
+    std::vector<int32_t> pos((size_t)T);  // where triplet t stands in the schedule
+    for (int i = 0; i < T; ++i) {
+        const int t = sch.order[(size_t)i];
+        rec[(size_t)i] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
+        pos[(size_t)t] = i;
+    }
+    long asked = 0;
+    if (const char *e = std::getenv("MSMHIP_MCMC_CHUNK_SWEEPS")) asked = std::atol(e);
+    const int chunk = mcmc_chunk_sweeps(asked, T, std::max(iters, 1), K);
+    const int chunks = sweep ? (iters + chunk - 1) / chunk : 0;
+    const int threads = mcmc_draw_threads(K);
+    const size_t per_chunk = (size_t)K * chunk * T, nterms = (size_t)N + T;
+    std::vector<int32_t> labs((size_t)K * N);
+    for (int k = 0; k < K; ++k) std::copy(labeling, labeling + N, labs.begin() + (size_t)k * N);
+    MSM_TRY(s.sched.upload_vec(rec, ctx));
+    MSM_TRY(s.level_off.upload_vec(sch.level_off, ctx));
+    MSM_TRY(s.labeling.upload_vec(labs, ctx));
+    if (s.prop.ensure(std::max<size_t>(per_chunk, 1)) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * per_chunk);
+    if (s.terms.ensure((size_t)K * nterms) != hipSuccess) return stage_alloc_failed(sizeof(double) * (size_t)K * nterms);
+    while (s.ev.size() < 2 * (size_t)chunks) {
+        hipEvent_t e;
+        MSM_HIP(hipEventCreate(&e));
+        s.ev.push_back(e);
+    }
+    McmcChainArgs c;
+    McmcArgs &a = c.a;
+    a.U = d_U;
+    a.tc = d_tc;
+    a.sched = s.sched.p;
+    a.level_off = s.level_off.p;
+    a.prop = s.prop.p;
+    a.labeling = s.labeling.p;
+    a.N = N;
+    a.L = L;
+    a.T = T;
+    a.levels = sch.levels();
+    a.sweeps = 0;
+    a.status = ctx->d_status;
+    c.chains = K;
+    c.chunk_sweeps = chunk;
+    double draw_ms = 0.0;
+    if (sweep) {
+        McmcChainStreams streams(seeds, K, mcparam, L);
+        std::vector<uint16_t> buf(per_chunk);
+        // a chunk of every chain in the kernel's layout, the chains spread over the host workers; the wall clock of the threaded draw
+        auto draw = [&](int sweeps) {
+            const auto t0 = std::chrono::steady_clock::now();
+            streams.draw(buf.data(), chunk, sweeps, T, pos.data(), threads);
+            draw_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        };
+        draw(std::min(chunk, iters));
+        for (int k = 0, done = 0; k < chunks; ++k) {
+            const int sweeps = std::min(chunk, iters - done);
+            // behind the previous chunk's kernel on the stream, as in mcmc_run_device; a short last chunk leaves the tail of every chain's block unread
+            MSM_TRY(upload_in_pieces(ctx, s.prop.p, buf.data(), sizeof(uint16_t) * (sweeps == chunk ? per_chunk : ((size_t)(K - 1) * chunk + sweeps) * T)));
+            a.sweeps = sweeps;
+            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
+            MSM_TRY(launch_mcmc_chains(ctx, c));
+            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
+            done += sweeps;
+            if (done < iters) draw(std::min(chunk, iters - done));  // while the device walks chunk k
+        }
+    }
+    MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.terms.p));
+    std::vector<double> terms((size_t)K * nterms);
+    MSM_TRY(s.labeling.download(labs.data(), labs.size(), ctx));
+    MSM_TRY(s.terms.download(terms.data(), terms.size(), ctx));
+    MSM_TRY(check_status(ctx, "msm_mcmc_optimise_chains_gpu"));
+    std::vector<double> E((size_t)K);
+    for (int k = 0; k < K; ++k) E[(size_t)k] = mcmc_energy_of_terms(terms.data() + (size_t)k * nterms, N, T);
+    const int b = mcmc_best_chain(E.data(), K);
+    std::copy(labs.begin() + (size_t)b * N, labs.begin() + (size_t)(b + 1) * N, labeling);
+    if (labelings) std::copy(labs.begin(), labs.end(), labelings);
+    if (energies) std::copy(E.begin(), E.end(), energies);
+    if (best) *best = b;
+    double kernel_ms = 0.0;
+    for (int k = 0; k < chunks; ++k) {
+        float ms = 0.f;
+        MSM_HIP(hipEventElapsedTime(&ms, s.ev[2 * (size_t)k], s.ev[2 * (size_t)k + 1]));
+        kernel_ms += ms;
+    }
+    s.stats[0] = kernel_ms;
+    s.stats[1] = sweep ? (double)iters * sch.levels() : 0.0;
+    s.stats[2] = draw_ms;
+    s.stats[3] = chunks;
+    s.stats[4] = sch.levels();
+    s.stats[5] = sch.widest();
+    s.chains = K;
+    s.draw_threads = threads;
     return MSM_OK;
 }
 
@@ -162,6 +273,75 @@ int msm_mcmc_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcost
     MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
     MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
     return mcmc_run_device(ctx, s.U.p, s.tc.p, triplets, N, L, T, mcparam, iters, seed, labeling);
+}
+
+int msm_mcmc_optimise_chains_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                                 double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings, double *energies,
+                                 int32_t *best) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains_gpu: null context");
+    if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
+    MSM_TRY(mcmc_check_chains(seeds, K));
+    MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    McmcScratch &s = mcmc_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L;
+    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
+    if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
+    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
+    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
+    return mcmc_run_device_chains(ctx, s.U.p, s.tc.p, triplets, N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
+}
+
+int msm_mcmc_optimise_chains(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
+                             int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best) {
+    if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
+    MSM_TRY(mcmc_check_chains(seeds, K));
+    MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
+    // K runs of the host optimiser from the one start, a chain per task on the host workers: a chain's result depends on its seed alone
+    std::vector<int32_t> labs((size_t)K * N);
+    std::vector<double> E((size_t)K);
+    parallel_for(K, mcmc_draw_threads(K), [&](int k) {
+        int32_t *lab = labs.data() + (size_t)k * N;
+        std::copy(labeling, labeling + N, lab);
+        mcmc_sweeps_host(unary, tcosts, triplets, N, L, T, mcparam, iters, seeds[k], lab);
+        std::vector<double> terms((size_t)N + T);
+        mcmc_energy_terms(unary, tcosts, triplets, N, L, T, lab, terms.data());
+        E[(size_t)k] = mcmc_energy_of_terms(terms.data(), N, T);
+    });
+    const int b = mcmc_best_chain(E.data(), K);
+    std::copy(labs.begin() + (size_t)b * N, labs.begin() + (size_t)(b + 1) * N, labeling);
+    if (labelings) std::copy(labs.begin(), labs.end(), labelings);
+    if (energies) std::copy(E.begin(), E.end(), energies);
+    if (best) *best = b;
+    return MSM_OK;
+}
+
+int msm_mcmc_energy(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const int32_t *labeling, double *energy) {
+    if (!unary || !labeling || !energy || N <= 0 || L <= 0 || T < 0 || (T > 0 && (!tcosts || !triplets))) return fail(MSM_ERR_INVALID, "msm_mcmc_energy: bad arguments");
+    for (int i = 0; i < N; ++i)
+        if (labeling[i] < 0 || labeling[i] >= L) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: label of node %d out of range", i);
+    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
+        if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
+    std::vector<double> terms((size_t)N + T);
+    mcmc_energy_terms(unary, tcosts, triplets, N, L, T, labeling, terms.data());
+    *energy = mcmc_energy_of_terms(terms.data(), N, T);
+    return MSM_OK;
+}
+
+int msm_mcmc_best(const double *energies, int32_t K, int32_t *best) {
+    if (!energies || !best || K < 1) return fail(MSM_ERR_INVALID, "msm_mcmc_best: bad arguments");
+    *best = mcmc_best_chain(energies, K);
+    return MSM_OK;
+}
+
+int msm_mcmc_chains_info(msm_ctx *ctx, int32_t *K, int32_t *draw_threads) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_chains_info: null argument");
+    if (K) *K = mcmc_scratch(ctx).chains;
+    if (draw_threads) *draw_threads = mcmc_scratch(ctx).draw_threads;
+    return MSM_OK;
 }
 
 int msm_mcmc_gpu_stats(msm_ctx *ctx, double stats[6]) {

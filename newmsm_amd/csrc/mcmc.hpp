@@ -22,10 +22,29 @@ struct McmcArgs {
 };
 int launch_mcmc_sweeps(msm_ctx *ctx, const McmcArgs &a);
 
+// K chains side by side, workgroup k walks chain k: a.labeling holds K x N labels, a.prop the chunk of every chain, sweep s of chain k at
+// ((size_t)k * chunk_sweeps + s) * T; the schedule and both tables are shared.  (McmcArgs itself stays as k_mcmc_sweeps takes it.)
+constexpr int kMcmcMaxChains = 256;
+struct McmcChainArgs {
+    McmcArgs a;
+    int chains, chunk_sweeps;
+};
+int launch_mcmc_chains(msm_ctx *ctx, const McmcChainArgs &c);
+// the terms of every chain's energy, terms[k * (N + T) + ...]: U[lab[i] * N + i] for i < N, then tc[t][la][lb][lc] for t < T (a.sweeps, a.prop unused)
+int launch_mcmc_chain_terms(msm_ctx *ctx, const McmcChainArgs &c, double *terms);
+
 // `iters` sweeps on the device over tables that lie there (d_U: L x N, d_tc: T x L^3); labeling (host, N) is read and updated.  The arguments have been
 // checked by the caller (mcmc_check_arguments).  Complete on return.
 int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
                     int32_t *labeling);
+// The same for K chains from one start (chain k: seeds[k]; chain 0 is mcmc_run_device with seeds[0]).  labelings (host, K x N) and energies (host, K) may
+// be null; labeling (host, N) is the start and receives chain *best's labelling (best may be null).  1 <= K <= kMcmcMaxChains, checked by the caller.
+int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters,
+                           const uint64_t *seeds, int K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best);
+int mcmc_check_chains(const uint64_t *seeds, int K);  // 1 <= K <= kMcmcMaxChains and seeds given, or MSM_ERR_INVALID
+// the sweeps of msm_mcmc_optimise over checked arguments (regtools.cpp)
+void mcmc_sweeps_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
+                      int32_t *labeling);
 // the checks of msm_mcmc_optimise on mcparam, the labeling and the triplets, with its messages
 int mcmc_check_arguments(const int32_t *triplets, int N, int L, int T, double mcparam, const int32_t *labeling);
 

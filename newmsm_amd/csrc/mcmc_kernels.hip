@@ -9,6 +9,9 @@
 // A level is a chain of dependent latencies and nothing else: barrier, schedule record and proposal (L2), three labels (LDS), fourteen table values (L2 /
 // HBM), the labels written back.  (Fetching the next level's record and proposal ahead of the barrier was tried and measured: 2.02 against 2.04 us per
 // level at ico4, not told apart; the plain loop stays.)
+//
+// Several chains (k_mcmc_chains, k_mcmc_chain_terms; DESIGN.md 5.16 "Chains"): K workgroups, each the loop above on a labelling and a proposal stream of
+// its own over the shared schedule and tables; they exchange nothing.  The terms of every chain's energy are written out and summed on the host.
 #include "mcmc.hpp"
 
 namespace msm {
@@ -83,6 +86,73 @@ __global__ __launch_bounds__(kMcmcThreads) void k_mcmc_sweeps(McmcArgs a) {
     for (int i = tid; i < a.N; i += kMcmcThreads) a.labeling[i] = (int)s_lab[i];
 }
 
+// K chains: workgroup k is k_mcmc_sweeps on chain k's labelling and proposals, over the shared schedule and tables.  The workgroups never meet: no atomic
+// but the status word's on the error path, every loop bounded by the host's counts.
+__global__ __launch_bounds__(kMcmcThreads) void k_mcmc_chains(McmcChainArgs c) {
+    extern __shared__ __align__(16) uint16_t s_lab[];  // N labels of this chain
+    const McmcArgs &a = c.a;
+    const int tid = (int)threadIdx.x, k = (int)blockIdx.x;
+    if (k >= c.chains) return;  // (the whole workgroup)
+    int32_t *__restrict__ labeling = a.labeling + (size_t)k * a.N;
+    for (int i = tid; i < a.N; i += kMcmcThreads) {
+        int l = labeling[i];
+        if ((unsigned)l >= (unsigned)a.L) {
+            raise_status(a.status, MSM_ERR_INVALID);
+            l = 0;
+        }
+        s_lab[i] = (uint16_t)l;
+    }
+    __syncthreads();
+    for (int s = 0; s < a.sweeps; ++s) {
+        const uint16_t *__restrict__ prop = a.prop + ((size_t)k * c.chunk_sweeps + s) * a.T;  // this chain's proposals for sweep s of the chunk
+        for (int lv = 0; lv < a.levels; ++lv) {
+            const int begin = a.level_off[lv], end = a.level_off[lv + 1];
+            for (int i = begin + tid; i < end; i += kMcmcThreads) mcmc_visit(a, s_lab, a.sched[i], prop[i]);
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < a.N; i += kMcmcThreads) labeling[i] = (int)s_lab[i];
+}
+
+// the N + T terms of every chain's energy, a term per thread; they are summed on the host in the reference's order
+__global__ __launch_bounds__(256) void k_mcmc_chain_terms(McmcChainArgs c, double *__restrict__ terms) {
+    const McmcArgs &a = c.a;
+    const int k = (int)blockIdx.y;
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= c.chains || j >= (long)a.N + a.T) return;
+    const unsigned N = (unsigned)a.N, L = (unsigned)a.L;
+    const int32_t *__restrict__ lab = a.labeling + (size_t)k * a.N;
+    double *__restrict__ out = terms + (size_t)k * ((size_t)a.N + a.T);
+    if (j < (long)a.N) {
+        const unsigned l = (unsigned)lab[j];
+        if (l >= L) {
+            raise_status(a.status, MSM_ERR_INVALID);
+            out[j] = 0.0;
+            return;
+        }
+        out[j] = a.U[(size_t)l * N + (size_t)j];
+        return;
+    }
+    const int4 r = a.sched[j - a.N];  // {triplet, node A, node B, node C}: the term goes to the triplet's place in list order
+    if ((unsigned)r.x >= (unsigned)a.T) {
+        raise_status(a.status, MSM_ERR_INVALID);
+        return;
+    }
+    if ((unsigned)r.y >= N || (unsigned)r.z >= N || (unsigned)r.w >= N) {
+        raise_status(a.status, MSM_ERR_INVALID);
+        out[(size_t)a.N + r.x] = 0.0;
+        return;
+    }
+    const unsigned la = (unsigned)lab[r.y], lb = (unsigned)lab[r.z], lc = (unsigned)lab[r.w];
+    if (la >= L || lb >= L || lc >= L) {
+        raise_status(a.status, MSM_ERR_INVALID);
+        out[(size_t)a.N + r.x] = 0.0;
+        return;
+    }
+    const size_t L1 = (size_t)L, L2 = L1 * L1, L3 = L2 * L1;
+    out[(size_t)a.N + r.x] = a.tc[(size_t)r.x * L3 + (size_t)la * L2 + (size_t)lb * L1 + lc];
+}
+
 }  // namespace
 
 int launch_mcmc_sweeps(msm_ctx *ctx, const McmcArgs &a) {
@@ -91,6 +161,27 @@ int launch_mcmc_sweeps(msm_ctx *ctx, const McmcArgs &a) {
     const size_t lds = (sizeof(uint16_t) * (size_t)a.N + 15) & ~(size_t)15;
     if (lds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mcmc_sweeps), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_mcmc_sweeps, dim3(1), dim3(kMcmcThreads), lds, ctx->stream, a);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_mcmc_chains(msm_ctx *ctx, const McmcChainArgs &c) {
+    const McmcArgs &a = c.a;
+    if (a.sweeps <= 0 || a.T <= 0 || a.levels <= 0) return MSM_OK;
+    if (c.chains < 1 || c.chains > kMcmcMaxChains || a.sweeps > c.chunk_sweeps) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains_gpu: bad launch (%d chains, %d sweeps of %d)", c.chains, a.sweeps, c.chunk_sweeps);
+    if (a.N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", a.N, kMcmcMaxNodes);
+    const size_t lds = (sizeof(uint16_t) * (size_t)a.N + 15) & ~(size_t)15;
+    if (lds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mcmc_chains), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_mcmc_chains, dim3((unsigned)c.chains), dim3(kMcmcThreads), lds, ctx->stream, c);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_mcmc_chain_terms(msm_ctx *ctx, const McmcChainArgs &c, double *terms) {
+    const McmcArgs &a = c.a;
+    if (c.chains < 1 || c.chains > kMcmcMaxChains || a.N <= 0 || a.T < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains_gpu: bad launch (%d chains)", c.chains);
+    const long n = (long)a.N + a.T;
+    hipLaunchKernelGGL(k_mcmc_chain_terms, dim3((unsigned)((n + 255) / 256), (unsigned)c.chains), dim3(256), 0, ctx->stream, c, terms);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

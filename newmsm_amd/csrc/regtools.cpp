@@ -136,6 +136,15 @@ int msm_mcmc_optimise(const double *unary, const double *tcosts, const int32_t *
                       int32_t iters, uint64_t seed, int32_t *labeling) {
     if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
     MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
+    mcmc_sweeps_host(unary, tcosts, triplets, N, L, T, mcparam, iters, seed, labeling);
+    return MSM_OK;
+}
+
+}  // extern "C"
+
+// the sweeps themselves, for msm_mcmc_optimise and for every chain of msm_mcmc_optimise_chains (mcmc.cpp)
+void msm::mcmc_sweeps_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
+                           int32_t *labeling) {
     McmcProposals proposals(seed, mcparam, L);  // the stream the GPU sweeps consume too (mcmc.hpp)
     const size_t L2 = (size_t)L * L, L3 = L2 * L;
     double costs[8];
@@ -156,8 +165,9 @@ int msm_mcmc_optimise(const double *unary, const double *tcosts, const int32_t *
             if (best & 2) labeling[node[1]] = label;
             if (best & 1) labeling[node[2]] = label;
         }
-    return MSM_OK;
 }
+
+extern "C" {
 
 int msm_fusion_icm_step(const double *unary2, const double *quads, const int32_t *pairs, int32_t P, const double *octets, const int32_t *triplets, int32_t T,
                         int32_t N, int32_t max_passes, int32_t *x) {

@@ -159,6 +159,9 @@ class ProductOps:
     def mcmc(self, unary, tcosts, triplets, labeling, mcparam, iters, seed):
         return api.mcmc_optimise(unary, tcosts, triplets, labeling, mcparam=mcparam, iters=iters, seed=seed)
 
+    def mcmc_chains(self, unary, tcosts, triplets, labeling, mcparam, iters, seeds):
+        return api.mcmc_optimise_chains(unary, tcosts, triplets, labeling, seeds, mcparam=mcparam, iters=iters)[0]
+
     def fusion_step(self, unary2, octets, triplets, passes, quads=None, pairs=None):
         return api.fusion_icm_step(unary2, octets, triplets, passes, quads=quads, pairs=pairs)
 
@@ -243,6 +246,9 @@ class _ProductCost:
 
     def mcmc_optimise(self, labeling, mcparam, iters, seed):
         return self.cf.mcmc_optimise(labeling, mcparam=mcparam, iters=iters, seed=seed)
+
+    def mcmc_optimise_chains(self, labeling, mcparam, iters, seeds):
+        return self.cf.mcmc_optimise_chains(labeling, seeds, mcparam=mcparam, iters=iters)[0]
 
     def total(self, labeling):
         return self.cf.evaluateTotalCostSum(labeling)[0]
@@ -429,7 +435,7 @@ def usable_transformed(trans_xyz, in_xyz):
 def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source_tri, src_feat, sph_reg, cp_order, *, sg_order=None,
                        iters=3, mciters=200, mcparam=0.8, seed=0, kind="univariate", simmeasure=2, rmode=3, labeldist=0.5,
                        rescale_labels=False, cost_params=None, timings=None, cp_start=None, in_weight=None, ref_weight=None,
-                       optimiser="mcmc", icm_passes=5, converge=False, anat=None, speculate=True):
+                       optimiser="mcmc", icm_passes=5, converge=False, anat=None, speculate=True, mcmc_chains=1):
     """Runs `iters` iterations of run_discrete_opt for one level.  optimiser: "mcmc" -- the reference's Monte Carlo optimiser over the
     unary and T x L^3 triplet tables (M/mcmc_opt.h:31-134) -- or "fusion": the label loop of Fusion::optimize (I/Fusion/Fusion.h:136-229: two
     sweeps over the labels, per label step 2 N unary and 8 T triplet costs -- ONE fusion-move call on the MI355X path --, nodes that the
@@ -447,6 +453,9 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
     cost-function weightings of the moving and the reference data at this resolution (SPHin_CFWEIGHTING / SPHref_CFWEIGHTING);
     with both given every iteration resamples the reference weighting onto the moving sphere and averages the two
     (combine_weighting, M/mesh_registration.cpp:234-248), otherwise the weighting is all ones.
+    mcmc_chains (optimiser "mcmc"): every iteration runs this many chains from the one labelling, chain k seeded with seed + it + 1000003 k
+    (api.chain_seeds), and keeps the labelling with the lowest table energy (ops' cost.mcmc_optimise_chains with ops.mcmc_gpu, ops.mcmc_chains
+    over the fetched tables without: the same labelling); 1 is the single run.
     speculate (fusion loop): queue the next label step's evaluations while the host solves the current one (ops' cost.prefetch_octets, if it has one).
     anat (rmode 4 / 5, aMSM): dict(order, in_anat, in_mesh, ref_anat, ref_mesh) -- --anatgrid of this level and the input / reference anatomical
     surfaces (V x 3) with the spheres (ops meshes) whose vertices they share (MESHES[0] / MESHES[1]).  initialize_level (M/mesh_registration.cpp:
@@ -547,10 +556,16 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
             paircosts = timed("pairwise_table", cost.pairwise_table)
             labeling = timed("optimiser", ops.pairwise_solve, unary, paircosts, pairs, 100)
         elif mcmc_gpu:  # --- MCMC with the tables and the sweeps on the device: the labeling of the branch below, bit for bit
-            labeling = timed("optimiser", cost.mcmc_optimise, labeling, mcparam, mciters, seed + it)
+            if mcmc_chains > 1:
+                labeling = timed("optimiser", cost.mcmc_optimise_chains, labeling, mcparam, mciters, api.chain_seeds(seed, it, mcmc_chains))
+            else:
+                labeling = timed("optimiser", cost.mcmc_optimise, labeling, mcparam, mciters, seed + it)
         else:  # --- MCMC: computeUnaryCosts, computeTripletCosts, optimise
             tcosts = timed("triplet_table", cost.triplet_table)
-            labeling = timed("optimiser", ops.mcmc, unary, tcosts, triplets, labeling, mcparam, mciters, seed + it)
+            if mcmc_chains > 1:
+                labeling = timed("optimiser", ops.mcmc_chains, unary, tcosts, triplets, labeling, mcparam, mciters, api.chain_seeds(seed, it, mcmc_chains))
+            else:
+                labeling = timed("optimiser", ops.mcmc, unary, tcosts, triplets, labeling, mcparam, mciters, seed + it)
         newenergy = timed("total_cost", cost.total, labeling)
         # the level's convergence test (M/mesh_registration.cpp:204-213): from the fourth iteration on, every second one, not for MCMC; the
         # iteration that triggers it is not applied

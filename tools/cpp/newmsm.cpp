@@ -188,7 +188,20 @@ bool features_gpu_enabled() {
     return env && std::string(env) == "gpu";
 }
 
+// MSMHIP_MCMC_CHAINS=n (1 ... 256): every iteration of a --dopt=MCMC level runs n chains from n seeds and keeps the labelling with the lowest energy
+// (DESIGN.md section 5.16); unset or 1: the single run.  Anything else ends the run with a message and exit status 1.
+int mcmc_chains_setting() {
+    const char *env = std::getenv("MSMHIP_MCMC_CHAINS");
+    if (!env) return 1;
+    char *end = nullptr;
+    const long n = std::strtol(env, &end, 10);
+    if (end == env || *end != '\0' || n < 1 || n > 256)
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MCMC_CHAINS=") + env + ": the number of Monte Carlo chains must be a whole number from 1 to 256");
+    return (int)n;
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
+    const int mcmc_chains = mcmc_chains_setting();
     for (const char *flag : {"inmesh", "indata", "refdata"})
         if (o.get(flag).empty()) throw Error(MSM_ERR_INVALID, std::string("newmsm: --") + flag + " is required");
     if (o.get("inanat").empty() != o.get("refanat").empty()) throw Error(MSM_ERR_INVALID, "Error: must supply both anatomical meshes or none");  // CLI/newmsm.cpp:41-43
@@ -212,6 +225,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
         for (LevelSpec &lv : levels) lv.options.mcmc_gpu = true;
     if (features_gpu_enabled())
         for (LevelSpec &lv : levels) lv.options.features_gpu = true;
+    for (LevelSpec &lv : levels) lv.options.mcmc_chains = mcmc_chains;
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
@@ -234,6 +248,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("verbose"))
         std::cout << "This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     if (o.has("verbose") && mcmc_gpu) std::cout << "MCMC sweeps on the GPU." << std::endl;
+    if (o.has("verbose") && mcmc_chains > 1) std::cout << "MCMC with " << mcmc_chains << " chains per iteration." << std::endl;
     if (o.has("verbose") && features_gpu_enabled()) std::cout << "Level features in one call on the GPU." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,
                                                     anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr,

@@ -132,6 +132,21 @@ def mcmc_gpu_enabled():
     return os.environ.get("MSMHIP_MCMC", "") == "gpu"
 
 
+def mcmc_chains_setting():
+    """MSMHIP_MCMC_CHAINS=n (1 ... 256): every iteration of a --dopt=MCMC level runs n chains from n seeds and keeps the labelling with the lowest energy
+    (DESIGN.md section 5.16); unset or 1: the single run.  Anything else ends the run with a message and exit status 1."""
+    text = os.environ.get("MSMHIP_MCMC_CHAINS")
+    if text is None:
+        return 1
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if not 1 <= n <= 256:
+        raise SystemExit("MSMHIP_MCMC_CHAINS=%s: the number of Monte Carlo chains must be a whole number from 1 to 256" % text)
+    return n
+
+
 def discrete_levels(cfg, D, anat=False, groupwise=False):
     levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
                                                         **(dict(histmatch=True) if histmatch_enabled() else {}))
@@ -197,6 +212,7 @@ def main_groupwise(a, surf_ext, data_ext):
 
 def main(argv):
     a = parse_args(argv)
+    chains = mcmc_chains_setting()  # (the groupwise loops run no MCMC: checked, then unused there)
     surf_ext, data_ext = output_formats(a.format)
     if surf_ext == ".vtk":
         raise SystemExit("register_files.py: VTK output is not written here (GIFTI, ASCII, ASCII_MAT)")
@@ -217,6 +233,8 @@ def main(argv):
     levels, run_kw = discrete_levels(cfg, idata.shape[0], anat=bool(a.inanat))
     excl = config.run_options(cfg)
     cfw = dict(excl)
+    if chains > 1:
+        cfw.update(mcmc_chains=chains)
     if a.trans:  # set_transformed: as loaded
         cfw.update(trans_xyz=meshio.load_surface(a.trans)[0])
     if a.inanat:  # set_anatomical: loaded as they are (in_anat keeps its triangles: its normals serve the strain map)
@@ -229,6 +247,8 @@ def main(argv):
         print("This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
         if mcmc_gpu_enabled():
             print("MCMC sweeps on the GPU.")
+        if chains > 1:
+            print("MCMC with %d chains per iteration." % chains)
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
     reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled()), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)

@@ -3,7 +3,14 @@ sweeps on the MI355X, over the unary and triplet tables of BASELINE config 2 (pa
 control grid.  In one process, alternating: the host path (msm_cost_unary_table + msm_cost_triplet_table into pinned memory + msm_mcmc_optimise) and
 msm_cost_mcmc_optimise (both tables stay on the device).  A time is reported only when the two labellings are equal.  Per grid, medians of the repeats with
 min and max: ms per sweep either way, us per level by the HIP events around the sweep kernels, the proposal stream's draws per second on the host alone,
-the time the host path spends computing and fetching the triplet table, and the time the device path spends on its two tables.  Prints one JSON object."""
+the time the host path spends computing and fetching the triplet table, and the time the device path spends on its two tables.  Prints one JSON object.
+
+tools/time_mcmc.py --chains 1,4,16,64 --baseline-lib PARENT/newmsm_amd/libmsmhip.so [--sweeps N] [--repeats R] [--out FILE] -- several chains in one launch
+(msm_cost_mcmc_optimise_chains, DESIGN.md 5.16 "Chains") against K successive msm_cost_mcmc_optimise calls of another build: the library of a checkout of
+the parent commit, driven through the Python mirror that lies beside it (loaded under another name), so both builds run in this one process, alternated,
+after warm-up.  Per grid and K, medians of the repeats with min and max: ms of the chains call, ms of the K baseline calls, kernel ms and us per level
+(levels walked by one chain) by the HIP events, the wall ms of the threaded draw and its threads.  A time is reported only when every chain's labelling
+equals the baseline call with that chain's seed.  "apart": the chains call's slowest repeat lies below the fastest repeat of the K baseline calls."""
 import argparse
 import json
 import os
@@ -96,8 +103,92 @@ def measure(ctx, cp_order, sweeps, repeats, mcparam, seed):
     return out
 
 
+def load_baseline(lib_path):
+    """the Python mirror beside another build's libmsmhip.so (a checkout's newmsm_amd/), imported under a name of its own: it binds that library"""
+    import importlib.util
+
+    pkg = os.path.dirname(os.path.abspath(lib_path))
+    if os.path.basename(lib_path) != "libmsmhip.so" or not os.path.exists(os.path.join(pkg, "__init__.py")):
+        raise SystemExit("time_mcmc.py: --baseline-lib must be the newmsm_amd/libmsmhip.so of another checkout (its Python mirror is loaded with it)")
+    if os.environ.get("MSM_LIB_PATH"):
+        raise SystemExit("time_mcmc.py: MSM_LIB_PATH would bind both mirrors to one library; unset it")
+    spec = importlib.util.spec_from_file_location("newmsm_amd_baseline", os.path.join(pkg, "__init__.py"), submodule_search_locations=[pkg])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["newmsm_amd_baseline"] = mod
+    spec.loader.exec_module(mod)
+    import newmsm_amd_baseline.problem  # noqa: F401
+
+    assert os.path.samefile(mod.LIB_PATH, lib_path) and not os.path.samefile(mod.LIB_PATH, M.LIB_PATH), (mod.LIB_PATH, M.LIB_PATH)
+    return mod
+
+
+def measure_chains(ctx, base, base_ctx, cp_order, chains, sweeps, repeats, mcparam, seed):
+    def build(mod, c):
+        inp = mod.problem.pairwise_inputs(6, cp_order, D=1)
+        cf, keep = mod.problem.build_cost(c, inp, kind="univariate")
+        cf.get_source_data()
+        keep["target"].prepare_search(wait=True)
+        return cf, keep
+
+    cf, keep = build(M, ctx)
+    cfb, keepb = build(base, base_ctx)
+    start = np.zeros(cf.N, dtype=np.int32)
+    out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, sweeps=sweeps, repeats=repeats, mcparam=mcparam, per_K=[])
+
+    def ours(seeds, iters):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        res = cf.mcmc_optimise_chains(start, seeds, mcparam=mcparam, iters=iters)
+        ms = (time.perf_counter() - t0) * 1e3
+        return res, dict(total_ms=ms, draw_threads=api.mcmc_chains_info(ctx)[1], **api.mcmc_gpu_stats(ctx))
+
+    def theirs(seeds, iters):
+        base_ctx.synchronize()
+        t0 = time.perf_counter()
+        labs = [cfb.mcmc_optimise(start, mcparam=mcparam, iters=iters, seed=s) for s in seeds]
+        return labs, (time.perf_counter() - t0) * 1e3
+
+    for K in chains:
+        seeds = api.chain_seeds(seed, 0, K)
+        for _ in range(2):  # warm-up of both builds at this K: code objects, staging blocks, the K-chain buffers
+            ours(seeds, 20), theirs(seeds[:2], 20)
+        runs, base_ms, equal = [], [], True
+        for _ in range(repeats):
+            (lab, labs, E, best), r = ours(seeds, sweeps)
+            want, ms = theirs(seeds, sweeps)
+            equal = equal and all(np.array_equal(labs[k], want[k]) for k in range(K)) and np.array_equal(lab, labs[best])
+            runs.append(r), base_ms.append(ms)
+        row = dict(K=K, labellings_equal=bool(equal), best=int(best), chunks=runs[0]["chunks"], draw_threads=runs[0]["draw_threads"],
+                   levels_per_sweep=runs[0]["levels_per_sweep"])
+        if equal:  # no time is reported for a result that is not the baseline's
+            row.update(chains_ms=spread([r["total_ms"] for r in runs]), baseline_ms=spread(base_ms),
+                       kernel_ms=spread([r["kernel_ms"] for r in runs]), us_per_level=spread([1e3 * r["kernel_ms"] / r["levels"] for r in runs]),
+                       draw_ms=spread([r["draw_ms"] for r in runs]))
+            row["apart"] = bool(row["chains_ms"]["max"] < row["baseline_ms"]["min"])
+            row["draw_binds"] = bool(row["draw_ms"]["median"] > row["kernel_ms"]["median"])
+        out["per_K"].append(row)
+    cf.close(), cfb.close()
+    return out
+
+
+def main_chains(a):
+    chains = [int(k) for k in a.chains.split(",")]
+    if not chains or min(chains) < 1 or max(chains) > 256:
+        raise SystemExit("time_mcmc.py: --chains takes numbers from 1 to 256")
+    if not a.baseline_lib:
+        raise SystemExit("time_mcmc.py: --chains needs --baseline-lib (the build the K successive calls run on)")
+    base = load_baseline(a.baseline_lib)
+    ctx, base_ctx = M.Context(0), base.Context(0)
+    result = dict(tool="tools/time_mcmc.py --chains", host_threads=os.environ.get("MSMHIP_HOST_THREADS"),
+                  grids=[measure_chains(ctx, base, base_ctx, cp, chains, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
+    ctx.close(), base_ctx.close()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", default=None, help="e.g. 1,4,16,64: time the chains call against K successive calls of --baseline-lib")
+    ap.add_argument("--baseline-lib", default=None, help="newmsm_amd/libmsmhip.so of a checkout of the commit to compare with")
     ap.add_argument("--sweeps", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--mcparam", type=float, default=0.8)
@@ -105,10 +196,13 @@ def main():
     a = ap.parse_args()
     if M.device_count() < 1:
         raise SystemExit("time_mcmc.py: no HIP device is visible (nothing is measured without one)")
-    ctx = M.Context(0)
-    result = dict(tool="tools/time_mcmc.py", grids=[measure(ctx, cp, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
-    ctx.close()
-    text = json.dumps(result, indent=1)
+    if a.chains:
+        result = main_chains(a)
+    else:
+        ctx = M.Context(0)
+        result = dict(tool="tools/time_mcmc.py", grids=[measure(ctx, cp, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
+        ctx.close()
+    text = json.dumps(result, indent=1, default=lambda o: o.item())  # (numpy scalars)
     if a.out:
         with open(a.out, "w") as f:
             f.write(text + "\n")
