@@ -874,4 +874,33 @@ int launch_group_triplet(msm_ctx *ctx, const GroupArgs &a, const int *qt, const 
     return MSM_OK;
 }
 
+// the range checks of patch lists that come from elsewhere, for n subjects at once (blockIdx.y), and what msm_group_finalize wants to know of their patches
+__global__ void k_check_patch_csr_batch(const int32_t *__restrict__ pptr, int64_t pptr_stride, size_t M, const int32_t *__restrict__ pidx, int64_t pidx_stride,
+                                        const int64_t *__restrict__ npidx, int32_t Vt, int small_len, int *__restrict__ out /* n x 4: bad, largest, small, - */) {
+    const int k = blockIdx.y;
+    const int32_t *pp = pptr + (size_t)k * pptr_stride, *pi = pidx + (size_t)k * pidx_stride;
+    const int64_t np = npidx[k];
+    int bad = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < M || (int64_t)i < np; i += (size_t)gridDim.x * blockDim.x) {
+        if (i == 0 && (pp[0] != 0 || pp[M] != np)) bad |= 1;
+        if (i < M) {
+            const int len = pp[i + 1] - pp[i];
+            if (len < 0) bad |= 2;
+            if (len > out[4 * k + 1]) atomicMax(&out[4 * k + 1], len);
+            const unsigned long long sm = __ballot(len >= 0 && len <= small_len);
+            if ((threadIdx.x & 63) == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) atomicAdd(&out[4 * k + 2], (int)__popcll(sm));
+        }
+        if ((int64_t)i < np && (pi[i] < 0 || pi[i] >= Vt)) bad |= 4;
+    }
+    if (bad) atomicOr(&out[4 * k], bad);
+}
+
+int launch_group_check_csr(msm_ctx *ctx, const int32_t *pptr, int64_t pptr_stride, size_t M, const int32_t *pidx, int64_t pidx_stride, const int64_t *d_npidx,
+                           int64_t most, int n, int32_t Vt, int *d_out) {
+    const unsigned gx = (unsigned)std::min<int64_t>((most + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_check_patch_csr_batch, dim3(gx, (unsigned)n), dim3(256), 0, ctx->stream, pptr, pptr_stride, M, pidx, pidx_stride, d_npidx, Vt, kPairSmallPatch, d_out);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
 }  // namespace msm

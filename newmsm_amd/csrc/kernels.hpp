@@ -251,7 +251,7 @@ struct GroupArgs {
     int move_label, move_offset;
     // processing order of a move's pairs (nullptr: list order): query i of a launch evaluates combination (move_offset + i) % 4 of
     // pair move_order[(move_offset + i) / 4] and writes out[4 * (pair - move_base) + combination] -- the results keep the list's
-    // order, the work runs control-point tile by tile (group.cpp: pair_order)
+    // order, the work runs control-point tile by tile (group_setup.cpp: pair_order)
     const int *move_order;
     const int4 *move_order4;     // beside move_order (or nullptr): {pair, its two global nodes, 0} per position -- one load instead of order -> pair -> nodes
     int move_base;
@@ -316,6 +316,11 @@ int launch_group_patch_dir(msm_ctx *ctx, const GroupArgs &a, double *const *pval
 // out[4 * (pair - base) + 3] = kept[pair - base] for the n pairs order[0 .. n)
 int launch_group_kept(msm_ctx *ctx, const int *order, int base, const double *kept, int n, double *out);
 int launch_group_triplet(msm_ctx *ctx, const GroupArgs &a, const int *qt, const int *qa, const int *qb, const int *qc, int n, double *out);
+// Patch lists of n subjects in device memory (subject k's row offsets at pptr + k * pptr_stride, M + 1 of them; its d_npidx[k] ids at pidx + k * pidx_stride; most:
+// the longest of these arrays) checked before anything indexes with them: d_out[4 k] = 0, or 1 (ends) | 2 (a row length) | 4 (a vertex id outside [0, Vt));
+// d_out[4 k + 1] the largest patch, d_out[4 k + 2] the patches of at most kPairSmallPatch entries.  d_out comes zeroed.
+int launch_group_check_csr(msm_ctx *ctx, const int32_t *pptr, int64_t pptr_stride, size_t M, const int32_t *pidx, int64_t pidx_stride, const int64_t *d_npidx,
+                           int64_t most, int n, int32_t Vt, int *d_out);
 // the search trees of the S control grids as one forest (arrays of tree b start b * s_* elements in), as the kernels below see it
 struct ForestDev {
     const int4 *node;

@@ -48,6 +48,16 @@ def with_one_row(n):
     return sizes
 
 
+def with_empty_last_rows():
+    """the threshold list with the last row (control point N - 1, label L - 1) of both subjects empty: nothing follows an empty patch in its list"""
+    sizes = threshold_sizes().copy()
+    sizes[:, N - 1, L - 1] = 0
+    return sizes
+
+
+EMPTY_LAST_QUERIES = [(N - 1, L - 1, L - 1), (N - 1, L - 1, 0), (N - 1, 0, L - 1)]  # pair 41: both patches empty, patch A, patch B
+
+
 # name -> row sizes (S x N x L)
 CASES = {
     "thresholds": threshold_sizes,
@@ -58,6 +68,7 @@ CASES = {
     "dice2100": threshold_sizes,             # 138 624 bytes: the attribute path
     "dice2500": lambda: with_one_row(2500),  # 164 224 bytes: refused (the dynamic bytes alone, 160 000, would have passed)
     "dice2561": lambda: with_one_row(2561),
+    "empty_last": lambda: with_empty_last_rows(),  # the clamped loads of the register path then start behind the subject's lists
 }
 
 
@@ -211,9 +222,9 @@ def expected_routes(lanes, D, sim):
 
 
 # ---------------------------------------------------------------- the product's side
-def product_group(ctx, name, D, sim, mask_kind="none", fixnan=False, percentile=0.75):
-    """the crafted group in the library: set_template / Initialize / the subjects' (small) data meshes as usual, an empty set-up for the pair list, then the
-    rows and maps exactly as written through import_subject, and finalize"""
+def empty_group(ctx, D, sim, mask_kind="none", fixnan=False, percentile=0.75):
+    """the crafted group's frame in the library: set_template / Initialize / the subjects' (small) data meshes as usual and an empty set-up for the pair
+    list -- ready for its subjects to be imported"""
     import newmsm_amd as M
 
     txyz, ttri = M.make_mesh_from_icosa(4)
@@ -235,6 +246,12 @@ def product_group(ctx, name, D, sim, mask_kind="none", fixnan=False, percentile=
         keep.append(m)
     g.set_labels(samples)
     g.setup_subjects([])
+    return g, keep
+
+
+def product_group(ctx, name, D, sim, mask_kind="none", fixnan=False, percentile=0.75):
+    """the crafted group in the library: its frame, then the rows and maps exactly as written through import_subject, and finalize"""
+    g, keep = empty_group(ctx, D, sim, mask_kind, fixnan, percentile)
     pptr, pidx = csr(name)
     for s in range(S):
         g.import_subject(s, features(D)[s], pptr[s], pidx[s])

@@ -93,6 +93,25 @@ def test_gather_and_compact_forms(ctx, monkeypatch, lanes, D, sim):
     assert np.array_equal(quads, step_from(gathered, labeling, label), equal_nan=True)
 
 
+@pytest.mark.parametrize("lanes", [16, 32])
+def test_empty_last_row_of_a_subject(ctx, monkeypatch, lanes):
+    """Both subjects' lists end with an empty row: the register path's loads, clamped to the patch, start at the element behind the list (ids in the
+    gather form, ids and values in the compact form -- the lists carry one element of padding for it).  All 15 162 queries in both forms against
+    the literal; pair 41 with the empty row as patch A, as patch B and as both has no cost."""
+    monkeypatch.setenv("MSMHIP_GROUP_PAIR_LANES", str(lanes))
+    ref = C.reference("empty_last", 2, 2, "none")
+    g, _ = C.product_group(ctx, "empty_last", 2, 2, "none")
+    assert g.pair_launch()["npatch"] == C.ROWS and not g.pair_launch()["pval"]
+    gathered = table(g)
+    assert_against_literal(gathered, ref, 2)
+    g.fusionMove(np.zeros(g.num_nodes, dtype=np.int32), C.L - 1)  # a whole step builds the value copies
+    assert g.pair_launch()["pval"] and g.pair_launch()["dir"]
+    compact = table(g)
+    assert np.array_equal(compact, gathered, equal_nan=True)
+    for p, la, lb in C.EMPTY_LAST_QUERIES:
+        assert np.isnan(ref["want"].reshape(C.P, C.L, C.L)[p, la, lb]) and np.isnan(compact[p, la, lb])
+
+
 def step_from(tab, labeling, label):
     """the P x 4 pair costs of a label step (I/Fusion/Fusion.h:170-173) out of the table of all queries"""
     pr, k = C.pairs(), np.arange(4)

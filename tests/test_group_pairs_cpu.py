@@ -139,6 +139,24 @@ def test_threshold_case_intersections(mask):
     assert ((nc == 0) & (ca > 0) & (cb > 0)).sum() > 500  # non-empty patches without a common vertex (FAR_LABEL)
 
 
+def test_empty_last_row_case():
+    """both subjects' lists end with an empty row (control point 41, label 18), the row before it does not; all queries hold pair 41 with that row as patch A,
+    as patch B and as both, and the literal has no cost for them"""
+    pptr, pidx = C.csr("empty_last")
+    for s in range(C.S):
+        assert pptr[s][-1] == pptr[s][-2] == len(pidx[s]) and pptr[s][-2] > pptr[s][-3]
+        assert np.array_equal(np.diff(pptr[s]), C.with_empty_last_rows()[s].ravel())
+    p, la, lb = C.all_queries()
+    ca, cb = C.query_sizes("empty_last")
+    for q, want_sizes in zip(C.EMPTY_LAST_QUERIES, [(0, 0), (0, None), (None, 0)]):
+        at = np.flatnonzero((p == q[0]) & (la == q[1]) & (lb == q[2]))
+        assert len(at) == 1
+        assert all(w is None or w == got for w, got in zip(want_sizes, (ca[at[0]], cb[at[0]])))
+        cost, ncommon = C.literal_batch("empty_last", 2, 2, "none", p[at], la[at], lb[at])
+        assert np.isnan(cost[0]) and ncommon[0] == 0
+    assert C.CASES["thresholds"]()[0, C.N - 1, 0] > 0 and C.CASES["thresholds"]()[1, C.N - 1, 0] > 0  # the other patch of the one-sided queries is not empty
+
+
 def test_lane_choice_cases_sit_on_the_boundary():
     small = {n: int((C.CASES[n]() <= 80).sum()) for n in ("lanes16", "lanes32")}
     assert small == {"lanes16": 1437, "lanes32": 1436} and C.ROWS == 1596
