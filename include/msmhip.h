@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MSM_ABI_VERSION 12  /* 12: msm_group_pair_route / msm_group_pair_launch added (which path of the pair-cost kernel a query takes, and what the group's launch was decided to be; additive, the version stays).  12: msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise / msm_mcmc_gpu_stats / msm_mcmc_proposals / msm_mcmc_schedule added (the Monte Carlo optimiser's sweeps on the GPU; additive, the version stays).  12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
+#define MSM_ABI_VERSION 12  /* 12: msm_ctx_set_mcmc_draw / msm_ctx_get_mcmc_draw / msm_mcmc_draw_thresholds / msm_mcmc_draw_block_bound / msm_mcmc_proposals_mirror / msm_mcmc_proposals_mirror_counted / msm_mcmc_draw_gpu / msm_mcmc_draw_stats added (the Monte Carlo optimiser's proposals drawn on the device; additive, the version stays).  12: msm_group_pair_route / msm_group_pair_launch added (which path of the pair-cost kernel a query takes, and what the group's launch was decided to be; additive, the version stays).  12: msm_mcmc_optimise_gpu / msm_cost_mcmc_optimise / msm_mcmc_gpu_stats / msm_mcmc_proposals / msm_mcmc_schedule added (the Monte Carlo optimiser's sweeps on the GPU; additive, the version stays).  12: msm_resample_plan_create_smooth / msm_resample_plan_divisors added (Gaussian smoothing as a fourth kind of plan row; additive, the version stays).  12: msm_cost_routes added (which kernel the last unary table and the last triclique label step ran); routes[MSM_ROUTE_MOVE_DEFERRED] fills a slot that was reserved and 0 (additive, the version stays).  11: msm_resample_plan_* added (weights built once, applied to many maps; additive, the version stays).  11: msm_dedrift_set_warp / msm_dedrift_group_stats_select added (merging registered groups up a hierarchy: a given warp, statistics over a list of subjects and a vertex mask; additive, the version stays).  11: msm_dedrift_create / _destroy / _reset / _accumulate / _finish / _correct / _set_map / _group_stats added (dedrifting and the statistics of a groupwise run; additive, the version stays).  11: msm_calculate_strains added (the strain map of an aMSM run; additive, the version stays).  11: msm_rigid_create / _destroy / _set_source / _get_source / _cost / _rotate / _run / _kernel_ms added (the rigid level; additive, the version stays).  11 (round 5): msm_ctx_wait_stream, msm_ctx_staging_stats, msm_group_context; msm_host_register takes whole pages only.  10 (round 4): msm_group_set_rotation_mode.  9 (round 4): msm_group_set_pair_layout.  8 (round 4): msm_query_lanes, msm_resample_anatomy_grid, msm_cost_triplet_octets_prefetch / msm_cost_prefetch_stats, msm_group_export_subjects_dev / msm_group_import_subjects_dev / msm_group_setup_more_subjects added.  6 (round 3): msm_pairwise_icm, msm_ctx_time_queries / msm_ctx_query_kernel_ms, msm_group_time_moves / msm_group_move_kernels_ms,
                              * msm_store_release_i64 / msm_load_acquire_i64 / msm_min_acquire_i64, msm_mesh_sphere_project_warp added; nothing removed or changed */
 
 #define MSM_OK 0
@@ -378,6 +378,37 @@ int msm_mcmc_chains_info(msm_ctx *ctx, int32_t *K, int32_t *draw_threads);
 /* [host] The proposal stream both optimisers consume: out[s * T + t] is the label proposed to triplet t in sweep s (sweeps x T values), drawn in chunks of
  * chunk_sweeps whole sweeps (<= 0: one chunk); the stream does not depend on the chunking.  L > 65535: MSM_ERR_INVALID. */
 int msm_mcmc_proposals(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, int32_t chunk_sweeps, uint16_t *out);
+/* [host] Where the GPU entry points of the Monte Carlo optimiser (msm_mcmc_optimise_gpu, msm_mcmc_optimise_chains_gpu, msm_cost_mcmc_optimise,
+ * msm_cost_mcmc_optimise_chains) get their proposals on this context.  mode 0 (the default): from the host's stream, as described above.  mode 1: a
+ * kernel draws them, a workgroup per chain with the chain's std::mt19937 state in LDS, the labels taken from thresholds the host locates once per call
+ * with its own log (msm_mcmc_draw_thresholds) -- the same proposals, labellings, energies and bytes.  The draw of chunk c + 1 runs on a side stream the
+ * context owns beside the sweeps of chunk c; it starts behind what the context's stream held at the call and is joined to that stream before the
+ * downloads, so the stream contract above describes these entry points in either mode.  After a mode 1 call msm_mcmc_gpu_stats[2] is 0 and
+ * msm_mcmc_chains_info's draw threads are 0.  Any other mode: MSM_ERR_INVALID.  The host optimisers ignore the mode. */
+int msm_ctx_set_mcmc_draw(msm_ctx *ctx, int32_t mode);
+int msm_ctx_get_mcmc_draw(msm_ctx *ctx, int32_t *mode);
+/* [host] The steps of the host's label function floor(log(x) / log(1 - mcparam)) over x = 1 - u in [2^-53, 1]: thr[k - 1], k = 1 .. L, is the bit pattern
+ * of the smallest such double whose label is at most k - 1 (2^-53's pattern where even that one's is), found by bisection on bit patterns with the
+ * host's log.  Non-increasing in k; the label of x is the number of k with bits(x) < thr[k - 1], and L means "drawn again". */
+int msm_mcmc_draw_thresholds(int32_t L, double mcparam, uint64_t *thr /* L */);
+/* [host] The 312-candidate blocks the draw kernel may generate for `need` accepted proposals of one chain: with a = 1 - (1 - mcparam)^L,
+ * ceil((need / a + 16 sqrt(need (1 - a)) / a + 624) / 312) + 1. */
+int msm_mcmc_draw_block_bound(int64_t need, int32_t L, double mcparam, int64_t *blocks);
+/* [host] msm_mcmc_proposals' stream (one chunk) from the hand-written pieces the draw kernel is made of -- the mt19937 recurrence and tempering, two
+ * words to a double, 1 - u, the thresholds -- without std::mt19937 or std::geometric_distribution: (sweeps x T values in visit order).  _counted also
+ * gives the candidates the stream consumed (candidates may be NULL). */
+int msm_mcmc_proposals_mirror(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, uint16_t *out);
+int msm_mcmc_proposals_mirror_counted(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, uint16_t *out, uint64_t *candidates);
+/* The device's streams alone: out[(k * sweeps + s) * T + pos[t]] is the label proposed to triplet t in sweep s of chain k (seeds[k]; 1 <= K <= 256), drawn
+ * chunk_sweeps sweeps per launch (<= 0: one launch) through the kernel and the per-chain record the optimiser's entry points use, then downloaded.  pos:
+ * a permutation of 0 .. T - 1, or NULL for the identity.  At most 2^30 proposals per call (MSM_ERR_CAPACITY).  Runs on the context's side stream and is
+ * joined to the context's stream before the download; complete on return.  `out` is written only when the call succeeds. */
+int msm_mcmc_draw_gpu(msm_ctx *ctx, int32_t L, double mcparam, const uint64_t *seeds, int32_t K, int32_t T, int32_t sweeps, int32_t chunk_sweeps,
+                      const int32_t *pos, uint16_t *out);
+/* [host] What the draw kernel did in the last msm_mcmc_draw_gpu or mode 1 optimiser call on the context: stats[0] ms in the draw kernels (HIP events),
+ * [1] candidates generated, [2] proposals accepted (both over all chains), [3] the block bound of the last chunk.  MSMHIP_MCMC_DRAW_BLOCKS=n (testing)
+ * replaces the bound; a chain that reaches it before its chunk is complete fails the call with MSM_ERR_CAPACITY and a message that names the draw. */
+int msm_mcmc_draw_stats(msm_ctx *ctx, double stats[4]);
 /* [host] The level schedule of a triplet list (any list with nodes in [0, N)): level[t] (0-based), order (the T triplets by level, ascending within a
  * level), level_off (offsets into order; room for T + 1), *levels.  level / order / level_off may be NULL. */
 int msm_mcmc_schedule(const int32_t *triplets, int32_t N, int32_t T, int32_t *level, int32_t *order, int32_t *level_off, int32_t *levels);

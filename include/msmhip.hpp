@@ -145,6 +145,14 @@ public:
     Context &operator=(const Context &) = delete;
     msm_ctx *handle() const { return h_; }
     void synchronize() { check(msm_ctx_synchronize(h_)); }
+    // msm_ctx_set_mcmc_draw: where the GPU entry points of the Monte Carlo optimiser get their proposals -- 0 the host's stream (the default), 1 a kernel
+    // draws them, bit for bit the same
+    void set_mcmc_draw(int mode) { check(msm_ctx_set_mcmc_draw(h_, mode)); }
+    int mcmc_draw() const {
+        int32_t mode = 0;
+        check(msm_ctx_get_mcmc_draw(h_, &mode));
+        return mode;
+    }
 
 private:
     msm_ctx *h_;
@@ -514,6 +522,16 @@ inline std::pair<int, int> mcmc_chains_info(Context &ctx) {
     int32_t chains = 0, threads = 0;
     check(msm_mcmc_chains_info(ctx.handle(), &chains, &threads));
     return {chains, threads};
+}
+// msm_mcmc_draw_gpu: the proposal streams of seeds.size() chains drawn by the draw kernel alone, chains x sweeps x T; the label of triplet t of a sweep
+// stands at pos[t] (pos empty: t)
+inline std::vector<uint16_t> mcmc_draw_gpu(Context &ctx, int num_labels, double dist_param, const std::vector<uint64_t> &seeds, int T, int sweeps,
+                                           int chunk_sweeps = 0, const std::vector<int32_t> &pos = std::vector<int32_t>()) {
+    std::vector<uint16_t> out(seeds.size() * (size_t)sweeps * (size_t)T);
+    if (!pos.empty() && pos.size() != (size_t)T) throw Error(MSM_ERR_INVALID, "mcmc_draw_gpu: pos holds a place per triplet");
+    check(msm_mcmc_draw_gpu(ctx.handle(), num_labels, dist_param, seeds.data(), (int32_t)seeds.size(), T, sweeps, chunk_sweeps, pos.empty() ? nullptr : pos.data(),
+                            out.data()));
+    return out;
 }
 // msm_mcmc_optimise_chains: seeds.size() runs of mcmc_optimise from the one start; labeling becomes the best chain's
 inline McmcChains mcmc_optimise_chains(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,

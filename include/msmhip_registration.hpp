@@ -60,6 +60,9 @@ struct LevelOptions {
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
+    // with mcmc_gpu: those sweeps take their proposals from the draw kernel instead of the host's stream (Context::set_mcmc_draw on the level's context):
+    // the same proposals, bit for bit (what MSMHIP_MCMC_DRAW=gpu asks of the executables)
+    bool mcmc_draw_gpu = false;
     // the MCMC branch runs this many chains per iteration from the one labelling (chain k seeded with seed + it + 1000003 k) and keeps the one with the
     // lowest energy (msm_cost_mcmc_optimise_chains with mcmc_gpu, msm_mcmc_optimise_chains without: the same labelling); 1: the single run
     int mcmc_chains = 1;
@@ -134,6 +137,10 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
     if (o.pairwise && o.cost.regularisermode != 1) throw Error(MSM_ERR_INVALID, "MeshREG ERROR:: you cannot run higher order clique regularisers with fastPD ");
     const std::vector<int32_t> triplets = o.pairwise ? std::vector<int32_t>() : estimate_triplets(cp_tri);
     const std::vector<int32_t> pairs = o.pairwise ? estimate_pairs(cp_tri, (int)(cp_xyz.size() / 3)) : std::vector<int32_t>();
+    if (o.mcmc_draw_gpu) {
+        if (!o.mcmc_gpu) throw Error(MSM_ERR_INVALID, "LevelOptions: mcmc_draw_gpu draws the proposals of the GPU sweeps: it needs mcmc_gpu");
+        ctx.set_mcmc_draw(1);
+    }
     DiscreteCostFunction costfct(ctx, o.cost);
     costfct.set_meshes(TARGET, SOURCE, CPGRID);  // _ORIG, _oCPgrid
     costfct.set_featurespace(src_feat, D);

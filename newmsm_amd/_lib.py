@@ -123,6 +123,14 @@ SIGNATURES = {
     "msm_mcmc_chains_info": (C.c_int, [_VP, c_ip, c_ip]),
     "msm_mcmc_proposals": (C.c_int, [C.c_int32, C.c_double, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint16)]),
     "msm_mcmc_schedule": (C.c_int, [c_ip, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]),
+    "msm_ctx_set_mcmc_draw": (C.c_int, [_VP, C.c_int32]),
+    "msm_ctx_get_mcmc_draw": (C.c_int, [_VP, c_ip]),
+    "msm_mcmc_draw_thresholds": (C.c_int, [C.c_int32, C.c_double, C.POINTER(C.c_uint64)]),
+    "msm_mcmc_draw_block_bound": (C.c_int, [C.c_int64, C.c_int32, C.c_double, C.POINTER(C.c_int64)]),
+    "msm_mcmc_proposals_mirror": (C.c_int, [C.c_int32, C.c_double, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint16)]),
+    "msm_mcmc_proposals_mirror_counted": (C.c_int, [C.c_int32, C.c_double, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint64)]),
+    "msm_mcmc_draw_gpu": (C.c_int, [_VP, C.c_int32, C.c_double, C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, C.POINTER(C.c_uint16)]),
+    "msm_mcmc_draw_stats": (C.c_int, [_VP, c_dp]),
     "msm_fusion_icm_step": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_pairwise_icm": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_nearest_neighbour": (C.c_int, [_VP, c_dp, C.c_int32, c_dp, C.c_int32, c_dp, c_dp, c_dp]),

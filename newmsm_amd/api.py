@@ -233,6 +233,16 @@ class Context:
         if getattr(self, "h", None):
             lib().msm_host_free(self.h, C.c_void_p(arr.ctypes.data))
 
+    def set_mcmc_draw(self, mode):
+        """msm_ctx_set_mcmc_draw: where the GPU entry points of the Monte Carlo optimiser get their proposals on this context -- 0 / "host" (the default)
+        or 1 / "gpu": drawn by a kernel, the same proposals bit for bit"""
+        check(lib().msm_ctx_set_mcmc_draw(self.h, {"host": 0, "gpu": 1}.get(mode, mode)))
+
+    def get_mcmc_draw(self):
+        mode = C.c_int32(-1)
+        check(lib().msm_ctx_get_mcmc_draw(self.h, C.byref(mode)))
+        return mode.value
+
     def time_queries(self, on=True):
         """HIP events around the search kernel of query_triangles / closest_vertex calls (msm_ctx_time_queries)"""
         check(lib().msm_ctx_time_queries(self.h, int(on)))
@@ -804,6 +814,57 @@ def mcmc_proposals(L, mcparam, seed, T, sweeps, chunk_sweeps=0):
     out = np.zeros((int(sweeps), int(T)), dtype=np.uint16)
     check(lib().msm_mcmc_proposals(int(L), float(mcparam), int(seed), int(T), int(sweeps), int(chunk_sweeps), out.ctypes.data_as(C.POINTER(C.c_uint16))))
     return out
+
+
+def mcmc_draw_thresholds(L, mcparam):
+    """msm_mcmc_draw_thresholds: thr[k - 1], k = 1 .. L (uint64 bit patterns): the smallest double x in [2^-53, 1] with floor(log(x) / log(1 - mcparam)) <= k - 1"""
+    thr = np.zeros(int(L), dtype=np.uint64)
+    check(lib().msm_mcmc_draw_thresholds(int(L), float(mcparam), thr.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return thr
+
+
+def mcmc_draw_block_bound(need, L, mcparam):
+    """msm_mcmc_draw_block_bound: the 312-candidate blocks the draw kernel may generate for `need` accepted proposals of one chain"""
+    n = C.c_int64()
+    check(lib().msm_mcmc_draw_block_bound(int(need), int(L), float(mcparam), C.byref(n)))
+    return n.value
+
+
+def mcmc_proposals_mirror(L, mcparam, seed, T, sweeps, counted=False):
+    """msm_mcmc_proposals_mirror: mcmc_proposals' stream from the hand-written pieces of the draw kernel, (sweeps, T) uint16 in visit order; counted: also
+    the candidates the stream consumed (msm_mcmc_proposals_mirror_counted)"""
+    out = np.zeros((int(sweeps), int(T)), dtype=np.uint16)
+    po = out.ctypes.data_as(C.POINTER(C.c_uint16))
+    if not counted:
+        check(lib().msm_mcmc_proposals_mirror(int(L), float(mcparam), int(seed), int(T), int(sweeps), po))
+        return out
+    n = C.c_uint64()
+    check(lib().msm_mcmc_proposals_mirror_counted(int(L), float(mcparam), int(seed), int(T), int(sweeps), po, C.byref(n)))
+    return out, n.value
+
+
+def mcmc_draw_gpu(ctx, L, mcparam, seeds, T, sweeps, chunk_sweeps=0, pos=None):
+    """msm_mcmc_draw_gpu: the proposal streams of len(seeds) chains drawn by the draw kernel alone, (K, sweeps, T) uint16; the label of triplet t of a sweep
+    stands at pos[t] (None: t), as the sweeps kernels read it"""
+    sd = np.ascontiguousarray(np.atleast_1d(seeds), dtype=np.uint64)
+    K = len(sd)
+    out = np.zeros((K, int(sweeps), int(T)), dtype=np.uint16)
+    if pos is None:
+        pp = C.cast(None, c_ip)
+    else:
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        assert pos.shape == (int(T),)
+        pp = pos.ctypes.data_as(c_ip)
+    check(lib().msm_mcmc_draw_gpu(ctx.h, int(L), float(mcparam), sd.ctypes.data_as(C.POINTER(C.c_uint64)), K, int(T), int(sweeps), int(chunk_sweeps), pp,
+                                  out.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return out
+
+
+def mcmc_draw_stats(ctx):
+    """msm_mcmc_draw_stats of the context's last device draw: dict(draw_ms, candidates, accepted, block_bound)"""
+    s = np.zeros(4)
+    check(lib().msm_mcmc_draw_stats(ctx.h, s.ctypes.data_as(c_dp)))
+    return dict(draw_ms=s[0], candidates=int(s[1]), accepted=int(s[2]), block_bound=int(s[3]))
 
 
 def mcmc_schedule(triplets, N):

@@ -33,9 +33,10 @@ class _OwnedProductOps(registration.ProductOps):
         self.ctx.close()
 
 
-def product_ops(device=0):
-    """make_ops for the MI355X path: every call makes a ProductOps over a Context of its own (closed by run_cohort when its worker ends)"""
-    return lambda: _OwnedProductOps(api.Context(device))
+def product_ops(device=0, **options):
+    """make_ops for the MI355X path: every call makes a ProductOps over a Context of its own (closed by run_cohort when its worker ends); `options` are
+    ProductOps' own (mcmc_gpu, mcmc_draw_gpu, features_gpu), so every worker's context gets them"""
+    return lambda: _OwnedProductOps(api.Context(device), **options)
 
 
 def _subject_arrays(subject):

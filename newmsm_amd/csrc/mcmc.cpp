@@ -1,6 +1,7 @@
 // mcmc.cpp -- the host side of the Monte Carlo optimiser's GPU sweeps (mcmc.hpp; kernel: mcmc_kernels.hip): the level schedule, the
 // proposal stream in chunks of whole sweeps, and the loop that draws chunk k + 1 while the device walks chunk k; the same for several chains from one
-// start (their streams drawn on the host workers, their energies summed here, the best one kept), and the host-only chains, energy and selection.
+// start (their streams drawn on the host workers, their energies summed here, the best one kept), and the host-only chains, energy and selection.  With
+// msm_ctx_set_mcmc_draw(ctx, 1) the streams are drawn by a kernel on a side stream instead (DeviceDraw; mcmc_draw.hpp, mcmc_draw_kernels.hip).
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -39,8 +40,25 @@ struct McmcScratch {
     std::vector<hipEvent_t> ev;  // a pair per chunk
     double stats[6] = {0, 0, 0, 0, 0, 0};
     int chains = 1, draw_threads = 1;  // of the last call
+    // proposals drawn on the device (DeviceDraw below): the second proposal buffer, the thresholds, the chains' records, the triplets' places, the draw's
+    // own status word, a side stream on which the draw of chunk c + 1 runs beside the sweeps of chunk c, and a pair of events per chunk around the kernel
+    DevBuf<uint16_t> prop2;
+    DevBuf<uint64_t> thr;
+    DevBuf<McmcDrawRecord> rec;
+    DevBuf<int32_t> pos;
+    DevBuf<int> draw_status;
+    hipStream_t draw_stream = nullptr;
+    hipEvent_t draw_begin = nullptr;
+    std::vector<hipEvent_t> draw_ev;
+    double draw_stats[4] = {0, 0, 0, 0};
     ~McmcScratch() {
+        if (draw_stream) {
+            (void)hipStreamSynchronize(draw_stream);
+            (void)hipStreamDestroy(draw_stream);
+        }
+        if (draw_begin) (void)hipEventDestroy(draw_begin);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : draw_ev) (void)hipEventDestroy(e);
     }
 };
 
@@ -65,6 +83,115 @@ int upload_in_pieces(msm_ctx *ctx, void *dst, const void *src, size_t bytes) {
     for (size_t off = 0; off < bytes; off += piece)
         MSM_TRY(stage_h2d(ctx, (char *)dst + off, (const char *)src + off, std::min(piece, bytes - off)));
     return MSM_OK;
+}
+
+// The proposals of K chains drawn on the device, chunk by chunk (k_mcmc_draw; DESIGN.md 5.16 "Proposals on the device").  begin() uploads what the host
+// computes once per call -- the thresholds, the seeded engines, the triplets' places -- and lets the side stream wait for the context's; draw() queues
+// chunk c there, behind `after` when the buffer it fills is still being walked; join() lets the context's stream wait for chunk c; collect() queues the
+// downloads of the status word and the records on the context's stream and finish(), after that stream's sync, reads them.  Every draw has been joined
+// when the entry point downloads, so the context's stream alone describes the call (msm_ctx_wait_stream's contract).
+struct DeviceDraw {
+    msm_ctx *ctx = nullptr;
+    McmcScratch *s = nullptr;
+    McmcDrawArgs d;
+    double mcparam = 0.0;
+    long forced_blocks = 0;  // MSMHIP_MCMC_DRAW_BLOCKS (testing): the block bound, whatever the formula says
+    int chunks_drawn = 0;
+    std::vector<McmcDrawRecord> recs;
+    int status = 0;
+
+    int begin(msm_ctx *ctx_, McmcScratch &s_, int L, double mcparam_, const uint64_t *seeds, int K, int T, int stride, const int32_t *pos, int chunks) {
+        ctx = ctx_;
+        s = &s_;
+        mcparam = mcparam_;
+        if (const char *e = std::getenv("MSMHIP_MCMC_DRAW_BLOCKS")) forced_blocks = std::max(0L, std::atol(e));
+        std::vector<uint64_t> thr((size_t)L);
+        mcmc_draw_thresholds(L, mcparam, thr.data());
+        recs.assign((size_t)K, McmcDrawRecord());
+        for (int k = 0; k < K; ++k) {
+            McmcDrawRecord &r = recs[(size_t)k];
+            mt_seed(seeds[k], r.state);
+            r.consumed = kDrawCandidates;
+            r.pad = 0;
+            r.candidates = r.accepted = 0;
+        }
+        MSM_TRY(s->thr.upload_vec(thr, ctx));
+        MSM_TRY(s->rec.upload_vec(recs, ctx));
+        if (pos) MSM_TRY(s->pos.upload(pos, (size_t)T, ctx));
+        if (s->draw_status.zero(1, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int));
+        if (!s->draw_stream) MSM_HIP(hipStreamCreateWithFlags(&s->draw_stream, hipStreamNonBlocking));
+        if (!s->draw_begin) MSM_HIP(hipEventCreateWithFlags(&s->draw_begin, hipEventDisableTiming));
+        while (s->draw_ev.size() < 2 * (size_t)chunks) {
+            hipEvent_t e;
+            MSM_HIP(hipEventCreate(&e));
+            s->draw_ev.push_back(e);
+        }
+        MSM_HIP(hipEventRecord(s->draw_begin, ctx->stream));  // the uploads above, and whatever read the buffers before this call
+        MSM_HIP(hipStreamWaitEvent(s->draw_stream, s->draw_begin, 0));
+        d.rec = s->rec.p;
+        d.thr = s->thr.p;
+        d.pos = pos ? s->pos.p : nullptr;
+        d.prop = nullptr;
+        d.chains = K;
+        d.L = L;
+        d.T = T;
+        d.chunk_sweeps = stride;
+        d.need = 0;
+        d.max_blocks = 0;
+        d.status = s->draw_status.p;
+        chunks_drawn = 0;
+        return MSM_OK;
+    }
+    // chunk c: the next `sweeps` sweeps of every chain into dst (chains x d.chunk_sweeps x T), once `after` (an event of the context's stream, or null) has passed
+    int draw(int c, uint16_t *dst, int sweeps, hipEvent_t after) {
+        if (after) MSM_HIP(hipStreamWaitEvent(s->draw_stream, after, 0));
+        d.prop = dst;
+        d.need = (uint32_t)((size_t)sweeps * (size_t)d.T);
+        d.max_blocks = forced_blocks > 0 ? forced_blocks : mcmc_draw_block_bound((long)d.need, d.L, mcparam);
+        MSM_HIP(hipEventRecord(s->draw_ev[2 * (size_t)c], s->draw_stream));
+        MSM_TRY(launch_mcmc_draw(ctx, d, s->draw_stream));
+        MSM_HIP(hipEventRecord(s->draw_ev[2 * (size_t)c + 1], s->draw_stream));
+        chunks_drawn = std::max(chunks_drawn, c + 1);
+        return MSM_OK;
+    }
+    int join(int c) {
+        MSM_HIP(hipStreamWaitEvent(ctx->stream, s->draw_ev[2 * (size_t)c + 1], 0));
+        return MSM_OK;
+    }
+    int collect() {
+        MSM_TRY(stage_d2h(ctx, &status, s->draw_status.p, sizeof(int)));
+        MSM_TRY(s->rec.download(recs.data(), recs.size(), ctx));
+        return MSM_OK;
+    }
+    // after the context's stream has been synchronised: the counters, and the draw's own error
+    int finish(const char *what) {
+        double ms = 0.0, candidates = 0.0, accepted = 0.0;
+        for (int c = 0; c < chunks_drawn; ++c) {
+            float f = 0.f;
+            MSM_HIP(hipEventElapsedTime(&f, s->draw_ev[2 * (size_t)c], s->draw_ev[2 * (size_t)c + 1]));
+            ms += f;
+        }
+        for (const McmcDrawRecord &r : recs) {
+            candidates += (double)r.candidates;
+            accepted += (double)r.accepted;
+        }
+        s->draw_stats[0] = ms;
+        s->draw_stats[1] = candidates;
+        s->draw_stats[2] = accepted;
+        s->draw_stats[3] = (double)d.max_blocks;
+        if (status == MSM_ERR_CAPACITY)
+            return fail(MSM_ERR_CAPACITY, "%s: the proposal draw on the device reached its bound of %ld blocks of 312 candidates before a chunk was complete", what, d.max_blocks);
+        if (status != 0) return fail(status, "%s: the proposal draw on the device reported status %d", what, status);
+        return MSM_OK;
+    }
+};
+
+// the end of a device-draw call: the context's status (read after the sync that also delivers the draw's), then the draw's own, which is the cause when both are raised
+int finish_device_draw(msm_ctx *ctx, DeviceDraw &dd, const char *what) {
+    const int st = check_status(ctx, what);
+    if (st == MSM_ERR_HIP) return st;
+    MSM_TRY(dd.finish(what));
+    return st;
 }
 
 }  // namespace
@@ -109,6 +236,45 @@ int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const i
     a.T = T;
     a.levels = sch.levels();
     a.status = ctx->d_status;
+    if (ctx->mcmc_draw == 1) {
+        // the proposals drawn on the device, chain machinery with K = 1: chunk k + 1 is drawn on the side stream into the other buffer while chunk k is walked
+        if (s.prop2.ensure((size_t)chunk * T) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * (size_t)chunk * T);
+        uint16_t *const bufs[2] = {s.prop.p, s.prop2.p};
+        DeviceDraw dd;
+        MSM_TRY(dd.begin(ctx, s, L, mcparam, &seed, 1, T, chunk, pos.data(), chunks));
+        MSM_TRY(dd.draw(0, bufs[0], std::min(chunk, iters), nullptr));
+        for (int k = 0, done = 0; k < chunks; ++k) {
+            const int sweeps = std::min(chunk, iters - done);
+            done += sweeps;
+            if (done < iters) MSM_TRY(dd.draw(k + 1, bufs[(k + 1) & 1], std::min(chunk, iters - done), k >= 1 ? s.ev[2 * (size_t)(k - 1) + 1] : nullptr));
+            MSM_TRY(dd.join(k));
+            a.prop = bufs[k & 1];
+            a.sweeps = sweeps;
+            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
+            MSM_TRY(launch_mcmc_sweeps(ctx, a));
+            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
+        }
+        std::vector<int32_t> lab((size_t)N);  // the caller's labelling stays as it is when the call fails
+        MSM_TRY(s.labeling.download(lab.data(), (size_t)N, ctx));
+        MSM_TRY(dd.collect());
+        MSM_TRY(finish_device_draw(ctx, dd, "msm_mcmc_optimise_gpu"));
+        std::copy(lab.begin(), lab.end(), labeling);
+        double kernel_ms = 0.0;
+        for (int k = 0; k < chunks; ++k) {
+            float ms = 0.f;
+            MSM_HIP(hipEventElapsedTime(&ms, s.ev[2 * (size_t)k], s.ev[2 * (size_t)k + 1]));
+            kernel_ms += ms;
+        }
+        s.stats[0] = kernel_ms;
+        s.stats[1] = (double)iters * sch.levels();
+        s.stats[2] = 0.0;
+        s.stats[3] = chunks;
+        s.stats[4] = sch.levels();
+        s.stats[5] = sch.widest();
+        s.chains = 1;
+        s.draw_threads = 0;
+        return MSM_OK;
+    }
     McmcProposals proposals(seed, mcparam, L);
     std::vector<uint16_t> buf((size_t)chunk * T);
     double draw_ms = 0.0;
@@ -201,7 +367,26 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
     c.chains = K;
     c.chunk_sweeps = chunk;
     double draw_ms = 0.0;
-    if (sweep) {
+    const bool device_draw = ctx->mcmc_draw == 1 && sweep;
+    DeviceDraw dd;
+    if (device_draw) {
+        // as in mcmc_run_device: chunk k + 1 of every chain is drawn on the side stream into the other buffer while chunk k is walked
+        if (s.prop2.ensure(per_chunk) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * per_chunk);
+        uint16_t *const bufs[2] = {s.prop.p, s.prop2.p};
+        MSM_TRY(dd.begin(ctx, s, L, mcparam, seeds, K, T, chunk, pos.data(), chunks));
+        MSM_TRY(dd.draw(0, bufs[0], std::min(chunk, iters), nullptr));
+        for (int k = 0, done = 0; k < chunks; ++k) {
+            const int sweeps = std::min(chunk, iters - done);
+            done += sweeps;
+            if (done < iters) MSM_TRY(dd.draw(k + 1, bufs[(k + 1) & 1], std::min(chunk, iters - done), k >= 1 ? s.ev[2 * (size_t)(k - 1) + 1] : nullptr));
+            MSM_TRY(dd.join(k));
+            a.prop = bufs[k & 1];
+            a.sweeps = sweeps;
+            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
+            MSM_TRY(launch_mcmc_chains(ctx, c));
+            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
+        }
+    } else if (sweep) {
         McmcChainStreams streams(seeds, K, mcparam, L);
         std::vector<uint16_t> buf(per_chunk);
         // a chunk of every chain in the kernel's layout, the chains spread over the host workers; the wall clock of the threaded draw
@@ -227,7 +412,11 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
     std::vector<double> terms((size_t)K * nterms);
     MSM_TRY(s.labeling.download(labs.data(), labs.size(), ctx));
     MSM_TRY(s.terms.download(terms.data(), terms.size(), ctx));
-    MSM_TRY(check_status(ctx, "msm_mcmc_optimise_chains_gpu"));
+    if (device_draw) {
+        MSM_TRY(dd.collect());
+        MSM_TRY(finish_device_draw(ctx, dd, "msm_mcmc_optimise_chains_gpu"));
+    } else
+        MSM_TRY(check_status(ctx, "msm_mcmc_optimise_chains_gpu"));
     std::vector<double> E((size_t)K);
     for (int k = 0; k < K; ++k) E[(size_t)k] = mcmc_energy_of_terms(terms.data() + (size_t)k * nterms, N, T);
     const int b = mcmc_best_chain(E.data(), K);
@@ -248,7 +437,7 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
     s.stats[4] = sch.levels();
     s.stats[5] = sch.widest();
     s.chains = K;
-    s.draw_threads = threads;
+    s.draw_threads = device_draw ? 0 : threads;
     return MSM_OK;
 }
 
@@ -360,6 +549,94 @@ int msm_mcmc_proposals(int32_t L, double mcparam, uint64_t seed, int32_t T, int3
         const int n = std::min(chunk, sweeps - done);
         proposals.fill(out + (size_t)done * T, (size_t)n * T);
     }
+    return MSM_OK;
+}
+
+int msm_ctx_set_mcmc_draw(msm_ctx *ctx, int32_t mode) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_ctx_set_mcmc_draw: null context");
+    if (mode != 0 && mode != 1) return fail(MSM_ERR_INVALID, "msm_ctx_set_mcmc_draw: mode %d (0: the proposals are drawn on the host, 1: on the device)", mode);
+    ctx->mcmc_draw = mode;
+    return MSM_OK;
+}
+
+int msm_ctx_get_mcmc_draw(msm_ctx *ctx, int32_t *mode) {
+    if (!ctx || !mode) return fail(MSM_ERR_INVALID, "msm_ctx_get_mcmc_draw: null argument");
+    *mode = ctx->mcmc_draw;
+    return MSM_OK;
+}
+
+int msm_mcmc_draw_thresholds(int32_t L, double mcparam, uint64_t *thr) {
+    if (!thr || L <= 0) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_thresholds: bad arguments");
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    mcmc_draw_thresholds(L, mcparam, thr);
+    return MSM_OK;
+}
+
+int msm_mcmc_draw_block_bound(int64_t need, int32_t L, double mcparam, int64_t *blocks) {
+    if (!blocks || L <= 0 || need < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_block_bound: bad arguments");
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    *blocks = mcmc_draw_block_bound((long)need, L, mcparam);
+    return MSM_OK;
+}
+
+int msm_mcmc_proposals_mirror_counted(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, uint16_t *out, uint64_t *candidates) {
+    if (!out || L <= 0 || T < 0 || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals_mirror: bad arguments");
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals_mirror: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    McmcDrawMirror mirror(seed, mcparam, L);
+    mirror.fill(out, (size_t)sweeps * T);
+    if (candidates) *candidates = mirror.candidates;
+    return MSM_OK;
+}
+
+int msm_mcmc_proposals_mirror(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, uint16_t *out) {
+    return msm_mcmc_proposals_mirror_counted(L, mcparam, seed, T, sweeps, out, nullptr);
+}
+
+int msm_mcmc_draw_gpu(msm_ctx *ctx, int32_t L, double mcparam, const uint64_t *seeds, int32_t K, int32_t T, int32_t sweeps, int32_t chunk_sweeps,
+                      const int32_t *pos, uint16_t *out) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: null context");
+    if (!out || L <= 0 || T < 0 || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: bad arguments");
+    MSM_TRY(mcmc_check_chains(seeds, K));
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    if (pos) {  // a place per triplet, each taken once
+        std::vector<char> seen((size_t)T, 0);
+        for (int t = 0; t < T; ++t) {
+            if (pos[t] < 0 || pos[t] >= T || seen[(size_t)pos[t]]) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: pos is not a permutation of 0 .. T - 1");
+            seen[(size_t)pos[t]] = 1;
+        }
+    }
+    const size_t total = (size_t)K * (size_t)sweeps * (size_t)T;
+    if (total > ((size_t)1 << 30)) return fail(MSM_ERR_CAPACITY, "msm_mcmc_draw_gpu: %zu proposals (at most 2^30 per call)", total);
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    McmcScratch &s = mcmc_scratch(ctx);
+    s.draw_stats[0] = s.draw_stats[1] = s.draw_stats[2] = s.draw_stats[3] = 0.0;
+    if (total == 0) return MSM_OK;
+    const int chunk = chunk_sweeps > 0 ? std::min(chunk_sweeps, sweeps) : sweeps;
+    const int chunks = (sweeps + chunk - 1) / chunk;
+    // the whole call's proposals in one device buffer, a chain's sweeps side by side: chunk c is drawn with the stride `sweeps`, `done` sweeps in
+    if (s.prop.ensure(total) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * total);
+    DeviceDraw dd;
+    MSM_TRY(dd.begin(ctx, s, L, mcparam, seeds, K, T, sweeps, pos, chunks));
+    for (int c = 0, done = 0; c < chunks; ++c) {
+        const int n = std::min(chunk, sweeps - done);
+        MSM_TRY(dd.draw(c, s.prop.p + (size_t)done * T, n, nullptr));
+        done += n;
+    }
+    MSM_TRY(dd.join(chunks - 1));
+    std::vector<uint16_t> host(total);  // the caller's array stays as it is when the call fails
+    MSM_TRY(stage_d2h(ctx, host.data(), s.prop.p, sizeof(uint16_t) * total));
+    MSM_TRY(dd.collect());
+    MSM_TRY(finish_device_draw(ctx, dd, "msm_mcmc_draw_gpu"));
+    std::copy(host.begin(), host.end(), out);
+    return MSM_OK;
+}
+
+int msm_mcmc_draw_stats(msm_ctx *ctx, double stats[4]) {
+    if (!ctx || !stats) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_stats: null argument");
+    std::memcpy(stats, mcmc_scratch(ctx).draw_stats, sizeof(double) * 4);
     return MSM_OK;
 }
 

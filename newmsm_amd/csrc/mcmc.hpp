@@ -3,6 +3,7 @@
 #pragma once
 
 #include "internal.hpp"
+#include "mcmc_draw.hpp"
 #include "mcmc_host.hpp"
 
 namespace msm {
@@ -32,6 +33,29 @@ struct McmcChainArgs {
 int launch_mcmc_chains(msm_ctx *ctx, const McmcChainArgs &c);
 // the terms of every chain's energy, terms[k * (N + T) + ...]: U[lab[i] * N + i] for i < N, then tc[t][la][lb][lc] for t < T (a.sweeps, a.prop unused)
 int launch_mcmc_chain_terms(msm_ctx *ctx, const McmcChainArgs &c, double *terms);
+
+// The proposals drawn on the device (mcmc_draw.hpp, mcmc_draw_kernels.hip; DESIGN.md 5.16 "Proposals on the device"): workgroup k continues chain k's
+// stream from rec[k] by `need` accepted proposals and stores them where McmcChainStreams::draw puts them: number j at
+// prop[((size_t)k * chunk_sweeps + j / T) * T + pos[j % T]] (pos null: j % T itself).
+constexpr int kMcmcDrawThreads = 320;      // five wavefronts: a candidate of the 312 per thread
+constexpr int kMcmcDrawLdsLabels = 4096;   // thresholds of up to this many labels (32 KB) are copied to LDS, more are read from global memory
+struct McmcDrawRecord {
+    uint32_t state[kMtWords];  // the engine's words; the current block's once the first block has been generated
+    uint32_t consumed;         // candidates of that block already taken (312: none left, as in a seeded engine)
+    uint32_t pad;
+    unsigned long long candidates, accepted;  // counted over the launches since the record was written by the host
+};
+struct McmcDrawArgs {
+    McmcDrawRecord *rec;   // chains
+    const uint64_t *thr;   // L thresholds (mcmc_draw_thresholds)
+    const int32_t *pos;    // T, or null
+    uint16_t *prop;        // chains x chunk_sweeps x T
+    int chains, L, T, chunk_sweeps;
+    uint32_t need;         // proposals per chain in this launch: sweeps x T <= chunk_sweeps x T
+    long max_blocks;       // 312-candidate blocks a chain may generate in this launch (mcmc_draw_block_bound)
+    int *status;           // raised (atomicMin) to MSM_ERR_CAPACITY by a chain that reaches max_blocks first
+};
+int launch_mcmc_draw(msm_ctx *ctx, const McmcDrawArgs &d, hipStream_t stream);
 
 // `iters` sweeps on the device over tables that lie there (d_U: L x N, d_tc: T x L^3); labeling (host, N) is read and updated.  The arguments have been
 // checked by the caller (mcmc_check_arguments).  Complete on return.

@@ -27,14 +27,21 @@ EXCL_WITH_WEIGHTINGS = ("--excl together with --inweight and --refweight is not 
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
-    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False):
+    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False):
         """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
         the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
         bytes (what MSMHIP_FEATURES=gpu asks of the executables).
         mcmc_gpu: the MCMC branch of run_discrete_level leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead
-        of fetching them for the host optimiser -- the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)"""
+        of fetching them for the host optimiser -- the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables).
+        mcmc_draw_gpu (with mcmc_gpu): those sweeps take their proposals from the draw kernel instead of the host's stream (the context's
+        set_mcmc_draw) -- the same proposals, bit for bit (what MSMHIP_MCMC_DRAW=gpu asks of the executables)"""
         self.ctx = ctx
         self.mcmc_gpu = bool(mcmc_gpu)
+        self.mcmc_draw_gpu = bool(mcmc_draw_gpu)
+        if self.mcmc_draw_gpu:
+            if not self.mcmc_gpu:
+                raise ValueError("mcmc_draw_gpu draws the proposals of the GPU sweeps: it needs mcmc_gpu")
+            ctx.set_mcmc_draw(1)
         self.features_gpu = bool(features_gpu)
 
     # --- meshes

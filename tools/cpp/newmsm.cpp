@@ -200,8 +200,22 @@ int mcmc_chains_setting() {
     return (int)n;
 }
 
+// MSMHIP_MCMC_DRAW=gpu (with MSMHIP_MCMC=gpu): the GPU sweeps take their proposals from the draw kernel instead of the host's stream (DESIGN.md section
+// 5.16, "Proposals on the device"; the same bytes); unset or host: the host's stream.  Anything else, or gpu without MSMHIP_MCMC=gpu, ends the run with a
+// message and exit status 1.
+bool mcmc_draw_gpu_setting() {
+    const char *env = std::getenv("MSMHIP_MCMC_DRAW");
+    if (!env || std::string(env) == "host") return false;
+    if (std::string(env) != "gpu")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MCMC_DRAW=") + env + ": the proposals are drawn on the host (host, or unset) or on the device (gpu)");
+    const char *mcmc_env = std::getenv("MSMHIP_MCMC");
+    if (!mcmc_env || std::string(mcmc_env) != "gpu") throw Error(MSM_ERR_INVALID, "MSMHIP_MCMC_DRAW=gpu draws the proposals of the GPU sweeps: it needs MSMHIP_MCMC=gpu");
+    return true;
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const int mcmc_chains = mcmc_chains_setting();
+    const bool mcmc_draw_gpu = mcmc_draw_gpu_setting();
     for (const char *flag : {"inmesh", "indata", "refdata"})
         if (o.get(flag).empty()) throw Error(MSM_ERR_INVALID, std::string("newmsm: --") + flag + " is required");
     if (o.get("inanat").empty() != o.get("refanat").empty()) throw Error(MSM_ERR_INVALID, "Error: must supply both anatomical meshes or none");  // CLI/newmsm.cpp:41-43
@@ -223,6 +237,8 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
     if (mcmc_gpu)
         for (LevelSpec &lv : levels) lv.options.mcmc_gpu = true;
+    if (mcmc_draw_gpu)
+        for (LevelSpec &lv : levels) lv.options.mcmc_draw_gpu = true;
     if (features_gpu_enabled())
         for (LevelSpec &lv : levels) lv.options.features_gpu = true;
     for (LevelSpec &lv : levels) lv.options.mcmc_chains = mcmc_chains;
@@ -248,6 +264,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("verbose"))
         std::cout << "This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     if (o.has("verbose") && mcmc_gpu) std::cout << "MCMC sweeps on the GPU." << std::endl;
+    if (o.has("verbose") && mcmc_draw_gpu) std::cout << "MCMC proposals drawn on the GPU." << std::endl;
     if (o.has("verbose") && mcmc_chains > 1) std::cout << "MCMC with " << mcmc_chains << " chains per iteration." << std::endl;
     if (o.has("verbose") && features_gpu_enabled()) std::cout << "Level features in one call on the GPU." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,

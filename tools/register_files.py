@@ -147,6 +147,20 @@ def mcmc_chains_setting():
     return n
 
 
+def mcmc_draw_gpu_setting():
+    """MSMHIP_MCMC_DRAW=gpu (with MSMHIP_MCMC=gpu): the GPU sweeps take their proposals from the draw kernel instead of the host's stream (DESIGN.md
+    section 5.16, "Proposals on the device"; the same bytes); unset or host: the host's stream.  Anything else, or gpu without MSMHIP_MCMC=gpu, ends the
+    run with a message and exit status 1."""
+    text = os.environ.get("MSMHIP_MCMC_DRAW")
+    if text is None or text == "host":
+        return False
+    if text != "gpu":
+        raise SystemExit("MSMHIP_MCMC_DRAW=%s: the proposals are drawn on the host (host, or unset) or on the device (gpu)" % text)
+    if not mcmc_gpu_enabled():
+        raise SystemExit("MSMHIP_MCMC_DRAW=gpu draws the proposals of the GPU sweeps: it needs MSMHIP_MCMC=gpu")
+    return True
+
+
 def discrete_levels(cfg, D, anat=False, groupwise=False):
     levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
                                                         **(dict(histmatch=True) if histmatch_enabled() else {}))
@@ -213,6 +227,7 @@ def main_groupwise(a, surf_ext, data_ext):
 def main(argv):
     a = parse_args(argv)
     chains = mcmc_chains_setting()  # (the groupwise loops run no MCMC: checked, then unused there)
+    draw_gpu = mcmc_draw_gpu_setting()
     surf_ext, data_ext = output_formats(a.format)
     if surf_ext == ".vtk":
         raise SystemExit("register_files.py: VTK output is not written here (GIFTI, ASCII, ASCII_MAT)")
@@ -247,11 +262,13 @@ def main(argv):
         print("This is newMSM's DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
         if mcmc_gpu_enabled():
             print("MCMC sweeps on the GPU.")
+        if draw_gpu:
+            print("MCMC proposals drawn on the GPU.")
         if chains > 1:
             print("MCMC with %d chains per iteration." % chains)
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled()), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])

@@ -10,7 +10,14 @@ tools/time_mcmc.py --chains 1,4,16,64 --baseline-lib PARENT/newmsm_amd/libmsmhip
 the parent commit, driven through the Python mirror that lies beside it (loaded under another name), so both builds run in this one process, alternated,
 after warm-up.  Per grid and K, medians of the repeats with min and max: ms of the chains call, ms of the K baseline calls, kernel ms and us per level
 (levels walked by one chain) by the HIP events, the wall ms of the threaded draw and its threads.  A time is reported only when every chain's labelling
-equals the baseline call with that chain's seed.  "apart": the chains call's slowest repeat lies below the fastest repeat of the K baseline calls."""
+equals the baseline call with that chain's seed.  "apart": the chains call's slowest repeat lies below the fastest repeat of the K baseline calls.
+
+tools/time_mcmc.py --chains 1,4,16,64,256 --draw host,gpu --baseline-lib PARENT/newmsm_amd/libmsmhip.so [--sweeps N] [--repeats R] [--out FILE] -- the chains
+call with the proposals drawn on the host and on the device (msm_ctx_set_mcmc_draw, DESIGN.md 5.16 "Proposals on the device") against the chains call of
+the baseline build (the parent commit's), both libraries in this one process, alternated after two warm-up rounds.  Per grid, K and mode, medians of the
+repeats with min and max: ms of the call, ms in the sweeps kernels, the draw's ms (host: wall clock of the threaded draw; gpu: the draw kernels by their
+events) and, for gpu, accepted proposals per second of draw-kernel time.  A mode's times are reported only when every labelling equals the baseline's.
+"apart": the mode's slowest repeat lies below the baseline call's fastest."""
 import argparse
 import json
 import os
@@ -171,16 +178,89 @@ def measure_chains(ctx, base, base_ctx, cp_order, chains, sweeps, repeats, mcpar
     return out
 
 
+def measure_draw(ctx, base, base_ctx, cp_order, chains, modes, sweeps, repeats, mcparam, seed):
+    """the chains call of this build with the proposals drawn as `modes` say ("host", "gpu": msm_ctx_set_mcmc_draw) against the chains call of the baseline
+    build, per K; a mode's times are reported only when every labelling of every repeat equals the baseline's"""
+    def build(mod, c):
+        inp = mod.problem.pairwise_inputs(6, cp_order, D=1)
+        cf, keep = mod.problem.build_cost(c, inp, kind="univariate")
+        cf.get_source_data()
+        keep["target"].prepare_search(wait=True)
+        return cf, keep
+
+    cf, keep = build(M, ctx)
+    cfb, keepb = build(base, base_ctx)
+    start = np.zeros(cf.N, dtype=np.int32)
+    out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, sweeps=sweeps, repeats=repeats, mcparam=mcparam, per_K=[])
+
+    def ours(mode, seeds, iters):
+        ctx.set_mcmc_draw(mode)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        res = cf.mcmc_optimise_chains(start, seeds, mcparam=mcparam, iters=iters)
+        ms = (time.perf_counter() - t0) * 1e3
+        r = dict(total_ms=ms, draw_threads=api.mcmc_chains_info(ctx)[1], **api.mcmc_gpu_stats(ctx))
+        if mode == "gpu":
+            r.update(api.mcmc_draw_stats(ctx))  # draw_ms: the draw kernels' (the host drew nothing)
+        ctx.set_mcmc_draw("host")
+        return res, r
+
+    def theirs(seeds, iters):
+        base_ctx.synchronize()
+        t0 = time.perf_counter()
+        res = cfb.mcmc_optimise_chains(start, seeds, mcparam=mcparam, iters=iters)
+        return res, (time.perf_counter() - t0) * 1e3
+
+    for K in chains:
+        seeds = api.chain_seeds(seed, 0, K)
+        for _ in range(2):  # warm-up of both builds at this K and in every mode: code objects, staging blocks, both proposal buffers
+            for mode in modes:
+                ours(mode, seeds, 20)
+            theirs(seeds, 20)
+        runs, base_ms, equal = {m: [] for m in modes}, [], {m: True for m in modes}
+        for _ in range(repeats):
+            got = {}
+            for mode in modes:
+                got[mode], r = ours(mode, seeds, sweeps)
+                runs[mode].append(r)
+            want, ms = theirs(seeds, sweeps)
+            base_ms.append(ms)
+            for mode in modes:
+                equal[mode] = equal[mode] and np.array_equal(got[mode][1], want[1]) and np.array_equal(got[mode][0], want[0]) and got[mode][3] == want[3]
+        row = dict(K=K, baseline_ms=spread(base_ms), levels_per_sweep=runs[modes[0]][0]["levels_per_sweep"], chunks=runs[modes[0]][0]["chunks"])
+        for mode in modes:
+            rs = runs[mode]
+            m = dict(labellings_equal=bool(equal[mode]), draw_threads=rs[0]["draw_threads"])
+            if equal[mode]:  # no time is reported for a result that is not the baseline's
+                m.update(total_ms=spread([r["total_ms"] for r in rs]), kernel_ms=spread([r["kernel_ms"] for r in rs]), draw_ms=spread([r["draw_ms"] for r in rs]))
+                m["apart"] = bool(m["total_ms"]["max"] < row["baseline_ms"]["min"])
+                if mode == "gpu":
+                    m["proposals_per_s"] = spread([r["accepted"] / (r["draw_ms"] * 1e-3) for r in rs])
+                    m["candidates_per_proposal"] = rs[0]["candidates"] / rs[0]["accepted"]
+                    m["block_bound"] = rs[0]["block_bound"]
+            row[mode] = m
+        out["per_K"].append(row)
+    cf.close(), cfb.close()
+    return out
+
+
 def main_chains(a):
     chains = [int(k) for k in a.chains.split(",")]
     if not chains or min(chains) < 1 or max(chains) > 256:
         raise SystemExit("time_mcmc.py: --chains takes numbers from 1 to 256")
     if not a.baseline_lib:
         raise SystemExit("time_mcmc.py: --chains needs --baseline-lib (the build the K successive calls run on)")
+    modes = a.draw.split(",") if a.draw else []
+    if any(m not in ("host", "gpu") for m in modes):
+        raise SystemExit("time_mcmc.py: --draw takes host, gpu or both")
     base = load_baseline(a.baseline_lib)
     ctx, base_ctx = M.Context(0), base.Context(0)
-    result = dict(tool="tools/time_mcmc.py --chains", host_threads=os.environ.get("MSMHIP_HOST_THREADS"),
-                  grids=[measure_chains(ctx, base, base_ctx, cp, chains, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
+    if modes:
+        result = dict(tool="tools/time_mcmc.py --chains --draw", host_threads=os.environ.get("MSMHIP_HOST_THREADS"),
+                      grids=[measure_draw(ctx, base, base_ctx, cp, chains, modes, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
+    else:
+        result = dict(tool="tools/time_mcmc.py --chains", host_threads=os.environ.get("MSMHIP_HOST_THREADS"),
+                      grids=[measure_chains(ctx, base, base_ctx, cp, chains, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
     ctx.close(), base_ctx.close()
     return result
 
@@ -189,6 +269,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", default=None, help="e.g. 1,4,16,64: time the chains call against K successive calls of --baseline-lib")
     ap.add_argument("--baseline-lib", default=None, help="newmsm_amd/libmsmhip.so of a checkout of the commit to compare with")
+    ap.add_argument("--draw", default=None, help="host,gpu (with --chains): time the chains call per proposal-draw mode against the chains call of --baseline-lib")
     ap.add_argument("--sweeps", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--mcparam", type=float, default=0.8)
