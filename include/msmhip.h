@@ -725,6 +725,56 @@ int msm_group_move_kernels_ms(msm_group *g, double *ms);
 int msm_group_pair_route(int32_t cntA, int32_t cntB, int32_t D, int32_t simmeasure, int32_t lanes, int32_t route[4]);
 int msm_group_pair_launch(msm_group *g, int64_t out[8]);
 
+/* ------------------------------------------------------------------------------------------------
+ * groupwise MCMC: gMSM with the Monte Carlo optimiser (MCMC::optimise, M/mcmc_opt.h:31-134), subject by subject.
+ * AN EXTENSION, opt-in: the reference refuses anything but HOCR in groupwise mode (M/group_mesh_registration.cpp:87).  The group energy restricted to
+ * one subject s, the other subjects' labels held fixed, has the form MCMC::optimise reads, so block-coordinate descent over the subjects solves each
+ * block with the reference's own optimiser through the unchanged chain kernels; no cost table leaves the device.  Nodes are s * N + v, the pair list
+ * is the group's current one (msm_group_get_pairs, whatever layout is set), labeling is over S * N nodes; every pair joins two different subjects
+ * (estimate_pairs, M/DiscreteGroupModel.cpp:37-55).
+ *   incidence          for node n the pair indices p with pairs[2p] == n or pairs[2p + 1] == n, ascending.
+ *   conditional unary  U_s[l * N + v] = the sum, from 0.0, over the incident pairs of s * N + v in ascending pair index of computePairwiseCost(p, la, lb)
+ *                      (M/DiscreteGroupCostFunction.cpp:54-98), the node's own slot taking l and the partner's slot labeling[partner]; sequential FP64,
+ *                      each addition rounded, no contraction; a node without incident pairs gives exactly 0.0.  Each term is the value
+ *                      msm_group_pairwise_batch returns for that query (the same kernel through the same launcher): --fixnan, masks and all four
+ *                      measures are as they are there.
+ *   triplet table      tc_s[t][a][b][c] = computeTripletCost (:26-52) of the subject's t-th triplet in list order (msm_group_triplet_batch's value for
+ *                      (s * Tc + t, a, b, c)); node ids are made local by subtracting s * N.
+ *   block              msm_mcmc_optimise_chains' semantics on (U_s, tc_s, local triplets, N, L, Tc, mcparam, iters, seeds[K]) from the subject's current
+ *                      labels: every chain is bit for bit the host optimiser on its seed, energies are msm_mcmc_energy, best is msm_mcmc_best.  The best
+ *                      chain's labelling replaces the subject's labels only when its energy is strictly below the start's energy in the same table
+ *                      arithmetic; a NaN energy is never accepted.  Otherwise the subject keeps its labels.
+ *   pass               the subjects in ascending order, each block seeing the labels the earlier blocks wrote.
+ *   seeds              chain k of subject s in pass p of iteration it: seed + it + 1000003 k + 15485863 (p S + s) (chain 0 of subject 0 in pass 0 is the
+ *                      pairwise loops' seed).
+ * The group energy is E_s plus terms that do not involve subject s (each incident pair appears once in U_s), so with the acceptance rule a pass never
+ * raises the table energy.  That is the whole claim: nothing is promised about the quality of the minimum.
+ *
+ * The device entry points refuse, before anything is queued: a group that is not finalised (MSM_ERR_STATE); a group with imported subjects (a rank of a
+ * sharded run: MSM_ERR_STATE, "one rank only"); a subject, label or K (1 ... 256) out of range, mcparam outside (0, 1], more than 65535 labels or more
+ * than 80000 control points (msm_mcmc_optimise_chains_gpu's messages); a DICE group whose patches do not fit (msm_group_pairwise_batch's message).
+ *   msm_group_mcmc_incidence [host]   pairs (P x 2, nodes in [0, nodes)) -> CSR: ptr[nodes + 1], idx[ptr[nodes]] (room for 2 P entries).  O(P).
+ *   msm_group_mcmc_seeds [host]       the K seeds of one block by the rule above.
+ *   msm_group_mcmc_accept [host]      the acceptance rule: *accepted = best < start.
+ *   msm_group_conditional_unary       U_s of `labeling` on the device; U (L x N, may be NULL) receives it.
+ *   msm_group_subject_triplet_table   tc_s on the device (filled in triplet ranges, so a table beyond 2^31 values is no special case); tc
+ *                                     (Tc x L^3, may be NULL) receives it.
+ *   msm_group_mcmc_subject            one block: labeling (S * N, in and out), energies[0] the start's and [1] the kept energy, *accepted 0 or 1
+ *                                     (either may be NULL).  The proposals are drawn as msm_ctx_set_mcmc_draw says.
+ *   msm_group_mcmc_pass               `passes` passes over the subjects with the seed rule.  per_block (passes * S records of 8 doubles, may be NULL):
+ *                                     start energy, kept energy, accepted, best chain, then the block's GPU milliseconds by HIP events: query build plus
+ *                                     pair costs, segment sums, triplet table, and the sweep kernels (msm_mcmc_gpu_stats).
+ * ---------------------------------------------------------------------------------------------- */
+int msm_group_mcmc_incidence(const int32_t *pairs, int32_t P, int32_t nodes, int32_t *ptr, int32_t *idx);
+int msm_group_mcmc_seeds(uint64_t seed, int32_t it, int32_t pass, int32_t S, int32_t subject, int32_t K, uint64_t *seeds);
+int msm_group_mcmc_accept(double start, double best, int32_t *accepted);
+int msm_group_conditional_unary(msm_group *g, int32_t subject, const int32_t *labeling, double *U);
+int msm_group_subject_triplet_table(msm_group *g, int32_t subject, double *tc);
+int msm_group_mcmc_subject(msm_group *g, int32_t subject, int32_t *labeling, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K,
+                           double energies[2], int32_t *accepted);
+int msm_group_mcmc_pass(msm_group *g, int32_t *labeling, double mcparam, int32_t iters, uint64_t seed, int32_t it, int32_t K, int32_t passes,
+                        double *per_block);
+
 
 /* ------------------------------------------------------------------------------------------------
  * rigid level (--opt=RIGID / AFFINE).  Replaces Rigid_cost_function (M/rigid_costfunction.cpp): the rotation of the whole data

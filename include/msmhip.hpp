@@ -767,6 +767,18 @@ public:
         triplet_octets.resize(8 * (size_t)triplets);
         check(msm_group_fusion_move(h_, labeling.data(), label, pair_quads.data(), triplet_octets.data()));
     }
+    // msm_group_mcmc_pass (an extension: the reference refuses MCMC in groupwise mode): `passes` passes of blocks over the subjects in
+    // ascending order -- a block is `chains` chains of MCMC::optimise on the subject's conditional tables, the best kept when its energy is strictly below
+    // the start's; chain k of subject s in pass p is seeded seed + it + 1000003 k + 15485863 (p S + s).  labeling (S x N) is read and updated; per_block
+    // (optional): passes x S records of 8 doubles (start energy, kept energy, accepted, best chain, four GPU times in ms)
+    void mcmc_pass(std::vector<int32_t> &labeling, double dist_param, int mciters, uint64_t seed, int it, int chains = 1, int passes = 1,
+                   std::vector<double> *per_block = nullptr) {
+        int32_t S = 0, N = 0;
+        check(msm_group_dims(h_, &S, &N, nullptr, nullptr, nullptr));
+        if (labeling.size() != (size_t)S * (size_t)N) throw Error(MSM_ERR_INVALID, "DiscreteGroupModel::mcmc_pass: one label per node of every subject");
+        if (per_block) per_block->assign((size_t)(passes > 0 ? passes : 0) * (size_t)S * 8, 0.0);
+        check(msm_group_mcmc_pass(h_, labeling.data(), dist_param, mciters, seed, it, chains, passes, per_block ? per_block->data() : nullptr));
+    }
     std::vector<double> computePairwiseCost(const std::vector<int32_t> &pair, const std::vector<int32_t> &a, const std::vector<int32_t> &b) {
         std::vector<double> out(pair.size());
         check(msm_group_pairwise_batch(h_, pair.data(), a.data(), b.data(), (int32_t)pair.size(), out.data()));

@@ -21,6 +21,16 @@ struct GroupLevelOptions {
     double labeldist = 0.5;  // _labeldist, M/DiscreteModel.h:167
     GroupParameters cost;    // --simval --lambda --fixnan --shearmod --bulkmod --k_exponent --regexp --cprange --percentile
     bool features_gpu = false;  // the level's features for all subjects through one msm_level_features call (LevelOptions::features_gpu): the same bytes
+    // An extension, opt-in (the reference refuses anything but HOCR in groupwise mode, M/group_mesh_registration.cpp:87): instead of the label loop with its
+    // stand-in solve, every iteration runs mcmc_passes passes of blocks over the subjects from the zero labelling, each block mcmc_chains chains of mciters
+    // sweeps of MCMC::optimise on the subject's conditional tables (DiscreteGroupModel::mcmc_pass); mcmc_draw_gpu: the proposals
+    // are drawn by the draw kernel (the same labellings)
+    bool mcmc = false;
+    int mciters = 200;     // --mciters
+    double mcparam = 0.8;  // --mcparam
+    uint64_t seed = 0;
+    int mcmc_chains = 1, mcmc_passes = 1;
+    bool mcmc_draw_gpu = false;
 };
 
 struct GroupLevelResult {
@@ -45,6 +55,7 @@ inline GroupLevelResult run_group_discrete_opt(Context &ctx, const Points &templ
     (void)barycentres;
     const double centre[3] = {samples[0], samples[1], samples[2]};
     const int L = (int)(samples.size() / 3);
+    if (o.mcmc && o.mcmc_draw_gpu) ctx.set_mcmc_draw(1);
     DiscreteGroupModel g(ctx, o.cost, S);
     Mesh TEMPLATE(ctx, template_xyz, template_tri);
     g.set_meshspace(TEMPLATE, mask);
@@ -81,7 +92,8 @@ inline GroupLevelResult run_group_discrete_opt(Context &ctx, const Points &templ
                 if (l != label) return true;
             return false;
         };
-        for (int step = 0; step < 2 * L; ++step) {  // two sweeps over the labels, I/Fusion/Fusion.h:136-138
+        if (o.mcmc) PhaseClock::timed(clock, "optimiser", [&] { g.mcmc_pass(labeling, o.mcparam, o.mciters, o.seed, it, o.mcmc_chains, o.mcmc_passes); });
+        for (int step = 0; step < (o.mcmc ? 0 : 2 * L); ++step) {  // two sweeps over the labels, I/Fusion/Fusion.h:136-138
             const int label = step % L;
             if (!differs(label)) continue;
             PhaseClock::timed(clock, "fusion_moves", [&] { g.fusionMove(labeling, label, quads, octets); });
@@ -208,13 +220,14 @@ inline GroupMultiresResult run_group_multiresolutions(Context &ctx, const std::v
 // The levels of a --groupwise run from a configuration (msmhip_config.hpp: parse_config), as Group_Mesh_registration reads it: every level DISCRETE
 // ("AFFINE/RIGID registration is not supported in groupwise mode.", M/group_mesh_registration.cpp:29-30), the optimiser HOCR (:87); the model has its own
 // regulariser, so --regoption is not looked at (the twin of newmsm_amd/config.py: levels_from_config(..., groupwise=True)).
-// intensity (optional; opt-in): --IN / --INc are taken instead of refused and *intensity receives what the level loop needs
-inline std::vector<GroupLevelSpec> group_levels_from_config(const Config &c, bool *varnorm = nullptr, IntensityNorm *intensity = nullptr) {
+// intensity (optional; opt-in): --IN / --INc are taken instead of refused and *intensity receives what the level loop needs.  group_mcmc (opt-in, an
+// extension): --dopt=MCMC is taken instead of refused and the levels run GroupLevelOptions::mcmc with --mciters and --mcparam
+inline std::vector<GroupLevelSpec> group_levels_from_config(const Config &c, bool *varnorm = nullptr, IntensityNorm *intensity = nullptr, bool group_mcmc = false) {
     if (intensity) *intensity = intensity_from_config(c);
     if ((c.IN || c.INc) && !intensity) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
     for (const std::string &m : c.opt)
         if (m == "RIGID" || m == "AFFINE") throw ConfigError("AFFINE/RIGID registration is not supported in groupwise mode.");
-    if (c.dopt != "HOCR") throw ConfigError("Groupwise mode is only supported in the HOCR version of MSM.");
+    if (c.dopt != "HOCR" && !(group_mcmc && c.dopt == "MCMC")) throw ConfigError("Groupwise mode is only supported in the HOCR version of MSM.");
     if (varnorm) *varnorm = c.VN;
     std::vector<GroupLevelSpec> levels;
     for (size_t i = 0; i < c.opt.size(); ++i) {
@@ -226,6 +239,7 @@ inline std::vector<GroupLevelSpec> group_levels_from_config(const Config &c, boo
         o.cost.simmeasure = c.simval[i], o.cost.fixnan = c.fixnan, o.cost.lambda = c.lambda[i];
         o.cost.shearmodulus = c.shearmod, o.cost.bulkmodulus = c.bulkmod, o.cost.kexponent = c.k_exponent, o.cost.exponent = c.regexp;
         o.cost.range = c.cprange, o.cost.percentile = c.percentile;
+        o.mcmc = c.dopt == "MCMC", o.mciters = c.mciters[i], o.mcparam = c.mcparam;
         levels.push_back(lv);
     }
     return levels;

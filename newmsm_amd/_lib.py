@@ -204,6 +204,13 @@ SIGNATURES = {
     "msm_group_triplet_batch": (C.c_int, [_VP, c_ip, c_ip, c_ip, c_ip, C.c_int32, c_dp]),
     "msm_group_pair_route": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32)]),
     "msm_group_pair_launch": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    "msm_group_mcmc_incidence": (C.c_int, [c_ip, C.c_int32, C.c_int32, c_ip, c_ip]),
+    "msm_group_mcmc_seeds": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "msm_group_mcmc_accept": (C.c_int, [C.c_double, C.c_double, c_ip]),
+    "msm_group_conditional_unary": (C.c_int, [_VP, C.c_int32, c_ip, c_dp]),
+    "msm_group_subject_triplet_table": (C.c_int, [_VP, C.c_int32, c_dp]),
+    "msm_group_mcmc_subject": (C.c_int, [_VP, C.c_int32, c_ip, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_int32, c_dp, c_ip]),
+    "msm_group_mcmc_pass": (C.c_int, [_VP, c_ip, C.c_double, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, c_dp]),
     "msm_rigid_create": (_VP, [_VP, _VP, _VP, c_dp, c_dp, C.c_int32, C.c_int32]),
     "msm_rigid_destroy": (None, [_VP]),
     "msm_rigid_set_source": (C.c_int, [_VP, c_dp]),

@@ -867,6 +867,31 @@ def mcmc_draw_stats(ctx):
     return dict(draw_ms=s[0], candidates=int(s[1]), accepted=int(s[2]), block_bound=int(s[3]))
 
 
+def group_mcmc_incidence(pairs, nodes):
+    """msm_group_mcmc_incidence: the incidence of a pair list (P x 2) over `nodes` nodes as CSR (ptr nodes + 1, idx): for node n the pair indices p with
+    pairs[p][0] == n or pairs[p][1] == n, ascending"""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P = pr.shape[0]
+    ptr = np.zeros(int(nodes) + 1, dtype=np.int32)
+    idx = np.zeros(max(2 * P, 1), dtype=np.int32)
+    check(lib().msm_group_mcmc_incidence(pr.ctypes.data_as(c_ip), P, int(nodes), ptr.ctypes.data_as(c_ip), idx.ctypes.data_as(c_ip)))
+    return ptr, idx[: ptr[-1]].copy()
+
+
+def group_mcmc_seeds(seed, it, K, S, subject, pass_=0):
+    """msm_group_mcmc_seeds: chain k of `subject` in pass pass_ of iteration it: seed + it + 1000003 k + 15485863 (pass_ S + subject), uint64 (K,)"""
+    out = np.zeros(int(K), dtype=np.uint64)
+    check(lib().msm_group_mcmc_seeds(int(seed) & 0xFFFFFFFFFFFFFFFF, int(it), int(pass_), int(S), int(subject), int(K), out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
+
+
+def group_mcmc_accept(start, best):
+    """msm_group_mcmc_accept: whether a block's best chain replaces the subject's labels -- its energy strictly below the start's, never with a NaN"""
+    a = C.c_int32(-1)
+    check(lib().msm_group_mcmc_accept(float(start), float(best), C.byref(a)))
+    return bool(a.value)
+
+
 def mcmc_schedule(triplets, N):
     """msm_mcmc_schedule: (level per triplet, the triplets by level, level offsets) of the GPU sweeps' level schedule"""
     tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
@@ -1426,6 +1451,51 @@ class DiscreteGroupCostFunction:
         out = np.zeros(len(t_))
         check(lib().msm_group_triplet_batch(self.h, pt, pa, pb, pc, len(t_), out.ctypes.data_as(c_dp)))
         return out
+
+    # ---- the Monte Carlo optimiser, subject by subject (an extension: the reference refuses MCMC in groupwise mode) ----
+    def conditional_unary(self, subject, labeling, fetch=True):
+        """msm_group_conditional_unary: U_s (L x N) of `subject` under `labeling` (S * N): per node and label the sum, in ascending pair index, of its
+        incident pairs' costs against the partners' current labels; fetch=False leaves it on the device and returns None"""
+        lab, pl = _i(labeling)
+        assert lab.size == self.S * self.N
+        U = np.zeros((self.L, self.N)) if fetch else None
+        check(lib().msm_group_conditional_unary(self.h, int(subject), pl, U.ctypes.data_as(c_dp) if fetch else None))
+        return U
+
+    def subject_triplet_table(self, subject, fetch=True):
+        """msm_group_subject_triplet_table: tc_s (Tc x L x L x L) of the subject's triplets in list order"""
+        tc = np.zeros((self.Tc, self.L, self.L, self.L)) if fetch else None
+        check(lib().msm_group_subject_triplet_table(self.h, int(subject), tc.ctypes.data_as(c_dp) if fetch else None))
+        return tc
+
+    def subject_triplets(self, subject):
+        """the subject's triplets with local node ids (Tc x 3)"""
+        s = int(subject)
+        return (self.getTriplets()[s * self.Tc:(s + 1) * self.Tc] - s * self.N).astype(np.int32)
+
+    def mcmc_subject(self, subject, labeling, seeds, mcparam=0.8, iters=100):
+        """msm_group_mcmc_subject: one block -- the chains of `seeds` on (U_s, tc_s) from the subject's labels, the best one kept when its energy is
+        strictly below the start's; returns (labeling S * N, (start energy, kept energy), accepted)"""
+        lab = np.array(labeling, dtype=np.int32).reshape(-1)
+        assert lab.size == self.S * self.N
+        sd = np.ascontiguousarray(np.atleast_1d(seeds), dtype=np.uint64)
+        e = np.zeros(2)
+        acc = C.c_int32(-1)
+        check(lib().msm_group_mcmc_subject(self.h, int(subject), lab.ctypes.data_as(c_ip), float(mcparam), int(iters), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           len(sd), e.ctypes.data_as(c_dp), C.byref(acc)))
+        return lab, (float(e[0]), float(e[1])), bool(acc.value)
+
+    BLOCK_RECORD = ("start", "kept", "accepted", "best", "pair_ms", "sum_ms", "triplet_ms", "sweep_ms")
+
+    def mcmc_pass(self, labeling, mcparam=0.8, iters=100, seed=0, it=0, chains=1, passes=1):
+        """msm_group_mcmc_pass: `passes` passes of blocks over the subjects in ascending order, chain k of subject s in pass p seeded
+        seed + it + 1000003 k + 15485863 (p S + s); returns (labeling S * N, per-block records (passes, S, 8): BLOCK_RECORD)"""
+        lab = np.array(labeling, dtype=np.int32).reshape(-1)
+        assert lab.size == self.S * self.N
+        rec = np.zeros((max(int(passes), 1), self.S, 8))
+        check(lib().msm_group_mcmc_pass(self.h, lab.ctypes.data_as(c_ip), float(mcparam), int(iters), int(seed) & 0xFFFFFFFFFFFFFFFF, int(it), int(chains),
+                                        int(passes), rec.ctypes.data_as(c_dp)))
+        return lab, rec
 
 
 # ------------------------------------------------------------------ rigid level

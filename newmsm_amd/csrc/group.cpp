@@ -191,6 +191,8 @@ void msm_group_destroy(msm_group *g) {
     for (hipEvent_t e : g->copy_events) (void)hipEventDestroy(e);
     if (g->t_ev0) (void)hipEventDestroy(g->t_ev0);
     if (g->t_ev1) (void)hipEventDestroy(g->t_ev1);
+    for (hipEvent_t e : g->mc_ev)
+        if (e) (void)hipEventDestroy(e);
     delete g;
 }
 

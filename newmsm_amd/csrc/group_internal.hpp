@@ -156,6 +156,13 @@ struct msm_group {
     bool timing = false, timed = false;
     hipStream_t copy_stream = nullptr;   // the finished pieces of a label step leave for the host while the next ones are computed
     std::vector<hipEvent_t> copy_events;
+    // msm_group_mcmc_* (group_mcmc.cpp): the incidence of the pair list of set-up mc_inc_gen, the labelling a block reads, its segment
+    // offsets, the pair costs of its queries and its two tables -- one set of buffers, reused by every block; events around a block's phases
+    std::vector<int32_t> mc_inc_ptr, mc_inc_idx;
+    DevBuf<int32_t> d_mc_inc_ptr, d_mc_inc_idx, d_mc_lab, d_mc_seg;
+    DevBuf<double> d_mc_U, d_mc_tc;
+    uint64_t mc_inc_gen = ~0ull;
+    hipEvent_t mc_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 

@@ -11,7 +11,11 @@ triplet costs --, applyLabeling, then per subject: unfold the moved control grid
 (sphere_project_warp), unfold it.  The loop is caller logic; what it calls goes through `ops` (ProductGroupOps below over the C ABI; the parity
 tests pass an oracle-backed object with the same methods).  The binary solve of a label step (ELC + FastPD: licence-restricted, FSL-bound)
 is replaced by a stand-in, as in registration.run_discrete_level(optimiser="fusion"): the run exercises the path as HOCR drives it, its
-result is not the reference's optimum."""
+result is not the reference's optimum.
+
+optimiser="mcmc" (an extension, opt-in: the reference refuses anything but HOCR in groupwise mode, M/group_mesh_registration.cpp:87) replaces the label loop
+by block-coordinate descent over the subjects with the reference's own Monte Carlo optimiser (MCMC::optimise, M/mcmc_opt.h:31-134) on every block
+(DiscreteGroupCostFunction.mcmc_pass)."""
 import numpy as np
 
 from . import api
@@ -19,11 +23,11 @@ from .registration import ProductOps, apply_labeling, finish_features, level_fea
 
 
 class ProductGroupOps(ProductOps):
-    def __init__(self, ctx, host_rotations=True, features_gpu=False):
-        """features_gpu: as ProductOps' (a level's features for all subjects in one msm_level_features call).  host_rotations (the library's default): the rotation matrices of the data meshes' vertices from the host's libm, as the reference computes them
+    def __init__(self, ctx, host_rotations=True, features_gpu=False, mcmc_draw_gpu=False):
+        """mcmc_draw_gpu: as ProductOps' (the proposals of the optimiser="mcmc" blocks are drawn by the draw kernel: the same labellings).  features_gpu: as ProductOps' (a level's features for all subjects in one msm_level_features call).  host_rotations (the library's default): the rotation matrices of the data meshes' vertices from the host's libm, as the reference computes them
         (DiscreteGroupCostFunction.set_rotation_mode) -- on regular icospheres (template and subjects' spheres alike, as gMSM's scripts set them up) a label
         carries data vertices exactly onto template vertices and the last bits of the rotation decide the resampled values there; False: the device computes them"""
-        super().__init__(ctx, features_gpu=features_gpu)
+        super().__init__(ctx, mcmc_gpu=bool(mcmc_draw_gpu), features_gpu=features_gpu, mcmc_draw_gpu=mcmc_draw_gpu)  # (a group's blocks sweep on the device)
         self.host_rotations = host_rotations
 
     def group(self, S, simmeasure, lambda_, fixnan, **params):
@@ -65,15 +69,22 @@ class _ProductGroup:
     def fusion_move(self, labeling, label):
         return self.g.fusionMove(labeling, label)
 
+    def mcmc_pass(self, labeling, mcparam, iters, seed, it, chains, passes):
+        return self.g.mcmc_pass(labeling, mcparam=mcparam, iters=iters, seed=seed, it=it, chains=chains, passes=passes)
+
 
 def run_group_level(ops, template_xyz, template_tri, data_xyz, data_tri, feats, sph_regs, cp_order, *, iters=2, simmeasure=2, lambda_=0.1,
-                    labeldist=0.5, icm_passes=5, timings=None, fixnan=True, sg_order=None, cps_start=None, mask=None, cost_params=None):
+                    labeldist=0.5, icm_passes=5, timings=None, fixnan=True, sg_order=None, cps_start=None, mask=None, cost_params=None, optimiser="fusion",
+                    mciters=200, mcparam=0.8, seed=0, mcmc_chains=1, mcmc_passes=1, blocks_out=None):
     """feats: S x D x V data on the subjects' data grid (data_xyz, data_tri: the regular sphere the features live on); sph_regs: S x V x 3,
     every subject's registered sphere so far.  sg_order: the sampling grid's resolution (--SGgrid, m_SGres; two above the control grid when not
     given); cps_start (S x N x 3, optional): the control grids the level starts from (warp_CPgrid of the previous level's warp,
     M/DiscreteGroupModel.h:69-72; the regular grid when not given); mask (V(template), optional): --mask, the weights of the common template
     vertices in a pair cost (M/DiscreteGroupCostFunction.cpp:77); cost_params: the strain and similarity parameters of ops.group.  fixnan (--fixnan, M/DiscreteGroupCostFunction.cpp:50,96): the cost of two patches without a
-    common template vertex is 1e7 instead of NaN -- with NaN costs the stand-in solve never moves a node of such a pair.  Returns (sph_regs, control grids S x N x 3, energies per iteration, labelings)."""
+    common template vertex is 1e7 instead of NaN -- with NaN costs the stand-in solve never moves a node of such a pair.  optimiser: "fusion" (the label
+    loop with the stand-in solve) or "mcmc": every iteration runs mcmc_passes passes of blocks over the subjects from the zero labelling the label loop
+    starts from, each block mcmc_chains chains of mciters sweeps with --mcparam, chain k of subject s in pass p seeded seed + it + 1000003 k +
+    15485863 (p S + s) (g.mcmc_pass); blocks_out (a list, optional) receives every iteration's per-block records.  Returns (sph_regs, control grids S x N x 3, energies per iteration, labelings)."""
     import time
 
     clock = timings if timings is not None else {}
@@ -84,6 +95,8 @@ def run_group_level(ops, template_xyz, template_tri, data_xyz, data_tri, feats, 
         clock[name] = clock.get(name, 0.0) + time.perf_counter() - t0
         return out
 
+    if optimiser not in ("fusion", "mcmc"):
+        raise ValueError("run_group_level: optimiser must be 'fusion' or 'mcmc', not %r" % (optimiser,))
     S = len(feats)
     cp_xyz0, cp_tri = ops.icosphere(cp_order)
     N = len(cp_xyz0)
@@ -119,7 +132,11 @@ def run_group_level(ops, template_xyz, template_tri, data_xyz, data_tri, feats, 
         timed("setup", g.setup)
         pairs, triplets = g.pairs(), g.triplets()
         labeling = np.zeros(S * N, dtype=np.int32)  # resetLabeling
-        for sweep in range(2):
+        if optimiser == "mcmc":
+            labeling, blocks = timed("optimiser", g.mcmc_pass, labeling, mcparam, mciters, seed, it, mcmc_chains, mcmc_passes)
+            if blocks_out is not None:
+                blocks_out.append(blocks)
+        for sweep in range(2 if optimiser == "fusion" else 0):
             for label in range(len(samples)):
                 if not np.any(labeling != label):
                     continue
@@ -144,6 +161,9 @@ def run_group_level(ops, template_xyz, template_tri, data_xyz, data_tri, feats, 
             prev[s], cps[s] = new_cp, new_cp
         energy = newenergy
     return np.stack(sph_regs), np.stack(cps), energies, labelings
+
+
+run_group_discrete_opt = run_group_level  # the reference's name for the level loop (Group_Mesh_registration::run_discrete_opt)
 
 
 def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, levels, *, mask=None, varnorm=False, fixnan=False, timings=None,
@@ -208,6 +228,8 @@ def run_group_multiresolution(ops, meshes, datas, template_xyz, template_tri, le
                 sph.append(moved)
         kw = dict(level_kw)
         kw.update({k: lv[k] for k in ("sg_order", "iters", "simmeasure") if k in lv})
+        if lv.get("optimiser") == "mcmc":  # (a level from config.levels_from_config carries "fusion" for --dopt=HOCR: the default)
+            kw.update({k: lv[k] for k in ("optimiser", "mciters", "mcparam") if k in lv})
         if "cost_params" in lv:
             kw["cost_params"] = {k: v for k, v in lv["cost_params"].items() if k != "lambda_"}
             if "lambda_" in lv["cost_params"]:

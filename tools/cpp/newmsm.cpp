@@ -213,6 +213,37 @@ bool mcmc_draw_gpu_setting() {
     return true;
 }
 
+// MSMHIP_GROUP_MCMC=on: a --groupwise configuration with --dopt=MCMC runs, block-coordinate descent over the subjects with the Monte Carlo optimiser on
+// every block (an extension); unset: it ends with the reference's message (M/group_mesh_registration.cpp:87).  Anything else ends
+// the run with a message and exit status 1.
+bool group_mcmc_setting() {
+    const char *env = std::getenv("MSMHIP_GROUP_MCMC");
+    if (!env) return false;
+    if (std::string(env) != "on")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_GROUP_MCMC=") + env + ": the groupwise Monte Carlo optimiser is switched on with MSMHIP_GROUP_MCMC=on (unset: off)");
+    return true;
+}
+
+// MSMHIP_GROUP_MCMC_PASSES=n (1 ... 64): passes over the subjects per iteration of a groupwise --dopt=MCMC level; unset: 1
+int group_mcmc_passes_setting() {
+    const char *env = std::getenv("MSMHIP_GROUP_MCMC_PASSES");
+    if (!env) return 1;
+    char *end = nullptr;
+    const long n = std::strtol(env, &end, 10);
+    if (end == env || *end != '\0' || n < 1 || n > 64)
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_GROUP_MCMC_PASSES=") + env + ": the number of passes over the subjects must be a whole number from 1 to 64");
+    return (int)n;
+}
+
+// MSMHIP_MCMC_DRAW for a groupwise --dopt=MCMC run, whose blocks always sweep on the device: gpu, host or unset
+bool group_mcmc_draw_setting() {
+    const char *env = std::getenv("MSMHIP_MCMC_DRAW");
+    if (!env || std::string(env) == "host") return false;
+    if (std::string(env) != "gpu")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MCMC_DRAW=") + env + ": the proposals are drawn on the host (host, or unset) or on the device (gpu)");
+    return true;
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const int mcmc_chains = mcmc_chains_setting();
     const bool mcmc_draw_gpu = mcmc_draw_gpu_setting();
@@ -296,6 +327,9 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
 }
 
 int run_groupwise(const Options &o, const Formats &fmt, int device) {
+    const bool group_mcmc = group_mcmc_setting();
+    const int mcmc_chains = group_mcmc ? mcmc_chains_setting() : 1, mcmc_passes = group_mcmc ? group_mcmc_passes_setting() : 1;
+    const bool mcmc_draw_gpu = group_mcmc && group_mcmc_draw_setting();
     for (const char *flag : {"meshes", "template", "data"})
         if (o.get(flag).empty()) throw Error(MSM_ERR_INVALID, std::string("newmsm: --groupwise needs --") + flag);
     const std::vector<std::string> mesh_files = read_ascii_list(o.get("meshes")), data_files = read_ascii_list(o.get("data"));
@@ -305,10 +339,12 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
     bool varnorm = false;
     IntensityNorm inorm;
-    std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm, histmatch_enabled() ? &inorm : nullptr);  // refuses AFFINE / RIGID levels and optimisers other than HOCR
+    // refuses AFFINE / RIGID levels and optimisers other than HOCR (and, with MSMHIP_GROUP_MCMC=on, MCMC)
+    std::vector<GroupLevelSpec> levels = group_levels_from_config(cfg, &varnorm, histmatch_enabled() ? &inorm : nullptr, group_mcmc);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
     if (features_gpu_enabled())
         for (GroupLevelSpec &lv : levels) lv.options.features_gpu = true;
+    for (GroupLevelSpec &lv : levels) lv.options.mcmc_chains = mcmc_chains, lv.options.mcmc_passes = mcmc_passes, lv.options.mcmc_draw_gpu = mcmc_draw_gpu;
     std::vector<std::pair<Points, Triangles>> meshes;
     for (size_t k = 0; k < mesh_files.size(); ++k) {
         if (o.has("verbose")) std::cout << "Mesh #" << k << " is " << mesh_files[k] << std::endl;
@@ -336,6 +372,9 @@ int run_groupwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("verbose"))
         std::cout << "This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with " << levels.size() << " levels." << std::endl;
     if (o.has("verbose") && features_gpu_enabled()) std::cout << "Level features in one call on the GPU." << std::endl;
+    if (o.has("verbose") && cfg.dopt == "MCMC")
+        std::cout << "Groupwise MCMC, subject by subject: " << mcmc_chains << " chains per block, " << mcmc_passes << " passes per iteration, proposals drawn on the "
+                  << (mcmc_draw_gpu ? "GPU" : "host") << "." << std::endl;
     const GroupMultiresResult res = run_group_multiresolutions(ctx, meshes, datas, D, txyz, ttri, levels, varnorm, mask.empty() ? nullptr : &mask, nullptr,
                                                                exclusion_from_config(cfg), inorm);
     const Triangles last_tri = make_mesh_from_icosa(levels.back().data_order).second;

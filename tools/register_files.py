@@ -161,6 +161,42 @@ def mcmc_draw_gpu_setting():
     return True
 
 
+def group_mcmc_setting():
+    """MSMHIP_GROUP_MCMC=on: a --groupwise configuration with --dopt=MCMC runs, block-coordinate descent over the subjects with the Monte Carlo optimiser
+    on every block (an extension); unset: it ends with the reference's message (M/group_mesh_registration.cpp:87).  Anything else
+    ends the run with a message and exit status 1."""
+    text = os.environ.get("MSMHIP_GROUP_MCMC")
+    if text is None:
+        return False
+    if text != "on":
+        raise SystemExit("MSMHIP_GROUP_MCMC=%s: the groupwise Monte Carlo optimiser is switched on with MSMHIP_GROUP_MCMC=on (unset: off)" % text)
+    return True
+
+
+def group_mcmc_passes_setting():
+    """MSMHIP_GROUP_MCMC_PASSES=n (1 ... 64): passes over the subjects per iteration of a groupwise --dopt=MCMC level; unset: 1"""
+    text = os.environ.get("MSMHIP_GROUP_MCMC_PASSES")
+    if text is None:
+        return 1
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if not 1 <= n <= 64:
+        raise SystemExit("MSMHIP_GROUP_MCMC_PASSES=%s: the number of passes over the subjects must be a whole number from 1 to 64" % text)
+    return n
+
+
+def group_mcmc_draw_setting():
+    """MSMHIP_MCMC_DRAW for a groupwise --dopt=MCMC run, whose blocks always sweep on the device: gpu, host or unset"""
+    text = os.environ.get("MSMHIP_MCMC_DRAW")
+    if text is None or text == "host":
+        return False
+    if text != "gpu":
+        raise SystemExit("MSMHIP_MCMC_DRAW=%s: the proposals are drawn on the host (host, or unset) or on the device (gpu)" % text)
+    return True
+
+
 def discrete_levels(cfg, D, anat=False, groupwise=False):
     levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
                                                         **(dict(histmatch=True) if histmatch_enabled() else {}))
@@ -176,8 +212,10 @@ def features_gpu_enabled():
     return os.environ.get("MSMHIP_FEATURES", "") == "gpu"
 
 
-def main_groupwise(a, surf_ext, data_ext):
-    """CLI/newmsm.cpp:13-27 + Group_Mesh_registration (M/group_mesh_registration.h:46-82, .cpp:26-133)"""
+def main_groupwise(a, surf_ext, data_ext, group_mcmc=False, chains=1, draw_gpu=False):
+    """CLI/newmsm.cpp:13-27 + Group_Mesh_registration (M/group_mesh_registration.h:46-82, .cpp:26-133).  group_mcmc (MSMHIP_GROUP_MCMC=on): --dopt=MCMC runs
+    instead of being refused, with `chains` chains per block and the proposals drawn where draw_gpu says"""
+    passes = group_mcmc_passes_setting() if group_mcmc else 1
     for flag in ("meshes", "template", "data"):
         if not getattr(a, flag):
             raise SystemExit("register_files.py: --groupwise needs --%s" % flag)
@@ -189,7 +227,7 @@ def main_groupwise(a, surf_ext, data_ext):
     cfg = config.parse_config(read_conf(a.conf))
     if any(m in ("RIGID", "AFFINE") for m in cfg["opt"]):
         raise SystemExit("AFFINE/RIGID registration is not supported in groupwise mode.")  # M/group_mesh_registration.cpp:29-30
-    if cfg["dopt"] != "HOCR":
+    if cfg["dopt"] != "HOCR" and not (group_mcmc and cfg["dopt"] == "MCMC"):
         raise SystemExit("Groupwise mode is only supported in the HOCR version of MSM.")  # :87
     meshes = []
     for k, path in enumerate(mesh_files):
@@ -209,8 +247,12 @@ def main_groupwise(a, surf_ext, data_ext):
         print("This is newMSM's groupwise DISCRETE path on an MI355X (msm-mi355x).\nStarting multiresolution with %d levels." % len(levels))
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
-    regs, level_regs, energies = group_registration.run_group_multiresolution(group_registration.ProductGroupOps(ctx, features_gpu=features_gpu_enabled()), meshes, datas, txyz, ttri, levels, mask=mask,
-                                                                              fixnan=cfg["fixnan"], **run_kw, **config.run_options(cfg))
+        if cfg["dopt"] == "MCMC":
+            print("Groupwise MCMC, subject by subject: %d chains per block, %d passes per iteration, proposals drawn on the %s." % (chains, passes, "GPU" if draw_gpu else "host"))
+    mc_kw = dict(mcmc_chains=chains, mcmc_passes=passes) if cfg["dopt"] == "MCMC" else {}
+    ops = group_registration.ProductGroupOps(ctx, features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu and cfg["dopt"] == "MCMC")
+    regs, level_regs, energies = group_registration.run_group_multiresolution(ops, meshes, datas, txyz, ttri, levels, mask=mask,
+                                                                              fixnan=cfg["fixnan"], **run_kw, **config.run_options(cfg), **mc_kw)
     last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])[1]
     target = M.Mesh(ctx, txyz, ttri)
     for s in range(len(meshes)):
@@ -226,13 +268,14 @@ def main_groupwise(a, surf_ext, data_ext):
 
 def main(argv):
     a = parse_args(argv)
-    chains = mcmc_chains_setting()  # (the groupwise loops run no MCMC: checked, then unused there)
-    draw_gpu = mcmc_draw_gpu_setting()
+    chains = mcmc_chains_setting()  # (the groupwise loops run no MCMC unless MSMHIP_GROUP_MCMC=on: checked, then unused there)
+    group_mcmc = a.groupwise and group_mcmc_setting()
+    draw_gpu = group_mcmc_draw_setting() if group_mcmc else mcmc_draw_gpu_setting()
     surf_ext, data_ext = output_formats(a.format)
     if surf_ext == ".vtk":
         raise SystemExit("register_files.py: VTK output is not written here (GIFTI, ASCII, ASCII_MAT)")
     if a.groupwise:
-        return main_groupwise(a, surf_ext, data_ext)
+        return main_groupwise(a, surf_ext, data_ext, group_mcmc, chains, draw_gpu)
     for flag in ("inmesh", "indata", "refdata"):
         if not getattr(a, flag):
             raise SystemExit("register_files.py: --%s is required" % flag)
