@@ -621,48 +621,39 @@ int msm_cost_triplet_table(msm_cost *c, int32_t t0, int32_t t1, double *tcosts) 
     return check_status(ctx, "computeTripletCosts");
 }
 
-// computeUnaryCosts + computeTripletCosts + MCMC::optimise with both tables staying where their kernels wrote them (mcmc.cpp runs the sweeps)
-int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t seed, int32_t *labeling) {
+// computeUnaryCosts + computeTripletCosts for MCMC::optimise, both tables staying where their kernels wrote them (c->d_U, c->d_clique_out): what both
+// msm_cost_mcmc_optimise* do ahead of the sweeps (mcmc.cpp runs those), the host optimiser's checks first, before anything is launched
+static int mcmc_tables_on_device(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, const int32_t *labeling, int *N, int *L, int *T) {
     if (!c || !labeling || iters < 0) return fail(MSM_ERR_INVALID, "msm_cost_mcmc_optimise: bad arguments");
     if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mcmc_optimise: meshes, labels and triplets must be set first");
-    // the host optimiser's checks, before anything is launched
+    MSM_TRY(mcmc_check_chains(seeds, K));
     MSM_TRY(mcmc_check_arguments(c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), mcparam, labeling));
     MSM_TRY(msm_cost_unary_table_async(c));  // (drops a label step queued ahead on the context first)
     MSM_TRY(check_status(c->ctx, "computeUnaryCosts"));  // what the table's kernels raised is reported as msm_cost_unary_table reports it
     CliqueArgs a;
     MSM_TRY(clique_args(c, true, false, a));
-    msm_ctx *ctx = c->ctx;
-    const int N = a.N, L = a.L, T = a.T;
-    const size_t per = (size_t)L * L * L, total = (size_t)T * per;
+    const size_t per = (size_t)a.L * a.L * a.L, total = (size_t)a.T * per;
     if (c->d_clique_out.ensure(total ? total : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * total);
     // the table kernel indexes one launch with 32 bits of workgroups: a table beyond 2^31 values is filled in triplet ranges
-    const int step = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, ((size_t)1 << 31) / per));
-    for (int t0 = 0; t0 < T; t0 += step) MSM_TRY(launch_triplet_table(ctx, a, t0, std::min(T, t0 + step), c->d_clique_out.p + (size_t)t0 * per));
+    const int step = (int)std::max<size_t>(1, std::min<size_t>((size_t)a.T, ((size_t)1 << 31) / per));
+    for (int t0 = 0; t0 < a.T; t0 += step) MSM_TRY(launch_triplet_table(c->ctx, a, t0, std::min(a.T, t0 + step), c->d_clique_out.p + (size_t)t0 * per));
     c->counters[2] += (int64_t)total;
-    MSM_TRY(check_status(ctx, "computeTripletCosts"));  // before the sweeps, as msm_cost_triplet_table reports it
-    return mcmc_run_device(ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seed, labeling);
+    *N = a.N, *L = a.L, *T = a.T;
+    return check_status(c->ctx, "computeTripletCosts");  // before the sweeps, as msm_cost_triplet_table reports it
 }
 
-// the same for K chains from one start (mcmc.cpp: mcmc_run_device_chains); the tables are built once and shared
+int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t seed, int32_t *labeling) {
+    int N, L, T;
+    MSM_TRY(mcmc_tables_on_device(c, mcparam, iters, &seed, 1, labeling, &N, &L, &T));
+    return mcmc_run_device(c->ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seed, labeling);
+}
+
+// the same for K chains from one start; the tables are built once and shared
 int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings,
                                   double *energies, int32_t *best) {
-    if (!c || !labeling || iters < 0) return fail(MSM_ERR_INVALID, "msm_cost_mcmc_optimise: bad arguments");
-    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mcmc_optimise: meshes, labels and triplets must be set first");
-    MSM_TRY(mcmc_check_chains(seeds, K));
-    MSM_TRY(mcmc_check_arguments(c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), mcparam, labeling));
-    MSM_TRY(msm_cost_unary_table_async(c));
-    MSM_TRY(check_status(c->ctx, "computeUnaryCosts"));
-    CliqueArgs a;
-    MSM_TRY(clique_args(c, true, false, a));
-    msm_ctx *ctx = c->ctx;
-    const int N = a.N, L = a.L, T = a.T;
-    const size_t per = (size_t)L * L * L, total = (size_t)T * per;
-    if (c->d_clique_out.ensure(total ? total : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * total);
-    const int step = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, ((size_t)1 << 31) / per));
-    for (int t0 = 0; t0 < T; t0 += step) MSM_TRY(launch_triplet_table(ctx, a, t0, std::min(T, t0 + step), c->d_clique_out.p + (size_t)t0 * per));
-    c->counters[2] += (int64_t)total;
-    MSM_TRY(check_status(ctx, "computeTripletCosts"));
-    return mcmc_run_device_chains(ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
+    int N, L, T;
+    MSM_TRY(mcmc_tables_on_device(c, mcparam, iters, seeds, K, labeling, &N, &L, &T));
+    return mcmc_run_device_chains(c->ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
 }
 
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on

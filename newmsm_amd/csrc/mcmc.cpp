@@ -1,7 +1,8 @@
 // mcmc.cpp -- the host side of the Monte Carlo optimiser's GPU sweeps (mcmc.hpp; kernel: mcmc_kernels.hip): the level schedule, the
-// proposal stream in chunks of whole sweeps, and the loop that draws chunk k + 1 while the device walks chunk k; the same for several chains from one
-// start (their streams drawn on the host workers, their energies summed here, the best one kept), and the host-only chains, energy and selection.  With
-// msm_ctx_set_mcmc_draw(ctx, 1) the streams are drawn by a kernel on a side stream instead (DeviceDraw; mcmc_draw.hpp, mcmc_draw_kernels.hip).
+// proposal streams of K chains from one start in chunks of whole sweeps, and the one loop that draws chunk c + 1 while the device walks chunk c (the
+// streams drawn on the host workers, the chains' energies summed here, the best one kept; a single chain is K = 1), and the host-only chains, energy and
+// selection.  With msm_ctx_set_mcmc_draw(ctx, 1) the streams are drawn by a kernel on a side stream instead (DeviceDraw; mcmc_draw.hpp,
+// mcmc_draw_kernels.hip).
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -12,13 +13,38 @@ using namespace msm;
 
 namespace msm {
 
-int mcmc_check_arguments(const int32_t *triplets, int N, int L, int T, double mcparam, const int32_t *labeling) {
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+// the refusals that recur, each reported under the name `what`
+static int check_mcparam(const char *what, double mcparam) {
+    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "%s: the geometric distribution parameter must be in (0, 1]", what);
+    return MSM_OK;
+}
+
+static int check_label_count(const char *what, int L) {
+    if (L > 65535) return fail(MSM_ERR_INVALID, "%s: %d labels; the proposals travel as 16-bit values (at most 65535)", what, L);
+    return MSM_OK;
+}
+
+int mcmc_check_node_count(const char *what, int N) {
+    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "%s: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", what, N, kMcmcMaxNodes);
+    return MSM_OK;
+}
+
+static int check_labels(const int32_t *labeling, int N, int L) {
     for (int i = 0; i < N; ++i)
         if (labeling[i] < 0 || labeling[i] >= L) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: label of node %d out of range", i);
+    return MSM_OK;
+}
+
+static int check_triplets(const int32_t *triplets, int N, int T) {
     for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
         if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
     return MSM_OK;
+}
+
+int mcmc_check_arguments(const int32_t *triplets, int N, int L, int T, double mcparam, const int32_t *labeling) {
+    MSM_TRY(check_mcparam("msm_mcmc_optimise", mcparam));
+    MSM_TRY(check_labels(labeling, N, L));
+    return check_triplets(triplets, N, T);
 }
 
 int mcmc_check_chains(const uint64_t *seeds, int K) {
@@ -67,14 +93,24 @@ McmcScratch &mcmc_scratch(msm_ctx *ctx) {
     return *static_cast<McmcScratch *>(ctx->mcmc_scratch.get());
 }
 
-// sweeps per chunk: MSMHIP_MCMC_CHUNK_SWEEPS, or as many as make half a million proposals (1 MB).  The host draws about as fast as the device walks
-// (DESIGN.md 5.16), so the device idles for as long as the first chunk takes to draw: at 4 MB that was a sixth of a 2 000-sweep run at ico4.
-int chunk_sweeps(int T, int iters) {
-    long n = 0;
-    if (const char *e = std::getenv("MSMHIP_MCMC_CHUNK_SWEEPS")) n = std::atol(e);
-    if (n <= 0) n = ((long)1 << 19) / std::max(T, 1);
-    n = std::min(n, ((long)1 << 30) / std::max(T, 1));  // (a chunk is at most 2 GB of proposals, whatever the environment says)
-    return (int)std::max(1L, std::min(n, (long)iters));
+// a pool of timing events, a pair per chunk: grown to `pairs` pairs, and the time between the two events of each of the first `pairs` pairs, summed
+int grow_event_pairs(std::vector<hipEvent_t> &ev, int pairs) {
+    while (ev.size() < 2 * (size_t)pairs) {
+        hipEvent_t e;
+        MSM_HIP(hipEventCreate(&e));
+        ev.push_back(e);
+    }
+    return MSM_OK;
+}
+
+int sum_event_pairs(const std::vector<hipEvent_t> &ev, int pairs, double *ms) {
+    *ms = 0.0;
+    for (int c = 0; c < pairs; ++c) {
+        float f = 0.f;
+        MSM_HIP(hipEventElapsedTime(&f, ev[2 * (size_t)c], ev[2 * (size_t)c + 1]));
+        *ms += f;
+    }
+    return MSM_OK;
 }
 
 // host -> device through the staging blocks in pieces (a table of 281 MB must not ask for one staging block of its size)
@@ -121,11 +157,7 @@ struct DeviceDraw {
         if (s->draw_status.zero(1, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int));
         if (!s->draw_stream) MSM_HIP(hipStreamCreateWithFlags(&s->draw_stream, hipStreamNonBlocking));
         if (!s->draw_begin) MSM_HIP(hipEventCreateWithFlags(&s->draw_begin, hipEventDisableTiming));
-        while (s->draw_ev.size() < 2 * (size_t)chunks) {
-            hipEvent_t e;
-            MSM_HIP(hipEventCreate(&e));
-            s->draw_ev.push_back(e);
-        }
+        MSM_TRY(grow_event_pairs(s->draw_ev, chunks));
         MSM_HIP(hipEventRecord(s->draw_begin, ctx->stream));  // the uploads above, and whatever read the buffers before this call
         MSM_HIP(hipStreamWaitEvent(s->draw_stream, s->draw_begin, 0));
         d.rec = s->rec.p;
@@ -166,11 +198,7 @@ struct DeviceDraw {
     // after the context's stream has been synchronised: the counters, and the draw's own error
     int finish(const char *what) {
         double ms = 0.0, candidates = 0.0, accepted = 0.0;
-        for (int c = 0; c < chunks_drawn; ++c) {
-            float f = 0.f;
-            MSM_HIP(hipEventElapsedTime(&f, s->draw_ev[2 * (size_t)c], s->draw_ev[2 * (size_t)c + 1]));
-            ms += f;
-        }
+        MSM_TRY(sum_event_pairs(s->draw_ev, chunks_drawn, &ms));
         for (const McmcDrawRecord &r : recs) {
             candidates += (double)r.candidates;
             accepted += (double)r.accepted;
@@ -200,129 +228,18 @@ namespace msm {
 
 int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
                     int32_t *labeling) {
-    if (iters <= 0 || T <= 0) return MSM_OK;
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
-    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
-    McmcScratch &s = mcmc_scratch(ctx);
-    McmcSchedule sch;
-    mcmc_build_schedule(triplets, N, T, sch);
-    std::vector<int4> rec((size_t)T);
-    std::vector<int32_t> pos((size_t)T);  // where triplet t stands in the schedule
-    for (int i = 0; i < T; ++i) {
-        const int t = sch.order[(size_t)i];
-        rec[(size_t)i] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
-        pos[(size_t)t] = i;
-    }
-    const int chunk = chunk_sweeps(T, iters);
-    const int chunks = (iters + chunk - 1) / chunk;
-    MSM_TRY(s.sched.upload_vec(rec, ctx));
-    MSM_TRY(s.level_off.upload_vec(sch.level_off, ctx));
-    MSM_TRY(s.labeling.upload(labeling, (size_t)N, ctx));
-    if (s.prop.ensure((size_t)chunk * T) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * (size_t)chunk * T);
-    while (s.ev.size() < 2 * (size_t)chunks) {
-        hipEvent_t e;
-        MSM_HIP(hipEventCreate(&e));
-        s.ev.push_back(e);
-    }
-    McmcArgs a;
-    a.U = d_U;
-    a.tc = d_tc;
-    a.sched = s.sched.p;
-    a.level_off = s.level_off.p;
-    a.prop = s.prop.p;
-    a.labeling = s.labeling.p;
-    a.N = N;
-    a.L = L;
-    a.T = T;
-    a.levels = sch.levels();
-    a.status = ctx->d_status;
-    if (ctx->mcmc_draw == 1) {
-        // the proposals drawn on the device, chain machinery with K = 1: chunk k + 1 is drawn on the side stream into the other buffer while chunk k is walked
-        if (s.prop2.ensure((size_t)chunk * T) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * (size_t)chunk * T);
-        uint16_t *const bufs[2] = {s.prop.p, s.prop2.p};
-        DeviceDraw dd;
-        MSM_TRY(dd.begin(ctx, s, L, mcparam, &seed, 1, T, chunk, pos.data(), chunks));
-        MSM_TRY(dd.draw(0, bufs[0], std::min(chunk, iters), nullptr));
-        for (int k = 0, done = 0; k < chunks; ++k) {
-            const int sweeps = std::min(chunk, iters - done);
-            done += sweeps;
-            if (done < iters) MSM_TRY(dd.draw(k + 1, bufs[(k + 1) & 1], std::min(chunk, iters - done), k >= 1 ? s.ev[2 * (size_t)(k - 1) + 1] : nullptr));
-            MSM_TRY(dd.join(k));
-            a.prop = bufs[k & 1];
-            a.sweeps = sweeps;
-            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
-            MSM_TRY(launch_mcmc_sweeps(ctx, a));
-            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
-        }
-        std::vector<int32_t> lab((size_t)N);  // the caller's labelling stays as it is when the call fails
-        MSM_TRY(s.labeling.download(lab.data(), (size_t)N, ctx));
-        MSM_TRY(dd.collect());
-        MSM_TRY(finish_device_draw(ctx, dd, "msm_mcmc_optimise_gpu"));
-        std::copy(lab.begin(), lab.end(), labeling);
-        double kernel_ms = 0.0;
-        for (int k = 0; k < chunks; ++k) {
-            float ms = 0.f;
-            MSM_HIP(hipEventElapsedTime(&ms, s.ev[2 * (size_t)k], s.ev[2 * (size_t)k + 1]));
-            kernel_ms += ms;
-        }
-        s.stats[0] = kernel_ms;
-        s.stats[1] = (double)iters * sch.levels();
-        s.stats[2] = 0.0;
-        s.stats[3] = chunks;
-        s.stats[4] = sch.levels();
-        s.stats[5] = sch.widest();
-        s.chains = 1;
-        s.draw_threads = 0;
-        return MSM_OK;
-    }
-    McmcProposals proposals(seed, mcparam, L);
-    std::vector<uint16_t> buf((size_t)chunk * T);
-    double draw_ms = 0.0;
-    // a chunk in the kernel's order: the stream is drawn in visit order, and the label of triplet t goes to t's place in the schedule
-    auto draw = [&](int sweeps) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int sw = 0; sw < sweeps; ++sw) {
-            uint16_t *row = buf.data() + (size_t)sw * T;
-            for (int t = 0; t < T; ++t) row[(size_t)pos[(size_t)t]] = (uint16_t)proposals.next();
-        }
-        draw_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    };
-    draw(std::min(chunk, iters));
-    for (int k = 0, done = 0; k < chunks; ++k) {
-        const int sweeps = std::min(chunk, iters - done);
-        // behind the previous chunk's kernel on the stream: the one device buffer is free when this copy runs; buf is consumed on return
-        MSM_TRY(stage_h2d(ctx, s.prop.p, buf.data(), sizeof(uint16_t) * (size_t)sweeps * T));
-        a.sweeps = sweeps;
-        MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
-        MSM_TRY(launch_mcmc_sweeps(ctx, a));
-        MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
-        done += sweeps;
-        if (done < iters) draw(std::min(chunk, iters - done));  // while the device walks chunk k
-    }
-    MSM_TRY(s.labeling.download(labeling, (size_t)N, ctx));
-    MSM_TRY(check_status(ctx, "msm_mcmc_optimise_gpu"));
-    double kernel_ms = 0.0;
-    for (int k = 0; k < chunks; ++k) {
-        float ms = 0.f;
-        MSM_HIP(hipEventElapsedTime(&ms, s.ev[2 * (size_t)k], s.ev[2 * (size_t)k + 1]));
-        kernel_ms += ms;
-    }
-    s.stats[0] = kernel_ms;
-    s.stats[1] = (double)iters * sch.levels();
-    s.stats[2] = draw_ms;
-    s.stats[3] = chunks;
-    s.stats[4] = sch.levels();
-    s.stats[5] = sch.widest();
-    s.chains = s.draw_threads = 1;
-    return MSM_OK;
+    if (iters <= 0 || T <= 0) return MSM_OK;  // (the context's stats stay the previous call's)
+    return mcmc_run_device_chains(ctx, d_U, d_tc, triplets, N, L, T, mcparam, iters, &seed, 1, labeling, nullptr, nullptr, nullptr, "msm_mcmc_optimise_gpu");
 }
 
 int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters,
-                           const uint64_t *seeds, int K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best) {
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
-    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
+                           const uint64_t *seeds, int K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best, const char *what) {
+    MSM_TRY(check_label_count("msm_mcmc_optimise_gpu", L));
+    MSM_TRY(mcmc_check_node_count("msm_mcmc_optimise_gpu", N));
     McmcScratch &s = mcmc_scratch(ctx);
     const bool sweep = iters > 0 && T > 0;  // otherwise every chain is the start: only the energies are computed
+    const bool device_draw = ctx->mcmc_draw == 1 && sweep, host_draw = sweep && !device_draw;
+    const bool want_energies = K > 1 || energies;  // a single chain is the best one whatever its energy: no term is computed or fetched for it
     McmcSchedule sch;
     mcmc_build_schedule(triplets, N, T, sch);
     std::vector<int4> rec((size_t)T);
@@ -332,24 +249,23 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
         rec[(size_t)i] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
         pos[(size_t)t] = i;
     }
+    // The host draws about as fast as the device walks, so the device idles for as long as the first chunk takes to draw: hence chunks
+    // of half a million proposals per chain (mcmc_chunk_sweeps) and not more.
     long asked = 0;
     if (const char *e = std::getenv("MSMHIP_MCMC_CHUNK_SWEEPS")) asked = std::atol(e);
     const int chunk = mcmc_chunk_sweeps(asked, T, std::max(iters, 1), K);
     const int chunks = sweep ? (iters + chunk - 1) / chunk : 0;
     const int threads = mcmc_draw_threads(K);
     const size_t per_chunk = (size_t)K * chunk * T, nterms = (size_t)N + T;
-    std::vector<int32_t> labs((size_t)K * N);
+    std::vector<int32_t> labs((size_t)K * N);  // the caller's labelling stays as it is when the call fails
     for (int k = 0; k < K; ++k) std::copy(labeling, labeling + N, labs.begin() + (size_t)k * N);
     MSM_TRY(s.sched.upload_vec(rec, ctx));
     MSM_TRY(s.level_off.upload_vec(sch.level_off, ctx));
     MSM_TRY(s.labeling.upload_vec(labs, ctx));
     if (s.prop.ensure(std::max<size_t>(per_chunk, 1)) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * per_chunk);
-    if (s.terms.ensure((size_t)K * nterms) != hipSuccess) return stage_alloc_failed(sizeof(double) * (size_t)K * nterms);
-    while (s.ev.size() < 2 * (size_t)chunks) {
-        hipEvent_t e;
-        MSM_HIP(hipEventCreate(&e));
-        s.ev.push_back(e);
-    }
+    if (device_draw && s.prop2.ensure(per_chunk) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * per_chunk);
+    if (want_energies && s.terms.ensure((size_t)K * nterms) != hipSuccess) return stage_alloc_failed(sizeof(double) * (size_t)K * nterms);
+    MSM_TRY(grow_event_pairs(s.ev, chunks));
     McmcChainArgs c;
     McmcArgs &a = c.a;
     a.U = d_U;
@@ -366,70 +282,57 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
     a.status = ctx->d_status;
     c.chains = K;
     c.chunk_sweeps = chunk;
-    double draw_ms = 0.0;
-    const bool device_draw = ctx->mcmc_draw == 1 && sweep;
+    // The proposals of chunk k come from one of two sources.  Drawn on the device: queued on the side stream into buffer k & 1, behind the sweeps of
+    // chunk k - 2, which read that buffer; the context's stream then waits for the draw.  Drawn here: every chain's next sweeps into buf in the kernel's
+    // layout, the chains spread over the host workers (the wall clock of the threaded draw is kept); uploaded behind the previous chunk's kernel on the
+    // stream, when the one device buffer is free (buf is consumed on return; a short last chunk leaves the tail of every chain's block unread).
+    uint16_t *const bufs[2] = {s.prop.p, device_draw ? s.prop2.p : s.prop.p};
     DeviceDraw dd;
-    if (device_draw) {
-        // as in mcmc_run_device: chunk k + 1 of every chain is drawn on the side stream into the other buffer while chunk k is walked
-        if (s.prop2.ensure(per_chunk) != hipSuccess) return stage_alloc_failed(sizeof(uint16_t) * per_chunk);
-        uint16_t *const bufs[2] = {s.prop.p, s.prop2.p};
-        MSM_TRY(dd.begin(ctx, s, L, mcparam, seeds, K, T, chunk, pos.data(), chunks));
-        MSM_TRY(dd.draw(0, bufs[0], std::min(chunk, iters), nullptr));
-        for (int k = 0, done = 0; k < chunks; ++k) {
-            const int sweeps = std::min(chunk, iters - done);
-            done += sweeps;
-            if (done < iters) MSM_TRY(dd.draw(k + 1, bufs[(k + 1) & 1], std::min(chunk, iters - done), k >= 1 ? s.ev[2 * (size_t)(k - 1) + 1] : nullptr));
-            MSM_TRY(dd.join(k));
-            a.prop = bufs[k & 1];
-            a.sweeps = sweeps;
-            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
-            MSM_TRY(launch_mcmc_chains(ctx, c));
-            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
-        }
-    } else if (sweep) {
-        McmcChainStreams streams(seeds, K, mcparam, L);
-        std::vector<uint16_t> buf(per_chunk);
-        // a chunk of every chain in the kernel's layout, the chains spread over the host workers; the wall clock of the threaded draw
-        auto draw = [&](int sweeps) {
-            const auto t0 = std::chrono::steady_clock::now();
-            streams.draw(buf.data(), chunk, sweeps, T, pos.data(), threads);
-            draw_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        };
-        draw(std::min(chunk, iters));
-        for (int k = 0, done = 0; k < chunks; ++k) {
-            const int sweeps = std::min(chunk, iters - done);
-            // behind the previous chunk's kernel on the stream, as in mcmc_run_device; a short last chunk leaves the tail of every chain's block unread
-            MSM_TRY(upload_in_pieces(ctx, s.prop.p, buf.data(), sizeof(uint16_t) * (sweeps == chunk ? per_chunk : ((size_t)(K - 1) * chunk + sweeps) * T)));
-            a.sweeps = sweeps;
-            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
-            MSM_TRY(launch_mcmc_chains(ctx, c));
-            MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
-            done += sweeps;
-            if (done < iters) draw(std::min(chunk, iters - done));  // while the device walks chunk k
-        }
+    McmcChainStreams streams(seeds, host_draw ? K : 0, mcparam, L);
+    std::vector<uint16_t> buf(host_draw ? per_chunk : 0);
+    double draw_ms = 0.0;
+    auto draw = [&](int k, int sweeps) -> int {
+        if (device_draw) return dd.draw(k, bufs[k & 1], sweeps, k >= 2 ? s.ev[2 * (size_t)(k - 2) + 1] : nullptr);
+        const auto t0 = std::chrono::steady_clock::now();
+        streams.draw(buf.data(), chunk, sweeps, T, pos.data(), threads);
+        draw_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return MSM_OK;
+    };
+    auto deliver = [&](int k, int sweeps) -> int {
+        if (device_draw) return dd.join(k);
+        return upload_in_pieces(ctx, s.prop.p, buf.data(), sizeof(uint16_t) * (sweeps == chunk ? per_chunk : ((size_t)(K - 1) * chunk + sweeps) * T));
+    };
+    if (device_draw) MSM_TRY(dd.begin(ctx, s, L, mcparam, seeds, K, T, chunk, pos.data(), chunks));
+    if (sweep) MSM_TRY(draw(0, std::min(chunk, iters)));
+    for (int k = 0, done = 0; k < chunks; ++k) {
+        const int sweeps = std::min(chunk, iters - done);
+        done += sweeps;
+        MSM_TRY(deliver(k, sweeps));
+        a.prop = bufs[k & 1];
+        a.sweeps = sweeps;
+        MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k], ctx->stream));
+        MSM_TRY(launch_mcmc_chains(ctx, c));
+        MSM_HIP(hipEventRecord(s.ev[2 * (size_t)k + 1], ctx->stream));
+        if (done < iters) MSM_TRY(draw(k + 1, std::min(chunk, iters - done)));  // while the device walks chunk k
     }
-    MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.terms.p));
-    std::vector<double> terms((size_t)K * nterms);
+    std::vector<double> terms(want_energies ? (size_t)K * nterms : 0), E((size_t)K, 0.0);
+    if (want_energies) MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.terms.p));
     MSM_TRY(s.labeling.download(labs.data(), labs.size(), ctx));
-    MSM_TRY(s.terms.download(terms.data(), terms.size(), ctx));
+    if (want_energies) MSM_TRY(s.terms.download(terms.data(), terms.size(), ctx));
     if (device_draw) {
         MSM_TRY(dd.collect());
-        MSM_TRY(finish_device_draw(ctx, dd, "msm_mcmc_optimise_chains_gpu"));
+        MSM_TRY(finish_device_draw(ctx, dd, what));
     } else
-        MSM_TRY(check_status(ctx, "msm_mcmc_optimise_chains_gpu"));
-    std::vector<double> E((size_t)K);
-    for (int k = 0; k < K; ++k) E[(size_t)k] = mcmc_energy_of_terms(terms.data() + (size_t)k * nterms, N, T);
+        MSM_TRY(check_status(ctx, what));
+    if (want_energies)
+        for (int k = 0; k < K; ++k) E[(size_t)k] = mcmc_energy_of_terms(terms.data() + (size_t)k * nterms, N, T);
     const int b = mcmc_best_chain(E.data(), K);
     std::copy(labs.begin() + (size_t)b * N, labs.begin() + (size_t)(b + 1) * N, labeling);
     if (labelings) std::copy(labs.begin(), labs.end(), labelings);
     if (energies) std::copy(E.begin(), E.end(), energies);
     if (best) *best = b;
     double kernel_ms = 0.0;
-    for (int k = 0; k < chunks; ++k) {
-        float ms = 0.f;
-        MSM_HIP(hipEventElapsedTime(&ms, s.ev[2 * (size_t)k], s.ev[2 * (size_t)k + 1]));
-        kernel_ms += ms;
-    }
+    MSM_TRY(sum_event_pairs(s.ev, chunks, &kernel_ms));
     s.stats[0] = kernel_ms;
     s.stats[1] = sweep ? (double)iters * sch.levels() : 0.0;
     s.stats[2] = draw_ms;
@@ -443,36 +346,17 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
 
 }  // namespace msm
 
-extern "C" {
-
-int msm_mcmc_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
-                          int32_t iters, uint64_t seed, int32_t *labeling) {
-    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: null context");
-    if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
-    MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
-    if (iters == 0 || T == 0) return MSM_OK;
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
-    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
-    MSM_HIP(hipSetDevice(ctx->device));
-    MSM_TRY(drop_ctx_pending(ctx));
-    McmcScratch &s = mcmc_scratch(ctx);
-    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L;
-    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
-    if (s.tc.ensure(ntc) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
-    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
-    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
-    return mcmc_run_device(ctx, s.U.p, s.tc.p, triplets, N, L, T, mcparam, iters, seed, labeling);
-}
-
-int msm_mcmc_optimise_chains_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
-                                 double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings, double *energies,
-                                 int32_t *best) {
-    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains_gpu: null context");
+// what both msm_mcmc_optimise*_gpu do ahead of the sweeps: their checks, then both tables uploaded in pieces into the context's scratch.  skip_empty: a
+// call without sweeps or triplets ends after the host optimiser's checks (the single-chain call; the chains call still computes the energies).
+static int check_and_upload_tables(msm_ctx *ctx, const char *what, const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T,
+                                   double mcparam, int iters, const uint64_t *seeds, int K, const int32_t *labeling, bool skip_empty) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "%s: null context", what);
     if (!unary || !tcosts || !triplets || !labeling || N <= 0 || L <= 0 || T < 0 || iters < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: bad arguments");
     MSM_TRY(mcmc_check_chains(seeds, K));
     MSM_TRY(mcmc_check_arguments(triplets, N, L, T, mcparam, labeling));
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
-    if (N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", N, kMcmcMaxNodes);
+    if (skip_empty && (iters == 0 || T == 0)) return MSM_OK;
+    MSM_TRY(check_label_count("msm_mcmc_optimise_gpu", L));
+    MSM_TRY(mcmc_check_node_count("msm_mcmc_optimise_gpu", N));
     MSM_HIP(hipSetDevice(ctx->device));
     MSM_TRY(drop_ctx_pending(ctx));
     McmcScratch &s = mcmc_scratch(ctx);
@@ -480,7 +364,23 @@ int msm_mcmc_optimise_chains_gpu(msm_ctx *ctx, const double *unary, const double
     if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
     if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
     MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
-    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
+    return upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc);
+}
+
+extern "C" {
+
+int msm_mcmc_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, double mcparam,
+                          int32_t iters, uint64_t seed, int32_t *labeling) {
+    MSM_TRY(check_and_upload_tables(ctx, "msm_mcmc_optimise_gpu", unary, tcosts, triplets, N, L, T, mcparam, iters, &seed, 1, labeling, true));
+    McmcScratch &s = mcmc_scratch(ctx);  // (nothing was uploaded for a call without sweeps or triplets: mcmc_run_device returns at once)
+    return mcmc_run_device(ctx, s.U.p, s.tc.p, triplets, N, L, T, mcparam, iters, seed, labeling);
+}
+
+int msm_mcmc_optimise_chains_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                                 double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings, double *energies,
+                                 int32_t *best) {
+    MSM_TRY(check_and_upload_tables(ctx, "msm_mcmc_optimise_chains_gpu", unary, tcosts, triplets, N, L, T, mcparam, iters, seeds, K, labeling, false));
+    McmcScratch &s = mcmc_scratch(ctx);
     return mcmc_run_device_chains(ctx, s.U.p, s.tc.p, triplets, N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
 }
 
@@ -510,10 +410,8 @@ int msm_mcmc_optimise_chains(const double *unary, const double *tcosts, const in
 
 int msm_mcmc_energy(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const int32_t *labeling, double *energy) {
     if (!unary || !labeling || !energy || N <= 0 || L <= 0 || T < 0 || (T > 0 && (!tcosts || !triplets))) return fail(MSM_ERR_INVALID, "msm_mcmc_energy: bad arguments");
-    for (int i = 0; i < N; ++i)
-        if (labeling[i] < 0 || labeling[i] >= L) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: label of node %d out of range", i);
-    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
-        if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
+    MSM_TRY(check_labels(labeling, N, L));
+    MSM_TRY(check_triplets(triplets, N, T));
     std::vector<double> terms((size_t)N + T);
     mcmc_energy_terms(unary, tcosts, triplets, N, L, T, labeling, terms.data());
     *energy = mcmc_energy_of_terms(terms.data(), N, T);
@@ -541,8 +439,8 @@ int msm_mcmc_gpu_stats(msm_ctx *ctx, double stats[6]) {
 
 int msm_mcmc_proposals(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, int32_t chunk_sweeps, uint16_t *out) {
     if (!out || L <= 0 || T < 0 || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals: bad arguments");
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    MSM_TRY(check_mcparam("msm_mcmc_optimise", mcparam));
+    MSM_TRY(check_label_count("msm_mcmc_proposals", L));
     McmcProposals proposals(seed, mcparam, L);
     const int chunk = chunk_sweeps > 0 ? chunk_sweeps : std::max(sweeps, 1);
     for (int done = 0; done < sweeps; done += chunk) {
@@ -567,22 +465,22 @@ int msm_ctx_get_mcmc_draw(msm_ctx *ctx, int32_t *mode) {
 
 int msm_mcmc_draw_thresholds(int32_t L, double mcparam, uint64_t *thr) {
     if (!thr || L <= 0) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_thresholds: bad arguments");
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    MSM_TRY(check_mcparam("msm_mcmc_optimise", mcparam));
     mcmc_draw_thresholds(L, mcparam, thr);
     return MSM_OK;
 }
 
 int msm_mcmc_draw_block_bound(int64_t need, int32_t L, double mcparam, int64_t *blocks) {
     if (!blocks || L <= 0 || need < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_block_bound: bad arguments");
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
+    MSM_TRY(check_mcparam("msm_mcmc_optimise", mcparam));
     *blocks = mcmc_draw_block_bound((long)need, L, mcparam);
     return MSM_OK;
 }
 
 int msm_mcmc_proposals_mirror_counted(int32_t L, double mcparam, uint64_t seed, int32_t T, int32_t sweeps, uint16_t *out, uint64_t *candidates) {
     if (!out || L <= 0 || T < 0 || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals_mirror: bad arguments");
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_proposals_mirror: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    MSM_TRY(check_mcparam("msm_mcmc_optimise", mcparam));
+    MSM_TRY(check_label_count("msm_mcmc_proposals_mirror", L));
     McmcDrawMirror mirror(seed, mcparam, L);
     mirror.fill(out, (size_t)sweeps * T);
     if (candidates) *candidates = mirror.candidates;
@@ -598,8 +496,8 @@ int msm_mcmc_draw_gpu(msm_ctx *ctx, int32_t L, double mcparam, const uint64_t *s
     if (!ctx) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: null context");
     if (!out || L <= 0 || T < 0 || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: bad arguments");
     MSM_TRY(mcmc_check_chains(seeds, K));
-    if (!(mcparam > 0.0 && mcparam <= 1.0)) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: the geometric distribution parameter must be in (0, 1]");
-    if (L > 65535) return fail(MSM_ERR_INVALID, "msm_mcmc_draw_gpu: %d labels; the proposals travel as 16-bit values (at most 65535)", L);
+    MSM_TRY(check_mcparam("msm_mcmc_optimise", mcparam));
+    MSM_TRY(check_label_count("msm_mcmc_draw_gpu", L));
     if (pos) {  // a place per triplet, each taken once
         std::vector<char> seen((size_t)T, 0);
         for (int t = 0; t < T; ++t) {
@@ -642,8 +540,7 @@ int msm_mcmc_draw_stats(msm_ctx *ctx, double stats[4]) {
 
 int msm_mcmc_schedule(const int32_t *triplets, int32_t N, int32_t T, int32_t *level, int32_t *order, int32_t *level_off, int32_t *levels) {
     if (N <= 0 || T < 0 || (T > 0 && !triplets)) return fail(MSM_ERR_INVALID, "msm_mcmc_schedule: bad arguments");
-    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
-        if (triplets[i] < 0 || triplets[i] >= N) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise: triplet node out of range");
+    MSM_TRY(check_triplets(triplets, N, T));
     McmcSchedule s;
     mcmc_build_schedule(triplets, N, T, s);
     if (level) std::copy(s.level.begin(), s.level.end(), level);

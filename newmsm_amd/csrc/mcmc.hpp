@@ -21,10 +21,9 @@ struct McmcArgs {
     int N, L, T, levels, sweeps;
     int *status;
 };
-int launch_mcmc_sweeps(msm_ctx *ctx, const McmcArgs &a);
 
 // K chains side by side, workgroup k walks chain k: a.labeling holds K x N labels, a.prop the chunk of every chain, sweep s of chain k at
-// ((size_t)k * chunk_sweeps + s) * T; the schedule and both tables are shared.  (McmcArgs itself stays as k_mcmc_sweeps takes it.)
+// ((size_t)k * chunk_sweeps + s) * T; the schedule and both tables are shared.  A single chain is K = 1: there is no other sweeps kernel.
 constexpr int kMcmcMaxChains = 256;
 struct McmcChainArgs {
     McmcArgs a;
@@ -57,15 +56,19 @@ struct McmcDrawArgs {
 };
 int launch_mcmc_draw(msm_ctx *ctx, const McmcDrawArgs &d, hipStream_t stream);
 
-// `iters` sweeps on the device over tables that lie there (d_U: L x N, d_tc: T x L^3); labeling (host, N) is read and updated.  The arguments have been
-// checked by the caller (mcmc_check_arguments).  Complete on return.
+// `iters` sweeps of K chains from one start (chain k: seeds[k]) on the device over tables that lie there (d_U: L x N, d_tc: T x L^3).  labeling (host, N)
+// is the start and receives chain *best's labelling (best may be null); labelings (host, K x N) and energies (host, K) may be null.  The energies are
+// computed when K > 1 or they are asked for.  The arguments have been checked by the caller (mcmc_check_arguments; 1 <= K <= kMcmcMaxChains:
+// mcmc_check_chains).  Complete on return; labeling is written only when the call succeeds.  `what` names the call in what the kernels' status reports.
+int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters,
+                           const uint64_t *seeds, int K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best,
+                           const char *what = "msm_mcmc_optimise_chains_gpu");
+// A single chain: mcmc_run_device_chains with K = 1, reported as msm_mcmc_optimise_gpu.  Without sweeps or triplets it returns at once (the context's
+// stats stay the previous call's).
 int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
                     int32_t *labeling);
-// The same for K chains from one start (chain k: seeds[k]; chain 0 is mcmc_run_device with seeds[0]).  labelings (host, K x N) and energies (host, K) may
-// be null; labeling (host, N) is the start and receives chain *best's labelling (best may be null).  1 <= K <= kMcmcMaxChains, checked by the caller.
-int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters,
-                           const uint64_t *seeds, int K, int32_t *labeling, int32_t *labelings, double *energies, int32_t *best);
 int mcmc_check_chains(const uint64_t *seeds, int K);  // 1 <= K <= kMcmcMaxChains and seeds given, or MSM_ERR_INVALID
+int mcmc_check_node_count(const char *what, int N);   // N <= kMcmcMaxNodes, or MSM_ERR_CAPACITY reported under the name `what`
 // the sweeps of msm_mcmc_optimise over checked arguments (regtools.cpp)
 void mcmc_sweeps_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
                       int32_t *labeling);

@@ -63,31 +63,8 @@ __device__ __forceinline__ void mcmc_visit(const McmcArgs &a, uint16_t *s_lab, c
     if (best & 1) s_lab[C] = (uint16_t)label;
 }
 
-__global__ __launch_bounds__(kMcmcThreads) void k_mcmc_sweeps(McmcArgs a) {
-    extern __shared__ __align__(16) uint16_t s_lab[];  // N labels
-    const int tid = (int)threadIdx.x;
-    for (int i = tid; i < a.N; i += kMcmcThreads) {
-        int l = a.labeling[i];
-        if ((unsigned)l >= (unsigned)a.L) {
-            raise_status(a.status, MSM_ERR_INVALID);
-            l = 0;
-        }
-        s_lab[i] = (uint16_t)l;
-    }
-    __syncthreads();
-    for (int s = 0; s < a.sweeps; ++s) {
-        const uint16_t *__restrict__ prop = a.prop + (size_t)s * a.T;  // this sweep's proposals, in schedule order
-        for (int lv = 0; lv < a.levels; ++lv) {
-            const int begin = a.level_off[lv], end = a.level_off[lv + 1];
-            for (int i = begin + tid; i < end; i += kMcmcThreads) mcmc_visit(a, s_lab, a.sched[i], prop[i]);  // strides: a level wider than the workgroup
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < a.N; i += kMcmcThreads) a.labeling[i] = (int)s_lab[i];
-}
-
-// K chains: workgroup k is k_mcmc_sweeps on chain k's labelling and proposals, over the shared schedule and tables.  The workgroups never meet: no atomic
-// but the status word's on the error path, every loop bounded by the host's counts.
+// K chains (a single chain is K = 1): workgroup k walks the levels on chain k's labelling and proposals, over the shared schedule and tables, a level
+// wider than the workgroup in strides.  The workgroups never meet: no atomic but the status word's on the error path, every loop bounded by the host's counts.
 __global__ __launch_bounds__(kMcmcThreads) void k_mcmc_chains(McmcChainArgs c) {
     extern __shared__ __align__(16) uint16_t s_lab[];  // N labels of this chain
     const McmcArgs &a = c.a;
@@ -155,21 +132,11 @@ __global__ __launch_bounds__(256) void k_mcmc_chain_terms(McmcChainArgs c, doubl
 
 }  // namespace
 
-int launch_mcmc_sweeps(msm_ctx *ctx, const McmcArgs &a) {
-    if (a.sweeps <= 0 || a.T <= 0 || a.levels <= 0) return MSM_OK;
-    if (a.N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", a.N, kMcmcMaxNodes);
-    const size_t lds = (sizeof(uint16_t) * (size_t)a.N + 15) & ~(size_t)15;
-    if (lds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mcmc_sweeps), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_mcmc_sweeps, dim3(1), dim3(kMcmcThreads), lds, ctx->stream, a);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
-}
-
 int launch_mcmc_chains(msm_ctx *ctx, const McmcChainArgs &c) {
     const McmcArgs &a = c.a;
     if (a.sweeps <= 0 || a.T <= 0 || a.levels <= 0) return MSM_OK;
     if (c.chains < 1 || c.chains > kMcmcMaxChains || a.sweeps > c.chunk_sweeps) return fail(MSM_ERR_INVALID, "msm_mcmc_optimise_chains_gpu: bad launch (%d chains, %d sweeps of %d)", c.chains, a.sweeps, c.chunk_sweeps);
-    if (a.N > kMcmcMaxNodes) return fail(MSM_ERR_CAPACITY, "msm_mcmc_optimise_gpu: the labels of %d nodes do not fit the LDS of one workgroup (at most %d)", a.N, kMcmcMaxNodes);
+    MSM_TRY(mcmc_check_node_count("msm_mcmc_optimise_gpu", a.N));
     const size_t lds = (sizeof(uint16_t) * (size_t)a.N + 15) & ~(size_t)15;
     if (lds > 64 * 1024) MSM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mcmc_chains), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_mcmc_chains, dim3((unsigned)c.chains), dim3(kMcmcThreads), lds, ctx->stream, c);

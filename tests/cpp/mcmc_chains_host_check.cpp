@@ -101,6 +101,14 @@ void check_chunk_length() {
     EXPECT(mcmc_chunk_sweeps(3, 320, 50, 17) == 3 && mcmc_chunk_sweeps(1, 320, 50, 17) == 1);  // the environment's value is per chain
     EXPECT(mcmc_chunk_sweeps(0, 20, 50, 5) == 50 && mcmc_chunk_sweeps(1000, 20, 50, 5) == 50);  // never more than the run
     EXPECT(mcmc_chunk_sweeps(0, 0, 5, 2) == 5);
+    // one chain: the rule the single-chain sweeps had before they became the chains' with K = 1 (the 2^23 bound never binds below 2^19 per chain)
+    for (long asked : {-5L, 0L, 1L, 3L, 102L, 1000000000L, 1L << 40})
+        for (int T : {0, 1, 20, 320, 5120, 240000})
+            for (int iters : {1, 50, 2000, 100000}) {
+                const long per = std::max(T, 1);
+                const long want = std::max(1L, std::min(std::min(asked > 0 ? asked : (1L << 19) / per, (1L << 30) / per), (long)iters));
+                EXPECT(mcmc_chunk_sweeps(asked, T, iters, 1) == (int)want);
+            }
 }
 
 }  // namespace

@@ -61,6 +61,28 @@ def test_random_tables_on_icosphere_faces(ctx, monkeypatch, order, chunk):
     assert stats["levels_per_sweep"] == {0: 10, 2: 28}[order] and stats["levels"] == 50 * stats["levels_per_sweep"]
 
 
+def test_a_single_chain_reports_as_one_chain_either_draw(ctx, monkeypatch):
+    """T = 320, 19 labels, 50 sweeps in chunks of three: the single-chain call is the chains' path with K = 1 and reports what it always did, with the
+    proposals drawn on the host and on the device; a following call without sweeps returns at once and leaves the stats"""
+    monkeypatch.setenv(CHUNK, "3")
+    U, tc, triplets, start, want, kw = _random_case(2, 19, 50)
+    assert np.array_equal(api.mcmc_optimise_gpu(ctx, U, tc, triplets, start, **kw), want)
+    stats = api.mcmc_gpu_stats(ctx)
+    assert api.mcmc_chains_info(ctx) == (1, 1)
+    assert stats["chunks"] == 17 and stats["levels_per_sweep"] == 28 and stats["levels"] == 1400 and stats["draw_ms"] > 0
+    ctx.set_mcmc_draw(1)
+    try:
+        assert np.array_equal(api.mcmc_optimise_gpu(ctx, U, tc, triplets, start, **kw), want)
+        stats = api.mcmc_gpu_stats(ctx)
+        assert api.mcmc_chains_info(ctx) == (1, 0)
+        assert stats["chunks"] == 17 and stats["levels_per_sweep"] == 28 and stats["levels"] == 1400 and stats["draw_ms"] == 0
+        assert api.mcmc_draw_stats(ctx)["accepted"] == 50 * 320
+        assert np.array_equal(api.mcmc_optimise_gpu(ctx, U, tc, triplets, start, **dict(kw, iters=0)), start)
+        assert api.mcmc_gpu_stats(ctx) == stats and api.mcmc_chains_info(ctx) == (1, 0)
+    finally:
+        ctx.set_mcmc_draw(0)
+
+
 def test_ico4_faces(ctx, monkeypatch):
     """T = 5120: the widest level holds 320 triplets"""
     monkeypatch.setenv(CHUNK, "3")

@@ -4,6 +4,7 @@ control grid.  In one process, alternating: the host path (msm_cost_unary_table 
 msm_cost_mcmc_optimise (both tables stay on the device).  A time is reported only when the two labellings are equal.  Per grid, medians of the repeats with
 min and max: ms per sweep either way, us per level by the HIP events around the sweep kernels, the proposal stream's draws per second on the host alone,
 the time the host path spends computing and fetching the triplet table, and the time the device path spends on its two tables.  Prints one JSON object.
+With --draw gpu the single-chain call is timed once more per repeat with its proposals drawn on the device (msm_ctx_set_mcmc_draw): gpu_device_draw.
 
 tools/time_mcmc.py --chains 1,4,16,64 --baseline-lib PARENT/newmsm_amd/libmsmhip.so [--sweeps N] [--repeats R] [--out FILE] -- several chains in one launch
 (msm_cost_mcmc_optimise_chains, DESIGN.md 5.16 "Chains") against K successive msm_cost_mcmc_optimise calls of another build: the library of a checkout of
@@ -17,7 +18,8 @@ call with the proposals drawn on the host and on the device (msm_ctx_set_mcmc_dr
 the baseline build (the parent commit's), both libraries in this one process, alternated after two warm-up rounds.  Per grid, K and mode, medians of the
 repeats with min and max: ms of the call, ms in the sweeps kernels, the draw's ms (host: wall clock of the threaded draw; gpu: the draw kernels by their
 events) and, for gpu, accepted proposals per second of draw-kernel time.  A mode's times are reported only when every labelling equals the baseline's.
-"apart": the mode's slowest repeat lies below the baseline call's fastest."""
+"apart": the mode's slowest repeat lies below the baseline call's fastest.  Without --baseline-lib no other build is loaded (MSM_LIB_PATH then selects the
+one that is timed): a mode's labellings are compared with those of the first mode."""
 import argparse
 import json
 import os
@@ -38,7 +40,7 @@ def spread(values):
     return dict(median=v[len(v) // 2], min=v[0], max=v[-1])
 
 
-def measure(ctx, cp_order, sweeps, repeats, mcparam, seed):
+def measure(ctx, cp_order, sweeps, repeats, mcparam, seed, device_draw=False):
     inp = problem.pairwise_inputs(6, cp_order, D=1)
     cf, keep = problem.build_cost(ctx, inp, kind="univariate")
     cf.get_source_data()
@@ -57,19 +59,27 @@ def measure(ctx, cp_order, sweeps, repeats, mcparam, seed):
         t3 = time.perf_counter()
         return lab, dict(unary_ms=(t1 - t0) * 1e3, triplet_fetch_ms=(t2 - t1) * 1e3, sweeps_ms=(t3 - t2) * 1e3, total_ms=(t3 - t0) * 1e3)
 
-    def device(iters):
+    def device(iters, draw="host"):
+        ctx.set_mcmc_draw(draw)
         ctx.synchronize()
         t0 = time.perf_counter()
         lab = cf.mcmc_optimise(start, iters=iters, **kw)
         t1 = time.perf_counter()
+        ctx.set_mcmc_draw("host")
         return lab, dict(total_ms=(t1 - t0) * 1e3, **api.mcmc_gpu_stats(ctx))
 
     for _ in range(2):  # warm-up of every shape the timed window uses: code objects, staging blocks, the pinned table buffer
         host(20), device(20)
-    runs_h, runs_d, tables_ms, equal = [], [], [], True
+        if device_draw:
+            device(20, "gpu")
+    runs_h, runs_d, runs_g, tables_ms, equal, equal_g = [], [], [], [], True, True
     for _ in range(repeats):
         lab_h, h = host(sweeps)
         lab_d, d = device(sweeps)
+        if device_draw:
+            lab_g, g = device(sweeps, "gpu")
+            equal_g = equal_g and np.array_equal(lab_h, lab_g)
+            runs_g.append(g)
         ctx.synchronize()
         t0 = time.perf_counter()
         cf.mcmc_optimise(start, iters=0, **kw)  # the two tables alone: no sweep is run
@@ -100,6 +110,10 @@ def measure(ctx, cp_order, sweeps, repeats, mcparam, seed):
         gpu_total_ms=spread([r["total_ms"] for r in runs_d]),
         proposal_draws_per_s=spread(draws),
     )
+    if device_draw:
+        out["gpu_device_draw"] = dict(labellings_equal=bool(equal_g))
+        if equal_g:
+            out["gpu_device_draw"].update(total_ms=spread([r["total_ms"] for r in runs_g]), kernel_ms=spread([r["kernel_ms"] for r in runs_g]))
     # "faster" only where the slower path's fastest run is above the faster path's slowest
     out["gpu_faster_total"] = out["gpu_total_ms"]["max"] < out["host_total_ms"]["min"]
     out["gpu_faster_sweeps"] = out["gpu_ms_per_sweep"]["max"] < out["host_ms_per_sweep"]["min"]
@@ -189,7 +203,7 @@ def measure_draw(ctx, base, base_ctx, cp_order, chains, modes, sweeps, repeats, 
         return cf, keep
 
     cf, keep = build(M, ctx)
-    cfb, keepb = build(base, base_ctx)
+    cfb, keepb = build(base, base_ctx) if base else (None, None)
     start = np.zeros(cf.N, dtype=np.int32)
     out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, sweeps=sweeps, repeats=repeats, mcparam=mcparam, per_K=[])
 
@@ -216,31 +230,38 @@ def measure_draw(ctx, base, base_ctx, cp_order, chains, modes, sweeps, repeats, 
         for _ in range(2):  # warm-up of both builds at this K and in every mode: code objects, staging blocks, both proposal buffers
             for mode in modes:
                 ours(mode, seeds, 20)
-            theirs(seeds, 20)
+            if base:
+                theirs(seeds, 20)
         runs, base_ms, equal = {m: [] for m in modes}, [], {m: True for m in modes}
         for _ in range(repeats):
             got = {}
             for mode in modes:
                 got[mode], r = ours(mode, seeds, sweeps)
                 runs[mode].append(r)
-            want, ms = theirs(seeds, sweeps)
-            base_ms.append(ms)
+            want, ms = theirs(seeds, sweeps) if base else (got[modes[0]], None)
+            if base:
+                base_ms.append(ms)
             for mode in modes:
                 equal[mode] = equal[mode] and np.array_equal(got[mode][1], want[1]) and np.array_equal(got[mode][0], want[0]) and got[mode][3] == want[3]
-        row = dict(K=K, baseline_ms=spread(base_ms), levels_per_sweep=runs[modes[0]][0]["levels_per_sweep"], chunks=runs[modes[0]][0]["chunks"])
+        row = dict(K=K, levels_per_sweep=runs[modes[0]][0]["levels_per_sweep"], chunks=runs[modes[0]][0]["chunks"])
+        if base:
+            row["baseline_ms"] = spread(base_ms)
         for mode in modes:
             rs = runs[mode]
             m = dict(labellings_equal=bool(equal[mode]), draw_threads=rs[0]["draw_threads"])
             if equal[mode]:  # no time is reported for a result that is not the baseline's
                 m.update(total_ms=spread([r["total_ms"] for r in rs]), kernel_ms=spread([r["kernel_ms"] for r in rs]), draw_ms=spread([r["draw_ms"] for r in rs]))
-                m["apart"] = bool(m["total_ms"]["max"] < row["baseline_ms"]["min"])
+                if base:
+                    m["apart"] = bool(m["total_ms"]["max"] < row["baseline_ms"]["min"])
                 if mode == "gpu":
                     m["proposals_per_s"] = spread([r["accepted"] / (r["draw_ms"] * 1e-3) for r in rs])
                     m["candidates_per_proposal"] = rs[0]["candidates"] / rs[0]["accepted"]
                     m["block_bound"] = rs[0]["block_bound"]
             row[mode] = m
         out["per_K"].append(row)
-    cf.close(), cfb.close()
+    cf.close()
+    if base:
+        cfb.close()
     return out
 
 
@@ -248,20 +269,22 @@ def main_chains(a):
     chains = [int(k) for k in a.chains.split(",")]
     if not chains or min(chains) < 1 or max(chains) > 256:
         raise SystemExit("time_mcmc.py: --chains takes numbers from 1 to 256")
-    if not a.baseline_lib:
-        raise SystemExit("time_mcmc.py: --chains needs --baseline-lib (the build the K successive calls run on)")
     modes = a.draw.split(",") if a.draw else []
     if any(m not in ("host", "gpu") for m in modes):
         raise SystemExit("time_mcmc.py: --draw takes host, gpu or both")
-    base = load_baseline(a.baseline_lib)
-    ctx, base_ctx = M.Context(0), base.Context(0)
+    if not a.baseline_lib and not modes:
+        raise SystemExit("time_mcmc.py: --chains needs --baseline-lib (the build the K successive calls run on)")
+    base = load_baseline(a.baseline_lib) if a.baseline_lib else None
+    ctx, base_ctx = M.Context(0), base.Context(0) if base else None
     if modes:
         result = dict(tool="tools/time_mcmc.py --chains --draw", host_threads=os.environ.get("MSMHIP_HOST_THREADS"),
                       grids=[measure_draw(ctx, base, base_ctx, cp, chains, modes, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
     else:
         result = dict(tool="tools/time_mcmc.py --chains", host_threads=os.environ.get("MSMHIP_HOST_THREADS"),
                       grids=[measure_chains(ctx, base, base_ctx, cp, chains, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
-    ctx.close(), base_ctx.close()
+    ctx.close()
+    if base:
+        base_ctx.close()
     return result
 
 
@@ -269,7 +292,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chains", default=None, help="e.g. 1,4,16,64: time the chains call against K successive calls of --baseline-lib")
     ap.add_argument("--baseline-lib", default=None, help="newmsm_amd/libmsmhip.so of a checkout of the commit to compare with")
-    ap.add_argument("--draw", default=None, help="host,gpu (with --chains): time the chains call per proposal-draw mode against the chains call of --baseline-lib")
+    ap.add_argument("--draw", default=None, help="host,gpu (with --chains): time the chains call per proposal-draw mode against the chains call of --baseline-lib; "
+                    "gpu (without --chains): time the single-chain call with the draw on the device as well")
     ap.add_argument("--sweeps", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--mcparam", type=float, default=0.8)
@@ -281,7 +305,9 @@ def main():
         result = main_chains(a)
     else:
         ctx = M.Context(0)
-        result = dict(tool="tools/time_mcmc.py", grids=[measure(ctx, cp, a.sweeps, a.repeats, a.mcparam, 3) for cp in (4, 3)])
+        if a.draw not in (None, "gpu"):
+            raise SystemExit("time_mcmc.py: without --chains, --draw takes gpu")
+        result = dict(tool="tools/time_mcmc.py", grids=[measure(ctx, cp, a.sweeps, a.repeats, a.mcparam, 3, device_draw=a.draw == "gpu") for cp in (4, 3)])
         ctx.close()
     text = json.dumps(result, indent=1, default=lambda o: o.item())  # (numpy scalars)
     if a.out:
