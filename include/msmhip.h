@@ -122,6 +122,14 @@ int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_t V, int32_
  * (4 x [5] are needed) that receive the cell array as stored. */
 int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
                        int64_t cells_cap);
+/* testing hook, host only: the certificates of the direction table's cells (one bit per sub-cell: the hinted first candidate is the answer for every
+ * direction of the sub-cell, and a kernel takes it without its acceptance test), at nsamples random directions and some 10 000 placed ones: next to
+ * sub-cell and cell borders and corners, cube-face edges and corners, through mesh vertices, and next to edge midpoints.  report: [0] points [1] points in a
+ * certified sub-cell [2] of those, points whose first candidate fails the FP64 edge-plane test at the threshold the table's proof asks for (must be 0)
+ * [3] of those, points for which the first pass of Octree::get_closest_triangle does not return it (must be 0) [4] sub-cells [5] certified sub-cells
+ * [6] cells [7] placed points.  cells: as msm_ray_hint_check.  MSMHIP_RAY_CERTS=off (read when a table is built) writes no certificates. */
+int msm_ray_cert_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
+                       int64_t cells_cap);
 
 /* ------------------------------------------------------------------------------------------------
  * context: one per GPU

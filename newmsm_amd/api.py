@@ -156,6 +156,21 @@ def ray_hint_check(xyz, tri, nsamples=20000, seed=1, return_cells=False):
     return out
 
 
+def ray_cert_check(xyz, tri, nsamples=20000, seed=1, return_cells=False):
+    """[host] the certificates of the direction table's cells: every sampled point of a certified sub-cell must have the sub-cell's first candidate for its
+    triangle, by the FP64 edge-plane test and by the reference's leaf search (testing hook, msm_ray_cert_check).  The points are `nsamples` random directions
+    and some 10 000 placed ones (borders and corners of sub-cells, cells and cube faces; mesh vertices; edge midpoints).  return_cells: as ray_hint_check."""
+    x, px = _soa(xyz)
+    t, pt = _tri_soa(tri)
+    rep = (C.c_int64 * 8)()
+    cells = np.zeros((6 * 512 * 512, 4), dtype=np.int32) if return_cells else None  # (the largest table build_ray_table makes)
+    check(lib().msm_ray_cert_check(px, pt, x.shape[1], t.shape[1], nsamples, seed, rep, cells.ctypes.data_as(c_ip) if return_cells else None, cells.size if return_cells else 0))
+    out = dict(points=rep[0], certified_points=rep[1], fp64_failures=rep[2], reference_disagrees=rep[3], subcells=rep[4], certified_subcells=rep[5], cells=rep[6], placed=rep[7])
+    if return_cells:
+        out["cell_array"] = cells[: rep[6]].copy()
+    return out
+
+
 def estimate_triplets(tri):
     t, pt = _tri_soa(tri)
     out = np.zeros((t.shape[1], 3), dtype=np.int32)

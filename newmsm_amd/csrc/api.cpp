@@ -240,10 +240,11 @@ static uint64_t content_hash(const msm_mesh *m) {
 }
 
 static std::shared_ptr<const RayCacheEntry> ray_cache_find(const msm_mesh *m, uint64_t h) {
+    const bool certs = ray_certs_enabled();  // a table built under the other setting of MSMHIP_RAY_CERTS has other cells: not this mesh's table
     std::lock_guard<std::mutex> lock(g_ray_cache_mu);
     for (auto it = g_ray_cache.begin(); it != g_ray_cache.end(); ++it) {
         const RayCacheEntry &e = **it;
-        if (e.hash == h && e.V == m->V && e.T == m->T && e.xyz == m->xyz && e.tri == m->tri) {
+        if (e.hash == h && e.V == m->V && e.T == m->T && e.rays.certs == certs && e.xyz == m->xyz && e.tri == m->tri) {
             g_ray_cache.splice(g_ray_cache.begin(), g_ray_cache, it);
             return g_ray_cache.front();
         }

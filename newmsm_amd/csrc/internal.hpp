@@ -67,8 +67,8 @@ constexpr int kRayPieces = 9;
 // First-candidate hints of a direction cell.  A cell is cut into kRayHintK x kRayHintK sub-cells, and two bits per sub-cell
 // say which of the candidates stored in the cell itself (x, y, z, and w when it is an id) to try first: the one whose
 // gnomonic triangle holds the sub-cell's centre, 0 = the stored order.  They ride in the top 6 bits of x, y, z -- word
-// su (x, y, z for su = 0, 1, 2), bits 26 + 2 sv -- above a 26-bit two's-complement id (-1 = none; w keeps all 32 bits
-// for an id, -1 or the ray_more reference).  The order of trial cannot change a result: at most one listed candidate
+// su (x, y, z for su = 0, 1, 2), bits 26 + 2 sv -- above a 26-bit two's-complement id (-1 = none; w holds an id, -1 or the
+// ray_more reference in its low 23 bits, see the certificates below). The order of trial cannot change a result: at most one listed candidate
 // passes the acceptance test (octree.cpp).  kRayHintK = 1: no hints are written and none are read.
 #ifndef MSM_RAY_HINT_K
 #define MSM_RAY_HINT_K 3
@@ -76,7 +76,17 @@ constexpr int kRayPieces = 9;
 constexpr int kRayHintK = MSM_RAY_HINT_K;
 static_assert(kRayHintK >= 1 && kRayHintK <= 3, "two bits per sub-cell, three sub-cells per word, three words");
 constexpr int kRayIdBits = 26;
-constexpr int kRayMaxTris = 1 << (kRayIdBits - 1);  // a mesh with more triangles gets no table (build_ray_table)
+// Certificates.  The fourth word gives its top nine bits to one bit per sub-cell, bit kRayWBits + 3 su + sv: "the candidate this
+// sub-cell's hint names passes the acceptance test for every direction of the sub-cell, and needs no vouching" (octree.cpp:
+// build_ray_table has the proof), so a kernel may take that candidate without loading its edge planes.  Below them w keeps what it held
+// as a 23-bit two's-complement field: an id, -1, or the ray_more reference -2 - index.  So an id has 22 bits (the unary path's own
+// kTriBits): a mesh with more than kRayMaxTris = 2^22 triangles gets no table, and a table whose ray_more list would pass
+// kRayMaxMore = 2^22 - 2 entries (its references would leave the field) gets none either -- with four candidates listed per entry
+// no mesh below the first limit comes near the second.  MSMHIP_RAY_CERTS=off writes all nine bits as zero.
+constexpr int kRayWBits = 23;
+static_assert(kRayWBits + 9 == 32 && kRayWBits <= kRayIdBits, "nine certificate bits above the fourth word's field");
+constexpr int kRayMaxTris = 1 << (kRayWBits - 1);  // a mesh with more triangles gets no table (build_ray_table)
+constexpr int kRayMaxMore = (1 << (kRayWBits - 1)) - 2;
 
 // Direction (ray) table of a simple surface (octree.cpp: build_ray_table), the host side; G == 0 when absent.
 struct RayTable {
@@ -89,6 +99,7 @@ struct RayTable {
     std::vector<int4> more;      // candidates 4..7 of the cells that have more than four
     std::vector<int4> excl;      // up to seven leaf boxes a query must not lie in for its triangle to be vouched for: {b0, b1, b2, count} and, for count > 3, {b3 .. b6} in the next record
     double r2lo = 0, r2hi = 0;   // squared radius range of the query points the table is valid for
+    bool certs = true;           // built with certificates in the cells (MSMHIP_RAY_CERTS); false: all nine bits of every cell are zero
 };
 
 struct FlatOctree {
@@ -118,6 +129,8 @@ struct FlatOctree {
 void build_octree(const double *xyz /*3 x V SoA*/, const int32_t *tri /*3 x T SoA*/, int V, int T, FlatOctree &out);
 // decides RayTable::simple and, for a simple surface, fills the ray table (tree.rays) of an already built tree
 void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOctree &tree);
+// MSMHIP_RAY_CERTS is not "off": build_ray_table writes certificates (read per call; the content cache of tables keys on it, api.cpp)
+bool ray_certs_enabled();
 
 // device view of a mesh's search structure
 struct DevTree {

@@ -369,7 +369,7 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
     out.rays.simple = simple_star_surface(xyz, tri, V, T);
     const char *no_table = std::getenv("MSMHIP_DISABLE_RAYTABLE");  // testing: force the complete search everywhere
     if (!out.rays.simple || (no_table && no_table[0] == '1')) return;
-    if (kRayHintK > 1 && T > kRayMaxTris) return;  // ids beyond the cell's id field: no table, the complete search everywhere
+    if (T > kRayMaxTris) return;  // ids beyond the id field of the cell's fourth word: no table, the complete search everywhere
     TICK("simple");
     const std::vector<double> margin = safe_margins(xyz, tri, V, T);
     TICK("margins");
@@ -561,6 +561,11 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
             out.rays.more.push_back(more);
         }
     }
+    if (out.rays.more.size() > (size_t)kRayMaxMore) {  // references beyond the fourth word's field (internal.hpp): no table
+        out.rays = RayTable();
+        out.rays.simple = true;
+        return;
+    }
     TICK("cells");
     // first-candidate hints (internal.hpp: kRayHintK): per sub-cell, the first of the candidates stored in the cell itself whose
     // image on the face holds the sub-cell's centre; none: 0, the ranked order.  Cell by cell, from the cell's own content only.
@@ -607,6 +612,112 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
         });
         TICK("hints");
     }
+    // Certificates (internal.hpp: kRayWBits): one bit per sub-cell in the top nine bits of w, set when the candidate t that the sub-cell's hint
+    // names -- the one ray_cell_of hands out first; stored in the cell itself, usable, without an exclusion record (e1.w negative), threshold
+    // tau = e0.w >= 0 -- satisfies n_k . d^ >= tau, k = 0, 1, 2, in FP64 for the direction through each of the four corners of the sub-cell GROWN
+    // by kRayCertGuard on every side (face units; n_k as ray_accepts_fp64 forms them, and the very expression it evaluates).  Why four corners
+    // suffice: {d : n . d >= tau |d|} with tau >= 0 is a convex cone (n . d is linear, tau |d| convex), so is the intersection of the three, and
+    // every direction of the grown sub-cell is a non-negative combination of its four corner rays (the sub-cell is a rectangle in the face's
+    // plane, the convex hull of its corners).  What a certificate is worth: tau already holds margin / rho (1 + 1e-6) plus the float test's
+    // allowance of 3e-6, so a certified direction lies at least as far inside the triangle as one the float test accepts (that test guarantees
+    // tau minus the allowance; the FP64 evaluation here errs by 1e-15), (2) of the table's guarantee holds for it, and (1) holds everywhere in the
+    // shell because t has no exclusion record.  At most one listed candidate passes the acceptance test, so a kernel that takes t unseen takes
+    // what its loop over the candidates would have ended with.
+    // The guard band.  A kernel places a point by ray_cell_at's float arithmetic.  u / w reaches gu through six roundings of 2^-24 (three
+    // conversions or products per component -- rsqrt's own error scales all components alike and cancels -- the reciprocal, the product),
+    // 3.6e-7 of |u / w| <= 1; adding 1 rounds by up to 1.2e-7; the product with G / 2 is exact.  So a point's true (u, v) is within 4.8e-7 face
+    // units of the one that chose its cell and, gu - iu being exact and its product with kRayHintK good to 2^-24, its sub-cell: for any G.  A
+    // direction that float rounding gives to the neighbouring cube face has |u| <= 1 + 4.8e-7 there and is clamped into a rim sub-cell, whose
+    // grown rectangle reaches beyond |u| = 1 by the guard (the direction through such a corner is as good as any other).  kRayCertGuard = 4e-6
+    // is eight times the bound: 1e-3 of a cell at G = 512, 5e-4 at the G = 256 of an ico6 sphere, a fraction of a per cent of the certificates.
+    // Cell by cell, from the cell's own content only, as the hints: the same words whatever the number of workers.
+    {
+        const bool certs = ray_certs_enabled();
+        out.rays.certs = certs;
+        constexpr double kRayCertGuard = 4e-6;
+        constexpr int K = kRayHintK;
+        // the planes of every triangle that can be certified, once, as ray_accepts_fp64 forms them: n = a x b turned towards the third vertex, and |n|;
+        // thr < 0: not to be certified (unusable, an exclusion record, a negative threshold)
+        struct Planes {
+            V3 n[3];
+            double nn[3], thr;
+        };
+        std::vector<Planes> planes(certs ? (size_t)T : 0);
+        parallel_chunks(certs ? T : 0, workers, [&](int, int t_begin, int t_end) {
+            for (int t = t_begin; t < t_end; ++t) {
+                Planes &q = planes[t];
+                const float4 e0 = out.rays.edge[3 * (size_t)t], e1 = out.rays.edge[3 * (size_t)t + 1];
+                q.thr = (usable[t] && e0.w < 2.f && e0.w >= 0.f && __builtin_bit_cast(int32_t, e1.w) < 0) ? (double)e0.w : -1.0;
+                if (q.thr < 0.0) continue;
+                const V3 v[3] = {vtx(xyz, V, tri[t]), vtx(xyz, V, tri[T + t]), vtx(xyz, V, tri[2 * (size_t)T + t])};
+                for (int k = 0; k < 3; ++k) {
+                    V3 n = cross(v[(k + 1) % 3], v[(k + 2) % 3]);
+                    if (dot(n, v[k]) < 0.0) n = scale(n, -1.0);
+                    q.n[k] = n, q.nn[k] = norm(n);
+                }
+            }
+        });
+        parallel_chunks((int)ncell, workers, [&](int, int c_begin, int c_end) {
+            for (int c = c_begin; c < c_end; ++c) {
+                int4 &cell = out.rays.cell[c];
+                uint32_t bits = 0u;
+                if (certs && ray_cell_ids(cell).x >= 0) {
+                    const int f = c / (G * G), iu = (c / G) % G, iv = c % G;
+                    const int a = f >> 1, bb = (a + 1) % 3, cc = (a + 2) % 3;
+                    // directions through the 2K x 2K grown corner positions, and their lengths (the test is homogeneous in d): index 2 s + (upper side)
+                    double du[2 * K], dvv[2 * K];
+                    for (int s = 0; s < K; ++s) {
+                        du[2 * s] = -1 + 2.0 * (iu + (double)s / K) / G - kRayCertGuard, du[2 * s + 1] = -1 + 2.0 * (iu + (double)(s + 1) / K) / G + kRayCertGuard;
+                        dvv[2 * s] = -1 + 2.0 * (iv + (double)s / K) / G - kRayCertGuard, dvv[2 * s + 1] = -1 + 2.0 * (iv + (double)(s + 1) / K) / G + kRayCertGuard;
+                    }
+                    V3 dir[2 * K][2 * K];
+                    double len[2 * K][2 * K];
+                    uint64_t have = 0;  // (set up when first asked for)
+                    auto corner = [&](int i, int j) {
+                        if (!((have >> (2 * K * i + j)) & 1ull)) {
+                            double comp[3];
+                            comp[a] = (f & 1) ? -1.0 : 1.0, comp[bb] = du[i], comp[cc] = dvv[j];
+                            dir[i][j] = mk(comp[0], comp[1], comp[2]);
+                            len[i][j] = norm(dir[i][j]);
+                            have |= 1ull << (2 * K * i + j);
+                        }
+                    };
+                    auto inside = [&](const Planes &q, int i, int j) {
+                        corner(i, j);
+                        const V3 &d = dir[i][j];
+                        bool ok = true;
+                        for (int k = 0; k < 3; ++k) ok = ok && dot(q.n[k], d) >= q.thr * q.nn[k] * len[i][j];
+                        return ok;
+                    };
+                    // one candidate hinted in every sub-cell, and the whole grown cell inside its cone: every grown sub-cell lies in the grown cell
+                    const int t0 = ray_cell_first(cell, ray_cell_hint(cell, 0, 0)).x;
+                    bool one = t0 >= 0 && planes[t0].thr >= 0.0;
+                    for (int su = 0; su < K && one; ++su)
+                        for (int sv = 0; sv < K && one; ++sv) one = ray_cell_first(cell, ray_cell_hint(cell, su, sv)).x == t0;
+                    if (one && inside(planes[t0], 0, 0) && inside(planes[t0], 2 * K - 1, 0) && inside(planes[t0], 0, 2 * K - 1) && inside(planes[t0], 2 * K - 1, 2 * K - 1)) {
+                        for (int su = 0; su < K; ++su)
+                            for (int sv = 0; sv < K; ++sv) bits |= 1u << (kRayWBits + 3 * su + sv);
+                    } else {
+                        for (int su = 0; su < K; ++su)
+                            for (int sv = 0; sv < K; ++sv) {
+                                const int t = ray_cell_first(cell, ray_cell_hint(cell, su, sv)).x;
+                                if (t < 0) continue;  // (the ray_more reference: the hinted candidate is not in the cell itself)
+                                const Planes &q = planes[t];
+                                if (q.thr >= 0.0 && inside(q, 2 * su, 2 * sv) && inside(q, 2 * su + 1, 2 * sv) && inside(q, 2 * su, 2 * sv + 1) && inside(q, 2 * su + 1, 2 * sv + 1))
+                                    bits |= 1u << (kRayWBits + 3 * su + sv);
+                            }
+                    }
+                }
+                cell.w = (int32_t)(((uint32_t)cell.w & ((1u << kRayWBits) - 1u)) | bits);
+            }
+        });
+        TICK("certs");
+    }
+}
+
+bool ray_certs_enabled() {
+    const char *e = std::getenv("MSMHIP_RAY_CERTS");
+    return !(e && std::strcmp(e, "off") == 0);
 }
 
 namespace {
@@ -820,7 +931,8 @@ extern "C" int msm_octree_signature(const double *xyz, const int32_t *tri, int32
 // random edges and vertices, on either side -- every candidate of the point's cell that a kernel may accept (the float test, or the FP64
 // re-test of a nearly accepted candidate, plus ray_vouches: the very functions the kernels call, search_device.hpp) must be THE answer of
 // Octree::get_closest_triangle's first pass (R/octree.cpp:156-178): listed in the leaf the point descends to, and the only listed triangle
-// that passes the -1e-8 inside test.  report: [0] points, [1] accepted by the float test, [2] accepted only by the FP64 re-test, [3] left to
+// that passes the -1e-8 inside test.  The first candidate of a certified sub-cell (internal.hpp: kRayWBits) is taken as the kernels take it, without
+// a test, and counts in [1]; what ray_find returns for the point is held to the same standard.  report: [0] points, [1] accepted by the float test, [2] accepted only by the FP64 re-test, [3] left to
 // the complete search, [4] VIOLATIONS (must be 0), [5] triangles the table cannot use, [6] triangles with exclusion boxes, [7] simple surface,
 // [8] exclusion boxes checked one by one (a point at the centre of the leaf a box stands for must be refused for that triangle, a violation otherwise),
 // [9] sampled points whose triangle passed the edge-plane test and was refused by ray_vouches alone.
@@ -918,12 +1030,19 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
         }
         // what a kernel may accept
         float fx, fy, fz;
-        const int4 cell = ray_cell_of(dt, p, fx, fy, fz);
+        bool cert;
+        const int4 cell = ray_cell_of(dt, p, fx, fy, fz, cert);
         int4 more = make_int4(cell.w, -1, -1, -1);
         if (cell.x >= 0 && cell.w < -1) more = o.rays.more[-2 - cell.w];
         const int cand[7] = {cell.x, cell.y, cell.z, more.x, more.y, more.z, more.w};
         const double pn = norm(p);
         bool by_float = false, by_fp64 = false, bad = false;
+        if (cert) {  // a certified sub-cell: the kernels take the first candidate without a test (counted with the float test's)
+            by_float = true;
+            if (!(hits.size() == 1 && hits[0] == cell.x)) bad = true;
+        }
+        const int found = ray_find_in(dt, o.rays.edge.data(), 3, p);  // the search of the kernels that take one point at a time, shortcut included
+        if (found >= 0 && !(hits.size() == 1 && hits[0] == found)) bad = true;
         for (int k = 0; k < 7 && cell.x >= 0; ++k) {
             const int t = cand[k];
             if (t < 0) break;
@@ -1035,5 +1154,121 @@ extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t
                 break;
             }
     }
+    return MSM_OK;
+}
+
+// Testing hook, host only: the certificates of the direction cells (internal.hpp: kRayWBits; build_ray_table has the proof), point by point.  A point in a
+// certified sub-cell -- placed by ray_cell_at, as a kernel places it -- is taken by the kernels for its first candidate unseen, so that candidate must pass the FP64
+// edge-plane test at the threshold the table's proof asks for (ray_accepts_fp64 at the stored threshold less the float allowance, as the kernels' FP64 re-test
+// runs it) and must be THE answer of the reference's first pass (msm_ray_table_check: the only listed triangle of the point's leaf that passes the inside test).
+// Points: `nsamples` random directions, then placed ones -- within 1e-6 of a cell of sub-cell borders and of cell borders (one coordinate, and both: the corners),
+// of cube-face edges and corners (on either side: beyond |u| = 1 the point belongs to the neighbouring face, and float rounding decides which), through mesh
+// vertices, and through edge midpoints displaced by 1e-9 of the way to the third vertex, either way.
+// report: [0] points, [1] points in a certified sub-cell, [2] OF THOSE, POINTS WHOSE FIRST CANDIDATE FAILS THE FP64 TEST, [3] OF THOSE, POINTS FOR WHICH THE REFERENCE'S
+// FIRST PASS DOES NOT RETURN IT (both must be 0), [4] sub-cells, [5] certified sub-cells, [6] cells, [7] placed points.  cells: as msm_ray_hint_check.
+extern "C" int msm_ray_cert_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
+                                  int64_t cells_cap) {
+    using namespace msm;
+    if (!xyz || !tri || !report || V <= 0 || T <= 0 || nsamples < 0) return fail(MSM_ERR_INVALID, "msm_ray_cert_check: bad arguments");
+    for (int64_t i = 0; i < 3 * (int64_t)T; ++i)
+        if (tri[i] < 0 || tri[i] >= V) return fail(MSM_ERR_INVALID, "msm_ray_cert_check: triangle vertex id %d out of range [0,%d)", tri[i], V);
+    FlatOctree o;
+    build_octree(xyz, tri, V, T, o);
+    build_ray_table(xyz, tri, V, T, o);
+    for (int k = 0; k < 8; ++k) report[k] = 0;
+    if (o.rays.G <= 0) return MSM_OK;
+    const size_t ncell = o.rays.cell.size();
+    report[6] = (int64_t)ncell;
+    if (cells) {
+        if (cells_cap < 4 * (int64_t)ncell) return fail(MSM_ERR_INVALID, "msm_ray_cert_check: room for %lld words, the cells have %lld", (long long)cells_cap, (long long)(4 * ncell));
+        std::memcpy(cells, o.rays.cell.data(), ncell * sizeof(int4));
+    }
+    for (size_t c = 0; c < ncell; ++c)
+        for (int su = 0; su < kRayHintK; ++su)
+            for (int sv = 0; sv < kRayHintK; ++sv) {
+                ++report[4];
+                if (ray_cell_cert(o.rays.cell[c], su, sv)) ++report[5];
+            }
+    DevTree dt{};
+    dt.ray_G = o.rays.G;
+    dt.ray_cell = o.rays.cell.data();
+    dt.ray_more = o.rays.more.data();
+    dt.ray_excl = o.rays.excl.data();
+    dt.ray_r2lo = o.rays.r2lo, dt.ray_r2hi = o.rays.r2hi;
+    uint64_t rs = seed * 6364136223846793005ull + 1442695040888963407ull;
+    auto rnd = [&]() {  // uniform in [0, 1)
+        rs = rs * 6364136223846793005ull + 1442695040888963407ull;
+        return (double)(rs >> 11) * (1.0 / 9007199254740992.0);
+    };
+    auto vert = [&](int t, int k) { return vtx(xyz, V, tri[(size_t)k * T + t]); };
+    const int G = o.rays.G;
+    auto on_face = [&](int f, double u, double v) {  // the direction of face coordinates (u, v), as ray_cell_at reads them
+        const int a = f >> 1;
+        double comp[3];
+        comp[a] = (f & 1) ? -1.0 : 1.0, comp[(a + 1) % 3] = u, comp[(a + 2) % 3] = v;
+        return mk(comp[0], comp[1], comp[2]);
+    };
+    auto check = [&](V3 p) {
+        p = scale(normalized(p), kRad);
+        ++report[0];
+        float fx, fy, fz;
+        bool cert;
+        const int4 first = ray_cell_of(dt, p, fx, fy, fz, cert);
+        if (!cert) return;
+        ++report[1];
+        const int t = first.x;
+        if (t < 0 || t >= T) {
+            ++report[2], ++report[3];
+            return;
+        }
+        if (!ray_accepts_fp64(vert(t, 0), vert(t, 1), vert(t, 2), p, norm(p), (double)o.rays.edge[3 * (size_t)t].w - kRayFloatAllowance + 1e-12)) ++report[2];
+        int n = 0;  // the reference's first pass: descend to the leaf, every listed triangle through the inside test
+        while (o.node[n].x >= 0) {
+            const double4 b = o.nodebox[n];
+            const double mx = (b.x + (b.x + b.w)) / 2.0, my = (b.y + (b.y + b.w)) / 2.0, mz = (b.z + (b.z + b.w)) / 2.0;
+            n = o.node[n].x + 4 * (!(p.x < mx)) + 2 * (!(p.y < my)) + (!(p.z < mz));
+        }
+        int answer = -1, nhits = 0;
+        for (int e = 0; e < -o.node[n].x - 1; ++e) {
+            const int tt = o.leaf_tri[o.node[n].y + e];
+            const V3 a = vert(tt, 0), b = vert(tt, 1), c = vert(tt, 2);
+            if (point_in_triangle(project_point(p, a, b, c), a, b, c)) answer = tt, ++nhits;
+        }
+        if (!(nhits == 1 && answer == t)) ++report[3];
+    };
+    for (int it = 0; it < nsamples; ++it) {
+        V3 p;
+        do p = mk(2 * rnd() - 1, 2 * rnd() - 1, 2 * rnd() - 1);
+        while (!(norm(p) > 0.1 && norm(p) <= 1.0));
+        check(p);
+    }
+    const int64_t before = report[0];
+    const double cellw = 2.0 / G;
+    auto nudge = [&]() { return rnd() < 0.2 ? 0.0 : (rnd() < 0.5 ? -1.0 : 1.0) * 1e-6 * rnd() * cellw; };
+    auto border = [&](bool cell_border) {  // a coordinate next to a sub-cell border (or a cell border) of a random cell
+        const int i = (int)(rnd() * G) % G, s = cell_border ? 0 : 1 + (int)(rnd() * (kRayHintK - 1)) % std::max(1, kRayHintK - 1);
+        return -1 + 2.0 * (i + (double)s / kRayHintK) / G + nudge();
+    };
+    auto rim = [&]() { return (rnd() < 0.5 ? -1.0 : 1.0) + nudge(); };
+    for (int it = 0; it < 6000; ++it) {
+        const int f = (int)(rnd() * 6) % 6, kind = it % 6;
+        double u = 2 * rnd() - 1, v = 2 * rnd() - 1;
+        if (kind == 0) u = border(false);                         // a sub-cell border
+        else if (kind == 1) u = border(false), v = border(false);  // a sub-cell corner
+        else if (kind == 2) v = border(true);                      // a cell border
+        else if (kind == 3) u = border(true), v = border(it % 12 < 6);  // a cell corner, or a cell border meeting a sub-cell border
+        else if (kind == 4) (rnd() < 0.5 ? u : v) = rim();         // a cube-face edge
+        else u = rim(), v = rim();                                 // a cube-face corner
+        check(on_face(f, u, v));
+    }
+    for (int j = 0; j < std::min(V, 3000); ++j) check(vtx(xyz, V, V <= 3000 ? j : (int)(rnd() * V) % V));
+    for (int it = 0; it < 3000; ++it) {
+        const int t = (int)(rnd() * T) % T, k = (int)(rnd() * 3) % 3;
+        const V3 a = vert(t, k), b = vert(t, (k + 1) % 3), c = vert(t, (k + 2) % 3);
+        const V3 mid = mk(0.5 * (a.x + b.x), 0.5 * (a.y + b.y), 0.5 * (a.z + b.z));
+        const double off = (it & 1) ? 1e-9 : -1e-9;
+        check(mk(mid.x + off * (c.x - mid.x), mid.y + off * (c.y - mid.y), mid.z + off * (c.z - mid.z)));
+    }
+    report[7] = report[0] - before;
     return MSM_OK;
 }

@@ -61,9 +61,12 @@ MSM_HD float ray_rsqrt(float x) {
 // cell as the kernels take it -- candidate h first, the others behind it in their stored order.
 MSM_HD int ray_cell_id(int word) { return (int)((unsigned)word << (32 - kRayIdBits)) >> (32 - kRayIdBits); }
 MSM_HD int4 ray_cell_ids(const int4 &raw) {
-    if (kRayHintK == 1) return raw;
-    return make_int4(ray_cell_id(raw.x), ray_cell_id(raw.y), ray_cell_id(raw.z), raw.w);
+    const int w = (int)((unsigned)raw.w << (32 - kRayWBits)) >> (32 - kRayWBits);  // (the certificates sit above it)
+    if (kRayHintK == 1) return make_int4(raw.x, raw.y, raw.z, w);
+    return make_int4(ray_cell_id(raw.x), ray_cell_id(raw.y), ray_cell_id(raw.z), w);
 }
+// the certificate of a sub-cell (internal.hpp: kRayWBits): its hinted candidate is the answer for every direction in it
+MSM_HD bool ray_cell_cert(const int4 &raw, int su, int sv) { return (((unsigned)raw.w >> (kRayWBits + 3 * su + sv)) & 1u) != 0u; }
 MSM_HD int ray_cell_hint(const int4 &raw, int su, int sv) {
     if (kRayHintK == 1) return 0;
     const unsigned word = (unsigned)(su == 0 ? raw.x : (su == 1 ? raw.y : raw.z));
@@ -102,11 +105,14 @@ MSM_HD bool ray_cell_at(const DevTree &T, const V3 &p, float &fx, float &fy, flo
     at = ((size_t)face * G + iu) * G + iv;
     return true;
 }
-MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, float &fz) {
+// (cert: the first candidate handed out is certified for this sub-cell; w comes out sign-extended, the certificate bits never reach a caller as part of an id)
+MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, float &fz, bool &cert) {
     size_t at;
     int su, sv;
+    cert = false;
     if (!ray_cell_at(T, p, fx, fy, fz, at, su, sv)) return make_int4(-1, -1, -1, -1);
     const int4 raw = T.ray_cell[at];
+    cert = ray_cell_cert(raw, su, sv);
     int4 c = ray_cell_first(raw, ray_cell_hint(raw, su, sv));
 #ifdef __HIP_DEVICE_COMPILE__
     // the decoded cell in one register quadruple, as the load delivered it before there were hints: without this the allocator
@@ -119,6 +125,10 @@ MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, flo
     }
 #endif
     return c;
+}
+MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, float &fz) {  // for a caller that tests every candidate
+    bool cert;
+    return ray_cell_of(T, p, fx, fy, fz, cert);
 }
 
 // the acceptance test of one candidate: all three edge-plane products at or above the triangle's threshold (e0.w)
@@ -293,24 +303,29 @@ MSM_HD bool ray_vouches(const DevTree &T, const float4 &e1, const V3 &p) {
 }
 
 // Ray-table search for one point: the triangle the reference's search returns, or -1 when the table cannot vouch for
-// it (then the caller runs find_closest_triangle).  Same test as k_unary_rays (unary_kernels.hip).
-__device__ __forceinline__ int ray_find(const DevTree &T, const V3 &p) {
+// it (then the caller runs find_closest_triangle).  Same test as k_unary_rays (unary_kernels.hip), the certificate's shortcut included: a
+// certified first candidate is the answer without a look at its record.  `planes`: the candidates' edge planes, `pieces` float4 apart
+// (the device records, or the host's RayTable::edge with 3: octree.cpp checks the table's guarantee through this very function).
+MSM_HD int ray_find_in(const DevTree &T, const float4 *planes, int pieces, const V3 &p) {
     if (T.ray_G <= 0) return -1;
     float fx, fy, fz;
-    const int4 c = ray_cell_of(T, p, fx, fy, fz);
+    bool cert;
+    const int4 c = ray_cell_of(T, p, fx, fy, fz, cert);
     if (c.x < 0) return -1;
+    if (cert) return c.x;
     int4 mo = make_int4(c.w, -1, -1, -1);
     if (c.w < -1) mo = T.ray_more[-2 - c.w];
 #pragma unroll 1
     for (int k = 0; k < 7; ++k) {
         const int ck = k == 0 ? c.x : (k == 1 ? c.y : (k == 2 ? c.z : (k == 3 ? mo.x : (k == 4 ? mo.y : (k == 5 ? mo.z : mo.w)))));
         if (ck < 0) break;
-        const float4 *r = T.ray_tri + (size_t)kRayPieces * ck;
+        const float4 *r = planes + (size_t)pieces * ck;
         const float4 e0 = r[0], e1 = r[1], e2 = r[2];
         if (ray_accepts(e0, e1, e2, fx, fy, fz)) return ray_vouches(T, e1, p) ? ck : -1;
     }
     return -1;
 }
+MSM_HD int ray_find(const DevTree &T, const V3 &p) { return ray_find_in(T, T.ray_tri, kRayPieces, p); }
 
 // Returns the triangle id (>= 0), or MSM_ERR_OUTSIDE / MSM_ERR_NOTFOUND.
 __device__ __forceinline__ int find_closest_triangle(const DevTree &T, const V3 &p, bool allow_fallback = true) {

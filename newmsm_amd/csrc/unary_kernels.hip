@@ -386,8 +386,15 @@ __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
 // LDS per wavefront they cut the occupancy to 3 waves per SIMD and lengthen the dependent chain (shuffle -> load ->
 // LDS -> test): 123 us (all four candidate rounds as a team) and 107 us (first candidate only) against 85 us for
 // the plain per-lane loads below.
+// Three of the nine pieces of the first candidate's record (the edge planes) exist only to accept it.  A cell carries one bit per sub-cell that
+// says the hinted candidate passes for every direction of the sub-cell and needs no vouching (internal.hpp: kRayWBits; octree.cpp: build_ray_table
+// has the proof); 0.57 of the samples of an ico6 target fall into such a sub-cell.  Their lanes are switched off for the three plane loads -- a lane
+// predicate: an inactive lane looks no line up -- and take the candidate untested; everything after acceptance is as it was, and so is every result
+// (a certificate only skips a test that would have passed).  72 VGPRs and seven waves per SIMD as before, which takes the two empty asm statements
+// in the loop and the occupancy request on the kernel (without it the retry loop's packed multiplies push the allocator to 74).  DESIGN.md section
+// 5.2 has the counters.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k_unary_rays(SamplesArgs a) {
     extern __shared__ __align__(16) double lds[];
     double *sx = lds, *sy = sx + a.pmax, *sz = sy + a.pmax, *sR = sz + a.pmax;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -425,10 +432,11 @@ __global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
         V3 p = mk(0.0, 0.0, 0.0);
         float fx = 0.f, fy = 0.f, fz = 0.f;
         int4 c = make_int4(-1, -1, -1, -1);
+        bool cert = false;
         if (act) {
             const int l = fast_div(s, P, invP), i = s - l * P;
             p = rotate(sR + 9 * l, mk(sx[i], sy[i], sz[i]));
-            c = ray_cell_of(a.tree, p, fx, fy, fz);
+            c = ray_cell_of(a.tree, p, fx, fy, fz, cert);
         }
         if (act) {
             if (c.x >= 0) {
@@ -436,13 +444,39 @@ __global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
                 // out of ten (three out of four for the best-ranked candidate of the whole cell): its vertices are requested
                 // together with its edge planes, so a settled sample costs two dependent loads after the cell
                 const float4 *rec = a.tree.ray_tri + (size_t)kRayPieces * c.x;
-                const float4 e0 = rec[0], e1 = rec[1], e2 = rec[2];
+                // A lane whose sub-cell is certified (internal.hpp: kRayWBits) knows that this candidate passes and needs no vouching: it sits
+                // out the three edge-plane loads -- a lane that is switched off looks no line up -- and takes the candidate as it is.
+                // (a lane predicate: the six vertex pieces are requested in the same breath, by every lane, and nothing waits in between)
                 const double2 *dv = reinterpret_cast<const double2 *>(rec + 3);
-                double2 d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
                 int t = c.x;
-                bool vouch_needed = __float_as_int(e1.w) >= 0;
-                float4 ev = e1;
-                if (!ray_accepts(e0, e1, e2, fx, fy, fz)) {
+                int excl = -1;  // the accepted candidate's exclusion record (its e1.w), negative: none -- as for a certified candidate
+                bool retry = false;
+#ifdef __HIP_DEVICE_COMPILE__
+                // The certified lanes never read the planes, so nothing need be written for them: the first empty statement names the
+                // twelve registers, without an instruction.  (Left to variables without a value, the allocator keeps the registers for the
+                // whole sample loop -- 85 instead of 72, two wavefronts per SIMD; written as zeros they cost twelve moves a round.)  The
+                // second one keeps the planes out of sight until the vertex loads are out: the packed multiplies of the test want two of
+                // their words side by side, and the compiler would otherwise wait for them, and move them, before it requests the vertices.
+                typedef float v4f __attribute__((ext_vector_type(4)));
+                v4f q0, q1, q2;
+                asm volatile("" : "=v"(q0), "=v"(q1), "=v"(q2));
+                if (!cert) {
+                    const v4f *rq = reinterpret_cast<const v4f *>(rec);
+                    q0 = rq[0], q1 = rq[1], q2 = rq[2];
+                }
+                double2 d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
+                if (!cert) {
+                    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
+                    const float4 e0 = make_float4(q0.x, q0.y, q0.z, q0.w), e1 = make_float4(q1.x, q1.y, q1.z, q1.w), e2 = make_float4(q2.x, q2.y, q2.z, q2.w);
+#else
+                double2 d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
+                if (!cert) {
+                    const float4 e0 = rec[0], e1 = rec[1], e2 = rec[2];
+#endif
+                    excl = __float_as_int(e1.w);
+                    retry = !ray_accepts(e0, e1, e2, fx, fy, fz);
+                }
+                if (retry) {
                     t = -1;
                     int4 mo = make_int4(c.w, -1, -1, -1);
                     if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
@@ -455,8 +489,7 @@ __global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
                         const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
                         if (ray_accepts(g0, g1, g2, fx, fy, fz)) {
                             t = ck;
-                            ev = g1;
-                            vouch_needed = __float_as_int(g1.w) >= 0;
+                            excl = __float_as_int(g1.w);
                         }
                     }
                     if (t >= 0) {
@@ -464,7 +497,7 @@ __global__ __launch_bounds__(256) void k_unary_rays(SamplesArgs a) {
                         d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
                     }
                 }
-                if (t >= 0 && vouch_needed && !ray_vouches(a.tree, ev, p)) t = -1;  // its leaf may not list the triangle
+                if (t >= 0 && excl >= 0 && !ray_vouches(a.tree, make_float4(0.f, 0.f, 0.f, __int_as_float(excl)), p)) t = -1;  // its leaf may not list the triangle
                 if (t >= 0) {
                     double wa, wb, wc;
                     area_weights(mk(d0.x, d0.y, d1.x), mk(d1.y, d2.x, d2.y), mk(d3.x, d3.y, d4.x), p, wa, wb, wc);
