@@ -107,7 +107,7 @@ int msm_estimate_pairs(const int32_t *tri, int32_t V, int32_t T, int32_t *pairs)
 /* testing hook: the search tree (newresampler::Octree, R/octree.cpp:31-141) of a mesh, built on the host without a GPU:
  * stats as msm_mesh_octree_stats, and a signature of the leaves (box + triangle list in stored order of every leaf) */
 int msm_octree_signature(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int64_t stats[5], uint64_t *signature);
-/* testing hook, host only: the guarantee of the direction table that the cost kernels search simple-surface targets with (csrc/octree.cpp:
+/* testing hook, host only: the guarantee of the direction table that the cost kernels search simple-surface targets with (csrc/ray_table.cpp:
  * build_ray_table), checked at nsamples points (random directions; points next to random edges and vertices) against the first pass of
  * Octree::get_closest_triangle (R/octree.cpp:156-178) over the host-built tree: whatever a kernel may accept must be the one listed triangle
  * that passes the inside test.  report: [0] points [1] accepted by the float test [2] only by the FP64 re-test [3] left to the complete search
@@ -130,6 +130,10 @@ int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t V, int32_t
  * [6] cells [7] placed points.  cells: as msm_ray_hint_check.  MSMHIP_RAY_CERTS=off (read when a table is built) writes no certificates. */
 int msm_ray_cert_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
                        int64_t cells_cap);
+/* testing hook, host only: a signature of the whole direction table of a mesh, as the host builds it.  out: [0] cells per face axis (0: no table, and
+ * every count is zero) [1] simple surface [2] built with certificates [3..6] elements of the cell, edge-plane, further-candidate and exclusion arrays
+ * [7] [8] the bit patterns of the squared radius range [9..12] 64-bit FNV-1a over the raw bytes of those four arrays. */
+int msm_ray_table_signature(const double *xyz, const int32_t *tri, int32_t V, int32_t T, uint64_t out[13]);
 
 /* ------------------------------------------------------------------------------------------------
  * context: one per GPU

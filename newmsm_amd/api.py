@@ -171,6 +171,17 @@ def ray_cert_check(xyz, tri, nsamples=20000, seed=1, return_cells=False):
     return out
 
 
+def ray_table_signature(xyz, tri):
+    """[host] a signature of the whole direction table of a mesh: its sizes, its radius range (bit patterns) and a 64-bit hash of each of its four arrays
+    (testing hook, msm_ray_table_signature).  A mesh without a table gives G = 0 and zero counts."""
+    x, px = _soa(xyz)
+    t, pt = _tri_soa(tri)
+    out = (C.c_uint64 * 13)()
+    check(lib().msm_ray_table_signature(px, pt, x.shape[1], t.shape[1], out))
+    names = ("G", "simple", "certs", "cells", "edges", "more", "excl", "r2lo_bits", "r2hi_bits", "cell_hash", "edge_hash", "more_hash", "excl_hash")
+    return dict(zip(names, (int(v) for v in out)))
+
+
 def estimate_triplets(tri):
     t, pt = _tri_soa(tri)
     out = np.zeros((t.shape[1], 3), dtype=np.int32)

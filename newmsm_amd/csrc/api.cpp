@@ -11,6 +11,7 @@
 
 #include "devbuf.hpp"
 #include "kernels.hpp"
+#include "ray_table.hpp"
 
 using namespace msm;
 
@@ -203,11 +204,6 @@ struct msm::RayJob {
 
 namespace msm {
 
-static bool ray_build_in_background() {
-    const char *e = std::getenv("MSMHIP_RAYTABLE");
-    return !(e && (std::strcmp(e, "sync") == 0 || std::strcmp(e, "off") == 0));
-}
-
 // Direction tables by mesh content.  A table is a pure function of the target's coordinates and triangles, and a pipeline registers
 // many subjects against the SAME targets (every level's target is the regular icosphere of its resolution; the template of a group):
 // the host arrays of the last few tables built in this process are kept (coordinates and triangles compared in full on a hit, so a
@@ -276,16 +272,15 @@ int ensure_rays(msm_mesh *m, bool wait) {
     if (m->rays_valid) return ensure_rayrec(m);
     msm_ctx *ctx = m->ctx;
     if (m->ray_job && m->ray_job->gen != m->tree_gen) retire_ray_job(m);
-    const char *mode = std::getenv("MSMHIP_RAYTABLE");
-    if (mode && std::strcmp(mode, "off") == 0) return MSM_OK;
+    const RayTableMode mode = ray_table_mode();
+    if (mode == RayTableMode::off) return MSM_OK;
     // (the switches that change what build_ray_table produces are read per call -- the tests flip them within a process: no cache then)
-    const char *no_table = std::getenv("MSMHIP_DISABLE_RAYTABLE");
-    const bool cache_ok = !(no_table && no_table[0] == '1');
+    const bool cache_ok = !ray_table_disabled();
     const uint64_t chash = cache_ok ? content_hash(m) : 0;
     std::shared_ptr<const RayCacheEntry> hit = (!m->ray_job && cache_ok) ? ray_cache_find(m, chash) : nullptr;
     if (hit) {  // a mesh with these coordinates and triangles has had its table built in this process
         m->tree.rays = hit->rays;
-    } else if (!m->ray_job && (wait || !ray_build_in_background())) {
+    } else if (!m->ray_job && (wait || mode != RayTableMode::background)) {
         if (m->tree.node.empty()) {  // the tree was built on the GPU: the table's builder walks a host copy of the same tree
             FlatOctree host_tree;
             build_octree(m->xyz.data(), m->tri.data(), m->V, m->T, host_tree);
@@ -714,8 +709,7 @@ int msm_mesh_prepare_search(msm_mesh *m, int wait, int32_t *ready) {
     int st = ensure_rays(m, wait != 0);
     if (st) return st;
     MSM_TRY(ctx_sync(m->ctx));
-    const char *mode = std::getenv("MSMHIP_RAYTABLE");
-    if (ready) *ready = (m->rays_valid || (mode && std::strcmp(mode, "off") == 0)) ? 1 : 0;
+    if (ready) *ready = (m->rays_valid || ray_table_mode() == RayTableMode::off) ? 1 : 0;
     return MSM_OK;
 }
 

@@ -18,7 +18,7 @@ namespace msm {
 constexpr double kEps = 1e-8;        // EPSILON, R/point.h:31
 constexpr double kRad = 100.0;       // RAD, R/point.h:32
 constexpr double kBounds = 101.0;    // MESH_BOUNDS, R/octree.h:37
-constexpr double kRayFloatAllowance = 3e-6;  // direction table: what the float evaluation of an edge-plane product may be off by (octree.cpp: build_ray_table)
+constexpr double kRayFloatAllowance = 3e-6;  // direction table: what the float evaluation of an edge-plane product may be off by (ray_table.cpp)
 constexpr int kMaxTriangles = 50;    // MAX_TRIANGLES, R/node.h:33
 
 struct V3 {
@@ -166,5 +166,8 @@ MSM_HD bool rotation_matrix(V3 ci, V3 index, double *R) {
 
 // geodesic distance from a chord, e.g. R/octree.cpp:200, M/DiscreteCostFunction.cpp:104-106
 MSM_HD double chord_to_arc(double chord) { return 2 * kRad * asin(chord / (2 * kRad)); }
+
+// vertex i of a mesh whose coordinates are stored 3 x V (host set-up code)
+inline V3 vtx(const double *xyz, int V, int i) { return mk(xyz[i], xyz[V + i], xyz[2 * V + i]); }
 
 }  // namespace msm

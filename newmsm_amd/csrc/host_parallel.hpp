@@ -9,12 +9,18 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
+
+// set-up timing to stderr when MSMHIP_TIMING is set: the time since the last TICK of a function that starts with
+//   auto tick_ = std::chrono::steady_clock::now();
+#define TICK(name) do { if (std::getenv("MSMHIP_TIMING")) { auto now_ = std::chrono::steady_clock::now(); fprintf(stderr, "  %s %.1f ms\n", name, std::chrono::duration<double, std::milli>(now_ - tick_).count()); tick_ = now_; } } while (0)
 
 namespace msm {
 

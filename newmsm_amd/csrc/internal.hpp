@@ -57,7 +57,7 @@ struct alignas(128) TriRec {
 static_assert(sizeof(TriRec) == 128, "TriRec must be 128 bytes");
 
 // Per-triangle record of the ray-table path, nine 16-byte pieces (144 bytes, two cache lines):
-//   pieces 0-2  the three edge planes (float4: inward unit normal, acceptance threshold)      -- octree.cpp
+//   pieces 0-2  the three edge planes (float4: inward unit normal, acceptance threshold)      -- ray_table.cpp
 //   pieces 3-8  the vertices v0,v1,v2 (9 doubles) and, on single-feature meshes, the feature at them (3 doubles)
 // so that a wavefront can fetch the records of its 64 samples with 9 load instructions that touch ~2 lines per
 // record (lanes of one instruction read neighbouring pieces) instead of 9 x 64 lines.  Built on the GPU
@@ -69,7 +69,7 @@ constexpr int kRayPieces = 9;
 // gnomonic triangle holds the sub-cell's centre, 0 = the stored order.  They ride in the top 6 bits of x, y, z -- word
 // su (x, y, z for su = 0, 1, 2), bits 26 + 2 sv -- above a 26-bit two's-complement id (-1 = none; w holds an id, -1 or the
 // ray_more reference in its low 23 bits, see the certificates below). The order of trial cannot change a result: at most one listed candidate
-// passes the acceptance test (octree.cpp).  kRayHintK = 1: no hints are written and none are read.
+// passes the acceptance test (ray_table.cpp).  kRayHintK = 1: no hints are written and none are read.
 #ifndef MSM_RAY_HINT_K
 #define MSM_RAY_HINT_K 3
 #endif
@@ -77,7 +77,7 @@ constexpr int kRayHintK = MSM_RAY_HINT_K;
 static_assert(kRayHintK >= 1 && kRayHintK <= 3, "two bits per sub-cell, three sub-cells per word, three words");
 constexpr int kRayIdBits = 26;
 // Certificates.  The fourth word gives its top nine bits to one bit per sub-cell, bit kRayWBits + 3 su + sv: "the candidate this
-// sub-cell's hint names passes the acceptance test for every direction of the sub-cell, and needs no vouching" (octree.cpp:
+// sub-cell's hint names passes the acceptance test for every direction of the sub-cell, and needs no vouching" (ray_table.cpp:
 // build_ray_table has the proof), so a kernel may take that candidate without loading its edge planes.  Below them w keeps what it held
 // as a 23-bit two's-complement field: an id, -1, or the ray_more reference -2 - index.  So an id has 22 bits (the unary path's own
 // kTriBits): a mesh with more than kRayMaxTris = 2^22 triangles gets no table, and a table whose ray_more list would pass
@@ -88,14 +88,14 @@ static_assert(kRayWBits + 9 == 32 && kRayWBits <= kRayIdBits, "nine certificate 
 constexpr int kRayMaxTris = 1 << (kRayWBits - 1);  // a mesh with more triangles gets no table (build_ray_table)
 constexpr int kRayMaxMore = (1 << (kRayWBits - 1)) - 2;
 
-// Direction (ray) table of a simple surface (octree.cpp: build_ray_table), the host side; G == 0 when absent.
+// Direction (ray) table of a simple surface (ray_table.cpp: build_ray_table), the host side; G == 0 when absent.
 struct RayTable {
     // closed, consistently oriented, star-shaped about the origin, covering the sphere exactly once: every ray from
     // the origin meets exactly one triangle (true for the icosphere targets; false for folded meshes)
     bool simple = false;
     int G = 0;                   // cube-map cells per face axis
     std::vector<int4> cell;      // 6 x G x G: up to four candidate triangles per direction cell, -1 padded
-    std::vector<float4> edge;    // 3 per triangle: inward unit normal of the plane (origin, edge k); .w: see octree.cpp
+    std::vector<float4> edge;    // 3 per triangle: inward unit normal of the plane (origin, edge k); .w: see ray_table.cpp
     std::vector<int4> more;      // candidates 4..7 of the cells that have more than four
     std::vector<int4> excl;      // up to seven leaf boxes a query must not lie in for its triangle to be vouched for: {b0, b1, b2, count} and, for count > 3, {b3 .. b6} in the next record
     double r2lo = 0, r2hi = 0;   // squared radius range of the query points the table is valid for
@@ -127,7 +127,7 @@ struct FlatOctree {
 };
 // builds the tree exactly as Octree::initialize_tree / add_triangle do (R/octree.cpp:42-141)
 void build_octree(const double *xyz /*3 x V SoA*/, const int32_t *tri /*3 x T SoA*/, int V, int T, FlatOctree &out);
-// decides RayTable::simple and, for a simple surface, fills the ray table (tree.rays) of an already built tree
+// decides RayTable::simple and, for a simple surface, fills the ray table (tree.rays) of an already built tree (ray_table.cpp)
 void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOctree &tree);
 // MSMHIP_RAY_CERTS is not "off": build_ray_table writes certificates (read per call; the content cache of tables keys on it, api.cpp)
 bool ray_certs_enabled();

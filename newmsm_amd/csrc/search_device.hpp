@@ -39,10 +39,10 @@ __device__ __forceinline__ bool inside_test(const TriRec &r, const V3 &p, V3 &mp
     return point_in_triangle(mp, rec_v0(r), rec_v1(r), rec_v2(r));
 }
 
-// Ray table (octree.cpp: build_ray_table): the direction cell of p, i.e. up to four candidate triangles, likeliest
+// Ray table (ray_table.cpp: build_ray_table): the direction cell of p, i.e. up to four candidate triangles, likeliest
 // first; all -1 when p is off the radius shell the table vouches for (or NaN).  Float arithmetic only proposes
 // candidates and accepts them with the margins built into the thresholds; it never decides between two candidates.
-// (the functions of the table's acceptance test also compile for the host: octree.cpp checks the table's guarantee with them, msm_ray_table_check)
+// (the functions of the table's acceptance test also compile for the host: ray_table_check.cpp checks the table's guarantee with them, msm_ray_table_check)
 MSM_HD int ray_clamp(int i, int hi) {  // max(0, min(hi, i))
 #ifdef __HIP_DEVICE_COMPILE__
     return max(0, min(hi, i));
@@ -139,7 +139,7 @@ MSM_HD bool ray_accepts(const float4 &e0, const float4 &e1, const float4 &e2, fl
     return (int)(d0 >= e0.w) & (int)(d1 >= e0.w) & (int)(d2 >= e0.w);
 }
 
-// The float test's allowance inside the stored threshold (octree.cpp: build_ray_table adds it to margin / rho: direction 2e-7, normals 6e-8, dot
+// The float test's allowance inside the stored threshold (ray_table.cpp: build_ray_table adds it to margin / rho: direction 2e-7, normals 6e-8, dot
 // 2e-7 and slack), and the two tests that use it: level 1 of ray_accept_level ("no float evaluation of a point the FP64 test would accept lies below this") and the FP64
 // test itself -- the inward unit normals of the planes through the origin and each edge from the FP64 vertices, p^ . n_k >= thr for k = 0, 1, 2
 // with thr = (stored threshold) - allowance (+ 1e-12 for its own rounding), which is at least the margin / rho the proof asks for.
@@ -168,7 +168,7 @@ MSM_HD bool ray_accepts_fp64(const V3 &v0, const V3 &v1, const V3 &v2, const V3 
 }
 
 // Is the accepted triangle listed in the octree leaf p descends to?  Yes unless p lies in one of the (at most seven)
-// leaf boxes recorded for the triangle (octree.cpp: build_ray_table); e1.w carries the index of that record, or -1.
+// leaf boxes recorded for the triangle (ray_table.cpp: build_ray_table); e1.w carries the index of that record, or -1.
 MSM_HD bool ray_vouches(const DevTree &T, const float4 &e1, const V3 &p);
 
 __device__ __forceinline__ double candidate_distance(const DevTree &T, int t, const V3 &p) {
@@ -305,7 +305,7 @@ MSM_HD bool ray_vouches(const DevTree &T, const float4 &e1, const V3 &p) {
 // Ray-table search for one point: the triangle the reference's search returns, or -1 when the table cannot vouch for
 // it (then the caller runs find_closest_triangle).  Same test as k_unary_rays (unary_kernels.hip), the certificate's shortcut included: a
 // certified first candidate is the answer without a look at its record.  `planes`: the candidates' edge planes, `pieces` float4 apart
-// (the device records, or the host's RayTable::edge with 3: octree.cpp checks the table's guarantee through this very function).
+// (the device records, or the host's RayTable::edge with 3: ray_table_check.cpp checks the table's guarantee through this very function).
 MSM_HD int ray_find_in(const DevTree &T, const float4 *planes, int pieces, const V3 &p) {
     if (T.ray_G <= 0) return -1;
     float fx, fy, fz;

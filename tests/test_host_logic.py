@@ -86,7 +86,7 @@ def test_top_down_octree_equals_incremental_insertion(built, monkeypatch, order,
 
 @pytest.mark.parametrize("order,shape", [(3, "regular"), (4, "regular"), (5, "warped"), (5, "radial"), (6, "regular"), (4, "jittered")])
 def test_direction_table_accepts_only_the_reference_answer(built, order, shape):
-    # The table the cost kernels search simple-surface targets with (csrc/octree.cpp: build_ray_table), against the first pass of
+    # The table the cost kernels search simple-surface targets with (csrc/ray_table.cpp: build_ray_table), against the first pass of
     # Octree::get_closest_triangle (R/octree.cpp:156-178) on the host: at random directions and at points placed 1e-10 .. 1e-3 of an edge
     # away from random edges and vertices, whatever a kernel may accept -- the float edge-plane test, or the FP64 re-test of a nearly
     # accepted candidate, and ray_vouches; the very functions the kernels call -- must be the one triangle listed in the point's leaf

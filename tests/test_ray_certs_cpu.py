@@ -1,4 +1,4 @@
-"""The certificates of the direction table's cells (csrc/internal.hpp: kRayWBits, csrc/octree.cpp: build_ray_table, csrc/search_device.hpp: ray_cell_of),
+"""The certificates of the direction table's cells (csrc/internal.hpp: kRayWBits, csrc/ray_table.cpp: build_ray_table, csrc/search_device.hpp: ray_cell_of),
 on the host, through the testing hook msm_ray_cert_check (no GPU needed).
 
 One bit per sub-cell, in the top nine bits of a cell's fourth word, says that the candidate the sub-cell's hint names passes the acceptance test for every

@@ -1,4 +1,4 @@
-"""The first-candidate hints of the direction table's cells (csrc/internal.hpp: kRayHintK, csrc/octree.cpp: build_ray_table,
+"""The first-candidate hints of the direction table's cells (csrc/internal.hpp: kRayHintK, csrc/ray_table.cpp: build_ray_table,
 csrc/search_device.hpp: ray_cell_of), on the host, through the testing hook msm_ray_hint_check (no GPU needed).
 
 A cell lists up to four candidate triangles (more in ray_more); the spare top bits of its first three words say, for each of its 3 x 3
