@@ -14,6 +14,7 @@
 #include "cost_internal.hpp"
 #include "host_parallel.hpp"
 #include "resample.hpp"
+#include "unary.hpp"
 
 using namespace msm;
 
@@ -196,30 +197,6 @@ int resample_weights(msm_cost *c) {
     MSM_TRY(stage_d2h(ctx, c->absw.data(), c->d_absw.p, sizeof(double) * (size_t)N));
     MSM_TRY(ctx_sync(ctx));
     return MSM_OK;
-}
-
-// Launch order of the control points in the unary kernels: Morton order of their positions (cp: 3 x N)
-static void unary_launch_order(const double *cp, int N, std::vector<int32_t> &order) {
-    auto spread = [](uint32_t v) {  // 10 bits -> every third bit
-        v &= 0x3ff;
-        v = (v | (v << 16)) & 0x030000ff;
-        v = (v | (v << 8)) & 0x0300f00f;
-        v = (v | (v << 4)) & 0x030c30c3;
-        v = (v | (v << 2)) & 0x09249249;
-        return v;
-    };
-    std::vector<std::pair<uint32_t, int32_t>> key(N);
-    for (int i = 0; i < N; ++i) {
-        uint32_t q[3];
-        for (int a = 0; a < 3; ++a) {
-            const double u = (cp[(size_t)a * N + i] + kBounds) / (2 * kBounds);
-            q[a] = (uint32_t)std::max(0.0, std::min(1023.0, u == u ? u * 1024.0 : 0.0));
-        }
-        key[i] = {spread(q[0]) << 2 | spread(q[1]) << 1 | spread(q[2]), i};
-    }
-    std::sort(key.begin(), key.end());
-    order.resize(N);
-    for (int i = 0; i < N; ++i) order[i] = key[i].second;
 }
 
 int ensure_unary_table(msm_cost *c) {

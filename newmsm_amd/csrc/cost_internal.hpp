@@ -5,6 +5,7 @@
 
 #include "devbuf.hpp"
 #include "kernels.hpp"
+#include "unary.hpp"
 
 using msm::DevBuf;
 

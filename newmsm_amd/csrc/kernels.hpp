@@ -1,4 +1,4 @@
-// kernels.hpp -- launch wrappers implemented in the *_kernels.hip files (device pointers only); the resampler's are in resample.hpp.
+// kernels.hpp -- launch wrappers implemented in the *_kernels.hip files (device pointers only); the resampler's are in resample.hpp, the unary table's in unary.hpp.
 #pragma once
 
 #include "internal.hpp"
@@ -58,67 +58,6 @@ int launch_scan_exclusive(msm_ctx *ctx, int *d_data, int n, int *d_tmp);
 // rnl[(node*L + l)*9..] = estimate_rotation_matrix(cp[node], rot[node]*labels[l]); moved (optional, N x L x 3 AoS) = rot[node]*labels[l]
 int launch_label_rotations(msm_ctx *ctx, const double *d_cp, int N, const double *d_rot, const double *d_labels, int L, double *d_rnl,
                            double *d_moved);
-
-// What a unary-table launch does for (cost kind, similarity, D, L, largest patch, sampler): unary_plan() takes every decision that depends on the
-// largest patch, the launchers act on the plan they are handed (UnaryLaunch::plan) and msm_unary_launch_plan shows it to the tests.
-struct UnaryPlan {
-    int nsplit = 1;              // workgroups (label ranges) per control point
-    int sampler = 0;             // MSM_SAMPLER_*
-    size_t sampler_lds = 0;      // dynamic LDS of the sampling kernel, bytes
-    int reduce = 0;              // MSM_UNARY_*: the reduction kernel
-    size_t reduce_lds = 0;       // its dynamic LDS, bytes
-    int reduce_threads = 256;    // its workgroup size
-    int refused = 0;             // MSM_PLAN_REFUSED_*: a kernel's LDS does not fit a workgroup; nothing is launched
-};
-UnaryPlan unary_plan(int kind, int simmeasure, int D, int L, int pmax, bool ray_table);
-int unary_plan_refusal(const UnaryPlan &p, int pmax);  // MSM_OK, or MSM_ERR_CAPACITY with the message that names the patch size
-bool unary_uses_ray_table(const DevTree &t);
-
-struct UnaryLaunch {
-    DevTree tree;
-    const double *tfeat;   // target features, V x D vertex-major
-    int D;
-    int N, L;
-    const double *cp;      // 3 x N
-    const double *rnl;     // N x L x 9 from launch_label_rotations
-    const double *labels;  // 3 x L
-    const double *src;     // 3 x Nsrc
-    int Nsrc;
-    const double *sfeat;   // D x Nsrc
-    const double *cfw;     // rows x Nsrc or nullptr
-    int cfw_rows;
-    const double *sfeat_vm = nullptr;  // Nsrc x D and Nsrc x rows vertex-major copies (multivariate reduction), optional
-    const double *cfw_vm = nullptr;
-    const int *pptr, *pidx;
-    const int *order;      // launch order of the control points (a permutation of 0..N-1)
-    const double *absw;
-    int pmax;
-    int simmeasure;
-    double percentile;     // DICE measures (sparsesimkernel::percentile)
-    double *U;             // L x N
-    // scratch owned by the cost object
-    int ntri;                      // triangles in the target mesh
-    double *tval;                  // one double per point sample (L * total patch points)
-    unsigned long long *fix_list;  // one slot per point sample
-    double *fix_pt;                // three doubles per slot
-    unsigned int *fix_cnt;         // unary_fix_counter_words() words (zeroed by the launch)
-    const unsigned int *fix_off;   // unary_fix_segments() + 1 offsets from unary_fix_offsets()
-    int *redo_list;                // N * plan->nsplit ints: every workgroup of a control point may list it
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // optional: recorded around the samples kernel
-    int *route = nullptr;          // optional: the launcher writes the MSM_UNARY_* value of the reduction kernel it chose
-    const UnaryPlan *plan = nullptr;  // unary_plan() for this launch
-};
-int unary_nsplit(int L, int pmax);
-int unary_fix_segments();
-size_t unary_fix_counter_words();
-void unary_fix_offsets(int N, int L, int pmax, const int32_t *pptr, const int32_t *order, std::vector<uint32_t> &off);
-int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u);
-// multivariate / patchwise: the samples kernel stores (triangle, raw weights) per sample, a second kernel reduces
-struct UnaryWeightsScratch {
-    int *stri;      // one int per sample
-    double *sw3;    // three doubles per sample
-};
-int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWeightsScratch &w, bool patchwise);
 
 // pairwise / triplet clique costs
 struct CliqueArgs {

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import newmsm_amd as M
+import unary_table_pin
 from newmsm_amd import problem
 from tests.helpers import oracle_cost
 
@@ -36,7 +37,10 @@ def test_univariate_dice_general_kernel(ctx, sim, monkeypatch):
     # folded target: the three-phase kernel with its fused reduction
     inp = problem.pairwise_inputs(5, 3, D=1, target_noise=0.6)
     cf, oc, _ = pair(ctx, inp, "univariate", simmeasure=sim)
-    assert np.array_equal(cf.computeUnaryCosts(), oc.unary_table())
+    U = cf.computeUnaryCosts()
+    assert np.array_equal(U, oc.unary_table())
+    # bit for bit against the pinned build too: the fused reduction, and k_unary_reduce_univariate over a redo list that is not empty
+    unary_table_pin.assert_pinned(U, unary_table_pin.key("pairwise-folded", "ico5/ico3", sim=sim, sampler="samples"))
 
 
 @pytest.mark.parametrize("kind", ["multivariate", "patchwise"])

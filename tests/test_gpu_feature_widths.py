@@ -1,7 +1,7 @@
 """Every feature-count route of the multivariate, patchwise and triclique multivariate classes against the oracle, with the route
 asserted through DiscreteCostFunction.routes() (msm_cost_routes: what the launchers recorded where they chose the kernel).
 
-unary table (unary_kernels.hip: launch_unary_multivariate)      features for D < 12, D > 64 or DICE; mv8 for 12 <= D <= 64 (multivariate);
+unary table (unary_plan.cpp: unary_plan)                        features for D < 12, D > 64 or DICE; mv8 for 12 <= D <= 64 (multivariate);
                                                                 pw8<4> for 12 <= D <= 32, pw8<8> for 33 <= D <= 64 (patchwise)
 fused fusion move (move_kernels.hip: move_mode)                 fused3 for even D in 12..32, fused2 for even D in 34..64, fused1 otherwise
 three-kernel path (clique_kernels.hip: launch_triplet_octets)   octets_sample_mv8 for 12 <= D <= 64 (odd D included), octets_sample otherwise

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import newmsm_amd as M
+import unary_table_pin
 from newmsm_amd import problem, synthetic
 from oracle import oracle as O
 from tests.helpers import oracle_cost
@@ -52,6 +53,8 @@ def test_unary_table_univariate(ctx, data_order, cp_order, sim):
     assert U.shape == Uo.shape == (len(inp["labels"]), len(inp["cp_xyz"]))
     assert np.isfinite(U).all()
     assert np.allclose(U, Uo, rtol=RTOL, atol=ATOL), np.max(np.abs(U - Uo))
+    if (data_order, cp_order) == (4, 2):  # patches of at most 96 points: k_unary_reduce_flat with every value in registers; bit for bit against the pinned build
+        unary_table_pin.assert_pinned(U, unary_table_pin.key("pairwise", "ico4/ico2", sim=sim, sampler="either"))
     # on-demand evaluation (Fusion's per-label sweep) returns the same numbers
     nodes = np.arange(0, cf.N, 7, dtype=np.int32)
     labels = (nodes * 5) % cf.L

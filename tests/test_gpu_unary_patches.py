@@ -3,7 +3,7 @@ oracle: the WHOLE table, every entry finite (tests/test_unary_patches_cpu.py), c
 the route the test is about asserted through the launch plan the launchers acted on (DiscreteCostFunction.unary_launch(), msm_cost_unary_launch) and
 routes(), so that a change of a threshold makes the test say that it no longer covers what it claims.
 
-Launch decisions that depend on the largest patch pmax (unary_kernels.hip: unary_plan) and the test that pins each:
+Launch decisions that depend on the largest patch pmax (unary_plan.cpp: unary_plan) and the test that pins each:
   pmax > 96          k_unary_reduce_flat's tail loops behind the 96 values per label kept in registers      test_flat_reduction_tails, _with_weights, _many_labels
   nsplit 4 -> L      label ranges per control point (L = 19: 4 up to 571 points, one label per workgroup from 817) test_complete_sampler
   lper * P > 768     several kChunk passes of k_unary_samples, its queue, its fused DICE reduction + redo list  test_complete_sampler, test_fused_dice
@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import unary_patch_cases as P
+import unary_table_pin
 from newmsm_amd import problem
 from newmsm_amd._lib import MsmError
 
@@ -62,13 +63,15 @@ def table(cf):
     return U
 
 
-def check(U, name, kind="univariate", D=1, sim=2, rows=0, sg_order=None):
+def check(U, name, kind="univariate", D=1, sim=2, rows=0, sg_order=None, sampler="rays"):
+    """against the oracle to the module's tolerance, and bit for bit against the pinned build (unary_table_pin.py)"""
     Uo = P.oracle_table(name, kind, D, sim, rows, sg_order)
     rtol, atol = (RTOL, ATOL) if kind == "univariate" else (MV_RTOL, MV_ATOL)
     assert U.shape == Uo.shape and np.isfinite(U).all()
     err = np.abs(U - Uo)
     print("%s %s D=%d sim=%d rows=%d: max abs err %.3e, max rel err %.3e" % (name, kind, D, sim, rows, err.max(), (err / np.abs(Uo).clip(1e-300)).max()))
     assert np.allclose(U, Uo, rtol=rtol, atol=atol), err.max()
+    unary_table_pin.assert_pinned(U, unary_table_pin.key("patches", name, kind, D, sim, rows, sampler, sg_order))
 
 
 def launch_of(cf, name, sampler, reduce):
@@ -133,7 +136,7 @@ def test_complete_sampler(ctx, monkeypatch, name, sim):
     assert lper * sizes.min() > P.CHUNK  # every workgroup makes a second LDS pass
     assert p["sampler_lds"] == 8 * (5 + lper) * p["pmax"] + 72 * L + 18432 and (p["sampler_lds"] > P.LDS_DEFAULT) == (name == "C")
     assert np.array_equal(U, U_ray)
-    check(U, name, sim=sim)
+    check(U, name, sim=sim, sampler="samples")
 
 
 def refused(cf, name, which="sampler"):
@@ -160,12 +163,12 @@ def test_complete_sampler_near_and_beyond_a_workgroups_lds(ctx, monkeypatch, sim
     U = table(cf)
     p, sizes = launch_of(cf, "F", "samples", "univariate" if sim == 4 else "flat")
     assert p["nsplit"] == cf.L and p["sampler_lds"] == 48 * p["pmax"] + 72 * cf.L + 18432 == 157512 and sizes.min() > 3 * P.CHUNK
-    check(U, "F", sim=sim)
+    check(U, "F", sim=sim, sampler="samples")
     p = refused(cg, "G")
     assert p["sampler"] == "samples" and p["sampler_lds"] == 48 * p["pmax"] + 72 * cg.L + 18432 > P.LDS_WORKGROUP
     U = table(ca)
     launch_of(ca, "A", "samples", "univariate" if sim == 4 else "flat")
-    check(U, "A", sim=sim)
+    check(U, "A", sim=sim, sampler="samples")
 
 
 # ------------------------------------------------------------------ DICE: k_unary_reduce_univariate, and the reduction fused into k_unary_samples
@@ -181,7 +184,7 @@ def test_fused_dice(ctx, monkeypatch, name, sampler, sim):
     U = table(cf)
     p, sizes = launch_of(cf, name, sampler, "univariate")
     assert p["reduce_lds"] == 16 * p["pmax"] and p["nsplit"] == {"A": 4, "C": cf.L, "F": cf.L}[name]
-    check(U, name, sim=sim)
+    check(U, name, sim=sim, sampler=sampler)
 
 
 # ------------------------------------------------------------------ dynamic LDS beyond 64 KB in the ray sampler and the univariate reductions
@@ -260,4 +263,4 @@ def test_too_large_everywhere(ctx, monkeypatch):
     ca = product(ctx, "A")
     U = table(ca)
     launch_of(ca, "A", "samples", "flat")
-    check(U, "A")
+    check(U, "A", sampler="samples")

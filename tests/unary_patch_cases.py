@@ -1,6 +1,6 @@
 """Shared by tests/test_unary_patches_cpu.py (the oracle and the launch plan alone, no GPU) and tests/test_gpu_unary_patches.py (the MI355X path against
 the oracle): unary tables over patches of hundreds to thousands of source points -- coarse control grids under fine data grids, as in the first levels
-of a multiresolution schedule -- where the launch decisions that depend on the largest patch pmax (unary_kernels.hip: unary_plan) leave the values
+of a multiresolution schedule -- where the launch decisions that depend on the largest patch pmax (unary_plan.cpp: unary_plan) leave the values
 they have at the workload's 40 to 90 points.
 
 Every shape is problem.pairwise_inputs(data, cp, D=...) with its default seed and warp, and the cost's range_ parameter.  Measured on the oracle
@@ -88,7 +88,7 @@ def patches(name):
 
 
 def workgroup_shares(N, L, nsplit, pptr, order):
-    """(segment, samples) of every workgroup of the sampling kernels, from the mapping at the top of k_unary_samples / k_unary_rays: workgroup b takes
+    """(segment, samples) of every workgroup of the sampling kernels, from the sampling kernels' mapping (unary.hpp: unary_workgroup_share), restated: workgroup b takes
     label range b // slots of the control point at launch position (slot & 7) * per + (slot >> 3), and appends to fix-up segment b % 64"""
     per = (N + 7) >> 3
     slots = 8 * per
