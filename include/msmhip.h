@@ -122,6 +122,11 @@ int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_t V, int32_
  * (4 x [5] are needed) that receive the cell array as stored. */
 int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
                        int64_t cells_cap);
+/* testing hook, host only: how deep in its cell's candidate list a point's triangle sits, in the order a kernel tries the candidates (the hinted first
+ * candidate, the other two of the cell, then the fourth or the four of the cell's further-candidate entry), at msm_ray_hint_check's points and with its
+ * notion of a point's triangle.  report: [0] points [1..5] points whose triangle is at position 0, 1, 2, 3, 4 [6] at position 5 or beyond [7] not listed
+ * (a point without a triangle counts in [0] only). */
+int msm_ray_depth_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8]);
 /* testing hook, host only: the certificates of the direction table's cells (one bit per sub-cell: the hinted first candidate is the answer for every
  * direction of the sub-cell, and a kernel takes it without its acceptance test), at nsamples random directions and some 10 000 placed ones: next to
  * sub-cell and cell borders and corners, cube-face edges and corners, through mesh vertices, and next to edge midpoints.  report: [0] points [1] points in a

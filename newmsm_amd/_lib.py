@@ -62,6 +62,7 @@ SIGNATURES = {
     "msm_octree_signature": (C.c_int, [c_dp, c_ip, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     "msm_ray_table_check": (C.c_int, [c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int64)]),
     "msm_ray_hint_check": (C.c_int, [c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int64), c_ip, C.c_int64]),
+    "msm_ray_depth_check": (C.c_int, [c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int64)]),
     "msm_ray_cert_check": (C.c_int, [c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int64), c_ip, C.c_int64]),
     "msm_ray_table_signature": (C.c_int, [c_dp, c_ip, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
     "msm_ctx_create": (_VP, [C.c_int]),

@@ -156,6 +156,16 @@ def ray_hint_check(xyz, tri, nsamples=20000, seed=1, return_cells=False):
     return out
 
 
+def ray_depth_check(xyz, tri, nsamples=20000, seed=1):
+    """[host] where in its cell's candidate list a point's triangle sits, in the order the kernels try the candidates (testing hook,
+    msm_ray_depth_check; the points and the triangles of ray_hint_check).  at: points by position 0, 1, 2, 3, 4 and 5 or beyond."""
+    x, px = _soa(xyz)
+    t, pt = _tri_soa(tri)
+    rep = (C.c_int64 * 8)()
+    check(lib().msm_ray_depth_check(px, pt, x.shape[1], t.shape[1], nsamples, seed, rep))
+    return dict(points=rep[0], at=[int(rep[k]) for k in range(1, 7)], unlisted=rep[7])
+
+
 def ray_cert_check(xyz, tri, nsamples=20000, seed=1, return_cells=False):
     """[host] the certificates of the direction table's cells: every sampled point of a certified sub-cell must have the sub-cell's first candidate for its
     triangle, by the FP64 edge-plane test and by the reference's leaf search (testing hook, msm_ray_cert_check).  The points are `nsamples` random directions

@@ -248,6 +248,41 @@ extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t
     return MSM_OK;
 }
 
+// Testing hook, host only: how deep in a cell's candidate list the answer sits, in the order a kernel tries the candidates: ray_cell_of(...).x (the hinted
+// first candidate), .y, .z, then .w or the four ids of the cell's ray_more entry.  The points and the answer are msm_ray_hint_check's (`nsamples` random
+// directions on the radius shell; the one triangle the reference's first pass returns, a point without one counts in [0] only).  What k_unary_rays does
+// behind a first-candidate miss is sized by these shares (unary_kernels.hip: MSM_RAY_RETRY).
+// report: [0] points, [1..5] points whose triangle is at position 0, 1, 2, 3, 4 of that order, [6] at position 5 or beyond, [7] not listed.
+extern "C" int msm_ray_depth_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8]) {
+    using namespace msm;
+    TableUnderTest u;
+    MSM_TRY(u.build("msm_ray_depth_check", xyz, tri, V, T, nsamples, seed, report, 8));
+    const FlatOctree &o = u.o;
+    const DevTree &dt = u.dt;
+    if (o.rays.G <= 0) return MSM_OK;
+    for (int it = 0; it < nsamples; ++it) {
+        const V3 p = scale(normalized(u.random_direction()), kRad);
+        ++report[0];
+        const std::vector<int> &hits = u.first_pass(p);
+        if (hits.size() != 1) continue;
+        const int answer = hits[0];
+        float fx, fy, fz;
+        const int4 c = ray_cell_of(dt, p, fx, fy, fz);
+        if (c.x < 0) continue;  // (off the shell: no cell)
+        int4 more = make_int4(c.w, -1, -1, -1);
+        if (c.w < -1) more = o.rays.more[-2 - c.w];
+        const int list[7] = {c.x, c.y, c.z, more.x, more.y, more.z, more.w};
+        int at = 7;
+        for (int k = 0; k < 7 && list[k] >= 0; ++k)
+            if (list[k] == answer) {
+                at = k;
+                break;
+            }
+        ++report[at == 7 ? 7 : 1 + std::min(at, 5)];
+    }
+    return MSM_OK;
+}
+
 // Testing hook, host only: the certificates of the direction cells (internal.hpp: kRayWBits; ray_table.cpp has the proof), point by point.  A point in a
 // certified sub-cell -- placed by ray_cell_at, as a kernel places it -- is taken by the kernels for its first candidate unseen, so that candidate must pass the FP64
 // edge-plane test at the threshold the table's proof asks for (ray_accepts_fp64 at the stored threshold less the float allowance, as the kernels' FP64 re-test

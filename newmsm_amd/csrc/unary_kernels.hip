@@ -111,6 +111,26 @@ __device__ __forceinline__ void emit_failure(const SamplesArgs &a, size_t g, int
     }
 }
 
+// What k_unary_rays does behind a first-candidate miss (a compile-time switch like MSM_RAY_HINT_K; every value gives the same table bit for bit, DESIGN.md
+// section 5.2 has all four measured: the kernel is bound by vL1D look-ups, so the value that looks up least behind a short chain wins, not the shortest chain):
+//   0  the rolled loop: the planes of one further candidate per dependent round trip, then the vertex pieces of the accepted one (the kernel as it was)
+//   1  round A -- the second candidate's planes, its vertex pieces and the cell's ray_more entry in one batch -- then the rolled loop from the third candidate on
+//   2  round A as in 1, then round T: the wavefront tests every remaining candidate of up to eight unsettled lanes in one trip, eight lanes per unsettled lane
+//   3  round A without the vertex pieces, then round T, then one reload for whatever either round accepted (the default: the fastest)
+#ifndef MSM_RAY_RETRY
+#define MSM_RAY_RETRY 3
+#endif
+static_assert(MSM_RAY_RETRY >= 0 && MSM_RAY_RETRY <= 3, "0: rolled loop, 1: round A + loop, 2: round A + team round, 3: round A (planes only) + team round");
+
+// how many lanes below this one are set in a ballot (no lane mask to keep in registers over the sample loop)
+__device__ __forceinline__ int set_below(unsigned long long m) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+#else
+    return 0;
+#endif
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
@@ -311,9 +331,37 @@ __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
 // has the proof); 0.57 of the samples of an ico6 target fall into such a sub-cell.  Their lanes are switched off for the three plane loads -- a lane
 // predicate: an inactive lane looks no line up -- and take the candidate untested; everything after acceptance is as it was, and so is every result
 // (a certificate only skips a test that would have passed).  72 VGPRs and seven waves per SIMD as before, which takes the two empty asm statements
-// in the loop and the occupancy request on the kernel (without it the retry loop's packed multiplies push the allocator to 74).  DESIGN.md section
+// in the loop and the occupancy request on the kernel (without it the retry path's packed multiplies push the allocator to 74).  DESIGN.md section
 // 5.2 has the counters.
+// Behind a first-candidate miss (one lane in ten, so nearly every wavefront round has some): the answer is the second candidate for two misses in
+// three, the third to seventh for the rest (msm_ray_depth_check).  A rolled loop over the further candidates, one dependent round trip each until the
+// deepest lane of the wavefront is served, and a last trip for the accepted candidate's vertex pieces made about six trips per round, of which four
+// served a tenth of the lanes.  Now (MSM_RAY_RETRY = 3; 0, 1 and 2 are kept for comparison) there are three: round A tests the second candidate and
+// fetches the cell's ray_more entry, round T has the wavefront test everything that is left for up to eight lanes at a time, eight helper lanes per
+// unsettled lane, by shuffles and one ballot, and one reload brings the vertex pieces of what either round accepted.  Requesting the second candidate's
+// vertex pieces with its planes (1, 2) saves that reload for two misses in three and was slower: the look-ups it adds cost more than the trip.  Same
+// tests on the same operands, so the same table; still 72 VGPRs, no scratch, seven waves per SIMD -- which is why the sample's end is text
+// (RAY_EMIT_ACCEPTED) and the unsettled list counts with mbcnt (set_below).
 // ------------------------------------------------------------------------------------------------
+// The end of a sample of k_unary_rays: the accepted triangle t (negative: none) vouched for, get_target_data's weights from the record's vertex pieces
+// d0..d5, the stores.  Text, not a function: the kernel has one end in two places (MSM_RAY_RETRY), and as a function or a lambda the same statements
+// cost it 12 bytes of scratch per lane.
+#define RAY_EMIT_ACCEPTED()                                                                                                                      \
+    if (t >= 0 && excl >= 0 && !ray_vouches(a.tree, make_float4(0.f, 0.f, 0.f, __int_as_float(excl)), p)) t = -1; /* its leaf may not list it */ \
+    if (t >= 0) {                                                                                                                                \
+        double wa, wb, wc;                                                                                                                       \
+        area_weights(mk(d0.x, d0.y, d1.x), mk(d1.y, d2.x, d2.y), mk(d3.x, d3.y, d4.x), p, wa, wb, wc);                                           \
+        const size_t g = gbase + s;                                                                                                              \
+        if (a.tval) {                                                                                                                            \
+            a.tval[g] = wa * d4.y + wb * d5.x + wc * d5.y;                                                                                       \
+        } else {                                                                                                                                 \
+            a.stri[g] = t;                                                                                                                       \
+            a.sw3[3 * g] = wa;                                                                                                                   \
+            a.sw3[3 * g + 1] = wb;                                                                                                               \
+            a.sw3[3 * g + 2] = wc;                                                                                                               \
+        }                                                                                                                                        \
+        done = true;                                                                                                                             \
+    }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k_unary_rays(SamplesArgs a) {
     extern __shared__ __align__(16) double lds[];
     double *sx = lds, *sy = sx + a.pmax, *sz = sy + a.pmax, *sR = sz + a.pmax;
@@ -360,6 +408,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
             p = rotate(sR + 9 * l, mk(sx[i], sy[i], sz[i]));
             c = ray_cell_of(a.tree, p, fx, fy, fz, cert);
         }
+        // (what a sample carries from its first candidate to its end; out here because round T runs at wave-uniform control flow)
+#if MSM_RAY_RETRY >= 2
+        int t = -1;
+        int excl = -1;  // the accepted candidate's exclusion record (its e1.w), negative: none -- as for a certified candidate
+        double2 d0, d1, d2, d3, d4, d5;
+        bool pend = false;  // unsettled behind round A, with a third candidate to try
+        bool got = false;   // settled behind the first candidate, the vertex pieces still to be fetched
+        int4 mo;
+#ifdef __HIP_DEVICE_COMPILE__
+        {  // no value on the paths that never read them, and no instruction: as for the planes below
+            typedef double v2d __attribute__((ext_vector_type(2)));
+            typedef int v4i __attribute__((ext_vector_type(4)));
+            v2d u0, u1, u2, u3, u4, u5;
+            v4i um;
+            asm volatile("" : "=v"(u0), "=v"(u1), "=v"(u2), "=v"(u3), "=v"(u4), "=v"(u5), "=v"(um));
+            d0 = make_double2(u0.x, u0.y), d1 = make_double2(u1.x, u1.y), d2 = make_double2(u2.x, u2.y);
+            d3 = make_double2(u3.x, u3.y), d4 = make_double2(u4.x, u4.y), d5 = make_double2(u5.x, u5.y);
+            mo = make_int4(um.x, um.y, um.z, um.w);
+        }
+#else
+        d0 = d1 = d2 = d3 = d4 = d5 = make_double2(0.0, 0.0);
+        mo = make_int4(-1, -1, -1, -1);
+#endif
+#endif
         if (act) {
             if (c.x >= 0) {
                 // the first candidate -- the one the cell's hint names for this sub-cell (ray_cell_of) -- is the answer nine times
@@ -370,8 +442,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                 // out the three edge-plane loads -- a lane that is switched off looks no line up -- and takes the candidate as it is.
                 // (a lane predicate: the six vertex pieces are requested in the same breath, by every lane, and nothing waits in between)
                 const double2 *dv = reinterpret_cast<const double2 *>(rec + 3);
-                int t = c.x;
+#if MSM_RAY_RETRY < 2
+                int t;
                 int excl = -1;  // the accepted candidate's exclusion record (its e1.w), negative: none -- as for a certified candidate
+                double2 d0, d1, d2, d3, d4, d5;
+#endif
+                t = c.x;
                 bool retry = false;
 #ifdef __HIP_DEVICE_COMPILE__
                 // The certified lanes never read the planes, so nothing need be written for them: the first empty statement names the
@@ -386,12 +462,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                     const v4f *rq = reinterpret_cast<const v4f *>(rec);
                     q0 = rq[0], q1 = rq[1], q2 = rq[2];
                 }
-                double2 d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
+                d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
                 if (!cert) {
                     asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
                     const float4 e0 = make_float4(q0.x, q0.y, q0.z, q0.w), e1 = make_float4(q1.x, q1.y, q1.z, q1.w), e2 = make_float4(q2.x, q2.y, q2.z, q2.w);
 #else
-                double2 d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
+                d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
                 if (!cert) {
                     const float4 e0 = rec[0], e1 = rec[1], e2 = rec[2];
 #endif
@@ -400,11 +476,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                 }
                 if (retry) {
                     t = -1;
+#if MSM_RAY_RETRY >= 2
+                    mo = make_int4(c.w, -1, -1, -1);
+#else
                     int4 mo = make_int4(c.w, -1, -1, -1);
+                    bool reload = true;  // the accepted candidate's vertex pieces are still to be fetched
+#endif
+#if MSM_RAY_RETRY >= 1
+                    // Round A: the second candidate is the answer for two misses in three (msm_ray_depth_check).  Its planes and the cell's ray_more entry
+                    // are requested together, one round trip; with MSM_RAY_RETRY 1 and 2 its vertex pieces too -- into d0..d5, whose content a retrying
+                    // lane no longer needs -- so that a lane whose second candidate passes is finished without a reload.
+                    if (c.y >= 0) {
+                        const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * c.y;
+                        const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
+#if MSM_RAY_RETRY != 3
+                        dv = reinterpret_cast<const double2 *>(r2 + 3);
+                        d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
+#endif
+                        if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
+                        if (ray_accepts(g0, g1, g2, fx, fy, fz)) {
+                            t = c.y;
+                            excl = __float_as_int(g1.w);
+#if MSM_RAY_RETRY == 3
+                            got = true;  // (its vertex pieces come with round T's)
+#endif
+                        }
+#if MSM_RAY_RETRY >= 2
+                        pend = t < 0 && c.z >= 0;  // (a list ends at its first negative id: rank_and_fill_cells packs them)
+#else
+                        reload = t < 0;
+#endif
+                    }
+#else
                     if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
+#endif
+#if MSM_RAY_RETRY < 2
                     // a real loop, not unrolled: this path is taken by one lane in ten and must not cost registers
 #pragma unroll 1
-                    for (int k = 0; k < 6 && t < 0; ++k) {
+                    for (int k = MSM_RAY_RETRY; k < 6 && t < 0; ++k) {
                         const int ck = k == 0 ? c.y : (k == 1 ? c.z : (k == 2 ? mo.x : (k == 3 ? mo.y : (k == 4 ? mo.z : mo.w))));
                         if (ck < 0) break;
                         const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * ck;
@@ -414,28 +523,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                             excl = __float_as_int(g1.w);
                         }
                     }
-                    if (t >= 0) {
+                    if (t >= 0 && reload) {
                         dv = reinterpret_cast<const double2 *>(a.tree.ray_tri + (size_t)kRayPieces * t + 3);
                         d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
                     }
+#endif
                 }
-                if (t >= 0 && excl >= 0 && !ray_vouches(a.tree, make_float4(0.f, 0.f, 0.f, __int_as_float(excl)), p)) t = -1;  // its leaf may not list the triangle
-                if (t >= 0) {
-                    double wa, wb, wc;
-                    area_weights(mk(d0.x, d0.y, d1.x), mk(d1.y, d2.x, d2.y), mk(d3.x, d3.y, d4.x), p, wa, wb, wc);
-                    const size_t g = gbase + s;
-                    if (a.tval) {
-                        a.tval[g] = wa * d4.y + wb * d5.x + wc * d5.y;
-                    } else {
-                        a.stri[g] = t;
-                        a.sw3[3 * g] = wa;
-                        a.sw3[3 * g + 1] = wb;
-                        a.sw3[3 * g + 2] = wc;
-                    }
-                    done = true;
-                }
+#if MSM_RAY_RETRY < 2
+                RAY_EMIT_ACCEPTED();
+#endif
             }
         }
+#if MSM_RAY_RETRY >= 2
+        // Round T, the team round: what is still unsettled has its remaining candidates (the third of the cell, then the four of its ray_more entry) tested
+        // together, eight lanes per unsettled lane as k_unary_fixup gives a listed sample eight lanes -- every lane of the wavefront helps, with or without
+        // a sample of its own.  Lane `sub` of a group fetches its owner's direction and candidate `sub` by shuffle, loads that candidate's planes and runs
+        // the same ray_accepts on the same operands; one ballot returns the results.  At most one listed candidate passes, so the first set bit of a
+        // group's byte is what the rolled loop would have found.  Eight unsettled lanes are served per pass (a second pass: about 5e-4 of the wavefront
+        // rounds with certificates, routinely without).  No LDS.
+        for (unsigned long long want = __ballot(pend); want != 0ull;) {
+            const int grp = lane >> 3, sub = lane & 7;
+            int owner = -1;
+            unsigned long long rest = want;  // (wave-uniform: scalar code)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int o = __ffsll((long long)rest) - 1;  // -1 once `rest` is empty
+                if (grp == i) owner = o;
+                rest &= rest - 1ull;
+            }
+            const int from = owner < 0 ? lane : owner;
+            const float ox = __shfl(fx, from, 64), oy = __shfl(fy, from, 64), oz = __shfl(fz, from, 64);
+            const int k0 = __shfl(c.z, from, 64), k1 = __shfl(mo.x, from, 64), k2 = __shfl(mo.y, from, 64), k3 = __shfl(mo.z, from, 64), k4 = __shfl(mo.w, from, 64);
+            int ck = sub == 0 ? k0 : (sub == 1 ? k1 : (sub == 2 ? k2 : (sub == 3 ? k3 : (sub == 4 ? k4 : -1))));
+            if (owner < 0) ck = -1;
+            bool ok = false;
+            int ex = -1;
+            if (ck >= 0) {
+                const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * ck;
+                const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
+                ok = ray_accepts(g0, g1, g2, ox, oy, oz);
+                ex = __float_as_int(g1.w);
+            }
+            const unsigned long long hit = __ballot(ok);
+            const int rank = set_below(want);
+            const bool served = pend && rank < 8;
+            const unsigned byte = served ? (unsigned)(hit >> (8 * rank)) & 0xffu : 0u;
+            const int helper = byte ? 8 * rank + __ffs((int)byte) - 1 : lane;
+            const int hck = __shfl(ck, helper, 64), hex = __shfl(ex, helper, 64);
+            if (byte) t = hck, excl = hex, got = true;
+            if (served) pend = false;
+            want = rest;
+        }
+        // the reload: the vertex pieces of a candidate accepted in round T (MSM_RAY_RETRY 3: or in round A)
+        if (got) {
+            const double2 *dv = reinterpret_cast<const double2 *>(a.tree.ray_tri + (size_t)kRayPieces * t + 3);
+            d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
+        }
+        if (act) {
+            RAY_EMIT_ACCEPTED();
+        }
+#endif
         const bool left = act && !done;
         const unsigned long long bal = __ballot(left);
         if (bal) {
@@ -443,7 +590,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
             int base = 0;
             if (lane == leader) base = atomicAdd(&s_nleft, __popcll(bal));
             base = __shfl(base, leader, 64);
-            if (left) sleft[base + __popcll(bal & ((1ull << lane) - 1ull))] = s;
+            if (left) sleft[base + set_below(bal)] = s;
         }
     }
     __syncthreads();
@@ -468,6 +615,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
         }
     }
 }
+#undef RAY_EMIT_ACCEPTED
 
 // The listed samples, eight lanes each.  The list is short (a few per cent of the samples at most), so what
 // counts is the length of one wavefront's dependent chain, not throughput: with a lane per sample the exact
