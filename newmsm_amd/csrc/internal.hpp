@@ -69,13 +69,11 @@ constexpr int kRayPieces = 9;
 // gnomonic triangle holds the sub-cell's centre, 0 = the stored order.  They ride in the top 6 bits of x, y, z -- word
 // su (x, y, z for su = 0, 1, 2), bits 26 + 2 sv -- above a 26-bit two's-complement id (-1 = none; w holds an id, -1 or the
 // ray_more reference in its low 23 bits, see the certificates below). The order of trial cannot change a result: at most one listed candidate
-// passes the acceptance test (ray_table.cpp).  kRayHintK = 1: no hints are written and none are read.
-#ifndef MSM_RAY_HINT_K
-#define MSM_RAY_HINT_K 3
-#endif
-constexpr int kRayHintK = MSM_RAY_HINT_K;
-static_assert(kRayHintK >= 1 && kRayHintK <= 3, "two bits per sub-cell, three sub-cells per word, three words");
+// passes the acceptance test (ray_table.cpp).  The cut is 3 x 3 and no parameter: the certificates below give the same nine sub-cells
+// a bit each, at 3 su + sv.
+constexpr int kRayHintK = 3;
 constexpr int kRayIdBits = 26;
+static_assert(kRayHintK == 3 && kRayIdBits + 2 * kRayHintK == 32, "3 x 3 sub-cells: a hint word per su (x, y, z), three two-bit fields above its id");
 // Certificates.  The fourth word gives its top nine bits to one bit per sub-cell, bit kRayWBits + 3 su + sv: "the candidate this
 // sub-cell's hint names passes the acceptance test for every direction of the sub-cell, and needs no vouching" (ray_table.cpp:
 // build_ray_table has the proof), so a kernel may take that candidate without loading its edge planes.  Below them w keeps what it held
@@ -84,7 +82,7 @@ constexpr int kRayIdBits = 26;
 // kRayMaxMore = 2^22 - 2 entries (its references would leave the field) gets none either -- with four candidates listed per entry
 // no mesh below the first limit comes near the second.  MSMHIP_RAY_CERTS=off writes all nine bits as zero.
 constexpr int kRayWBits = 23;
-static_assert(kRayWBits + 9 == 32 && kRayWBits <= kRayIdBits, "nine certificate bits above the fourth word's field");
+static_assert(kRayWBits + kRayHintK * kRayHintK == 32 && kRayWBits <= kRayIdBits, "nine certificate bits, one per sub-cell, above the fourth word's field");
 constexpr int kRayMaxTris = 1 << (kRayWBits - 1);  // a mesh with more triangles gets no table (build_ray_table)
 constexpr int kRayMaxMore = (1 << (kRayWBits - 1)) - 2;
 

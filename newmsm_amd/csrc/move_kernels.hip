@@ -45,14 +45,6 @@ __device__ __forceinline__ void raise_both(const CliqueArgs &a, const MoveArgs &
     __hip_atomic_store(m.host_flags, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// s / P for 0 <= s < 2^22, P > 0, with a float reciprocal and an exact correction step
-__device__ __forceinline__ int fast_div(int s, int P, float invP) {
-    int q = (int)((float)s * invP);
-    if (q * P > s) --q;
-    else if ((q + 1) * P <= s) ++q;
-    return q;
-}
-
 // position of a bin point for a proposed triangle (n0, n1, n2 = g[0..9)): HO*::get_target_data :506-510 / :584-590 from
 // the point's barycentric coordinates in the current control triangle
 __device__ __forceinline__ V3 moved_point(const double *g, double wa, double wb, double wc) {
@@ -102,9 +94,7 @@ __device__ __forceinline__ int ray_find_rec(const DevTree &T, const V3 &p, doubl
         if (t >= 0) {
             dv = reinterpret_cast<const double2 *>(T.ray_tri + (size_t)kRayPieces * t + 3);
             d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
-        }
-#ifndef MSM_MOVE_NO_FP64_RETEST  // (diagnostics: the kernel without this step)
-        else if (near_a >= 0) {
+        } else if (near_a >= 0) {
             // No candidate passed in float: 3e-6 of the stored threshold are the float evaluation's allowance, thirty times the margin the
             // proof needs (octree.cpp: build_ray_table).  The (at most two) candidates the float test nearly accepted are looked at again
             // with FP64 edge planes from the record's vertices, which leaves open one sample in 15 000 instead of one in 1 000 -- and with
@@ -133,7 +123,6 @@ __device__ __forceinline__ int ray_find_rec(const DevTree &T, const V3 &p, doubl
                 }
             }
         }
-#endif
     }
     if (t >= 0 && __float_as_int(ev.w) >= 0 && !ray_vouches(T, ev, p)) t = -1;  // its leaf may not list the triangle
     return t;
@@ -363,11 +352,7 @@ __global__ __launch_bounds__(kThreads) void k_ho_move(CliqueArgs a, MoveArgs m, 
     // ---- the samples the direction table left open (0.2 %): the octree leaf's candidates, eight lanes per sample
     // (search_device.hpp: group8_find); what even that cannot decide (no candidate in the leaf: sibling leaves, nearest vertex)
     // is left to the tail kernel, which the host launches only when told to
-#ifdef MSM_MOVE_SKIP_OPEN  // diagnostics (WRONG results): what the leaf search of the open samples costs the launch -- 1: no workgroup runs it, 2: one in 32 does
-    const int npend = ((MSM_MOVE_SKIP_OPEN == 2 && (blockIdx.x & 31) == 0) || m.cap < 0) ? s_npend : 0;  // (cap < 0 never holds: keeps the code in)
-#else
     const int npend = s_npend;
-#endif
     // the strain of the 64 evaluations (a chain of some hundred dependent FP64 operations that only needs the proposed triangles) is
     // computed by the last wavefront here, while the first ones search for the open samples and then start on the similarities:
     // it used to follow the similarity in every evaluation's lane, 2 us of the 4.3 us last phase

@@ -617,10 +617,8 @@ void build_ray_table(const double *xyz, const int32_t *tri, int V, int T, FlatOc
     TICK("bucket");
     if (!rank_and_fill_cells(b, cand, count)) return;
     TICK("cells");
-    if (kRayHintK > 1) {
-        hints(b);
-        TICK("hints");
-    }
+    hints(b);
+    TICK("hints");
     certificates(b);
     TICK("certs");
 }

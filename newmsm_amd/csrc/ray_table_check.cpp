@@ -2,6 +2,7 @@
 // point against the reference's own search, and a signature of the whole table.  A hook builds the tree and the table of the mesh it is given and looks at
 // them through the very functions the kernels call (search_device.hpp, which also compiles for the host).
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 
@@ -66,6 +67,20 @@ struct TableUnderTest {
             if (point_in_triangle(project_point(p, a, b, c), a, b, c)) hits.push_back(t);
         }
         return hits;
+    }
+    // the next point of msm_ray_hint_check and msm_ray_depth_check: a random direction on the radius shell, and the one triangle the reference's first pass
+    // returns for it (-1: none, or several)
+    int random_point(V3 &p) {
+        p = scale(normalized(random_direction()), kRad);
+        const std::vector<int> &h = first_pass(p);
+        return h.size() == 1 ? h[0] : -1;
+    }
+    // A cell's candidates in the order a kernel tries them: x, y, z, then w or, where w refers to one, the four ids of the cell's ray_more entry; the first
+    // negative id ends the list.  c: the cell as ray_cell_of hands it out (the hinted candidate first), or its stored ids (ray_cell_ids).
+    std::array<int, 7> candidates(const int4 &c) const {
+        int4 more = make_int4(c.w, -1, -1, -1);
+        if (c.x >= 0 && c.w < -1) more = o.rays.more[-2 - c.w];
+        return {c.x, c.y, c.z, more.x, more.y, more.z, more.w};
     }
     // the cell array as stored into cells (may be NULL: nothing to do), when cells_cap words hold it
     int copy_cells(int32_t *cells, int64_t cells_cap) const {
@@ -154,9 +169,7 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
         float fx, fy, fz;
         bool cert;
         const int4 cell = ray_cell_of(dt, p, fx, fy, fz, cert);
-        int4 more = make_int4(cell.w, -1, -1, -1);
-        if (cell.x >= 0 && cell.w < -1) more = o.rays.more[-2 - cell.w];
-        const int cand[7] = {cell.x, cell.y, cell.z, more.x, more.y, more.z, more.w};
+        const std::array<int, 7> cand = u.candidates(cell);
         const double pn = norm(p);
         bool by_float = false, by_fp64 = false, bad = false;
         if (cert) {  // a certified sub-cell: the kernels take the first candidate without a test (counted with the float test's)
@@ -193,7 +206,7 @@ extern "C" int msm_ray_table_check(const double *xyz, const int32_t *tri, int32_
 // report: [0] points, [1] points whose triangle is ray_cell_of(...).x, [2] points whose triangle is the cell's first stored candidate (hints ignored),
 // [3] points whose triangle is anywhere in the cell's list (ray_more included), [4] CELLS WHOSE DECODED CANDIDATES DIFFER FROM THE STORED ONES in some
 // sub-cell (must be 0: the same ids, the others in their stored order, a ray_more reference where it was, a first candidate whenever there is one),
-// [5] cells, [6] cells that use ray_more, [7] kRayHintK.  cells (may be NULL): the cell array as stored, 4 x [5] words, when cells_cap holds it.
+// [5] cells, [6] cells that use ray_more, [7] kRayHintK (3).  cells (may be NULL): the cell array as stored, 4 x [5] words, when cells_cap holds it.
 extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8], int32_t *cells,
                                   int64_t cells_cap) {
     using namespace msm;
@@ -224,11 +237,10 @@ extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t
         if (!same) ++report[4];
     }
     for (int it = 0; it < nsamples; ++it) {
-        const V3 p = scale(normalized(u.random_direction()), kRad);
+        V3 p;
+        const int answer = u.random_point(p);
         ++report[0];
-        const std::vector<int> &hits = u.first_pass(p);
-        if (hits.size() != 1) continue;
-        const int answer = hits[0];
+        if (answer < 0) continue;
         float fx, fy, fz;
         size_t at;
         int su, sv;
@@ -236,14 +248,8 @@ extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t
         const int4 first = ray_cell_of(dt, p, fx, fy, fz), ids = ray_cell_ids(o.rays.cell[at]);
         if (first.x == answer) ++report[1];
         if (ids.x == answer) ++report[2];
-        int4 more = make_int4(ids.w, -1, -1, -1);
-        if (ids.x >= 0 && ids.w < -1) more = o.rays.more[-2 - ids.w];
-        const int list[7] = {ids.x, ids.y, ids.z, more.x, more.y, more.z, more.w};
-        for (int k = 0; k < 7; ++k)
-            if (list[k] == answer) {
-                ++report[3];
-                break;
-            }
+        const std::array<int, 7> list = u.candidates(ids);
+        if (std::find(list.begin(), list.end(), answer) != list.end()) ++report[3];
     }
     return MSM_OK;
 }
@@ -251,7 +257,7 @@ extern "C" int msm_ray_hint_check(const double *xyz, const int32_t *tri, int32_t
 // Testing hook, host only: how deep in a cell's candidate list the answer sits, in the order a kernel tries the candidates: ray_cell_of(...).x (the hinted
 // first candidate), .y, .z, then .w or the four ids of the cell's ray_more entry.  The points and the answer are msm_ray_hint_check's (`nsamples` random
 // directions on the radius shell; the one triangle the reference's first pass returns, a point without one counts in [0] only).  What k_unary_rays does
-// behind a first-candidate miss is sized by these shares (unary_kernels.hip: MSM_RAY_RETRY).
+// behind a first-candidate miss is sized by these shares (unary_kernels.hip: round A, round T).
 // report: [0] points, [1..5] points whose triangle is at position 0, 1, 2, 3, 4 of that order, [6] at position 5 or beyond, [7] not listed.
 extern "C" int msm_ray_depth_check(const double *xyz, const int32_t *tri, int32_t V, int32_t T, int32_t nsamples, uint64_t seed, int64_t report[8]) {
     using namespace msm;
@@ -261,17 +267,14 @@ extern "C" int msm_ray_depth_check(const double *xyz, const int32_t *tri, int32_
     const DevTree &dt = u.dt;
     if (o.rays.G <= 0) return MSM_OK;
     for (int it = 0; it < nsamples; ++it) {
-        const V3 p = scale(normalized(u.random_direction()), kRad);
+        V3 p;
+        const int answer = u.random_point(p);
         ++report[0];
-        const std::vector<int> &hits = u.first_pass(p);
-        if (hits.size() != 1) continue;
-        const int answer = hits[0];
+        if (answer < 0) continue;
         float fx, fy, fz;
         const int4 c = ray_cell_of(dt, p, fx, fy, fz);
         if (c.x < 0) continue;  // (off the shell: no cell)
-        int4 more = make_int4(c.w, -1, -1, -1);
-        if (c.w < -1) more = o.rays.more[-2 - c.w];
-        const int list[7] = {c.x, c.y, c.z, more.x, more.y, more.z, more.w};
+        const std::array<int, 7> list = u.candidates(c);
         int at = 7;
         for (int k = 0; k < 7 && list[k] >= 0; ++k)
             if (list[k] == answer) {
@@ -339,7 +342,7 @@ extern "C" int msm_ray_cert_check(const double *xyz, const int32_t *tri, int32_t
     const double cellw = 2.0 / G;
     auto nudge = [&]() { return rnd() < 0.2 ? 0.0 : (rnd() < 0.5 ? -1.0 : 1.0) * 1e-6 * rnd() * cellw; };
     auto border = [&](bool cell_border) {  // a coordinate next to a sub-cell border (or a cell border) of a random cell
-        const int i = (int)(rnd() * G) % G, s = cell_border ? 0 : 1 + (int)(rnd() * (kRayHintK - 1)) % std::max(1, kRayHintK - 1);
+        const int i = (int)(rnd() * G) % G, s = cell_border ? 0 : 1 + (int)(rnd() * (kRayHintK - 1)) % (kRayHintK - 1);
         return -1 + 2.0 * (i + (double)s / kRayHintK) / G + nudge();
     };
     auto rim = [&]() { return (rnd() < 0.5 ? -1.0 : 1.0) + nudge(); };

@@ -23,6 +23,14 @@
 
 namespace msm {
 
+// s / P for 0 <= s < 2^22, P > 0, with a float reciprocal and an exact correction step
+__device__ __forceinline__ int fast_div(int s, int P, float invP) {
+    int q = (int)((float)s * invP);
+    if (q * P > s) --q;
+    else if ((q + 1) * P <= s) ++q;
+    return q;
+}
+
 struct ScanState {
     int best;      // winning triangle so far, -1 = EMPTY_TRIANGLE
     int have_d;    // bestd holds dist_to_point of `best`
@@ -62,19 +70,16 @@ MSM_HD float ray_rsqrt(float x) {
 MSM_HD int ray_cell_id(int word) { return (int)((unsigned)word << (32 - kRayIdBits)) >> (32 - kRayIdBits); }
 MSM_HD int4 ray_cell_ids(const int4 &raw) {
     const int w = (int)((unsigned)raw.w << (32 - kRayWBits)) >> (32 - kRayWBits);  // (the certificates sit above it)
-    if (kRayHintK == 1) return make_int4(raw.x, raw.y, raw.z, w);
     return make_int4(ray_cell_id(raw.x), ray_cell_id(raw.y), ray_cell_id(raw.z), w);
 }
 // the certificate of a sub-cell (internal.hpp: kRayWBits): its hinted candidate is the answer for every direction in it
 MSM_HD bool ray_cell_cert(const int4 &raw, int su, int sv) { return (((unsigned)raw.w >> (kRayWBits + 3 * su + sv)) & 1u) != 0u; }
 MSM_HD int ray_cell_hint(const int4 &raw, int su, int sv) {
-    if (kRayHintK == 1) return 0;
     const unsigned word = (unsigned)(su == 0 ? raw.x : (su == 1 ? raw.y : raw.z));
     return (int)((word >> (kRayIdBits + 2 * sv)) & 3u);
 }
 MSM_HD int4 ray_cell_first(const int4 &raw, int h) {
     const int4 c = ray_cell_ids(raw);
-    if (kRayHintK == 1) return c;
     return make_int4(h == 0 ? c.x : (h == 1 ? c.y : (h == 2 ? c.z : c.w)), h >= 1 ? c.x : c.y, h >= 2 ? c.y : c.z, h == 3 ? c.z : c.w);
 }
 // the cell of p and the sub-cell of p in it; false when p is off the shell (fx = fy = fz = 0 then)
@@ -117,12 +122,10 @@ MSM_HD int4 ray_cell_of(const DevTree &T, const V3 &p, float &fx, float &fy, flo
 #ifdef __HIP_DEVICE_COMPILE__
     // the decoded cell in one register quadruple, as the load delivered it before there were hints: without this the allocator
     // scatters the four ids and k_unary_rays needs 74 registers instead of 72, which is a wavefront per SIMD
-    if (kRayHintK > 1) {
-        typedef int v4i __attribute__((ext_vector_type(4)));
-        v4i q = {c.x, c.y, c.z, c.w};
-        asm volatile("" : "+v"(q));
-        c = make_int4(q.x, q.y, q.z, q.w);
-    }
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    v4i q = {c.x, c.y, c.z, c.w};
+    asm volatile("" : "+v"(q));
+    c = make_int4(q.x, q.y, q.z, q.w);
 #endif
     return c;
 }

@@ -74,14 +74,6 @@ struct SamplesArgs {
     int *status;
 };
 
-// s / P for 0 <= s < 2^22, P > 0, with a float reciprocal and an exact correction step
-__device__ __forceinline__ int fast_div(int s, int P, float invP) {
-    int q = (int)((float)s * invP);
-    if (q * P > s) --q;
-    else if ((q + 1) * P <= s) ++q;
-    return q;
-}
-
 // get_target_data's tail (:361-375): barycentric_interpolation on the raw (un-projected) point
 __device__ __forceinline__ double emit_sample(const SamplesArgs &a, size_t g, const V3 &p, int t) {
     const TriRec &r = a.tree.rec[t];
@@ -110,17 +102,6 @@ __device__ __forceinline__ void emit_failure(const SamplesArgs &a, size_t g, int
         a.sw3[3 * g] = a.sw3[3 * g + 1] = a.sw3[3 * g + 2] = nan;
     }
 }
-
-// What k_unary_rays does behind a first-candidate miss (a compile-time switch like MSM_RAY_HINT_K; every value gives the same table bit for bit, DESIGN.md
-// section 5.2 has all four measured: the kernel is bound by vL1D look-ups, so the value that looks up least behind a short chain wins, not the shortest chain):
-//   0  the rolled loop: the planes of one further candidate per dependent round trip, then the vertex pieces of the accepted one (the kernel as it was)
-//   1  round A -- the second candidate's planes, its vertex pieces and the cell's ray_more entry in one batch -- then the rolled loop from the third candidate on
-//   2  round A as in 1, then round T: the wavefront tests every remaining candidate of up to eight unsettled lanes in one trip, eight lanes per unsettled lane
-//   3  round A without the vertex pieces, then round T, then one reload for whatever either round accepted (the default: the fastest)
-#ifndef MSM_RAY_RETRY
-#define MSM_RAY_RETRY 3
-#endif
-static_assert(MSM_RAY_RETRY >= 0 && MSM_RAY_RETRY <= 3, "0: rolled loop, 1: round A + loop, 2: round A + team round, 3: round A (planes only) + team round");
 
 // how many lanes below this one are set in a ballot (no lane mask to keep in registers over the sample loop)
 __device__ __forceinline__ int set_below(unsigned long long m) {
@@ -335,33 +316,13 @@ __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
 // 5.2 has the counters.
 // Behind a first-candidate miss (one lane in ten, so nearly every wavefront round has some): the answer is the second candidate for two misses in
 // three, the third to seventh for the rest (msm_ray_depth_check).  A rolled loop over the further candidates, one dependent round trip each until the
-// deepest lane of the wavefront is served, and a last trip for the accepted candidate's vertex pieces made about six trips per round, of which four
-// served a tenth of the lanes.  Now (MSM_RAY_RETRY = 3; 0, 1 and 2 are kept for comparison) there are three: round A tests the second candidate and
-// fetches the cell's ray_more entry, round T has the wavefront test everything that is left for up to eight lanes at a time, eight helper lanes per
-// unsettled lane, by shuffles and one ballot, and one reload brings the vertex pieces of what either round accepted.  Requesting the second candidate's
-// vertex pieces with its planes (1, 2) saves that reload for two misses in three and was slower: the look-ups it adds cost more than the trip.  Same
-// tests on the same operands, so the same table; still 72 VGPRs, no scratch, seven waves per SIMD -- which is why the sample's end is text
-// (RAY_EMIT_ACCEPTED) and the unsettled list counts with mbcnt (set_below).
+// deepest lane of the wavefront is served, and a last trip for the accepted candidate's vertex pieces would make about six trips per round, of which
+// four serve a tenth of the lanes.  The kernel makes three: round A tests the second candidate and fetches the cell's ray_more entry, round T has the
+// wavefront test everything that is left for up to eight lanes at a time, eight helper lanes per unsettled lane, by shuffles and one ballot, and one
+// reload brings the vertex pieces of what either round accepted.  The tests and their operands are the rolled loop's, so the table is the same bit for
+// bit; 72 VGPRs, no scratch, seven waves per SIMD -- which is why the unsettled list counts with mbcnt (set_below).  DESIGN.md section 5.2 has what else
+// was measured and lost: the rolled loop itself, and the second candidate's vertex pieces requested with its planes, before and without round T.
 // ------------------------------------------------------------------------------------------------
-// The end of a sample of k_unary_rays: the accepted triangle t (negative: none) vouched for, get_target_data's weights from the record's vertex pieces
-// d0..d5, the stores.  Text, not a function: the kernel has one end in two places (MSM_RAY_RETRY), and as a function or a lambda the same statements
-// cost it 12 bytes of scratch per lane.
-#define RAY_EMIT_ACCEPTED()                                                                                                                      \
-    if (t >= 0 && excl >= 0 && !ray_vouches(a.tree, make_float4(0.f, 0.f, 0.f, __int_as_float(excl)), p)) t = -1; /* its leaf may not list it */ \
-    if (t >= 0) {                                                                                                                                \
-        double wa, wb, wc;                                                                                                                       \
-        area_weights(mk(d0.x, d0.y, d1.x), mk(d1.y, d2.x, d2.y), mk(d3.x, d3.y, d4.x), p, wa, wb, wc);                                           \
-        const size_t g = gbase + s;                                                                                                              \
-        if (a.tval) {                                                                                                                            \
-            a.tval[g] = wa * d4.y + wb * d5.x + wc * d5.y;                                                                                       \
-        } else {                                                                                                                                 \
-            a.stri[g] = t;                                                                                                                       \
-            a.sw3[3 * g] = wa;                                                                                                                   \
-            a.sw3[3 * g + 1] = wb;                                                                                                               \
-            a.sw3[3 * g + 2] = wc;                                                                                                               \
-        }                                                                                                                                        \
-        done = true;                                                                                                                             \
-    }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k_unary_rays(SamplesArgs a) {
     extern __shared__ __align__(16) double lds[];
     double *sx = lds, *sy = sx + a.pmax, *sz = sy + a.pmax, *sR = sz + a.pmax;
@@ -409,7 +370,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
             c = ray_cell_of(a.tree, p, fx, fy, fz, cert);
         }
         // (what a sample carries from its first candidate to its end; out here because round T runs at wave-uniform control flow)
-#if MSM_RAY_RETRY >= 2
         int t = -1;
         int excl = -1;  // the accepted candidate's exclusion record (its e1.w), negative: none -- as for a certified candidate
         double2 d0, d1, d2, d3, d4, d5;
@@ -431,7 +391,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
         d0 = d1 = d2 = d3 = d4 = d5 = make_double2(0.0, 0.0);
         mo = make_int4(-1, -1, -1, -1);
 #endif
-#endif
         if (act) {
             if (c.x >= 0) {
                 // the first candidate -- the one the cell's hint names for this sub-cell (ray_cell_of) -- is the answer nine times
@@ -442,11 +401,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                 // out the three edge-plane loads -- a lane that is switched off looks no line up -- and takes the candidate as it is.
                 // (a lane predicate: the six vertex pieces are requested in the same breath, by every lane, and nothing waits in between)
                 const double2 *dv = reinterpret_cast<const double2 *>(rec + 3);
-#if MSM_RAY_RETRY < 2
-                int t;
-                int excl = -1;  // the accepted candidate's exclusion record (its e1.w), negative: none -- as for a certified candidate
-                double2 d0, d1, d2, d3, d4, d5;
-#endif
                 t = c.x;
                 bool retry = false;
 #ifdef __HIP_DEVICE_COMPILE__
@@ -476,65 +430,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                 }
                 if (retry) {
                     t = -1;
-#if MSM_RAY_RETRY >= 2
                     mo = make_int4(c.w, -1, -1, -1);
-#else
-                    int4 mo = make_int4(c.w, -1, -1, -1);
-                    bool reload = true;  // the accepted candidate's vertex pieces are still to be fetched
-#endif
-#if MSM_RAY_RETRY >= 1
                     // Round A: the second candidate is the answer for two misses in three (msm_ray_depth_check).  Its planes and the cell's ray_more entry
-                    // are requested together, one round trip; with MSM_RAY_RETRY 1 and 2 its vertex pieces too -- into d0..d5, whose content a retrying
-                    // lane no longer needs -- so that a lane whose second candidate passes is finished without a reload.
+                    // are requested together, one round trip; its vertex pieces are not (the look-ups they add cost more than the reload they save).
                     if (c.y >= 0) {
                         const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * c.y;
                         const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
-#if MSM_RAY_RETRY != 3
-                        dv = reinterpret_cast<const double2 *>(r2 + 3);
-                        d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
-#endif
                         if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
                         if (ray_accepts(g0, g1, g2, fx, fy, fz)) {
                             t = c.y;
                             excl = __float_as_int(g1.w);
-#if MSM_RAY_RETRY == 3
                             got = true;  // (its vertex pieces come with round T's)
-#endif
                         }
-#if MSM_RAY_RETRY >= 2
                         pend = t < 0 && c.z >= 0;  // (a list ends at its first negative id: rank_and_fill_cells packs them)
-#else
-                        reload = t < 0;
-#endif
                     }
-#else
-                    if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
-#endif
-#if MSM_RAY_RETRY < 2
-                    // a real loop, not unrolled: this path is taken by one lane in ten and must not cost registers
-#pragma unroll 1
-                    for (int k = MSM_RAY_RETRY; k < 6 && t < 0; ++k) {
-                        const int ck = k == 0 ? c.y : (k == 1 ? c.z : (k == 2 ? mo.x : (k == 3 ? mo.y : (k == 4 ? mo.z : mo.w))));
-                        if (ck < 0) break;
-                        const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * ck;
-                        const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
-                        if (ray_accepts(g0, g1, g2, fx, fy, fz)) {
-                            t = ck;
-                            excl = __float_as_int(g1.w);
-                        }
-                    }
-                    if (t >= 0 && reload) {
-                        dv = reinterpret_cast<const double2 *>(a.tree.ray_tri + (size_t)kRayPieces * t + 3);
-                        d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
-                    }
-#endif
                 }
-#if MSM_RAY_RETRY < 2
-                RAY_EMIT_ACCEPTED();
-#endif
             }
         }
-#if MSM_RAY_RETRY >= 2
         // Round T, the team round: what is still unsettled has its remaining candidates (the third of the cell, then the four of its ray_more entry) tested
         // together, eight lanes per unsettled lane as k_unary_fixup gives a listed sample eight lanes -- every lane of the wavefront helps, with or without
         // a sample of its own.  Lane `sub` of a group fetches its owner's direction and candidate `sub` by shuffle, loads that candidate's planes and runs
@@ -574,15 +486,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
             if (served) pend = false;
             want = rest;
         }
-        // the reload: the vertex pieces of a candidate accepted in round T (MSM_RAY_RETRY 3: or in round A)
+        // the reload: the vertex pieces of a candidate accepted in round A or in round T
         if (got) {
             const double2 *dv = reinterpret_cast<const double2 *>(a.tree.ray_tri + (size_t)kRayPieces * t + 3);
             d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
         }
+        // The end of a sample: the accepted triangle t (negative: none) vouched for, get_target_data's weights from the record's vertex pieces d0..d5,
+        // the stores.  (In place: hoisted into a function or a lambda the same statements cost the kernel 12 bytes of scratch per lane.)
         if (act) {
-            RAY_EMIT_ACCEPTED();
+            if (t >= 0 && excl >= 0 && !ray_vouches(a.tree, make_float4(0.f, 0.f, 0.f, __int_as_float(excl)), p)) t = -1;  // its leaf may not list it
+            if (t >= 0) {
+                double wa, wb, wc;
+                area_weights(mk(d0.x, d0.y, d1.x), mk(d1.y, d2.x, d2.y), mk(d3.x, d3.y, d4.x), p, wa, wb, wc);
+                const size_t g = gbase + s;
+                if (a.tval) {
+                    a.tval[g] = wa * d4.y + wb * d5.x + wc * d5.y;
+                } else {
+                    a.stri[g] = t;
+                    a.sw3[3 * g] = wa;
+                    a.sw3[3 * g + 1] = wb;
+                    a.sw3[3 * g + 2] = wc;
+                }
+                done = true;
+            }
         }
-#endif
         const bool left = act && !done;
         const unsigned long long bal = __ballot(left);
         if (bal) {
@@ -615,7 +542,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
         }
     }
 }
-#undef RAY_EMIT_ACCEPTED
 
 // The listed samples, eight lanes each.  The list is short (a few per cent of the samples at most), so what
 // counts is the length of one wavefront's dependent chain, not throughput: with a lane per sample the exact

@@ -1,4 +1,4 @@
-"""Cases of the tests of what k_unary_rays does behind a first-candidate miss (csrc/unary_kernels.hip: MSM_RAY_RETRY): warped targets, whose cells hold
+"""Cases of the tests of what k_unary_rays does behind a first-candidate miss (csrc/unary_kernels.hip: round A, round T and the reload): warped targets, whose cells hold
 the answer at every position of their candidate lists (tests/test_ray_depth_cpu.py has the counts), under control grids that give patches of a few
 points, of about 65 and of several hundred."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""k_unary_rays behind a first-candidate miss (csrc/unary_kernels.hip: MSM_RAY_RETRY): round A -- the second candidate's planes and the cell's further
+"""k_unary_rays behind a first-candidate miss (csrc/unary_kernels.hip): round A -- the second candidate's planes and the cell's further
 candidates in one batch -- round T, in which the wavefront tests the remaining candidates of up to eight unsettled lanes together, eight lanes each, and
 runs again while more than eight are unsettled, and the reload of the vertex pieces of what either round accepted.
 

@@ -1,5 +1,5 @@
 """Where in a direction cell's candidate list the answer sits, in the order the kernels try the candidates, through the testing hook msm_ray_depth_check
-(no GPU needed).  k_unary_rays settles a first-candidate miss in two rounds (csrc/unary_kernels.hip: MSM_RAY_RETRY): round A takes position 1, the team
+(no GPU needed).  k_unary_rays settles a first-candidate miss in two rounds (csrc/unary_kernels.hip: k_unary_rays): round A takes position 1, the team
 round positions 2 to 6.  The bounds below are the condition under which tests/test_gpu_unary_retries.py reaches every branch of both rounds on these
 meshes; measured with 200 000 directions, seed 7: at least 13 165 / 2 216 / 2 089 / 1 187 / 733 points at positions 1, 2, 3, 4 and 5 or beyond."""
 import pytest
