@@ -429,6 +429,29 @@ int msm_mcmc_draw_stats(msm_ctx *ctx, double stats[4]);
 /* [host] The level schedule of a triplet list (any list with nodes in [0, N)): level[t] (0-based), order (the T triplets by level, ascending within a
  * level), level_off (offsets into order; room for T + 1), *levels.  level / order / level_off may be NULL. */
 int msm_mcmc_schedule(const int32_t *triplets, int32_t N, int32_t T, int32_t *level, int32_t *order, int32_t *level_off, int32_t *levels);
+/* [host] AN EXTENSION (not newMSM's): max-product linear programming (MPLP; Globerson & Jaakkola 2007, Sontag et al. 2011 Fig. 1.4) over the tables
+ * msm_mcmc_optimise reads -- block-coordinate ascent on the dual of the labelling LP, deterministic, written from the published update rule; DESIGN.md
+ * 5.19 has the definition this serial literal and the GPU entry points follow bit for bit.  Messages m[t][s][x] (T x 3 x L doubles) start at 0.0; a
+ * sweep updates the factors t = 0 .. T - 1 in order; after every sweep the beliefs are decoded (argmin, lowest label on ties).  Candidate 0 is the start
+ * (labeling, N, in), candidate k the decode after sweep k; labeling receives the candidate of the first lowest msm_mcmc_energy (msm_mcmc_best's rule),
+ * so the result is never worse than the start.  The run ends after `sweeps` sweeps, or after the first sweep that leaves every message's bits as they
+ * were; *sweeps_run says how many ran.  Outputs, all optional (NULL): *energy the winner's energy; *bound the dual value D after the last sweep, which
+ * no labelling's energy lies below (up to rounding) and which never falls from sweep to sweep; energies / bounds (`sweeps` values each): the decode's
+ * energy and D after every sweep (the sweeps a fixed point spares repeat its values; untouched when no sweep ran); messages (T x 3 x L).  Asking for
+ * bounds costs a second pass over the triplet table per sweep, asking for bound alone one pass.  sweeps == 0 or T == 0: the labelling stays, *sweeps_run
+ * = 0.  Refused before anything is written: what msm_mcmc_optimise refuses, with its messages; a triplet that names a node twice (MSM_ERR_INVALID); a
+ * non-finite table entry (MSM_ERR_INVALID, the message names the table and --fixnan); L > 1024 (MSM_ERR_CAPACITY). */
+int msm_mplp_optimise(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps, int32_t *labeling,
+                      int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages);
+/* msm_mplp_optimise with the sweeps on the GPU: the same labelling, sweeps_run, energies, bounds and messages, bit for bit.  The host tables are
+ * uploaded as msm_mcmc_optimise_gpu uploads them; a sweep is one launch per level of msm_mcmc_schedule, a workgroup per factor; the terms of the
+ * energies and bounds are evaluated on the device and summed on the host in the literal's order; the finiteness check is one device pass.  Everything
+ * runs on the context's stream and the call is complete on return. */
+int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
+                          int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages);
+/* What the last msm_mplp_optimise_gpu / msm_cost_mplp_optimise on the context did: stats[0] ms in the sweeps' kernels (HIP events around every chunk
+ * of sweeps: updates, decodes, energy and bound terms), [1] levels per sweep, [2] sweeps run, [3] the widest level. */
+int msm_mplp_gpu_stats(msm_ctx *ctx, double stats[4]);
 /* [host] A STAND-IN for the binary solve of one label step of Fusion::optimize (I/Fusion/Fusion.h:198-229 hands the step to ELC's
  * reduction + FastPD, which are licence-restricted and FSL-bound: not reproduced).  Iterated conditional modes over x in {0,1}^N
  * (0: the node keeps its label, 1: it takes the proposed one) for
@@ -541,6 +564,10 @@ int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t 
  * msm_cost_triplet_table(0, T) + msm_mcmc_optimise_chains give, bit for bit. */
 int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, int32_t *labeling, int32_t *labelings,
                                   double *energies, int32_t *best);
+/* msm_mplp_optimise_gpu over the cost function's own device tables, filled as msm_cost_mcmc_optimise fills them: what msm_cost_unary_table +
+ * msm_cost_triplet_table(0, T) + msm_mplp_optimise give, bit for bit (labelling, sweeps_run, energies, bounds, messages). */
+int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies,
+                           double *bounds, double *messages);
 /* evaluateTotalCostSum :55-77: parts = {unary, pairwise, triplet} sums in the reference's serial order */
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]);
 /* Optional HIP-event timing of the sampling kernel (k_unary_rays or k_unary_samples) of each unary-table launch, recorded on the

@@ -492,6 +492,34 @@ inline void mcmc_optimise_gpu(Context &ctx, const Matrix &unary_costs, const Mat
     check(msm_mcmc_optimise_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
                                 dist_param, mciters, seed, labeling.data()));
 }
+// What an MPLP run hands back besides the labeling (msm_mplp_optimise; an extension, not newMSM's): the sweeps it ran, the energy of the labelling it
+// kept (never above the start's), the lower bound D after the last sweep, and per sweep the decode's energy and D
+struct MplpRun {
+    int32_t sweeps_run = 0;
+    double energy = 0.0, bound = 0.0;
+    std::vector<double> energies, bounds;
+};
+// max-product linear programming over the tables mcmc_optimise reads, `sweeps` sweeps from `labeling`, which becomes the best candidate; with_bounds:
+// D after every sweep too (a second pass over the triplet table per sweep)
+inline MplpRun mplp_optimise(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels, int sweeps,
+                             std::vector<int32_t> &labeling, bool with_bounds = false) {
+    MplpRun r;
+    r.energies.assign((size_t)sweeps, 0.0);
+    if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
+    check(msm_mplp_optimise(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), sweeps, labeling.data(),
+                            &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
+    return r;
+}
+// the same with the sweeps on the GPU (msm_mplp_optimise_gpu): the same labeling, energies and bounds, bit for bit
+inline MplpRun mplp_optimise_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes,
+                                 int num_labels, int sweeps, std::vector<int32_t> &labeling, bool with_bounds = false) {
+    MplpRun r;
+    r.energies.assign((size_t)sweeps, 0.0);
+    if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
+    check(msm_mplp_optimise_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), sweeps,
+                                labeling.data(), &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
+    return r;
+}
 // what several chains from one start hand back: labelings chains x N, energies per chain, best by std::min_element's rule
 struct McmcChains {
     std::vector<int32_t> labelings;
@@ -671,6 +699,16 @@ public:
         r.energies.assign(seeds.size(), 0.0);
         check(msm_cost_mcmc_optimise_chains(h_, dist_param, mciters, seeds.data(), (int32_t)seeds.size(), labeling.data(), r.labelings.data(), r.energies.data(),
                                             &r.best));
+        return r;
+    }
+    // computeUnaryCosts + computeTripletCosts + MPLP with both tables staying on the device (msm_cost_mplp_optimise): what computeUnaryCosts() +
+    // computeTripletCosts() + msmhip::mplp_optimise give, bit for bit
+    MplpRun mplp_optimise(int sweeps, std::vector<int32_t> &labeling, bool with_bounds = false) {
+        MplpRun r;
+        r.energies.assign((size_t)sweeps, 0.0);
+        if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
+        check(msm_cost_mplp_optimise(h_, sweeps, labeling.data(), &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr,
+                                     nullptr));
         return r;
     }
     // the batched forms the optimisers' loops collapse to (I/Fusion/Fusion.h:138-196)

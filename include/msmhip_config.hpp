@@ -201,7 +201,7 @@ inline IntensityNorm intensity_from_config(const Config &c) {
 // what Rigid_cost_function::set_parameters reads, M/rigid_costfunction.cpp:50-58) instead of being listed in `skipped`
 // intensity (optional; opt-in): --IN / --INc are taken instead of refused and *intensity receives what the level loops need
 inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *varnorm = nullptr, std::vector<std::pair<int, std::string>> *skipped = nullptr,
-                                                 bool anat = false, bool rigid = false, IntensityNorm *intensity = nullptr) {
+                                                 bool anat = false, bool rigid = false, IntensityNorm *intensity = nullptr, bool mplp = false) {
     if (intensity) *intensity = intensity_from_config(c);
     if ((c.IN || c.INc) && !intensity) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
     if (c.regoption == 4)  // M/mesh_registration.cpp:101-102
@@ -212,7 +212,9 @@ inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *v
     int kind;
     if (D > 1) kind = c.patchwise ? MSM_COST_PATCHWISE : (c.triclique ? MSM_COST_HO_MULTIVARIATE : MSM_COST_MULTIVARIATE);  // M/DiscreteModel.cpp:44-58
     else kind = c.triclique ? MSM_COST_HO_UNIVARIATE : MSM_COST_UNIVARIATE;
-    if (c.dopt != "HOCR" && c.dopt != "MCMC" && c.dopt != "FastPD") throw ConfigError("Unrecognized optimiser");  // M/mesh_registration.cpp:202
+    // mplp (opt-in): --dopt=MPLP, which is not newMSM's, is taken instead of refused and sets LevelOptions::mplp; like MCMC it reads triplets
+    const bool use_mplp = mplp && c.dopt == "MPLP";
+    if (c.dopt != "HOCR" && c.dopt != "MCMC" && c.dopt != "FastPD" && !use_mplp) throw ConfigError("Unrecognized optimiser");  // M/mesh_registration.cpp:202
     if (c.dopt != "FastPD" && c.regoption == 1)
         throw ConfigError("--regoption=1 (pairwise regulariser) is driven by FastPD only in the reference; Fusion / MCMC read triplets");
     if (varnorm) *varnorm = c.VN;
@@ -235,7 +237,7 @@ inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *v
         lv.data_order = c.datagrid[i], lv.cp_order = c.CPgrid[i], lv.sigma_in = c.sigma_in[i], lv.sigma_ref = c.sigma_ref[i];
         LevelOptions &o = lv.options;
         o.sg_order = c.SGgrid[i], o.iters = c.it[i], o.mciters = c.mciters[i], o.mcparam = c.mcparam, o.rescale_labels = c.rescaleL;
-        o.fusion = c.dopt == "HOCR", o.pairwise = c.dopt == "FastPD";
+        o.fusion = c.dopt == "HOCR", o.pairwise = c.dopt == "FastPD", o.mplp = use_mplp;
         o.anat_order = i < c.anatgrid.size() ? c.anatgrid[i] : c.CPgrid[i] + 2;
         o.cost.kind = kind, o.cost.simmeasure = c.simval[i], o.cost.regularisermode = c.regoption, o.cost.lambda = c.lambda[i];
         o.cost.shearmodulus = c.shearmod, o.cost.bulkmodulus = c.bulkmod, o.cost.kexponent = c.k_exponent, o.cost.exponent = c.regexp;

@@ -57,6 +57,9 @@ struct LevelOptions {
     // licence-restricted binary solve (msm_fusion_icm_step, icm_passes passes): the path is exercised as HOCR would, the result is not HOCR's
     bool fusion = false;
     int icm_passes = 5;
+    // true (an extension, not newMSM's; what --dopt=MPLP asks for under MSMHIP_MPLP=on): max-product linear programming over the MCMC optimiser's two
+    // tables, mciters sweeps per iteration from the zero labelling (DiscreteCostFunction::mplp_optimise: the tables stay on the device)
+    bool mplp = false;
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
@@ -189,8 +192,9 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
         if (o.pairwise) costfct.setPairs(pairs);
         else costfct.setTriplets(triplets);
         ++m_iter;
-        const bool mcmc_gpu = o.mcmc_gpu && !o.fusion && !o.pairwise;
-        if (!mcmc_gpu) PhaseClock::timed(clock, "unary_table", [&] { costfct.computeUnaryCosts(); });
+        const bool mplp = o.mplp && !o.fusion && !o.pairwise;
+        const bool mcmc_gpu = o.mcmc_gpu && !o.fusion && !o.pairwise && !mplp;
+        if (!mcmc_gpu && !mplp) PhaseClock::timed(clock, "unary_table", [&] { costfct.computeUnaryCosts(); });
         std::vector<int32_t> labeling((size_t)N, 0);  // resetLabeling
         const int L = (int)(labels.size() / 3), T = (int)(triplets.size() / 3);
         if (o.fusion) {  // ---- Fusion::optimize: two sweeps over the labels, a fusion move per label step
@@ -234,6 +238,8 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
         } else if (o.pairwise) {  // ---- FastPD: computeUnaryCosts, computePairwiseCosts, the solve
             PhaseClock::timed(clock, "pairwise_table", [&] { costfct.computePairwiseCosts(); });
             PhaseClock::timed(clock, "optimiser", [&] { pairwise_icm(costfct.unarycosts, costfct.paircosts, pairs, N, L, labeling, 100); });
+        } else if (mplp) {  // ---- MPLP with the tables and the sweeps on the device
+            PhaseClock::timed(clock, "optimiser", [&] { costfct.mplp_optimise(o.mciters, labeling); });
         } else if (mcmc_gpu) {  // ---- MCMC with the tables and the sweeps on the device: the labeling of the branch below
             if (o.mcmc_chains > 1)
                 PhaseClock::timed(clock, "optimiser", [&] { costfct.mcmc_optimise_chains(o.mcparam, o.mciters, mcmc_chain_seeds(o.seed + (uint64_t)it, o.mcmc_chains), labeling); });

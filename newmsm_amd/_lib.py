@@ -134,6 +134,9 @@ SIGNATURES = {
     "msm_mcmc_proposals_mirror_counted": (C.c_int, [C.c_int32, C.c_double, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint64)]),
     "msm_mcmc_draw_gpu": (C.c_int, [_VP, C.c_int32, C.c_double, C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, C.POINTER(C.c_uint16)]),
     "msm_mcmc_draw_stats": (C.c_int, [_VP, c_dp]),
+    "msm_mplp_optimise": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "msm_mplp_optimise_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "msm_mplp_gpu_stats": (C.c_int, [_VP, c_dp]),
     "msm_fusion_icm_step": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_pairwise_icm": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_nearest_neighbour": (C.c_int, [_VP, c_dp, C.c_int32, c_dp, C.c_int32, c_dp, c_dp, c_dp]),
@@ -165,6 +168,7 @@ SIGNATURES = {
     "msm_cost_triplet_table": (C.c_int, [_VP, C.c_int32, C.c_int32, c_dp]),
     "msm_cost_mcmc_optimise": (C.c_int, [_VP, C.c_double, C.c_int32, C.c_uint64, c_ip]),
     "msm_cost_mcmc_optimise_chains": (C.c_int, [_VP, C.c_double, C.c_int32, C.POINTER(C.c_uint64), C.c_int32, c_ip, c_ip, c_dp, c_ip]),
+    "msm_cost_mplp_optimise": (C.c_int, [_VP, C.c_int32, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "msm_cost_total": (C.c_int, [_VP, c_ip, c_dp, c_dp]),
     "msm_cost_enable_timing": (C.c_int, [_VP, C.c_int]),
     "msm_cost_kernel_times": (C.c_int, [_VP, c_dp, C.c_int32, c_ip]),

@@ -6,6 +6,7 @@ DiscreteCostFunction (/root/reference/libraries/msm-newmeshreg/src/DiscreteCostF
 :161-209).  Points are (N,3) numpy arrays here; the ABI's 3 x N SoA layout is produced at the boundary.
 This module is plumbing for tests and bench.py -- all computation happens in libmsmhip.so.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -758,6 +759,64 @@ def mcmc_optimise_gpu(ctx, unary, tcosts, triplets, labeling, mcparam=0.8, iters
     return lab
 
 
+MplpResult = collections.namedtuple("MplpResult", "labeling sweeps_run energy bound energies bounds messages")
+
+
+def _mplp_outputs(N, L, T, sweeps, labeling, bound, bounds, messages):
+    """the arrays of one MPLP call and the tail of its argument list (labeling .. messages); what is not asked for travels as NULL and comes back None"""
+    out = dict(lab=np.array(labeling, dtype=np.int32), run=C.c_int32(-1), energy=C.c_double(np.nan), bound=C.c_double(np.nan) if bound or bounds else None,
+               energies=np.full(int(sweeps), np.nan), bounds=np.full(int(sweeps), np.nan) if bounds else None,
+               messages=np.zeros((T, 3, L)) if messages else None)
+    assert out["lab"].size == N
+    null = C.cast(None, c_dp)
+    args = [out["lab"].ctypes.data_as(c_ip), C.byref(out["run"]), C.byref(out["energy"]), C.byref(out["bound"]) if out["bound"] is not None else null,
+            out["energies"].ctypes.data_as(c_dp), out["bounds"].ctypes.data_as(c_dp) if bounds else null,
+            out["messages"].ctypes.data_as(c_dp) if messages else null]
+    return out, args
+
+
+def _mplp_result(out):
+    return MplpResult(out["lab"], out["run"].value, out["energy"].value, None if out["bound"] is None else out["bound"].value, out["energies"],
+                      out["bounds"], out["messages"])
+
+
+def _mplp_tables(unary, tcosts, triplets):
+    U, pu = _d(unary)
+    L, N = U.shape
+    tc, ptc = _d(tcosts)
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    T = tr.shape[0]
+    assert tc.size == T * L ** 3
+    return (U, tc, tr), (pu, ptc, tr.ctypes.data_as(c_ip), N, L, T)
+
+
+def mplp_optimise(unary, tcosts, triplets, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+    """msm_mplp_optimise [host]: max-product linear programming over the unary (L x N) and triplet (T x L x L x L) tables -- an extension, not newMSM's
+    (DESIGN.md 5.19).  Returns MplpResult(labeling, sweeps_run, energy, bound, energies, bounds, messages): the labelling is the lowest-energy one among
+    the start and the decode after every sweep (never worse than the start), bound is a lower bound on every labelling's energy.  bounds=True costs a
+    second pass over the triplet table per sweep, bound=True alone one pass."""
+    keep, head = _mplp_tables(unary, tcosts, triplets)
+    out, tail = _mplp_outputs(head[3], head[4], head[5], sweeps, labeling, bound, bounds, messages)
+    check(lib().msm_mplp_optimise(*head, int(sweeps), *tail))
+    return _mplp_result(out)
+
+
+def mplp_optimise_gpu(ctx, unary, tcosts, triplets, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+    """msm_mplp_optimise_gpu: mplp_optimise with the sweeps on the GPU (a launch per level of mcmc_schedule, a workgroup per factor); the same
+    MplpResult, bit for bit"""
+    keep, head = _mplp_tables(unary, tcosts, triplets)
+    out, tail = _mplp_outputs(head[3], head[4], head[5], sweeps, labeling, bound, bounds, messages)
+    check(lib().msm_mplp_optimise_gpu(ctx.h, *head, int(sweeps), *tail))
+    return _mplp_result(out)
+
+
+def mplp_gpu_stats(ctx):
+    """msm_mplp_gpu_stats of the context's last GPU MPLP run: dict(kernel_ms, levels_per_sweep, sweeps_run, widest_level)"""
+    s = np.zeros(4)
+    check(lib().msm_mplp_gpu_stats(ctx.h, s.ctypes.data_as(c_dp)))
+    return dict(kernel_ms=float(s[0]), levels_per_sweep=int(s[1]), sweeps_run=int(s[2]), widest_level=int(s[3]))
+
+
 def _chain_args(seeds, N):
     """(seeds array or None, its pointer or NULL, K, labelings K x N, energies K) of a chains call; seeds=None passes a NULL pointer with K = 1"""
     c_u64p = C.POINTER(C.c_uint64)
@@ -1177,6 +1236,13 @@ class DiscreteCostFunction:
         check(lib().msm_cost_mcmc_optimise_chains(self.h, float(mcparam), int(iters), ps, K, lab.ctypes.data_as(c_ip), labs.ctypes.data_as(c_ip),
                                                   E.ctypes.data_as(c_dp), C.byref(best)))
         return lab, labs, E, best.value
+
+    def mplp_optimise(self, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+        """msm_cost_mplp_optimise: computeUnaryCosts + computeTripletCosts + MPLP with both tables staying on the device; the MplpResult that
+        computeUnaryCosts() + computeTripletCosts() + api.mplp_optimise give, bit for bit"""
+        out, tail = _mplp_outputs(self.N, self.L, self.T, sweeps, labeling, bound, bounds, messages)
+        check(lib().msm_cost_mplp_optimise(self.h, int(sweeps), *tail))
+        return _mplp_result(out)
 
     def computePairwiseCost(self, pair, la, lb):
         p, pp = _i(np.atleast_1d(pair))

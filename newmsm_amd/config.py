@@ -124,7 +124,7 @@ def parse_config(text):
     return cfg
 
 
-def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmatch=False):
+def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmatch=False, mplp=False):
     """The DISCRETE levels of `cfg` (parse_config's result) for data with D feature rows, as keyword sets of run_multiresolution, plus what
     applies to the whole run: returns (levels, run_kw, skipped) -- run_multiresolution(ops, ..., levels, **run_kw).  skipped: the (index,
     method) of levels that are not DISCRETE (the affine stage is outside the path).  fix_parameters_for_level + NonLinearSRegDiscreteModel::
@@ -135,7 +135,9 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmat
     gradsampling) -- what Rigid_cost_function::set_parameters reads (M/rigid_costfunction.cpp:50-58) -- instead of being listed in `skipped`
     (opt-in: the executables run them when MSMHIP_RIGID=on).  Groupwise runs refuse them whatever this says (group_registration.py).
     histmatch: --IN / --INc are taken instead of refused (opt-in: the executables do when MSMHIP_HISTMATCH=on) and run_kw carries what the level
-    loops need: intensity (_IN) and cut (_cut: set by --INc alone, M/mesh_registration.cpp:694-703)."""
+    loops need: intensity (_IN) and cut (_cut: set by --INc alone, M/mesh_registration.cpp:694-703).
+    mplp: --dopt=MPLP, which is not newMSM's, is taken instead of refused (opt-in: the executables do when MSMHIP_MPLP=on) and names optimiser "mplp"
+    (registration.run_discrete_level; a level's --mciters is its sweep count); like MCMC it reads triplets, so --regoption=1 is refused."""
     if (cfg["IN"] or cfg["INc"]) and not histmatch:
         raise ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available")
     if groupwise:
@@ -151,6 +153,8 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmat
     else:
         kind = "ho_univariate" if cfg["triclique"] else "univariate"
     optimiser = {"HOCR": "fusion", "MCMC": "mcmc", "FastPD": "fastpd"}.get(cfg["dopt"])
+    if mplp and cfg["dopt"] == "MPLP":
+        optimiser = "mplp"
     if optimiser is None:
         raise ConfigError("Unrecognized optimiser")  # M/mesh_registration.cpp:202
     rmode = cfg["regoption"]

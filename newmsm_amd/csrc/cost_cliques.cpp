@@ -7,6 +7,7 @@
 
 #include "cost_internal.hpp"
 #include "mcmc.hpp"
+#include "mplp.hpp"
 
 using namespace msm;
 
@@ -621,13 +622,9 @@ int msm_cost_triplet_table(msm_cost *c, int32_t t0, int32_t t1, double *tcosts) 
     return check_status(ctx, "computeTripletCosts");
 }
 
-// computeUnaryCosts + computeTripletCosts for MCMC::optimise, both tables staying where their kernels wrote them (c->d_U, c->d_clique_out): what both
-// msm_cost_mcmc_optimise* do ahead of the sweeps (mcmc.cpp runs those), the host optimiser's checks first, before anything is launched
-static int mcmc_tables_on_device(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, const int32_t *labeling, int *N, int *L, int *T) {
-    if (!c || !labeling || iters < 0) return fail(MSM_ERR_INVALID, "msm_cost_mcmc_optimise: bad arguments");
-    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mcmc_optimise: meshes, labels and triplets must be set first");
-    MSM_TRY(mcmc_check_chains(seeds, K));
-    MSM_TRY(mcmc_check_arguments(c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), mcparam, labeling));
+// computeUnaryCosts + computeTripletCosts with both tables staying where their kernels wrote them (c->d_U, c->d_clique_out), once the caller's checks have
+// passed (msm_cost_mcmc_optimise*, msm_cost_mplp_optimise)
+static int fill_tables_on_device(msm_cost *c, int *N, int *L, int *T) {
     MSM_TRY(msm_cost_unary_table_async(c));  // (drops a label step queued ahead on the context first)
     MSM_TRY(check_status(c->ctx, "computeUnaryCosts"));  // what the table's kernels raised is reported as msm_cost_unary_table reports it
     CliqueArgs a;
@@ -642,6 +639,16 @@ static int mcmc_tables_on_device(msm_cost *c, double mcparam, int32_t iters, con
     return check_status(c->ctx, "computeTripletCosts");  // before the sweeps, as msm_cost_triplet_table reports it
 }
 
+// what both msm_cost_mcmc_optimise* do ahead of the sweeps (mcmc.cpp runs those): the host optimiser's checks first, before anything is launched, then
+// the two tables on the device
+static int mcmc_tables_on_device(msm_cost *c, double mcparam, int32_t iters, const uint64_t *seeds, int32_t K, const int32_t *labeling, int *N, int *L, int *T) {
+    if (!c || !labeling || iters < 0) return fail(MSM_ERR_INVALID, "msm_cost_mcmc_optimise: bad arguments");
+    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mcmc_optimise: meshes, labels and triplets must be set first");
+    MSM_TRY(mcmc_check_chains(seeds, K));
+    MSM_TRY(mcmc_check_arguments(c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), mcparam, labeling));
+    return fill_tables_on_device(c, N, L, T);
+}
+
 int msm_cost_mcmc_optimise(msm_cost *c, double mcparam, int32_t iters, uint64_t seed, int32_t *labeling) {
     int N, L, T;
     MSM_TRY(mcmc_tables_on_device(c, mcparam, iters, &seed, 1, labeling, &N, &L, &T));
@@ -654,6 +661,18 @@ int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, co
     int N, L, T;
     MSM_TRY(mcmc_tables_on_device(c, mcparam, iters, seeds, K, labeling, &N, &L, &T));
     return mcmc_run_device_chains(c->ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
+}
+
+// MPLP over the same two device tables (mplp.cpp runs the sweeps): the Monte Carlo argument checks do not apply, the MPLP ones do
+int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies,
+                           double *bounds, double *messages) {
+    if (!c || !labeling || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_cost_mplp_optimise: bad arguments");
+    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mplp_optimise: meshes, labels and triplets must be set first");
+    MSM_TRY(mplp_check_arguments("msm_mplp_optimise", c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), sweeps, labeling));
+    int N, L, T;
+    MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
+    const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
+    return mplp_run_device(c->ctx, "msm_mplp_optimise", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o);
 }
 
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on

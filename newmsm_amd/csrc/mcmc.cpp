@@ -53,6 +53,14 @@ int mcmc_check_chains(const uint64_t *seeds, int K) {
     return MSM_OK;
 }
 
+// host -> device through the staging blocks in pieces (a table of 281 MB must not ask for one staging block of its size)
+int upload_in_pieces(msm_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    const size_t piece = (size_t)16 << 20;
+    for (size_t off = 0; off < bytes; off += piece)
+        MSM_TRY(stage_h2d(ctx, (char *)dst + off, (const char *)src + off, std::min(piece, bytes - off)));
+    return MSM_OK;
+}
+
 }  // namespace msm
 
 namespace {
@@ -110,14 +118,6 @@ int sum_event_pairs(const std::vector<hipEvent_t> &ev, int pairs, double *ms) {
         MSM_HIP(hipEventElapsedTime(&f, ev[2 * (size_t)c], ev[2 * (size_t)c + 1]));
         *ms += f;
     }
-    return MSM_OK;
-}
-
-// host -> device through the staging blocks in pieces (a table of 281 MB must not ask for one staging block of its size)
-int upload_in_pieces(msm_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    const size_t piece = (size_t)16 << 20;
-    for (size_t off = 0; off < bytes; off += piece)
-        MSM_TRY(stage_h2d(ctx, (char *)dst + off, (const char *)src + off, std::min(piece, bytes - off)));
     return MSM_OK;
 }
 

@@ -67,6 +67,7 @@ int mcmc_run_device_chains(msm_ctx *ctx, const double *d_U, const double *d_tc, 
 // stats stay the previous call's).
 int mcmc_run_device(msm_ctx *ctx, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, double mcparam, int iters, uint64_t seed,
                     int32_t *labeling);
+int upload_in_pieces(msm_ctx *ctx, void *dst, const void *src, size_t bytes);  // host -> device through the staging blocks, 16 MB at a time (mcmc.cpp)
 int mcmc_check_chains(const uint64_t *seeds, int K);  // 1 <= K <= kMcmcMaxChains and seeds given, or MSM_ERR_INVALID
 int mcmc_check_node_count(const char *what, int N);   // N <= kMcmcMaxNodes, or MSM_ERR_CAPACITY reported under the name `what`
 // the sweeps of msm_mcmc_optimise over checked arguments (regtools.cpp)

@@ -1,0 +1,243 @@
+// mplp.cpp -- the host side of the MPLP optimiser (mplp.hpp; kernels: mplp_kernels.hip; the serial literal: mplp_host.hpp): the checks
+// both sides share, the loop that queues a chunk of sweeps -- a launch per level, the decode, the energy terms, the bound terms -- and sums what comes
+// back in the literal's order, and the entry points over host tables.
+#include <cstring>
+
+#include "mplp.hpp"
+
+using namespace msm;
+
+namespace {
+
+struct MplpScratch {
+    DevBuf<double> U, tc;  // the host tables of msm_mplp_optimise_gpu
+    DevBuf<int4> sched;
+    DevBuf<int32_t> inc_ptr, inc_slot, start, labs, changed, flags;
+    DevBuf<double> m, eterms, bterms;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double stats[4] = {0, 0, 0, 0};
+    ~MplpScratch() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+MplpScratch &mplp_scratch(msm_ctx *ctx) {
+    if (!ctx->mplp_scratch) ctx->mplp_scratch = std::shared_ptr<void>(new MplpScratch(), [](void *p) { delete static_cast<MplpScratch *>(p); });
+    return *static_cast<MplpScratch *>(ctx->mplp_scratch.get());
+}
+
+int refuse_non_finite(const char *what, const char *table) {
+    return fail(MSM_ERR_INVALID,
+                "%s: the %s table holds a non-finite value (NaN or infinity); clean the input data first (--fixnan), and mind that a label set which lets "
+                "two control points meet collapses a triangle and makes the regulariser non-finite (the unscaled sampling grid does: use --rescaleL)",
+                what, table);
+}
+
+int refuse_label_count(const char *what, int L) {
+    return fail(MSM_ERR_CAPACITY, "%s: %d labels; a factor's cavities and minima (6 L doubles) live in the LDS of one workgroup (at most %d labels)", what, L,
+                kMplpMaxLabels);
+}
+
+int check_pointers(const char *what, const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling) {
+    if (!unary || !labeling || N <= 0 || L <= 0 || T < 0 || sweeps < 0 || (T > 0 && (!tcosts || !triplets))) return fail(MSM_ERR_INVALID, "%s: bad arguments", what);
+    return MSM_OK;
+}
+
+}  // namespace
+
+namespace msm {
+
+int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling) {
+    if (sweeps < 0) return fail(MSM_ERR_INVALID, "%s: bad arguments", what);
+    MSM_TRY(mcmc_check_arguments(triplets, N, L, T, 1.0, labeling));
+    const int t = mplp_first_repeated_node(triplets, T);
+    if (t >= 0) return fail(MSM_ERR_INVALID, "%s: triplet %d names a node twice", what, t);
+    return MSM_OK;
+}
+
+int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, int sweeps,
+                    const MplpOutputs &o) {
+    MplpScratch &s = mplp_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
+    // the refusals that need the tables: one pass over both, before anything else is launched
+    int32_t bad[2] = {0, 0};
+    if (s.flags.zero(2, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 2);
+    MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
+    MSM_TRY(s.flags.download(bad, 2, ctx));
+    MSM_TRY(check_status(ctx, what));
+    if (bad[0]) return refuse_non_finite(what, "unary");
+    if (bad[1]) return refuse_non_finite(what, "triplet");
+    if (L > kMplpMaxLabels) return refuse_label_count(what, L);
+
+    McmcSchedule sch;
+    mcmc_build_schedule(triplets, N, T, sch);
+    std::vector<int4> rec((size_t)T);
+    for (int i = 0; i < T; ++i) {
+        const int t = sch.order[(size_t)i];
+        rec[(size_t)i] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
+    }
+    MplpIncidence inc;
+    mplp_build_incidence(triplets, N, T, inc);
+    // sweeps per chunk: the terms of a chunk (two arrays of N + T doubles per sweep) stay below 32 MB each, and a run that reaches its fixed point
+    // early in a chunk has at most 255 idle sweeps' launches behind it
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min(sweeps, 256), ((size_t)1 << 22) / nterms));
+    MSM_TRY(s.sched.upload_vec(rec, ctx));
+    MSM_TRY(s.inc_ptr.upload_vec(inc.ptr, ctx));
+    MSM_TRY(s.inc_slot.upload_vec(inc.slot, ctx));
+    MSM_TRY(s.start.upload(o.labeling, (size_t)N, ctx));
+    if (s.m.zero(std::max<size_t>(nm, 1), ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(double) * nm);
+    if (s.changed.zero((size_t)std::max(sweeps, 1), ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * (size_t)sweeps);
+    if (s.labs.ensure((size_t)chunk * N) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * (size_t)chunk * N);
+    if (s.eterms.ensure((size_t)chunk * nterms) != hipSuccess || s.bterms.ensure((size_t)chunk * nterms) != hipSuccess)
+        return stage_alloc_failed(sizeof(double) * (size_t)chunk * nterms);
+    for (hipEvent_t &e : s.ev)
+        if (!e) MSM_HIP(hipEventCreate(&e));
+
+    MplpArgs a;
+    a.U = d_U;
+    a.tc = d_tc;
+    a.sched = s.sched.p;
+    a.inc_ptr = s.inc_ptr.p;
+    a.inc_slot = s.inc_slot.p;
+    a.m = s.m.p;
+    a.changed = s.changed.p;
+    a.N = N;
+    a.L = L;
+    a.T = T;
+    a.status = ctx->d_status;
+    McmcChainArgs c;  // the energy terms of one labelling: k_mcmc_chain_terms with K = 1
+    c.a.U = d_U;
+    c.a.tc = d_tc;
+    c.a.sched = s.sched.p;
+    c.a.level_off = nullptr;
+    c.a.prop = nullptr;
+    c.a.labeling = s.start.p;
+    c.a.N = N;
+    c.a.L = L;
+    c.a.T = T;
+    c.a.levels = sch.levels();
+    c.a.sweeps = 0;
+    c.a.status = ctx->d_status;
+    c.chains = 1;
+    c.chunk_sweeps = 0;
+
+    // candidate 0: the start
+    std::vector<double> eterms((size_t)chunk * nterms), bterms((size_t)chunk * nterms);
+    MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.eterms.p));
+    MSM_TRY(s.eterms.download(eterms.data(), nterms, ctx));
+    MSM_TRY(check_status(ctx, what));
+    MplpWinner win(o.labeling, N, mcmc_energy_of_terms(eterms.data(), N, T));
+
+    std::vector<int32_t> labs((size_t)chunk * N), changed((size_t)sweeps, 0);
+    std::vector<double> energies((size_t)sweeps), bounds(o.bounds ? (size_t)sweeps : 0);
+    int run = 0;
+    double kernel_ms = 0.0, e_last = 0.0, b_last = 0.0;
+    bool fixed = false;
+    for (int k0 = 0; k0 < sweeps && T > 0 && !fixed; k0 += chunk) {
+        const int n = std::min(chunk, sweeps - k0);
+        MSM_HIP(hipEventRecord(s.ev[0], ctx->stream));
+        for (int j = 0; j < n; ++j) {
+            for (int lv = 0; lv < sch.levels(); ++lv)
+                MSM_TRY(launch_mplp_update(ctx, a, sch.level_off[(size_t)lv], sch.level_off[(size_t)lv + 1] - sch.level_off[(size_t)lv], k0 + j));
+            MSM_TRY(launch_mplp_decode(ctx, a, s.labs.p + (size_t)j * N, s.bterms.p + (size_t)j * nterms));
+            c.a.labeling = s.labs.p + (size_t)j * N;
+            MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.eterms.p + (size_t)j * nterms));
+            if (o.bounds) MSM_TRY(launch_mplp_factor_terms(ctx, a, s.bterms.p + (size_t)j * nterms + N, k0 + j));
+        }
+        MSM_HIP(hipEventRecord(s.ev[1], ctx->stream));
+        MSM_TRY(s.labs.download(labs.data(), (size_t)n * N, ctx));
+        MSM_TRY(s.eterms.download(eterms.data(), (size_t)n * nterms, ctx));
+        if (o.bounds) MSM_TRY(s.bterms.download(bterms.data(), (size_t)n * nterms, ctx));
+        MSM_TRY(stage_d2h(ctx, changed.data() + k0, s.changed.p + k0, sizeof(int32_t) * (size_t)n));
+        MSM_TRY(check_status(ctx, what));
+        float ms = 0.f;
+        MSM_HIP(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+        kernel_ms += ms;
+        for (int j = 0; j < n; ++j) {
+            const int k = k0 + j;
+            if (k > 0 && changed[(size_t)k - 1] == 0) {  // sweep k - 1 moved nothing: sweep k and the rest did not run
+                fixed = true;
+                break;
+            }
+            run = k + 1;
+            energies[(size_t)k] = e_last = mcmc_energy_of_terms(eterms.data() + (size_t)j * nterms, N, T);
+            win.offer(labs.data() + (size_t)j * N, N, e_last);
+            if (o.bounds) bounds[(size_t)k] = b_last = mplp_bound_of_terms(bterms.data() + (size_t)j * nterms, N, T);
+        }
+    }
+    for (int k = run; k < sweeps && run > 0; ++k) {
+        energies[(size_t)k] = e_last;
+        if (o.bounds) bounds[(size_t)k] = b_last;
+    }
+    double bound = b_last;
+    if (o.bound && !(o.bounds && run > 0)) {  // one pass over the table for the bound of the last messages
+        MSM_TRY(launch_mplp_decode(ctx, a, nullptr, s.bterms.p));
+        MSM_TRY(launch_mplp_factor_terms(ctx, a, s.bterms.p + N, -1));
+        MSM_TRY(s.bterms.download(bterms.data(), nterms, ctx));
+        MSM_TRY(check_status(ctx, what));
+        bound = mplp_bound_of_terms(bterms.data(), N, T);
+    }
+    if (o.messages && nm) {
+        std::vector<double> m(nm);  // the caller's array stays as it is when the call fails
+        MSM_TRY(s.m.download(m.data(), nm, ctx));
+        MSM_TRY(check_status(ctx, what));
+        std::copy(m.begin(), m.end(), o.messages);
+    }
+    std::copy(win.lab.begin(), win.lab.end(), o.labeling);
+    if (o.sweeps_run) *o.sweeps_run = run;
+    if (o.energy) *o.energy = win.energy;
+    if (o.bound) *o.bound = bound;
+    if (run > 0) {
+        if (o.energies) std::copy(energies.begin(), energies.end(), o.energies);
+        if (o.bounds) std::copy(bounds.begin(), bounds.end(), o.bounds);
+    }
+    s.stats[0] = kernel_ms;
+    s.stats[1] = sch.levels();
+    s.stats[2] = run;
+    s.stats[3] = sch.widest();
+    return MSM_OK;
+}
+
+}  // namespace msm
+
+extern "C" {
+
+int msm_mplp_optimise(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps, int32_t *labeling,
+                      int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages) {
+    const char *what = "msm_mplp_optimise";
+    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, sweeps, labeling));
+    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, sweeps, labeling));
+    if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
+    if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
+    if (L > kMplpMaxLabels) return refuse_label_count(what, L);
+    const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
+    mplp_run_host(unary, tcosts, triplets, N, L, T, sweeps, o);
+    return MSM_OK;
+}
+
+int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
+                          int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages) {
+    const char *what = "msm_mplp_optimise_gpu";
+    if (!ctx) return fail(MSM_ERR_INVALID, "%s: null context", what);
+    MSM_TRY(check_pointers("msm_mplp_optimise", unary, tcosts, triplets, N, L, T, sweeps, labeling));
+    MSM_TRY(mplp_check_arguments("msm_mplp_optimise", triplets, N, L, T, sweeps, labeling));
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    MplpScratch &s = mplp_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L;
+    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
+    if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
+    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
+    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
+    const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
+    return mplp_run_device(ctx, "msm_mplp_optimise", s.U.p, s.tc.p, triplets, N, L, T, sweeps, o);
+}
+
+int msm_mplp_gpu_stats(msm_ctx *ctx, double stats[4]) {
+    if (!ctx || !stats) return fail(MSM_ERR_INVALID, "msm_mplp_gpu_stats: null argument");
+    std::memcpy(stats, mplp_scratch(ctx).stats, sizeof(double) * 4);
+    return MSM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,43 @@
+// mplp.hpp -- the MPLP optimiser's sweeps on the GPU: the kernels' arguments and the host loop around them (mplp.cpp,
+// mplp_kernels.hip).  The definition, the incidence lists and the serial literal are plain host code: mplp_host.hpp.
+#pragma once
+
+#include "internal.hpp"
+#include "mcmc.hpp"
+#include "mplp_host.hpp"
+
+namespace msm {
+
+constexpr int kMplpThreads = 256;  // the workgroup of a factor (update, bound term)
+
+struct MplpArgs {
+    const double *U;          // L x N
+    const double *tc;         // T x L^3
+    const int4 *sched;        // T records in schedule order: {triplet, node A, node B, node C} (McmcArgs::sched)
+    const int32_t *inc_ptr;   // N + 1
+    const int32_t *inc_slot;  // 3 T slots (3 t + s), a node's ascending
+    double *m;                // T x 3 x L messages
+    int32_t *changed;         // a word per sweep: raised to 1 by a message whose bits the sweep changed
+    int N, L, T;
+    int *status;
+};
+
+// one level of sweep `sweep`: a workgroup per factor sched[begin .. begin + count).  The whole launch returns at once when the sweep before left every
+// message as it was (changed[sweep - 1] == 0): a run past its fixed point costs launches and nothing else.
+int launch_mplp_update(msm_ctx *ctx, const MplpArgs &a, int begin, int count, int sweep);
+// beliefs and decode, a wavefront per node: label[i] (may be null) and node_terms[i] = min_x b_i(x)
+int launch_mplp_decode(msm_ctx *ctx, const MplpArgs &a, int32_t *label, double *node_terms);
+// the factor terms of the bound after sweep `sweep`, a workgroup per factor, factor_terms[t]; returns at once where the update of that sweep did (the
+// host repeats the previous sweep's bound).  sweep < 0: unconditional.
+int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_terms, int sweep);
+// flags[0] / flags[1] raised to 1 by a non-finite entry of the unary / triplet table
+int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, int32_t *flags);
+
+// the host optimiser's checks, with its messages (what: the entry point's name for the MPLP-specific refusals); the tables are not looked at
+int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling);
+// MPLP over tables that lie on the device (d_U: L x N, d_tc: T x L^3), arguments checked by the caller: the finiteness pass first, then the sweeps.
+// Complete on return; the outputs are written only when the call succeeds.
+int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, int sweeps,
+                    const MplpOutputs &o);
+
+}  // namespace msm

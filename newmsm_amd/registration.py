@@ -24,18 +24,26 @@ EXCL_WITH_WEIGHTINGS = ("--excl together with --inweight and --refweight is not 
                         "meshes have the same size")
 
 
+def _mplp_host(unary, tcosts, triplets, labeling, sweeps):
+    """the MPLP branch of run_discrete_level over fetched tables: the host literal's labelling (any ops without an mplp method of its own gets this)"""
+    return api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False).labeling
+
+
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
-    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False):
+    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True):
         """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
         the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
         bytes (what MSMHIP_FEATURES=gpu asks of the executables).
         mcmc_gpu: the MCMC branch of run_discrete_level leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead
         of fetching them for the host optimiser -- the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables).
         mcmc_draw_gpu (with mcmc_gpu): those sweeps take their proposals from the draw kernel instead of the host's stream (the context's
-        set_mcmc_draw) -- the same proposals, bit for bit (what MSMHIP_MCMC_DRAW=gpu asks of the executables)"""
+        set_mcmc_draw) -- the same proposals, bit for bit (what MSMHIP_MCMC_DRAW=gpu asks of the executables)
+        mplp_gpu: the MPLP branch of run_discrete_level (optimiser="mplp", an extension) leaves both tables on the device and runs its sweeps there
+        (msm_cost_mplp_optimise); False fetches them for the host literal (msm_mplp_optimise) -- the same labelings, bit for bit"""
         self.ctx = ctx
+        self.mplp_gpu = bool(mplp_gpu)
         self.mcmc_gpu = bool(mcmc_gpu)
         self.mcmc_draw_gpu = bool(mcmc_draw_gpu)
         if self.mcmc_draw_gpu:
@@ -169,6 +177,9 @@ class ProductOps:
     def mcmc_chains(self, unary, tcosts, triplets, labeling, mcparam, iters, seeds):
         return api.mcmc_optimise_chains(unary, tcosts, triplets, labeling, seeds, mcparam=mcparam, iters=iters)[0]
 
+    def mplp(self, unary, tcosts, triplets, labeling, sweeps):
+        return _mplp_host(unary, tcosts, triplets, labeling, sweeps)
+
     def fusion_step(self, unary2, octets, triplets, passes, quads=None, pairs=None):
         return api.fusion_icm_step(unary2, octets, triplets, passes, quads=quads, pairs=pairs)
 
@@ -256,6 +267,9 @@ class _ProductCost:
 
     def mcmc_optimise_chains(self, labeling, mcparam, iters, seeds):
         return self.cf.mcmc_optimise_chains(labeling, seeds, mcparam=mcparam, iters=iters)[0]
+
+    def mplp_optimise(self, labeling, sweeps):
+        return self.cf.mplp_optimise(labeling, sweeps=sweeps, bound=False).labeling
 
     def total(self, labeling):
         return self.cf.evaluateTotalCostSum(labeling)[0]
@@ -450,7 +464,10 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
     (ELC + FastPD, licence-restricted) is replaced by a stand-in (ops.fusion_step: iterated conditional modes, icm_passes passes): such a run
     exercises and times the path as HOCR would, its result is not the reference's optimum.  "fastpd": --regoption=1 as --dopt=FastPD drives it
     (M/mesh_registration.cpp:182-188): the unary table and the P x L x L pair tables (computePairwiseCosts), then a stand-in for FPD::FastPD
-    (ops.pairwise_solve: iterated conditional modes over all labels).  converge=True applies the reference's convergence test of a level
+    (ops.pairwise_solve: iterated conditional modes over all labels).  "mplp" (an extension, not newMSM's): max-product linear programming over the
+    MCMC optimiser's two tables, `mciters` sweeps per iteration from the zero labelling (api.mplp_optimise) -- deterministic, never
+    worse than its start; the tables stay on the device where ops.mplp_gpu is set and the ops' cost function has mplp_optimise, otherwise they are
+    fetched for the host literal (ops.mplp), which gives the same labelling.  converge=True applies the reference's convergence test of a level
     (:204-213; the stand-in solves make its energies differ from the reference's, so it is off unless asked for).
 
     target / source: the reference and the moving sphere at the data resolution of this level (source_xyz = the sphere the
@@ -538,7 +555,8 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
             cost.set_triplets(triplets)
         m_iter += 1
         mcmc_gpu = optimiser == "mcmc" and getattr(ops, "mcmc_gpu", False)  # both tables stay on the device (msm_cost_mcmc_optimise)
-        unary = None if mcmc_gpu else timed("unary_table", cost.unary_table)
+        mplp_gpu = optimiser == "mplp" and getattr(ops, "mplp_gpu", False) and hasattr(cost, "mplp_optimise")  # the same for msm_cost_mplp_optimise
+        unary = None if mcmc_gpu or mplp_gpu else timed("unary_table", cost.unary_table)
         labeling = np.zeros(len(cp_xyz), dtype=np.int32)  # resetLabeling
         if optimiser == "fusion":  # --- Fusion::optimize: computeUnaryCosts, then per label step the 8 T combinations
             nodes = np.arange(len(cp_xyz))
@@ -562,6 +580,11 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
         elif pairwise:  # --- FastPD: computeUnaryCosts, computePairwiseCosts, FPD::FastPD(model, 100) (M/mesh_registration.cpp:182-188)
             paircosts = timed("pairwise_table", cost.pairwise_table)
             labeling = timed("optimiser", ops.pairwise_solve, unary, paircosts, pairs, 100)
+        elif mplp_gpu:  # --- MPLP with the tables and the sweeps on the device: the labeling of the branch below, bit for bit
+            labeling = timed("optimiser", cost.mplp_optimise, labeling, mciters)
+        elif optimiser == "mplp":  # --- MPLP: computeUnaryCosts, computeTripletCosts, the host literal
+            tcosts = timed("triplet_table", cost.triplet_table)
+            labeling = timed("optimiser", getattr(ops, "mplp", _mplp_host), unary, tcosts, triplets, labeling, mciters)
         elif mcmc_gpu:  # --- MCMC with the tables and the sweeps on the device: the labeling of the branch below, bit for bit
             if mcmc_chains > 1:
                 labeling = timed("optimiser", cost.mcmc_optimise_chains, labeling, mcparam, mciters, api.chain_seeds(seed, it, mcmc_chains))

@@ -263,7 +263,9 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const bool rigid = rigid_env && std::string(rigid_env) == "on";
     const Config cfg = parse_config(slurp(o.get("conf")), o.get("conf").empty());
     IntensityNorm inorm;  // --IN / --INc: taken when MSMHIP_HISTMATCH=on, refused otherwise
-    std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr);
+    const char *mplp_env = std::getenv("MSMHIP_MPLP");  // "on": --dopt=MPLP (an extension: DESIGN.md section 5.19) runs instead of "Unrecognized optimiser"
+    const bool mplp = mplp_env && std::string(mplp_env) == "on";
+    std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr, mplp);
     const char *mcmc_env = std::getenv("MSMHIP_MCMC");  // "gpu": the --dopt=MCMC levels keep both cost tables on the device and run the sweeps there
     const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
     if (mcmc_gpu)

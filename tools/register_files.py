@@ -127,6 +127,12 @@ def histmatch_enabled():
     return os.environ.get("MSMHIP_HISTMATCH", "") == "on"
 
 
+def mplp_enabled():
+    """MSMHIP_MPLP=on: --dopt=MPLP (an extension, not newMSM's: max-product linear programming over the MCMC optimiser's tables, --mciters sweeps per
+    iteration) runs instead of ending the run with the reference's message (Unrecognized optimiser)"""
+    return os.environ.get("MSMHIP_MPLP", "") == "on"
+
+
 def mcmc_gpu_enabled():
     """MSMHIP_MCMC=gpu: the --dopt=MCMC levels keep both cost tables on the device and run the optimiser's sweeps there (the same labelings)"""
     return os.environ.get("MSMHIP_MCMC", "") == "gpu"
@@ -199,7 +205,8 @@ def group_mcmc_draw_setting():
 
 def discrete_levels(cfg, D, anat=False, groupwise=False):
     levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
-                                                        **(dict(histmatch=True) if histmatch_enabled() else {}))
+                                                        **(dict(histmatch=True) if histmatch_enabled() else {}),
+                                                        **(dict(mplp=True) if mplp_enabled() else {}))
     for index, method in skipped:
         print("register_files.py: level %d (--opt=%s) is outside the path (the affine stage stays on the CPU in newmsm): skipped" % (index + 1, method), file=sys.stderr)
     if not levels:

@@ -1,0 +1,100 @@
+"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
+MI355X against its host literal, over the unary and triplet tables tools/time_mcmc.py builds: BASELINE config 2 (pairwise sulc, ico6 data, ico4 control
+grid, 19 labels) and an ico3 control grid.  It reports and judges nothing.  Per grid: the energy of the start (all zero), the energy the Monte Carlo
+optimiser reaches on the device in --mcmc-sweeps sweeps (msm_cost_mcmc_optimise, tools/time_mcmc.py's sweep count by default), the energy of MPLP's decode
+and its bound after every sweep, ms per sweep on the device by the HIP events around the sweeps' kernels (without and with the bound's second pass over
+the table) beside the time the sweep's table bytes take at the HBM rate, and the ms of the host literal (msm_mplp_optimise over the fetched tables).  Times
+are medians of the repeats with min and max, after a warm-up, and are reported only when the device's result equals the host literal's, bit for bit.
+A table the optimiser refuses (a non-finite entry) is reported as refused, with the message.  Prints one JSON object."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import newmsm_amd as M  # noqa: E402
+from newmsm_amd import api, problem  # noqa: E402
+
+HBM_BYTES_PER_S = 6.29e12  # measured float4 copy on the MI355X (8.0e12 is the specification)
+
+
+def spread(values):
+    v = sorted(values)
+    return dict(median=v[len(v) // 2], min=v[0], max=v[-1])
+
+
+def equal(a, b):
+    return (np.array_equal(a.labeling, b.labeling) and a.sweeps_run == b.sweeps_run and a.energy == b.energy and a.energies.tobytes() == b.energies.tobytes()
+            and (a.bounds is None or b.bounds is None or a.bounds.tobytes() == b.bounds.tobytes()))
+
+
+def measure(ctx, cp_order, sweeps, mcmc_sweeps, repeats):
+    inp = problem.pairwise_inputs(6, cp_order, D=1)
+    cf, keep = problem.build_cost(ctx, inp, kind="univariate")
+    cf.get_source_data()
+    keep["target"].prepare_search(wait=True)
+    triplets = inp["triplets"]
+    start = np.zeros(cf.N, dtype=np.int32)
+    table_bytes = cf.T * cf.L ** 3 * 8
+    out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, sweeps=sweeps, repeats=repeats, triplet_table_MB=table_bytes / 1e6,
+               table_ms_at_hbm_rate=table_bytes / HBM_BYTES_PER_S * 1e3, hbm_bytes_per_s=HBM_BYTES_PER_S)
+    U = cf.computeUnaryCosts()
+    tc = np.array(cf.computeTripletCosts(pinned=True))
+    out["energy_start"] = api.mcmc_energy(U, tc, triplets, start)
+    out["mcmc"] = dict(sweeps=mcmc_sweeps, mcparam=0.8, seed=3, energy=api.mcmc_energy(U, tc, triplets, cf.mcmc_optimise(start, mcparam=0.8, iters=mcmc_sweeps, seed=3)))
+    try:
+        cf.mplp_optimise(start, sweeps=2, bounds=True)  # warm-up: code objects, staging blocks, the scratch buffers
+        cf.mplp_optimise(start, sweeps=2, bound=False)
+    except M.MsmError as e:
+        out["refused"] = str(e)
+        cf.close()
+        return out
+    plain, bounded, host_ms, same = [], [], [], True
+    for _ in range(repeats):
+        fast = cf.mplp_optimise(start, sweeps=sweeps, bound=False)
+        plain.append(api.mplp_gpu_stats(ctx))
+        full = cf.mplp_optimise(start, sweeps=sweeps, bounds=True)
+        bounded.append(api.mplp_gpu_stats(ctx))
+        t0 = time.perf_counter()
+        want = api.mplp_optimise(U, tc, triplets, start, sweeps=sweeps, bounds=True)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+        same = same and equal(fast, want) and equal(full, want)
+    out.update(results_equal=bool(same), sweeps_run=full.sweeps_run, levels_per_sweep=plain[0]["levels_per_sweep"], widest_level=plain[0]["widest_level"],
+               energy=full.energy, bound=full.bound, energies=full.energies.tolist(), bounds=full.bounds.tolist())
+    cf.close()
+    if not same:
+        return out  # no time is reported for a result that is not the host literal's
+    out.update(gpu_kernel_ms_per_sweep=spread([s["kernel_ms"] / max(s["sweeps_run"], 1) for s in plain]),
+               gpu_kernel_ms_per_sweep_with_bounds=spread([s["kernel_ms"] / max(s["sweeps_run"], 1) for s in bounded]),
+               gpu_us_per_level=spread([1e3 * s["kernel_ms"] / max(s["sweeps_run"] * s["levels_per_sweep"], 1) for s in plain]),
+               host_literal_ms=spread(host_ms), host_literal_ms_per_sweep=spread([ms / max(full.sweeps_run, 1) for ms in host_ms]))
+    out["sweep_over_table_at_hbm_rate"] = out["gpu_kernel_ms_per_sweep"]["median"] / out["table_ms_at_hbm_rate"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sweeps", type=int, default=30)
+    ap.add_argument("--mcmc-sweeps", type=int, default=2000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if M.device_count() < 1:
+        raise SystemExit("time_mplp.py: no HIP device is visible (nothing is measured without one)")
+    ctx = M.Context(0)
+    result = dict(tool="tools/time_mplp.py", grids=[measure(ctx, cp, a.sweeps, a.mcmc_sweeps, a.repeats) for cp in (4, 3)])
+    ctx.close()
+    text = json.dumps(result, indent=1, default=lambda o: o.item())  # (numpy scalars)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
