@@ -452,6 +452,31 @@ int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcost
 /* What the last msm_mplp_optimise_gpu / msm_cost_mplp_optimise on the context did: stats[0] ms in the sweeps' kernels (HIP events around every chunk
  * of sweeps: updates, decodes, energy and bound terms), [1] levels per sweep, [2] sweeps run, [3] the widest level. */
 int msm_mplp_gpu_stats(msm_ctx *ctx, double stats[4]);
+/* [host] The colouring the rounding walks (DESIGN.md 5.19 "Rounding"): nodes in ascending order, colour[i] (N, out) the smallest colour no lower-index
+ * node that shares a triplet with i holds; a node in no triplet has colour 0; nodes of one colour share no triplet.  *classes (may be NULL): the number
+ * of colours.  Refuses a node out of range and a triplet that names a node twice. */
+int msm_mplp_colouring(const int32_t *triplets, int32_t N, int32_t T, int32_t *colour, int32_t *classes);
+/* [host] Rounds MPLP's messages (T x 3 x L as msm_mplp_optimise returns them; NULL: all zero) to a labelling, by the definition of DESIGN.md 5.19
+ * "Rounding", which this serial literal and the GPU entry points follow bit for bit.  The conditioned decode walks the colour classes k = 0, 1, ...:
+ * every node of class k takes the first argmin of theta_i(x) + sum over its slots of g(x), where g minimises the factor's table, less the messages of
+ * the other two slots, over those of the two other nodes that lie in a class >= k, the ones in a lower class held at the label they have just taken.
+ * A polish pass is the same walk with every other node held: iterated conditional modes class by class, the current label kept unless another is
+ * strictly lower; a pass that changes no label ends the run.  Candidate 0 is the labelling handed in (labeling, N); mode 0 adds the conditioned decode
+ * and every polish pass of it, mode 1 every polish pass of the labelling handed in (messages are not read).  labeling receives the candidate of the
+ * first lowest msm_mcmc_energy, never worse than what was handed in.  Optional outputs (NULL): *passes_run the polish passes run; *energy the winner's;
+ * energies, 2 + polish values in mode 0 and 1 + polish in mode 1, one per candidate (the passes a fixed point spares repeat the last value).  Refused
+ * before anything is written: what msm_mplp_optimise refuses, with its messages; a non-finite message (mode 0); a mode other than 0 / 1; polish < 0 or
+ * > 1024. */
+int msm_mplp_round(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages, int32_t mode,
+                   int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
+/* msm_mplp_round on the GPU, bit for bit: the tables and the messages are uploaded; a pass is one launch per colour class on the context's stream (the
+ * conditioned decode a workgroup per node, a polish pass a wavefront per node); the energy terms are evaluated on the device and summed on the host.
+ * Complete on return. */
+int msm_mplp_round_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages,
+                       int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
+/* What the last rounding on the context's GPU did: stats[0] ms in the conditioned decode's launches, [1] ms in the polish passes (with their energy
+ * terms), [2] colour classes, [3] polish passes run. */
+int msm_mplp_round_gpu_stats(msm_ctx *ctx, double stats[4]);
 /* [host] A STAND-IN for the binary solve of one label step of Fusion::optimize (I/Fusion/Fusion.h:198-229 hands the step to ELC's
  * reduction + FastPD, which are licence-restricted and FSL-bound: not reproduced).  Iterated conditional modes over x in {0,1}^N
  * (0: the node keeps its label, 1: it takes the proposed one) for
@@ -568,6 +593,14 @@ int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, co
  * msm_cost_triplet_table(0, T) + msm_mplp_optimise give, bit for bit (labelling, sweeps_run, energies, bounds, messages). */
 int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies,
                            double *bounds, double *messages);
+/* MPLP's sweeps and the rounding over the cost function's own device tables; the messages never leave the device.  What msm_cost_mplp_optimise(messages)
+ * followed by msm_mplp_round(mode 0) on those messages with that winner handed in give, bit for bit: labeling, *sweeps_run, *passes_run, *energy,
+ * *bound (after the last sweep), energies (2 + polish).  then_polish != 0: one msm_mplp_round(mode 1) call on that result follows over the same tables
+ * (labeling and *energy are its; a no-op where the polish reached its fixed point, it matters when the labelling handed in won). */
+int msm_cost_mplp_round(msm_cost *c, int32_t sweeps, int32_t polish, int32_t then_polish, int32_t *labeling, int32_t *sweeps_run, int32_t *passes_run,
+                        double *energy, double *bound, double *energies);
+/* msm_mplp_round(mode 1) over the cost function's own device tables, filled as msm_cost_mplp_optimise fills them; energies: 1 + polish values */
+int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
 /* evaluateTotalCostSum :55-77: parts = {unary, pairwise, triplet} sums in the reference's serial order */
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]);
 /* Optional HIP-event timing of the sampling kernel (k_unary_rays or k_unary_samples) of each unary-table launch, recorded on the

@@ -520,6 +520,37 @@ inline MplpRun mplp_optimise_gpu(Context &ctx, const Matrix &unary_costs, const 
                                 labeling.data(), &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
     return r;
 }
+// What a rounding of MPLP's messages hands back besides the labeling (msm_mplp_round; DESIGN.md 5.19 "Rounding"): the polish passes it ran, the
+// energy of the labelling it kept (never above that of the one handed in) and the energy of every candidate
+struct MplpRound {
+    int32_t passes_run = 0;
+    double energy = 0.0;
+    std::vector<double> energies;  // 2 + polish in mode 0, 1 + polish in mode 1
+};
+// colour per node and the number of colours (msm_mplp_colouring)
+inline std::vector<int32_t> mplp_colouring(const std::vector<int32_t> &triplets, int num_nodes, int32_t *classes = nullptr) {
+    std::vector<int32_t> colour((size_t)num_nodes, 0);
+    check(msm_mplp_colouring(triplets.data(), num_nodes, (int32_t)(triplets.size() / 3), colour.data(), classes));
+    return colour;
+}
+// rounds the messages (empty: all zero) to a labelling: mode 0 the conditioned decode and its polish passes, mode 1 the polish passes of `labeling`
+inline MplpRound mplp_round(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
+                            const std::vector<double> &messages, int mode, int polish, std::vector<int32_t> &labeling) {
+    MplpRound r;
+    r.energies.assign((size_t)(mode == 0 ? 2 : 1) + (size_t)std::max(polish, 0), 0.0);
+    check(msm_mplp_round(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
+                         messages.empty() ? nullptr : messages.data(), mode, polish, labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
+    return r;
+}
+// the same on the GPU (msm_mplp_round_gpu), bit for bit
+inline MplpRound mplp_round_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes,
+                                int num_labels, const std::vector<double> &messages, int mode, int polish, std::vector<int32_t> &labeling) {
+    MplpRound r;
+    r.energies.assign((size_t)(mode == 0 ? 2 : 1) + (size_t)std::max(polish, 0), 0.0);
+    check(msm_mplp_round_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
+                             messages.empty() ? nullptr : messages.data(), mode, polish, labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
+    return r;
+}
 // what several chains from one start hand back: labelings chains x N, energies per chain, best by std::min_element's rule
 struct McmcChains {
     std::vector<int32_t> labelings;
@@ -709,6 +740,22 @@ public:
         if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
         check(msm_cost_mplp_optimise(h_, sweeps, labeling.data(), &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr,
                                      nullptr));
+        return r;
+    }
+    // MPLP's sweeps, then the rounding of mode 0 on the messages they left on the device (msm_cost_mplp_round); then_polish: one mode-1 call on the
+    // result follows, as an iteration of a level does
+    MplpRound mplp_round(int sweeps, int polish, std::vector<int32_t> &labeling, bool then_polish = false, int32_t *sweeps_run = nullptr,
+                         double *bound = nullptr) {
+        MplpRound r;
+        r.energies.assign(2 + (size_t)std::max(polish, 0), 0.0);
+        check(msm_cost_mplp_round(h_, sweeps, polish, then_polish ? 1 : 0, labeling.data(), sweeps_run, &r.passes_run, &r.energy, bound, r.energies.data()));
+        return r;
+    }
+    // the polish passes of `labeling` alone over the device tables (msm_cost_mplp_polish)
+    MplpRound mplp_polish(int polish, std::vector<int32_t> &labeling) {
+        MplpRound r;
+        r.energies.assign(1 + (size_t)std::max(polish, 0), 0.0);
+        check(msm_cost_mplp_polish(h_, polish, labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
         return r;
     }
     // the batched forms the optimisers' loops collapse to (I/Fusion/Fusion.h:138-196)

@@ -60,6 +60,10 @@ struct LevelOptions {
     // true (an extension, not newMSM's; what --dopt=MPLP asks for under MSMHIP_MPLP=on): max-product linear programming over the MCMC optimiser's two
     // tables, mciters sweeps per iteration from the zero labelling (DiscreteCostFunction::mplp_optimise: the tables stay on the device)
     bool mplp = false;
+    // with mplp: an iteration rounds the final messages to a labelling after its sweeps -- the conditioned decode and mplp_polish polish passes, then
+    // one polish call on the winner (DiscreteCostFunction::mplp_round; what MSMHIP_MPLP_ROUND=on and MSMHIP_MPLP_POLISH=n ask of the executables)
+    bool mplp_round = false;
+    int mplp_polish = 8;
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
@@ -239,7 +243,10 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
             PhaseClock::timed(clock, "pairwise_table", [&] { costfct.computePairwiseCosts(); });
             PhaseClock::timed(clock, "optimiser", [&] { pairwise_icm(costfct.unarycosts, costfct.paircosts, pairs, N, L, labeling, 100); });
         } else if (mplp) {  // ---- MPLP with the tables and the sweeps on the device
-            PhaseClock::timed(clock, "optimiser", [&] { costfct.mplp_optimise(o.mciters, labeling); });
+            if (o.mplp_round)
+                PhaseClock::timed(clock, "optimiser", [&] { costfct.mplp_round(o.mciters, o.mplp_polish, labeling, true); });
+            else
+                PhaseClock::timed(clock, "optimiser", [&] { costfct.mplp_optimise(o.mciters, labeling); });
         } else if (mcmc_gpu) {  // ---- MCMC with the tables and the sweeps on the device: the labeling of the branch below
             if (o.mcmc_chains > 1)
                 PhaseClock::timed(clock, "optimiser", [&] { costfct.mcmc_optimise_chains(o.mcparam, o.mciters, mcmc_chain_seeds(o.seed + (uint64_t)it, o.mcmc_chains), labeling); });

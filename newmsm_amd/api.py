@@ -817,6 +817,61 @@ def mplp_gpu_stats(ctx):
     return dict(kernel_ms=float(s[0]), levels_per_sweep=int(s[1]), sweeps_run=int(s[2]), widest_level=int(s[3]))
 
 
+MplpRound = collections.namedtuple("MplpRound", "labeling passes_run energy energies")
+
+
+def _mplp_round_outputs(N, mode, polish, labeling):
+    out = dict(lab=np.array(labeling, dtype=np.int32), run=C.c_int32(-1), energy=C.c_double(np.nan),
+               energies=np.full((2 if int(mode) == 0 else 1) + max(int(polish), 0), np.nan))
+    assert out["lab"].size == N
+    return out, [out["lab"].ctypes.data_as(c_ip), C.byref(out["run"]), C.byref(out["energy"]), out["energies"].ctypes.data_as(c_dp)]
+
+
+def _mplp_messages(messages, T, L):
+    """(the array kept alive, its pointer or NULL)"""
+    if messages is None:
+        return None, C.cast(None, c_dp)
+    m, pm = _d(messages)
+    assert m.size == T * 3 * L
+    return m, pm
+
+
+def mplp_colouring(triplets, N):
+    """msm_mplp_colouring [host]: (colour per node, number of colours) -- nodes ascending, each the smallest colour no lower-index node sharing a
+    triplet with it holds (DESIGN.md 5.19 "Rounding")"""
+    tr = np.ascontiguousarray(triplets, dtype=np.int32).reshape(-1, 3)
+    colour, classes = np.zeros(int(N), dtype=np.int32), C.c_int32(0)
+    check(lib().msm_mplp_colouring(tr.ctypes.data_as(c_ip), int(N), tr.shape[0], colour.ctypes.data_as(c_ip), C.byref(classes)))
+    return colour, classes.value
+
+
+def mplp_round(unary, tcosts, triplets, labeling, messages=None, mode=0, polish=8):
+    """msm_mplp_round [host]: rounds MPLP's messages (T x 3 x L; None: all zero) to a labelling -- the conditioned decode over the colour classes and
+    `polish` passes of iterated conditional modes (mode 0), or the polish passes of `labeling` alone (mode 1); DESIGN.md 5.19 "Rounding".  Returns
+    MplpRound(labeling, passes_run, energy, energies): the lowest-energy candidate, never worse than the labelling handed in."""
+    keep, head = _mplp_tables(unary, tcosts, triplets)
+    m, pm = _mplp_messages(messages, head[5], head[4])
+    out, tail = _mplp_round_outputs(head[3], mode, polish, labeling)
+    check(lib().msm_mplp_round(*head, pm, int(mode), int(polish), *tail))
+    return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
+
+
+def mplp_round_gpu(ctx, unary, tcosts, triplets, labeling, messages=None, mode=0, polish=8):
+    """msm_mplp_round_gpu: mplp_round on the GPU (a launch per colour class and pass); the same MplpRound, bit for bit"""
+    keep, head = _mplp_tables(unary, tcosts, triplets)
+    m, pm = _mplp_messages(messages, head[5], head[4])
+    out, tail = _mplp_round_outputs(head[3], mode, polish, labeling)
+    check(lib().msm_mplp_round_gpu(ctx.h, *head, pm, int(mode), int(polish), *tail))
+    return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
+
+
+def mplp_round_gpu_stats(ctx):
+    """msm_mplp_round_gpu_stats of the context's last GPU rounding: dict(decode_ms, polish_ms, classes, passes_run)"""
+    s = np.zeros(4)
+    check(lib().msm_mplp_round_gpu_stats(ctx.h, s.ctypes.data_as(c_dp)))
+    return dict(decode_ms=float(s[0]), polish_ms=float(s[1]), classes=int(s[2]), passes_run=int(s[3]))
+
+
 def _chain_args(seeds, N):
     """(seeds array or None, its pointer or NULL, K, labelings K x N, energies K) of a chains call; seeds=None passes a NULL pointer with K = 1"""
     c_u64p = C.POINTER(C.c_uint64)
@@ -1243,6 +1298,22 @@ class DiscreteCostFunction:
         out, tail = _mplp_outputs(self.N, self.L, self.T, sweeps, labeling, bound, bounds, messages)
         check(lib().msm_cost_mplp_optimise(self.h, int(sweeps), *tail))
         return _mplp_result(out)
+
+    def mplp_round(self, labeling, sweeps=30, polish=8, then_polish=False):
+        """msm_cost_mplp_round: MPLP's sweeps and the rounding of mode 0 with tables and messages staying on the device; what mplp_optimise(messages=True)
+        followed by api.mplp_round on those messages with that winner give, bit for bit.  then_polish: one mode-1 call on the result follows.  Returns
+        (MplpRound, sweeps_run, bound)."""
+        out, tail = _mplp_round_outputs(self.N, 0, polish, labeling)
+        run, bound = C.c_int32(-1), C.c_double(np.nan)
+        check(lib().msm_cost_mplp_round(self.h, int(sweeps), int(polish), int(bool(then_polish)), tail[0], C.byref(run), tail[1], tail[2], C.byref(bound),
+                                        tail[3]))
+        return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"]), run.value, bound.value
+
+    def mplp_polish(self, labeling, polish=8):
+        """msm_cost_mplp_polish: api.mplp_round(mode=1) over the cost function's own device tables"""
+        out, tail = _mplp_round_outputs(self.N, 1, polish, labeling)
+        check(lib().msm_cost_mplp_polish(self.h, int(polish), *tail))
+        return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
 
     def computePairwiseCost(self, pair, la, lb):
         p, pp = _i(np.atleast_1d(pair))

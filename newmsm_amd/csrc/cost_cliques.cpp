@@ -675,6 +675,45 @@ int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32
     return mplp_run_device(c->ctx, "msm_mplp_optimise", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o);
 }
 
+// MPLP's sweeps, then the rounding of mode 0 on the messages they left on the device, the sweeps' winner handed in (DESIGN.md 5.19 "Rounding").
+// then_polish: a mode-1 call on that result follows over the same tables (what a level's iteration does); passes_run and energies stay mode 0's.
+int msm_cost_mplp_round(msm_cost *c, int32_t sweeps, int32_t polish, int32_t then_polish, int32_t *labeling, int32_t *sweeps_run, int32_t *passes_run,
+                        double *energy, double *bound, double *energies) {
+    if (!c || !labeling || sweeps < 0) return fail(MSM_ERR_INVALID, "msm_cost_mplp_round: bad arguments");
+    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mplp_round: meshes, labels and triplets must be set first");
+    MSM_TRY(mplp_check_arguments("msm_mplp_round", c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), sweeps, labeling));
+    MSM_TRY(mplp_round_check("msm_mplp_round", c->L, 0, polish));
+    int N, L, T;
+    MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
+    std::vector<int32_t> lab(labeling, labeling + N);  // the caller's labelling stays as it is when the rounding fails
+    int32_t run = 0;
+    double b = 0.0;
+    const MplpOutputs o = {lab.data(), &run, nullptr, bound ? &b : nullptr, nullptr, nullptr, nullptr};
+    MSM_TRY(mplp_run_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o));
+    const MplpRoundOutputs r = {lab.data(), passes_run, energy, energies};
+    MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, true, false, c->triplets.data(), N, L, T, 0, polish, r));
+    if (then_polish) {
+        const MplpRoundOutputs r1 = {lab.data(), nullptr, energy, nullptr};
+        MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, false, c->triplets.data(), N, L, T, 1, polish, r1));
+    }
+    std::copy(lab.begin(), lab.end(), labeling);
+    if (sweeps_run) *sweeps_run = run;
+    if (bound) *bound = b;
+    return MSM_OK;
+}
+
+// the rounding of mode 1 (polish passes of the labelling handed in; no messages) over the device tables
+int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies) {
+    if (!c || !labeling) return fail(MSM_ERR_INVALID, "msm_cost_mplp_polish: bad arguments");
+    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "msm_cost_mplp_polish: meshes, labels and triplets must be set first");
+    MSM_TRY(mplp_check_arguments("msm_mplp_round", c->triplets.data(), c->cpgrid->V, c->L, (int)(c->triplets.size() / 3), 0, labeling));
+    MSM_TRY(mplp_round_check("msm_mplp_round", c->L, 1, polish));
+    int N, L, T;
+    MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
+    const MplpRoundOutputs r = {labeling, passes_run, energy, energies};
+    return mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, true, c->triplets.data(), N, L, T, 1, polish, r);
+}
+
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on
 // the host over device-evaluated terms (N + P + T values), because the order defines the reported energy
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]) {

@@ -1,6 +1,7 @@
 // mplp.cpp -- the host side of the MPLP optimiser (mplp.hpp; kernels: mplp_kernels.hip; the serial literal: mplp_host.hpp): the checks
 // both sides share, the loop that queues a chunk of sweeps -- a launch per level, the decode, the energy terms, the bound terms -- and sums what comes
-// back in the literal's order, and the entry points over host tables.
+// back in the literal's order, and the entry points over host tables.  The rounding of the messages (mplp_round_device) has the same shape: a launch
+// per colour class and pass, a copy of the labelling and its energy terms per pass, one synchronisation per chunk of passes.
 #include <cstring>
 
 #include "mplp.hpp"
@@ -14,8 +15,12 @@ struct MplpScratch {
     DevBuf<int4> sched;
     DevBuf<int32_t> inc_ptr, inc_slot, start, labs, changed, flags;
     DevBuf<double> m, eterms, bterms;
+    // the rounding's own (mplp_round_device): it leaves m alone
+    DevBuf<int4> tri;
+    DevBuf<int32_t> colour, cls_node, cur, rlabs, rchanged;
+    DevBuf<double> rm, rterms;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double stats[4] = {0, 0, 0, 0};
+    double stats[4] = {0, 0, 0, 0}, round_stats[4] = {0, 0, 0, 0};
     ~MplpScratch() {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -53,6 +58,155 @@ int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L
     MSM_TRY(mcmc_check_arguments(triplets, N, L, T, 1.0, labeling));
     const int t = mplp_first_repeated_node(triplets, T);
     if (t >= 0) return fail(MSM_ERR_INVALID, "%s: triplet %d names a node twice", what, t);
+    return MSM_OK;
+}
+
+int mplp_round_check(const char *what, int L, int mode, int polish) {
+    if (mode != 0 && mode != 1) return fail(MSM_ERR_INVALID, "%s: mode %d (0: conditioned decode and polish, 1: polish alone)", what, mode);
+    if (polish < 0 || polish > kMplpMaxPolish) return fail(MSM_ERR_INVALID, "%s: %d polish passes (0 to %d)", what, polish, kMplpMaxPolish);
+    if (L > kMplpMaxLabels) return refuse_label_count(what, L);
+    return MSM_OK;
+}
+
+int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, bool use_scratch_m, bool check_tables,
+                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o) {
+    MplpScratch &s = mplp_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
+    if (use_scratch_m) d_m = s.m.p;
+    if (mode != 0 || nm == 0) d_m = nullptr;  // mode 1 reads no messages
+    int32_t bad[4] = {0, 0, 0, 0};
+    if (s.flags.zero(4, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 4);
+    if (check_tables) MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
+    if (d_m) MSM_TRY(launch_mplp_finite(ctx, d_m, nm, nullptr, 0, s.flags.p + 2));
+    MSM_TRY(s.flags.download(bad, 4, ctx));
+    MSM_TRY(check_status(ctx, what));
+    if (bad[0]) return refuse_non_finite(what, "unary");
+    if (bad[1]) return refuse_non_finite(what, "triplet");
+    if (bad[2]) return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
+    MSM_TRY(mplp_round_check(what, L, mode, polish));
+
+    MplpIncidence inc;
+    mplp_build_incidence(triplets, N, T, inc);
+    MplpColouring col;
+    mplp_build_colouring(triplets, N, inc, col);
+    std::vector<int4> rec((size_t)T);
+    for (int t = 0; t < T; ++t) rec[(size_t)t] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
+    // passes per chunk: a chunk's labellings and terms stay below 32 MB, as the sweeps' do
+    const int first = mode == 0 ? 2 : 1;  // candidates ahead of the polish passes
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(polish, 256), ((size_t)1 << 22) / nterms));
+    const size_t held = (size_t)std::max(chunk, first);
+    MSM_TRY(s.tri.upload_vec(rec, ctx));
+    MSM_TRY(s.inc_ptr.upload_vec(inc.ptr, ctx));
+    MSM_TRY(s.inc_slot.upload_vec(inc.slot, ctx));
+    MSM_TRY(s.colour.upload_vec(col.colour, ctx));
+    MSM_TRY(s.cls_node.upload_vec(col.node, ctx));
+    MSM_TRY(s.cur.upload(o.labeling, (size_t)N, ctx));
+    if (s.rchanged.zero((size_t)std::max(polish, 1), ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * (size_t)polish);
+    if (s.rlabs.ensure(held * N) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * held * N);
+    if (s.rterms.ensure(held * nterms) != hipSuccess) return stage_alloc_failed(sizeof(double) * held * nterms);
+    for (hipEvent_t &e : s.ev)
+        if (!e) MSM_HIP(hipEventCreate(&e));
+
+    MplpRoundArgs a;
+    a.U = d_U;
+    a.tc = d_tc;
+    a.m = d_m;
+    a.tri = s.tri.p;
+    a.inc_ptr = s.inc_ptr.p;
+    a.inc_slot = s.inc_slot.p;
+    a.colour = s.colour.p;
+    a.cls_node = s.cls_node.p;
+    a.lab = s.cur.p;
+    a.changed = s.rchanged.p;
+    a.N = N;
+    a.L = L;
+    a.T = T;
+    a.status = ctx->d_status;
+    McmcChainArgs c;  // the energy terms of the labelling being walked: k_mcmc_chain_terms with K = 1 (the records may come in any order)
+    c.a.U = d_U;
+    c.a.tc = d_tc;
+    c.a.sched = s.tri.p;
+    c.a.level_off = nullptr;
+    c.a.prop = nullptr;
+    c.a.labeling = s.cur.p;
+    c.a.N = N;
+    c.a.L = L;
+    c.a.T = T;
+    c.a.levels = 0;
+    c.a.sweeps = 0;
+    c.a.status = ctx->d_status;
+    c.chains = 1;
+    c.chunk_sweeps = 0;
+    const int classes = col.classes();
+    auto snapshot = [&](size_t j) -> int {  // the labelling as it stands and its energy terms, to place j of the chunk
+        MSM_HIP(hipMemcpyAsync(s.rlabs.p + j * N, s.cur.p, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
+        return launch_mcmc_chain_terms(ctx, c, s.rterms.p + j * nterms);
+    };
+
+    // candidate 0 and, in mode 0, the conditioned decode
+    std::vector<double> terms(held * nterms), energies((size_t)first + polish);
+    std::vector<int32_t> labs(held * N), changed((size_t)polish, 0);
+    float ms = 0.f;
+    double decode_ms = 0.0, polish_ms = 0.0;
+    MSM_TRY(snapshot(0));
+    if (mode == 0) {
+        MSM_HIP(hipEventRecord(s.ev[0], ctx->stream));
+        for (int k = 0; k < classes; ++k) MSM_TRY(launch_mplp_round(ctx, a, col.class_off[(size_t)k], col.class_off[(size_t)k + 1] - col.class_off[(size_t)k], k));
+        MSM_HIP(hipEventRecord(s.ev[1], ctx->stream));
+        MSM_TRY(snapshot(1));
+    }
+    MSM_TRY(s.rterms.download(terms.data(), (size_t)first * nterms, ctx));
+    MSM_TRY(s.rlabs.download(labs.data(), (size_t)first * N, ctx));
+    MSM_TRY(check_status(ctx, what));
+    if (mode == 0) {
+        MSM_HIP(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+        decode_ms = ms;
+    }
+    double e_last = mcmc_energy_of_terms(terms.data(), N, T);
+    MplpWinner win(o.labeling, N, e_last);
+    energies[0] = e_last;
+    if (mode == 0) {
+        energies[1] = e_last = mcmc_energy_of_terms(terms.data() + nterms, N, T);
+        win.offer(labs.data() + N, N, e_last);
+    }
+
+    int run = 0;
+    bool fixed = false;
+    for (int p0 = 0; p0 < polish && !fixed; p0 += chunk) {
+        const int n = std::min(chunk, polish - p0);
+        MSM_HIP(hipEventRecord(s.ev[0], ctx->stream));
+        for (int j = 0; j < n; ++j) {
+            for (int k = 0; k < classes; ++k)
+                MSM_TRY(launch_mplp_polish(ctx, a, col.class_off[(size_t)k], col.class_off[(size_t)k + 1] - col.class_off[(size_t)k], p0 + j));
+            MSM_TRY(snapshot((size_t)j));
+        }
+        MSM_HIP(hipEventRecord(s.ev[1], ctx->stream));
+        MSM_TRY(s.rlabs.download(labs.data(), (size_t)n * N, ctx));
+        MSM_TRY(s.rterms.download(terms.data(), (size_t)n * nterms, ctx));
+        MSM_TRY(stage_d2h(ctx, changed.data() + p0, s.rchanged.p + p0, sizeof(int32_t) * (size_t)n));
+        MSM_TRY(check_status(ctx, what));
+        MSM_HIP(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
+        polish_ms += ms;
+        for (int j = 0; j < n; ++j) {
+            const int p = p0 + j;
+            if (p > 0 && changed[(size_t)p - 1] == 0) {  // pass p - 1 changed no label: pass p and the rest did not run
+                fixed = true;
+                break;
+            }
+            run = p + 1;
+            energies[(size_t)first + p] = e_last = mcmc_energy_of_terms(terms.data() + (size_t)j * nterms, N, T);
+            win.offer(labs.data() + (size_t)j * N, N, e_last);
+        }
+    }
+    for (int p = run; p < polish; ++p) energies[(size_t)first + p] = e_last;
+    std::copy(win.lab.begin(), win.lab.end(), o.labeling);
+    if (o.passes_run) *o.passes_run = run;
+    if (o.energy) *o.energy = win.energy;
+    if (o.energies) std::copy(energies.begin(), energies.end(), o.energies);
+    s.round_stats[0] = decode_ms;
+    s.round_stats[1] = polish_ms;
+    s.round_stats[2] = classes;
+    s.round_stats[3] = run;
     return MSM_OK;
 }
 
@@ -232,6 +386,62 @@ int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcost
     MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
     const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
     return mplp_run_device(ctx, "msm_mplp_optimise", s.U.p, s.tc.p, triplets, N, L, T, sweeps, o);
+}
+
+int msm_mplp_colouring(const int32_t *triplets, int32_t N, int32_t T, int32_t *colour, int32_t *classes) {
+    const char *what = "msm_mplp_colouring";
+    if (!colour || N <= 0 || T < 0 || (T > 0 && !triplets)) return fail(MSM_ERR_INVALID, "%s: bad arguments", what);
+    const std::vector<int32_t> zeros((size_t)N, 0);
+    MSM_TRY(mplp_check_arguments(what, triplets, N, 1, T, 0, zeros.data()));
+    MplpIncidence inc;
+    mplp_build_incidence(triplets, N, T, inc);
+    MplpColouring col;
+    mplp_build_colouring(triplets, N, inc, col);
+    std::copy(col.colour.begin(), col.colour.end(), colour);
+    if (classes) *classes = col.classes();
+    return MSM_OK;
+}
+
+int msm_mplp_round(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages, int32_t mode,
+                   int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies) {
+    const char *what = "msm_mplp_round";
+    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, labeling));
+    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, labeling));
+    if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
+    if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
+    if (mode == 0 && messages && !mplp_all_finite(messages, 3 * (size_t)T * L))
+        return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
+    MSM_TRY(mplp_round_check(what, L, mode, polish));
+    const MplpRoundOutputs o = {labeling, passes_run, energy, energies};
+    mplp_round_host(unary, tcosts, triplets, N, L, T, mode == 0 ? messages : nullptr, mode, polish, o);
+    return MSM_OK;
+}
+
+int msm_mplp_round_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages,
+                       int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies) {
+    const char *what = "msm_mplp_round";
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: null context");
+    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, labeling));
+    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, labeling));
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    MplpScratch &s = mplp_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L;
+    const bool with_m = mode == 0 && messages && nm;
+    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
+    if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
+    if (with_m && s.rm.ensure(nm) != hipSuccess) return stage_alloc_failed(sizeof(double) * nm);
+    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
+    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
+    if (with_m) MSM_TRY(upload_in_pieces(ctx, s.rm.p, messages, sizeof(double) * nm));
+    const MplpRoundOutputs o = {labeling, passes_run, energy, energies};
+    return mplp_round_device(ctx, what, s.U.p, s.tc.p, with_m ? s.rm.p : nullptr, false, true, triplets, N, L, T, mode, polish, o);
+}
+
+int msm_mplp_round_gpu_stats(msm_ctx *ctx, double stats[4]) {
+    if (!ctx || !stats) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu_stats: null argument");
+    std::memcpy(stats, mplp_scratch(ctx).round_stats, sizeof(double) * 4);
+    return MSM_OK;
 }
 
 int msm_mplp_gpu_stats(msm_ctx *ctx, double stats[4]) {

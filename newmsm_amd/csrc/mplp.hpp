@@ -33,6 +33,35 @@ int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_ter
 // flags[0] / flags[1] raised to 1 by a non-finite entry of the unary / triplet table
 int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, int32_t *flags);
 
+// The rounding (DESIGN.md 5.19 "Rounding"; the literal: mplp_round_host).
+struct MplpRoundArgs {
+    const double *U;           // L x N
+    const double *tc;          // T x L^3
+    const double *m;           // T x 3 x L messages, or null: all zero
+    const int4 *tri;           // T records in list order: {triplet, node A, node B, node C}
+    const int32_t *inc_ptr;    // N + 1
+    const int32_t *inc_slot;   // 3 T
+    const int32_t *colour;     // N (MplpColouring::colour)
+    const int32_t *cls_node;   // N nodes class by class (MplpColouring::node)
+    int32_t *lab;              // N: the labelling being walked
+    int32_t *changed;          // a word per polish pass: raised to 1 by a label the pass changed
+    int N, L, T;
+    int *status;
+};
+// the conditioned decode of the class cls_node[begin .. begin + count) at `frontier`: a workgroup per node
+int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int frontier);
+// polish pass `pass` over that class, a wavefront per node; the whole launch returns at once when pass - 1 changed no label
+int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass);
+int mplp_update_slots(int L);
+
+// the checks of msm_mplp_round besides mplp_check_arguments: the mode, the polish count, the label count
+int mplp_round_check(const char *what, int L, int mode, int polish);
+// The rounding over tables that lie on the device, arguments checked by the caller.  d_m: the device messages of mode 0 (null: all zero; use_scratch_m:
+// the messages the context's last mplp_run_device left).  check_tables: look for non-finite table entries first (the messages of mode 0 always are).
+// Complete on return; the outputs are written only when the call succeeds.
+int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, bool use_scratch_m, bool check_tables,
+                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o);
+
 // the host optimiser's checks, with its messages (what: the entry point's name for the MPLP-specific refusals); the tables are not looked at
 int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling);
 // MPLP over tables that lie on the device (d_U: L x N, d_tc: T x L^3), arguments checked by the caller: the finiteness pass first, then the sweeps.

@@ -1,7 +1,8 @@
 // mplp_host.hpp -- max-product linear programming (MPLP) over the Monte Carlo optimiser's two tables, the part that is plain host C++ (no HIP header): the
-// incidence lists, the serial literal of DESIGN.md 5.19 that msm_mplp_optimise runs and the GPU entry points reproduce bit for bit, and the sums both
-// sides form on the host.  Block-coordinate ascent on the dual of the labelling LP, written from the published update rule for factors of three
-// variables (Globerson & Jaakkola, NIPS 2007; Sontag, Globerson & Jaakkola 2011, Fig. 1.4).
+// incidence lists, the serial literal of DESIGN.md 5.19 that msm_mplp_optimise runs and the GPU entry points reproduce bit for bit, the sums both
+// sides form on the host, and the rounding of the messages to a labelling (the colouring and the literal msm_mplp_round runs).  Block-coordinate
+// ascent on the dual of the labelling LP, written from the published update rule for factors of three variables (Globerson & Jaakkola, NIPS 2007;
+// Sontag, Globerson & Jaakkola 2011, Fig. 1.4).
 #pragma once
 
 #include <algorithm>
@@ -182,6 +183,151 @@ inline void mplp_run_host(const double *unary, const double *tcosts, const int32
     if (o.sweeps_run) *o.sweeps_run = run;
     if (o.energy) *o.energy = win.energy;
     if (o.messages) std::copy(m.begin(), m.end(), o.messages);
+}
+
+// ---------------------------------------------------------------- rounding (DESIGN.md 5.19 "Rounding")
+
+constexpr int kMplpMaxPolish = 1024;
+
+// colour[i]: the smallest colour no lower-index node that shares a triplet with i holds (a node in no triplet: 0), so nodes of one colour share no
+// triplet.  node lists the nodes class by class, ascending within a class: class k is node[class_off[k]] .. node[class_off[k + 1] - 1].
+struct MplpColouring {
+    std::vector<int32_t> colour, node, class_off;
+    int classes() const { return (int)class_off.size() - 1; }
+};
+
+inline void mplp_build_colouring(const int32_t *triplets, int N, const MplpIncidence &inc, MplpColouring &col) {
+    col.colour.assign((size_t)N, 0);
+    std::vector<int32_t> taken;  // taken[c] == i + 1: colour c is held by a lower neighbour of node i
+    int classes = N > 0 ? 1 : 0;
+    for (int i = 0; i < N; ++i) {
+        for (int32_t k = inc.ptr[(size_t)i]; k < inc.ptr[(size_t)i + 1]; ++k) {
+            const int32_t t = inc.slot[(size_t)k] / 3;
+            for (int s = 0; s < 3; ++s) {
+                const int32_t j = triplets[3 * (size_t)t + s];
+                if (j >= i) continue;
+                const size_t c = (size_t)col.colour[(size_t)j];
+                if (taken.size() <= c) taken.resize(c + 1, 0);
+                taken[c] = i + 1;
+            }
+        }
+        int32_t c = 0;
+        while ((size_t)c < taken.size() && taken[(size_t)c] == i + 1) ++c;
+        col.colour[(size_t)i] = c;
+        classes = std::max(classes, c + 1);
+    }
+    col.class_off.assign((size_t)classes + 1, 0);
+    col.node.assign((size_t)N, 0);
+    for (int i = 0; i < N; ++i) ++col.class_off[(size_t)col.colour[(size_t)i] + 1];
+    for (int k = 0; k < classes; ++k) col.class_off[(size_t)k + 1] += col.class_off[(size_t)k];
+    std::vector<int32_t> fill(col.class_off.begin(), col.class_off.end() - 1);
+    for (int i = 0; i < N; ++i) col.node[(size_t)fill[(size_t)col.colour[(size_t)i]]++] = i;  // ascending within a class
+}
+
+// the other two slots of slot s, ascending
+inline void mplp_other_slots(int s, int &s1, int &s2) { s1 = s == 0 ? 1 : 0, s2 = s == 2 ? 1 : 2; }
+
+// score(x) of node i at frontier f (node j is fixed when colour[j] < f): theta_i(x), then g_{t,s}(x) over the incidence of i in list order.  m null:
+// all messages zero.  frontier INT_MAX reads no message.
+inline void mplp_round_scores(const double *unary, const double *tcosts, const int32_t *triplets, const double *m, const MplpIncidence &inc,
+                              const int32_t *colour, int frontier, const int32_t *lab, int N, int L, int i, double *score) {
+    const size_t L1 = (size_t)L, L2 = L1 * L1, L3 = L2 * L1;
+    const size_t stride[3] = {L2, L1, 1};
+    for (int x = 0; x < L; ++x) score[x] = unary[(size_t)x * N + i];
+    for (int32_t k = inc.ptr[(size_t)i]; k < inc.ptr[(size_t)i + 1]; ++k) {
+        const int32_t q = inc.slot[(size_t)k], t = q / 3;
+        const int s = q - 3 * t;
+        int s1, s2;
+        mplp_other_slots(s, s1, s2);
+        const int32_t j1 = triplets[3 * (size_t)t + s1], j2 = triplets[3 * (size_t)t + s2];
+        const bool f1 = colour[(size_t)j1] < frontier, f2 = colour[(size_t)j2] < frontier;
+        const double *th = tcosts + (size_t)t * L3;
+        const double *m1 = m ? m + ((size_t)3 * t + s1) * L : nullptr, *m2 = m ? m + ((size_t)3 * t + s2) * L : nullptr;
+        for (int x = 0; x < L; ++x) {
+            const double *row = th + (size_t)x * stride[s];
+            double g;
+            if (f1 && f2)
+                g = row[(size_t)lab[(size_t)j1] * stride[s1] + (size_t)lab[(size_t)j2] * stride[s2]];
+            else {
+                g = std::numeric_limits<double>::infinity();
+                const int a0 = f1 ? lab[(size_t)j1] : 0, a1 = f1 ? a0 + 1 : L, b0 = f2 ? lab[(size_t)j2] : 0, b1 = f2 ? b0 + 1 : L;
+                for (int y1 = a0; y1 < a1; ++y1)
+                    for (int y2 = b0; y2 < b1; ++y2) {
+                        double v = row[(size_t)y1 * stride[s1] + (size_t)y2 * stride[s2]];
+                        if (!f1) v = v - (m1 ? m1[y1] : 0.0);
+                        if (!f2) v = v - (m2 ? m2[y2] : 0.0);
+                        if (v < g) g = v;
+                    }
+                g = g + 0.0;
+            }
+            score[x] += g;
+        }
+    }
+}
+
+// one walk over the classes: frontier k for class k in the conditioned decode (polish false), INT_MAX in a polish pass, where a node keeps its label
+// unless another one's score is strictly lower.  Returns whether a label changed.
+inline bool mplp_round_pass(const double *unary, const double *tcosts, const int32_t *triplets, const double *m, const MplpIncidence &inc,
+                            const MplpColouring &col, bool polish, int32_t *lab, int N, int L, double *score /* L */) {
+    bool changed = false;
+    for (int k = 0; k < col.classes(); ++k)
+        for (int32_t p = col.class_off[(size_t)k]; p < col.class_off[(size_t)k + 1]; ++p) {
+            const int32_t i = col.node[(size_t)p];
+            mplp_round_scores(unary, tcosts, triplets, m, inc, col.colour.data(), polish ? std::numeric_limits<int>::max() : k, lab, N, L, i, score);
+            int best = 0;
+            for (int x = 1; x < L; ++x)
+                if (score[x] < score[best]) best = x;
+            if (polish && !(score[best] < score[lab[(size_t)i]])) best = lab[(size_t)i];
+            changed |= best != lab[(size_t)i];
+            lab[(size_t)i] = best;
+        }
+    return changed;
+}
+
+struct MplpRoundOutputs {
+    int32_t *labeling;    // N: candidate 0 in, the winner out
+    int32_t *passes_run;  // the rest may be null
+    double *energy, *energies;  // energies: 2 + polish values in mode 0, 1 + polish in mode 1
+};
+
+// the serial literal of the rounding over checked arguments; messages may be null (all zero) and are not read in mode 1
+inline void mplp_round_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, const double *messages, int mode,
+                            int polish, const MplpRoundOutputs &o) {
+    MplpIncidence inc;
+    mplp_build_incidence(triplets, N, T, inc);
+    MplpColouring col;
+    mplp_build_colouring(triplets, N, inc, col);
+    std::vector<double> terms((size_t)N + T), score((size_t)L);
+    std::vector<int32_t> cur(o.labeling, o.labeling + N);
+    auto energy_of = [&](const int32_t *lab) {
+        mcmc_energy_terms(unary, tcosts, triplets, N, L, T, lab, terms.data());
+        return mcmc_energy_of_terms(terms.data(), N, T);
+    };
+    double e_last = energy_of(cur.data());
+    MplpWinner win(cur.data(), N, e_last);
+    int n = 0, run = 0;
+    if (o.energies) o.energies[n] = e_last;
+    ++n;
+    if (mode == 0) {
+        mplp_round_pass(unary, tcosts, triplets, messages, inc, col, false, cur.data(), N, L, score.data());
+        e_last = energy_of(cur.data());
+        win.offer(cur.data(), N, e_last);
+        if (o.energies) o.energies[n] = e_last;
+        ++n;
+    }
+    for (int p = 0; p < polish; ++p) {
+        const bool changed = mplp_round_pass(unary, tcosts, triplets, nullptr, inc, col, true, cur.data(), N, L, score.data());
+        run = p + 1;
+        e_last = energy_of(cur.data());
+        win.offer(cur.data(), N, e_last);
+        if (o.energies) o.energies[n + p] = e_last;
+        if (!changed) break;  // a fixed point
+    }
+    for (int p = run; p < polish; ++p)
+        if (o.energies) o.energies[n + p] = e_last;
+    std::copy(win.lab.begin(), win.lab.end(), o.labeling);
+    if (o.passes_run) *o.passes_run = run;
+    if (o.energy) *o.energy = win.energy;
 }
 
 }  // namespace msm

@@ -16,6 +16,10 @@
 // node's slots and then its messages are loaded eight at a time, independent of one another, and added in list order afterwards; (3) every minimum has
 // `slots` copies in LDS, lane l lowering copy l % slots (a padded row per minimum: the lanes of one instruction hit distinct banks), folded into one
 // when the table is through.  slots is the largest power of two up to 64 that keeps the factor's LDS within 64 KB: 64 up to 41 labels, 1 from 683.
+//
+// The rounding of the messages to a labelling (k_mplp_round, k_mplp_polish; DESIGN.md 5.19 "Rounding") walks the colour classes of the nodes, a launch per
+// class: nodes of one class share no triplet, so whatever the workgroups of a launch do among themselves every node sees the labels the serial walk
+// would show it.
 #include <climits>
 #include <cstdlib>
 
@@ -200,6 +204,180 @@ __global__ __launch_bounds__(256) void k_mplp_finite(const double *__restrict__ 
     if (bad_t) flags[1] = 1;
 }
 
+// ---------------------------------------------------------------- rounding (DESIGN.md 5.19 "Rounding"; the literal: mplp_round_host)
+
+// the lowest (value, label) of a wavefront, lowest label on ties, to lane 0; a lane without a label holds INT_MAX
+__device__ __forceinline__ void wave_argmin(double &bv, int &bx) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_down(bv, off);
+        const int ox = __shfl_down(bx, off);
+        if (ox != INT_MAX && (bx == INT_MAX || ov < bv || (ov == bv && ox < bx))) bv = ov, bx = ox;
+    }
+}
+
+// The conditioned decode of one class: a workgroup per node.  The L scores sit in LDS, label x owned by thread x % 256; every incident slot adds its
+// g(x) in list order.  With neither other node fixed the factor's L^3 block is streamed as k_mplp_update streams it, each entry lowering g[x_s] in a
+// padded row of `slots` key copies; with one fixed the L^2 sub-block at its label goes the same way, threads along the faster free axis; with both
+// fixed thread x reads its own entry.
+__global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, int begin, int count, int frontier, int slots) {
+    extern __shared__ __align__(16) double s_mplp[];  // L scores, 2 L staged messages, 8 words of the argmin, L rows of `slots` keys (padded by one)
+    const unsigned tid = threadIdx.x, L = (unsigned)a.L, N = (unsigned)a.N;
+    if ((int)blockIdx.x >= count) return;
+    const unsigned i = (unsigned)a.cls_node[begin + (int)blockIdx.x];
+    if (i >= N) {
+        if (tid == 0) raise_status(a.status, MSM_ERR_INVALID);
+        return;
+    }
+    double *score = s_mplp, *mo = s_mplp + L, *w = s_mplp + 3 * (size_t)L;
+    long long *G = reinterpret_cast<long long *>(w + 8);
+    const unsigned S = (unsigned)slots, stride = S > 1 ? S + 1 : 1, mine = tid & (S - 1);
+    const unsigned L2 = L * L, L3 = L2 * L;
+    const long long inf_key = key_of(__longlong_as_double(0x7ff0000000000000LL));
+    for (unsigned x = tid; x < L; x += kMplpThreads) score[x] = a.U[(size_t)x * N + i];
+    const int k0 = a.inc_ptr[i], k1 = a.inc_ptr[i + 1];
+    for (int k = k0; k < k1; ++k) {  // (everything that decides a branch below is the same in every thread of the workgroup)
+        const unsigned q = (unsigned)a.inc_slot[k];
+        if (q >= 3u * (unsigned)a.T) {
+            if (tid == 0) raise_status(a.status, MSM_ERR_INVALID);
+            return;
+        }
+        const unsigned t = q / 3, s = q - 3 * t, s1 = s == 0 ? 1 : 0, s2 = s == 2 ? 1 : 2;
+        const int4 r = a.tri[t];  // {triplet, node A, node B, node C}
+        const unsigned j1 = (unsigned)(s1 == 0 ? r.y : r.z), j2 = (unsigned)(s2 == 1 ? r.z : r.w);
+        if (j1 >= N || j2 >= N) {
+            if (tid == 0) raise_status(a.status, MSM_ERR_INVALID);
+            return;
+        }
+        const bool f1 = a.colour[j1] < frontier, f2 = a.colour[j2] < frontier;
+        const unsigned l1 = f1 ? (unsigned)a.lab[j1] : 0u, l2 = f2 ? (unsigned)a.lab[j2] : 0u;
+        if (l1 >= L || l2 >= L) {
+            if (tid == 0) raise_status(a.status, MSM_ERR_INVALID);
+            return;
+        }
+        const double *__restrict__ th = a.tc + (size_t)t * L3;
+        const unsigned st = s == 0 ? L2 : s == 1 ? L : 1u, st1 = s1 == 0 ? L2 : L, st2 = s2 == 1 ? L : 1u;
+        if (f1 && f2) {
+            for (unsigned x = tid; x < L; x += kMplpThreads) score[x] += th[x * st + l1 * st1 + l2 * st2];
+            continue;
+        }
+        for (unsigned idx = tid; idx < L * stride; idx += kMplpThreads) G[idx] = inf_key;
+        if (!f1 && !f2) {
+            double cur[kMplpBatch], nxt[kMplpBatch];
+            load_batch(th, tid, L3, cur);
+            for (unsigned idx = tid; idx < 2 * L; idx += kMplpThreads) {
+                const unsigned so = idx < L ? s1 : s2, y = idx < L ? idx : idx - L;
+                mo[idx] = a.m ? a.m[((size_t)3 * t + so) * L + y] : 0.0;
+            }
+            __syncthreads();
+            Abc p(tid, kMplpThreads, L);
+            for (unsigned e0 = tid; e0 < L3; e0 += kMplpBatch * kMplpThreads) {
+                load_batch(th, e0 + kMplpBatch * kMplpThreads, L3, nxt);
+#pragma unroll
+                for (int j = 0; j < kMplpBatch; ++j) {
+                    if (e0 + (unsigned)j * kMplpThreads >= L3) break;
+                    const unsigned x = s == 0 ? p.a : s == 1 ? p.b : p.c, y1 = s1 == 0 ? p.a : p.b, y2 = s2 == 1 ? p.b : p.c;
+                    const double v = (cur[j] - mo[y1]) - mo[L + y2];
+                    atomicMin(&G[x * stride + mine], key_of(v));
+                    p.advance();
+                }
+#pragma unroll
+                for (int j = 0; j < kMplpBatch; ++j) cur[j] = nxt[j];
+            }
+        } else {
+            // one other fixed at label lf of slot sf; the free axes are s and su, `lo` the one that runs faster in the table
+            const unsigned su = f1 ? s2 : s1, stu = f1 ? st2 : st1, base = f1 ? l1 * st1 : l2 * st2;
+            for (unsigned y = tid; y < L; y += kMplpThreads) mo[y] = a.m ? a.m[((size_t)3 * t + su) * L + y] : 0.0;
+            __syncthreads();
+            const bool x_fast = s > su;
+            const unsigned st_hi = x_fast ? stu : st, st_lo = x_fast ? st : stu;
+            for (unsigned e = tid; e < L2; e += kMplpThreads) {
+                const unsigned hi = e / L, lo = e - hi * L;
+                const unsigned x = x_fast ? lo : hi, y = x_fast ? hi : lo;
+                const double v = th[base + hi * st_hi + lo * st_lo] - mo[y];
+                atomicMin(&G[x * stride + mine], key_of(v));
+            }
+        }
+        __syncthreads();
+        for (unsigned x = tid; x < L; x += kMplpThreads) {
+            long long lowest = G[x * stride];
+            for (unsigned j = 1; j < S; ++j) lowest = min(lowest, G[x * stride + j]);
+            score[x] += value_of(lowest) + 0.0;
+        }
+        __syncthreads();  // the rows and the staged messages are free again
+    }
+    double bv = 0.0;
+    int bx = INT_MAX;
+    for (unsigned x = tid; x < L; x += kMplpThreads) {
+        const double v = score[x];
+        if (bx == INT_MAX || v < bv) bv = v, bx = (int)x;
+    }
+    wave_argmin(bv, bx);
+    int *wx = reinterpret_cast<int *>(w + 4);
+    if ((tid & 63u) == 0) w[tid >> 6] = bv, wx[tid >> 6] = bx;
+    __syncthreads();
+    if (tid == 0) {
+        for (unsigned j = 1; j < kMplpThreads / 64; ++j)
+            if (wx[j] != INT_MAX && (w[j] < bv || (w[j] == bv && wx[j] < bx))) bv = w[j], bx = wx[j];
+        a.lab[i] = bx;
+    }
+}
+
+// A polish pass over one class, a wavefront per node: every other node is fixed, so label x costs theta_i(x) plus one table entry per incident slot,
+// added in list order.  The current label stays unless another one is strictly lower.
+__global__ __launch_bounds__(256) void k_mplp_polish(MplpRoundArgs a, int begin, int count, int pass) {
+    if (pass > 0 && a.changed[pass - 1] == 0) return;  // the pass before moved no label (the whole launch)
+    const unsigned lane = threadIdx.x & 63u, L = (unsigned)a.L, N = (unsigned)a.N;
+    const long n = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= (long)count) return;  // (the whole wavefront)
+    const unsigned i = (unsigned)a.cls_node[begin + n];
+    if (i >= N) {
+        if (lane == 0) raise_status(a.status, MSM_ERR_INVALID);
+        return;
+    }
+    const unsigned cur = (unsigned)a.lab[i];
+    if (cur >= L) {
+        if (lane == 0) raise_status(a.status, MSM_ERR_INVALID);
+        return;
+    }
+    const unsigned L2 = L * L, L3 = L2 * L;
+    const int k0 = a.inc_ptr[i], k1 = a.inc_ptr[i + 1];
+    double bv = 0.0, cv = 0.0;
+    int bx = INT_MAX;
+    for (unsigned x = lane; x < L; x += 64) {
+        double v = a.U[(size_t)x * N + i];
+        for (int k = k0; k < k1; ++k) {
+            const unsigned q = (unsigned)a.inc_slot[k];
+            if (q >= 3u * (unsigned)a.T) {
+                raise_status(a.status, MSM_ERR_INVALID);
+                continue;
+            }
+            const unsigned t = q / 3, s = q - 3 * t;
+            const int4 r = a.tri[t];
+            const unsigned j1 = (unsigned)(s == 0 ? r.z : r.y), j2 = (unsigned)(s == 2 ? r.z : r.w);
+            if (j1 >= N || j2 >= N) {
+                raise_status(a.status, MSM_ERR_INVALID);
+                continue;
+            }
+            const unsigned l1 = (unsigned)a.lab[j1], l2 = (unsigned)a.lab[j2];
+            if (l1 >= L || l2 >= L) {
+                raise_status(a.status, MSM_ERR_INVALID);
+                continue;
+            }
+            const unsigned st = s == 0 ? L2 : s == 1 ? L : 1u, st1 = s == 0 ? L : L2, st2 = s == 2 ? L : 1u;
+            v += a.tc[(size_t)t * L3 + x * st + l1 * st1 + l2 * st2];
+        }
+        if (x == cur) cv = v;
+        if (bx == INT_MAX || v < bv) bv = v, bx = (int)x;
+    }
+    wave_argmin(bv, bx);
+    cv = __shfl(cv, (int)(cur & 63u));
+    if (lane == 0 && bv < cv) {
+        a.lab[i] = bx;
+        a.changed[pass] = 1;
+    }
+}
+
 int check_shape(const MplpArgs &a) {
     if (a.N <= 0 || a.L <= 0 || a.L > kMplpMaxLabels || a.T < 0) return fail(MSM_ERR_INVALID, "msm_mplp_optimise_gpu: bad launch (N %d, L %d, T %d)", a.N, a.L, a.T);
     return MSM_OK;
@@ -250,6 +428,31 @@ int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *t
     const size_t n = std::max(nU, ntc);
     const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 4096));
     hipLaunchKernelGGL(k_mplp_finite, dim3(blocks), dim3(256), 0, ctx->stream, U, nU, tc, ntc, flags);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+static int check_round_launch(const MplpRoundArgs &a, int begin, int count) {
+    if (a.N <= 0 || a.L <= 0 || a.L > kMplpMaxLabels || a.T < 0 || begin < 0 || count < 0 || begin + count > a.N)
+        return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: bad launch (N %d, L %d, T %d, nodes %d + %d)", a.N, a.L, a.T, begin, count);
+    return MSM_OK;
+}
+
+int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int frontier) {
+    MSM_TRY(check_round_launch(a, begin, count));
+    if (count == 0) return MSM_OK;
+    const int slots = mplp_update_slots(a.L);
+    const size_t lds = sizeof(double) * (3 * (size_t)a.L + 8 + (size_t)a.L * (size_t)(slots > 1 ? slots + 1 : 1));
+    hipLaunchKernelGGL(k_mplp_round, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
+int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass) {
+    MSM_TRY(check_round_launch(a, begin, count));
+    if (count == 0) return MSM_OK;
+    if (pass < 0) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: bad launch (pass %d)", pass);
+    hipLaunchKernelGGL(k_mplp_polish, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

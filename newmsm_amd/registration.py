@@ -29,10 +29,18 @@ def _mplp_host(unary, tcosts, triplets, labeling, sweeps):
     return api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False).labeling
 
 
+def _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, polish):
+    """the same with the rounding (DESIGN.md 5.19 "Rounding"): the sweeps, mode 0 on their messages with their winner handed in, one mode-1 call on the
+    result -- what msm_cost_mplp_round(then_polish) does over the device tables"""
+    r = api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False, messages=True)
+    lab = api.mplp_round(unary, tcosts, triplets, r.labeling, messages=r.messages, mode=0, polish=polish).labeling
+    return api.mplp_round(unary, tcosts, triplets, lab, mode=1, polish=polish).labeling
+
+
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
-    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True):
+    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True, mplp_round=False, mplp_polish=8):
         """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
         the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
         bytes (what MSMHIP_FEATURES=gpu asks of the executables).
@@ -41,8 +49,15 @@ class ProductOps:
         mcmc_draw_gpu (with mcmc_gpu): those sweeps take their proposals from the draw kernel instead of the host's stream (the context's
         set_mcmc_draw) -- the same proposals, bit for bit (what MSMHIP_MCMC_DRAW=gpu asks of the executables)
         mplp_gpu: the MPLP branch of run_discrete_level (optimiser="mplp", an extension) leaves both tables on the device and runs its sweeps there
-        (msm_cost_mplp_optimise); False fetches them for the host literal (msm_mplp_optimise) -- the same labelings, bit for bit"""
+        (msm_cost_mplp_optimise); False fetches them for the host literal (msm_mplp_optimise) -- the same labelings, bit for bit
+        mplp_round: an iteration of the MPLP branch rounds the final messages to a labelling after its sweeps (the conditioned decode and mplp_polish
+        polish passes, then one polish call on the winner: msm_cost_mplp_round, or msm_mplp_round over the fetched tables -- the same labelings; what
+        MSMHIP_MPLP_ROUND=on and MSMHIP_MPLP_POLISH=n ask of the executables)"""
         self.ctx = ctx
+        self.mplp_round = bool(mplp_round)
+        self.mplp_polish = int(mplp_polish)
+        if not 0 <= self.mplp_polish <= 64:
+            raise ValueError("mplp_polish: the polish passes of the rounding are a whole number from 0 to 64")
         self.mplp_gpu = bool(mplp_gpu)
         self.mcmc_gpu = bool(mcmc_gpu)
         self.mcmc_draw_gpu = bool(mcmc_draw_gpu)
@@ -178,6 +193,8 @@ class ProductOps:
         return api.mcmc_optimise_chains(unary, tcosts, triplets, labeling, seeds, mcparam=mcparam, iters=iters)[0]
 
     def mplp(self, unary, tcosts, triplets, labeling, sweeps):
+        if self.mplp_round:
+            return _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, self.mplp_polish)
         return _mplp_host(unary, tcosts, triplets, labeling, sweeps)
 
     def fusion_step(self, unary2, octets, triplets, passes, quads=None, pairs=None):
@@ -270,6 +287,9 @@ class _ProductCost:
 
     def mplp_optimise(self, labeling, sweeps):
         return self.cf.mplp_optimise(labeling, sweeps=sweeps, bound=False).labeling
+
+    def mplp_round(self, labeling, sweeps, polish):
+        return self.cf.mplp_round(labeling, sweeps=sweeps, polish=polish, then_polish=True)[0].labeling
 
     def total(self, labeling):
         return self.cf.evaluateTotalCostSum(labeling)[0]
@@ -467,7 +487,8 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
     (ops.pairwise_solve: iterated conditional modes over all labels).  "mplp" (an extension, not newMSM's): max-product linear programming over the
     MCMC optimiser's two tables, `mciters` sweeps per iteration from the zero labelling (api.mplp_optimise) -- deterministic, never
     worse than its start; the tables stay on the device where ops.mplp_gpu is set and the ops' cost function has mplp_optimise, otherwise they are
-    fetched for the host literal (ops.mplp), which gives the same labelling.  converge=True applies the reference's convergence test of a level
+    fetched for the host literal (ops.mplp), which gives the same labelling; with ops.mplp_round the iteration rounds the final messages to a labelling
+    after its sweeps (DESIGN.md 5.19 "Rounding"), on either route.  converge=True applies the reference's convergence test of a level
     (:204-213; the stand-in solves make its energies differ from the reference's, so it is off unless asked for).
 
     target / source: the reference and the moving sphere at the data resolution of this level (source_xyz = the sphere the
@@ -581,7 +602,10 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
             paircosts = timed("pairwise_table", cost.pairwise_table)
             labeling = timed("optimiser", ops.pairwise_solve, unary, paircosts, pairs, 100)
         elif mplp_gpu:  # --- MPLP with the tables and the sweeps on the device: the labeling of the branch below, bit for bit
-            labeling = timed("optimiser", cost.mplp_optimise, labeling, mciters)
+            if getattr(ops, "mplp_round", False):  # the sweeps, then the rounding of their messages (msm_cost_mplp_round)
+                labeling = timed("optimiser", cost.mplp_round, labeling, mciters, ops.mplp_polish)
+            else:
+                labeling = timed("optimiser", cost.mplp_optimise, labeling, mciters)
         elif optimiser == "mplp":  # --- MPLP: computeUnaryCosts, computeTripletCosts, the host literal
             tcosts = timed("triplet_table", cost.triplet_table)
             labeling = timed("optimiser", getattr(ops, "mplp", _mplp_host), unary, tcosts, triplets, labeling, mciters)

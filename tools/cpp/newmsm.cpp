@@ -244,6 +244,25 @@ bool group_mcmc_draw_setting() {
     return true;
 }
 
+// MSMHIP_MPLP_ROUND=on (beside MSMHIP_MPLP=on): every iteration of a --dopt=MPLP level rounds the final messages to a labelling after its sweeps
+// ("Rounding"), with MSMHIP_MPLP_POLISH=n (0 ... 64, default 8) polish passes.  Returns whether it is on and sets *polish.
+bool mplp_round_setting(bool mplp, int *polish) {
+    const char *env = std::getenv("MSMHIP_MPLP_ROUND"), *passes = std::getenv("MSMHIP_MPLP_POLISH");
+    if (env && std::string(env) != "on")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MPLP_ROUND=") + env + ": the rounding of MPLP's messages is switched on with MSMHIP_MPLP_ROUND=on (unset: off)");
+    if (env && !mplp) throw Error(MSM_ERR_INVALID, "MSMHIP_MPLP_ROUND=on rounds the messages of --dopt=MPLP: it needs MSMHIP_MPLP=on");
+    *polish = 8;
+    if (passes) {
+        if (!env) throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MPLP_POLISH=") + passes + " sets the polish passes of the rounding: it needs MSMHIP_MPLP_ROUND=on");
+        char *end = nullptr;
+        const long n = std::strtol(passes, &end, 10);
+        if (end == passes || *end != '\0' || n < 0 || n > 64)
+            throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MPLP_POLISH=") + passes + ": the number of polish passes must be a whole number from 0 to 64");
+        *polish = (int)n;
+    }
+    return env != nullptr;
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const int mcmc_chains = mcmc_chains_setting();
     const bool mcmc_draw_gpu = mcmc_draw_gpu_setting();
@@ -265,6 +284,8 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     IntensityNorm inorm;  // --IN / --INc: taken when MSMHIP_HISTMATCH=on, refused otherwise
     const char *mplp_env = std::getenv("MSMHIP_MPLP");  // "on": --dopt=MPLP (an extension: DESIGN.md section 5.19) runs instead of "Unrecognized optimiser"
     const bool mplp = mplp_env && std::string(mplp_env) == "on";
+    int mplp_polish = 8;
+    const bool mplp_round = mplp_round_setting(mplp, &mplp_polish);
     std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr, mplp);
     const char *mcmc_env = std::getenv("MSMHIP_MCMC");  // "gpu": the --dopt=MCMC levels keep both cost tables on the device and run the sweeps there
     const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
@@ -275,6 +296,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     if (features_gpu_enabled())
         for (LevelSpec &lv : levels) lv.options.features_gpu = true;
     for (LevelSpec &lv : levels) lv.options.mcmc_chains = mcmc_chains;
+    for (LevelSpec &lv : levels) lv.options.mplp_round = mplp_round, lv.options.mplp_polish = mplp_polish;
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");

@@ -133,6 +133,28 @@ def mplp_enabled():
     return os.environ.get("MSMHIP_MPLP", "") == "on"
 
 
+def mplp_round_setting():
+    """MSMHIP_MPLP_ROUND=on (beside MSMHIP_MPLP=on): every iteration of a --dopt=MPLP level rounds the final messages to a labelling after its sweeps
+    ("Rounding"), with MSMHIP_MPLP_POLISH=n (0 ... 64, default 8) polish passes.  Returns (on, polish); anything else, or either
+    variable without MSMHIP_MPLP=on, ends the run with a message and exit status 1."""
+    text, passes = os.environ.get("MSMHIP_MPLP_ROUND"), os.environ.get("MSMHIP_MPLP_POLISH")
+    if text is not None and text != "on":
+        raise SystemExit("MSMHIP_MPLP_ROUND=%s: the rounding of MPLP's messages is switched on with MSMHIP_MPLP_ROUND=on (unset: off)" % text)
+    if text is not None and not mplp_enabled():
+        raise SystemExit("MSMHIP_MPLP_ROUND=on rounds the messages of --dopt=MPLP: it needs MSMHIP_MPLP=on")
+    n = 8
+    if passes is not None:
+        if text is None:
+            raise SystemExit("MSMHIP_MPLP_POLISH=%s sets the polish passes of the rounding: it needs MSMHIP_MPLP_ROUND=on" % passes)
+        try:
+            n = int(passes)
+        except ValueError:
+            n = -1
+        if not 0 <= n <= 64:
+            raise SystemExit("MSMHIP_MPLP_POLISH=%s: the number of polish passes must be a whole number from 0 to 64" % passes)
+    return text == "on", n
+
+
 def mcmc_gpu_enabled():
     """MSMHIP_MCMC=gpu: the --dopt=MCMC levels keep both cost tables on the device and run the optimiser's sweeps there (the same labelings)"""
     return os.environ.get("MSMHIP_MCMC", "") == "gpu"
@@ -283,6 +305,7 @@ def main(argv):
         raise SystemExit("register_files.py: VTK output is not written here (GIFTI, ASCII, ASCII_MAT)")
     if a.groupwise:
         return main_groupwise(a, surf_ext, data_ext, group_mcmc, chains, draw_gpu)
+    mplp_round, mplp_polish = mplp_round_setting()
     for flag in ("inmesh", "indata", "refdata"):
         if not getattr(a, flag):
             raise SystemExit("register_files.py: --%s is required" % flag)
@@ -318,7 +341,7 @@ def main(argv):
             print("MCMC with %d chains per iteration." % chains)
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])

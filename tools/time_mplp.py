@@ -1,11 +1,16 @@
-"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
+"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--round] [--polish P] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
 MI355X against its host literal, over the unary and triplet tables tools/time_mcmc.py builds: BASELINE config 2 (pairwise sulc, ico6 data, ico4 control
 grid, 19 labels) and an ico3 control grid.  It reports and judges nothing.  Per grid: the energy of the start (all zero), the energy the Monte Carlo
 optimiser reaches on the device in --mcmc-sweeps sweeps (msm_cost_mcmc_optimise, tools/time_mcmc.py's sweep count by default), the energy of MPLP's decode
 and its bound after every sweep, ms per sweep on the device by the HIP events around the sweeps' kernels (without and with the bound's second pass over
 the table) beside the time the sweep's table bytes take at the HBM rate, and the ms of the host literal (msm_mplp_optimise over the fetched tables).  Times
 are medians of the repeats with min and max, after a warm-up, and are reported only when the device's result equals the host literal's, bit for bit.
-A table the optimiser refuses (a non-finite entry) is reported as refused, with the message.  Prints one JSON object."""
+A table the optimiser refuses (a non-finite entry) is reported as refused, with the message.  Prints one JSON object.
+
+--round measures the rounding of the messages instead (DESIGN.md 5.19 "Rounding"; profiles/mplp_round_time.json): per grid the energy of the conditioned
+decode and of the polished winner after 1 / 5 / 10 / 20 / 30 sweeps (msm_cost_mplp_round, --polish passes), the polish of the zero labelling alone
+(msm_cost_mplp_polish), ms per decode pass and per polish pass by the HIP events around their launches beside one sweep and the table at the HBM rate,
+and the start, the Monte Carlo optimiser's energy and the bound.  Times are reported only when the device's result equals the host literal's."""
 import argparse
 import json
 import os
@@ -77,17 +82,76 @@ def measure(ctx, cp_order, sweeps, mcmc_sweeps, repeats):
     return out
 
 
+ROUND_SWEEPS = (1, 5, 10, 20, 30)
+
+
+def measure_round(ctx, cp_order, mcmc_sweeps, repeats, polish):
+    inp = problem.pairwise_inputs(6, cp_order, D=1)
+    cf, keep = problem.build_cost(ctx, inp, kind="univariate")
+    cf.get_source_data()
+    keep["target"].prepare_search(wait=True)
+    triplets = inp["triplets"]
+    start = np.zeros(cf.N, dtype=np.int32)
+    table_bytes = cf.T * cf.L ** 3 * 8
+    out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, polish=polish, repeats=repeats, triplet_table_MB=table_bytes / 1e6,
+               table_ms_at_hbm_rate=table_bytes / HBM_BYTES_PER_S * 1e3, hbm_bytes_per_s=HBM_BYTES_PER_S)
+    U = cf.computeUnaryCosts()
+    tc = np.array(cf.computeTripletCosts(pinned=True))
+    out["energy_start"] = api.mcmc_energy(U, tc, triplets, start)
+    out["mcmc"] = dict(sweeps=mcmc_sweeps, mcparam=0.8, seed=3, energy=api.mcmc_energy(U, tc, triplets, cf.mcmc_optimise(start, mcparam=0.8, iters=mcmc_sweeps, seed=3)))
+    try:
+        cf.mplp_round(start, sweeps=2, polish=2)  # warm-up
+        cf.mplp_polish(start, polish=2)
+    except M.MsmError as e:
+        out["refused"] = str(e)
+        cf.close()
+        return out
+    same, rows, decode_ms, polish_ms, sweep_ms = True, [], [], [], []
+    for n in ROUND_SWEEPS:
+        for rep in range(repeats):
+            got, run, bound = cf.mplp_round(start, sweeps=n, polish=polish)
+            stats = api.mplp_round_gpu_stats(ctx)
+            decode_ms.append(stats["decode_ms"])
+            polish_ms.append(stats["polish_ms"] / max(stats["passes_run"], 1))
+            sweep = api.mplp_gpu_stats(ctx)
+            sweep_ms.append(sweep["kernel_ms"] / max(sweep["sweeps_run"], 1))
+        r = api.mplp_optimise(U, tc, triplets, start, sweeps=n, bound=False, messages=True)
+        want = api.mplp_round(U, tc, triplets, r.labeling, messages=r.messages, mode=0, polish=polish)
+        same = same and np.array_equal(got.labeling, want.labeling) and got.passes_run == want.passes_run and got.energies.tobytes() == want.energies.tobytes()
+        rows.append(dict(sweeps=n, sweeps_run=run, bound=bound, energy_naive_best=float(min(r.energies.min(), out["energy_start"])), energy_rounded=got.energies[1],
+                         energy_polished=float(got.energies[2:].min()) if polish else None, energy_returned=got.energy, passes_run=got.passes_run,
+                         classes=stats["classes"]))
+    zero = cf.mplp_polish(start, polish=64)
+    zstats = api.mplp_round_gpu_stats(ctx)
+    zwant = api.mplp_round(U, tc, triplets, start, mode=1, polish=64)
+    same = same and np.array_equal(zero.labeling, zwant.labeling) and zero.energies.tobytes() == zwant.energies.tobytes()
+    out.update(results_equal=bool(same), after_sweeps=rows,
+               polish_of_zero_labelling=dict(polish=64, passes_run=zero.passes_run, energy=zero.energy, energies=zero.energies[:zero.passes_run + 1].tolist()))
+    cf.close()
+    if not same:
+        return out
+    out.update(gpu_ms_per_decode_pass=spread(decode_ms), gpu_ms_per_polish_pass=spread(polish_ms), gpu_kernel_ms_per_sweep=spread(sweep_ms),
+               gpu_ms_polish_call_of_zero_labelling=zstats["polish_ms"])  # (every pass asked for is queued: those behind the fixed point return at once)
+    out["decode_pass_over_table_at_hbm_rate"] = out["gpu_ms_per_decode_pass"]["median"] / out["table_ms_at_hbm_rate"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweeps", type=int, default=30)
     ap.add_argument("--mcmc-sweeps", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--round", action="store_true", help="measure the rounding of the messages instead of the sweeps")
+    ap.add_argument("--polish", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if M.device_count() < 1:
         raise SystemExit("time_mplp.py: no HIP device is visible (nothing is measured without one)")
     ctx = M.Context(0)
-    result = dict(tool="tools/time_mplp.py", grids=[measure(ctx, cp, a.sweeps, a.mcmc_sweeps, a.repeats) for cp in (4, 3)])
+    if a.round:
+        result = dict(tool="tools/time_mplp.py --round", grids=[measure_round(ctx, cp, a.mcmc_sweeps, a.repeats, a.polish) for cp in (4, 3)])
+    else:
+        result = dict(tool="tools/time_mplp.py", grids=[measure(ctx, cp, a.sweeps, a.mcmc_sweeps, a.repeats) for cp in (4, 3)])
     ctx.close()
     text = json.dumps(result, indent=1, default=lambda o: o.item())  # (numpy scalars)
     if a.out:
