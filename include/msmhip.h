@@ -477,6 +477,34 @@ int msm_mplp_round_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, 
 /* What the last rounding on the context's GPU did: stats[0] ms in the conditioned decode's launches, [1] ms in the polish passes (with their energy
  * terms), [2] colour classes, [3] polish passes run. */
 int msm_mplp_round_gpu_stats(msm_ctx *ctx, double stats[4]);
+/* FORBIDDEN ENTRIES (opt-in; DESIGN.md 5.19 "Forbidden entries").  The entry points above refuse every table with a NaN or an infinity.  The ones below
+ * read a triplet entry that is NaN or +infinity as a forbidden label combination: theta^(a,b,c) = theta(a,b,c) where that is below +infinity and
+ * +infinity otherwise.  A message of +infinity says that label of that node is proved infeasible; messages are never NaN or -infinity.  The bound's
+ * factor term is the minimum over the combinations whose entry and three messages are all below +infinity (+infinity where there is none): D lies
+ * below the energy of every labelling that uses no forbidden entry, up to rounding, and D = +infinity says there is none.  Energies are E^: every term
+ * passed through the same mapping, so finite or +infinity and never NaN; the winner is the first strictly lower E^, never worse than the start in E^,
+ * and a start on a forbidden entry loses to any feasible candidate.  In the rounding a combination is +infinity when its entry or a message it would
+ * subtract is.  Still refused (MSM_ERR_INVALID, nothing written, the message names the table and the class of value): -infinity in the triplet table,
+ * any non-finite unary entry, and for the rounding a message that is NaN or -infinity.  On tables without a forbidden entry every output equals the
+ * plain entry point's, bit for bit: the host decides the route from the counts and runs the plain code there.
+ * [host] msm_mplp_classify counts: counts[0] the non-finite unary entries, counts[1..3] the NaN, +infinity and -infinity triplet entries. */
+int msm_mplp_classify(const double *unary, const double *tcosts, int32_t N, int32_t L, int32_t T, int64_t counts[4]);
+/* [host] msm_mplp_optimise under that reading; counts (may be NULL) receives msm_mplp_classify's four values */
+int msm_mplp_optimise_forbid(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
+                             int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages,
+                             int64_t counts[4]);
+/* the same on the GPU, bit for bit: one device pass counts both tables (counts, may be NULL), then the forbidden-aware kernels run where the table
+ * holds a forbidden entry and the plain ones where it does not */
+int msm_mplp_optimise_forbid_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                                 int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds,
+                                 double *messages, int64_t counts[4]);
+/* [host] msm_mplp_round under that reading (messages may hold +infinity); counts as above */
+int msm_mplp_round_forbid(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages,
+                          int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies, int64_t counts[4]);
+/* the same on the GPU, bit for bit */
+int msm_mplp_round_forbid_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                              const double *messages, int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies,
+                              int64_t counts[4]);
 /* [host] A STAND-IN for the binary solve of one label step of Fusion::optimize (I/Fusion/Fusion.h:198-229 hands the step to ELC's
  * reduction + FastPD, which are licence-restricted and FSL-bound: not reproduced).  Iterated conditional modes over x in {0,1}^N
  * (0: the node keeps its label, 1: it takes the proposed one) for
@@ -601,6 +629,12 @@ int msm_cost_mplp_round(msm_cost *c, int32_t sweeps, int32_t polish, int32_t the
                         double *energy, double *bound, double *energies);
 /* msm_mplp_round(mode 1) over the cost function's own device tables, filled as msm_cost_mplp_optimise fills them; energies: 1 + polish values */
 int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
+/* [host] on != 0: msm_cost_mplp_optimise / _round / _polish read the device triplet table's NaN and +infinity entries as forbidden combinations, as
+ * msm_mplp_optimise_forbid_gpu / msm_mplp_round_forbid_gpu do (the strain regulariser produces such entries where a label set lets control points
+ * meet); 0, the default: they refuse such a table. */
+int msm_cost_set_mplp_forbid(msm_cost *c, int32_t on);
+/* [host] what the last of those calls counted over the two device tables while the switch was on (msm_mplp_classify's four values) */
+int msm_cost_mplp_forbidden(msm_cost *c, int64_t counts[4]);
 /* evaluateTotalCostSum :55-77: parts = {unary, pairwise, triplet} sums in the reference's serial order */
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]);
 /* Optional HIP-event timing of the sampling kernel (k_unary_rays or k_unary_samples) of each unary-table launch, recorded on the

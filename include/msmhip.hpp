@@ -21,6 +21,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <mutex>
@@ -500,24 +501,39 @@ struct MplpRun {
     std::vector<double> energies, bounds;
 };
 // max-product linear programming over the tables mcmc_optimise reads, `sweeps` sweeps from `labeling`, which becomes the best candidate; with_bounds:
-// D after every sweep too (a second pass over the triplet table per sweep)
+// D after every sweep too (a second pass over the triplet table per sweep).  forbid (here and in the three calls below; msm_mplp_*_forbid): NaN and
+// +infinity triplet entries are forbidden label combinations instead of a refusal (DESIGN.md 5.19 "Forbidden entries"); counts (4 values, may be null):
+// the non-finite unary entries and the NaN, +infinity, -infinity triplet entries
 inline MplpRun mplp_optimise(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels, int sweeps,
-                             std::vector<int32_t> &labeling, bool with_bounds = false) {
+                             std::vector<int32_t> &labeling, bool with_bounds = false, bool forbid = false, int64_t *counts = nullptr) {
     MplpRun r;
     r.energies.assign((size_t)sweeps, 0.0);
     if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
-    check(msm_mplp_optimise(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), sweeps, labeling.data(),
-                            &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
+    const int32_t T = (int32_t)(triplets.size() / 3);
+    double *bounds = with_bounds ? r.bounds.data() : nullptr;
+    if (forbid)
+        check(msm_mplp_optimise_forbid(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, sweeps, labeling.data(), &r.sweeps_run,
+                                       &r.energy, &r.bound, r.energies.data(), bounds, nullptr, counts));
+    else
+        check(msm_mplp_optimise(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, sweeps, labeling.data(), &r.sweeps_run, &r.energy,
+                                &r.bound, r.energies.data(), bounds, nullptr));
     return r;
 }
 // the same with the sweeps on the GPU (msm_mplp_optimise_gpu): the same labeling, energies and bounds, bit for bit
 inline MplpRun mplp_optimise_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes,
-                                 int num_labels, int sweeps, std::vector<int32_t> &labeling, bool with_bounds = false) {
+                                 int num_labels, int sweeps, std::vector<int32_t> &labeling, bool with_bounds = false, bool forbid = false,
+                                 int64_t *counts = nullptr) {
     MplpRun r;
     r.energies.assign((size_t)sweeps, 0.0);
     if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
-    check(msm_mplp_optimise_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3), sweeps,
-                                labeling.data(), &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
+    const int32_t T = (int32_t)(triplets.size() / 3);
+    double *bounds = with_bounds ? r.bounds.data() : nullptr;
+    if (forbid)
+        check(msm_mplp_optimise_forbid_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, sweeps, labeling.data(),
+                                           &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), bounds, nullptr, counts));
+    else
+        check(msm_mplp_optimise_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, sweeps, labeling.data(),
+                                    &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), bounds, nullptr));
     return r;
 }
 // What a rounding of MPLP's messages hands back besides the labeling (msm_mplp_round; DESIGN.md 5.19 "Rounding"): the polish passes it ran, the
@@ -535,20 +551,34 @@ inline std::vector<int32_t> mplp_colouring(const std::vector<int32_t> &triplets,
 }
 // rounds the messages (empty: all zero) to a labelling: mode 0 the conditioned decode and its polish passes, mode 1 the polish passes of `labeling`
 inline MplpRound mplp_round(const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes, int num_labels,
-                            const std::vector<double> &messages, int mode, int polish, std::vector<int32_t> &labeling) {
+                            const std::vector<double> &messages, int mode, int polish, std::vector<int32_t> &labeling, bool forbid = false,
+                            int64_t *counts = nullptr) {
     MplpRound r;
     r.energies.assign((size_t)(mode == 0 ? 2 : 1) + (size_t)std::max(polish, 0), 0.0);
-    check(msm_mplp_round(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
-                         messages.empty() ? nullptr : messages.data(), mode, polish, labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
+    const int32_t T = (int32_t)(triplets.size() / 3);
+    const double *m = messages.empty() ? nullptr : messages.data();
+    if (forbid)
+        check(msm_mplp_round_forbid(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, m, mode, polish, labeling.data(), &r.passes_run,
+                                    &r.energy, r.energies.data(), counts));
+    else
+        check(msm_mplp_round(unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, m, mode, polish, labeling.data(), &r.passes_run,
+                             &r.energy, r.energies.data()));
     return r;
 }
 // the same on the GPU (msm_mplp_round_gpu), bit for bit
 inline MplpRound mplp_round_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &tcosts, const std::vector<int32_t> &triplets, int num_nodes,
-                                int num_labels, const std::vector<double> &messages, int mode, int polish, std::vector<int32_t> &labeling) {
+                                int num_labels, const std::vector<double> &messages, int mode, int polish, std::vector<int32_t> &labeling,
+                                bool forbid = false, int64_t *counts = nullptr) {
     MplpRound r;
     r.energies.assign((size_t)(mode == 0 ? 2 : 1) + (size_t)std::max(polish, 0), 0.0);
-    check(msm_mplp_round_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, (int32_t)(triplets.size() / 3),
-                             messages.empty() ? nullptr : messages.data(), mode, polish, labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
+    const int32_t T = (int32_t)(triplets.size() / 3);
+    const double *m = messages.empty() ? nullptr : messages.data();
+    if (forbid)
+        check(msm_mplp_round_forbid_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, m, mode, polish,
+                                        labeling.data(), &r.passes_run, &r.energy, r.energies.data(), counts));
+    else
+        check(msm_mplp_round_gpu(ctx.handle(), unary_costs.data(), tcosts.data(), triplets.data(), num_nodes, num_labels, T, m, mode, polish, labeling.data(),
+                                 &r.passes_run, &r.energy, r.energies.data()));
     return r;
 }
 // what several chains from one start hand back: labelings chains x N, energies per chain, best by std::min_element's rule
@@ -731,6 +761,14 @@ public:
         check(msm_cost_mcmc_optimise_chains(h_, dist_param, mciters, seeds.data(), (int32_t)seeds.size(), labeling.data(), r.labelings.data(), r.energies.data(),
                                             &r.best));
         return r;
+    }
+    // the three MPLP calls below read the device triplet table's NaN and +infinity entries as forbidden combinations instead of refusing the table
+    // (msm_cost_set_mplp_forbid; DESIGN.md 5.19 "Forbidden entries"), and what the last of them counted (msm_cost_mplp_forbidden)
+    void set_mplp_forbid(bool on = true) { check(msm_cost_set_mplp_forbid(h_, on ? 1 : 0)); }
+    std::array<int64_t, 4> mplp_forbidden() {
+        std::array<int64_t, 4> counts{};
+        check(msm_cost_mplp_forbidden(h_, counts.data()));
+        return counts;
     }
     // computeUnaryCosts + computeTripletCosts + MPLP with both tables staying on the device (msm_cost_mplp_optimise): what computeUnaryCosts() +
     // computeTripletCosts() + msmhip::mplp_optimise give, bit for bit

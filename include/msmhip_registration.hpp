@@ -64,6 +64,10 @@ struct LevelOptions {
     // one polish call on the winner (DiscreteCostFunction::mplp_round; what MSMHIP_MPLP_ROUND=on and MSMHIP_MPLP_POLISH=n ask of the executables)
     bool mplp_round = false;
     int mplp_polish = 8;
+    // with mplp: NaN and +infinity entries of the triplet table are forbidden label combinations instead of a refusal (DiscreteCostFunction::
+    // set_mplp_forbid, DESIGN.md 5.19 "Forbidden entries"; what MSMHIP_MPLP_FORBID=on asks of the executables) -- the strain regulariser produces
+    // such entries wherever a label set lets control points meet, as the unscaled sampling grid does
+    bool mplp_forbid = false;
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
@@ -151,6 +155,7 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
     DiscreteCostFunction costfct(ctx, o.cost);
     costfct.set_meshes(TARGET, SOURCE, CPGRID);  // _ORIG, _oCPgrid
     costfct.set_featurespace(src_feat, D);
+    if (o.mplp_forbid) costfct.set_mplp_forbid(true);
     costfct.set_spacings(MAXSEP, MVDmax);
     std::unique_ptr<Mesh> anat_sphere;
     if (o.cost.regularisermode == 4 || o.cost.regularisermode == 5) {  // initialize_level, M/mesh_registration.cpp:91-104

@@ -790,23 +790,52 @@ def _mplp_tables(unary, tcosts, triplets):
     return (U, tc, tr), (pu, ptc, tr.ctypes.data_as(c_ip), N, L, T)
 
 
-def mplp_optimise(unary, tcosts, triplets, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+def _mplp_counts(counts):
+    """the pointer of the optional counts argument of the forbid entry points: an int64 array of 4 that the call fills, or NULL"""
+    if counts is None:
+        return C.cast(None, c_lp)
+    assert counts.dtype == np.int64 and counts.size == 4 and counts.flags.c_contiguous and counts.flags.writeable
+    return counts.ctypes.data_as(c_lp)
+
+
+def mplp_classify(unary, tcosts):
+    """msm_mplp_classify [host]: int64 array of (non-finite unary entries, NaN, +inf, -inf triplet entries) -- what the forbid route of the MPLP entry
+    points decides by (DESIGN.md 5.19 "Forbidden entries")"""
+    U, pu = _d(unary)
+    tc, ptc = _d(tcosts)
+    L, N = U.shape
+    T = tc.size // L ** 3
+    assert tc.size == T * L ** 3
+    counts = np.zeros(4, dtype=np.int64)
+    check(lib().msm_mplp_classify(pu, ptc, N, L, T, counts.ctypes.data_as(c_lp)))
+    return counts
+
+
+def mplp_optimise(unary, tcosts, triplets, labeling, sweeps=30, bound=True, bounds=False, messages=False, forbid=False, counts=None):
     """msm_mplp_optimise [host]: max-product linear programming over the unary (L x N) and triplet (T x L x L x L) tables -- an extension, not newMSM's
     (DESIGN.md 5.19).  Returns MplpResult(labeling, sweeps_run, energy, bound, energies, bounds, messages): the labelling is the lowest-energy one among
     the start and the decode after every sweep (never worse than the start), bound is a lower bound on every labelling's energy.  bounds=True costs a
-    second pass over the triplet table per sweep, bound=True alone one pass."""
+    second pass over the triplet table per sweep, bound=True alone one pass.  forbid (msm_mplp_optimise_forbid): NaN and +inf triplet entries are
+    forbidden label combinations instead of a refusal (DESIGN.md 5.19 "Forbidden entries"): energies are then finite or +inf, the bound holds for the
+    labellings that use no forbidden entry, and counts (an int64 array of 4, optional) receives mplp_classify's values."""
     keep, head = _mplp_tables(unary, tcosts, triplets)
     out, tail = _mplp_outputs(head[3], head[4], head[5], sweeps, labeling, bound, bounds, messages)
-    check(lib().msm_mplp_optimise(*head, int(sweeps), *tail))
+    if forbid:
+        check(lib().msm_mplp_optimise_forbid(*head, int(sweeps), *tail, _mplp_counts(counts)))
+    else:
+        check(lib().msm_mplp_optimise(*head, int(sweeps), *tail))
     return _mplp_result(out)
 
 
-def mplp_optimise_gpu(ctx, unary, tcosts, triplets, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+def mplp_optimise_gpu(ctx, unary, tcosts, triplets, labeling, sweeps=30, bound=True, bounds=False, messages=False, forbid=False, counts=None):
     """msm_mplp_optimise_gpu: mplp_optimise with the sweeps on the GPU (a launch per level of mcmc_schedule, a workgroup per factor); the same
-    MplpResult, bit for bit"""
+    MplpResult, bit for bit; forbid: msm_mplp_optimise_forbid_gpu, counts filled by the device's classification pass"""
     keep, head = _mplp_tables(unary, tcosts, triplets)
     out, tail = _mplp_outputs(head[3], head[4], head[5], sweeps, labeling, bound, bounds, messages)
-    check(lib().msm_mplp_optimise_gpu(ctx.h, *head, int(sweeps), *tail))
+    if forbid:
+        check(lib().msm_mplp_optimise_forbid_gpu(ctx.h, *head, int(sweeps), *tail, _mplp_counts(counts)))
+    else:
+        check(lib().msm_mplp_optimise_gpu(ctx.h, *head, int(sweeps), *tail))
     return _mplp_result(out)
 
 
@@ -845,23 +874,31 @@ def mplp_colouring(triplets, N):
     return colour, classes.value
 
 
-def mplp_round(unary, tcosts, triplets, labeling, messages=None, mode=0, polish=8):
+def mplp_round(unary, tcosts, triplets, labeling, messages=None, mode=0, polish=8, forbid=False, counts=None):
     """msm_mplp_round [host]: rounds MPLP's messages (T x 3 x L; None: all zero) to a labelling -- the conditioned decode over the colour classes and
     `polish` passes of iterated conditional modes (mode 0), or the polish passes of `labeling` alone (mode 1); DESIGN.md 5.19 "Rounding".  Returns
-    MplpRound(labeling, passes_run, energy, energies): the lowest-energy candidate, never worse than the labelling handed in."""
+    MplpRound(labeling, passes_run, energy, energies): the lowest-energy candidate, never worse than the labelling handed in.  forbid
+    (msm_mplp_round_forbid): NaN / +inf triplet entries are forbidden combinations and the messages may hold +inf; counts as in mplp_optimise."""
     keep, head = _mplp_tables(unary, tcosts, triplets)
     m, pm = _mplp_messages(messages, head[5], head[4])
     out, tail = _mplp_round_outputs(head[3], mode, polish, labeling)
-    check(lib().msm_mplp_round(*head, pm, int(mode), int(polish), *tail))
+    if forbid:
+        check(lib().msm_mplp_round_forbid(*head, pm, int(mode), int(polish), *tail, _mplp_counts(counts)))
+    else:
+        check(lib().msm_mplp_round(*head, pm, int(mode), int(polish), *tail))
     return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
 
 
-def mplp_round_gpu(ctx, unary, tcosts, triplets, labeling, messages=None, mode=0, polish=8):
-    """msm_mplp_round_gpu: mplp_round on the GPU (a launch per colour class and pass); the same MplpRound, bit for bit"""
+def mplp_round_gpu(ctx, unary, tcosts, triplets, labeling, messages=None, mode=0, polish=8, forbid=False, counts=None):
+    """msm_mplp_round_gpu: mplp_round on the GPU (a launch per colour class and pass); the same MplpRound, bit for bit; forbid:
+    msm_mplp_round_forbid_gpu"""
     keep, head = _mplp_tables(unary, tcosts, triplets)
     m, pm = _mplp_messages(messages, head[5], head[4])
     out, tail = _mplp_round_outputs(head[3], mode, polish, labeling)
-    check(lib().msm_mplp_round_gpu(ctx.h, *head, pm, int(mode), int(polish), *tail))
+    if forbid:
+        check(lib().msm_mplp_round_forbid_gpu(ctx.h, *head, pm, int(mode), int(polish), *tail, _mplp_counts(counts)))
+    else:
+        check(lib().msm_mplp_round_gpu(ctx.h, *head, pm, int(mode), int(polish), *tail))
     return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
 
 
@@ -1291,6 +1328,17 @@ class DiscreteCostFunction:
         check(lib().msm_cost_mcmc_optimise_chains(self.h, float(mcparam), int(iters), ps, K, lab.ctypes.data_as(c_ip), labs.ctypes.data_as(c_ip),
                                                   E.ctypes.data_as(c_dp), C.byref(best)))
         return lab, labs, E, best.value
+
+    def set_mplp_forbid(self, on=True):
+        """msm_cost_set_mplp_forbid: mplp_optimise / mplp_round / mplp_polish read the device triplet table's NaN and +inf entries as forbidden label
+        combinations (DESIGN.md 5.19 "Forbidden entries") instead of refusing the table"""
+        check(lib().msm_cost_set_mplp_forbid(self.h, int(bool(on))))
+
+    def mplp_forbidden(self):
+        """msm_cost_mplp_forbidden: what the last such call counted -- int64 (non-finite unary, NaN, +inf, -inf triplet entries)"""
+        counts = np.zeros(4, dtype=np.int64)
+        check(lib().msm_cost_mplp_forbidden(self.h, counts.ctypes.data_as(c_lp)))
+        return counts
 
     def mplp_optimise(self, labeling, sweeps=30, bound=True, bounds=False, messages=False):
         """msm_cost_mplp_optimise: computeUnaryCosts + computeTripletCosts + MPLP with both tables staying on the device; the MplpResult that

@@ -672,7 +672,21 @@ int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32
     int N, L, T;
     MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
     const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
-    return mplp_run_device(c->ctx, "msm_mplp_optimise", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o);
+    return mplp_run_device(c->ctx, "msm_mplp_optimise", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o, c->mplp_forbid, c->mplp_counts);
+}
+
+// the switch to the forbidden-entry reading of the triplet table (DESIGN.md 5.19 "Forbidden entries") for the three calls here, and what the last
+// of them counted
+int msm_cost_set_mplp_forbid(msm_cost *c, int32_t on) {
+    if (!c) return fail(MSM_ERR_INVALID, "msm_cost_set_mplp_forbid: null argument");
+    c->mplp_forbid = on != 0;
+    return MSM_OK;
+}
+
+int msm_cost_mplp_forbidden(msm_cost *c, int64_t counts[4]) {
+    if (!c || !counts) return fail(MSM_ERR_INVALID, "msm_cost_mplp_forbidden: null argument");
+    std::copy(c->mplp_counts, c->mplp_counts + 4, counts);
+    return MSM_OK;
 }
 
 // MPLP's sweeps, then the rounding of mode 0 on the messages they left on the device, the sweeps' winner handed in (DESIGN.md 5.19 "Rounding").
@@ -689,12 +703,14 @@ int msm_cost_mplp_round(msm_cost *c, int32_t sweeps, int32_t polish, int32_t the
     int32_t run = 0;
     double b = 0.0;
     const MplpOutputs o = {lab.data(), &run, nullptr, bound ? &b : nullptr, nullptr, nullptr, nullptr};
-    MSM_TRY(mplp_run_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o));
+    MSM_TRY(mplp_run_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o, c->mplp_forbid, c->mplp_counts));
     const MplpRoundOutputs r = {lab.data(), passes_run, energy, energies};
-    MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, true, false, c->triplets.data(), N, L, T, 0, polish, r));
+    MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, true, false, c->triplets.data(), N, L, T, 0, polish, r,
+                              c->mplp_forbid, c->mplp_counts));
     if (then_polish) {
         const MplpRoundOutputs r1 = {lab.data(), nullptr, energy, nullptr};
-        MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, false, c->triplets.data(), N, L, T, 1, polish, r1));
+        MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, false, c->triplets.data(), N, L, T, 1, polish, r1,
+                                  c->mplp_forbid, c->mplp_counts));
     }
     std::copy(lab.begin(), lab.end(), labeling);
     if (sweeps_run) *sweeps_run = run;
@@ -711,7 +727,8 @@ int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t
     int N, L, T;
     MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
     const MplpRoundOutputs r = {labeling, passes_run, energy, energies};
-    return mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, true, c->triplets.data(), N, L, T, 1, polish, r);
+    return mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, true, c->triplets.data(), N, L, T, 1, polish, r, c->mplp_forbid,
+                             c->mplp_counts);
 }
 
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on

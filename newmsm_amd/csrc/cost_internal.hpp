@@ -90,6 +90,9 @@ struct msm_cost {
     std::vector<double> h_U;
     DevBuf<unsigned long long> d_counters;
     int64_t counters[4] = {0, 0, 0, 0};
+    // msm_cost_set_mplp_forbid: the MPLP calls read NaN / +inf triplet entries as forbidden combinations; what the last such call counted
+    bool mplp_forbid = false;
+    int64_t mplp_counts[4] = {0, 0, 0, 0};
     // scratch for the range kernel
     DevBuf<uint32_t> d_slots;
     // scratch of the unary kernels

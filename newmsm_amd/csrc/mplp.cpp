@@ -14,6 +14,7 @@ struct MplpScratch {
     DevBuf<double> U, tc;  // the host tables of msm_mplp_optimise_gpu
     DevBuf<int4> sched;
     DevBuf<int32_t> inc_ptr, inc_slot, start, labs, changed, flags;
+    DevBuf<unsigned long long> counts;  // k_mplp_classify: four of the tables, four of the rounding's messages
     DevBuf<double> m, eterms, bterms;
     // the rounding's own (mplp_round_device): it leaves m alone
     DevBuf<int4> tri;
@@ -37,6 +38,26 @@ int refuse_non_finite(const char *what, const char *table) {
                 "%s: the %s table holds a non-finite value (NaN or infinity); clean the input data first (--fixnan), and mind that a label set which lets "
                 "two control points meet collapses a triangle and makes the regulariser non-finite (the unscaled sampling grid does: use --rescaleL)",
                 what, table);
+}
+
+// the refusals of the forbidden-entry reading (DESIGN.md 5.19 "Forbidden entries"): each names the table and the class of value
+int refuse_minus_infinity(const char *what) {
+    return fail(MSM_ERR_INVALID,
+                "%s: the triplet table holds -infinity; the forbidden-entry reading takes NaN and +infinity as forbidden label combinations and nothing "
+                "else",
+                what);
+}
+
+int refuse_messages(const char *what, const int64_t mc[4]) {
+    return fail(MSM_ERR_INVALID, "%s: the messages hold %s; under the forbidden-entry reading a message is finite or +infinity", what, mc[1] ? "a NaN" : "-infinity");
+}
+
+// the forbid route's refusals over counted tables; MSM_OK leaves *forbidden = whether the triplet table holds a forbidden entry
+int check_counts(const char *what, const int64_t counts[4], bool *forbidden) {
+    if (counts[0]) return refuse_non_finite(what, "unary");
+    if (counts[3]) return refuse_minus_infinity(what);
+    *forbidden = counts[1] + counts[2] > 0;
+    return MSM_OK;
 }
 
 int refuse_label_count(const char *what, int L) {
@@ -69,20 +90,37 @@ int mplp_round_check(const char *what, int L, int mode, int polish) {
 }
 
 int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, bool use_scratch_m, bool check_tables,
-                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o) {
+                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o, bool forbid, int64_t *counts) {
     MplpScratch &s = mplp_scratch(ctx);
     const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
     if (use_scratch_m) d_m = s.m.p;
     if (mode != 0 || nm == 0) d_m = nullptr;  // mode 1 reads no messages
-    int32_t bad[4] = {0, 0, 0, 0};
-    if (s.flags.zero(4, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 4);
-    if (check_tables) MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
-    if (d_m) MSM_TRY(launch_mplp_finite(ctx, d_m, nm, nullptr, 0, s.flags.p + 2));
-    MSM_TRY(s.flags.download(bad, 4, ctx));
-    MSM_TRY(check_status(ctx, what));
-    if (bad[0]) return refuse_non_finite(what, "unary");
-    if (bad[1]) return refuse_non_finite(what, "triplet");
-    if (bad[2]) return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
+    bool F = false;  // the forbidden-aware kernels: taken where the tables or the messages call for them, the plain ones otherwise
+    if (forbid) {
+        // one pass over both tables and one over the messages; check_tables false: counts holds what the caller's pass over these tables counted
+        int64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are downloaded as they are");
+        if (s.counts.zero(8, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int64_t) * 8);
+        if (check_tables) MSM_TRY(launch_mplp_classify(ctx, d_U, nU, d_tc, ntc, s.counts.p));
+        if (d_m) MSM_TRY(launch_mplp_classify(ctx, nullptr, 0, d_m, nm, s.counts.p + 4));
+        MSM_TRY(s.counts.download(reinterpret_cast<unsigned long long *>(got), 8, ctx));
+        MSM_TRY(check_status(ctx, what));
+        if (!check_tables && counts) std::copy(counts, counts + 4, got);
+        MSM_TRY(check_counts(what, got, &F));
+        if (got[5] || got[7]) return refuse_messages(what, got + 4);
+        F |= got[6] > 0;  // a message of +infinity
+        if (counts) std::copy(got, got + 4, counts);
+    } else {
+        int32_t bad[4] = {0, 0, 0, 0};
+        if (s.flags.zero(4, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 4);
+        if (check_tables) MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
+        if (d_m) MSM_TRY(launch_mplp_finite(ctx, d_m, nm, nullptr, 0, s.flags.p + 2));
+        MSM_TRY(s.flags.download(bad, 4, ctx));
+        MSM_TRY(check_status(ctx, what));
+        if (bad[0]) return refuse_non_finite(what, "unary");
+        if (bad[1]) return refuse_non_finite(what, "triplet");
+        if (bad[2]) return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
+    }
     MSM_TRY(mplp_round_check(what, L, mode, polish));
 
     MplpIncidence inc;
@@ -151,7 +189,7 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
     MSM_TRY(snapshot(0));
     if (mode == 0) {
         MSM_HIP(hipEventRecord(s.ev[0], ctx->stream));
-        for (int k = 0; k < classes; ++k) MSM_TRY(launch_mplp_round(ctx, a, col.class_off[(size_t)k], col.class_off[(size_t)k + 1] - col.class_off[(size_t)k], k));
+        for (int k = 0; k < classes; ++k) MSM_TRY(launch_mplp_round(ctx, a, col.class_off[(size_t)k], col.class_off[(size_t)k + 1] - col.class_off[(size_t)k], k, F));
         MSM_HIP(hipEventRecord(s.ev[1], ctx->stream));
         MSM_TRY(snapshot(1));
     }
@@ -162,11 +200,11 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
         MSM_HIP(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
         decode_ms = ms;
     }
-    double e_last = mcmc_energy_of_terms(terms.data(), N, T);
+    double e_last = mplp_energy_of_terms(terms.data(), N, T, F);
     MplpWinner win(o.labeling, N, e_last);
     energies[0] = e_last;
     if (mode == 0) {
-        energies[1] = e_last = mcmc_energy_of_terms(terms.data() + nterms, N, T);
+        energies[1] = e_last = mplp_energy_of_terms(terms.data() + nterms, N, T, F);
         win.offer(labs.data() + N, N, e_last);
     }
 
@@ -177,7 +215,7 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
         MSM_HIP(hipEventRecord(s.ev[0], ctx->stream));
         for (int j = 0; j < n; ++j) {
             for (int k = 0; k < classes; ++k)
-                MSM_TRY(launch_mplp_polish(ctx, a, col.class_off[(size_t)k], col.class_off[(size_t)k + 1] - col.class_off[(size_t)k], p0 + j));
+                MSM_TRY(launch_mplp_polish(ctx, a, col.class_off[(size_t)k], col.class_off[(size_t)k + 1] - col.class_off[(size_t)k], p0 + j, F));
             MSM_TRY(snapshot((size_t)j));
         }
         MSM_HIP(hipEventRecord(s.ev[1], ctx->stream));
@@ -194,7 +232,7 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
                 break;
             }
             run = p + 1;
-            energies[(size_t)first + p] = e_last = mcmc_energy_of_terms(terms.data() + (size_t)j * nterms, N, T);
+            energies[(size_t)first + p] = e_last = mplp_energy_of_terms(terms.data() + (size_t)j * nterms, N, T, F);
             win.offer(labs.data() + (size_t)j * N, N, e_last);
         }
     }
@@ -211,17 +249,28 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
 }
 
 int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, int sweeps,
-                    const MplpOutputs &o) {
+                    const MplpOutputs &o, bool forbid, int64_t *counts) {
     MplpScratch &s = mplp_scratch(ctx);
     const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
     // the refusals that need the tables: one pass over both, before anything else is launched
-    int32_t bad[2] = {0, 0};
-    if (s.flags.zero(2, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 2);
-    MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
-    MSM_TRY(s.flags.download(bad, 2, ctx));
-    MSM_TRY(check_status(ctx, what));
-    if (bad[0]) return refuse_non_finite(what, "unary");
-    if (bad[1]) return refuse_non_finite(what, "triplet");
+    bool F = false;  // the forbidden-aware kernels: only where the table holds a forbidden entry, so a finite table runs the plain ones
+    if (forbid) {
+        int64_t got[4] = {0, 0, 0, 0};
+        if (s.counts.zero(4, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int64_t) * 4);
+        MSM_TRY(launch_mplp_classify(ctx, d_U, nU, d_tc, ntc, s.counts.p));
+        MSM_TRY(s.counts.download(reinterpret_cast<unsigned long long *>(got), 4, ctx));
+        MSM_TRY(check_status(ctx, what));
+        MSM_TRY(check_counts(what, got, &F));
+        if (counts) std::copy(got, got + 4, counts);
+    } else {
+        int32_t bad[2] = {0, 0};
+        if (s.flags.zero(2, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 2);
+        MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
+        MSM_TRY(s.flags.download(bad, 2, ctx));
+        MSM_TRY(check_status(ctx, what));
+        if (bad[0]) return refuse_non_finite(what, "unary");
+        if (bad[1]) return refuse_non_finite(what, "triplet");
+    }
     if (L > kMplpMaxLabels) return refuse_label_count(what, L);
 
     McmcSchedule sch;
@@ -281,7 +330,7 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
     MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.eterms.p));
     MSM_TRY(s.eterms.download(eterms.data(), nterms, ctx));
     MSM_TRY(check_status(ctx, what));
-    MplpWinner win(o.labeling, N, mcmc_energy_of_terms(eterms.data(), N, T));
+    MplpWinner win(o.labeling, N, mplp_energy_of_terms(eterms.data(), N, T, F));
 
     std::vector<int32_t> labs((size_t)chunk * N), changed((size_t)sweeps, 0);
     std::vector<double> energies((size_t)sweeps), bounds(o.bounds ? (size_t)sweeps : 0);
@@ -293,11 +342,11 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
         MSM_HIP(hipEventRecord(s.ev[0], ctx->stream));
         for (int j = 0; j < n; ++j) {
             for (int lv = 0; lv < sch.levels(); ++lv)
-                MSM_TRY(launch_mplp_update(ctx, a, sch.level_off[(size_t)lv], sch.level_off[(size_t)lv + 1] - sch.level_off[(size_t)lv], k0 + j));
+                MSM_TRY(launch_mplp_update(ctx, a, sch.level_off[(size_t)lv], sch.level_off[(size_t)lv + 1] - sch.level_off[(size_t)lv], k0 + j, F));
             MSM_TRY(launch_mplp_decode(ctx, a, s.labs.p + (size_t)j * N, s.bterms.p + (size_t)j * nterms));
             c.a.labeling = s.labs.p + (size_t)j * N;
             MSM_TRY(launch_mcmc_chain_terms(ctx, c, s.eterms.p + (size_t)j * nterms));
-            if (o.bounds) MSM_TRY(launch_mplp_factor_terms(ctx, a, s.bterms.p + (size_t)j * nterms + N, k0 + j));
+            if (o.bounds) MSM_TRY(launch_mplp_factor_terms(ctx, a, s.bterms.p + (size_t)j * nterms + N, k0 + j, F));
         }
         MSM_HIP(hipEventRecord(s.ev[1], ctx->stream));
         MSM_TRY(s.labs.download(labs.data(), (size_t)n * N, ctx));
@@ -315,7 +364,7 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
                 break;
             }
             run = k + 1;
-            energies[(size_t)k] = e_last = mcmc_energy_of_terms(eterms.data() + (size_t)j * nterms, N, T);
+            energies[(size_t)k] = e_last = mplp_energy_of_terms(eterms.data() + (size_t)j * nterms, N, T, F);
             win.offer(labs.data() + (size_t)j * N, N, e_last);
             if (o.bounds) bounds[(size_t)k] = b_last = mplp_bound_of_terms(bterms.data() + (size_t)j * nterms, N, T);
         }
@@ -327,7 +376,7 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
     double bound = b_last;
     if (o.bound && !(o.bounds && run > 0)) {  // one pass over the table for the bound of the last messages
         MSM_TRY(launch_mplp_decode(ctx, a, nullptr, s.bterms.p));
-        MSM_TRY(launch_mplp_factor_terms(ctx, a, s.bterms.p + N, -1));
+        MSM_TRY(launch_mplp_factor_terms(ctx, a, s.bterms.p + N, -1, F));
         MSM_TRY(s.bterms.download(bterms.data(), nterms, ctx));
         MSM_TRY(check_status(ctx, what));
         bound = mplp_bound_of_terms(bterms.data(), N, T);
@@ -355,27 +404,34 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
 
 }  // namespace msm
 
-extern "C" {
+namespace {
 
-int msm_mplp_optimise(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps, int32_t *labeling,
-                      int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages) {
+// msm_mplp_optimise and msm_mplp_optimise_forbid (forbid; counts may be null)
+int optimise_host(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps, const MplpOutputs &o,
+                  bool forbid, int64_t *counts) {
     const char *what = "msm_mplp_optimise";
-    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, sweeps, labeling));
-    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, sweeps, labeling));
-    if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
-    if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
+    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, sweeps, o.labeling));
+    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, sweeps, o.labeling));
+    bool F = false;  // the plain literal where the table holds no forbidden entry
+    if (forbid) {
+        int64_t got[4];
+        mplp_classify(unary, (size_t)L * N, tcosts, (size_t)T * L * L * L, got);
+        MSM_TRY(check_counts(what, got, &F));
+        if (counts) std::copy(got, got + 4, counts);
+    } else {
+        if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
+        if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
+    }
     if (L > kMplpMaxLabels) return refuse_label_count(what, L);
-    const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
-    mplp_run_host(unary, tcosts, triplets, N, L, T, sweeps, o);
+    mplp_run_host(unary, tcosts, triplets, N, L, T, sweeps, o, F);
     return MSM_OK;
 }
 
-int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
-                          int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages) {
-    const char *what = "msm_mplp_optimise_gpu";
-    if (!ctx) return fail(MSM_ERR_INVALID, "%s: null context", what);
-    MSM_TRY(check_pointers("msm_mplp_optimise", unary, tcosts, triplets, N, L, T, sweeps, labeling));
-    MSM_TRY(mplp_check_arguments("msm_mplp_optimise", triplets, N, L, T, sweeps, labeling));
+int optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
+                 const MplpOutputs &o, bool forbid, int64_t *counts) {
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mplp_optimise_gpu: null context");
+    MSM_TRY(check_pointers("msm_mplp_optimise", unary, tcosts, triplets, N, L, T, sweeps, o.labeling));
+    MSM_TRY(mplp_check_arguments("msm_mplp_optimise", triplets, N, L, T, sweeps, o.labeling));
     MSM_HIP(hipSetDevice(ctx->device));
     MSM_TRY(drop_ctx_pending(ctx));
     MplpScratch &s = mplp_scratch(ctx);
@@ -384,8 +440,84 @@ int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcost
     if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
     MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
     MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
-    const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
-    return mplp_run_device(ctx, "msm_mplp_optimise", s.U.p, s.tc.p, triplets, N, L, T, sweeps, o);
+    return mplp_run_device(ctx, "msm_mplp_optimise", s.U.p, s.tc.p, triplets, N, L, T, sweeps, o, forbid, counts);
+}
+
+int round_host(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages, int32_t mode,
+               int32_t polish, const MplpRoundOutputs &o, bool forbid, int64_t *counts) {
+    const char *what = "msm_mplp_round";
+    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, o.labeling));
+    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, o.labeling));
+    bool F = false;
+    if (forbid) {
+        int64_t got[4], mc[4] = {0, 0, 0, 0};
+        mplp_classify(unary, (size_t)L * N, tcosts, (size_t)T * L * L * L, got);
+        MSM_TRY(check_counts(what, got, &F));
+        if (mode == 0 && messages) mplp_classify(nullptr, 0, messages, 3 * (size_t)T * L, mc);
+        if (mc[1] || mc[3]) return refuse_messages(what, mc);
+        F |= mc[2] > 0;  // a message of +infinity
+        if (counts) std::copy(got, got + 4, counts);
+    } else {
+        if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
+        if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
+        if (mode == 0 && messages && !mplp_all_finite(messages, 3 * (size_t)T * L))
+            return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
+    }
+    MSM_TRY(mplp_round_check(what, L, mode, polish));
+    mplp_round_host(unary, tcosts, triplets, N, L, T, mode == 0 ? messages : nullptr, mode, polish, o, F);
+    return MSM_OK;
+}
+
+int round_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages,
+              int32_t mode, int32_t polish, const MplpRoundOutputs &o, bool forbid, int64_t *counts) {
+    const char *what = "msm_mplp_round";
+    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: null context");
+    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, o.labeling));
+    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, o.labeling));
+    MSM_HIP(hipSetDevice(ctx->device));
+    MSM_TRY(drop_ctx_pending(ctx));
+    MplpScratch &s = mplp_scratch(ctx);
+    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L;
+    const bool with_m = mode == 0 && messages && nm;
+    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
+    if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
+    if (with_m && s.rm.ensure(nm) != hipSuccess) return stage_alloc_failed(sizeof(double) * nm);
+    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
+    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
+    if (with_m) MSM_TRY(upload_in_pieces(ctx, s.rm.p, messages, sizeof(double) * nm));
+    return mplp_round_device(ctx, what, s.U.p, s.tc.p, with_m ? s.rm.p : nullptr, false, true, triplets, N, L, T, mode, polish, o, forbid, counts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_mplp_optimise(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps, int32_t *labeling,
+                      int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages) {
+    return optimise_host(unary, tcosts, triplets, N, L, T, sweeps, {labeling, sweeps_run, energy, bound, energies, bounds, messages}, false, nullptr);
+}
+
+int msm_mplp_optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
+                          int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages) {
+    return optimise_gpu(ctx, unary, tcosts, triplets, N, L, T, sweeps, {labeling, sweeps_run, energy, bound, energies, bounds, messages}, false, nullptr);
+}
+
+int msm_mplp_classify(const double *unary, const double *tcosts, int32_t N, int32_t L, int32_t T, int64_t counts[4]) {
+    if (!unary || !counts || N <= 0 || L <= 0 || T < 0 || (T > 0 && !tcosts)) return fail(MSM_ERR_INVALID, "msm_mplp_classify: bad arguments");
+    mplp_classify(unary, (size_t)L * N, tcosts, (size_t)T * L * L * L, counts);
+    return MSM_OK;
+}
+
+int msm_mplp_optimise_forbid(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps,
+                             int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages,
+                             int64_t counts[4]) {
+    return optimise_host(unary, tcosts, triplets, N, L, T, sweeps, {labeling, sweeps_run, energy, bound, energies, bounds, messages}, true, counts);
+}
+
+int msm_mplp_optimise_forbid_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                                 int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds,
+                                 double *messages, int64_t counts[4]) {
+    return optimise_gpu(ctx, unary, tcosts, triplets, N, L, T, sweeps, {labeling, sweeps_run, energy, bound, energies, bounds, messages}, true, counts);
 }
 
 int msm_mplp_colouring(const int32_t *triplets, int32_t N, int32_t T, int32_t *colour, int32_t *classes) {
@@ -404,38 +536,23 @@ int msm_mplp_colouring(const int32_t *triplets, int32_t N, int32_t T, int32_t *c
 
 int msm_mplp_round(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages, int32_t mode,
                    int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies) {
-    const char *what = "msm_mplp_round";
-    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, labeling));
-    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, labeling));
-    if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
-    if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
-    if (mode == 0 && messages && !mplp_all_finite(messages, 3 * (size_t)T * L))
-        return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
-    MSM_TRY(mplp_round_check(what, L, mode, polish));
-    const MplpRoundOutputs o = {labeling, passes_run, energy, energies};
-    mplp_round_host(unary, tcosts, triplets, N, L, T, mode == 0 ? messages : nullptr, mode, polish, o);
-    return MSM_OK;
+    return round_host(unary, tcosts, triplets, N, L, T, messages, mode, polish, {labeling, passes_run, energy, energies}, false, nullptr);
 }
 
 int msm_mplp_round_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages,
                        int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies) {
-    const char *what = "msm_mplp_round";
-    if (!ctx) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: null context");
-    MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, labeling));
-    MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, labeling));
-    MSM_HIP(hipSetDevice(ctx->device));
-    MSM_TRY(drop_ctx_pending(ctx));
-    MplpScratch &s = mplp_scratch(ctx);
-    const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L;
-    const bool with_m = mode == 0 && messages && nm;
-    if (s.U.ensure(nU) != hipSuccess) return stage_alloc_failed(sizeof(double) * nU);
-    if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
-    if (with_m && s.rm.ensure(nm) != hipSuccess) return stage_alloc_failed(sizeof(double) * nm);
-    MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
-    MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
-    if (with_m) MSM_TRY(upload_in_pieces(ctx, s.rm.p, messages, sizeof(double) * nm));
-    const MplpRoundOutputs o = {labeling, passes_run, energy, energies};
-    return mplp_round_device(ctx, what, s.U.p, s.tc.p, with_m ? s.rm.p : nullptr, false, true, triplets, N, L, T, mode, polish, o);
+    return round_gpu(ctx, unary, tcosts, triplets, N, L, T, messages, mode, polish, {labeling, passes_run, energy, energies}, false, nullptr);
+}
+
+int msm_mplp_round_forbid(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages,
+                          int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies, int64_t counts[4]) {
+    return round_host(unary, tcosts, triplets, N, L, T, messages, mode, polish, {labeling, passes_run, energy, energies}, true, counts);
+}
+
+int msm_mplp_round_forbid_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
+                              const double *messages, int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies,
+                              int64_t counts[4]) {
+    return round_gpu(ctx, unary, tcosts, triplets, N, L, T, messages, mode, polish, {labeling, passes_run, energy, energies}, true, counts);
 }
 
 int msm_mplp_round_gpu_stats(msm_ctx *ctx, double stats[4]) {

@@ -24,14 +24,17 @@ struct MplpArgs {
 
 // one level of sweep `sweep`: a workgroup per factor sched[begin .. begin + count).  The whole launch returns at once when the sweep before left every
 // message as it was (changed[sweep - 1] == 0): a run past its fixed point costs launches and nothing else.
-int launch_mplp_update(msm_ctx *ctx, const MplpArgs &a, int begin, int count, int sweep);
+// forbid (here and below): the instantiation that reads NaN / +inf table entries as forbidden combinations (DESIGN.md 5.19 "Forbidden entries")
+int launch_mplp_update(msm_ctx *ctx, const MplpArgs &a, int begin, int count, int sweep, bool forbid = false);
 // beliefs and decode, a wavefront per node: label[i] (may be null) and node_terms[i] = min_x b_i(x)
 int launch_mplp_decode(msm_ctx *ctx, const MplpArgs &a, int32_t *label, double *node_terms);
 // the factor terms of the bound after sweep `sweep`, a workgroup per factor, factor_terms[t]; returns at once where the update of that sweep did (the
 // host repeats the previous sweep's bound).  sweep < 0: unconditional.
-int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_terms, int sweep);
+int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_terms, int sweep, bool forbid = false);
 // flags[0] / flags[1] raised to 1 by a non-finite entry of the unary / triplet table
 int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, int32_t *flags);
+// adds to counts[0] the non-finite entries of U and to counts[1..3] the NaN / +inf / -inf entries of tc (either may be null with n = 0)
+int launch_mplp_classify(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, unsigned long long *counts);
 
 // The rounding (DESIGN.md 5.19 "Rounding"; the literal: mplp_round_host).
 struct MplpRoundArgs {
@@ -49,24 +52,28 @@ struct MplpRoundArgs {
     int *status;
 };
 // the conditioned decode of the class cls_node[begin .. begin + count) at `frontier`: a workgroup per node
-int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int frontier);
+int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int frontier, bool forbid = false);
 // polish pass `pass` over that class, a wavefront per node; the whole launch returns at once when pass - 1 changed no label
-int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass);
+int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass, bool forbid = false);
 int mplp_update_slots(int L);
 
 // the checks of msm_mplp_round besides mplp_check_arguments: the mode, the polish count, the label count
 int mplp_round_check(const char *what, int L, int mode, int polish);
 // The rounding over tables that lie on the device, arguments checked by the caller.  d_m: the device messages of mode 0 (null: all zero; use_scratch_m:
 // the messages the context's last mplp_run_device left).  check_tables: look for non-finite table entries first (the messages of mode 0 always are).
-// Complete on return; the outputs are written only when the call succeeds.
+// Complete on return; the outputs are written only when the call succeeds.  forbid: the forbidden-entry reading (DESIGN.md 5.19 "Forbidden entries") --
+// the tables and the messages are classified instead, and counts[4] (may be null) receives the tables' counts; with check_tables false counts hands in
+// what the caller's mplp_run_device counted over these tables.
 int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, bool use_scratch_m, bool check_tables,
-                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o);
+                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o,
+                      bool forbid = false, int64_t *counts = nullptr);
 
 // the host optimiser's checks, with its messages (what: the entry point's name for the MPLP-specific refusals); the tables are not looked at
 int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling);
 // MPLP over tables that lie on the device (d_U: L x N, d_tc: T x L^3), arguments checked by the caller: the finiteness pass first, then the sweeps.
-// Complete on return; the outputs are written only when the call succeeds.
+// Complete on return; the outputs are written only when the call succeeds.  forbid: k_mplp_classify instead of the finiteness pass, its four counts to
+// counts (may be null), and the forbidden-aware kernels where the triplet table holds a NaN or +inf.
 int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, int sweeps,
-                    const MplpOutputs &o);
+                    const MplpOutputs &o, bool forbid = false, int64_t *counts = nullptr);
 
 }  // namespace msm

@@ -41,6 +41,30 @@ inline int mplp_first_repeated_node(const int32_t *triplets, int T) {
     return -1;
 }
 
+// Forbidden entries: under `forbid` a table entry or an energy term that is NaN or +inf reads as +inf, a forbidden label combination.
+// The test is v < +inf, false for both; without forbid the value passes as it is.
+inline double mplp_hat(double v, bool forbid) { return !forbid || v < std::numeric_limits<double>::infinity() ? v : std::numeric_limits<double>::infinity(); }
+
+// counts[0]: non-finite unary entries; counts[1..3]: NaN, +inf, -inf triplet entries (either table may be null with n = 0)
+inline void mplp_classify(const double *unary, size_t nu, const double *tcosts, size_t nt, int64_t counts[4]) {
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    for (size_t i = 0; i < nu; ++i) counts[0] += !(unary[i] - unary[i] == 0.0);
+    for (size_t i = 0; i < nt; ++i) {
+        const double v = tcosts[i];
+        if (v - v == 0.0) continue;
+        ++counts[v != v ? 1 : v > 0.0 ? 2 : 3];
+    }
+}
+
+// Ehat: mcmc_energy_of_terms over the terms passed through mplp_hat -- finite or +inf, never NaN, where the tables passed the forbid route's checks
+inline double mplp_energy_of_terms(const double *terms, int N, int T, bool forbid) {
+    if (!forbid) return mcmc_energy_of_terms(terms, N, T);
+    double u = 0.0, pw = 0.0, tc = 0.0;
+    for (int i = 0; i < N; ++i) u += mplp_hat(terms[i], true);
+    for (int t = 0; t < T; ++t) tc += mplp_hat(terms[(size_t)N + t], true);
+    return u + pw + tc;
+}
+
 inline bool mplp_all_finite(const double *v, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!(v[i] - v[i] == 0.0)) return false;  // a NaN or an infinity
@@ -62,7 +86,7 @@ inline void mplp_node_sum(const double *unary, const double *m, const MplpIncide
 // The update of factor t: the three cavities, the three minima of the summed table, the new messages.  A minimum of finite values is order-free but for
 // the sign of a zero; `+ 0.0` turns a -0.0 minimum into +0.0 and changes nothing else, so any reduction shape gives these bits.
 inline void mplp_update_factor(const double *unary, const double *tcosts, const int32_t *triplets, const MplpIncidence &inc, int N, int L, int t, double *m,
-                               double *scratch /* 6 L */) {
+                               double *scratch /* 6 L */, bool forbid = false) {
     const size_t L1 = (size_t)L, L2 = L1 * L1, L3 = L2 * L1;
     double *d0 = scratch, *d1 = d0 + L, *d2 = d1 + L, *M0 = d2 + L, *M1 = M0 + L, *M2 = M1 + L;
     double *d[3] = {d0, d1, d2}, *M[3] = {M0, M1, M2};
@@ -73,14 +97,18 @@ inline void mplp_update_factor(const double *unary, const double *tcosts, const 
         for (int b = 0; b < L; ++b) {
             const double *row = th + (size_t)a * L2 + (size_t)b * L1;
             for (int c = 0; c < L; ++c) {
-                const double v = ((row[c] + d0[a]) + d1[b]) + d2[c];
+                const double v = ((mplp_hat(row[c], forbid) + d0[a]) + d1[b]) + d2[c];
                 if (v < M0[a]) M0[a] = v;
                 if (v < M1[b]) M1[b] = v;
                 if (v < M2[c]) M2[c] = v;
             }
         }
     for (int s = 0; s < 3; ++s)
-        for (int x = 0; x < L; ++x) m[((size_t)3 * t + s) * L + x] = (M[s][x] + 0.0) / 3.0 - d[s][x];
+        for (int x = 0; x < L; ++x) {
+            double nv = (M[s][x] + 0.0) / 3.0 - d[s][x];
+            if (forbid && !(M[s][x] < std::numeric_limits<double>::infinity())) nv = std::numeric_limits<double>::infinity();  // label x is proved infeasible
+            m[((size_t)3 * t + s) * L + x] = nv;
+        }
 }
 
 // beliefs and decode: label[i] = argmin_x b_i(x), lowest label on ties; node_terms[i] = that minimum (the first N terms of the bound); either may be null
@@ -95,16 +123,20 @@ inline void mplp_decode(const double *unary, const double *m, const MplpIncidenc
     }
 }
 
-// the last T terms of the bound: min over (a, b, c) of ((theta_t(a, b, c) - m[t][0][a]) - m[t][1][b]) - m[t][2][c]
-inline void mplp_factor_terms(const double *tcosts, const double *m, int L, int T, double *factor_terms) {
+// the last T terms of the bound: min over (a, b, c) of ((theta_t(a, b, c) - m[t][0][a]) - m[t][1][b]) - m[t][2][c]; under forbid over the combinations
+// whose entry and three messages are all below +inf, +inf where there is none
+inline void mplp_factor_terms(const double *tcosts, const double *m, int L, int T, double *factor_terms, bool forbid = false) {
     const size_t L1 = (size_t)L, L2 = L1 * L1, L3 = L2 * L1;
     for (int t = 0; t < T; ++t) {
         const double *th = tcosts + (size_t)t * L3, *m0 = m + (size_t)3 * t * L, *m1 = m0 + L, *m2 = m1 + L;
-        double lo = std::numeric_limits<double>::infinity();
+        const double inf = std::numeric_limits<double>::infinity();
+        double lo = inf;
         for (int a = 0; a < L; ++a)
             for (int b = 0; b < L; ++b)
                 for (int c = 0; c < L; ++c) {
-                    const double v = ((th[(size_t)a * L2 + (size_t)b * L1 + c] - m0[a]) - m1[b]) - m2[c];
+                    const double e = th[(size_t)a * L2 + (size_t)b * L1 + c];
+                    if (forbid && !(e < inf && m0[a] < inf && m1[b] < inf && m2[c] < inf)) continue;
+                    const double v = ((e - m0[a]) - m1[b]) - m2[c];
                     if (v < lo) lo = v;
                 }
         factor_terms[t] = lo;
@@ -141,27 +173,28 @@ struct MplpWinner {
 };
 
 // the serial literal over checked arguments
-inline void mplp_run_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, int sweeps, const MplpOutputs &o) {
+inline void mplp_run_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, int sweeps, const MplpOutputs &o,
+                          bool forbid = false) {
     MplpIncidence inc;
     mplp_build_incidence(triplets, N, T, inc);
     const size_t nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
     std::vector<double> m(nm, 0.0), before(nm), scratch(6 * (size_t)L), terms(nterms), bterms(nterms);
     std::vector<int32_t> cand((size_t)N);
     mcmc_energy_terms(unary, tcosts, triplets, N, L, T, o.labeling, terms.data());
-    MplpWinner win(o.labeling, N, mcmc_energy_of_terms(terms.data(), N, T));
+    MplpWinner win(o.labeling, N, mplp_energy_of_terms(terms.data(), N, T, forbid));
     int run = 0;
     double e_last = 0.0, b_last = 0.0;
     for (int k = 0; k < sweeps && T > 0; ++k) {
         before = m;
-        for (int t = 0; t < T; ++t) mplp_update_factor(unary, tcosts, triplets, inc, N, L, t, m.data(), scratch.data());
+        for (int t = 0; t < T; ++t) mplp_update_factor(unary, tcosts, triplets, inc, N, L, t, m.data(), scratch.data(), forbid);
         run = k + 1;
         mplp_decode(unary, m.data(), inc, N, L, cand.data(), bterms.data(), scratch.data());
         mcmc_energy_terms(unary, tcosts, triplets, N, L, T, cand.data(), terms.data());
-        e_last = mcmc_energy_of_terms(terms.data(), N, T);
+        e_last = mplp_energy_of_terms(terms.data(), N, T, forbid);
         win.offer(cand.data(), N, e_last);
         if (o.energies) o.energies[k] = e_last;
         if (o.bounds) {
-            mplp_factor_terms(tcosts, m.data(), L, T, bterms.data() + N);
+            mplp_factor_terms(tcosts, m.data(), L, T, bterms.data() + N, forbid);
             o.bounds[k] = b_last = mplp_bound_of_terms(bterms.data(), N, T);
         }
         if (std::memcmp(before.data(), m.data(), sizeof(double) * nm) == 0) break;  // a fixed point
@@ -175,7 +208,7 @@ inline void mplp_run_host(const double *unary, const double *tcosts, const int32
             *o.bound = b_last;
         else {
             mplp_decode(unary, m.data(), inc, N, L, nullptr, bterms.data(), scratch.data());
-            mplp_factor_terms(tcosts, m.data(), L, T, bterms.data() + N);
+            mplp_factor_terms(tcosts, m.data(), L, T, bterms.data() + N, forbid);
             *o.bound = mplp_bound_of_terms(bterms.data(), N, T);
         }
     }
@@ -230,7 +263,9 @@ inline void mplp_other_slots(int s, int &s1, int &s2) { s1 = s == 0 ? 1 : 0, s2 
 // score(x) of node i at frontier f (node j is fixed when colour[j] < f): theta_i(x), then g_{t,s}(x) over the incidence of i in list order.  m null:
 // all messages zero.  frontier INT_MAX reads no message.
 inline void mplp_round_scores(const double *unary, const double *tcosts, const int32_t *triplets, const double *m, const MplpIncidence &inc,
-                              const int32_t *colour, int frontier, const int32_t *lab, int N, int L, int i, double *score) {
+                              const int32_t *colour, int frontier, const int32_t *lab, int N, int L, int i, double *score,
+                              bool forbid = false) {
+    const double inf = std::numeric_limits<double>::infinity();
     const size_t L1 = (size_t)L, L2 = L1 * L1, L3 = L2 * L1;
     const size_t stride[3] = {L2, L1, 1};
     for (int x = 0; x < L; ++x) score[x] = unary[(size_t)x * N + i];
@@ -247,13 +282,15 @@ inline void mplp_round_scores(const double *unary, const double *tcosts, const i
             const double *row = th + (size_t)x * stride[s];
             double g;
             if (f1 && f2)
-                g = row[(size_t)lab[(size_t)j1] * stride[s1] + (size_t)lab[(size_t)j2] * stride[s2]];
+                g = mplp_hat(row[(size_t)lab[(size_t)j1] * stride[s1] + (size_t)lab[(size_t)j2] * stride[s2]], forbid);
             else {
                 g = std::numeric_limits<double>::infinity();
                 const int a0 = f1 ? lab[(size_t)j1] : 0, a1 = f1 ? a0 + 1 : L, b0 = f2 ? lab[(size_t)j2] : 0, b1 = f2 ? b0 + 1 : L;
                 for (int y1 = a0; y1 < a1; ++y1)
                     for (int y2 = b0; y2 < b1; ++y2) {
                         double v = row[(size_t)y1 * stride[s1] + (size_t)y2 * stride[s2]];
+                        // a forbidden entry, or a message of +inf it would subtract: the combination is +inf and lowers nothing
+                        if (forbid && !(v < inf && (f1 || !m1 || m1[y1] < inf) && (f2 || !m2 || m2[y2] < inf))) continue;
                         if (!f1) v = v - (m1 ? m1[y1] : 0.0);
                         if (!f2) v = v - (m2 ? m2[y2] : 0.0);
                         if (v < g) g = v;
@@ -268,12 +305,13 @@ inline void mplp_round_scores(const double *unary, const double *tcosts, const i
 // one walk over the classes: frontier k for class k in the conditioned decode (polish false), INT_MAX in a polish pass, where a node keeps its label
 // unless another one's score is strictly lower.  Returns whether a label changed.
 inline bool mplp_round_pass(const double *unary, const double *tcosts, const int32_t *triplets, const double *m, const MplpIncidence &inc,
-                            const MplpColouring &col, bool polish, int32_t *lab, int N, int L, double *score /* L */) {
+                            const MplpColouring &col, bool polish, int32_t *lab, int N, int L, double *score /* L */,
+                            bool forbid = false) {
     bool changed = false;
     for (int k = 0; k < col.classes(); ++k)
         for (int32_t p = col.class_off[(size_t)k]; p < col.class_off[(size_t)k + 1]; ++p) {
             const int32_t i = col.node[(size_t)p];
-            mplp_round_scores(unary, tcosts, triplets, m, inc, col.colour.data(), polish ? std::numeric_limits<int>::max() : k, lab, N, L, i, score);
+            mplp_round_scores(unary, tcosts, triplets, m, inc, col.colour.data(), polish ? std::numeric_limits<int>::max() : k, lab, N, L, i, score, forbid);
             int best = 0;
             for (int x = 1; x < L; ++x)
                 if (score[x] < score[best]) best = x;
@@ -292,7 +330,7 @@ struct MplpRoundOutputs {
 
 // the serial literal of the rounding over checked arguments; messages may be null (all zero) and are not read in mode 1
 inline void mplp_round_host(const double *unary, const double *tcosts, const int32_t *triplets, int N, int L, int T, const double *messages, int mode,
-                            int polish, const MplpRoundOutputs &o) {
+                            int polish, const MplpRoundOutputs &o, bool forbid = false) {
     MplpIncidence inc;
     mplp_build_incidence(triplets, N, T, inc);
     MplpColouring col;
@@ -301,7 +339,7 @@ inline void mplp_round_host(const double *unary, const double *tcosts, const int
     std::vector<int32_t> cur(o.labeling, o.labeling + N);
     auto energy_of = [&](const int32_t *lab) {
         mcmc_energy_terms(unary, tcosts, triplets, N, L, T, lab, terms.data());
-        return mcmc_energy_of_terms(terms.data(), N, T);
+        return mplp_energy_of_terms(terms.data(), N, T, forbid);
     };
     double e_last = energy_of(cur.data());
     MplpWinner win(cur.data(), N, e_last);
@@ -309,14 +347,14 @@ inline void mplp_round_host(const double *unary, const double *tcosts, const int
     if (o.energies) o.energies[n] = e_last;
     ++n;
     if (mode == 0) {
-        mplp_round_pass(unary, tcosts, triplets, messages, inc, col, false, cur.data(), N, L, score.data());
+        mplp_round_pass(unary, tcosts, triplets, messages, inc, col, false, cur.data(), N, L, score.data(), forbid);
         e_last = energy_of(cur.data());
         win.offer(cur.data(), N, e_last);
         if (o.energies) o.energies[n] = e_last;
         ++n;
     }
     for (int p = 0; p < polish; ++p) {
-        const bool changed = mplp_round_pass(unary, tcosts, triplets, nullptr, inc, col, true, cur.data(), N, L, score.data());
+        const bool changed = mplp_round_pass(unary, tcosts, triplets, nullptr, inc, col, true, cur.data(), N, L, score.data(), forbid);
         run = p + 1;
         e_last = energy_of(cur.data());
         win.offer(cur.data(), N, e_last);

@@ -80,6 +80,16 @@ __device__ __forceinline__ double node_sum(const MplpArgs &a, unsigned i, unsign
 
 constexpr int kMplpBatch = 4;  // table entries a thread has in flight
 
+// Forbidden entries: the kernels that read the triplet table come in two instantiations.  F = true reads an entry that is NaN or +inf
+// as +inf -- one compare and one select -- and keeps +inf messages out of every subtraction; F = false is the plain code, unchanged.  A batch in flight
+// is mapped where it is folded in, not where it is requested: a compare beside the load would wait for the load there and end the overlap the
+// batches exist for (measured: 0.70 against 0.44 ms per sweep on the ico4 table).
+template <bool F>
+__device__ __forceinline__ double hat(double v) {
+    if constexpr (F) return v < __longlong_as_double(0x7ff0000000000000LL) ? v : __longlong_as_double(0x7ff0000000000000LL);
+    return v;
+}
+
 __device__ __forceinline__ void load_batch(const double *__restrict__ th, unsigned e0, unsigned L3, double (&v)[kMplpBatch]) {
 #pragma unroll
     for (int j = 0; j < kMplpBatch; ++j) {
@@ -88,6 +98,7 @@ __device__ __forceinline__ void load_batch(const double *__restrict__ th, unsign
     }
 }
 
+template <bool F>
 __global__ __launch_bounds__(kMplpThreads) void k_mplp_update(MplpArgs a, int begin, int count, int sweep, int slots) {
     extern __shared__ __align__(16) double s_mplp[];  // 3 L cavities, then 3 L rows of `slots` minima as keys (a row padded by one when slots > 1)
     if (sweep > 0 && a.changed[sweep - 1] == 0) return;  // the run is at its fixed point (the whole launch)
@@ -119,7 +130,7 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_update(MplpArgs a, int be
 #pragma unroll
         for (int j = 0; j < kMplpBatch; ++j) {
             if (e0 + (unsigned)j * kMplpThreads >= L3) break;
-            const double v = ((cur[j] + d[p.a]) + d[L + p.b]) + d[2 * L + p.c];
+            const double v = ((hat<F>(cur[j]) + d[p.a]) + d[L + p.b]) + d[2 * L + p.c];
             const long long k = key_of(v);
             atomicMin(&M[p.a * stride + mine], k);
             atomicMin(&M[(L + p.b) * stride + mine], k);
@@ -135,7 +146,9 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_update(MplpArgs a, int be
     for (unsigned idx = tid; idx < 3 * L; idx += kMplpThreads) {
         long long lowest = M[idx * stride];
         for (unsigned j = 1; j < S; ++j) lowest = min(lowest, M[idx * stride + j]);
-        const double nv = (value_of(lowest) + 0.0) / 3.0 - d[idx];
+        double nv = (value_of(lowest) + 0.0) / 3.0 - d[idx];
+        if constexpr (F)
+            if (lowest == inf_key) nv = value_of(inf_key);  // no combination with this label is below +inf: the label is proved infeasible
         moved |= __double_as_longlong(nv) != __double_as_longlong(out[idx]);
         out[idx] = nv;
     }
@@ -165,6 +178,7 @@ __global__ __launch_bounds__(256) void k_mplp_decode(MplpArgs a, int32_t *__rest
     }
 }
 
+template <bool F>
 __global__ __launch_bounds__(kMplpThreads) void k_mplp_factor_terms(MplpArgs a, double *__restrict__ factor_terms, int sweep) {
     extern __shared__ __align__(16) double s_mplp[];  // 3 L messages, then a minimum per wavefront
     if (sweep > 0 && a.changed[sweep - 1] == 0) return;
@@ -174,10 +188,13 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_factor_terms(MplpArgs a, 
     __syncthreads();
     const unsigned L3 = L * L * L;
     const double *__restrict__ th = a.tc + (size_t)t * L3;
-    double lo = __longlong_as_double(0x7ff0000000000000LL);
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    double lo = inf;
     Abc p(tid, kMplpThreads, L);
     for (unsigned e = tid; e < L3; e += kMplpThreads, p.advance()) {
-        const double v = ((th[e] - s_mplp[p.a]) - s_mplp[L + p.b]) - s_mplp[2 * L + p.c];
+        const double m0 = s_mplp[p.a], m1 = s_mplp[L + p.b], m2 = s_mplp[2 * L + p.c], en = th[e];
+        double v = ((en - m0) - m1) - m2;
+        if constexpr (F) v = en < inf && m0 < inf && m1 < inf && m2 < inf ? v : inf;  // only combinations that are below +inf in all four
         if (v < lo) lo = v;
     }
 #pragma unroll
@@ -192,6 +209,35 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_factor_terms(MplpArgs a, 
         for (unsigned k = 1; k < kMplpThreads / 64; ++k)
             if (w[k] < lo) lo = w[k];
         factor_terms[t] = lo;  // (the sign of a zero minimum depends on the order; the sum it joins starts at +0.0 and does not see it)
+    }
+}
+
+// One pass over both tables: counts[0] non-finite unary entries, counts[1..3] NaN / +inf / -inf triplet entries.  A wavefront reduces its four counts by
+// shuffles, the workgroup's four wavefronts meet in LDS, and thread c adds the workgroup's count c with one 64-bit atomic (none where it is zero).
+__global__ __launch_bounds__(256) void k_mplp_classify(const double *__restrict__ U, size_t nU, const double *__restrict__ tc, size_t ntc,
+                                                       unsigned long long *__restrict__ counts) {
+    __shared__ unsigned s_cnt[4][4];
+    const size_t stride = (size_t)gridDim.x * 256;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    unsigned n[4] = {0, 0, 0, 0};  // (a thread sees at most ceil(2^63 / stride) entries; the grid keeps that far below 2^32)
+    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nU; j += stride) n[0] += !(U[j] - U[j] == 0.0);
+    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < ntc; j += stride) {
+        const double v = tc[j];
+        n[1] += v != v;
+        n[2] += v == inf;
+        n[3] += v == -inf;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) n[c] += __shfl_down(n[c], off);
+    if ((threadIdx.x & 63u) == 0)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s_cnt[threadIdx.x >> 6][c] = n[c];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const unsigned long long total = (unsigned long long)s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+        if (total) atomicAdd(&counts[threadIdx.x], total);
     }
 }
 
@@ -220,6 +266,7 @@ __device__ __forceinline__ void wave_argmin(double &bv, int &bx) {
 // g(x) in list order.  With neither other node fixed the factor's L^3 block is streamed as k_mplp_update streams it, each entry lowering g[x_s] in a
 // padded row of `slots` key copies; with one fixed the L^2 sub-block at its label goes the same way, threads along the faster free axis; with both
 // fixed thread x reads its own entry.
+template <bool F>
 __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, int begin, int count, int frontier, int slots) {
     extern __shared__ __align__(16) double s_mplp[];  // L scores, 2 L staged messages, 8 words of the argmin, L rows of `slots` keys (padded by one)
     const unsigned tid = threadIdx.x, L = (unsigned)a.L, N = (unsigned)a.N;
@@ -233,7 +280,8 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, in
     long long *G = reinterpret_cast<long long *>(w + 8);
     const unsigned S = (unsigned)slots, stride = S > 1 ? S + 1 : 1, mine = tid & (S - 1);
     const unsigned L2 = L * L, L3 = L2 * L;
-    const long long inf_key = key_of(__longlong_as_double(0x7ff0000000000000LL));
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const long long inf_key = key_of(inf);
     for (unsigned x = tid; x < L; x += kMplpThreads) score[x] = a.U[(size_t)x * N + i];
     const int k0 = a.inc_ptr[i], k1 = a.inc_ptr[i + 1];
     for (int k = k0; k < k1; ++k) {  // (everything that decides a branch below is the same in every thread of the workgroup)
@@ -258,7 +306,7 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, in
         const double *__restrict__ th = a.tc + (size_t)t * L3;
         const unsigned st = s == 0 ? L2 : s == 1 ? L : 1u, st1 = s1 == 0 ? L2 : L, st2 = s2 == 1 ? L : 1u;
         if (f1 && f2) {
-            for (unsigned x = tid; x < L; x += kMplpThreads) score[x] += th[x * st + l1 * st1 + l2 * st2];
+            for (unsigned x = tid; x < L; x += kMplpThreads) score[x] += hat<F>(th[x * st + l1 * st1 + l2 * st2]);
             continue;
         }
         for (unsigned idx = tid; idx < L * stride; idx += kMplpThreads) G[idx] = inf_key;
@@ -277,7 +325,8 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, in
                 for (int j = 0; j < kMplpBatch; ++j) {
                     if (e0 + (unsigned)j * kMplpThreads >= L3) break;
                     const unsigned x = s == 0 ? p.a : s == 1 ? p.b : p.c, y1 = s1 == 0 ? p.a : p.b, y2 = s2 == 1 ? p.b : p.c;
-                    const double v = (cur[j] - mo[y1]) - mo[L + y2];
+                    double v = (cur[j] - mo[y1]) - mo[L + y2];
+                    if constexpr (F) v = cur[j] < inf && mo[y1] < inf && mo[L + y2] < inf ? v : inf;  // a forbidden entry (NaN too) or a +inf message
                     atomicMin(&G[x * stride + mine], key_of(v));
                     p.advance();
                 }
@@ -294,7 +343,9 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, in
             for (unsigned e = tid; e < L2; e += kMplpThreads) {
                 const unsigned hi = e / L, lo = e - hi * L;
                 const unsigned x = x_fast ? lo : hi, y = x_fast ? hi : lo;
-                const double v = th[base + hi * st_hi + lo * st_lo] - mo[y];
+                const double en = hat<F>(th[base + hi * st_hi + lo * st_lo]);
+                double v = en - mo[y];
+                if constexpr (F) v = en < inf && mo[y] < inf ? v : inf;
                 atomicMin(&G[x * stride + mine], key_of(v));
             }
         }
@@ -325,6 +376,7 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, in
 
 // A polish pass over one class, a wavefront per node: every other node is fixed, so label x costs theta_i(x) plus one table entry per incident slot,
 // added in list order.  The current label stays unless another one is strictly lower.
+template <bool F>
 __global__ __launch_bounds__(256) void k_mplp_polish(MplpRoundArgs a, int begin, int count, int pass) {
     if (pass > 0 && a.changed[pass - 1] == 0) return;  // the pass before moved no label (the whole launch)
     const unsigned lane = threadIdx.x & 63u, L = (unsigned)a.L, N = (unsigned)a.N;
@@ -365,7 +417,7 @@ __global__ __launch_bounds__(256) void k_mplp_polish(MplpRoundArgs a, int begin,
                 continue;
             }
             const unsigned st = s == 0 ? L2 : s == 1 ? L : 1u, st1 = s == 0 ? L : L2, st2 = s == 2 ? L : 1u;
-            v += a.tc[(size_t)t * L3 + x * st + l1 * st1 + l2 * st2];
+            v += hat<F>(a.tc[(size_t)t * L3 + x * st + l1 * st1 + l2 * st2]);
         }
         if (x == cur) cv = v;
         if (bx == INT_MAX || v < bv) bv = v, bx = (int)x;
@@ -397,13 +449,16 @@ int mplp_update_slots(int L) {
     return slots;
 }
 
-int launch_mplp_update(msm_ctx *ctx, const MplpArgs &a, int begin, int count, int sweep) {
+int launch_mplp_update(msm_ctx *ctx, const MplpArgs &a, int begin, int count, int sweep, bool forbid) {
     MSM_TRY(check_shape(a));
     if (count <= 0) return MSM_OK;
     if (begin < 0 || begin + count > a.T || sweep < 0) return fail(MSM_ERR_INVALID, "msm_mplp_optimise_gpu: bad launch (factors %d + %d of %d)", begin, count, a.T);
     const int slots = mplp_update_slots(a.L);
     const size_t lds = sizeof(double) * 3 * (size_t)a.L * (1 + (size_t)(slots > 1 ? slots + 1 : 1));
-    hipLaunchKernelGGL(k_mplp_update, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, sweep, slots);
+    if (forbid)
+        hipLaunchKernelGGL(k_mplp_update<true>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, sweep, slots);
+    else
+        hipLaunchKernelGGL(k_mplp_update<false>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, sweep, slots);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }
@@ -415,11 +470,14 @@ int launch_mplp_decode(msm_ctx *ctx, const MplpArgs &a, int32_t *label, double *
     return MSM_OK;
 }
 
-int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_terms, int sweep) {
+int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_terms, int sweep, bool forbid) {
     MSM_TRY(check_shape(a));
     if (a.T == 0) return MSM_OK;
     const size_t lds = sizeof(double) * (3 * (size_t)a.L + kMplpThreads / 64);
-    hipLaunchKernelGGL(k_mplp_factor_terms, dim3((unsigned)a.T), dim3(kMplpThreads), lds, ctx->stream, a, factor_terms, sweep);
+    if (forbid)
+        hipLaunchKernelGGL(k_mplp_factor_terms<true>, dim3((unsigned)a.T), dim3(kMplpThreads), lds, ctx->stream, a, factor_terms, sweep);
+    else
+        hipLaunchKernelGGL(k_mplp_factor_terms<false>, dim3((unsigned)a.T), dim3(kMplpThreads), lds, ctx->stream, a, factor_terms, sweep);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }
@@ -432,27 +490,41 @@ int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *t
     return MSM_OK;
 }
 
+int launch_mplp_classify(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, unsigned long long *counts) {
+    const size_t n = std::max(nU, ntc);
+    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(k_mplp_classify, dim3(blocks), dim3(256), 0, ctx->stream, U, nU, tc, ntc, counts);
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
 static int check_round_launch(const MplpRoundArgs &a, int begin, int count) {
     if (a.N <= 0 || a.L <= 0 || a.L > kMplpMaxLabels || a.T < 0 || begin < 0 || count < 0 || begin + count > a.N)
         return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: bad launch (N %d, L %d, T %d, nodes %d + %d)", a.N, a.L, a.T, begin, count);
     return MSM_OK;
 }
 
-int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int frontier) {
+int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int frontier, bool forbid) {
     MSM_TRY(check_round_launch(a, begin, count));
     if (count == 0) return MSM_OK;
     const int slots = mplp_update_slots(a.L);
     const size_t lds = sizeof(double) * (3 * (size_t)a.L + 8 + (size_t)a.L * (size_t)(slots > 1 ? slots + 1 : 1));
-    hipLaunchKernelGGL(k_mplp_round, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
+    if (forbid)
+        hipLaunchKernelGGL(k_mplp_round<true>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
+    else
+        hipLaunchKernelGGL(k_mplp_round<false>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }
 
-int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass) {
+int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass, bool forbid) {
     MSM_TRY(check_round_launch(a, begin, count));
     if (count == 0) return MSM_OK;
     if (pass < 0) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: bad launch (pass %d)", pass);
-    hipLaunchKernelGGL(k_mplp_polish, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
+    if (forbid)
+        hipLaunchKernelGGL(k_mplp_polish<true>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
+    else
+        hipLaunchKernelGGL(k_mplp_polish<false>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

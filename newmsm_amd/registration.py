@@ -24,23 +24,24 @@ EXCL_WITH_WEIGHTINGS = ("--excl together with --inweight and --refweight is not 
                         "meshes have the same size")
 
 
-def _mplp_host(unary, tcosts, triplets, labeling, sweeps):
+def _mplp_host(unary, tcosts, triplets, labeling, sweeps, forbid=False):
     """the MPLP branch of run_discrete_level over fetched tables: the host literal's labelling (any ops without an mplp method of its own gets this)"""
-    return api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False).labeling
+    return api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False, forbid=forbid).labeling
 
 
-def _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, polish):
+def _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, polish, forbid=False):
     """the same with the rounding (DESIGN.md 5.19 "Rounding"): the sweeps, mode 0 on their messages with their winner handed in, one mode-1 call on the
     result -- what msm_cost_mplp_round(then_polish) does over the device tables"""
-    r = api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False, messages=True)
-    lab = api.mplp_round(unary, tcosts, triplets, r.labeling, messages=r.messages, mode=0, polish=polish).labeling
-    return api.mplp_round(unary, tcosts, triplets, lab, mode=1, polish=polish).labeling
+    r = api.mplp_optimise(unary, tcosts, triplets, labeling, sweeps=sweeps, bound=False, messages=True, forbid=forbid)
+    lab = api.mplp_round(unary, tcosts, triplets, r.labeling, messages=r.messages, mode=0, polish=polish, forbid=forbid).labeling
+    return api.mplp_round(unary, tcosts, triplets, lab, mode=1, polish=polish, forbid=forbid).labeling
 
 
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
-    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True, mplp_round=False, mplp_polish=8):
+    def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True, mplp_round=False, mplp_polish=8,
+                 mplp_forbid=False):
         """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
         the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
         bytes (what MSMHIP_FEATURES=gpu asks of the executables).
@@ -52,8 +53,12 @@ class ProductOps:
         (msm_cost_mplp_optimise); False fetches them for the host literal (msm_mplp_optimise) -- the same labelings, bit for bit
         mplp_round: an iteration of the MPLP branch rounds the final messages to a labelling after its sweeps (the conditioned decode and mplp_polish
         polish passes, then one polish call on the winner: msm_cost_mplp_round, or msm_mplp_round over the fetched tables -- the same labelings; what
-        MSMHIP_MPLP_ROUND=on and MSMHIP_MPLP_POLISH=n ask of the executables)"""
+        MSMHIP_MPLP_ROUND=on and MSMHIP_MPLP_POLISH=n ask of the executables)
+        mplp_forbid: the MPLP branch reads NaN and +inf entries of the triplet table as forbidden label combinations instead of refusing the table
+        (DESIGN.md 5.19 "Forbidden entries"; the strain regulariser produces them wherever a label set lets control points meet), on the device route
+        (msm_cost_set_mplp_forbid) and on the host route (msm_mplp_optimise_forbid) alike; what MSMHIP_MPLP_FORBID=on asks of the executables"""
         self.ctx = ctx
+        self.mplp_forbid = bool(mplp_forbid)
         self.mplp_round = bool(mplp_round)
         self.mplp_polish = int(mplp_polish)
         if not 0 <= self.mplp_polish <= 64:
@@ -184,6 +189,8 @@ class ProductOps:
         cf = api.DiscreteCostFunction(self.ctx, kind=kind, simmeasure=simmeasure, rmode=rmode, **params)
         cf.set_meshes(target, source, cpgrid)
         cf.set_featurespace(src_feat)
+        if self.mplp_forbid:
+            cf.set_mplp_forbid(True)
         return _ProductCost(cf)
 
     def mcmc(self, unary, tcosts, triplets, labeling, mcparam, iters, seed):
@@ -194,8 +201,8 @@ class ProductOps:
 
     def mplp(self, unary, tcosts, triplets, labeling, sweeps):
         if self.mplp_round:
-            return _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, self.mplp_polish)
-        return _mplp_host(unary, tcosts, triplets, labeling, sweeps)
+            return _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, self.mplp_polish, self.mplp_forbid)
+        return _mplp_host(unary, tcosts, triplets, labeling, sweeps, self.mplp_forbid)
 
     def fusion_step(self, unary2, octets, triplets, passes, quads=None, pairs=None):
         return api.fusion_icm_step(unary2, octets, triplets, passes, quads=quads, pairs=pairs)

@@ -244,6 +244,17 @@ bool group_mcmc_draw_setting() {
     return true;
 }
 
+// MSMHIP_MPLP_FORBID=on (beside MSMHIP_MPLP=on): a --dopt=MPLP level reads the NaN and +infinity entries of its triplet table as forbidden label
+// combinations instead of refusing the table ("Forbidden entries")
+bool mplp_forbid_setting(bool mplp) {
+    const char *env = std::getenv("MSMHIP_MPLP_FORBID");
+    if (env && std::string(env) != "on")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MPLP_FORBID=") + env +
+                                         ": the forbidden-entry reading of MPLP's triplet table is switched on with MSMHIP_MPLP_FORBID=on (unset: off)");
+    if (env && !mplp) throw Error(MSM_ERR_INVALID, "MSMHIP_MPLP_FORBID=on changes how --dopt=MPLP reads its triplet table: it needs MSMHIP_MPLP=on");
+    return env != nullptr;
+}
+
 // MSMHIP_MPLP_ROUND=on (beside MSMHIP_MPLP=on): every iteration of a --dopt=MPLP level rounds the final messages to a labelling after its sweeps
 // ("Rounding"), with MSMHIP_MPLP_POLISH=n (0 ... 64, default 8) polish passes.  Returns whether it is on and sets *polish.
 bool mplp_round_setting(bool mplp, int *polish) {
@@ -286,6 +297,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     const bool mplp = mplp_env && std::string(mplp_env) == "on";
     int mplp_polish = 8;
     const bool mplp_round = mplp_round_setting(mplp, &mplp_polish);
+    const bool mplp_forbid = mplp_forbid_setting(mplp);
     std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr, mplp);
     const char *mcmc_env = std::getenv("MSMHIP_MCMC");  // "gpu": the --dopt=MCMC levels keep both cost tables on the device and run the sweeps there
     const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
@@ -296,7 +308,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     if (features_gpu_enabled())
         for (LevelSpec &lv : levels) lv.options.features_gpu = true;
     for (LevelSpec &lv : levels) lv.options.mcmc_chains = mcmc_chains;
-    for (LevelSpec &lv : levels) lv.options.mplp_round = mplp_round, lv.options.mplp_polish = mplp_polish;
+    for (LevelSpec &lv : levels) lv.options.mplp_round = mplp_round, lv.options.mplp_polish = mplp_polish, lv.options.mplp_forbid = mplp_forbid;
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");

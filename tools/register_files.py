@@ -133,6 +133,18 @@ def mplp_enabled():
     return os.environ.get("MSMHIP_MPLP", "") == "on"
 
 
+def mplp_forbid_setting():
+    """MSMHIP_MPLP_FORBID=on (beside MSMHIP_MPLP=on): a --dopt=MPLP level reads the NaN and +infinity entries of its triplet table as forbidden label
+    combinations instead of refusing the table ("Forbidden entries").  Anything else, or the variable without MSMHIP_MPLP=on,
+    ends the run with a message and exit status 1."""
+    text = os.environ.get("MSMHIP_MPLP_FORBID")
+    if text is not None and text != "on":
+        raise SystemExit("MSMHIP_MPLP_FORBID=%s: the forbidden-entry reading of MPLP's triplet table is switched on with MSMHIP_MPLP_FORBID=on (unset: off)" % text)
+    if text is not None and not mplp_enabled():
+        raise SystemExit("MSMHIP_MPLP_FORBID=on changes how --dopt=MPLP reads its triplet table: it needs MSMHIP_MPLP=on")
+    return text == "on"
+
+
 def mplp_round_setting():
     """MSMHIP_MPLP_ROUND=on (beside MSMHIP_MPLP=on): every iteration of a --dopt=MPLP level rounds the final messages to a labelling after its sweeps
     ("Rounding"), with MSMHIP_MPLP_POLISH=n (0 ... 64, default 8) polish passes.  Returns (on, polish); anything else, or either
@@ -306,6 +318,7 @@ def main(argv):
     if a.groupwise:
         return main_groupwise(a, surf_ext, data_ext, group_mcmc, chains, draw_gpu)
     mplp_round, mplp_polish = mplp_round_setting()
+    mplp_forbid = mplp_forbid_setting()
     for flag in ("inmesh", "indata", "refdata"):
         if not getattr(a, flag):
             raise SystemExit("register_files.py: --%s is required" % flag)
@@ -341,7 +354,7 @@ def main(argv):
             print("MCMC with %d chains per iteration." % chains)
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish, mplp_forbid=mplp_forbid), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])

@@ -1,4 +1,4 @@
-"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--round] [--polish P] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
+"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--round | --forbid] [--polish P] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
 MI355X against its host literal, over the unary and triplet tables tools/time_mcmc.py builds: BASELINE config 2 (pairwise sulc, ico6 data, ico4 control
 grid, 19 labels) and an ico3 control grid.  It reports and judges nothing.  Per grid: the energy of the start (all zero), the energy the Monte Carlo
 optimiser reaches on the device in --mcmc-sweeps sweeps (msm_cost_mcmc_optimise, tools/time_mcmc.py's sweep count by default), the energy of MPLP's decode
@@ -10,7 +10,13 @@ A table the optimiser refuses (a non-finite entry) is reported as refused, with 
 --round measures the rounding of the messages instead (DESIGN.md 5.19 "Rounding"; profiles/mplp_round_time.json): per grid the energy of the conditioned
 decode and of the polished winner after 1 / 5 / 10 / 20 / 30 sweeps (msm_cost_mplp_round, --polish passes), the polish of the zero labelling alone
 (msm_cost_mplp_polish), ms per decode pass and per polish pass by the HIP events around their launches beside one sweep and the table at the HBM rate,
-and the start, the Monte Carlo optimiser's energy and the bound.  Times are reported only when the device's result equals the host literal's."""
+and the start, the Monte Carlo optimiser's energy and the bound.  Times are reported only when the device's result equals the host literal's.
+
+--forbid measures the forbidden-entry reading (DESIGN.md 5.19 "Forbidden entries"; profiles/mplp_forbid_time.json) on the ico4 and ico3 tables built
+without label rescaling on the regular control grid, which hold NaN and +infinity entries (their counts are printed): ms per sweep, per conditioned
+decode and per polish pass of the forbidden-aware kernels (msm_mplp_optimise_forbid_gpu, msm_mplp_round_forbid_gpu) and, beside them, of the plain
+kernels on a copy of the table whose forbidden entries the host replaced by 1e7 -- both in one process, alternated, by the HIP events around the
+kernels.  With them the energies E^ of the start, of every sweep's decode and of the rounding's candidates, and the bound.  No time is a threshold."""
 import argparse
 import json
 import os
@@ -136,19 +142,79 @@ def measure_round(ctx, cp_order, mcmc_sweeps, repeats, polish):
     return out
 
 
+def measure_forbid(ctx, cp_order, sweeps, repeats, polish):
+    from newmsm_amd import synthetic
+    inp = problem.pairwise_inputs(6, cp_order, D=1, rescale=False, warp_amp=0.0, warp_rot=0.0)  # the regular control grid under the sampling grid's own labels
+    inp["src_feat"] = synthetic.features(synthetic.known_warp(inp["source_orig_xyz"], seed=77, rot_deg=3.0, amp=1.2), 1, 1234)  # (a unary table that is not flat)
+    cf, keep = problem.build_cost(ctx, inp, kind="univariate")
+    cf.get_source_data()
+    keep["target"].prepare_search(wait=True)
+    triplets = inp["triplets"]
+    start = np.zeros(cf.N, dtype=np.int32)
+    table_bytes = cf.T * cf.L ** 3 * 8
+    U = np.array(cf.computeUnaryCosts())
+    tc = np.array(cf.computeTripletCosts(pinned=True))
+    counts = api.mplp_classify(U, tc)
+    out = dict(cp_order=cp_order, N=cf.N, T=cf.T, L=cf.L, sweeps=sweeps, polish=polish, repeats=repeats, triplet_table_MB=table_bytes / 1e6,
+               table_ms_at_hbm_rate=table_bytes / HBM_BYTES_PER_S * 1e3, hbm_bytes_per_s=HBM_BYTES_PER_S,
+               counts=dict(unary_non_finite=int(counts[0]), triplet_nan=int(counts[1]), triplet_plus_inf=int(counts[2]), triplet_minus_inf=int(counts[3])))
+    stand_in = np.where(tc < np.inf, tc, 1e7)  # what the plain route can read: the yardstick
+    cf.set_mplp_forbid()
+    device_counts = np.zeros(4, dtype=np.int64)
+    routes = {"forbid": dict(tc=tc, kw=dict(forbid=True, counts=device_counts)), "plain_on_1e7_stand_in": dict(tc=stand_in, kw=dict())}
+    for r in routes.values():  # warm-up: code objects, staging blocks, the scratch buffers; and the messages the rounding is timed on
+        r["run"] = api.mplp_optimise_gpu(ctx, U, r["tc"], triplets, start, sweeps=sweeps, bounds=True, messages=True, **r["kw"])
+        api.mplp_round_gpu(ctx, U, r["tc"], triplets, r["run"].labeling, messages=r["run"].messages, mode=0, polish=polish, **r["kw"])
+        r.update(sweep_ms=[], sweep_bounds_ms=[], decode_ms=[], polish_ms=[])
+    for _ in range(repeats):
+        for r in routes.values():  # alternated
+            api.mplp_optimise_gpu(ctx, U, r["tc"], triplets, start, sweeps=sweeps, bound=False, **r["kw"])
+            st = api.mplp_gpu_stats(ctx)
+            r["sweep_ms"].append(st["kernel_ms"] / max(st["sweeps_run"], 1))
+            api.mplp_optimise_gpu(ctx, U, r["tc"], triplets, start, sweeps=sweeps, bounds=True, **r["kw"])
+            st = api.mplp_gpu_stats(ctx)
+            r["sweep_bounds_ms"].append(st["kernel_ms"] / max(st["sweeps_run"], 1))
+            r["round"] = api.mplp_round_gpu(ctx, U, r["tc"], triplets, r["run"].labeling, messages=r["run"].messages, mode=0, polish=polish, **r["kw"])
+            st = api.mplp_round_gpu_stats(ctx)
+            r["decode_ms"].append(st["decode_ms"])
+            r["polish_ms"].append(st["polish_ms"] / max(st["passes_run"], 1))
+    f = routes["forbid"]
+    got = cf.mplp_optimise(start, sweeps=sweeps, bounds=True, messages=True)  # the cost function's own device tables
+    want = api.mplp_optimise(U, tc, triplets, start, sweeps=sweeps, bounds=True, messages=True, forbid=True)
+    wround = api.mplp_round(U, tc, triplets, want.labeling, messages=want.messages, mode=0, polish=polish, forbid=True)
+    same = (equal(f["run"], want) and equal(got, want) and f["run"].messages.tobytes() == want.messages.tobytes() and device_counts.tolist() == counts.tolist()
+            and cf.mplp_forbidden().tolist() == counts.tolist() and np.array_equal(f["round"].labeling, wround.labeling)
+            and f["round"].energies.tobytes() == wround.energies.tobytes())
+    cf.close()
+    out["results_equal"] = bool(same)
+    for name, r in routes.items():
+        row = dict(sweeps_run=r["run"].sweeps_run, energy=r["run"].energy,
+                   bound=r["run"].bound, energies=r["run"].energies.tolist(), bounds=r["run"].bounds.tolist(), infinite_messages=int(np.isinf(r["run"].messages).sum()),
+                   rounding_energies=r["round"].energies.tolist(), rounding_energy=r["round"].energy, passes_run=r["round"].passes_run)
+        row["energy_start"] = api.mplp_round(U, r["tc"], triplets, start, mode=1, polish=0, forbid=name == "forbid").energy
+        if same:  # no time is reported beside a result that is not the host literal's
+            row.update(gpu_kernel_ms_per_sweep=spread(r["sweep_ms"]), gpu_kernel_ms_per_sweep_with_bounds=spread(r["sweep_bounds_ms"]),
+                       gpu_ms_per_decode_pass=spread(r["decode_ms"]), gpu_ms_per_polish_pass=spread(r["polish_ms"]))
+        out[name] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweeps", type=int, default=30)
     ap.add_argument("--mcmc-sweeps", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--round", action="store_true", help="measure the rounding of the messages instead of the sweeps")
+    ap.add_argument("--forbid", action="store_true", help="measure the forbidden-entry reading beside the plain route on a 1e7 stand-in table")
     ap.add_argument("--polish", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if M.device_count() < 1:
         raise SystemExit("time_mplp.py: no HIP device is visible (nothing is measured without one)")
     ctx = M.Context(0)
-    if a.round:
+    if a.forbid:
+        result = dict(tool="tools/time_mplp.py --forbid", grids=[measure_forbid(ctx, cp, a.sweeps, a.repeats, a.polish) for cp in (4, 3)])
+    elif a.round:
         result = dict(tool="tools/time_mplp.py --round", grids=[measure_round(ctx, cp, a.mcmc_sweeps, a.repeats, a.polish) for cp in (4, 3)])
     else:
         result = dict(tool="tools/time_mplp.py", grids=[measure(ctx, cp, a.sweeps, a.mcmc_sweeps, a.repeats) for cp in (4, 3)])
