@@ -663,6 +663,13 @@ int msm_cost_mcmc_optimise_chains(msm_cost *c, double mcparam, int32_t iters, co
     return mcmc_run_device_chains(c->ctx, c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, mcparam, iters, seeds, K, labeling, labelings, energies, best);
 }
 
+// what msm_cost_mplp_forbidden reports after the three calls below: the tables' counts under the forbidden-entry reading, once the tables have passed
+// (st: the call's status, handed through)
+static int keep_counts(msm_cost *c, const MplpReading &r, int st) {
+    if (r.forbid && r.inspected) std::copy(r.counts, r.counts + 4, c->mplp_counts);
+    return st;
+}
+
 // MPLP over the same two device tables (mplp.cpp runs the sweeps): the Monte Carlo argument checks do not apply, the MPLP ones do
 int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies,
                            double *bounds, double *messages) {
@@ -672,7 +679,8 @@ int msm_cost_mplp_optimise(msm_cost *c, int32_t sweeps, int32_t *labeling, int32
     int N, L, T;
     MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
     const MplpOutputs o = {labeling, sweeps_run, energy, bound, energies, bounds, messages};
-    return mplp_run_device(c->ctx, "msm_mplp_optimise", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o, c->mplp_forbid, c->mplp_counts);
+    MplpReading r(c->mplp_forbid);
+    return keep_counts(c, r, mplp_run_device(c->ctx, "msm_mplp_optimise", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o, r));
 }
 
 // the switch to the forbidden-entry reading of the triplet table (DESIGN.md 5.19 "Forbidden entries") for the three calls here, and what the last
@@ -703,15 +711,14 @@ int msm_cost_mplp_round(msm_cost *c, int32_t sweeps, int32_t polish, int32_t the
     int32_t run = 0;
     double b = 0.0;
     const MplpOutputs o = {lab.data(), &run, nullptr, bound ? &b : nullptr, nullptr, nullptr, nullptr};
-    MSM_TRY(mplp_run_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, c->triplets.data(), N, L, T, sweeps, o, c->mplp_forbid, c->mplp_counts));
-    const MplpRoundOutputs r = {lab.data(), passes_run, energy, energies};
-    MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, true, false, c->triplets.data(), N, L, T, 0, polish, r,
-                              c->mplp_forbid, c->mplp_counts));
-    if (then_polish) {
-        const MplpRoundOutputs r1 = {lab.data(), nullptr, energy, nullptr};
-        MSM_TRY(mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, false, c->triplets.data(), N, L, T, 1, polish, r1,
-                                  c->mplp_forbid, c->mplp_counts));
-    }
+    // run, round on the run's messages with the run's reading, polish with the same reading
+    const char *what = "msm_mplp_round";
+    const double *d_U = c->d_U.p, *d_tc = c->d_clique_out.p;
+    MplpReading r(c->mplp_forbid);
+    MSM_TRY(keep_counts(c, r, mplp_run_device(c->ctx, what, d_U, d_tc, c->triplets.data(), N, L, T, sweeps, o, r)));
+    const MplpRoundOutputs r0 = {lab.data(), passes_run, energy, energies}, r1 = {lab.data(), nullptr, energy, nullptr};
+    MSM_TRY(mplp_round_device(c->ctx, what, d_U, d_tc, mplp_last_messages(c->ctx), c->triplets.data(), N, L, T, 0, polish, r0, r));
+    if (then_polish) MSM_TRY(mplp_round_device(c->ctx, what, d_U, d_tc, nullptr, c->triplets.data(), N, L, T, 1, polish, r1, r));
     std::copy(lab.begin(), lab.end(), labeling);
     if (sweeps_run) *sweeps_run = run;
     if (bound) *bound = b;
@@ -727,8 +734,8 @@ int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t
     int N, L, T;
     MSM_TRY(fill_tables_on_device(c, &N, &L, &T));
     const MplpRoundOutputs r = {labeling, passes_run, energy, energies};
-    return mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, false, true, c->triplets.data(), N, L, T, 1, polish, r, c->mplp_forbid,
-                             c->mplp_counts);
+    MplpReading rd(c->mplp_forbid);
+    return keep_counts(c, rd, mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, c->triplets.data(), N, L, T, 1, polish, r, rd));
 }
 
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on

@@ -1,7 +1,9 @@
 // mplp.cpp -- the host side of the MPLP optimiser (mplp.hpp; kernels: mplp_kernels.hip; the serial literal: mplp_host.hpp): the checks
-// both sides share, the loop that queues a chunk of sweeps -- a launch per level, the decode, the energy terms, the bound terms -- and sums what comes
-// back in the literal's order, and the entry points over host tables.  The rounding of the messages (mplp_round_device) has the same shape: a launch
-// per colour class and pass, a copy of the labelling and its energy terms per pass, one synchronisation per chunk of passes.
+// both sides share -- the tables are counted by one classification, on the host or on the device, and mplp_judge reads the counts as the plain or the
+// forbidden-entry reading asks (MplpReading carries the verdict from the sweeps to the rounding) -- the loop that queues a chunk of sweeps -- a launch
+// per level, the decode, the energy terms, the bound terms -- and sums what comes back in the literal's order, and the entry points over host tables.
+// The rounding of the messages (mplp_round_device) has the same shape: a launch per colour class and pass, a copy of the labelling and its energy
+// terms per pass, one synchronisation per chunk of passes.
 #include <cstring>
 
 #include "mplp.hpp"
@@ -13,7 +15,7 @@ namespace {
 struct MplpScratch {
     DevBuf<double> U, tc;  // the host tables of msm_mplp_optimise_gpu
     DevBuf<int4> sched;
-    DevBuf<int32_t> inc_ptr, inc_slot, start, labs, changed, flags;
+    DevBuf<int32_t> inc_ptr, inc_slot, start, labs, changed;
     DevBuf<unsigned long long> counts;  // k_mplp_classify: four of the tables, four of the rounding's messages
     DevBuf<double> m, eterms, bterms;
     // the rounding's own (mplp_round_device): it leaves m alone
@@ -40,26 +42,6 @@ int refuse_non_finite(const char *what, const char *table) {
                 what, table);
 }
 
-// the refusals of the forbidden-entry reading (DESIGN.md 5.19 "Forbidden entries"): each names the table and the class of value
-int refuse_minus_infinity(const char *what) {
-    return fail(MSM_ERR_INVALID,
-                "%s: the triplet table holds -infinity; the forbidden-entry reading takes NaN and +infinity as forbidden label combinations and nothing "
-                "else",
-                what);
-}
-
-int refuse_messages(const char *what, const int64_t mc[4]) {
-    return fail(MSM_ERR_INVALID, "%s: the messages hold %s; under the forbidden-entry reading a message is finite or +infinity", what, mc[1] ? "a NaN" : "-infinity");
-}
-
-// the forbid route's refusals over counted tables; MSM_OK leaves *forbidden = whether the triplet table holds a forbidden entry
-int check_counts(const char *what, const int64_t counts[4], bool *forbidden) {
-    if (counts[0]) return refuse_non_finite(what, "unary");
-    if (counts[3]) return refuse_minus_infinity(what);
-    *forbidden = counts[1] + counts[2] > 0;
-    return MSM_OK;
-}
-
 int refuse_label_count(const char *what, int L) {
     return fail(MSM_ERR_CAPACITY, "%s: %d labels; a factor's cavities and minima (6 L doubles) live in the LDS of one workgroup (at most %d labels)", what, L,
                 kMplpMaxLabels);
@@ -70,9 +52,64 @@ int check_pointers(const char *what, const double *unary, const double *tcosts, 
     return MSM_OK;
 }
 
+// The inspection both device routes start with: k_mplp_classify over the tables unless r holds their counts already, and over the messages d_m (null:
+// none), one download for both, then the judgement.  Where neither is to be looked at nothing is zeroed, launched or waited for.
+int inspect_device(msm_ctx *ctx, const char *what, MplpScratch &s, const double *d_U, size_t nU, const double *d_tc, size_t ntc, const double *d_m, size_t nm,
+                   MplpReading &r, bool *F) {
+    int64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are downloaded as they are");
+    if (!r.inspected || d_m) {
+        if (s.counts.zero(8, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int64_t) * 8);
+        if (!r.inspected) MSM_TRY(launch_mplp_classify(ctx, d_U, nU, d_tc, ntc, s.counts.p));
+        if (d_m) MSM_TRY(launch_mplp_classify(ctx, nullptr, 0, d_m, nm, s.counts.p + 4));
+        MSM_TRY(s.counts.download(reinterpret_cast<unsigned long long *>(got), 8, ctx));
+        MSM_TRY(check_status(ctx, what));
+        if (!r.inspected) std::copy(got, got + 4, r.counts);
+    }
+    return mplp_judge(what, r, d_m ? got + 4 : nullptr, F);
+}
+
+// What the two device loops share.  The energy terms of one labelling: k_mcmc_chain_terms with K = 1 (the records may come in any order)
+McmcChainArgs chain_terms_args(const double *d_U, const double *d_tc, const int4 *records, int32_t *labeling, int N, int L, int T, int levels, int *status) {
+    return {{d_U, d_tc, records, nullptr, nullptr, labeling, N, L, T, levels, 0, status}, 1, 0};
+}
+
+// sweeps or passes per chunk of n: what a chunk brings back (arrays of N + T doubles per sweep) stays below 32 MB each, and a run that reaches its
+// fixed point early in a chunk has at most 255 idle sweeps' launches behind it
+int chunk_size(int n, size_t nterms) { return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(n, 256), ((size_t)1 << 22) / nterms)); }
+
+int ensure_events(MplpScratch &s) {
+    for (hipEvent_t &e : s.ev)
+        if (!e) MSM_HIP(hipEventCreate(&e));
+    return MSM_OK;
+}
+
 }  // namespace
 
 namespace msm {
+
+int mplp_judge(const char *what, MplpReading &r, const int64_t *mc, bool *F) {
+    const int64_t *t = r.counts;
+    if (t[0]) return refuse_non_finite(what, "unary");
+    if (!r.forbid) {
+        if (t[1] || t[2] || t[3]) return refuse_non_finite(what, "triplet");
+        if (mc && (mc[1] || mc[2] || mc[3])) return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
+    } else {  // DESIGN.md 5.19 "Forbidden entries": each refusal names the table and the class of value
+        if (t[3])
+            return fail(MSM_ERR_INVALID,
+                        "%s: the triplet table holds -infinity; the forbidden-entry reading takes NaN and +infinity as forbidden label combinations and "
+                        "nothing else",
+                        what);
+        if (mc && (mc[1] || mc[3]))
+            return fail(MSM_ERR_INVALID, "%s: the messages hold %s; under the forbidden-entry reading a message is finite or +infinity", what,
+                        mc[1] ? "a NaN" : "-infinity");
+    }
+    // what is left of the counts is zero under the plain reading: the plain code where nothing is forbidden, whichever reading was asked for
+    r.inspected = true;
+    r.F = t[1] + t[2] > 0;
+    *F = r.F || (mc && mc[2] > 0);  // a message of +infinity
+    return MSM_OK;
+}
 
 int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling) {
     if (sweeps < 0) return fail(MSM_ERR_INVALID, "%s: bad arguments", what);
@@ -89,38 +126,15 @@ int mplp_round_check(const char *what, int L, int mode, int polish) {
     return MSM_OK;
 }
 
-int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, bool use_scratch_m, bool check_tables,
-                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o, bool forbid, int64_t *counts) {
+const double *mplp_last_messages(msm_ctx *ctx) { return mplp_scratch(ctx).m.p; }
+
+int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, const int32_t *triplets, int N, int L, int T,
+                      int mode, int polish, const MplpRoundOutputs &o, MplpReading &r) {
     MplpScratch &s = mplp_scratch(ctx);
     const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
-    if (use_scratch_m) d_m = s.m.p;
     if (mode != 0 || nm == 0) d_m = nullptr;  // mode 1 reads no messages
     bool F = false;  // the forbidden-aware kernels: taken where the tables or the messages call for them, the plain ones otherwise
-    if (forbid) {
-        // one pass over both tables and one over the messages; check_tables false: counts holds what the caller's pass over these tables counted
-        int64_t got[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are downloaded as they are");
-        if (s.counts.zero(8, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int64_t) * 8);
-        if (check_tables) MSM_TRY(launch_mplp_classify(ctx, d_U, nU, d_tc, ntc, s.counts.p));
-        if (d_m) MSM_TRY(launch_mplp_classify(ctx, nullptr, 0, d_m, nm, s.counts.p + 4));
-        MSM_TRY(s.counts.download(reinterpret_cast<unsigned long long *>(got), 8, ctx));
-        MSM_TRY(check_status(ctx, what));
-        if (!check_tables && counts) std::copy(counts, counts + 4, got);
-        MSM_TRY(check_counts(what, got, &F));
-        if (got[5] || got[7]) return refuse_messages(what, got + 4);
-        F |= got[6] > 0;  // a message of +infinity
-        if (counts) std::copy(got, got + 4, counts);
-    } else {
-        int32_t bad[4] = {0, 0, 0, 0};
-        if (s.flags.zero(4, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 4);
-        if (check_tables) MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
-        if (d_m) MSM_TRY(launch_mplp_finite(ctx, d_m, nm, nullptr, 0, s.flags.p + 2));
-        MSM_TRY(s.flags.download(bad, 4, ctx));
-        MSM_TRY(check_status(ctx, what));
-        if (bad[0]) return refuse_non_finite(what, "unary");
-        if (bad[1]) return refuse_non_finite(what, "triplet");
-        if (bad[2]) return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
-    }
+    MSM_TRY(inspect_device(ctx, what, s, d_U, nU, d_tc, ntc, d_m, nm, r, &F));
     MSM_TRY(mplp_round_check(what, L, mode, polish));
 
     MplpIncidence inc;
@@ -129,9 +143,8 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
     mplp_build_colouring(triplets, N, inc, col);
     std::vector<int4> rec((size_t)T);
     for (int t = 0; t < T; ++t) rec[(size_t)t] = make_int4(t, triplets[3 * (size_t)t], triplets[3 * (size_t)t + 1], triplets[3 * (size_t)t + 2]);
-    // passes per chunk: a chunk's labellings and terms stay below 32 MB, as the sweeps' do
     const int first = mode == 0 ? 2 : 1;  // candidates ahead of the polish passes
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(polish, 256), ((size_t)1 << 22) / nterms));
+    const int chunk = chunk_size(polish, nterms);
     const size_t held = (size_t)std::max(chunk, first);
     MSM_TRY(s.tri.upload_vec(rec, ctx));
     MSM_TRY(s.inc_ptr.upload_vec(inc.ptr, ctx));
@@ -142,8 +155,7 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
     if (s.rchanged.zero((size_t)std::max(polish, 1), ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * (size_t)polish);
     if (s.rlabs.ensure(held * N) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * held * N);
     if (s.rterms.ensure(held * nterms) != hipSuccess) return stage_alloc_failed(sizeof(double) * held * nterms);
-    for (hipEvent_t &e : s.ev)
-        if (!e) MSM_HIP(hipEventCreate(&e));
+    MSM_TRY(ensure_events(s));
 
     MplpRoundArgs a;
     a.U = d_U;
@@ -160,21 +172,7 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
     a.L = L;
     a.T = T;
     a.status = ctx->d_status;
-    McmcChainArgs c;  // the energy terms of the labelling being walked: k_mcmc_chain_terms with K = 1 (the records may come in any order)
-    c.a.U = d_U;
-    c.a.tc = d_tc;
-    c.a.sched = s.tri.p;
-    c.a.level_off = nullptr;
-    c.a.prop = nullptr;
-    c.a.labeling = s.cur.p;
-    c.a.N = N;
-    c.a.L = L;
-    c.a.T = T;
-    c.a.levels = 0;
-    c.a.sweeps = 0;
-    c.a.status = ctx->d_status;
-    c.chains = 1;
-    c.chunk_sweeps = 0;
+    const McmcChainArgs c = chain_terms_args(d_U, d_tc, s.tri.p, s.cur.p, N, L, T, 0, ctx->d_status);  // of the labelling being walked
     const int classes = col.classes();
     auto snapshot = [&](size_t j) -> int {  // the labelling as it stands and its energy terms, to place j of the chunk
         MSM_HIP(hipMemcpyAsync(s.rlabs.p + j * N, s.cur.p, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToDevice, ctx->stream));
@@ -249,28 +247,12 @@ int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const d
 }
 
 int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, int sweeps,
-                    const MplpOutputs &o, bool forbid, int64_t *counts) {
+                    const MplpOutputs &o, MplpReading &r) {
     MplpScratch &s = mplp_scratch(ctx);
     const size_t nU = (size_t)L * N, ntc = (size_t)T * L * L * L, nm = 3 * (size_t)T * L, nterms = (size_t)N + T;
     // the refusals that need the tables: one pass over both, before anything else is launched
     bool F = false;  // the forbidden-aware kernels: only where the table holds a forbidden entry, so a finite table runs the plain ones
-    if (forbid) {
-        int64_t got[4] = {0, 0, 0, 0};
-        if (s.counts.zero(4, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int64_t) * 4);
-        MSM_TRY(launch_mplp_classify(ctx, d_U, nU, d_tc, ntc, s.counts.p));
-        MSM_TRY(s.counts.download(reinterpret_cast<unsigned long long *>(got), 4, ctx));
-        MSM_TRY(check_status(ctx, what));
-        MSM_TRY(check_counts(what, got, &F));
-        if (counts) std::copy(got, got + 4, counts);
-    } else {
-        int32_t bad[2] = {0, 0};
-        if (s.flags.zero(2, ctx->stream) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * 2);
-        MSM_TRY(launch_mplp_finite(ctx, d_U, nU, d_tc, ntc, s.flags.p));
-        MSM_TRY(s.flags.download(bad, 2, ctx));
-        MSM_TRY(check_status(ctx, what));
-        if (bad[0]) return refuse_non_finite(what, "unary");
-        if (bad[1]) return refuse_non_finite(what, "triplet");
-    }
+    MSM_TRY(inspect_device(ctx, what, s, d_U, nU, d_tc, ntc, nullptr, 0, r, &F));
     if (L > kMplpMaxLabels) return refuse_label_count(what, L);
 
     McmcSchedule sch;
@@ -282,9 +264,7 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
     }
     MplpIncidence inc;
     mplp_build_incidence(triplets, N, T, inc);
-    // sweeps per chunk: the terms of a chunk (two arrays of N + T doubles per sweep) stay below 32 MB each, and a run that reaches its fixed point
-    // early in a chunk has at most 255 idle sweeps' launches behind it
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min(sweeps, 256), ((size_t)1 << 22) / nterms));
+    const int chunk = chunk_size(sweeps, nterms);
     MSM_TRY(s.sched.upload_vec(rec, ctx));
     MSM_TRY(s.inc_ptr.upload_vec(inc.ptr, ctx));
     MSM_TRY(s.inc_slot.upload_vec(inc.slot, ctx));
@@ -294,8 +274,7 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
     if (s.labs.ensure((size_t)chunk * N) != hipSuccess) return stage_alloc_failed(sizeof(int32_t) * (size_t)chunk * N);
     if (s.eterms.ensure((size_t)chunk * nterms) != hipSuccess || s.bterms.ensure((size_t)chunk * nterms) != hipSuccess)
         return stage_alloc_failed(sizeof(double) * (size_t)chunk * nterms);
-    for (hipEvent_t &e : s.ev)
-        if (!e) MSM_HIP(hipEventCreate(&e));
+    MSM_TRY(ensure_events(s));
 
     MplpArgs a;
     a.U = d_U;
@@ -309,21 +288,7 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
     a.L = L;
     a.T = T;
     a.status = ctx->d_status;
-    McmcChainArgs c;  // the energy terms of one labelling: k_mcmc_chain_terms with K = 1
-    c.a.U = d_U;
-    c.a.tc = d_tc;
-    c.a.sched = s.sched.p;
-    c.a.level_off = nullptr;
-    c.a.prop = nullptr;
-    c.a.labeling = s.start.p;
-    c.a.N = N;
-    c.a.L = L;
-    c.a.T = T;
-    c.a.levels = sch.levels();
-    c.a.sweeps = 0;
-    c.a.status = ctx->d_status;
-    c.chains = 1;
-    c.chunk_sweeps = 0;
+    McmcChainArgs c = chain_terms_args(d_U, d_tc, s.sched.p, s.start.p, N, L, T, sch.levels(), ctx->d_status);
 
     // candidate 0: the start
     std::vector<double> eterms((size_t)chunk * nterms), bterms((size_t)chunk * nterms);
@@ -406,6 +371,24 @@ int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const dou
 
 namespace {
 
+// The host routes' inspection: mplp_classify over the tables and, in the rounding's mode 0, the messages; the same judgement.  counts (the forbid
+// entry points'; may be null) receives the tables' counts once nothing is refused.
+int inspect_host(const char *what, bool forbid, const double *unary, const double *tcosts, int N, int L, int T, const double *messages, int64_t *counts, bool *F) {
+    MplpReading r(forbid);
+    int64_t mc[4];
+    mplp_classify(unary, (size_t)L * N, tcosts, (size_t)T * L * L * L, r.counts);
+    if (messages) mplp_classify(nullptr, 0, messages, 3 * (size_t)T * L, mc);
+    MSM_TRY(mplp_judge(what, r, messages ? mc : nullptr, F));
+    if (counts) std::copy(r.counts, r.counts + 4, counts);
+    return MSM_OK;
+}
+
+// what a device route's reading leaves in the forbid entry points' counts (may be null): as inspect_host, and before a later refusal as well
+int hand_counts(const MplpReading &r, int64_t *counts, int st) {
+    if (counts && r.inspected) std::copy(r.counts, r.counts + 4, counts);
+    return st;
+}
+
 // msm_mplp_optimise and msm_mplp_optimise_forbid (forbid; counts may be null)
 int optimise_host(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, int32_t sweeps, const MplpOutputs &o,
                   bool forbid, int64_t *counts) {
@@ -413,15 +396,7 @@ int optimise_host(const double *unary, const double *tcosts, const int32_t *trip
     MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, sweeps, o.labeling));
     MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, sweeps, o.labeling));
     bool F = false;  // the plain literal where the table holds no forbidden entry
-    if (forbid) {
-        int64_t got[4];
-        mplp_classify(unary, (size_t)L * N, tcosts, (size_t)T * L * L * L, got);
-        MSM_TRY(check_counts(what, got, &F));
-        if (counts) std::copy(got, got + 4, counts);
-    } else {
-        if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
-        if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
-    }
+    MSM_TRY(inspect_host(what, forbid, unary, tcosts, N, L, T, nullptr, counts, &F));
     if (L > kMplpMaxLabels) return refuse_label_count(what, L);
     mplp_run_host(unary, tcosts, triplets, N, L, T, sweeps, o, F);
     return MSM_OK;
@@ -440,7 +415,8 @@ int optimise_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const 
     if (s.tc.ensure(ntc ? ntc : 1) != hipSuccess) return stage_alloc_failed(sizeof(double) * ntc);
     MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
     MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
-    return mplp_run_device(ctx, "msm_mplp_optimise", s.U.p, s.tc.p, triplets, N, L, T, sweeps, o, forbid, counts);
+    MplpReading r(forbid);
+    return hand_counts(r, counts, mplp_run_device(ctx, "msm_mplp_optimise", s.U.p, s.tc.p, triplets, N, L, T, sweeps, o, r));
 }
 
 int round_host(const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T, const double *messages, int32_t mode,
@@ -448,23 +424,11 @@ int round_host(const double *unary, const double *tcosts, const int32_t *triplet
     const char *what = "msm_mplp_round";
     MSM_TRY(check_pointers(what, unary, tcosts, triplets, N, L, T, 0, o.labeling));
     MSM_TRY(mplp_check_arguments(what, triplets, N, L, T, 0, o.labeling));
+    if (mode != 0) messages = nullptr;  // mode 1 reads no messages
     bool F = false;
-    if (forbid) {
-        int64_t got[4], mc[4] = {0, 0, 0, 0};
-        mplp_classify(unary, (size_t)L * N, tcosts, (size_t)T * L * L * L, got);
-        MSM_TRY(check_counts(what, got, &F));
-        if (mode == 0 && messages) mplp_classify(nullptr, 0, messages, 3 * (size_t)T * L, mc);
-        if (mc[1] || mc[3]) return refuse_messages(what, mc);
-        F |= mc[2] > 0;  // a message of +infinity
-        if (counts) std::copy(got, got + 4, counts);
-    } else {
-        if (!mplp_all_finite(unary, (size_t)L * N)) return refuse_non_finite(what, "unary");
-        if (!mplp_all_finite(tcosts, (size_t)T * L * L * L)) return refuse_non_finite(what, "triplet");
-        if (mode == 0 && messages && !mplp_all_finite(messages, 3 * (size_t)T * L))
-            return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
-    }
+    MSM_TRY(inspect_host(what, forbid, unary, tcosts, N, L, T, messages, counts, &F));
     MSM_TRY(mplp_round_check(what, L, mode, polish));
-    mplp_round_host(unary, tcosts, triplets, N, L, T, mode == 0 ? messages : nullptr, mode, polish, o, F);
+    mplp_round_host(unary, tcosts, triplets, N, L, T, messages, mode, polish, o, F);
     return MSM_OK;
 }
 
@@ -485,7 +449,8 @@ int round_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int
     MSM_TRY(upload_in_pieces(ctx, s.U.p, unary, sizeof(double) * nU));
     MSM_TRY(upload_in_pieces(ctx, s.tc.p, tcosts, sizeof(double) * ntc));
     if (with_m) MSM_TRY(upload_in_pieces(ctx, s.rm.p, messages, sizeof(double) * nm));
-    return mplp_round_device(ctx, what, s.U.p, s.tc.p, with_m ? s.rm.p : nullptr, false, true, triplets, N, L, T, mode, polish, o, forbid, counts);
+    MplpReading r(forbid);
+    return hand_counts(r, counts, mplp_round_device(ctx, what, s.U.p, s.tc.p, with_m ? s.rm.p : nullptr, triplets, N, L, T, mode, polish, o, r));
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
-// mplp.hpp -- the MPLP optimiser's sweeps on the GPU: the kernels' arguments and the host loop around them (mplp.cpp,
-// mplp_kernels.hip).  The definition, the incidence lists and the serial literal are plain host code: mplp_host.hpp.
+// mplp.hpp -- the MPLP optimiser's sweeps on the GPU: the kernels' arguments, the reading of the tables that every route judges the same
+// way (MplpReading, mplp_judge) and the host loops around the kernels (mplp.cpp, mplp_kernels.hip).  The definition, the incidence lists and the serial
+// literal are plain host code: mplp_host.hpp.
 #pragma once
 
 #include "internal.hpp"
@@ -31,8 +32,6 @@ int launch_mplp_decode(msm_ctx *ctx, const MplpArgs &a, int32_t *label, double *
 // the factor terms of the bound after sweep `sweep`, a workgroup per factor, factor_terms[t]; returns at once where the update of that sweep did (the
 // host repeats the previous sweep's bound).  sweep < 0: unconditional.
 int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_terms, int sweep, bool forbid = false);
-// flags[0] / flags[1] raised to 1 by a non-finite entry of the unary / triplet table
-int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, int32_t *flags);
 // adds to counts[0] the non-finite entries of U and to counts[1..3] the NaN / +inf / -inf entries of tc (either may be null with n = 0)
 int launch_mplp_classify(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, unsigned long long *counts);
 
@@ -59,21 +58,33 @@ int mplp_update_slots(int L);
 
 // the checks of msm_mplp_round besides mplp_check_arguments: the mode, the polish count, the label count
 int mplp_round_check(const char *what, int L, int mode, int polish);
-// The rounding over tables that lie on the device, arguments checked by the caller.  d_m: the device messages of mode 0 (null: all zero; use_scratch_m:
-// the messages the context's last mplp_run_device left).  check_tables: look for non-finite table entries first (the messages of mode 0 always are).
-// Complete on return; the outputs are written only when the call succeeds.  forbid: the forbidden-entry reading (DESIGN.md 5.19 "Forbidden entries") --
-// the tables and the messages are classified instead, and counts[4] (may be null) receives the tables' counts; with check_tables false counts hands in
-// what the caller's mplp_run_device counted over these tables.
-int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, bool use_scratch_m, bool check_tables,
-                      const int32_t *triplets, int N, int L, int T, int mode, int polish, const MplpRoundOutputs &o,
-                      bool forbid = false, int64_t *counts = nullptr);
+// How the tables are read and what an inspection of them found: handed from the sweeps to the rounding that follows them over the same tables, so that
+// the tables are inspected once.  forbid: the forbidden-entry reading (DESIGN.md 5.19 "Forbidden entries"), the plain one otherwise.
+struct MplpReading {
+    bool forbid;
+    bool inspected = false;             // counts and F hold what a pass over the tables found, and the reading does not refuse them
+    int64_t counts[4] = {0, 0, 0, 0};   // mplp_classify's
+    bool F = false;                     // the tables call for the forbidden-aware code (never under the plain reading)
+    explicit MplpReading(bool forbid_) : forbid(forbid_) {}
+};
+// The one judgement of counted tables, and of the counted messages of mode 0 (mc; null: none), under either reading: a refusal, or MSM_OK with
+// r.inspected and r.F set and *F = whether the tables or the messages call for the forbidden-aware code.
+int mplp_judge(const char *what, MplpReading &r, const int64_t *mc, bool *F);
+
+// the device messages the context's last mplp_run_device left (T x 3 x L; null before the first run)
+const double *mplp_last_messages(msm_ctx *ctx);
+// The rounding over tables that lie on the device, arguments checked by the caller.  d_m: the device messages of mode 0 (null: all zero; mode 1 reads
+// none).  r: the reading; where a run has inspected these tables already no pass over them is launched, and nothing at all where there are no messages
+// to inspect either; otherwise the inspection fills r.  Complete on return; the outputs are written only when the call succeeds.
+int mplp_round_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const double *d_m, const int32_t *triplets, int N, int L, int T,
+                      int mode, int polish, const MplpRoundOutputs &o, MplpReading &r);
 
 // the host optimiser's checks, with its messages (what: the entry point's name for the MPLP-specific refusals); the tables are not looked at
 int mplp_check_arguments(const char *what, const int32_t *triplets, int N, int L, int T, int sweeps, const int32_t *labeling);
-// MPLP over tables that lie on the device (d_U: L x N, d_tc: T x L^3), arguments checked by the caller: the finiteness pass first, then the sweeps.
-// Complete on return; the outputs are written only when the call succeeds.  forbid: k_mplp_classify instead of the finiteness pass, its four counts to
-// counts (may be null), and the forbidden-aware kernels where the triplet table holds a NaN or +inf.
+// MPLP over tables that lie on the device (d_U: L x N, d_tc: T x L^3), arguments checked by the caller: the inspection first (k_mplp_classify, judged
+// under r.forbid; r leaves with the counts), then the sweeps, with the forbidden-aware kernels where r.F.  Complete on return; the outputs are written
+// only when the call succeeds.
 int mplp_run_device(msm_ctx *ctx, const char *what, const double *d_U, const double *d_tc, const int32_t *triplets, int N, int L, int T, int sweeps,
-                    const MplpOutputs &o, bool forbid = false, int64_t *counts = nullptr);
+                    const MplpOutputs &o, MplpReading &r);
 
 }  // namespace msm

@@ -65,12 +65,6 @@ inline double mplp_energy_of_terms(const double *terms, int N, int T, bool forbi
     return u + pw + tc;
 }
 
-inline bool mplp_all_finite(const double *v, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!(v[i] - v[i] == 0.0)) return false;  // a NaN or an infinity
-    return true;
-}
-
 // d(x) = unary[x * N + i] plus the messages over the incidence of i in order, but for slot `skip` (-1: none skipped -- the belief)
 inline void mplp_node_sum(const double *unary, const double *m, const MplpIncidence &inc, int N, int L, int i, int32_t skip, double *d) {
     for (int x = 0; x < L; ++x) {

@@ -22,6 +22,7 @@
 // would show it.
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 #include "mplp.hpp"
 
@@ -30,6 +31,7 @@ namespace msm {
 namespace {
 
 __device__ __forceinline__ void raise_status(int *status, int code) { atomicMin(status, code); }
+__device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 // doubles to integers of the same order (-0.0 below +0.0) and back: the map is its own inverse
 __device__ __forceinline__ long long order_key(long long b) { return b ^ ((b >> 63) & 0x7fffffffffffffffLL); }
@@ -86,7 +88,7 @@ constexpr int kMplpBatch = 4;  // table entries a thread has in flight
 // batches exist for (measured: 0.70 against 0.44 ms per sweep on the ico4 table).
 template <bool F>
 __device__ __forceinline__ double hat(double v) {
-    if constexpr (F) return v < __longlong_as_double(0x7ff0000000000000LL) ? v : __longlong_as_double(0x7ff0000000000000LL);
+    if constexpr (F) return v < pos_inf() ? v : pos_inf();
     return v;
 }
 
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_update(MplpArgs a, int be
     double *d = s_mplp;
     long long *M = reinterpret_cast<long long *>(s_mplp + 3 * (size_t)L);
     const unsigned S = (unsigned)slots, stride = S > 1 ? S + 1 : 1, mine = tid & (S - 1);
-    const long long inf_key = key_of(__longlong_as_double(0x7ff0000000000000LL));
+    const long long inf_key = key_of(pos_inf());
     for (unsigned idx = tid; idx < 3 * L * stride; idx += kMplpThreads) M[idx] = inf_key;
     for (unsigned idx = tid; idx < 3 * L; idx += kMplpThreads) {
         const unsigned s = idx / L, x = idx - s * L;
@@ -166,6 +168,7 @@ __global__ __launch_bounds__(256) void k_mplp_decode(MplpArgs a, int32_t *__rest
         const double v = node_sum(a, (unsigned)i, x, -1);
         if (bx == INT_MAX || v < bv) bv = v, bx = (int)x;
     }
+    // (wave_argmin spelled out: through the helper the compiler orders this kernel's instructions differently, and its schedule stays as measured)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const double ov = __shfl_down(bv, off);
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_factor_terms(MplpArgs a, 
     __syncthreads();
     const unsigned L3 = L * L * L;
     const double *__restrict__ th = a.tc + (size_t)t * L3;
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const double inf = pos_inf();
     double lo = inf;
     Abc p(tid, kMplpThreads, L);
     for (unsigned e = tid; e < L3; e += kMplpThreads, p.advance()) {
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(256) void k_mplp_classify(const double *__restrict_
                                                        unsigned long long *__restrict__ counts) {
     __shared__ unsigned s_cnt[4][4];
     const size_t stride = (size_t)gridDim.x * 256;
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const double inf = pos_inf();
     unsigned n[4] = {0, 0, 0, 0};  // (a thread sees at most ceil(2^63 / stride) entries; the grid keeps that far below 2^32)
     for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nU; j += stride) n[0] += !(U[j] - U[j] == 0.0);
     for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < ntc; j += stride) {
@@ -239,15 +242,6 @@ __global__ __launch_bounds__(256) void k_mplp_classify(const double *__restrict_
         const unsigned long long total = (unsigned long long)s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
         if (total) atomicAdd(&counts[threadIdx.x], total);
     }
-}
-
-__global__ __launch_bounds__(256) void k_mplp_finite(const double *__restrict__ U, size_t nU, const double *__restrict__ tc, size_t ntc, int32_t *flags) {
-    const size_t stride = (size_t)gridDim.x * 256;
-    bool bad_u = false, bad_t = false;
-    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nU; j += stride) bad_u |= !(U[j] - U[j] == 0.0);
-    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < ntc; j += stride) bad_t |= !(tc[j] - tc[j] == 0.0);
-    if (bad_u) flags[0] = 1;
-    if (bad_t) flags[1] = 1;
 }
 
 // ---------------------------------------------------------------- rounding (DESIGN.md 5.19 "Rounding"; the literal: mplp_round_host)
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(kMplpThreads) void k_mplp_round(MplpRoundArgs a, in
     long long *G = reinterpret_cast<long long *>(w + 8);
     const unsigned S = (unsigned)slots, stride = S > 1 ? S + 1 : 1, mine = tid & (S - 1);
     const unsigned L2 = L * L, L3 = L2 * L;
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const double inf = pos_inf();
     const long long inf_key = key_of(inf);
     for (unsigned x = tid; x < L; x += kMplpThreads) score[x] = a.U[(size_t)x * N + i];
     const int k0 = a.inc_ptr[i], k1 = a.inc_ptr[i + 1];
@@ -435,6 +429,17 @@ int check_shape(const MplpArgs &a) {
     return MSM_OK;
 }
 
+// launch(std::true_type) or launch(std::false_type): the one choice between a kernel's forbidden-aware instantiation and its plain one
+template <class Launch>
+int launch_either(bool forbid, Launch launch) {
+    if (forbid)
+        launch(std::true_type());
+    else
+        launch(std::false_type());
+    MSM_HIP(hipGetLastError());
+    return MSM_OK;
+}
+
 }  // namespace
 
 // copies of every minimum in LDS: the largest power of two up to 64 with 3 L cavities and 3 L padded rows of copies within 64 KB.  MSMHIP_MPLP_SLOTS=n
@@ -455,12 +460,9 @@ int launch_mplp_update(msm_ctx *ctx, const MplpArgs &a, int begin, int count, in
     if (begin < 0 || begin + count > a.T || sweep < 0) return fail(MSM_ERR_INVALID, "msm_mplp_optimise_gpu: bad launch (factors %d + %d of %d)", begin, count, a.T);
     const int slots = mplp_update_slots(a.L);
     const size_t lds = sizeof(double) * 3 * (size_t)a.L * (1 + (size_t)(slots > 1 ? slots + 1 : 1));
-    if (forbid)
-        hipLaunchKernelGGL(k_mplp_update<true>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, sweep, slots);
-    else
-        hipLaunchKernelGGL(k_mplp_update<false>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, sweep, slots);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
+    return launch_either(forbid, [&](auto F) {
+        hipLaunchKernelGGL(k_mplp_update<decltype(F)::value>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, sweep, slots);
+    });
 }
 
 int launch_mplp_decode(msm_ctx *ctx, const MplpArgs &a, int32_t *label, double *node_terms) {
@@ -474,20 +476,9 @@ int launch_mplp_factor_terms(msm_ctx *ctx, const MplpArgs &a, double *factor_ter
     MSM_TRY(check_shape(a));
     if (a.T == 0) return MSM_OK;
     const size_t lds = sizeof(double) * (3 * (size_t)a.L + kMplpThreads / 64);
-    if (forbid)
-        hipLaunchKernelGGL(k_mplp_factor_terms<true>, dim3((unsigned)a.T), dim3(kMplpThreads), lds, ctx->stream, a, factor_terms, sweep);
-    else
-        hipLaunchKernelGGL(k_mplp_factor_terms<false>, dim3((unsigned)a.T), dim3(kMplpThreads), lds, ctx->stream, a, factor_terms, sweep);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
-}
-
-int launch_mplp_finite(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, int32_t *flags) {
-    const size_t n = std::max(nU, ntc);
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 4096));
-    hipLaunchKernelGGL(k_mplp_finite, dim3(blocks), dim3(256), 0, ctx->stream, U, nU, tc, ntc, flags);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
+    return launch_either(forbid, [&](auto F) {
+        hipLaunchKernelGGL(k_mplp_factor_terms<decltype(F)::value>, dim3((unsigned)a.T), dim3(kMplpThreads), lds, ctx->stream, a, factor_terms, sweep);
+    });
 }
 
 int launch_mplp_classify(msm_ctx *ctx, const double *U, size_t nU, const double *tc, size_t ntc, unsigned long long *counts) {
@@ -509,24 +500,18 @@ int launch_mplp_round(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count
     if (count == 0) return MSM_OK;
     const int slots = mplp_update_slots(a.L);
     const size_t lds = sizeof(double) * (3 * (size_t)a.L + 8 + (size_t)a.L * (size_t)(slots > 1 ? slots + 1 : 1));
-    if (forbid)
-        hipLaunchKernelGGL(k_mplp_round<true>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
-    else
-        hipLaunchKernelGGL(k_mplp_round<false>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
+    return launch_either(forbid, [&](auto F) {
+        hipLaunchKernelGGL(k_mplp_round<decltype(F)::value>, dim3((unsigned)count), dim3(kMplpThreads), lds, ctx->stream, a, begin, count, frontier, slots);
+    });
 }
 
 int launch_mplp_polish(msm_ctx *ctx, const MplpRoundArgs &a, int begin, int count, int pass, bool forbid) {
     MSM_TRY(check_round_launch(a, begin, count));
     if (count == 0) return MSM_OK;
     if (pass < 0) return fail(MSM_ERR_INVALID, "msm_mplp_round_gpu: bad launch (pass %d)", pass);
-    if (forbid)
-        hipLaunchKernelGGL(k_mplp_polish<true>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
-    else
-        hipLaunchKernelGGL(k_mplp_polish<false>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
-    MSM_HIP(hipGetLastError());
-    return MSM_OK;
+    return launch_either(forbid, [&](auto F) {
+        hipLaunchKernelGGL(k_mplp_polish<decltype(F)::value>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, a, begin, count, pass);
+    });
 }
 
 }  // namespace msm

@@ -31,7 +31,9 @@ int main() {
         std::vector<double> U((size_t)L * N), tc((size_t)T * L * L * L);
         for (double &v : U) v = u(gen);
         for (double &v : tc) v = u(gen);
-        if (!mplp_all_finite(tc.data(), tc.size())) return fail("finite table called non-finite");
+        int64_t counts[4];
+        mplp_classify(U.data(), U.size(), tc.data(), tc.size(), counts);
+        if (counts[0] || counts[1] || counts[2] || counts[3]) return fail("finite tables called non-finite");
         std::vector<int32_t> lab(N, 4), start = lab;
         std::vector<double> energies(sweeps), bounds(sweeps), m((size_t)3 * T * L), terms((size_t)N + T);
         int32_t run = -1;
@@ -48,7 +50,8 @@ int main() {
         mplp_run_host(U.data(), tc.data(), tri.data(), N, L, T, sweeps, MplpOutputs{lab2.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
         if (lab2 != lab) return fail("the labelling depends on the optional outputs");
         tc[17] = std::nan("");
-        if (mplp_all_finite(tc.data(), tc.size())) return fail("a NaN not found");
+        mplp_classify(U.data(), U.size(), tc.data(), tc.size(), counts);
+        if (counts[0] != 0 || counts[1] != 1 || counts[2] != 0 || counts[3] != 0) return fail("a NaN not counted as one NaN");
         tri[5] = tri[3];
         if (mplp_first_repeated_node(tri.data(), T) != 1) return fail("the repeated node not found");
     }

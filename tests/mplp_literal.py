@@ -162,3 +162,27 @@ def fan_case(L=4, seed=5):
 
 
 OCTAHEDRON = np.array([[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]], dtype=np.int32)
+
+
+def non_finite_refusals():
+    """((U, tc, triplets, start), the message) of the plain reading's refusals over tables with a non-finite entry, on the T = 20 / L = 5 case: every
+    class of triplet entry is named as the triplet table's non-finite value (-inf too: "holds -infinity" is the forbidden-entry reading's text), an
+    infinite unary entry as the unary table's, and the unary table is named first where both tables hold one"""
+    U, tc, triplets, start = (np.array(a) for a in ico_case(0, 5, 31))
+    unary, triplet = "MSM_ERR_INVALID.*the unary table holds a non-finite value.*--fixnan", "MSM_ERR_INVALID.*the triplet table holds a non-finite value.*--fixnan"
+    minus_t, plus_t, nan_t, minus_u, nan_u = np.array(tc), np.array(tc), np.array(tc), np.array(U), np.array(U)
+    minus_t[7, 0, 3, 1] = -np.inf
+    plus_t[19, 4, 4, 4] = np.inf
+    nan_t[0, 0, 0, 0] = np.nan
+    minus_u[4, 11] = -np.inf
+    nan_u[2, 3] = np.nan
+    return [((U, minus_t, triplets, start), triplet), ((U, plus_t, triplets, start), triplet), ((U, nan_t, triplets, start), triplet),
+            ((minus_u, tc, triplets, start), unary), ((nan_u, plus_t, triplets, start), unary)]
+
+
+def last_entry_forbidden():
+    """the T = 20 / L = 5 case whose only non-finite entry is +inf in the last element of the last triplet: the forbidden-entry reading counts
+    (0, 0, 1, 0), the last thing a pass over the table reads"""
+    U, tc, triplets, start = (np.array(a) for a in ico_case(0, 5, 31))
+    tc[-1, -1, -1, -1] = np.inf
+    return U, tc, triplets, start

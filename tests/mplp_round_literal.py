@@ -138,6 +138,17 @@ def combinations(triplets, N):
     return seen
 
 
+def unread_messages():
+    """messages of the T = 20 / L = 5 case with one +inf, one -inf, one NaN: the plain reading's mode 0 refuses each with the same words (not the
+    forbidden-entry reading's, which allows the first), and mode 1 reads none of them"""
+    out = []
+    for value in (np.inf, -np.inf, np.nan):
+        m = np.zeros((20, 3, 5))
+        m[3, 1, 2] = value
+        out.append(m)
+    return out
+
+
 def refusal_cases():
     """(arguments of mplp_round, the message); shared with the GPU tests"""
     U, tc, triplets, start = (np.array(a) for a in ML.ico_case(0, 5, 31))
@@ -151,6 +162,8 @@ def refusal_cases():
     inf_t[19, 4, 4, 4] = -np.inf
     nan_m[3, 1, 2] = np.inf
     ok = (U, tc, triplets, start, None, 0, 2)
+    plain = [(args + (None, 1, 2), pattern) for args, pattern in ML.non_finite_refusals()]  # the tables are looked at in either mode
+    plain += [((U, tc, triplets, start, m, 0, 2), "MSM_ERR_INVALID.*the messages hold a non-finite value") for m in unread_messages()]
     return ok, [((U, tc, triplets, bad_label, None, 0, 2), "MSM_ERR_INVALID.*msm_mcmc_optimise: label of node 7 out of range"),
                 ((U, tc, bad_node, start, None, 0, 2), "MSM_ERR_INVALID.*msm_mcmc_optimise: triplet node out of range"),
                 ((U, tc, twice, start, None, 0, 2), "MSM_ERR_INVALID.*triplet 4 names a node twice"),
@@ -162,7 +175,7 @@ def refusal_cases():
                 ((U, tc, triplets, start, None, 0, -1), "MSM_ERR_INVALID.*-1 polish passes"),
                 ((U, tc, triplets, start, None, 1, 1025), "MSM_ERR_INVALID.*1025 polish passes"),
                 ((np.zeros((1025, 3)), np.zeros((0, 1, 1, 1)), np.zeros((0, 3), dtype=np.int32), np.zeros(3, dtype=np.int32), None, 0, 2),
-                 "MSM_ERR_CAPACITY.*1025 labels")]
+                 "MSM_ERR_CAPACITY.*1025 labels")] + plain
 
 
 CASES = {

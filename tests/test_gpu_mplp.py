@@ -149,6 +149,18 @@ def test_refusals_are_the_host_literals(ctx):
     _both(ctx, (U, tc, triplets, start), 2)    # and the context is as good as before
 
 
+def test_every_non_finite_entry_is_refused_by_its_table(ctx):
+    """the device's one classification pass read the plain way: the host literal's refusals (test_mplp_cpu.py), and no sweep runs"""
+    ok = ML.ico_case(0, 5, 31)
+    _both(ctx, ok, 2)
+    before = api.mplp_gpu_stats(ctx)
+    for args, pattern in ML.non_finite_refusals():
+        with pytest.raises(M.MsmError, match=pattern):
+            api.mplp_optimise_gpu(ctx, *args, sweeps=3)
+    assert api.mplp_gpu_stats(ctx) == before
+    _both(ctx, ok, 2)
+
+
 @pytest.mark.parametrize("kind", ["univariate", "ho_univariate"])
 def test_cost_function_tables_stay_on_the_device(ctx, kind):
     """msm_cost_mplp_optimise = computeUnaryCosts + computeTripletCosts + the host literal; twice in a row"""

@@ -113,6 +113,34 @@ def test_refusals_are_the_host_literals(ctx):
     _both(ctx, ok, sweeps=2)  # and the context is as good as before
 
 
+def test_the_last_entry_of_the_table_is_counted(ctx):
+    """+inf in the last element of the last triplet and nothing else: the end of the classification pass's walk over the table"""
+    case = ML.last_entry_forbidden()
+    _both(ctx, case, sweeps=3, polish=2, what="last entry")
+    counts = np.full(4, -1, dtype=np.int64)
+    api.mplp_optimise_gpu(ctx, *case, sweeps=3, forbid=True, counts=counts)
+    assert counts.tolist() == [0, 0, 1, 0]
+
+
+def test_the_rounding_keeps_the_sweeps_counts(ctx):
+    """the collapsed-triangle table: after mplp_round(then_polish=True) on a cost function that has made no other call, mplp_forbidden() is what it is
+    after mplp_optimise on the same tables -- the sweeps' reading reaches the rounding and the polish and comes back from them"""
+    swept, keep_swept = SC.product_cost(ctx)
+    rounded, keep_rounded = SC.product_cost(ctx)
+    start = np.zeros(swept.N, dtype=np.int32)
+    for cf in (swept, rounded):
+        cf.set_mplp_forbid()
+        assert cf.mplp_forbidden().tolist() == [0, 0, 0, 0]
+    swept.mplp_optimise(start, sweeps=3)
+    rounded.mplp_round(start, sweeps=3, polish=2, then_polish=True)
+    tc = np.array(swept.computeTripletCosts())
+    want = [0, int(np.isnan(tc).sum()), int((tc == INF).sum()), 0]
+    assert want[1] >= 1 and want[2] >= 1
+    assert swept.mplp_forbidden().tolist() == rounded.mplp_forbidden().tolist() == want
+    swept.close()
+    rounded.close()
+
+
 def test_the_real_table(ctx):
     """the strain regulariser's own table on the regular ico1 control grid under unrescaled labels, the moving data warped so that the unary table is
     not flat: 10 sweeps and the rounding with polish 8 over the cost function's device tables, over uploaded tables and on the host -- the same bits;

@@ -123,6 +123,14 @@ def test_refusals_are_the_host_literals(ctx):
     _both(ctx, ok[:4])
 
 
+def test_mode_1_reads_no_messages(ctx):
+    """the messages mode 0 refuses change nothing in mode 1"""
+    ok, _ = RL.refusal_cases()
+    want = api.mplp_round(*ok[:4], mode=1, polish=2)
+    for m in RL.unread_messages():
+        RL.same(api.mplp_round_gpu(ctx, *ok[:4], messages=m, mode=1, polish=2), want)
+
+
 @pytest.mark.parametrize("kind", ["univariate", "ho_univariate"])
 def test_cost_function_tables_and_messages_stay_on_the_device(ctx, kind):
     """msm_cost_mplp_round = msm_cost_mplp_optimise(messages) + msm_mplp_round(mode 0) with that winner handed in; msm_cost_mplp_polish = mode 1"""

@@ -172,6 +172,15 @@ def test_refusals_leave_the_outputs_untouched():
     assert st == 0 and not untouched
 
 
+def test_every_non_finite_entry_is_refused_by_its_table():
+    """-inf, +inf and NaN in the triplet table, -inf in the unary table, and the unary table named first where both hold one"""
+    for args, pattern in ML.non_finite_refusals():
+        st, untouched = _raw(*args, 3)
+        assert st != 0 and untouched, pattern
+        with pytest.raises(M.MsmError, match=pattern):
+            api.mplp_optimise(*args, sweeps=3)
+
+
 def test_host_literal_under_the_sanitizers(tmp_path):
     """tests/cpp/mplp_host_check.cpp: the incidence lists and the literal as a program of their own (no HIP, no Python), built with
     -fsanitize=address,undefined and run directly"""

@@ -187,6 +187,19 @@ def test_refusals_leave_the_outputs_untouched():
         api.mplp_round(*ok, mode=1, polish=2)
 
 
+def test_the_last_entry_of_the_table_is_counted():
+    U, tc, triplets, start = case = ML.last_entry_forbidden()
+    assert api.mplp_classify(U, tc).tolist() == [0, 0, 1, 0]
+    counts = np.full(4, -1, dtype=np.int64)
+    got = api.mplp_optimise(*case, sweeps=3, bounds=True, messages=True, forbid=True, counts=counts)
+    assert counts.tolist() == [0, 0, 1, 0]
+    ML.same(got, FL.mplp(*case, 3))
+    for mode in (0, 1):
+        counts[:] = -1
+        api.mplp_round(*case, messages=got.messages, mode=mode, polish=2, forbid=True, counts=counts)
+        assert counts.tolist() == [0, 0, 1, 0]
+
+
 def test_host_literal_under_the_sanitizers(tmp_path):
     """tests/cpp/mplp_forbid_host_check.cpp: the literal with forbid set as a program of its own (no HIP, no Python), built with
     -fsanitize=address,undefined and run directly"""

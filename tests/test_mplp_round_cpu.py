@@ -162,6 +162,16 @@ def test_refusals_leave_the_outputs_untouched():
         api.mplp_colouring(cases[1][0][2], 12)
 
 
+def test_mode_1_reads_no_messages():
+    """the messages mode 0 refuses change nothing in mode 1"""
+    ok, _ = RL.refusal_cases()
+    want = api.mplp_round(*ok[:4], mode=1, polish=2)
+    for m in RL.unread_messages():
+        st, untouched = _raw(*ok[:4], m, 1, 2)
+        assert st == 0 and not untouched
+        RL.same(api.mplp_round(*ok[:4], messages=m, mode=1, polish=2), want)
+
+
 def test_host_literal_under_the_sanitizers(tmp_path):
     """tests/cpp/mplp_round_host_check.cpp: the colouring and the rounding's literal as a program of their own (no HIP, no Python), built with
     -fsanitize=address,undefined and run directly"""
