@@ -267,12 +267,7 @@ int ensure_unary_table(msm_cost *c) {
     u.fix_off = c->d_fix_off.p;
     u.redo_list = c->d_queues.p;
     u.route = &c->route_unary;
-    if (c->timing) {
-        u.ev_start = c->ev0[c->ev_next];
-        u.ev_stop = c->ev1[c->ev_next];
-        c->ev_next = (c->ev_next + 1) % (int)c->ev0.size();
-        c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
-    }
+    next_timing_slot(c, u.ev_start, u.ev_stop);
     switch (c->p.kind) {
         case MSM_COST_UNIVARIATE: st = launch_unary_univariate(ctx, u); break;
         case MSM_COST_MULTIVARIATE:
@@ -730,6 +725,6 @@ int msm_cost_counters(msm_cost *c, int64_t counters[4]) {
     return MSM_OK;
 }
 
-// ---- clique costs: implemented in cost_cliques.cpp ----
+// ---- clique costs: implemented in cost_cliques.cpp, the label step in label_step.cpp ----
 
 }  // extern "C"

@@ -1,50 +1,15 @@
 // cost_cliques.cpp -- C ABI of the pairwise / triplet clique costs and of evaluateTotalCostSum
-// (include/msmhip.h).  Kernels: clique_kernels.hip.
+// (include/msmhip.h), except the label step (label_step.cpp).  Kernels: clique_kernels.hip.
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 
 #include "cost_internal.hpp"
+#include "label_step.hpp"
 #include "mcmc.hpp"
 #include "mplp.hpp"
 
 using namespace msm;
 
 namespace msm {
-// A label step queued by msm_cost_triplet_octets_prefetch that nobody took: wait for its kernel and discard what it may have raised (its evaluations
-// were never asked for).  Called by every entry point of a cost function except the msm_cost_triplet_octets call that matches the prefetch.
-int drop_pending_move(msm_cost *c) {
-    if (!c->pending.valid) return MSM_OK;
-    c->pending.valid = false;
-    ++c->prefetch_drops;
-    msm_ctx *ctx = c->ctx;
-    if (ctx->pending_cost == c) ctx->pending_cost = nullptr;
-    MSM_TRY(ctx_sync(ctx));
-    volatile int *flags = ctx->h_flag;
-    if (flags) {
-        flags[1] = 0;
-        if (flags[0] != 0) {
-            flags[0] = 0;
-            (void)check_status(ctx, "a dropped prefetch");  // clears the device status word
-        }
-    }
-    return MSM_OK;
-}
-
-// The same from the context's side: whichever cost function holds the context's queued step.  Every entry point that synchronises the stream and reads the
-// status word or the mapped flags calls this first (or drop_pending_move on its own object) -- a status raised by a speculative kernel must not be reported
-// against another call, a tail request in flags[1] not be consumed by another cost function's move.
-int drop_ctx_pending(msm_ctx *ctx) {
-    msm_cost *c = ctx->pending_cost;
-    if (!c) return MSM_OK;
-    ctx->pending_cost = nullptr;
-    return drop_pending_move(c);
-}
-
-}  // namespace msm
-
-namespace {
 
 // everything the clique kernels read; uploads the control grid's connectivity on first use
 int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a) {
@@ -164,78 +129,12 @@ int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a)
     return MSM_OK;
 }
 
-// ---- fused fusion move of the HO classes (move_kernels.hip) ----
-// bin slots and control triangles per workgroup (at most 64 and 8: the kernel's LDS holds 64 proposed triangles)
-constexpr int kMoveSlots = 64, kMoveTriangles = 8;
+}  // namespace msm
 
-bool fused_move_applies(const msm_cost *c, const CliqueArgs &a) {
-    return cost_is_ho(c) && a.ho_vals && a.tree.simple && a.tree.ray_G > 0 && a.rmode != 4 && a.rmode != 5 && c->pmax <= 128 && a.T > 0;
-}
-
-// per get_source_data(): the workgroups' runs of control triangles and the label-independent part of every bin point
-int ensure_move(msm_cost *c, const CliqueArgs &a) {
-    if (c->move_valid) return MSM_OK;
-    msm_ctx *ctx = c->ctx;
-    const int T = a.T;
-    std::vector<int4> blk;
-    // with many features per sample (the eight-lanes-per-sample passes of k_ho_move<., 2>) smaller workgroups do better: 88 against
-    // 95 us at D = 32 with 48 slots / 6 triangles; with one feature the two shapes are level in the kernel and the larger is cheaper to launch
-    const bool wide = a.kind == MSM_COST_HO_MULTIVARIATE && a.D >= 12;
-    int max_slots = wide ? 48 : kMoveSlots, max_tris = wide ? 6 : kMoveTriangles;
-    // A workgroup's time is a chain (proposed triangles, sampling rounds, similarity passes, last phase) whose length grows with the
-    // triangles it holds, and the whole grid is resident at once up to ~1000 workgroups: on the coarser control grids of a registration's
-    // first levels fewer triangles per workgroup shorten every chain at no cost (D = 32: 55 -> 41 us at ico3, 55 -> 34 us at ico2; the
-    // ico4 grid keeps 6 / 8).  The smallest run of triangles that still fits the grid into one residency round:
-    const int most = max_tris;
-    for (int t : {1, 2, 4, 6, 8})
-        if ((T + most - 1) / most <= 512 && t <= most && (T + t - 1) / t <= 1024) {  // only when the usual run leaves half the GPU empty
-            max_tris = t;
-            max_slots = 8 * t;
-            break;
-        }
-    int slots = 0, nt = 0, cap = max_slots, first = 0, most_tris = 0;
-    auto close = [&](int t_end) {
-        most_tris = std::max(most_tris, nt);
-        if (nt > 0) blk.push_back(make_int4(first, nt, c->pptr[first], c->pptr[t_end] - c->pptr[first]));
-        first = t_end;
-        slots = nt = 0;
-    };
-    for (int t = 0; t < T; ++t) {
-        const int n = c->pptr[t + 1] - c->pptr[t];
-        if (nt > 0 && (slots + n > max_slots || nt == max_tris)) close(t);
-        slots += n;
-        ++nt;
-        cap = std::max(cap, slots);
-    }
-    close(T);
-    const size_t ns = std::max<size_t>(c->pidx.size(), 1);
-    MSM_TRY(c->d_blk.upload(blk.data(), blk.size(), ctx));
-    MSM_HIP(c->d_tri_frame.ensure(5 * (size_t)T));
-    MSM_HIP(c->d_tri_stat.ensure(3 * (size_t)T));
-    MSM_HIP(c->d_slot_wda.ensure(ns));
-    MSM_HIP(c->d_slot_tri.ensure(ns));
-    MSM_HIP(c->d_slot_w.ensure(3 * ns));
-    MSM_HIP(c->d_slot_sf.ensure(ns));
-    if (a.cfw) MSM_HIP(c->d_slot_cw.ensure(ns));
-    MSM_HIP(c->d_defer_list.ensure((size_t)8 * T));
-    if (!c->d_defer_cnt.p) MSM_HIP(c->d_defer_cnt.zero(2, ctx->stream));
-    int st = launch_move_prepare(ctx, a, (int)c->pidx.size(), c->d_slot_tri.p, c->d_slot_w.p, c->d_slot_sf.p, a.cfw ? c->d_slot_cw.p : nullptr, c->d_slot_wda.p,
-                                 c->d_tri_frame.p, c->d_tri_stat.p);
-    if (st) return st;
-    MSM_TRY(ctx_sync(ctx));  // blk is a local
-    c->move_nblk = (int)blk.size();
-    c->move_cap = cap;
-    c->move_maxtri = most_tris;
-    c->move_valid = true;
-    return MSM_OK;
-}
-
-int upload_ints(msm_ctx *ctx, DevBuf<int> &buf, const int32_t *host, size_t n) {
+static int upload_ints(msm_ctx *ctx, DevBuf<int> &buf, const int32_t *host, size_t n) {
     MSM_TRY(buf.upload(host, n, ctx));
     return MSM_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -300,273 +199,6 @@ int msm_cost_triplet_batch(msm_cost *c, const int32_t *triplet, const int32_t *l
     MSM_TRY(dout.download(out, n, ctx));
     c->counters[2] += n;
     return check_status(ctx, "computeTripletCost");
-}
-
-// The fused fusion move of the triclique classes (move_kernels.hip) for one labeling: all eight combinations of every control triangle
-// (E: 8 x T, a label step of Fusion) or, single, combination 000 only (E: T values -- the triplet part of evaluateTotalCostSum,
-// M/DiscreteCostFunction.cpp:55-77, which used to go through the general on-demand kernel at 143 us per call at ico4 / 32 features).
-static int fused_move_finish(msm_cost *c, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *lab, bool staged_copy, bool direct, void *pin, size_t in_pad,
-                             size_t out_bytes, double *out_dev, double *E);
-
-// prefetch != nullptr: queue the move and return without waiting (requires the fast form of the call: labeling in the kernel arguments, costs written into
-// the caller's mapped array); *prefetch tells whether it was queued
-static int fused_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling, int32_t label, double *E, bool single, bool *prefetch = nullptr) {
-    msm_ctx *ctx = c->ctx;
-    int st;
-    if (prefetch) *prefetch = false;
-    const size_t in_bytes = sizeof(int32_t) * (size_t)a.N, out_bytes = sizeof(double) * (single ? 1 : 8) * (size_t)a.T, in_pad = (in_bytes + 255) & ~(size_t)255;
-    // The call of the optimisers' inner loop (once per label step).  Two launches and one synchronisation: the labeling
-    // rides in the kernel arguments, the costs are written into mapped pinned memory (the caller's own array when it
-    // came from msm_host_alloc), a raised status shows up in a mapped flag.
-    st = ensure_move(c, a);
-    if (st) return st;
-    st = ctx_flag(ctx);
-    if (st) return st;
-    const bool packed = a.N <= 4 * kMoveLabelWords && a.L <= 256;
-    MoveLabels lab;
-    if (packed) std::memset(lab.w, 0, sizeof(uint32_t) * (size_t)((a.N + 3) / 4));
-    for (int i = 0; i < a.N; ++i) {
-        if (labeling[i] < 0 || labeling[i] >= a.L) return fail(MSM_ERR_INVALID, "labeling[%d] out of range", i);
-        if (packed) lab.w[i >> 2] |= (uint32_t)labeling[i] << ((i & 3) * 8);
-    }
-    void *pin = nullptr;
-    double *out_dev = (double *)ctx_mapped(ctx, E, out_bytes);
-    const bool direct = out_dev != nullptr;
-    if (prefetch && (!direct || !packed || single)) return MSM_OK;  // not the fast form: the hint is ignored, the call itself will do everything
-    if (!direct || !packed) {
-        st = ctx_io_pinned(ctx, in_pad + out_bytes, &pin);
-        if (st) return st;
-    }
-    bool staged_copy = false;  // the costs come back with a copy command (the pinned block could not be mapped)
-    if (!direct) {
-        if (ctx->io_dev) {
-            out_dev = (double *)((char *)ctx->io_dev + in_pad);
-        } else {
-            MSM_HIP(c->d_clique_out.ensure((size_t)8 * a.T));  // (also large enough for the T values of a single-combination call)
-            out_dev = c->d_clique_out.p;
-            staged_copy = true;
-        }
-    }
-    if (!packed) {
-        std::memcpy(pin, labeling, in_bytes);
-        MSM_HIP(c->d_labeling.ensure(a.N));
-        MSM_HIP(hipMemcpyAsync(c->d_labeling.p, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    MoveArgs m;
-    m.slot_tri = c->d_slot_tri.p;
-    m.slot_w = c->d_slot_w.p;
-    m.slot_sf = c->d_slot_sf.p;
-    m.slot_cw = a.cfw ? c->d_slot_cw.p : nullptr;
-    m.slot_wda = c->d_slot_wda.p;
-    m.tri_frame = c->d_tri_frame.p;
-    m.tri_stat = c->d_tri_stat.p;
-    m.blk = c->d_blk.p;
-    m.nblk = c->move_nblk;
-    m.cap = c->move_cap;
-    m.labeling = packed ? nullptr : c->d_labeling.p;
-    m.label = label;
-    m.vals = c->d_ho_vals.p;
-    m.defer_list = c->d_defer_list.p;
-    m.defer_cnt = c->d_defer_cnt.p;
-    m.parity = c->move_parity;
-    c->move_parity ^= 1;
-    m.out = out_dev;
-    m.host_flags = ctx->d_flag_map;
-    m.single = single ? 1 : 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        e0 = c->ev0[c->ev_next];
-        e1 = c->ev1[c->ev_next];
-        c->ev_next = (c->ev_next + 1) % (int)c->ev0.size();
-        c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
-    }
-    st = launch_move(ctx, a, m, packed ? &lab : nullptr, e0, e1, &c->route_move);
-    if (st) return st;
-    if (staged_copy) MSM_HIP(hipMemcpyAsync((char *)pin + in_pad, out_dev, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    c->counters[2] += (int64_t)(single ? 1 : 8) * a.T;
-    if (prefetch) {  // queued: msm_cost_triplet_octets(labeling, label, E) will wait for it
-        c->pending.kind = 1;
-        c->pending.label = label;
-        c->pending.E = E;
-        c->pending.epoch = ctx->epoch;
-        ctx->pending_cost = c;
-        c->pending.labeling.assign(labeling, labeling + a.N);
-        c->pending.a = a;
-        c->pending.m = m;
-        c->pending.lab = lab;
-        c->pending.valid = true;
-        *prefetch = true;
-        return MSM_OK;
-    }
-    MSM_TRY(ctx_sync(ctx));
-    return fused_move_finish(c, a, m, packed ? &lab : nullptr, staged_copy, direct, pin, in_pad, out_bytes, out_dev, E);
-}
-
-// after the move's kernel has completed (the stream is synchronised): the tail kernel when the main one asked for it, a raised status, the staged copy
-static int fused_move_finish(msm_cost *c, const CliqueArgs &a, const MoveArgs &m, const MoveLabels *lab, bool staged_copy, bool direct, void *pin, size_t in_pad,
-                             size_t out_bytes, double *out_dev, double *E) {
-    msm_ctx *ctx = c->ctx;
-    int st;
-    volatile int *flags = ctx->h_flag;
-    c->move_deferred = 0;
-    if (flags[1] != 0) {  // rare: some evaluations need the complete search (sibling leaves, nearest vertex)
-        flags[1] = 0;
-        st = launch_move_tail(ctx, a, m, lab);
-        if (st) return st;
-        if (staged_copy) MSM_HIP(hipMemcpyAsync((char *)pin + in_pad, out_dev, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        MSM_TRY(ctx_sync(ctx));
-        c->move_tails++;
-        unsigned listed = 0;  // how many evaluations the tail kernel took (msm_cost_routes): this move's counter stays until the next move but one clears it
-        MSM_TRY(stage_d2h(ctx, &listed, m.defer_cnt + m.parity, sizeof listed));
-        MSM_TRY(ctx_sync(ctx));
-        c->move_deferred = (int32_t)std::min<unsigned>(listed, (unsigned)INT32_MAX);
-    }
-    st = MSM_OK;
-    if (flags[0] != 0) {
-        flags[0] = 0;
-        st = check_status(ctx, "computeTripletCost");
-    }
-    if (!direct) std::memcpy(E, (char *)pin + in_pad, out_bytes);
-    return st;
-}
-
-// the strain-only label step in its fast form (labeling in the kernel arguments, costs into mapped memory): launch, and unless queued ahead, wait
-static int packed_strain_move(msm_cost *c, const CliqueArgs &a, const int32_t *labeling, int32_t label, double *E, double *out_dev, bool direct, void *pin, size_t in_pad,
-                              size_t out_bytes, bool queue_only) {
-    msm_ctx *ctx = c->ctx;
-    MoveLabels lab;
-    std::memset(lab.w, 0, sizeof(uint32_t) * (size_t)((a.N + 3) / 4));
-    for (int i = 0; i < a.N; ++i) lab.w[i >> 2] |= (uint32_t)labeling[i] << ((i & 3) * 8);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {  // msm_cost_enable_timing: events around this move's kernel, like the triclique move's
-        e0 = c->ev0[c->ev_next];
-        e1 = c->ev1[c->ev_next];
-        c->ev_next = (c->ev_next + 1) % (int)c->ev0.size();
-        c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
-        MSM_HIP(hipEventRecord(e0, ctx->stream));
-    }
-    int st = launch_triplet_octets_packed(ctx, a, lab, label, out_dev, ctx->d_flag_map);
-    if (st) return st;
-    c->route_move = MSM_MOVE_STRAIN;  // that launcher has one kernel
-    if (e1) MSM_HIP(hipEventRecord(e1, ctx->stream));
-    c->counters[2] += (int64_t)8 * a.T;
-    if (queue_only) {
-        c->pending.kind = 2;
-        c->pending.label = label;
-        c->pending.E = E;
-        c->pending.epoch = ctx->epoch;
-        ctx->pending_cost = c;
-        c->pending.labeling.assign(labeling, labeling + a.N);
-        c->pending.valid = true;
-        return MSM_OK;
-    }
-    MSM_TRY(ctx_sync(ctx));
-    volatile int *flags = ctx->h_flag;
-    st = MSM_OK;
-    if (flags[0] != 0) {
-        flags[0] = 0;
-        st = check_status(ctx, "computeTripletCost");
-    }
-    if (!direct) std::memcpy(E, static_cast<char *>(pin) + in_pad, out_bytes);
-    return st;
-}
-
-// the msm_cost_triplet_octets call a prefetch was queued for: wait for the kernel, then what follows a move's kernel in the synchronous call
-static int take_pending_move(msm_cost *c, double *E) {
-    msm_ctx *ctx = c->ctx;
-    msm_cost::PendingMove &p = c->pending;
-    p.valid = false;
-    if (ctx->pending_cost == c) ctx->pending_cost = nullptr;
-    ++c->prefetch_hits;
-    MSM_TRY(ctx_sync(ctx));
-    if (p.kind == 1) return fused_move_finish(c, p.a, p.m, &p.lab, false, true, nullptr, 0, 0, nullptr, E);
-    volatile int *flags = ctx->h_flag;
-    if (flags[0] != 0) {
-        flags[0] = 0;
-        return check_status(ctx, "computeTripletCost");
-    }
-    return MSM_OK;
-}
-
-static int triplet_octets_impl(msm_cost *c, const int32_t *labeling, int32_t label, double *E, bool *prefetch);
-
-int msm_cost_triplet_octets(msm_cost *c, const int32_t *labeling, int32_t label, double *E) {
-    if (!c || !labeling || !E) return fail(MSM_ERR_INVALID, "msm_cost_triplet_octets: null argument");
-    if (c->pending.valid && c->pending.label == label && c->pending.E == E && c->pending.epoch == c->ctx->epoch && c->ctx->pending_cost == c && c->cpgrid && (int)c->pending.labeling.size() == c->cpgrid->V &&
-        std::memcmp(c->pending.labeling.data(), labeling, sizeof(int32_t) * c->pending.labeling.size()) == 0)
-        return take_pending_move(c, E);  // queued ahead by msm_cost_triplet_octets_prefetch: the kernel ran while the host solved
-    return triplet_octets_impl(c, labeling, label, E, nullptr);
-}
-
-// A hint: queue the label step (labeling, label) into E without waiting -- the optimiser's host-side solve of the step before runs meanwhile, and most
-// steps of a converging level leave the labeling as it was (three of four in the MSMAll schedule).  Honoured when E lies in msm_host_alloc memory and the
-// step takes the one-kernel form (triclique fused move or strain-only packed move); silently ignored otherwise.  The results do not depend on it.
-int msm_cost_triplet_octets_prefetch(msm_cost *c, const int32_t *labeling, int32_t label, double *E) {
-    if (!c || !labeling || !E) return fail(MSM_ERR_INVALID, "msm_cost_triplet_octets_prefetch: null argument");
-    bool queued = false;
-    return triplet_octets_impl(c, labeling, label, E, &queued);
-}
-
-int msm_cost_prefetch_stats(msm_cost *c, int64_t *taken, int64_t *dropped) {
-    if (!c) return fail(MSM_ERR_INVALID, "null cost");
-    if (taken) *taken = c->prefetch_hits;
-    if (dropped) *dropped = c->prefetch_drops;
-    return MSM_OK;
-}
-
-static int triplet_octets_impl(msm_cost *c, const int32_t *labeling, int32_t label, double *E, bool *prefetch) {
-    CliqueArgs a;
-    int st = clique_args(c, true, false, a);  // (drops a queued step nobody took)
-    if (st) return st;
-    if (label < 0 || label >= a.L) return fail(MSM_ERR_INVALID, "label %d out of range", label);
-    msm_ctx *ctx = c->ctx;
-    const size_t in_bytes = sizeof(int32_t) * (size_t)a.N, out_bytes = sizeof(double) * 8 * (size_t)a.T, in_pad = (in_bytes + 255) & ~(size_t)255;
-    if (fused_move_applies(c, a)) return fused_move(c, a, labeling, label, E, false, prefetch);  // the call of the optimisers' inner loop (once per label step)
-    for (int i = 0; i < a.N; ++i)
-        if (labeling[i] < 0 || labeling[i] >= a.L) return fail(MSM_ERR_INVALID, "labeling[%d] out of range", i);
-    if (prefetch && !ctx_mapped(ctx, E, out_bytes)) return MSM_OK;  // the hint needs the caller's mapped array
-    // labeling and energies travel through pinned memory (pageable copies of these sizes cost more than the kernels)
-    void *pin = nullptr;
-    st = ctx_io_pinned(ctx, in_pad + out_bytes, &pin);
-    if (st) return st;
-    const char *octets_env = std::getenv("MSMHIP_OCTETS");  // read per call: the tests run both ways in one process
-    const bool octets_by_copy = octets_env && std::strcmp(octets_env, "copy") == 0;
-    if (!cost_is_ho(c) && a.N <= 4 * kMoveLabelWords && a.L <= 256 && !octets_by_copy && ctx_flag(ctx) == MSM_OK) {
-        // The strain-only label step (--regoption=3 without --triclique: BASELINE config 2) like the triclique move: the labeling rides in
-        // the kernel arguments, the costs land in mapped pinned memory -- the caller's array when it came from msm_host_alloc --, a raised
-        // status in the mapped flag: one launch + one synchronisation instead of two copy commands around the kernel and a status read-back
-        // (57 -> 25 us per call at ico4; MSMHIP_OCTETS=copy: the old way)
-        double *out_dev = static_cast<double *>(ctx_mapped(ctx, E, out_bytes));
-        const bool direct = out_dev != nullptr;
-        if (!direct && ctx->io_dev) out_dev = reinterpret_cast<double *>(static_cast<char *>(ctx->io_dev) + in_pad);
-        if (out_dev) {
-            st = packed_strain_move(c, a, labeling, label, E, out_dev, direct, pin, in_pad, out_bytes, prefetch != nullptr && direct);
-            if (!st && prefetch && direct) *prefetch = true;
-            if (prefetch && !direct) return MSM_OK;
-            return st;
-        }
-    }
-    if (prefetch) return MSM_OK;  // the general path is not queued ahead
-    std::memcpy(pin, labeling, in_bytes);
-    MSM_HIP(c->d_labeling.ensure(a.N));
-    MSM_HIP(hipMemcpyAsync(c->d_labeling.p, pin, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    MSM_HIP(c->d_clique_out.ensure((size_t)8 * a.T));
-    hipEvent_t g0 = nullptr, g1 = nullptr;
-    if (c->timing) {  // msm_cost_enable_timing: events around this move's kernels (the on-demand kernels: anatomical strain, large bins, general targets)
-        g0 = c->ev0[c->ev_next];
-        g1 = c->ev1[c->ev_next];
-        c->ev_next = (c->ev_next + 1) % (int)c->ev0.size();
-        c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
-        MSM_HIP(hipEventRecord(g0, ctx->stream));
-    }
-    st = launch_triplet_octets(ctx, a, c->d_labeling.p, label, c->d_clique_out.p, &c->route_move);
-    if (st) return st;
-    if (g1) MSM_HIP(hipEventRecord(g1, ctx->stream));
-    MSM_HIP(hipMemcpyAsync((char *)pin + in_pad, c->d_clique_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    c->counters[2] += (int64_t)8 * a.T;
-    st = check_status(ctx, "computeTripletCost");  // synchronises
-    std::memcpy(E, (char *)pin + in_pad, out_bytes);
-    return st;
 }
 
 int msm_cost_pairwise_batch(msm_cost *c, const int32_t *pair, const int32_t *la, const int32_t *lb, int32_t n, double *out) {
@@ -768,18 +400,11 @@ int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double p
     }
     bool triplets_done = false;
     if (T > 0 && cost_is_ho(c)) {
-        // combination 000 of a fusion move IS computeTripletCost(t, labeling[a], labeling[b], labeling[c]): the fused move kernel with one
-        // combination per control triangle instead of the general on-demand kernel (143 -> about 20 us at ico4 / 32 features)
-        CliqueArgs a;
-        int st = clique_args(c, true, false, a);
+        std::vector<double> vals(T);
+        int st = fused_single_costs(c, labeling, vals.data(), &triplets_done);  // the fused move with one combination per control triangle, where it applies
         if (st) return st;
-        if (fused_move_applies(c, a)) {
-            std::vector<double> vals(T);
-            st = fused_move(c, a, labeling, 0, vals.data(), true);
-            if (st) return st;
+        if (triplets_done)
             for (int t = 0; t < T; ++t) tc += vals[t];  // serial, in triplet order (:70-75)
-            triplets_done = true;
-        }
     }
     if (T > 0 && !triplets_done) {
         std::vector<int32_t> id(T), la(T), lb(T), lc(T);

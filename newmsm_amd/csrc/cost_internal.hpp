@@ -1,10 +1,12 @@
-// cost_internal.hpp -- the msm_cost handle shared by cost.cpp (unary) and cost_cliques.cpp (pairwise / triplet).
+// cost_internal.hpp -- the msm_cost handle shared by cost.cpp (unary), cost_cliques.cpp (pairwise / triplet) and label_step.cpp (the label step).
 #pragma once
 
+#include <algorithm>
 #include <vector>
 
 #include "devbuf.hpp"
 #include "kernels.hpp"
+#include "label_step.hpp"
 #include "unary.hpp"
 
 using msm::DevBuf;
@@ -58,6 +60,7 @@ struct msm_cost {
         msm::CliqueArgs a;
         msm::MoveArgs m;
         msm::MoveLabels lab;
+        msm::StepDelivery d;  // where its costs land
     } pending;
     int64_t prefetch_hits = 0, prefetch_drops = 0;
     DevBuf<unsigned> d_defer_list, d_defer_cnt;
@@ -120,7 +123,18 @@ struct msm_cost {
 namespace msm {
 // (re)computes the per (control point, label) rotation matrices and moved control points if stale
 int ensure_label_rotations(msm_cost *c);
-int drop_pending_move(msm_cost *c);  // cost_cliques.cpp: waits for and discards a label step queued by msm_cost_triplet_octets_prefetch that nobody took
+int drop_pending_move(msm_cost *c);  // label_step.cpp: waits for and discards a label step queued by msm_cost_triplet_octets_prefetch that nobody took
+// cost_cliques.cpp: everything the clique kernels read (resolves a queued label step first; uploads the control grid's connectivity on first use)
+int clique_args(msm_cost *c, bool need_triplets, bool need_pairs, CliqueArgs &a);
 int ensure_vertex_major(msm_cost *c);  // d_sfeat_vm / d_cfw_vm
 inline bool cost_is_ho(const msm_cost *c) { return c->p.kind == MSM_COST_HO_UNIVARIATE || c->p.kind == MSM_COST_HO_MULTIVARIATE; }
+// msm_cost_enable_timing: the next pair of the timing events' ring for a launch to record around its kernel(s); false (e0, e1 untouched) when timing is off
+inline bool next_timing_slot(msm_cost *c, hipEvent_t &e0, hipEvent_t &e1) {
+    if (!c->timing) return false;
+    e0 = c->ev0[c->ev_next];
+    e1 = c->ev1[c->ev_next];
+    c->ev_next = (c->ev_next + 1) % (int)c->ev0.size();
+    c->ev_count = std::min(c->ev_count + 1, (int)c->ev0.size());
+    return true;
+}
 }  // namespace msm

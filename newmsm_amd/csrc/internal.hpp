@@ -172,7 +172,7 @@ struct msm_ctx {
     hipEvent_t wait_ev = nullptr;  // msm_ctx_wait_stream
     // A label step queued ahead (msm_cost_triplet_octets_prefetch) shares the stream, the status word and the mapped flags with every other call on the context:
     // the cost function that holds one (at most one per context), resolved -- taken by its matching call, or waited for and discarded -- before any other
-    // entry point synchronises the stream or reads the flags (cost_cliques.cpp: drop_ctx_pending)
+    // entry point synchronises the stream or reads the flags (label_step.cpp: drop_ctx_pending)
     struct msm_cost *pending_cost = nullptr;
     // bumped by everything a queued label step's inputs or destination depend on and that the cost function cannot see: a mesh's coordinates or features
     // changed, a pinned block released (a new block may get the old one's address).  A queued step is only taken when the epoch is the one it was queued under.
@@ -304,7 +304,7 @@ int ctx_io_pinned(msm_ctx *ctx, size_t bytes, void **out);  // grow-only pinned 
 // device address of [p, p + bytes) when it lies in a msm_host_alloc block of this context, else nullptr
 void *ctx_mapped(msm_ctx *ctx, const void *p, size_t bytes);
 int ctx_flag(msm_ctx *ctx);  // makes ctx->h_flag / d_flag_map available
-int drop_ctx_pending(msm_ctx *ctx);  // cost_cliques.cpp: the label step queued ahead on this context, if any, is waited for and discarded (see msm_ctx::pending_cost)
+int drop_ctx_pending(msm_ctx *ctx);  // label_step.cpp: the label step queued ahead on this context, if any, is waited for and discarded (see msm_ctx::pending_cost)
 // host -> device on the context's stream: from where it lies when src is pinned memory of this context (msm_host_alloc / msm_host_register; complete on
 // return, the caller may write the array again), through the staging blocks otherwise (src consumed on return, the copy queued; nothing waits)
 int upload_staged(msm_ctx *ctx, void *dst, const void *src, size_t bytes);
