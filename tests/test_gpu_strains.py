@@ -11,33 +11,11 @@ import newmsm_amd as M
 import strains_literal as SL
 from newmsm_amd import config, meshio, registration, synthetic
 from oracle import oracle as O
+from tests.strain_shape_cases import anatomy_case, compare
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ILL = 1e6  # a 5-column block above this condition number is compared at a tolerance scaled by it
-
-
-def anatomy_case(order, seed=0):
-    xyz, tri = O.icosphere(order)
-    orig = synthetic.anatomy(xyz, seed=seed)
-    final = synthetic.anatomy(synthetic.known_warp(xyz, seed=seed + 5, rot_deg=2.0, amp=1.5), seed=seed)
-    return orig, tri, final
-
-
-def compare(ctx, orig, tri, final, max_ill=0.02):
-    """the device against the restatement: neighbourhoods equal, strains to rtol 1e-9 / atol 1e-12 (scaled by the condition number above ILL)"""
-    got, kept, radius = M.calculate_strains(M.Mesh(ctx, orig, tri), final, 2.0, with_neighbourhoods=True)
-    want = SL.calculate_strains(orig, tri, final)
-    assert np.array_equal(kept, want["kept"])
-    assert np.array_equal(radius, want["radius"])
-    cond = want["cond"]
-    ill = cond > ILL
-    assert np.count_nonzero(ill) <= max_ill * len(orig)
-    scale = np.where(ill, cond / ILL, 1.0)
-    err = np.abs(got - want["strains"])
-    assert np.all(err <= 1e-12 * scale + 1e-9 * scale * np.abs(want["strains"])), (err.max(), cond.max())
-    return got, kept, radius, want
 
 
 @pytest.mark.parametrize("order", [4, 5, 6])

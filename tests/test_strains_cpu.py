@@ -9,26 +9,11 @@ import pytest
 
 import newmsm_amd as M
 import strains_literal as SL
-from newmsm_amd import _lib, synthetic
+from newmsm_amd import _lib
 from oracle import oracle as O
+from tests.strain_shape_cases import anatomy_case, assert_same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def anatomy_case(order, seed=0):
-    """a synthetic anatomy on icosphere(order) and the same anatomy after a known warp of the sphere"""
-    xyz, tri = O.icosphere(order)
-    orig = synthetic.anatomy(xyz, seed=seed)
-    final = synthetic.anatomy(synthetic.known_warp(xyz, seed=seed + 5, rot_deg=2.0, amp=1.5), seed=seed)
-    return orig, tri, final
-
-
-def assert_same(a, b, rtol=1e-12, atol=1e-14):
-    assert np.array_equal(a["kept"], b["kept"])
-    assert np.array_equal(a["radius"], b["radius"])
-    for x, y in zip(a["members"], b["members"]):
-        assert np.array_equal(x, y)
-    np.testing.assert_allclose(a["strains"], b["strains"], rtol=rtol, atol=atol)
 
 
 @pytest.mark.parametrize("order", [2, 3])
