@@ -505,6 +505,47 @@ int msm_mplp_round_forbid(const double *unary, const double *tcosts, const int32
 int msm_mplp_round_forbid_gpu(msm_ctx *ctx, const double *unary, const double *tcosts, const int32_t *triplets, int32_t N, int32_t L, int32_t T,
                               const double *messages, int32_t mode, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies,
                               int64_t counts[4]);
+/* MPLP OVER THE PAIR TABLES (an extension): the optimiser above for the pairwise model of a --regoption=1 level, whose factors are the
+ * P pairs of msm_cost_set_pairs.  unary: L x N as above; pairs: 2 P nodes, pair p on A = pairs[2p] (slot 0) and B = pairs[2p+1] (slot 1), A not
+ * required to be below B, two pairs may name the same two nodes; paircosts: P x L x L as msm_cost_pairwise_table writes them, theta_p(a, b) at
+ * (p L + b) L + a.  Messages m[p][s][x] are P x 2 x L doubles.  The plain reading only: the forbidden-entry reading above does not apply.
+ * [host] The two colourings 5.20 walks.  pair_colour[p] (P): the smallest colour no pair q < p that shares a node with p holds -- a sweep walks the
+ * colours ascending and a colour's pairs ascending, and pairs of one colour share no node.  node_colour[i] (N): the smallest colour no lower-index node
+ * that shares a pair with i holds (a node in no pair: 0) -- what a polish pass walks.  Every output may be NULL.  Refuses a node out of range and a
+ * pair that names one node twice. */
+int msm_mplp_pairs_colouring(const int32_t *pairs, int32_t N, int32_t P, int32_t *pair_colour, int32_t *pair_classes, int32_t *node_colour,
+                             int32_t *node_classes);
+/* [host] The energy of a labelling over these tables: the unary terms summed over i ascending from 0.0, `+ 0.0`, plus the pair terms
+ * theta_p(x_A, x_B) summed over p ascending from 0.0 (msm_mcmc_energy's shape with the pair terms in the triplet terms' place). */
+int msm_mplp_pairs_energy(const double *unary, const double *paircosts, const int32_t *pairs, int32_t N, int32_t L, int32_t P, const int32_t *labeling,
+                          double *energy);
+/* [host] The serial literal of DESIGN.md 5.20.  Candidates, winner, stop and the optional outputs are msm_mplp_optimise's: labeling (N) is the start
+ * in and the first lowest energy among the start and the decode after every sweep out; *sweeps_run; *energy; *bound (the dual value after the last
+ * sweep); energies / bounds (`sweeps` values, the sweeps a fixed point spares repeat the last; untouched when no sweep ran); messages (P x 2 x L).
+ * sweeps == 0 or P == 0: the labelling stays, *sweeps_run = 0.  Refused before anything is written: a node or a start label out of range and negative
+ * counts (msm_mcmc_optimise's wording where it applies); a pair that names one node twice (MSM_ERR_INVALID); a non-finite entry in either table
+ * (MSM_ERR_INVALID, the message names the table, the unary one first); L > 1024 (MSM_ERR_CAPACITY). */
+int msm_mplp_pairs_optimise(const double *unary, const double *paircosts, const int32_t *pairs, int32_t N, int32_t L, int32_t P, int32_t sweeps,
+                            int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds, double *messages);
+/* msm_mplp_pairs_optimise with the sweeps on the GPU, bit for bit: the tables are uploaded, a sweep is one launch per pair colour (a wavefront per pair
+ * up to 64 labels, a workgroup per pair above), the terms of the energies and bounds are evaluated on the device and summed on the host in the
+ * literal's order, the finiteness check is one device pass.  Everything runs on the context's stream; complete on return. */
+int msm_mplp_pairs_optimise_gpu(msm_ctx *ctx, const double *unary, const double *paircosts, const int32_t *pairs, int32_t N, int32_t L, int32_t P,
+                                int32_t sweeps, int32_t *labeling, int32_t *sweeps_run, double *energy, double *bound, double *energies, double *bounds,
+                                double *messages);
+/* [host] The polish of 5.20: `polish` passes (0 to 1024) of iterated conditional modes over the node colours, every other node held at its label, the
+ * current label kept unless the first argmin is strictly lower; a pass that changes no label ends the run.  Candidate 0 is the labelling handed in,
+ * candidate k the labelling after pass k; labeling receives the first lowest energy.  Optional: *passes_run, *energy, energies (1 + polish values,
+ * the passes a fixed point spares repeat the last).  Refuses what msm_mplp_pairs_optimise refuses. */
+int msm_mplp_pairs_polish(const double *unary, const double *paircosts, const int32_t *pairs, int32_t N, int32_t L, int32_t P, int32_t polish,
+                          int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
+/* msm_mplp_pairs_polish on the GPU, bit for bit: a launch per node colour and pass, a wavefront per node */
+int msm_mplp_pairs_polish_gpu(msm_ctx *ctx, const double *unary, const double *paircosts, const int32_t *pairs, int32_t N, int32_t L, int32_t P,
+                              int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
+/* What the last sweeps and the last polish over pair tables on the context's GPU did: stats[0] ms in the sweeps' kernels (HIP events around every
+ * chunk), [1] pair colours per sweep, [2] sweeps run, [3] the widest colour class, [4] ms in the polish passes, [5] passes run (the sweeps reset [4]
+ * and [5] to 0). */
+int msm_mplp_pairs_gpu_stats(msm_ctx *ctx, double stats[6]);
 /* [host] A STAND-IN for the binary solve of one label step of Fusion::optimize (I/Fusion/Fusion.h:198-229 hands the step to ELC's
  * reduction + FastPD, which are licence-restricted and FSL-bound: not reproduced).  Iterated conditional modes over x in {0,1}^N
  * (0: the node keeps its label, 1: it takes the proposed one) for
@@ -635,6 +676,15 @@ int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t
 int msm_cost_set_mplp_forbid(msm_cost *c, int32_t on);
 /* [host] what the last of those calls counted over the two device tables while the switch was on (msm_mplp_classify's four values) */
 int msm_cost_mplp_forbidden(msm_cost *c, int64_t counts[4]);
+/* MPLP over the pair tables with both tables staying on the device: the unary table and the pair table are filled as
+ * msm_cost_mcmc_optimise fills its two (the pair table by the kernel of msm_cost_pairwise_table, never downloaded), the sweeps run from `labeling`, and
+ * with polish > 0 the sweeps' winner is polished over the same tables.  What msm_cost_unary_table + msm_cost_pairwise_table + msm_mplp_pairs_optimise
+ * (+ msm_mplp_pairs_polish of its result) give, bit for bit: labeling, *sweeps_run, *passes_run (0 without polish), *energy (the final labelling's),
+ * *bound (after the last sweep), energies / bounds (`sweeps` values), polish_energies (1 + polish values, written when polish > 0).  All but labeling
+ * may be NULL.  Needs msm_cost_set_pairs (MSM_ERR_STATE without).  msm_cost_set_mplp_forbid is ignored here: computePairwiseCost returns a finite cost
+ * or the folding value. */
+int msm_cost_mplp_pairs_optimise(msm_cost *c, int32_t sweeps, int32_t polish, int32_t *labeling, int32_t *sweeps_run, int32_t *passes_run, double *energy,
+                                 double *bound, double *energies, double *bounds, double *polish_energies);
 /* evaluateTotalCostSum :55-77: parts = {unary, pairwise, triplet} sums in the reference's serial order */
 int msm_cost_total(msm_cost *c, const int32_t *labeling, double *total, double parts[3]);
 /* Optional HIP-event timing of the sampling kernel (k_unary_rays or k_unary_samples) of each unary-table launch, recorded on the

@@ -581,6 +581,70 @@ inline MplpRound mplp_round_gpu(Context &ctx, const Matrix &unary_costs, const M
                                  &r.passes_run, &r.energy, r.energies.data()));
     return r;
 }
+// MPLP over the pair tables of a --regoption=1 level (msm_mplp_pairs_*): unary_costs L x N, paircosts P x L x L as computePairwiseCosts
+// returns them, pairs 2 P nodes.  The two colourings: colour per pair (what a sweep walks) and per node (what a polish pass walks)
+struct MplpPairsColouring {
+    std::vector<int32_t> pair_colour, node_colour;
+    int32_t pair_classes = 0, node_classes = 0;
+};
+inline MplpPairsColouring mplp_pairs_colouring(const std::vector<int32_t> &pairs, int num_nodes) {
+    MplpPairsColouring c;
+    c.pair_colour.assign(pairs.size() / 2, 0), c.node_colour.assign((size_t)num_nodes, 0);
+    check(msm_mplp_pairs_colouring(pairs.data(), num_nodes, (int32_t)(pairs.size() / 2), c.pair_colour.data(), &c.pair_classes, c.node_colour.data(),
+                                   &c.node_classes));
+    return c;
+}
+inline double mplp_pairs_energy(const Matrix &unary_costs, const Matrix &paircosts, const std::vector<int32_t> &pairs, int num_nodes, int num_labels,
+                                const std::vector<int32_t> &labeling) {
+    double e = 0.0;
+    check(msm_mplp_pairs_energy(unary_costs.data(), paircosts.data(), pairs.data(), num_nodes, num_labels, (int32_t)(pairs.size() / 2), labeling.data(), &e));
+    return e;
+}
+// `sweeps` sweeps from `labeling`, which becomes the best candidate; with_bounds: D after every sweep too (a second pass over the pair table per sweep)
+inline MplpRun mplp_pairs_optimise(const Matrix &unary_costs, const Matrix &paircosts, const std::vector<int32_t> &pairs, int num_nodes, int num_labels,
+                                   int sweeps, std::vector<int32_t> &labeling, bool with_bounds = false) {
+    MplpRun r;
+    r.energies.assign((size_t)sweeps, 0.0);
+    if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
+    check(msm_mplp_pairs_optimise(unary_costs.data(), paircosts.data(), pairs.data(), num_nodes, num_labels, (int32_t)(pairs.size() / 2), sweeps, labeling.data(),
+                                  &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
+    return r;
+}
+// the same with the sweeps on the GPU (msm_mplp_pairs_optimise_gpu), bit for bit
+inline MplpRun mplp_pairs_optimise_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &paircosts, const std::vector<int32_t> &pairs, int num_nodes,
+                                       int num_labels, int sweeps, std::vector<int32_t> &labeling, bool with_bounds = false) {
+    MplpRun r;
+    r.energies.assign((size_t)sweeps, 0.0);
+    if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
+    check(msm_mplp_pairs_optimise_gpu(ctx.handle(), unary_costs.data(), paircosts.data(), pairs.data(), num_nodes, num_labels, (int32_t)(pairs.size() / 2), sweeps,
+                                      labeling.data(), &r.sweeps_run, &r.energy, &r.bound, r.energies.data(), with_bounds ? r.bounds.data() : nullptr, nullptr));
+    return r;
+}
+// `polish` passes of iterated conditional modes over the node colours from `labeling`, which becomes the best candidate (1 + polish energies)
+inline MplpRound mplp_pairs_polish(const Matrix &unary_costs, const Matrix &paircosts, const std::vector<int32_t> &pairs, int num_nodes, int num_labels,
+                                   int polish, std::vector<int32_t> &labeling) {
+    MplpRound r;
+    r.energies.assign(1 + (size_t)std::max(polish, 0), 0.0);
+    check(msm_mplp_pairs_polish(unary_costs.data(), paircosts.data(), pairs.data(), num_nodes, num_labels, (int32_t)(pairs.size() / 2), polish, labeling.data(),
+                                &r.passes_run, &r.energy, r.energies.data()));
+    return r;
+}
+// the same on the GPU (msm_mplp_pairs_polish_gpu), bit for bit
+inline MplpRound mplp_pairs_polish_gpu(Context &ctx, const Matrix &unary_costs, const Matrix &paircosts, const std::vector<int32_t> &pairs, int num_nodes,
+                                       int num_labels, int polish, std::vector<int32_t> &labeling) {
+    MplpRound r;
+    r.energies.assign(1 + (size_t)std::max(polish, 0), 0.0);
+    check(msm_mplp_pairs_polish_gpu(ctx.handle(), unary_costs.data(), paircosts.data(), pairs.data(), num_nodes, num_labels, (int32_t)(pairs.size() / 2), polish,
+                                    labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
+    return r;
+}
+// what the context's last GPU run over pair tables did (msm_mplp_pairs_gpu_stats): ms in the sweeps' kernels, pair colours per sweep, sweeps run, the
+// widest colour class, ms in the polish, passes run
+inline std::array<double, 6> mplp_pairs_gpu_stats(Context &ctx) {
+    std::array<double, 6> s{};
+    check(msm_mplp_pairs_gpu_stats(ctx.handle(), s.data()));
+    return s;
+}
 // what several chains from one start hand back: labelings chains x N, energies per chain, best by std::min_element's rule
 struct McmcChains {
     std::vector<int32_t> labelings;
@@ -794,6 +858,21 @@ public:
         MplpRound r;
         r.energies.assign(1 + (size_t)std::max(polish, 0), 0.0);
         check(msm_cost_mplp_polish(h_, polish, labeling.data(), &r.passes_run, &r.energy, r.energies.data()));
+        return r;
+    }
+    // computeUnaryCosts + computePairwiseCosts + MPLP over the pair tables with both tables staying on the device, then `polish` passes of the sweeps'
+    // winner (msm_cost_mplp_pairs_optimise): what the two tables + msmhip::mplp_pairs_optimise (+ mplp_pairs_polish) give, bit for bit.
+    // The run's energy is the final labelling's; polished (optional) receives the polish's passes and 1 + polish energies.  Needs setPairs.
+    MplpRun mplp_pairs_optimise(int sweeps, int polish, std::vector<int32_t> &labeling, bool with_bounds = false, MplpRound *polished = nullptr) {
+        MplpRun r;
+        r.energies.assign((size_t)sweeps, 0.0);
+        if (with_bounds) r.bounds.assign((size_t)sweeps, 0.0);
+        MplpRound p;
+        p.energies.assign(1 + (size_t)std::max(polish, 0), 0.0);
+        check(msm_cost_mplp_pairs_optimise(h_, sweeps, polish, labeling.data(), &r.sweeps_run, &p.passes_run, &r.energy, &r.bound, r.energies.data(),
+                                           with_bounds ? r.bounds.data() : nullptr, p.energies.data()));
+        p.energy = r.energy;
+        if (polished) *polished = p;
         return r;
     }
     // the batched forms the optimisers' loops collapse to (I/Fusion/Fusion.h:138-196)

@@ -201,7 +201,8 @@ inline IntensityNorm intensity_from_config(const Config &c) {
 // what Rigid_cost_function::set_parameters reads, M/rigid_costfunction.cpp:50-58) instead of being listed in `skipped`
 // intensity (optional; opt-in): --IN / --INc are taken instead of refused and *intensity receives what the level loops need
 inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *varnorm = nullptr, std::vector<std::pair<int, std::string>> *skipped = nullptr,
-                                                 bool anat = false, bool rigid = false, IntensityNorm *intensity = nullptr, bool mplp = false) {
+                                                 bool anat = false, bool rigid = false, IntensityNorm *intensity = nullptr, bool mplp = false,
+                                                 bool mplp_pairs = false) {
     if (intensity) *intensity = intensity_from_config(c);
     if ((c.IN || c.INc) && !intensity) throw ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available");
     if (c.regoption == 4)  // M/mesh_registration.cpp:101-102
@@ -215,7 +216,10 @@ inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *v
     // mplp (opt-in): --dopt=MPLP, which is not newMSM's, is taken instead of refused and sets LevelOptions::mplp; like MCMC it reads triplets
     const bool use_mplp = mplp && c.dopt == "MPLP";
     if (c.dopt != "HOCR" && c.dopt != "MCMC" && c.dopt != "FastPD" && !use_mplp) throw ConfigError("Unrecognized optimiser");  // M/mesh_registration.cpp:202
-    if (c.dopt != "FastPD" && c.regoption == 1)
+    // mplp_pairs (opt-in, beside mplp): --dopt=MPLP with --regoption=1 is taken too and sets LevelOptions::pairwise and mplp_pairs -- MPLP over the
+    // unary and pair tables of the pairwise model
+    const bool use_pairs = use_mplp && mplp_pairs && c.regoption == 1;
+    if (c.dopt != "FastPD" && c.regoption == 1 && !use_pairs)
         throw ConfigError("--regoption=1 (pairwise regulariser) is driven by FastPD only in the reference; Fusion / MCMC read triplets");
     if (varnorm) *varnorm = c.VN;
     std::vector<LevelSpec> levels;
@@ -237,7 +241,7 @@ inline std::vector<LevelSpec> levels_from_config(const Config &c, int D, bool *v
         lv.data_order = c.datagrid[i], lv.cp_order = c.CPgrid[i], lv.sigma_in = c.sigma_in[i], lv.sigma_ref = c.sigma_ref[i];
         LevelOptions &o = lv.options;
         o.sg_order = c.SGgrid[i], o.iters = c.it[i], o.mciters = c.mciters[i], o.mcparam = c.mcparam, o.rescale_labels = c.rescaleL;
-        o.fusion = c.dopt == "HOCR", o.pairwise = c.dopt == "FastPD", o.mplp = use_mplp;
+        o.fusion = c.dopt == "HOCR", o.pairwise = c.dopt == "FastPD" || use_pairs, o.mplp = use_mplp && !use_pairs, o.mplp_pairs = use_pairs;
         o.anat_order = i < c.anatgrid.size() ? c.anatgrid[i] : c.CPgrid[i] + 2;
         o.cost.kind = kind, o.cost.simmeasure = c.simval[i], o.cost.regularisermode = c.regoption, o.cost.lambda = c.lambda[i];
         o.cost.shearmodulus = c.shearmod, o.cost.bulkmodulus = c.bulkmod, o.cost.kexponent = c.k_exponent, o.cost.exponent = c.regexp;

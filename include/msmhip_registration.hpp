@@ -68,6 +68,11 @@ struct LevelOptions {
     // set_mplp_forbid, DESIGN.md 5.19 "Forbidden entries"; what MSMHIP_MPLP_FORBID=on asks of the executables) -- the strain regulariser produces
     // such entries wherever a label set lets control points meet, as the unscaled sampling grid does
     bool mplp_forbid = false;
+    // with pairwise (an extension; what --dopt=MPLP with --regoption=1 asks for under MSMHIP_MPLP=on and MSMHIP_MPLP_PAIRS=on): the pairwise model is
+    // solved by MPLP over its unary and pair tables, mciters sweeps per iteration from the zero labelling, both tables on the device (DiscreteCostFunction::
+    // mplp_pairs_optimise), in the stand-in solve's place; with mplp_round, mplp_polish polish passes of the winner follow.  mplp_forbid
+    // does not apply to it
+    bool mplp_pairs = false;
     // the MCMC branch leaves both tables on the device and runs the sweeps there (msm_cost_mcmc_optimise) instead of fetching them for the host
     // optimiser: the same labelings, bit for bit (what MSMHIP_MCMC=gpu asks of the executables)
     bool mcmc_gpu = false;
@@ -203,7 +208,8 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
         ++m_iter;
         const bool mplp = o.mplp && !o.fusion && !o.pairwise;
         const bool mcmc_gpu = o.mcmc_gpu && !o.fusion && !o.pairwise && !mplp;
-        if (!mcmc_gpu && !mplp) PhaseClock::timed(clock, "unary_table", [&] { costfct.computeUnaryCosts(); });
+        const bool mplp_pairs = o.mplp_pairs && o.pairwise && !o.fusion;
+        if (!mcmc_gpu && !mplp && !mplp_pairs) PhaseClock::timed(clock, "unary_table", [&] { costfct.computeUnaryCosts(); });
         std::vector<int32_t> labeling((size_t)N, 0);  // resetLabeling
         const int L = (int)(labels.size() / 3), T = (int)(triplets.size() / 3);
         if (o.fusion) {  // ---- Fusion::optimize: two sweeps over the labels, a fusion move per label step
@@ -244,6 +250,8 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
                 for (int i = 0; i < N; ++i)
                     if (x[(size_t)i] == 1 && labeling[(size_t)i] != label) labeling[(size_t)i] = label;
             }
+        } else if (mplp_pairs) {  // ---- MPLP over the pair tables, tables and sweeps on the device, then the polish of the winner where asked for
+            PhaseClock::timed(clock, "optimiser", [&] { costfct.mplp_pairs_optimise(o.mciters, o.mplp_round ? o.mplp_polish : 0, labeling); });
         } else if (o.pairwise) {  // ---- FastPD: computeUnaryCosts, computePairwiseCosts, the solve
             PhaseClock::timed(clock, "pairwise_table", [&] { costfct.computePairwiseCosts(); });
             PhaseClock::timed(clock, "optimiser", [&] { pairwise_icm(costfct.unarycosts, costfct.paircosts, pairs, N, L, labeling, 100); });

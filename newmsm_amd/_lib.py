@@ -148,6 +148,13 @@ SIGNATURES = {
     "msm_mplp_round_forbid": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_dp, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp, c_lp]),
     "msm_mplp_round_forbid_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_dp, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp,
                                             c_lp]),
+    "msm_mplp_pairs_colouring": (C.c_int, [c_ip, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_ip]),
+    "msm_mplp_pairs_energy": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip, c_dp]),
+    "msm_mplp_pairs_optimise": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "msm_mplp_pairs_optimise_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "msm_mplp_pairs_polish": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp]),
+    "msm_mplp_pairs_polish_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp]),
+    "msm_mplp_pairs_gpu_stats": (C.c_int, [_VP, c_dp]),
     "msm_fusion_icm_step": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_pairwise_icm": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_nearest_neighbour": (C.c_int, [_VP, c_dp, C.c_int32, c_dp, C.c_int32, c_dp, c_dp, c_dp]),
@@ -184,6 +191,7 @@ SIGNATURES = {
     "msm_cost_mplp_polish": (C.c_int, [_VP, C.c_int32, c_ip, c_ip, c_dp, c_dp]),
     "msm_cost_set_mplp_forbid": (C.c_int, [_VP, C.c_int32]),
     "msm_cost_mplp_forbidden": (C.c_int, [_VP, c_lp]),
+    "msm_cost_mplp_pairs_optimise": (C.c_int, [_VP, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "msm_cost_total": (C.c_int, [_VP, c_ip, c_dp, c_dp]),
     "msm_cost_enable_timing": (C.c_int, [_VP, C.c_int]),
     "msm_cost_kernel_times": (C.c_int, [_VP, c_dp, C.c_int32, c_ip]),

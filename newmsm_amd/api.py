@@ -909,6 +909,87 @@ def mplp_round_gpu_stats(ctx):
     return dict(decode_ms=float(s[0]), polish_ms=float(s[1]), classes=int(s[2]), passes_run=int(s[3]))
 
 
+def _mplp_pair_tables(unary, paircosts, pairs):
+    U, pu = _d(unary)
+    L, N = U.shape
+    pc, ppc = _d(paircosts)
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P = pr.shape[0]
+    assert pc.size == P * L * L
+    return (U, pc, pr), (pu, ppc, pr.ctypes.data_as(c_ip), N, L, P)
+
+
+def _mplp_pair_outputs(N, L, P, sweeps, labeling, bound, bounds, messages):
+    """_mplp_outputs with messages of P x 2 x L"""
+    out, args = _mplp_outputs(N, L, 0, sweeps, labeling, bound, bounds, False)
+    if messages:
+        out["messages"] = np.zeros((P, 2, L))
+        args[-1] = out["messages"].ctypes.data_as(c_dp)
+    return out, args
+
+
+def mplp_pairs_colouring(pairs, N):
+    """msm_mplp_pairs_colouring [host]: (colour per pair, pair colours, colour per node, node colours) of DESIGN.md 5.20 -- a sweep walks the pair
+    colours, a polish pass the node colours"""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    pcol, ncol, pk, nk = np.zeros(pr.shape[0], dtype=np.int32), np.zeros(int(N), dtype=np.int32), C.c_int32(0), C.c_int32(0)
+    check(lib().msm_mplp_pairs_colouring(pr.ctypes.data_as(c_ip), int(N), pr.shape[0], pcol.ctypes.data_as(c_ip), C.byref(pk), ncol.ctypes.data_as(c_ip),
+                                         C.byref(nk)))
+    return pcol, pk.value, ncol, nk.value
+
+
+def mplp_pairs_energy(unary, paircosts, pairs, labeling):
+    """msm_mplp_pairs_energy [host]: the energy of a labelling over the unary (L x N) and pair (P x L x L, [p, b, a]) tables"""
+    keep, head = _mplp_pair_tables(unary, paircosts, pairs)
+    lab = np.ascontiguousarray(labeling, dtype=np.int32)
+    assert lab.size == head[3]
+    e = C.c_double(np.nan)
+    check(lib().msm_mplp_pairs_energy(*head, lab.ctypes.data_as(c_ip), C.byref(e)))
+    return e.value
+
+
+def mplp_pairs_optimise(unary, paircosts, pairs, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+    """msm_mplp_pairs_optimise [host]: MPLP over the unary table (L x N) and the pair table of a --regoption=1 level (P x L x L as
+    computePairwiseCosts returns it: [p, b, a]) -- an extension, DESIGN.md 5.20.  Returns MplpResult as mplp_optimise does, messages P x 2 x L."""
+    keep, head = _mplp_pair_tables(unary, paircosts, pairs)
+    out, tail = _mplp_pair_outputs(head[3], head[4], head[5], sweeps, labeling, bound, bounds, messages)
+    check(lib().msm_mplp_pairs_optimise(*head, int(sweeps), *tail))
+    return _mplp_result(out)
+
+
+def mplp_pairs_optimise_gpu(ctx, unary, paircosts, pairs, labeling, sweeps=30, bound=True, bounds=False, messages=False):
+    """msm_mplp_pairs_optimise_gpu: mplp_pairs_optimise with the sweeps on the GPU (a launch per pair colour); the same MplpResult, bit for bit"""
+    keep, head = _mplp_pair_tables(unary, paircosts, pairs)
+    out, tail = _mplp_pair_outputs(head[3], head[4], head[5], sweeps, labeling, bound, bounds, messages)
+    check(lib().msm_mplp_pairs_optimise_gpu(ctx.h, *head, int(sweeps), *tail))
+    return _mplp_result(out)
+
+
+def mplp_pairs_polish(unary, paircosts, pairs, labeling, polish=8):
+    """msm_mplp_pairs_polish [host]: `polish` passes of iterated conditional modes over the node colours; MplpRound(labeling,
+    passes_run, energy, energies) with 1 + polish energies, never worse than the labelling handed in"""
+    keep, head = _mplp_pair_tables(unary, paircosts, pairs)
+    out, tail = _mplp_round_outputs(head[3], 1, polish, labeling)
+    check(lib().msm_mplp_pairs_polish(*head, int(polish), *tail))
+    return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
+
+
+def mplp_pairs_polish_gpu(ctx, unary, paircosts, pairs, labeling, polish=8):
+    """msm_mplp_pairs_polish_gpu: mplp_pairs_polish on the GPU (a launch per node colour and pass); the same MplpRound, bit for bit"""
+    keep, head = _mplp_pair_tables(unary, paircosts, pairs)
+    out, tail = _mplp_round_outputs(head[3], 1, polish, labeling)
+    check(lib().msm_mplp_pairs_polish_gpu(ctx.h, *head, int(polish), *tail))
+    return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
+
+
+def mplp_pairs_gpu_stats(ctx):
+    """msm_mplp_pairs_gpu_stats of the context's last GPU run over pair tables: dict(kernel_ms, classes, sweeps_run, widest_class, polish_ms,
+    passes_run)"""
+    s = np.zeros(6)
+    check(lib().msm_mplp_pairs_gpu_stats(ctx.h, s.ctypes.data_as(c_dp)))
+    return dict(kernel_ms=float(s[0]), classes=int(s[1]), sweeps_run=int(s[2]), widest_class=int(s[3]), polish_ms=float(s[4]), passes_run=int(s[5]))
+
+
 def _chain_args(seeds, N):
     """(seeds array or None, its pointer or NULL, K, labelings K x N, energies K) of a chains call; seeds=None passes a NULL pointer with K = 1"""
     c_u64p = C.POINTER(C.c_uint64)
@@ -1362,6 +1443,18 @@ class DiscreteCostFunction:
         out, tail = _mplp_round_outputs(self.N, 1, polish, labeling)
         check(lib().msm_cost_mplp_polish(self.h, int(polish), *tail))
         return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"])
+
+    def mplp_pairs_optimise(self, labeling, sweeps=30, polish=0, bound=True, bounds=False):
+        """msm_cost_mplp_pairs_optimise: computeUnaryCosts + computePairwiseCosts + MPLP over the pair tables with both tables
+        staying on the device, then `polish` passes of the sweeps' winner; what computeUnaryCosts() + computePairwiseCosts() + api.mplp_pairs_optimise
+        (+ api.mplp_pairs_polish) give, bit for bit.  Returns (MplpResult of the sweeps with the final labelling and energy, MplpRound of the polish or
+        None).  The forbidden-entry switch (set_mplp_forbid) is ignored: a pair cost is finite or the folding value."""
+        out, tail = _mplp_pair_outputs(self.N, self.L, getattr(self, "P", 0), sweeps, labeling, bound, bounds, False)  # (no pairs: the library says so)
+        passes, pe = C.c_int32(-1), np.full(1 + max(int(polish), 0), np.nan)
+        check(lib().msm_cost_mplp_pairs_optimise(self.h, int(sweeps), int(polish), tail[0], tail[1], C.byref(passes), tail[2], tail[3], tail[4], tail[5],
+                                                 pe.ctypes.data_as(c_dp)))
+        res = _mplp_result(out)
+        return res, (MplpRound(res.labeling, passes.value, res.energy, pe) if int(polish) > 0 else None)
 
     def computePairwiseCost(self, pair, la, lb):
         p, pp = _i(np.atleast_1d(pair))

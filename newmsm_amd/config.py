@@ -124,7 +124,7 @@ def parse_config(text):
     return cfg
 
 
-def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmatch=False, mplp=False):
+def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmatch=False, mplp=False, mplp_pairs=False):
     """The DISCRETE levels of `cfg` (parse_config's result) for data with D feature rows, as keyword sets of run_multiresolution, plus what
     applies to the whole run: returns (levels, run_kw, skipped) -- run_multiresolution(ops, ..., levels, **run_kw).  skipped: the (index,
     method) of levels that are not DISCRETE (the affine stage is outside the path).  fix_parameters_for_level + NonLinearSRegDiscreteModel::
@@ -137,7 +137,9 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmat
     histmatch: --IN / --INc are taken instead of refused (opt-in: the executables do when MSMHIP_HISTMATCH=on) and run_kw carries what the level
     loops need: intensity (_IN) and cut (_cut: set by --INc alone, M/mesh_registration.cpp:694-703).
     mplp: --dopt=MPLP, which is not newMSM's, is taken instead of refused (opt-in: the executables do when MSMHIP_MPLP=on) and names optimiser "mplp"
-    (registration.run_discrete_level; a level's --mciters is its sweep count); like MCMC it reads triplets, so --regoption=1 is refused."""
+    (registration.run_discrete_level; a level's --mciters is its sweep count); like MCMC it reads triplets, so --regoption=1 is refused.
+    mplp_pairs (beside mplp; the executables' MSMHIP_MPLP_PAIRS=on): --dopt=MPLP with --regoption=1 is taken instead and names optimiser "mplp_pairs",
+    MPLP over the unary and pair tables of the pairwise model; every other combination is what it was."""
     if (cfg["IN"] or cfg["INc"]) and not histmatch:
         raise ConfigError("--IN / --INc (histogram matching through FSL's MISCMATHS::Histogram, M/reg_tools.cpp:745-802) is not available")
     if groupwise:
@@ -154,11 +156,11 @@ def levels_from_config(cfg, D, anat=False, groupwise=False, rigid=False, histmat
         kind = "ho_univariate" if cfg["triclique"] else "univariate"
     optimiser = {"HOCR": "fusion", "MCMC": "mcmc", "FastPD": "fastpd"}.get(cfg["dopt"])
     if mplp and cfg["dopt"] == "MPLP":
-        optimiser = "mplp"
+        optimiser = "mplp_pairs" if mplp_pairs and cfg["regoption"] == 1 and not groupwise else "mplp"
     if optimiser is None:
         raise ConfigError("Unrecognized optimiser")  # M/mesh_registration.cpp:202
     rmode = cfg["regoption"]
-    if optimiser != "fastpd" and rmode == 1 and not groupwise:
+    if optimiser not in ("fastpd", "mplp_pairs") and rmode == 1 and not groupwise:
         raise ConfigError("--regoption=1 (pairwise regulariser) is driven by FastPD only in the reference; Fusion / MCMC read triplets")
     levels, skipped = [], []
     for i, method in enumerate(cfg["opt"]):

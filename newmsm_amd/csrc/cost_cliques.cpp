@@ -6,6 +6,7 @@
 #include "label_step.hpp"
 #include "mcmc.hpp"
 #include "mplp.hpp"
+#include "mplp_pairs.hpp"
 
 using namespace msm;
 
@@ -368,6 +369,49 @@ int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t
     const MplpRoundOutputs r = {labeling, passes_run, energy, energies};
     MplpReading rd(c->mplp_forbid);
     return keep_counts(c, rd, mplp_round_device(c->ctx, "msm_mplp_round", c->d_U.p, c->d_clique_out.p, nullptr, c->triplets.data(), N, L, T, 1, polish, r, rd));
+}
+
+// MPLP over the pair tables (mplp_pairs.cpp runs the sweeps and the polish): computeUnaryCosts + computePairwiseCosts with both tables
+// staying where their kernels wrote them (c->d_U, c->d_clique_out), the sweeps from `labeling`, then `polish` passes of the sweeps' winner over the
+// same tables, inspected once.  The forbidden-entry switch does not apply: computePairwiseCost returns a finite cost or the folding value.
+int msm_cost_mplp_pairs_optimise(msm_cost *c, int32_t sweeps, int32_t polish, int32_t *labeling, int32_t *sweeps_run, int32_t *passes_run, double *energy,
+                                 double *bound, double *energies, double *bounds, double *polish_energies) {
+    const char *what = "msm_cost_mplp_pairs_optimise";  // every refusal and failure of this call, the sweeps' and the polish's included, names it
+    if (!c || !labeling || sweeps < 0) return fail(MSM_ERR_INVALID, "%s: bad arguments", what);
+    if (!c->cpgrid || c->L <= 0) return fail(MSM_ERR_STATE, "%s: meshes and labels must be set first", what);
+    if (c->pairs.empty()) return fail(MSM_ERR_STATE, "%s: pairs must be set first (msm_cost_set_pairs)", what);
+    if (polish < 0 || polish > kMplpMaxPolish) return fail(MSM_ERR_INVALID, "%s: %d polish passes (0 to %d)", what, polish, kMplpMaxPolish);
+    MSM_TRY(mplp_pairs_check_arguments(what, c->pairs.data(), c->cpgrid->V, c->L, (int)(c->pairs.size() / 2), sweeps, labeling));
+    MSM_TRY(msm_cost_unary_table_async(c));  // (drops a label step queued ahead on the context first)
+    MSM_TRY(check_status(c->ctx, "computeUnaryCosts"));
+    CliqueArgs a;
+    MSM_TRY(clique_args(c, false, true, a));
+    const size_t total = (size_t)a.P * a.L * a.L;
+    if (c->d_clique_out.ensure(total) != hipSuccess) return stage_alloc_failed(sizeof(double) * total);
+    MSM_TRY(launch_pairwise_table(c->ctx, a, c->d_clique_out.p));
+    c->counters[3] += (int64_t)total;
+    MSM_TRY(check_status(c->ctx, "computePairwiseCosts"));
+    std::vector<int32_t> lab(labeling, labeling + a.N);  // the caller's labelling stays as it is when the polish fails
+    int32_t run = 0, passes = 0;
+    double e = 0.0, b = 0.0;
+    std::vector<double> es((size_t)sweeps), bs(bounds ? (size_t)sweeps : 0);
+    bool inspected = false;
+    const MplpOutputs o = {lab.data(), &run, &e, bound ? &b : nullptr, es.data(), bounds ? bs.data() : nullptr, nullptr};
+    MSM_TRY(mplp_pairs_run_device(c->ctx, what, c->d_U.p, c->d_clique_out.p, c->pairs.data(), a.N, a.L, a.P, sweeps, o, &inspected));
+    if (polish > 0) {
+        const MplpRoundOutputs r = {lab.data(), &passes, &e, polish_energies};
+        MSM_TRY(mplp_pairs_polish_device(c->ctx, what, c->d_U.p, c->d_clique_out.p, c->pairs.data(), a.N, a.L, a.P, polish, r, &inspected));
+    }
+    std::copy(lab.begin(), lab.end(), labeling);
+    if (sweeps_run) *sweeps_run = run;
+    if (passes_run) *passes_run = passes;
+    if (energy) *energy = e;
+    if (bound) *bound = b;
+    if (run > 0) {
+        if (energies) std::copy(es.begin(), es.end(), energies);
+        if (bounds) std::copy(bs.begin(), bs.end(), bounds);
+    }
+    return MSM_OK;
 }
 
 // evaluateTotalCostSum, M/DiscreteCostFunction.cpp:55-77: the three sums run in the reference's serial order on

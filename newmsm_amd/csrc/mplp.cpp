@@ -92,7 +92,7 @@ int mplp_judge(const char *what, MplpReading &r, const int64_t *mc, bool *F) {
     const int64_t *t = r.counts;
     if (t[0]) return refuse_non_finite(what, "unary");
     if (!r.forbid) {
-        if (t[1] || t[2] || t[3]) return refuse_non_finite(what, "triplet");
+        if (t[1] || t[2] || t[3]) return refuse_non_finite(what, r.table);
         if (mc && (mc[1] || mc[2] || mc[3])) return fail(MSM_ERR_INVALID, "%s: the messages hold a non-finite value (NaN or infinity)", what);
     } else {  // DESIGN.md 5.19 "Forbidden entries": each refusal names the table and the class of value
         if (t[3])

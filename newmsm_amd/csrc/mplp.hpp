@@ -65,6 +65,7 @@ struct MplpReading {
     bool inspected = false;             // counts and F hold what a pass over the tables found, and the reading does not refuse them
     int64_t counts[4] = {0, 0, 0, 0};   // mplp_classify's
     bool F = false;                     // the tables call for the forbidden-aware code (never under the plain reading)
+    const char *table = "triplet";      // what the plain reading's refusal calls the factor table ("pair": mplp_pairs.cpp)
     explicit MplpReading(bool forbid_) : forbid(forbid_) {}
 };
 // The one judgement of counted tables, and of the counted messages of mode 0 (mc; null: none), under either reading: a refusal, or MSM_OK with

@@ -37,11 +37,18 @@ def _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, polish, forbid=F
     return api.mplp_round(unary, tcosts, triplets, lab, mode=1, polish=polish, forbid=forbid).labeling
 
 
+def _mplp_pairs_host(unary, paircosts, pairs, labeling, sweeps, polish=0):
+    """the pairwise MPLP branch of run_discrete_level over fetched tables: the host literal's labelling, polished where polish > 0 -- what
+    msm_cost_mplp_pairs_optimise does over the device tables"""
+    lab = api.mplp_pairs_optimise(unary, paircosts, pairs, labeling, sweeps=sweeps, bound=False).labeling
+    return api.mplp_pairs_polish(unary, paircosts, pairs, lab, polish=polish).labeling if polish > 0 else lab
+
+
 class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
     def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True, mplp_round=False, mplp_polish=8,
-                 mplp_forbid=False):
+                 mplp_forbid=False, mplp_pairs=False):
         """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
         the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
         bytes (what MSMHIP_FEATURES=gpu asks of the executables).
@@ -56,9 +63,13 @@ class ProductOps:
         MSMHIP_MPLP_ROUND=on and MSMHIP_MPLP_POLISH=n ask of the executables)
         mplp_forbid: the MPLP branch reads NaN and +inf entries of the triplet table as forbidden label combinations instead of refusing the table
         (DESIGN.md 5.19 "Forbidden entries"; the strain regulariser produces them wherever a label set lets control points meet), on the device route
-        (msm_cost_set_mplp_forbid) and on the host route (msm_mplp_optimise_forbid) alike; what MSMHIP_MPLP_FORBID=on asks of the executables"""
+        (msm_cost_set_mplp_forbid) and on the host route (msm_mplp_optimise_forbid) alike; what MSMHIP_MPLP_FORBID=on asks of the executables
+        mplp_pairs: what MSMHIP_MPLP_PAIRS=on asks of the executables -- --dopt=MPLP with --regoption=1 runs as optimiser "mplp_pairs" (MPLP over the
+        unary and pair tables; config.levels_from_config(mplp_pairs=True) names it), and run_discrete_level refuses that optimiser without it.  That branch follows mplp_gpu (tables and sweeps on
+        the device: msm_cost_mplp_pairs_optimise) and, with mplp_round, polishes the sweeps' winner with mplp_polish passes; it ignores mplp_forbid"""
         self.ctx = ctx
         self.mplp_forbid = bool(mplp_forbid)
+        self.mplp_pairs = bool(mplp_pairs)
         self.mplp_round = bool(mplp_round)
         self.mplp_polish = int(mplp_polish)
         if not 0 <= self.mplp_polish <= 64:
@@ -204,6 +215,9 @@ class ProductOps:
             return _mplp_round_host(unary, tcosts, triplets, labeling, sweeps, self.mplp_polish, self.mplp_forbid)
         return _mplp_host(unary, tcosts, triplets, labeling, sweeps, self.mplp_forbid)
 
+    def mplp_pairs_solve(self, unary, paircosts, pairs, labeling, sweeps):
+        return _mplp_pairs_host(unary, paircosts, pairs, labeling, sweeps, self.mplp_polish if self.mplp_round else 0)
+
     def fusion_step(self, unary2, octets, triplets, passes, quads=None, pairs=None):
         return api.fusion_icm_step(unary2, octets, triplets, passes, quads=quads, pairs=pairs)
 
@@ -297,6 +311,9 @@ class _ProductCost:
 
     def mplp_round(self, labeling, sweeps, polish):
         return self.cf.mplp_round(labeling, sweeps=sweeps, polish=polish, then_polish=True)[0].labeling
+
+    def mplp_pairs_optimise(self, labeling, sweeps, polish):
+        return self.cf.mplp_pairs_optimise(labeling, sweeps=sweeps, polish=polish, bound=False)[0].labeling
 
     def total(self, labeling):
         return self.cf.evaluateTotalCostSum(labeling)[0]
@@ -491,7 +508,9 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
     (ELC + FastPD, licence-restricted) is replaced by a stand-in (ops.fusion_step: iterated conditional modes, icm_passes passes): such a run
     exercises and times the path as HOCR would, its result is not the reference's optimum.  "fastpd": --regoption=1 as --dopt=FastPD drives it
     (M/mesh_registration.cpp:182-188): the unary table and the P x L x L pair tables (computePairwiseCosts), then a stand-in for FPD::FastPD
-    (ops.pairwise_solve: iterated conditional modes over all labels).  "mplp" (an extension, not newMSM's): max-product linear programming over the
+    (ops.pairwise_solve: iterated conditional modes over all labels).  "mplp_pairs" (an extension, taken only where ops.mplp_pairs is set): that pairwise model solved by MPLP over its unary
+    and pair tables, `mciters` sweeps per iteration from the zero labelling and, with ops.mplp_round, ops.mplp_polish polish passes of
+    the winner; on the device through the cost function where ops.mplp_gpu is set, over the fetched tables otherwise -- the same labelling.  "mplp" (an extension, not newMSM's): max-product linear programming over the
     MCMC optimiser's two tables, `mciters` sweeps per iteration from the zero labelling (api.mplp_optimise) -- deterministic, never
     worse than its start; the tables stay on the device where ops.mplp_gpu is set and the ops' cost function has mplp_optimise, otherwise they are
     fetched for the host literal (ops.mplp), which gives the same labelling; with ops.mplp_round the iteration rounds the final messages to a labelling
@@ -534,9 +553,11 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
     maxsep, mvdmax = ops.cp_spacings(cpgrid, cp_xyz, cp_tri)
     samples, barycentres = ops.label_sampling_grid(sg_order, labeldist * mvdmax)
     centre = samples[0]
-    pairwise = optimiser == "fastpd"  # --regoption=1: the model lists pairs instead of triplets (M/DiscreteModel.cpp:40,98-101,258-259)
+    pairwise = optimiser in ("fastpd", "mplp_pairs")  # --regoption=1: the model lists pairs instead of triplets (M/DiscreteModel.cpp:40,98-101,258-259)
     if pairwise and rmode != 1:
         raise ValueError("MeshREG ERROR:: you cannot run higher order clique regularisers with fastPD ")  # M/mesh_registration.cpp:759-760
+    if optimiser == "mplp_pairs" and not getattr(ops, "mplp_pairs", False):  # an extension, opt-in like the others: the ops must have asked for it
+        raise ValueError("optimiser \"mplp_pairs\" (MPLP over the pair tables, an extension) needs ops.mplp_pairs: ProductOps(mplp_pairs=True)")
     triplets = None if pairwise else ops.estimate_triplets(cpgrid, cp_tri)
     pairs = ops.estimate_pairs(cpgrid, cp_tri, len(cp_xyz)) if pairwise else None
     cost = ops.cost(kind, simmeasure, rmode, cost_params, target, source, cpgrid, src_feat)  # set_meshes: _ORIG, _oCPgrid
@@ -584,7 +605,8 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
         m_iter += 1
         mcmc_gpu = optimiser == "mcmc" and getattr(ops, "mcmc_gpu", False)  # both tables stay on the device (msm_cost_mcmc_optimise)
         mplp_gpu = optimiser == "mplp" and getattr(ops, "mplp_gpu", False) and hasattr(cost, "mplp_optimise")  # the same for msm_cost_mplp_optimise
-        unary = None if mcmc_gpu or mplp_gpu else timed("unary_table", cost.unary_table)
+        mplp_pairs_gpu = optimiser == "mplp_pairs" and getattr(ops, "mplp_gpu", False) and hasattr(cost, "mplp_pairs_optimise")  # msm_cost_mplp_pairs_optimise
+        unary = None if mcmc_gpu or mplp_gpu or mplp_pairs_gpu else timed("unary_table", cost.unary_table)
         labeling = np.zeros(len(cp_xyz), dtype=np.int32)  # resetLabeling
         if optimiser == "fusion":  # --- Fusion::optimize: computeUnaryCosts, then per label step the 8 T combinations
             nodes = np.arange(len(cp_xyz))
@@ -605,6 +627,11 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
                 unary2 = np.stack([unary[labeling, nodes], unary[label]], axis=1)
                 x = timed("optimiser", ops.fusion_step, unary2, octets, triplets, icm_passes)
                 labeling = np.where((x == 1) & (labeling != label), label, labeling).astype(np.int32)
+        elif mplp_pairs_gpu:  # --- MPLP over the pair tables, tables and sweeps on the device: the labeling of the branch below, bit for bit
+            labeling = timed("optimiser", cost.mplp_pairs_optimise, labeling, mciters, ops.mplp_polish if getattr(ops, "mplp_round", False) else 0)
+        elif optimiser == "mplp_pairs":  # --- the same over fetched tables: computeUnaryCosts, computePairwiseCosts, the host literal and its polish
+            paircosts = timed("pairwise_table", cost.pairwise_table)
+            labeling = timed("optimiser", getattr(ops, "mplp_pairs_solve", _mplp_pairs_host), unary, paircosts, pairs, labeling, mciters)
         elif pairwise:  # --- FastPD: computeUnaryCosts, computePairwiseCosts, FPD::FastPD(model, 100) (M/mesh_registration.cpp:182-188)
             paircosts = timed("pairwise_table", cost.pairwise_table)
             labeling = timed("optimiser", ops.pairwise_solve, unary, paircosts, pairs, 100)

@@ -255,6 +255,16 @@ bool mplp_forbid_setting(bool mplp) {
     return env != nullptr;
 }
 
+// MSMHIP_MPLP_PAIRS=on (beside MSMHIP_MPLP=on): --dopt=MPLP with --regoption=1 runs, as MPLP over the unary and pair tables of the pairwise model with
+// both tables on the device, instead of ending the run with the FastPD-only message
+bool mplp_pairs_setting(bool mplp) {
+    const char *env = std::getenv("MSMHIP_MPLP_PAIRS");
+    if (env && std::string(env) != "on")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_MPLP_PAIRS=") + env + ": MPLP over the pair tables of --regoption=1 is switched on with MSMHIP_MPLP_PAIRS=on (unset: off)");
+    if (env && !mplp) throw Error(MSM_ERR_INVALID, "MSMHIP_MPLP_PAIRS=on lets --dopt=MPLP run a --regoption=1 level: it needs MSMHIP_MPLP=on");
+    return env != nullptr;
+}
+
 // MSMHIP_MPLP_ROUND=on (beside MSMHIP_MPLP=on): every iteration of a --dopt=MPLP level rounds the final messages to a labelling after its sweeps
 // ("Rounding"), with MSMHIP_MPLP_POLISH=n (0 ... 64, default 8) polish passes.  Returns whether it is on and sets *polish.
 bool mplp_round_setting(bool mplp, int *polish) {
@@ -298,7 +308,8 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     int mplp_polish = 8;
     const bool mplp_round = mplp_round_setting(mplp, &mplp_polish);
     const bool mplp_forbid = mplp_forbid_setting(mplp);
-    std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr, mplp);
+    const bool mplp_pairs = mplp_pairs_setting(mplp);
+    std::vector<LevelSpec> levels = levels_from_config(cfg, D, &varnorm, &skipped, anat, rigid, histmatch_enabled() ? &inorm : nullptr, mplp, mplp_pairs);
     const char *mcmc_env = std::getenv("MSMHIP_MCMC");  // "gpu": the --dopt=MCMC levels keep both cost tables on the device and run the sweeps there
     const bool mcmc_gpu = mcmc_env && std::string(mcmc_env) == "gpu";
     if (mcmc_gpu)

@@ -145,6 +145,18 @@ def mplp_forbid_setting():
     return text == "on"
 
 
+def mplp_pairs_setting():
+    """MSMHIP_MPLP_PAIRS=on (beside MSMHIP_MPLP=on): --dopt=MPLP with --regoption=1 runs, as MPLP over the unary and pair tables of the pairwise model
+    with both tables on the device, instead of ending the run with the FastPD-only message.  Anything else, or the variable
+    without MSMHIP_MPLP=on, ends the run with a message and exit status 1."""
+    text = os.environ.get("MSMHIP_MPLP_PAIRS")
+    if text is not None and text != "on":
+        raise SystemExit("MSMHIP_MPLP_PAIRS=%s: MPLP over the pair tables of --regoption=1 is switched on with MSMHIP_MPLP_PAIRS=on (unset: off)" % text)
+    if text is not None and not mplp_enabled():
+        raise SystemExit("MSMHIP_MPLP_PAIRS=on lets --dopt=MPLP run a --regoption=1 level: it needs MSMHIP_MPLP=on")
+    return text == "on"
+
+
 def mplp_round_setting():
     """MSMHIP_MPLP_ROUND=on (beside MSMHIP_MPLP=on): every iteration of a --dopt=MPLP level rounds the final messages to a labelling after its sweeps
     ("Rounding"), with MSMHIP_MPLP_POLISH=n (0 ... 64, default 8) polish passes.  Returns (on, polish); anything else, or either
@@ -240,7 +252,8 @@ def group_mcmc_draw_setting():
 def discrete_levels(cfg, D, anat=False, groupwise=False):
     levels, run_kw, skipped = config.levels_from_config(cfg, D, anat=anat, groupwise=groupwise, rigid=rigid_enabled() and not groupwise,
                                                         **(dict(histmatch=True) if histmatch_enabled() else {}),
-                                                        **(dict(mplp=True) if mplp_enabled() else {}))
+                                                        **(dict(mplp=True) if mplp_enabled() else {}),
+                                                        **(dict(mplp_pairs=True) if not groupwise and mplp_pairs_setting() else {}))
     for index, method in skipped:
         print("register_files.py: level %d (--opt=%s) is outside the path (the affine stage stays on the CPU in newmsm): skipped" % (index + 1, method), file=sys.stderr)
     if not levels:
@@ -319,6 +332,7 @@ def main(argv):
         return main_groupwise(a, surf_ext, data_ext, group_mcmc, chains, draw_gpu)
     mplp_round, mplp_polish = mplp_round_setting()
     mplp_forbid = mplp_forbid_setting()
+    mplp_pairs = mplp_pairs_setting()
     for flag in ("inmesh", "indata", "refdata"):
         if not getattr(a, flag):
             raise SystemExit("register_files.py: --%s is required" % flag)
@@ -354,7 +368,7 @@ def main(argv):
             print("MCMC with %d chains per iteration." % chains)
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish, mplp_forbid=mplp_forbid), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish, mplp_forbid=mplp_forbid, mplp_pairs=mplp_pairs), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])

@@ -1,4 +1,4 @@
-"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--round | --forbid] [--polish P] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
+"""tools/time_mplp.py [--sweeps N] [--mcmc-sweeps N] [--repeats R] [--round | --forbid | --pairs] [--polish P] [--out FILE] -- the MPLP optimiser (an extension, not newMSM's) on the
 MI355X against its host literal, over the unary and triplet tables tools/time_mcmc.py builds: BASELINE config 2 (pairwise sulc, ico6 data, ico4 control
 grid, 19 labels) and an ico3 control grid.  It reports and judges nothing.  Per grid: the energy of the start (all zero), the energy the Monte Carlo
 optimiser reaches on the device in --mcmc-sweeps sweeps (msm_cost_mcmc_optimise, tools/time_mcmc.py's sweep count by default), the energy of MPLP's decode
@@ -16,7 +16,14 @@ and the start, the Monte Carlo optimiser's energy and the bound.  Times are repo
 without label rescaling on the regular control grid, which hold NaN and +infinity entries (their counts are printed): ms per sweep, per conditioned
 decode and per polish pass of the forbidden-aware kernels (msm_mplp_optimise_forbid_gpu, msm_mplp_round_forbid_gpu) and, beside them, of the plain
 kernels on a copy of the table whose forbidden entries the host replaced by 1e7 -- both in one process, alternated, by the HIP events around the
-kernels.  With them the energies E^ of the start, of every sweep's decode and of the rounding's candidates, and the bound.  No time is a threshold."""
+kernels.  With them the energies E^ of the start, of every sweep's decode and of the rounding's candidates, and the bound.  No time is a threshold.
+
+--pairs measures MPLP over the pair tables of a --regoption=1 level instead (profiles/mplp_pairs_time.json), on the unary and pair tables
+of the same two grids with the pairwise regulariser: ms per sweep by the HIP events around the sweeps' kernels (without and with the bound's pass), us per
+pair class, the pair table at the HBM rate beside them, ms per polish pass, the wall clock of one call (msm_cost_mplp_pairs_optimise, tables on the
+device) alternated in the same process with the wall clock of the present route of one iteration's solve (both tables fetched, msm_pairwise_icm with
+100 passes), the host literal's ms per sweep, and the energies: the zero labelling, the stand-in's, the decode and the bound after 1 / 5 / 10 / 20 / 30
+sweeps, the polished winner."""
 import argparse
 import json
 import os
@@ -199,6 +206,63 @@ def measure_forbid(ctx, cp_order, sweeps, repeats, polish):
     return out
 
 
+def measure_pairs(ctx, cp_order, sweeps, repeats, polish):
+    inp = problem.pairwise_inputs(6, cp_order, D=1)
+    cf, keep = problem.build_cost(ctx, inp, kind="univariate", rmode=1)
+    cf.get_source_data()
+    keep["target"].prepare_search(wait=True)
+    pairs = inp["pairs"]
+    start = np.zeros(cf.N, dtype=np.int32)
+    table_bytes = cf.P * cf.L ** 2 * 8
+    out = dict(cp_order=cp_order, N=cf.N, P=cf.P, L=cf.L, sweeps=sweeps, polish=polish, repeats=repeats, pair_table_MB=table_bytes / 1e6,
+               table_ms_at_hbm_rate=table_bytes / HBM_BYTES_PER_S * 1e3, hbm_bytes_per_s=HBM_BYTES_PER_S)
+    U = cf.computeUnaryCosts()
+    pc = np.array(cf.computePairwiseCosts())
+    out["energy_start"] = api.mplp_pairs_energy(U, pc, pairs, start)
+    try:
+        cf.mplp_pairs_optimise(start, sweeps=2, polish=2, bounds=True)  # warm-up: code objects, staging blocks, the scratch buffers
+        cf.mplp_pairs_optimise(start, sweeps=2, bound=False)
+    except M.MsmError as e:
+        out["refused"] = str(e)
+        cf.close()
+        return out
+    plain, bounded, polished, host_ms, call_ms, icm_ms, same = [], [], [], [], [], [], True
+    for _ in range(repeats):  # the new call and the present route of one iteration's solve, alternated in this process
+        t0 = time.perf_counter()
+        fast, _ = cf.mplp_pairs_optimise(start, sweeps=sweeps, bound=False)
+        call_ms.append((time.perf_counter() - t0) * 1e3)
+        plain.append(api.mplp_pairs_gpu_stats(ctx))
+        t0 = time.perf_counter()
+        icm = api.pairwise_icm(cf.computeUnaryCosts(), cf.computePairwiseCosts(), pairs, passes=100)
+        icm_ms.append((time.perf_counter() - t0) * 1e3)
+        full, _ = cf.mplp_pairs_optimise(start, sweeps=sweeps, bounds=True)
+        bounded.append(api.mplp_pairs_gpu_stats(ctx))
+        both, pol = cf.mplp_pairs_optimise(start, sweeps=sweeps, polish=polish, bound=False)
+        polished.append(api.mplp_pairs_gpu_stats(ctx))
+        t0 = time.perf_counter()
+        want = api.mplp_pairs_optimise(U, pc, pairs, start, sweeps=sweeps, bounds=True)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+        wpol = api.mplp_pairs_polish(U, pc, pairs, want.labeling, polish=polish)
+        same = (same and equal(fast, want) and equal(full, want) and np.array_equal(pol.labeling, wpol.labeling) and pol.passes_run == wpol.passes_run
+                and pol.energies.tobytes() == wpol.energies.tobytes())
+    out.update(results_equal=bool(same), sweeps_run=full.sweeps_run, classes_per_sweep=plain[0]["classes"], widest_class=plain[0]["widest_class"],
+               energy=full.energy, bound=full.bound, energies=full.energies.tolist(), bounds=full.bounds.tolist(),
+               energy_icm_stand_in=api.mplp_pairs_energy(U, pc, pairs, icm), energy_polished=pol.energy, polish_passes_run=pol.passes_run,
+               polish_energies=pol.energies.tolist(),
+               after_sweeps=[dict(sweeps=n, energy_decode=full.energies[n - 1], bound=full.bounds[n - 1]) for n in ROUND_SWEEPS if n <= sweeps])
+    cf.close()
+    if not same:
+        return out  # no time is reported for a result that is not the host literal's
+    out.update(gpu_kernel_ms_per_sweep=spread([s["kernel_ms"] / max(s["sweeps_run"], 1) for s in plain]),
+               gpu_kernel_ms_per_sweep_with_bounds=spread([s["kernel_ms"] / max(s["sweeps_run"], 1) for s in bounded]),
+               gpu_us_per_class=spread([1e3 * s["kernel_ms"] / max(s["sweeps_run"] * s["classes"], 1) for s in plain]),
+               gpu_ms_per_polish_pass=spread([s["polish_ms"] / max(s["passes_run"], 1) for s in polished]),
+               wall_ms_new_call=spread(call_ms), wall_ms_present_route_fetch_and_icm=spread(icm_ms),
+               host_literal_ms=spread(host_ms), host_literal_ms_per_sweep=spread([ms / max(full.sweeps_run, 1) for ms in host_ms]))
+    out["sweep_over_table_at_hbm_rate"] = out["gpu_kernel_ms_per_sweep"]["median"] / out["table_ms_at_hbm_rate"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweeps", type=int, default=30)
@@ -206,13 +270,16 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--round", action="store_true", help="measure the rounding of the messages instead of the sweeps")
     ap.add_argument("--forbid", action="store_true", help="measure the forbidden-entry reading beside the plain route on a 1e7 stand-in table")
+    ap.add_argument("--pairs", action="store_true", help="measure MPLP over the pair tables of a --regoption=1 level (DESIGN.md 5.20)")
     ap.add_argument("--polish", type=int, default=8)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if M.device_count() < 1:
         raise SystemExit("time_mplp.py: no HIP device is visible (nothing is measured without one)")
     ctx = M.Context(0)
-    if a.forbid:
+    if a.pairs:
+        result = dict(tool="tools/time_mplp.py --pairs", grids=[measure_pairs(ctx, cp, a.sweeps, a.repeats, a.polish) for cp in (4, 3)])
+    elif a.forbid:
         result = dict(tool="tools/time_mplp.py --forbid", grids=[measure_forbid(ctx, cp, a.sweeps, a.repeats, a.polish) for cp in (4, 3)])
     elif a.round:
         result = dict(tool="tools/time_mplp.py --round", grids=[measure_round(ctx, cp, a.mcmc_sweeps, a.repeats, a.polish) for cp in (4, 3)])
