@@ -557,6 +557,28 @@ int msm_mplp_pairs_gpu_stats(msm_ctx *ctx, double stats[6]);
 int msm_fusion_icm_step(const double *unary2 /* N x 2 or NULL */, const double *quads /* P x 4 */, const int32_t *pairs /* P x 2 */, int32_t P,
                         const double *octets /* T x 8 */, const int32_t *triplets /* T x 3 */, int32_t T, int32_t N, int32_t max_passes,
                         int32_t *x /* N, out */);
+/* [host] AN EXTENSION (not newMSM's), in place of the binary solve of one label step of Fusion::optimize (I/Fusion/Fusion.h:198-229: ELC + FastPD, not
+ * reproduced): MPLP over the step's binary problem, by the definitions of msm_mplp_optimise and msm_mplp_round at L = 2.  With
+ * theta_i(x) = unary2[2 i + x] (U[x N + i] in msm_mplp_optimise's layout; NULL: all zero) and the octets as the triplet table (octets[8 t + 4 x_a + 2 x_b
+ * + x_c] is tcosts[((t L + a) L + b) L + c] at L = 2): msm_mplp_optimise from x = 0 for `sweeps` sweeps, then, polish > 0, msm_mplp_round mode 0 over the
+ * final messages with the sweeps' winner handed in.  x (N values 0 / 1) is never worse than x = 0; *bound, the bound after the last sweep run, never
+ * lies above the step's optimum.  Optional: *sweeps_run, *passes_run, *energy (of x), *bound, energies -- 1 + sweeps values (the start, then every
+ * sweep's decode; sweeps a fixed point spares repeat the last) followed, polish > 0, by 1 + polish values (the conditioned decode, then the polish
+ * passes) --, bounds (one per sweep).  Refused before anything is written: what msm_mplp_optimise and msm_mplp_round refuse (a non-finite entry names
+ * its table, the unary one first), sweeps outside 0 .. 1024, polish outside 0 .. 1024.  Only the plain reading: no forbidden entries.  Pair factors
+ * (msm_group_fusion_move's quads) are not taken. */
+int msm_fusion_mplp_step(const double *unary2 /* N x 2 or NULL */, const double *octets /* T x 8 */, const int32_t *triplets /* T x 3 */, int32_t T, int32_t N,
+                         int32_t sweeps, int32_t polish, int32_t *x /* N, out */, int32_t *sweeps_run, int32_t *passes_run, double *energy, double *bound,
+                         double *energies, double *bounds);
+/* msm_fusion_mplp_step on the GPU (an extension), bit for bit in every output: the tables are uploaded, and the sweeps, their decodes, the rounding and
+ * the polish run in one launch of one workgroup with one synchronisation.  MSMHIP_FUSION_MSG=lds|global (for tests) forces where the messages live;
+ * results do not depend on it. */
+int msm_fusion_mplp_step_gpu(msm_ctx *ctx, const double *unary2, const double *octets, const int32_t *triplets, int32_t T, int32_t N, int32_t sweeps,
+                             int32_t polish, int32_t *x, int32_t *sweeps_run, int32_t *passes_run, double *energy, double *bound, double *energies,
+                             double *bounds);
+/* The last msm_fusion_mplp_step_gpu / msm_cost_fusion_mplp_step on the context (an extension): stats[0] ms in the solve launch (HIP events), [1] levels
+ * per sweep, [2] sweeps run, [3] launches the solve took (1; 2 where a fused move's tail kernel completed the octets after the first) */
+int msm_fusion_mplp_gpu_stats(msm_ctx *ctx, double stats[4]);
 /* [host] A STAND-IN for FPD::FastPD on the multi-label pairwise MRF of --regoption=1 (M/mesh_registration.cpp:182-188: computeUnaryCosts,
  * computePairwiseCosts, FastPD): iterated conditional modes over unary[label * N + node] and paircosts[(pair * L + labelB) * L + labelA]
  * (the layouts FastPD reads, I/FastPD/FastPD.h:126,213,224), nodes in ascending order, lowest label on ties, at most max_passes passes.
@@ -670,6 +692,14 @@ int msm_cost_mplp_round(msm_cost *c, int32_t sweeps, int32_t polish, int32_t the
                         double *energy, double *bound, double *energies);
 /* msm_mplp_round(mode 1) over the cost function's own device tables, filled as msm_cost_mplp_optimise fills them; energies: 1 + polish values */
 int msm_cost_mplp_polish(msm_cost *c, int32_t polish, int32_t *labeling, int32_t *passes_run, double *energy, double *energies);
+/* msm_fusion_mplp_step (an extension, in place of I/Fusion/Fusion.h:198-229's binary solve) over the label step (labeling, label) with the tables staying
+ * on the device: the step's 8 T costs are evaluated as msm_cost_triplet_octets evaluates them (fused triclique move, packed strain move or the copied
+ * route) into a device buffer, unary2 is gathered on the device from the cost function's unary table -- filled as msm_cost_mplp_optimise fills it where
+ * the iteration's table is not valid, reused otherwise --, the solve runs behind the step's kernel, one synchronisation.  What msm_fusion_mplp_step
+ * gives over msm_cost_unary_table (unary2[2 i] = U[labeling[i] N + i], unary2[2 i + 1] = U[label N + i]) and msm_cost_triplet_octets, bit for bit.  A
+ * step queued by msm_cost_triplet_octets_prefetch is dropped first.  msm_cost_set_mplp_forbid is ignored: non-finite values are refused. */
+int msm_cost_fusion_mplp_step(msm_cost *c, const int32_t *labeling, int32_t label, int32_t sweeps, int32_t polish, int32_t *x, int32_t *sweeps_run,
+                              int32_t *passes_run, double *energy, double *bound, double *energies, double *bounds);
 /* [host] on != 0: msm_cost_mplp_optimise / _round / _polish read the device triplet table's NaN and +infinity entries as forbidden combinations, as
  * msm_mplp_optimise_forbid_gpu / msm_mplp_round_forbid_gpu do (the strain regulariser produces such entries where a label set lets control points
  * meet); 0, the default: they refuse such a table. */

@@ -717,6 +717,34 @@ inline std::vector<int32_t> fusion_icm_step(int num_nodes, const std::vector<dou
     return x;
 }
 
+// MPLP over the binary problem of one label step (an extension, in place of the ELC + FastPD solve of I/Fusion/Fusion.h:198-229; msm_fusion_mplp_step,
+// DESIGN.md 5.21): x[node] = 1 where the proposed label is taken, never worse than x = 0; bound never above the step's optimum.  energies: the start,
+// every sweep's decode and, polish > 0, the conditioned decode and every polish pass; bounds: one per sweep.
+struct FusionMplp {
+    std::vector<int32_t> x;
+    int32_t sweeps_run = 0, passes_run = 0;
+    double energy = 0.0, bound = 0.0;
+    std::vector<double> energies, bounds;
+    FusionMplp(int num_nodes, int sweeps, int polish)
+        : x((size_t)num_nodes, 0), energies(1 + (size_t)std::max(sweeps, 0) + (polish > 0 ? 1 + (size_t)polish : 0), 0.0), bounds((size_t)std::max(sweeps, 0), 0.0) {}
+};
+// the host literal: unary2 N x 2 (may be empty: no unary costs), octets T x 8
+inline FusionMplp fusion_mplp_step(int num_nodes, const std::vector<double> &unary2, const double *octets, const std::vector<int32_t> &triplets, int sweeps = 10,
+                                   int polish = 8) {
+    FusionMplp r(num_nodes, sweeps, polish);
+    check(msm_fusion_mplp_step(unary2.empty() ? nullptr : unary2.data(), octets, triplets.data(), (int32_t)(triplets.size() / 3), num_nodes, sweeps, polish,
+                               r.x.data(), &r.sweeps_run, &r.passes_run, &r.energy, &r.bound, r.energies.data(), r.bounds.data()));
+    return r;
+}
+// the same in one launch on the GPU (msm_fusion_mplp_step_gpu), bit for bit
+inline FusionMplp fusion_mplp_step_gpu(Context &ctx, int num_nodes, const std::vector<double> &unary2, const double *octets, const std::vector<int32_t> &triplets,
+                                       int sweeps = 10, int polish = 8) {
+    FusionMplp r(num_nodes, sweeps, polish);
+    check(msm_fusion_mplp_step_gpu(ctx.handle(), unary2.empty() ? nullptr : unary2.data(), octets, triplets.data(), (int32_t)(triplets.size() / 3), num_nodes,
+                                   sweeps, polish, r.x.data(), &r.sweeps_run, &r.passes_run, &r.energy, &r.bound, r.energies.data(), r.bounds.data()));
+    return r;
+}
+
 // The stand-in for FPD::FastPD on the multi-label pairwise MRF of --regoption=1 (msm_pairwise_icm: iterated conditional modes): unary L x N,
 // paircosts P x L x L as computePairwiseCosts fills it, labeling in (the start) and out.
 inline void pairwise_icm(const Matrix &unary_costs, const Matrix &paircosts, const std::vector<int32_t> &pairs, int num_nodes, int num_labels,
@@ -851,6 +879,14 @@ public:
         MplpRound r;
         r.energies.assign(2 + (size_t)std::max(polish, 0), 0.0);
         check(msm_cost_mplp_round(h_, sweeps, polish, then_polish ? 1 : 0, labeling.data(), sweeps_run, &r.passes_run, &r.energy, bound, r.energies.data()));
+        return r;
+    }
+    // the label step (labeling, label) solved by MPLP with its octets and unary costs staying on the device (msm_cost_fusion_mplp_step):
+    // what computeUnaryCosts + msm_cost_triplet_octets + msmhip::fusion_mplp_step give, bit for bit
+    FusionMplp fusion_mplp_step(const std::vector<int32_t> &labeling, int label, int sweeps = 10, int polish = 8) {
+        FusionMplp r((int)labeling.size(), sweeps, polish);
+        check(msm_cost_fusion_mplp_step(h_, labeling.data(), label, sweeps, polish, r.x.data(), &r.sweeps_run, &r.passes_run, &r.energy, &r.bound,
+                                        r.energies.data(), r.bounds.data()));
         return r;
     }
     // the polish passes of `labeling` alone over the device tables (msm_cost_mplp_polish)

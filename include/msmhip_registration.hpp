@@ -57,6 +57,11 @@ struct LevelOptions {
     // licence-restricted binary solve (msm_fusion_icm_step, icm_passes passes): the path is exercised as HOCR would, the result is not HOCR's
     bool fusion = false;
     int icm_passes = 5;
+    // with fusion (an extension; what MSMHIP_FUSION=mplp, MSMHIP_FUSION_SWEEPS=n and MSMHIP_FUSION_POLISH=n ask of the executables): the
+    // binary problem of a label step is solved by MPLP -- fusion_sweeps sweeps from x = 0, then the rounding with fusion_polish polish passes -- in one
+    // launch behind the step's own kernel (DiscreteCostFunction::fusion_mplp_step) instead of the stand-in; nothing is queued ahead then
+    bool fusion_mplp = false;
+    int fusion_sweeps = 10, fusion_polish = 8;
     // true (an extension, not newMSM's; what --dopt=MPLP asks for under MSMHIP_MPLP=on): max-product linear programming over the MCMC optimiser's two
     // tables, mciters sweeps per iteration from the zero labelling (DiscreteCostFunction::mplp_optimise: the tables stay on the device)
     bool mplp = false;
@@ -225,6 +230,12 @@ inline LevelResult run_discrete_opt(Context &ctx, const Points &target_xyz, cons
             for (int step = 0; step < 2 * L; ++step) {
                 const int label = step % L;
                 if (!differs(label)) continue;
+                if (o.fusion_mplp) {  // octets, unary gather and the MPLP solve on the device
+                    const FusionMplp r = PhaseClock::timed(clock, "optimiser", [&] { return costfct.fusion_mplp_step(labeling, label, o.fusion_sweeps, o.fusion_polish); });
+                    for (int i = 0; i < N; ++i)
+                        if (r.x[(size_t)i] == 1 && labeling[(size_t)i] != label) labeling[(size_t)i] = label;
+                    continue;
+                }
                 double *E = Ebuf[turn];
                 turn ^= 1;
                 PhaseClock::timed(clock, "fusion_moves", [&] { check(msm_cost_triplet_octets(costfct.handle(), labeling.data(), label, E)); });

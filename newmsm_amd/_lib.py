@@ -156,6 +156,10 @@ SIGNATURES = {
     "msm_mplp_pairs_polish_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_dp, c_dp]),
     "msm_mplp_pairs_gpu_stats": (C.c_int, [_VP, c_dp]),
     "msm_fusion_icm_step": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip]),
+    "msm_fusion_mplp_step": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp]),
+    "msm_fusion_mplp_step_gpu": (C.c_int, [_VP, c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp]),
+    "msm_fusion_mplp_gpu_stats": (C.c_int, [_VP, c_dp]),
+    "msm_cost_fusion_mplp_step": (C.c_int, [_VP, c_ip, C.c_int32, C.c_int32, C.c_int32, c_ip, c_ip, c_ip, c_dp, c_dp, c_dp, c_dp]),
     "msm_pairwise_icm": (C.c_int, [c_dp, c_dp, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip]),
     "msm_nearest_neighbour": (C.c_int, [_VP, c_dp, C.c_int32, c_dp, C.c_int32, c_dp, c_dp, c_dp]),
     "msm_cost_create": (_VP, [_VP, C.POINTER(CostParams)]),

@@ -1192,6 +1192,65 @@ def fusion_icm_step(unary2, octets, triplets, passes=5, quads=None, pairs=None):
     return x
 
 
+FusionMplp = collections.namedtuple("FusionMplp", "x sweeps_run passes_run energy bound energies bounds")
+
+
+def _fusion_mplp_outputs(N, sweeps, polish):
+    """the output arrays of the msm_fusion_mplp_step family and their pointers; energies: 1 + sweeps values, then 1 + polish where polish > 0"""
+    S, P = max(int(sweeps), 0), max(int(polish), 0)
+    out = dict(x=np.zeros(int(N), dtype=np.int32), run=C.c_int32(-1), passes=C.c_int32(-1), energy=C.c_double(np.nan), bound=C.c_double(np.nan),
+               energies=np.full(1 + S + (1 + P if P > 0 else 0), np.nan), bounds=np.full(S, np.nan))
+    return out, [out["x"].ctypes.data_as(c_ip), C.byref(out["run"]), C.byref(out["passes"]), C.byref(out["energy"]), C.byref(out["bound"]),
+                 out["energies"].ctypes.data_as(c_dp), out["bounds"].ctypes.data_as(c_dp)]
+
+
+def _fusion_mplp_result(out):
+    return FusionMplp(out["x"], out["run"].value, out["passes"].value, out["energy"].value, out["bound"].value, out["energies"], out["bounds"])
+
+
+def _fusion_mplp_tables(unary2, octets, triplets):
+    if unary2 is None or np.ndim(unary2) == 0:
+        assert unary2 is None or int(unary2) > 0
+        u, pu, N = None, C.cast(None, c_dp), (None if unary2 is None else int(unary2))
+    else:
+        u = np.ascontiguousarray(unary2, dtype=np.float64)
+        N, pu = u.shape[0], u.ctypes.data_as(c_dp)
+        assert u.shape == (N, 2)
+    tr = np.ascontiguousarray(triplets if triplets is not None else np.zeros((0, 3)), dtype=np.int32).reshape(-1, 3)
+    e = np.ascontiguousarray(octets if octets is not None else np.zeros((0, 8)), dtype=np.float64)
+    T = tr.shape[0]
+    assert e.size == 8 * T
+    return (u, e, tr), (pu, e.ctypes.data_as(c_dp), tr.ctypes.data_as(c_ip), T), N
+
+
+def fusion_mplp_step(unary2, octets, triplets, sweeps=10, polish=8, N=None):
+    """msm_fusion_mplp_step [host]: MPLP over the binary problem of one label step (an extension) -- api.mplp_optimise from x = 0 and,
+    polish > 0, api.mplp_round(mode 0) at L = 2 over the transposed unary2 (N x 2: current, proposed; None with N given: no unary costs) and the octets
+    (T x 8).  Returns FusionMplp(x, sweeps_run, passes_run, energy, bound, energies, bounds): x is 1 where the proposed label is taken and never worse
+    than x = 0 (energies[0]); bound is a lower bound on the step's optimum."""
+    keep, head, n = _fusion_mplp_tables(unary2, octets, triplets)
+    N = n if n is not None else int(N)
+    out, tail = _fusion_mplp_outputs(N, sweeps, polish)
+    check(lib().msm_fusion_mplp_step(*head, N, int(sweeps), int(polish), *tail))
+    return _fusion_mplp_result(out)
+
+
+def fusion_mplp_step_gpu(ctx, unary2, octets, triplets, sweeps=10, polish=8, N=None):
+    """msm_fusion_mplp_step_gpu: fusion_mplp_step in one launch of one workgroup on the GPU; the same FusionMplp, bit for bit"""
+    keep, head, n = _fusion_mplp_tables(unary2, octets, triplets)
+    N = n if n is not None else int(N)
+    out, tail = _fusion_mplp_outputs(N, sweeps, polish)
+    check(lib().msm_fusion_mplp_step_gpu(ctx.h, *head, N, int(sweeps), int(polish), *tail))
+    return _fusion_mplp_result(out)
+
+
+def fusion_mplp_gpu_stats(ctx):
+    """msm_fusion_mplp_gpu_stats of the context's last GPU label-step solve: dict(kernel_ms, levels_per_sweep, sweeps_run, launches)"""
+    s = np.zeros(4)
+    check(lib().msm_fusion_mplp_gpu_stats(ctx.h, s.ctypes.data_as(c_dp)))
+    return dict(kernel_ms=float(s[0]), levels_per_sweep=int(s[1]), sweeps_run=int(s[2]), launches=int(s[3]))
+
+
 def pairwise_icm(unary, paircosts, pairs, labeling=None, passes=100):
     """msm_pairwise_icm: the stand-in solve of the multi-label pairwise MRF of --regoption=1 (iterated conditional modes; NOT FastPD).
     unary L x N, paircosts P x L x L flat as computePairwiseCosts returns it, pairs P x 2; returns the labeling (N)."""
@@ -1437,6 +1496,15 @@ class DiscreteCostFunction:
         check(lib().msm_cost_mplp_round(self.h, int(sweeps), int(polish), int(bool(then_polish)), tail[0], C.byref(run), tail[1], tail[2], C.byref(bound),
                                         tail[3]))
         return MplpRound(out["lab"], out["run"].value, out["energy"].value, out["energies"]), run.value, bound.value
+
+    def fusion_mplp_step(self, labeling, label, sweeps=10, polish=8):
+        """msm_cost_fusion_mplp_step: the label step (labeling, label) solved by MPLP with octets and unary costs staying on the device; the FusionMplp
+        that unary_table() + triplet_octets(labeling, label) + api.fusion_mplp_step give, bit for bit"""
+        lab = np.ascontiguousarray(labeling, dtype=np.int32)
+        assert lab.shape == (self.N,)
+        out, tail = _fusion_mplp_outputs(self.N, sweeps, polish)
+        check(lib().msm_cost_fusion_mplp_step(self.h, lab.ctypes.data_as(c_ip), int(label), int(sweeps), int(polish), *tail))
+        return _fusion_mplp_result(out)
 
     def mplp_polish(self, labeling, polish=8):
         """msm_cost_mplp_polish: api.mplp_round(mode=1) over the cost function's own device tables"""

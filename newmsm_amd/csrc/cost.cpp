@@ -457,6 +457,7 @@ int msm_cost_set_triplets(msm_cost *c, const int32_t *triplets, int32_t T) {
     MSM_TRY(ctx_sync(c->ctx));
     c->triplets.assign(triplets, triplets + 3 * (size_t)T);
     c->move_valid = false;
+    c->fusion_plan.reset();
     if (T > 0) MSM_TRY(c->d_triplets.upload(c->triplets.data(), c->triplets.size(), c->ctx));
     return MSM_OK;
 }

@@ -40,6 +40,11 @@ struct msm_cost {
     bool cp_conn_valid = false;
     DevBuf<int32_t> d_labeling;
     DevBuf<double> d_clique_out;
+    // msm_cost_fusion_mplp_step: the step's octets, its labeling and what the triplet list fixes (a FusionMplpPlan; built on first use, dropped by
+    // msm_cost_set_triplets)
+    DevBuf<double> d_step_octets;
+    DevBuf<int32_t> d_step_labeling;
+    std::shared_ptr<void> fusion_plan;
     DevBuf<double> d_ho_vals, d_ho_big;
     DevBuf<unsigned> d_ho_pending, d_ho_count;
     // fused fusion move of the HO classes (move_kernels.hip): per bin slot data prepared once per get_source_data()

@@ -190,7 +190,8 @@ struct msm_ctx {
     std::shared_ptr<void> mcmc_scratch;       // mcmc.cpp: device buffers, events and counters of the Monte Carlo sweeps, kept between calls
     std::shared_ptr<void> mplp_scratch;       // mplp.cpp: device buffers, events and counters of the MPLP sweeps, kept between calls
     std::shared_ptr<void> mplp_pairs_scratch;  // mplp_pairs.cpp: the same for MPLP over the pair tables
-    int mcmc_draw = 0;                        // msm_ctx_set_mcmc_draw: 0 the GPU sweeps take their proposals from the host's stream, 1 they are drawn on the device
+    std::shared_ptr<void> fusion_mplp_scratch;  // fusion_mplp.cpp: device buffers, events and counters of MPLP over a label step, kept between calls
+    int mcmc_draw = 0;                   // msm_ctx_set_mcmc_draw: 0 the GPU sweeps take their proposals from the host's stream, 1 they are drawn on the device
     std::shared_ptr<void> features_scratch;  // features.cpp: device buffers of msm_level_features, kept between calls
     // msm_ctx_time_queries: events around the search kernel of the host-array query entry points
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;

@@ -6,8 +6,10 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 #include "cost_internal.hpp"
+#include "fusion_mplp.hpp"
 
 using namespace msm;
 
@@ -49,6 +51,10 @@ struct StepCall {
     int32_t label;
     double *E;
     bool single;
+    // msm_cost_fusion_mplp_step: the costs stay on the device, in dev (8 x T; E is not written), and behind() queues the solve that reads them on the
+    // context's stream -- behind the step's kernel, ahead of the step's one synchronisation; again: once more, after a fused move's tail kernel
+    double *dev = nullptr;
+    const std::function<int(bool again)> *behind = nullptr;
 };
 
 // ---- fused fusion move of the HO classes (move_kernels.hip) ----
@@ -137,7 +143,7 @@ int deliver(msm_cost *c, const CliqueArgs &a, const StepCall &call, bool hint, b
     msm_ctx *ctx = c->ctx;
     d.in_pad = (sizeof(int32_t) * (size_t)a.N + 255) & ~(size_t)255;
     d.out_bytes = sizeof(double) * (call.single ? 1 : 8) * (size_t)a.T;
-    d.out_dev = static_cast<double *>(ctx_mapped(ctx, call.E, d.out_bytes));
+    d.out_dev = call.dev ? call.dev : static_cast<double *>(ctx_mapped(ctx, call.E, d.out_bytes));
     d.direct = d.out_dev != nullptr;
     if (hint || (d.direct && !pin_anyway)) return MSM_OK;
     MSM_TRY(ctx_io_pinned(ctx, d.in_pad + d.out_bytes, &d.pin));
@@ -280,7 +286,7 @@ int label_step(msm_cost *c, const CliqueArgs &a, const StepCall &call, bool hint
     // the caller's own mapped array, and never in the single form.  Any other hint is silently ignored: the call itself will do everything.
     if (hint && !((fused || strain) && packed && d.direct && !call.single)) return MSM_OK;
     const bool general = !fused && !strain;
-    if (general) d.direct = false, d.staged_copy = true;  // whatever E is
+    if (general && !call.dev) d.direct = false, d.staged_copy = true;  // whatever E is
     if (d.staged_copy) {
         MSM_HIP(c->d_clique_out.ensure((size_t)8 * a.T));  // (also large enough for the T values of a single-combination call)
         d.out_dev = c->d_clique_out.p;
@@ -296,13 +302,20 @@ int label_step(msm_cost *c, const CliqueArgs &a, const StepCall &call, bool hint
     if (d.staged_copy) MSM_HIP(hipMemcpyAsync((char *)d.pin + d.in_pad, d.out_dev, d.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     c->counters[2] += (int64_t)(d.out_bytes / sizeof(double));
     if (hint) return queue_step(c, call, a, fused ? &m : nullptr, lab, d);
+    if (call.behind) MSM_TRY((*call.behind)(false));
     if (general) {
         const int st = check_status(ctx, "computeTripletCost");  // synchronises
-        std::memcpy(call.E, (char *)d.pin + d.in_pad, d.out_bytes);
+        if (!call.dev) std::memcpy(call.E, (char *)d.pin + d.in_pad, d.out_bytes);
         return st;
     }
     MSM_TRY(ctx_sync(ctx));
-    return finish_step(c, a, fused ? &m : nullptr, labp, d, call.E);
+    const int64_t tails = c->move_tails;
+    MSM_TRY(finish_step(c, a, fused ? &m : nullptr, labp, d, call.E));
+    if (call.behind && c->move_tails != tails) {  // rare: the tail kernel completed the octets after the solve had read them -- the solve runs again
+        MSM_TRY((*call.behind)(true));
+        MSM_TRY(ctx_sync(ctx));
+    }
+    return MSM_OK;
 }
 
 int triplet_octets_impl(msm_cost *c, const int32_t *labeling, int32_t label, double *E, bool hint) {
@@ -339,6 +352,43 @@ int msm_cost_triplet_octets(msm_cost *c, const int32_t *labeling, int32_t label,
 int msm_cost_triplet_octets_prefetch(msm_cost *c, const int32_t *labeling, int32_t label, double *E) {
     if (!c || !labeling || !E) return fail(MSM_ERR_INVALID, "msm_cost_triplet_octets_prefetch: null argument");
     return triplet_octets_impl(c, labeling, label, E, true);
+}
+
+// MPLP over the binary problem of the label step (labeling, label) with nothing but the results leaving the device: the step's kernel
+// -- whichever form label_step chooses -- writes its 8 T costs into d_step_octets, k_fusion_mplp gathers theta from the unary table and solves behind it,
+// one synchronisation.  A step queued ahead is dropped first (clique_args), by the rule of every entry point but the matching msm_cost_triplet_octets.
+int msm_cost_fusion_mplp_step(msm_cost *c, const int32_t *labeling, int32_t label, int32_t sweeps, int32_t polish, int32_t *x, int32_t *sweeps_run,
+                              int32_t *passes_run, double *energy, double *bound, double *energies, double *bounds) {
+    const char *what = "msm_cost_fusion_mplp_step";
+    if (!c || !labeling || !x) return fail(MSM_ERR_INVALID, "%s: null argument", what);
+    if (!c->cpgrid || c->L <= 0 || c->triplets.empty()) return fail(MSM_ERR_STATE, "%s: meshes, labels and triplets must be set first", what);
+    const int N = c->cpgrid->V, T = (int)(c->triplets.size() / 3);
+    MSM_TRY(fusion_mplp_check(what, c->triplets.data(), N, T, sweeps, polish));
+    if (label < 0 || label >= c->L) return fail(MSM_ERR_INVALID, "label %d out of range", label);
+    msm_ctx *ctx = c->ctx;
+    MSM_TRY(drop_pending_move(c));  // a step queued ahead that nobody took
+    if (!c->table_valid) {  // computeUnaryCosts as msm_cost_mplp_optimise runs it; an iteration's table serves all its label steps
+        MSM_TRY(msm_cost_unary_table_async(c));
+        MSM_TRY(check_status(ctx, "computeUnaryCosts"));
+    }
+    CliqueArgs a;  // (after the table: it recomputes the label rotations the clique kernels read)
+    MSM_TRY(clique_args(c, true, false, a));
+    if (!c->fusion_plan) {
+        std::shared_ptr<FusionMplpPlan> plan = std::make_shared<FusionMplpPlan>();
+        MSM_TRY(fusion_mplp_build_plan(ctx, c->triplets.data(), N, T, *plan));
+        c->fusion_plan = plan;
+    }
+    const FusionMplpPlan &plan = *static_cast<const FusionMplpPlan *>(c->fusion_plan.get());
+    if (c->d_step_octets.ensure((size_t)8 * T) != hipSuccess) return stage_alloc_failed(sizeof(double) * 8 * (size_t)T);
+    MSM_TRY(c->d_step_labeling.upload(labeling, (size_t)N, ctx));
+    const std::function<int(bool)> behind = [&](bool again) {
+        return fusion_mplp_queue(ctx, what, plan, nullptr, c->d_U.p, c->d_step_labeling.p, label, a.L, c->d_step_octets.p, sweeps, polish, again);
+    };
+    StepCall call{labeling, label, nullptr, false};
+    call.dev = c->d_step_octets.p;
+    call.behind = &behind;
+    MSM_TRY(label_step(c, a, call, false));
+    return fusion_mplp_collect(ctx, what, {x, sweeps_run, passes_run, energy, bound, energies, bounds});
 }
 
 int msm_cost_prefetch_stats(msm_cost *c, int64_t *taken, int64_t *dropped) {

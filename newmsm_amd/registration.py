@@ -48,7 +48,7 @@ class ProductOps:
     """The calls of the level loop on the MI355X path (every method is one or two C-ABI calls)."""
 
     def __init__(self, ctx, mcmc_gpu=False, features_gpu=False, mcmc_draw_gpu=False, mplp_gpu=True, mplp_round=False, mplp_polish=8,
-                 mplp_forbid=False, mplp_pairs=False):
+                 mplp_forbid=False, mplp_pairs=False, fusion_mplp=False, fusion_sweeps=10, fusion_polish=8):
         """features_gpu: the level loops prepare a level's features for all data sets through ONE call (level_features_batch: msm_level_features, with
         the masked list surgery and create_exclusion on the device) instead of the chain of calls of level_features / finish_features -- the same
         bytes (what MSMHIP_FEATURES=gpu asks of the executables).
@@ -66,8 +66,19 @@ class ProductOps:
         (msm_cost_set_mplp_forbid) and on the host route (msm_mplp_optimise_forbid) alike; what MSMHIP_MPLP_FORBID=on asks of the executables
         mplp_pairs: what MSMHIP_MPLP_PAIRS=on asks of the executables -- --dopt=MPLP with --regoption=1 runs as optimiser "mplp_pairs" (MPLP over the
         unary and pair tables; config.levels_from_config(mplp_pairs=True) names it), and run_discrete_level refuses that optimiser without it.  That branch follows mplp_gpu (tables and sweeps on
-        the device: msm_cost_mplp_pairs_optimise) and, with mplp_round, polishes the sweeps' winner with mplp_polish passes; it ignores mplp_forbid"""
+        the device: msm_cost_mplp_pairs_optimise) and, with mplp_round, polishes the sweeps' winner with mplp_polish passes; it ignores mplp_forbid
+        fusion_mplp: the binary problem of every label step of run_discrete_level(optimiser="fusion") is solved by MPLP (an extension, DESIGN.md 5.21:
+        fusion_sweeps sweeps from x = 0, then the rounding with fusion_polish polish passes) instead of the stand-in fusion_step -- with mplp_gpu in one
+        launch behind the step's own kernel (msm_cost_fusion_mplp_step), without it by the host literal over the fetched octets
+        (msm_fusion_mplp_step): the same labellings; what MSMHIP_FUSION=mplp, MSMHIP_FUSION_SWEEPS=n and MSMHIP_FUSION_POLISH=n ask of the executables.
+        Groupwise label steps (pair factors) keep the stand-in."""
         self.ctx = ctx
+        self.fusion_mplp = bool(fusion_mplp)
+        self.fusion_sweeps, self.fusion_polish = int(fusion_sweeps), int(fusion_polish)
+        if not 1 <= self.fusion_sweeps <= 256:
+            raise ValueError("fusion_sweeps: the sweeps of a label step's MPLP solve are a whole number from 1 to 256")
+        if not 0 <= self.fusion_polish <= 64:
+            raise ValueError("fusion_polish: the polish passes of a label step's MPLP solve are a whole number from 0 to 64")
         self.mplp_forbid = bool(mplp_forbid)
         self.mplp_pairs = bool(mplp_pairs)
         self.mplp_round = bool(mplp_round)
@@ -218,6 +229,10 @@ class ProductOps:
     def mplp_pairs_solve(self, unary, paircosts, pairs, labeling, sweeps):
         return _mplp_pairs_host(unary, paircosts, pairs, labeling, sweeps, self.mplp_polish if self.mplp_round else 0)
 
+    def fusion_mplp_step(self, unary2, octets, triplets):
+        """the label step's binary problem by the host literal of DESIGN.md 5.21: api.FusionMplp"""
+        return api.fusion_mplp_step(unary2, octets, triplets, sweeps=self.fusion_sweeps, polish=self.fusion_polish)
+
     def fusion_step(self, unary2, octets, triplets, passes, quads=None, pairs=None):
         return api.fusion_icm_step(unary2, octets, triplets, passes, quads=quads, pairs=pairs)
 
@@ -311,6 +326,9 @@ class _ProductCost:
 
     def mplp_round(self, labeling, sweeps, polish):
         return self.cf.mplp_round(labeling, sweeps=sweeps, polish=polish, then_polish=True)[0].labeling
+
+    def fusion_mplp_step(self, labeling, label, sweeps, polish):
+        return self.cf.fusion_mplp_step(labeling, label, sweeps=sweeps, polish=polish)
 
     def mplp_pairs_optimise(self, labeling, sweeps, polish):
         return self.cf.mplp_pairs_optimise(labeling, sweeps=sweeps, polish=polish, bound=False)[0].labeling
@@ -500,7 +518,7 @@ def usable_transformed(trans_xyz, in_xyz):
 def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source_tri, src_feat, sph_reg, cp_order, *, sg_order=None,
                        iters=3, mciters=200, mcparam=0.8, seed=0, kind="univariate", simmeasure=2, rmode=3, labeldist=0.5,
                        rescale_labels=False, cost_params=None, timings=None, cp_start=None, in_weight=None, ref_weight=None,
-                       optimiser="mcmc", icm_passes=5, converge=False, anat=None, speculate=True, mcmc_chains=1):
+                       optimiser="mcmc", icm_passes=5, converge=False, anat=None, speculate=True, mcmc_chains=1, fusion_trace=None):
     """Runs `iters` iterations of run_discrete_opt for one level.  optimiser: "mcmc" -- the reference's Monte Carlo optimiser over the
     unary and T x L^3 triplet tables (M/mcmc_opt.h:31-134) -- or "fusion": the label loop of Fusion::optimize (I/Fusion/Fusion.h:136-229: two
     sweeps over the labels, per label step 2 N unary and 8 T triplet costs -- ONE fusion-move call on the MI355X path --, nodes that the
@@ -528,6 +546,10 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
     (api.chain_seeds), and keeps the labelling with the lowest table energy (ops' cost.mcmc_optimise_chains with ops.mcmc_gpu, ops.mcmc_chains
     over the fetched tables without: the same labelling); 1 is the single run.
     speculate (fusion loop): queue the next label step's evaluations while the host solves the current one (ops' cost.prefetch_octets, if it has one).
+    Where ops.fusion_mplp is set (an extension) the binary problem of a label step is solved by MPLP instead of ops.fusion_step: with
+    ops.mplp_gpu on the device behind the step's own kernel (the ops' cost.fusion_mplp_step; nothing is left for the host to solve meanwhile, so no
+    step is queued ahead), otherwise by the host literal over the fetched octets (ops.fusion_mplp_step), speculation as before -- the same
+    labellings on either route, with or without speculate.  fusion_trace (optional list) receives (iteration, label, api.FusionMplp) per solved step.
     anat (rmode 4 / 5, aMSM): dict(order, in_anat, in_mesh, ref_anat, ref_mesh) -- --anatgrid of this level and the input / reference anatomical
     surfaces (V x 3) with the spheres (ops meshes) whose vertices they share (MESHES[0] / MESHES[1]).  initialize_level (M/mesh_registration.cpp:
     91-99) then prepares the anatomical regulariser: resample_anatomy (:250-332: the control grid retessellated to anatomical resolution with the
@@ -613,8 +635,16 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
             L = len(labels)
             steps = [(sweep, label) for sweep in range(2) for label in range(L)]
             prefetch = getattr(cost, "prefetch_octets", None) if speculate else None
+            fusion_mplp = bool(getattr(ops, "fusion_mplp", False))
+            fusion_gpu = fusion_mplp and getattr(ops, "mplp_gpu", False) and hasattr(cost, "fusion_mplp_step")  # msm_cost_fusion_mplp_step
             for k, (sweep, label) in enumerate(steps):
                 if not np.any(labeling != label):
+                    continue
+                if fusion_gpu:  # --- octets, unary gather and the MPLP solve in one go on the device
+                    r = timed("optimiser", cost.fusion_mplp_step, labeling, label, ops.fusion_sweeps, ops.fusion_polish)
+                    if fusion_trace is not None:
+                        fusion_trace.append((it, label, r))
+                    labeling = np.where((r.x == 1) & (labeling != label), label, labeling).astype(np.int32)
                     continue
                 octets = timed("fusion_moves", cost.triplet_octets, labeling, label)
                 if prefetch is not None:
@@ -625,7 +655,13 @@ def run_discrete_level(ops, target_xyz, target_tri, ref_feat, source_xyz, source
                     if nxt is not None:
                         timed("fusion_prefetch", prefetch, labeling, nxt)
                 unary2 = np.stack([unary[labeling, nodes], unary[label]], axis=1)
-                x = timed("optimiser", ops.fusion_step, unary2, octets, triplets, icm_passes)
+                if fusion_mplp:  # --- the same solve by the host literal
+                    r = timed("optimiser", ops.fusion_mplp_step, unary2, octets, triplets)
+                    if fusion_trace is not None:
+                        fusion_trace.append((it, label, r))
+                    x = r.x
+                else:
+                    x = timed("optimiser", ops.fusion_step, unary2, octets, triplets, icm_passes)
                 labeling = np.where((x == 1) & (labeling != label), label, labeling).astype(np.int32)
         elif mplp_pairs_gpu:  # --- MPLP over the pair tables, tables and sweeps on the device: the labeling of the branch below, bit for bit
             labeling = timed("optimiser", cost.mplp_pairs_optimise, labeling, mciters, ops.mplp_polish if getattr(ops, "mplp_round", False) else 0)

@@ -284,7 +284,37 @@ bool mplp_round_setting(bool mplp, int *polish) {
     return env != nullptr;
 }
 
+// MSMHIP_FUSION=mplp: the binary problem of every label step of a --dopt=HOCR level is solved by MPLP on the device (an extension: DESIGN.md section
+// 5.21) instead of the stand-in; icm or unset: the stand-in, today's bytes.  MSMHIP_FUSION_SWEEPS=n (1 ... 256, default 10) and
+// MSMHIP_FUSION_POLISH=n (0 ... 64, default 8) set its sweeps and polish passes and need MSMHIP_FUSION=mplp.  Returns whether it is on.
+bool fusion_mplp_setting(int *sweeps, int *polish) {
+    const char *env = std::getenv("MSMHIP_FUSION");
+    if (env && std::string(env) != "mplp" && std::string(env) != "icm")
+        throw Error(MSM_ERR_INVALID, std::string("MSMHIP_FUSION=") + env + ": the binary solve of a label step is the stand-in (icm, or unset) or MPLP on the device (mplp)");
+    const bool on = env && std::string(env) == "mplp";
+    *sweeps = 10, *polish = 8;
+    const struct {
+        const char *name, *what;
+        long lo, hi;
+        int *value;
+    } counts[2] = {{"MSMHIP_FUSION_SWEEPS", "sweeps", 1, 256, sweeps}, {"MSMHIP_FUSION_POLISH", "polish passes", 0, 64, polish}};
+    for (const auto &c : counts) {
+        const char *text = std::getenv(c.name);
+        if (!text) continue;
+        if (!on) throw Error(MSM_ERR_INVALID, std::string(c.name) + "=" + text + " sets the " + c.what + " of a label step's MPLP solve: it needs MSMHIP_FUSION=mplp");
+        char *end = nullptr;
+        const long n = std::strtol(text, &end, 10);
+        if (end == text || *end != '\0' || n < c.lo || n > c.hi)
+            throw Error(MSM_ERR_INVALID, std::string(c.name) + "=" + text + ": the number of " + c.what + " must be a whole number from " + std::to_string(c.lo) + " to " +
+                                             std::to_string(c.hi));
+        *c.value = (int)n;
+    }
+    return on;
+}
+
 int run_pairwise(const Options &o, const Formats &fmt, int device) {
+    int fusion_sweeps = 10, fusion_polish = 8;
+    const bool fusion_mplp = fusion_mplp_setting(&fusion_sweeps, &fusion_polish);
     const int mcmc_chains = mcmc_chains_setting();
     const bool mcmc_draw_gpu = mcmc_draw_gpu_setting();
     for (const char *flag : {"inmesh", "indata", "refdata"})
@@ -320,6 +350,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
         for (LevelSpec &lv : levels) lv.options.features_gpu = true;
     for (LevelSpec &lv : levels) lv.options.mcmc_chains = mcmc_chains;
     for (LevelSpec &lv : levels) lv.options.mplp_round = mplp_round, lv.options.mplp_polish = mplp_polish, lv.options.mplp_forbid = mplp_forbid;
+    for (LevelSpec &lv : levels) lv.options.fusion_mplp = fusion_mplp, lv.options.fusion_sweeps = fusion_sweeps, lv.options.fusion_polish = fusion_polish;
     const Exclusion excl = exclusion_from_config(cfg);
     note_skipped(skipped);
     if (levels.empty()) throw Error(MSM_ERR_INVALID, "newmsm: the configuration holds no DISCRETE level");
@@ -345,6 +376,7 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
     if (o.has("verbose") && mcmc_draw_gpu) std::cout << "MCMC proposals drawn on the GPU." << std::endl;
     if (o.has("verbose") && mcmc_chains > 1) std::cout << "MCMC with " << mcmc_chains << " chains per iteration." << std::endl;
     if (o.has("verbose") && features_gpu_enabled()) std::cout << "Level features in one call on the GPU." << std::endl;
+    if (o.has("verbose") && fusion_mplp) std::cout << "Label steps solved by MPLP on the GPU (" << fusion_sweeps << " sweeps, " << fusion_polish << " polish passes)." << std::endl;
     const MultiresResult res = run_multiresolutions(ctx, ixyz, itri, idata, rxyz, rtri, rdata, D, levels, varnorm, nullptr, anat ? &in_anat : nullptr,
                                                     anat ? &ref_anat : nullptr, weighted ? &in_w : nullptr, in_wr, weighted ? &ref_w : nullptr, ref_wr,
                                                     o.get("trans").empty() ? nullptr : &trans, excl, inorm);
@@ -374,6 +406,9 @@ int run_pairwise(const Options &o, const Formats &fmt, int device) {
 }
 
 int run_groupwise(const Options &o, const Formats &fmt, int device) {
+    int fusion_sweeps = 10, fusion_polish = 8;
+    if (fusion_mplp_setting(&fusion_sweeps, &fusion_polish))
+        throw Error(MSM_ERR_INVALID, "MSMHIP_FUSION=mplp solves label steps of triplets alone: a --groupwise run (pair factors between the subjects) keeps the stand-in; unset it");
     const bool group_mcmc = group_mcmc_setting();
     const int mcmc_chains = group_mcmc ? mcmc_chains_setting() : 1, mcmc_passes = group_mcmc ? group_mcmc_passes_setting() : 1;
     const bool mcmc_draw_gpu = group_mcmc && group_mcmc_draw_setting();

@@ -179,6 +179,31 @@ def mplp_round_setting():
     return text == "on", n
 
 
+def fusion_mplp_setting():
+    """MSMHIP_FUSION=mplp: the binary problem of every label step of a --dopt=HOCR level is solved by MPLP on the device (an extension: DESIGN.md section
+    5.21) instead of the stand-in; icm or unset: the stand-in, today's bytes.  MSMHIP_FUSION_SWEEPS=n (1 ... 256, default 10) and MSMHIP_FUSION_POLISH=n
+    (0 ... 64, default 8) set its sweeps and polish passes and need MSMHIP_FUSION=mplp.  Returns (on, sweeps, polish); anything else ends the run with a
+    message and exit status 1."""
+    text = os.environ.get("MSMHIP_FUSION")
+    if text is not None and text not in ("mplp", "icm"):
+        raise SystemExit("MSMHIP_FUSION=%s: the binary solve of a label step is the stand-in (icm, or unset) or MPLP on the device (mplp)" % text)
+    on = text == "mplp"
+    values = []
+    for name, what, lo, hi, default in (("MSMHIP_FUSION_SWEEPS", "sweeps", 1, 256, 10), ("MSMHIP_FUSION_POLISH", "polish passes", 0, 64, 8)):
+        t, n = os.environ.get(name), default
+        if t is not None:
+            if not on:
+                raise SystemExit("%s=%s sets the %s of a label step's MPLP solve: it needs MSMHIP_FUSION=mplp" % (name, t, what))
+            try:
+                n = int(t)
+            except ValueError:
+                n = lo - 1
+            if not lo <= n <= hi:
+                raise SystemExit("%s=%s: the number of %s must be a whole number from %d to %d" % (name, t, what, lo, hi))
+        values.append(n)
+    return on, values[0], values[1]
+
+
 def mcmc_gpu_enabled():
     """MSMHIP_MCMC=gpu: the --dopt=MCMC levels keep both cost tables on the device and run the optimiser's sweeps there (the same labelings)"""
     return os.environ.get("MSMHIP_MCMC", "") == "gpu"
@@ -328,7 +353,10 @@ def main(argv):
     surf_ext, data_ext = output_formats(a.format)
     if surf_ext == ".vtk":
         raise SystemExit("register_files.py: VTK output is not written here (GIFTI, ASCII, ASCII_MAT)")
+    fusion_mplp, fusion_sweeps, fusion_polish = fusion_mplp_setting()
     if a.groupwise:
+        if fusion_mplp:
+            raise SystemExit("MSMHIP_FUSION=mplp solves label steps of triplets alone: a --groupwise run (pair factors between the subjects) keeps the stand-in; unset it")
         return main_groupwise(a, surf_ext, data_ext, group_mcmc, chains, draw_gpu)
     mplp_round, mplp_polish = mplp_round_setting()
     mplp_forbid = mplp_forbid_setting()
@@ -368,7 +396,7 @@ def main(argv):
             print("MCMC with %d chains per iteration." % chains)
         if features_gpu_enabled():
             print("Level features in one call on the GPU.")
-    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish, mplp_forbid=mplp_forbid, mplp_pairs=mplp_pairs), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
+    reg, level_regs, energies = registration.run_multiresolution(registration.ProductOps(ctx, mcmc_gpu=mcmc_gpu_enabled(), features_gpu=features_gpu_enabled(), mcmc_draw_gpu=draw_gpu, mplp_round=mplp_round, mplp_polish=mplp_polish, mplp_forbid=mplp_forbid, mplp_pairs=mplp_pairs, fusion_mplp=fusion_mplp, fusion_sweeps=fusion_sweeps, fusion_polish=fusion_polish), ixyz, itri, idata, rxyz, rtri, rdata, levels, **run_kw, **cfw)
     out = a.out
     meshio.save_surface(out + "sphere.reg" + surf_ext, reg, itri)                                   # transform
     last_xyz, last_tri = M.make_mesh_from_icosa(levels[-1]["data_order"])
