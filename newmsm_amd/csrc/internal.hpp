@@ -60,8 +60,9 @@ static_assert(sizeof(TriRec) == 128, "TriRec must be 128 bytes");
 //   pieces 0-2  the three edge planes (float4: inward unit normal, acceptance threshold)      -- ray_table.cpp
 //   pieces 3-8  the vertices v0,v1,v2 (9 doubles) and, on single-feature meshes, the feature at them (3 doubles)
 // so that a wavefront can fetch the records of its 64 samples with 9 load instructions that touch ~2 lines per
-// record (lanes of one instruction read neighbouring pieces) instead of 9 x 64 lines.  Built on the GPU
-// (kernels.hip: k_build_raytri).
+// record (lanes of one instruction read neighbouring pieces) instead of 9 x 64 lines.  k_unary_rays reads pieces 3-8 that way by lane
+// pairs (two neighbouring lanes take two adjacent pieces of one record in each instruction, at 32-bit byte offsets from the table's base:
+// 16 * kRayPieces * kRayMaxTris fits 32 bits), pieces 0-2 lane by lane.  Built on the GPU (kernels.hip: k_build_raytri).
 constexpr int kRayPieces = 9;
 
 // First-candidate hints of a direction cell.  A cell is cut into kRayHintK x kRayHintK sub-cells, and two bits per sub-cell

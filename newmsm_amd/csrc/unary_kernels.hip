@@ -112,6 +112,49 @@ __device__ __forceinline__ int set_below(unsigned long long m) {
 #endif
 }
 
+// Lane pairs of k_unary_rays (lanes 2j and 2j + 1): a value of the other lane of the pair, by one DPP move (quad_perm:[1,0,3,2], every row and
+// bank).  Both lanes of a pair must be switched on where this stands.
+__device__ __forceinline__ int pair_swap(int v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);
+#else
+    return v;
+#endif
+}
+
+#ifdef __HIP_DEVICE_COMPILE__
+// One even and one odd piece of each lane's own record from what a pair of lanes loaded.  X is this lane's piece of the even lane's record
+// (the even piece in the even lane, the odd piece in the odd lane), Y its piece of the odd lane's record.  The even lane keeps X and takes the
+// odd lane's X for its odd piece; the odd lane keeps Y and takes the even lane's Y for its even piece.  In place, three instructions a dword
+// with the even lanes' mask in VCC (a DPP bank mask names groups of four lanes and cannot tell the two lanes of a pair apart):
+//     t = the partner's x;    x = even ? x : the partner's y;    y = even ? t : y
+// Written as assembly because the compiler has no way to be told "in the registers of the loads": from builtins and selects it makes two moves
+// and two selects a dword into 24 registers of their own, and the kernel, which stands at 72 for seven waves per SIMD, spills.  No instruction
+// here reads through DPP a register that an earlier one of the statement wrote, and the operands come from loads, so the two wait states
+// between a VALU write and a DPP read of the same register are none of this statement's business; the leading s_nop covers whatever VALU
+// instruction the compiler may have put in front.
+typedef int pair_v4i __attribute__((ext_vector_type(4)));
+#define MSM_PAIR_DPP " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+#define MSM_PAIR_DWORD(x, y)                                                 \
+    "v_mov_b32_dpp %[t], " x MSM_PAIR_DPP                                    \
+    "v_cndmask_b32_dpp " x ", " y ", " x ", vcc" MSM_PAIR_DPP                \
+    "v_cndmask_b32_e32 " y ", " y ", %[t], vcc\n\t"
+__device__ __forceinline__ void pair_merge(pair_v4i X, pair_v4i Y, double2 &even_piece, double2 &odd_piece) {
+    int x0 = X.x, x1 = X.y, x2 = X.z, x3 = X.w, y0 = Y.x, y1 = Y.y, y2 = Y.z, y3 = Y.w, t;
+    asm volatile("s_mov_b32 vcc_lo, 0x55555555\n\t"
+                 "s_mov_b32 vcc_hi, 0x55555555\n\t"
+                 "s_nop 1\n\t"
+                 MSM_PAIR_DWORD("%[x0]", "%[y0]") MSM_PAIR_DWORD("%[x1]", "%[y1]") MSM_PAIR_DWORD("%[x2]", "%[y2]") MSM_PAIR_DWORD("%[x3]", "%[y3]")
+                 : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [x3] "+v"(x3), [y0] "+v"(y0), [y1] "+v"(y1), [y2] "+v"(y2), [y3] "+v"(y3), [t] "=&v"(t)
+                 :
+                 : "vcc");
+    even_piece = make_double2(__hiloint2double(x1, x0), __hiloint2double(x3, x2));
+    odd_piece = make_double2(__hiloint2double(y1, y0), __hiloint2double(y3, y2));
+}
+#undef MSM_PAIR_DWORD
+#undef MSM_PAIR_DPP
+#endif
+
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
@@ -314,6 +357,11 @@ __global__ __launch_bounds__(256) void k_unary_samples(SamplesArgs a) {
 // (a certificate only skips a test that would have passed).  72 VGPRs and seven waves per SIMD as before, which takes the two empty asm statements
 // in the loop and the occupancy request on the kernel (without it the retry path's packed multiplies push the allocator to 74).  DESIGN.md section
 // 5.2 has the counters.
+// The other six pieces of the first candidate's record (its vertices and features) are fetched by lane pairs: lanes 2j and 2j + 1 load both their
+// records together, each load instruction taking two adjacent pieces of one record for the pair -- one line look-up where it was two, but for the one
+// record in eight whose 32 bytes straddle a line -- and swap half of what they loaded by DPP moves, in the registers of the loads (pair_merge: 36 VALU
+// instructions a wavefront round).  Pairs, not the quads that were measured earlier (39 % fewer look-ups, 47 % more VALU instructions, the same time),
+// and the vertex pieces only; every lane ends with the bytes it loaded for itself before.  DESIGN.md section 5.2 has the counters.
 // Behind a first-candidate miss (one lane in ten, so nearly every wavefront round has some): the answer is the second candidate for two misses in
 // three, the third to seventh for the rest (msm_ray_depth_check).  A rolled loop over the further candidates, one dependent round trip each until the
 // deepest lane of the wavefront is served, and a last trip for the accepted candidate's vertex pieces would make about six trips per round, of which
@@ -391,18 +439,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
         d0 = d1 = d2 = d3 = d4 = d5 = make_double2(0.0, 0.0);
         mo = make_int4(-1, -1, -1, -1);
 #endif
-        if (act) {
-            if (c.x >= 0) {
-                // the first candidate -- the one the cell's hint names for this sub-cell (ray_cell_of) -- is the answer nine times
-                // out of ten (three out of four for the best-ranked candidate of the whole cell): its vertices are requested
-                // together with its edge planes, so a settled sample costs two dependent loads after the cell
-                const float4 *rec = a.tree.ray_tri + (size_t)kRayPieces * c.x;
+        // The first candidate -- the one the cell's hint names for this sub-cell (ray_cell_of) -- is the answer nine times out of ten (three out of
+        // four for the best-ranked candidate of the whole cell): its vertex pieces are requested together with its edge planes, so a settled
+        // sample costs two dependent loads after the cell.  The six vertex pieces (3-8 of the record) are fetched by lane pairs, 2j and 2j + 1:
+        // every load instruction has the two lanes of a pair read two adjacent pieces of ONE record, 32 bytes that lie in one 128-byte line seven
+        // times out of eight, and the vector L1 looks a line up once for neighbouring lanes that share it.  With par = lane & 1, each lane loads
+        // the pieces 3 + par, 5 + par and 7 + par of the even lane's record (X) and of the odd lane's (Y); the even lane then takes its odd pieces
+        // from the odd lane's X, the odd lane its even pieces from the even lane's Y, by one DPP move and one select per dword (pair_merge).
+        // Six loads per lane as before and the same bytes in d0..d5, for 1.125 line look-ups per pair and load instead of 2.  A lane without a
+        // first candidate (no sample, or a point outside the table's radius range) helps its partner with the partner's record, which is why
+        // this block stands outside `act`: a DPP move reads nothing from a lane that is switched off, so the two lanes of a pair take every
+        // branch around the moves together.  The bank mask of a DPP move names groups of four lanes and cannot tell the lanes of a pair apart.
+        {
+            const int tc = c.x;  // negative: no first candidate (as c was initialised for a lane without a sample)
+            const int tp = pair_swap(tc);
+            if ((tc & tp) >= 0) {  // either lane has one: the same decision in both lanes of the pair
+                const unsigned par = (unsigned)lane & 1u;
+                int te = par ? tp : tc, to = par ? tc : tp;  // the even lane's candidate and the odd lane's, each standing in for the other where that has none
+                te = te < 0 ? to : te, to = to < 0 ? te : to;
+                // 32-bit byte offsets from the table's base (a scalar pair): per-lane 64-bit pointers cost the registers that keep seven waves per SIMD
+                static_assert(16ull * kRayPieces * kRayMaxTris < (1ull << 32), "a ray record's byte offset fits 32 bits");
+                const char *tab = reinterpret_cast<const char *>(a.tree.ray_tri);
+                const unsigned ox = 16u * ((unsigned)kRayPieces * (unsigned)te + 3u + par), oy = 16u * ((unsigned)kRayPieces * (unsigned)to + 3u + par);
                 // A lane whose sub-cell is certified (internal.hpp: kRayWBits) knows that this candidate passes and needs no vouching: it sits
                 // out the three edge-plane loads -- a lane that is switched off looks no line up -- and takes the candidate as it is.
-                // (a lane predicate: the six vertex pieces are requested in the same breath, by every lane, and nothing waits in between)
-                const double2 *dv = reinterpret_cast<const double2 *>(rec + 3);
-                t = c.x;
-                bool retry = false;
+                // (a lane predicate: the six vertex loads are requested in the same breath, by every lane of the pair, and nothing waits in between)
+                const bool test = tc >= 0 && !cert;
 #ifdef __HIP_DEVICE_COMPILE__
                 // The certified lanes never read the planes, so nothing need be written for them: the first empty statement names the
                 // twelve registers, without an instruction.  (Left to variables without a value, the allocator keeps the registers for the
@@ -410,39 +472,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
                 // second one keeps the planes out of sight until the vertex loads are out: the packed multiplies of the test want two of
                 // their words side by side, and the compiler would otherwise wait for them, and move them, before it requests the vertices.
                 typedef float v4f __attribute__((ext_vector_type(4)));
+                typedef int v4i __attribute__((ext_vector_type(4)));
                 v4f q0, q1, q2;
                 asm volatile("" : "=v"(q0), "=v"(q1), "=v"(q2));
-                if (!cert) {
-                    const v4f *rq = reinterpret_cast<const v4f *>(rec);
+                if (test) {
+                    const v4f *rq = reinterpret_cast<const v4f *>(tab + 16u * ((unsigned)kRayPieces * (unsigned)tc));
                     q0 = rq[0], q1 = rq[1], q2 = rq[2];
                 }
-                d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
-                if (!cert) {
-                    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
-                    const float4 e0 = make_float4(q0.x, q0.y, q0.z, q0.w), e1 = make_float4(q1.x, q1.y, q1.z, q1.w), e2 = make_float4(q2.x, q2.y, q2.z, q2.w);
+                const v4i *px = reinterpret_cast<const v4i *>(tab + ox), *py = reinterpret_cast<const v4i *>(tab + oy);
+                const v4i X0 = px[0], Y0 = py[0], X1 = px[2], Y1 = py[2], X2 = px[4], Y2 = py[4];
+                pair_merge(X0, Y0, d0, d1);
+                pair_merge(X1, Y1, d2, d3);
+                pair_merge(X2, Y2, d4, d5);
 #else
+                const double2 *dv = reinterpret_cast<const double2 *>(tab + (par ? oy : ox) - 16u * par);
                 d0 = dv[0], d1 = dv[1], d2 = dv[2], d3 = dv[3], d4 = dv[4], d5 = dv[5];
-                if (!cert) {
-                    const float4 e0 = rec[0], e1 = rec[1], e2 = rec[2];
 #endif
-                    excl = __float_as_int(e1.w);
-                    retry = !ray_accepts(e0, e1, e2, fx, fy, fz);
-                }
-                if (retry) {
-                    t = -1;
-                    mo = make_int4(c.w, -1, -1, -1);
-                    // Round A: the second candidate is the answer for two misses in three (msm_ray_depth_check).  Its planes and the cell's ray_more entry
-                    // are requested together, one round trip; its vertex pieces are not (the look-ups they add cost more than the reload they save).
-                    if (c.y >= 0) {
-                        const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * c.y;
-                        const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
-                        if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
-                        if (ray_accepts(g0, g1, g2, fx, fy, fz)) {
-                            t = c.y;
-                            excl = __float_as_int(g1.w);
-                            got = true;  // (its vertex pieces come with round T's)
+                if (tc >= 0) {
+                    t = tc;
+                    bool retry = false;
+                    if (test) {
+#ifdef __HIP_DEVICE_COMPILE__
+                        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2));
+                        const float4 e0 = make_float4(q0.x, q0.y, q0.z, q0.w), e1 = make_float4(q1.x, q1.y, q1.z, q1.w), e2 = make_float4(q2.x, q2.y, q2.z, q2.w);
+#else
+                        const float4 *rec = a.tree.ray_tri + (size_t)kRayPieces * tc;
+                        const float4 e0 = rec[0], e1 = rec[1], e2 = rec[2];
+#endif
+                        excl = __float_as_int(e1.w);
+                        retry = !ray_accepts(e0, e1, e2, fx, fy, fz);
+                    }
+                    if (retry) {
+                        t = -1;
+                        mo = make_int4(c.w, -1, -1, -1);
+                        // Round A: the second candidate is the answer for two misses in three (msm_ray_depth_check).  Its planes and the cell's ray_more entry
+                        // are requested together, one round trip; its vertex pieces are not (the look-ups they add cost more than the reload they save).
+                        if (c.y >= 0) {
+                            const float4 *r2 = a.tree.ray_tri + (size_t)kRayPieces * c.y;
+                            const float4 g0 = r2[0], g1 = r2[1], g2 = r2[2];
+                            if (c.w < -1) mo = a.tree.ray_more[-2 - c.w];  // a cell with more than four candidates
+                            if (ray_accepts(g0, g1, g2, fx, fy, fz)) {
+                                t = c.y;
+                                excl = __float_as_int(g1.w);
+                                got = true;  // (its vertex pieces come with round T's)
+                            }
+                            pend = t < 0 && c.z >= 0;  // (a list ends at its first negative id: rank_and_fill_cells packs them)
                         }
-                        pend = t < 0 && c.z >= 0;  // (a list ends at its first negative id: rank_and_fill_cells packs them)
                     }
                 }
             }
