@@ -731,8 +731,10 @@ int msm_cost_counters(msm_cost *c, int64_t counters[4]);
  * move, bin slots one of them holds at most, and the largest number of control triangles in one (0 until a fused move has run);
  * routes[MSM_ROUTE_MOVE_TAILS]: moves that needed the tail kernel since creation (saturating); routes[MSM_ROUTE_MOVE_DEFERRED]: evaluations (of the
  * move's 8 x T, or T in msm_cost_total) that the last fused move handed to the tail kernel, 0 when it launched none -- read back (four bytes) behind the
- * tail kernel only, so a move that needs no tail pays nothing; samples settled by the leaf search inside the main kernel are not counted.  routes[7]: 0
- * (reserved). */
+ * tail kernel only, so a move that needs no tail pays nothing; samples settled by the leaf search inside the main kernel are not counted.
+ * routes[MSM_ROUTE_UNARY_FORM]: the form of the last table's MSM_UNARY_FLAT reduction, MSM_UNARY_FORM_ROWS where k_unary_reduce_rows ran (univariate
+ * correlation / SSD, no patch above 96 points: a row per 8-lane group, the moving patches prepared beside the fix-up), MSM_UNARY_FORM_STAGED where
+ * k_unary_reduce_flat staged them per workgroup and for every other reduction. */
 #define MSM_ROUTE_UNARY 0
 #define MSM_ROUTE_MOVE 1
 #define MSM_ROUTE_MOVE_NBLK 2
@@ -740,6 +742,7 @@ int msm_cost_counters(msm_cost *c, int64_t counters[4]);
 #define MSM_ROUTE_MOVE_MAXTRI 4
 #define MSM_ROUTE_MOVE_TAILS 5
 #define MSM_ROUTE_MOVE_DEFERRED 6
+#define MSM_ROUTE_UNARY_FORM 7
 #define MSM_UNARY_NONE 0        /* no unary table yet (the triclique classes' table is all zeros: no kernel) */
 #define MSM_UNARY_UNIVARIATE 1  /* k_unary_reduce_univariate (DICE measures of the univariate class) */
 #define MSM_UNARY_FLAT 2        /* k_unary_reduce_flat */
@@ -747,6 +750,8 @@ int msm_cost_counters(msm_cost *c, int64_t counters[4]);
 #define MSM_UNARY_MV8 4         /* k_unary_reduce_mv8 */
 #define MSM_UNARY_PW8_4 5       /* k_unary_reduce_pw8<4> */
 #define MSM_UNARY_PW8_8 6       /* k_unary_reduce_pw8<8> */
+#define MSM_UNARY_FORM_STAGED 0
+#define MSM_UNARY_FORM_ROWS 1
 #define MSM_MOVE_NONE 0
 #define MSM_MOVE_FUSED_0 1      /* k_ho_move<., 0>: the univariate triclique class */
 #define MSM_MOVE_FUSED_1 2      /* k_ho_move<., 1>: one lane per sample */

@@ -1559,6 +1559,7 @@ class DiscreteCostFunction:
         return dict(samples=c[0], unary=c[1], triplet=c[2], pairwise=c[3])
 
     UNARY_ROUTES = ("none", "univariate", "flat", "features", "mv8", "pw8<4>", "pw8<8>")  # MSM_UNARY_* of include/msmhip.h
+    UNARY_FORMS = ("staged", "rows")  # MSM_UNARY_FORM_*
     MOVE_ROUTES = ("none", "fused0", "fused1", "fused2", "fused3", "octets_sample", "octets_sample_mv8", "octets_ho", "strain")  # MSM_MOVE_*
 
     def routes(self):
@@ -1566,10 +1567,12 @@ class DiscreteCostFunction:
         table (UNARY_ROUTES); move: the route of the last triclique label step (MOVE_ROUTES: fusedM = k_ho_move<., M>, octets_* = the three-kernel
         path with that sampling kernel, octets_ho = k_triplet_octets_ho); move_nblk / move_cap / move_maxtri: workgroups of the fused move, bin slots
         and control triangles one of them holds at most; move_tails: moves that needed the tail kernel, since creation; move_deferred: evaluations the last fused
-        move handed to the tail kernel (0 when it launched none)."""
+        move handed to the tail kernel (0 when it launched none); unary_form: "rows" where k_unary_reduce_rows stood in for the "flat" reduction of the
+        last table (no patch above 96 points), else "staged"."""
         r = (C.c_int32 * 8)()
         check(lib().msm_cost_routes(self.h, r))
-        return dict(unary=self.UNARY_ROUTES[r[0]], move=self.MOVE_ROUTES[r[1]], move_nblk=r[2], move_cap=r[3], move_maxtri=r[4], move_tails=r[5], move_deferred=r[6])
+        return dict(unary=self.UNARY_ROUTES[r[0]], move=self.MOVE_ROUTES[r[1]], move_nblk=r[2], move_cap=r[3], move_maxtri=r[4], move_tails=r[5], move_deferred=r[6],
+                    unary_form=self.UNARY_FORMS[r[7]])
 
     SAMPLERS = ("none", "samples", "rays")  # MSM_SAMPLER_* of include/msmhip.h
     REFUSALS = ("", "sampler", "reduction")  # MSM_PLAN_REFUSED_*

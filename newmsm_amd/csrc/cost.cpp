@@ -267,6 +267,16 @@ int ensure_unary_table(msm_cost *c) {
     u.fix_off = c->d_fix_off.p;
     u.redo_list = c->d_queues.p;
     u.route = &c->route_unary;
+    c->unary_form = 0;
+    u.form = &c->unary_form;
+    if (c->p.kind == MSM_COST_UNIVARIATE && unary_row_form(c->p.simmeasure, c->pmax)) {  // the moving side of k_unary_reduce_rows
+        MSM_HIP(c->d_mov_a.ensure(c->pidx.size()));
+        if (u.cfw && u.cfw_rows >= 1) MSM_HIP(c->d_mov_w.ensure(c->pidx.size()));
+        MSM_HIP(c->d_mov_stat.ensure(3 * (size_t)N));
+        u.mov_a = c->d_mov_a.p;
+        u.mov_w = (u.cfw && u.cfw_rows >= 1) ? c->d_mov_w.p : nullptr;
+        u.mov_stat = c->d_mov_stat.p;
+    }
     next_timing_slot(c, u.ev_start, u.ev_stop);
     switch (c->p.kind) {
         case MSM_COST_UNIVARIATE: st = launch_unary_univariate(ctx, u); break;
@@ -658,6 +668,7 @@ int msm_cost_routes(msm_cost *c, int32_t routes[8]) {
     routes[MSM_ROUTE_MOVE_MAXTRI] = c->move_maxtri;
     routes[MSM_ROUTE_MOVE_TAILS] = (int32_t)std::min<int64_t>(c->move_tails, INT32_MAX);
     routes[MSM_ROUTE_MOVE_DEFERRED] = c->move_deferred;
+    routes[MSM_ROUTE_UNARY_FORM] = c->unary_form;
     return MSM_OK;
 }
 

@@ -72,6 +72,7 @@ struct msm_cost {
     int move_nblk = 0, move_cap = 0, move_parity = 0;
     int move_maxtri = 0;                  // most control triangles in one workgroup of the fused move
     int route_unary = 0, route_move = 0;  // msm_cost_routes: MSM_UNARY_* / MSM_MOVE_* as the launchers reported them
+    int unary_form = MSM_UNARY_FORM_STAGED;  // ... MSM_UNARY_FORM_*: whether the last table's correlation / SSD reduction ran by rows
     msm::UnaryPlan unary_plan;            // msm_cost_unary_launch: the plan of the last unary table (refused ones included)
     int unary_plan_pmax = 0;
     bool move_valid = false;
@@ -105,6 +106,7 @@ struct msm_cost {
     DevBuf<uint32_t> d_slots;
     // scratch of the unary kernels
     DevBuf<double> d_tval;
+    DevBuf<double> d_mov_a, d_mov_w, d_mov_stat;  // the row form's moving side (unary.hpp: UnaryLaunch::mov_*), rewritten by every table
     DevBuf<int> d_stri;
     DevBuf<double> d_sw3;
     DevBuf<unsigned long long> d_fix_list;

@@ -3,8 +3,8 @@
 //   unary_plan.cpp             host only: every decision that depends on the largest patch (the plan, the LDS formulae, the refusals), the
 //                              fix-up list's segments and the control points' launch order
 //   unary_kernels.hip          the samplers: k_unary_rays (targets with a direction table), k_unary_samples (the complete sampler, the
-//                              fallback) and k_unary_fixup behind either
-//   unary_reduce_kernels.hip   the five reductions, and the two launchers that cost.cpp calls
+//                              fallback) and k_unary_fixup behind either, with the prepare blocks of the row form as its passengers
+//   unary_reduce_kernels.hip   the six reductions, and the two launchers that cost.cpp calls
 #pragma once
 
 #include "internal.hpp"
@@ -22,6 +22,13 @@ constexpr int kCntStride = 32;    // the fix-up counters sit 128 bytes apart
 constexpr size_t kLdsWorkgroup = 160 * 1024, kLdsDefault = 64 * 1024;
 constexpr size_t kStaticSampler = 16;  // k_unary_samples: s_qn, s_ndefer; k_unary_rays: s_nleft, s_base
 constexpr size_t kStaticFlat = 32;     // k_unary_reduce_flat: s_stat[3]
+constexpr int kFixBlocks = 4096;       // k_unary_fixup's own workgroups; the prepare blocks of the row form ride behind them in the same launch
+constexpr int kRowsPmax = 96;          // k_unary_reduce_rows keeps a whole patch in registers: 12 values in each of a row's 8 lanes
+
+// The form of the univariate correlation / SSD reduction (msm_cost_routes: routes[MSM_ROUTE_UNARY_FORM]).  Rows: the fix-up launch also writes every
+// control point's moving patch in patch order with its statistics, and k_unary_reduce_rows reduces one table row per 8-lane group from them.
+// Otherwise (a patch that does not fit the registers) k_unary_reduce_flat stages the moving patch per workgroup as before.
+inline bool unary_row_form(int simmeasure, int pmax) { return (simmeasure == 1 || simmeasure == 2) && pmax <= kRowsPmax; }
 
 // ---- the sampling kernels' grid: which workgroup takes which control point and which of its labels ----
 // The workgroups of one XCD (workgroup % 8, round-robin dispatch) get a contiguous range of launch positions, i.e. spatial neighbours on
@@ -96,8 +103,14 @@ struct UnaryLaunch {
     unsigned int *fix_cnt;         // unary_fix_counter_words() words (zeroed by the launch)
     const unsigned int *fix_off;   // unary_fix_segments() + 1 offsets from unary_fix_offsets()
     int *redo_list;                // N * plan->nsplit ints: every workgroup of a control point may list it
+    // the row form's moving side (univariate correlation / SSD with unary_row_form(); all nullptr otherwise): written by the prepare blocks of the
+    // fix-up launch for every table, read by k_unary_reduce_rows
+    double *mov_a = nullptr;       // the moving patches in patch order, one double per patch point (pptr's offsets)
+    double *mov_w = nullptr;       // their weight row likewise, or nullptr without weights
+    double *mov_stat = nullptr;    // 3 x N: sum of weights, weighted mean, weighted variance sum of each moving patch
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // optional: recorded around the samples kernel
     int *route = nullptr;          // optional: the launcher writes the MSM_UNARY_* value of the reduction kernel it chose
+    int *form = nullptr;           // optional: ... and 1 where k_unary_reduce_rows stood in for k_unary_reduce_flat, else 0
     const UnaryPlan *plan = nullptr;  // unary_plan() for this launch
 };
 // multivariate / patchwise: the sampler stores (triangle, raw weights) per sample, a second kernel reduces
@@ -108,8 +121,9 @@ struct UnaryWeightsScratch {
 int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u);
 int launch_unary_multivariate(msm_ctx *ctx, const UnaryLaunch &u, const UnaryWeightsScratch &w, bool patchwise);
 // The plan's sampler and k_unary_fixup behind it; the launchers above call it before their reduction.  w: store (triangle, weights) instead of
-// tval.  fused_reduction: k_unary_samples also reduces the control points it settles (DICE) and lists the others in u.redo_list.
-int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, const UnaryWeightsScratch *w, bool fused_reduction);
+// tval.  fused_reduction: k_unary_samples also reduces the control points it settles (DICE) and lists the others in u.redo_list.  prepare_rows: the
+// fix-up launch carries the prepare blocks that fill u.mov_a / mov_w / mov_stat (k_unary_reduce_rows follows).
+int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, const UnaryWeightsScratch *w, bool fused_reduction, bool prepare_rows = false);
 
 // dynamic LDS beyond the default limit: the kernel's attribute first (the plan has checked that it fits a workgroup)
 template <class K>

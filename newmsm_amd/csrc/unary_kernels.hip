@@ -23,7 +23,8 @@
 //                     handled here (keeps this kernel's register budget small = more waves per SIMD).
 //                     For DICE / genDICE (launch_samples: fused_reduction) it also reduces the control points all of whose samples it
 //                     settled, straight from LDS, and lists the others for k_unary_reduce_univariate.
-//   k_unary_fixup     behind either sampler: re-does the listed samples with the complete search (search_device.hpp).
+//   k_unary_fixup     behind either sampler: re-does the listed samples with the complete search (search_device.hpp).  Workgroups behind its own
+//                     4 096 prepare the moving patches for k_unary_reduce_rows where that kernel follows.
 //
 // Decisions (which triangle) use the reference's FP64 arithmetic; see search_device.hpp.
 #include "search_device.hpp"
@@ -72,6 +73,11 @@ struct SamplesArgs {
     int *redo_list;        // nodes whose reduction must wait for the fix-up kernel
     unsigned int *redo_count;
     int *status;
+    // the prepare blocks of the fix-up launch (behind every member the samplers read, whose places stay what they were): the moving side of
+    // k_unary_reduce_rows, or all nullptr when that kernel does not follow
+    const double *mov_cfw;  // the weight row, Nsrc, or nullptr
+    double *mov_a, *mov_w;  // moving patches and their weights in patch order (mov_w: nullptr without weights)
+    double *mov_stat;       // 3 x N: sum of weights, weighted mean, weighted variance sum (correlation only)
 };
 
 // get_target_data's tail (:361-375): barycentric_interpolation on the raw (un-projected) point
@@ -627,7 +633,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void k
 // triangle wins whatever its distance); anything else (tie-break by dist_to_point, sibling leaves, nearest vertex,
 // oversized leaves) is redone by the group's first lane with the complete search of search_device.hpp (with the
 // exclusion boxes and overflow candidates of the ray table these are a handful per table).
+//
+// Passengers: the workgroups behind the first kFixBlocks prepare the moving side of k_unary_reduce_rows (launch_samples: prepare_rows), a wavefront
+// per control point.  Nothing they read comes from the sampler or the fix-up list, and this launch leaves most of the chip idle; the row kernel then
+// finds each moving patch contiguous, in patch order, with its statistics done.  The statistics are k_unary_reduce_flat's own statements in their
+// own order (lane t sums the points t, t + 64, ...; wave_sum; the same divisions), so the two reductions give the same bits.
+__device__ __forceinline__ double fixup_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ void prepare_moving_patch(const SamplesArgs &a, int node, int t) {
+    const int beg = a.pptr[node], P = a.pptr[node + 1] - beg;
+    // patches of the row form have at most kRowsPmax <= 128 points: two per lane, kept in registers between the two sums
+    double A[2], W[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int i = t + 64 * k;
+        A[k] = 0.0, W[k] = 1.0;
+        if (i < P) {
+            const int s = a.pidx[beg + i];
+            A[k] = a.sfeat[s];
+            if (a.mov_cfw) W[k] = a.mov_cfw[s];
+            a.mov_a[beg + i] = A[k];
+            if (a.mov_w) a.mov_w[beg + i] = W[k];
+        }
+    }
+    if (a.simmeasure != 2) return;
+    double sw = 0, ma = 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (t + 64 * k < P) {
+            sw += W[k];
+            ma += W[k] * A[k];
+        }
+    sw = fixup_wave_sum(sw);
+    ma = fixup_wave_sum(ma);
+    if (sw > 0.0) ma /= sw;
+    double va = 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (t + 64 * k < P) {
+            const double da = A[k] - ma;
+            va += W[k] * da * da;
+        }
+    va = fixup_wave_sum(va);
+    if (t == 0) a.mov_stat[3 * (size_t)node] = sw, a.mov_stat[3 * (size_t)node + 1] = ma, a.mov_stat[3 * (size_t)node + 2] = va;
+}
+
 __global__ __launch_bounds__(256) void k_unary_fixup(SamplesArgs a) {
+    if (blockIdx.x >= kFixBlocks) {  // uniform over the workgroup, ahead of the barrier below
+        const int node = (blockIdx.x - kFixBlocks) * 4 + (threadIdx.x >> 6);
+        if (node < a.N) prepare_moving_patch(a, node, threadIdx.x & 63);
+        return;
+    }
     // dense index over the segments: prefix sums of the segment counts (one wavefront, kFixSegs == 64)
     __shared__ unsigned s_pre[kFixSegs + 1];
     if (threadIdx.x < kFixSegs) {
@@ -645,7 +705,7 @@ __global__ __launch_bounds__(256) void k_unary_fixup(SamplesArgs a) {
     __syncthreads();
     const unsigned n = s_pre[kFixSegs];
     const int lane = threadIdx.x & 63, sub = lane & 7, grp = lane >> 3;
-    const unsigned per_block = 256 / 8, stride = gridDim.x * per_block;
+    const unsigned per_block = 256 / 8, stride = kFixBlocks * per_block;  // (the grid may be longer: the passengers above)
     // wavefront-uniform loop: the ballots below need all 64 lanes
     for (unsigned j0 = blockIdx.x * per_block + (threadIdx.x >> 6) * 8; j0 < n; j0 += stride) {
         const unsigned j = j0 + grp;
@@ -673,7 +733,9 @@ __global__ __launch_bounds__(256) void k_unary_fixup(SamplesArgs a) {
 // ------------------------------------------------------------------------------------------------
 // launch: the plan's sampler, then the fix-up kernel
 // ------------------------------------------------------------------------------------------------
-int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, const UnaryWeightsScratch *w, bool fused_reduction) {
+int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, const UnaryWeightsScratch *w, bool fused_reduction, bool prepare_rows) {
+    if (prepare_rows && (!u.mov_a || !u.mov_stat || (u.cfw && u.cfw_rows >= 1 && !u.mov_w) || u.pmax > kRowsPmax))
+        return fail(MSM_ERR_STATE, "launch_samples: the row form's buffers are missing, or a patch of %d points does not fit it", u.pmax);
     if (u.tree.nnodes <= 0 || !u.tree.mask) return fail(MSM_ERR_STATE, "target search structure missing");
     if (u.ntri >= (1 << kTriBits)) return fail(MSM_ERR_CAPACITY, "target mesh has %d triangles; the sample queue packs ids in %d bits", u.ntri, kTriBits);
     const bool rays = plan.sampler == MSM_SAMPLER_RAYS;
@@ -707,6 +769,11 @@ int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, co
     a.redo_list = u.redo_list;
     a.redo_count = u.fix_cnt;
     a.status = ctx->d_status;
+    const bool mov_weights = prepare_rows && u.cfw && u.cfw_rows >= 1;
+    a.mov_cfw = mov_weights ? u.cfw : nullptr;
+    a.mov_a = prepare_rows ? u.mov_a : nullptr;
+    a.mov_w = mov_weights ? u.mov_w : nullptr;
+    a.mov_stat = prepare_rows ? u.mov_stat : nullptr;
     MSM_TRY(rays ? allow_lds(k_unary_rays, plan.sampler_lds) : allow_lds(k_unary_samples, plan.sampler_lds));
     const int blocks = unary_workgroups(u.N, plan.nsplit);
     if (u.ev_start) MSM_HIP(hipEventRecord(u.ev_start, ctx->stream));
@@ -717,7 +784,7 @@ int launch_samples(msm_ctx *ctx, const UnaryLaunch &u, const UnaryPlan &plan, co
     }
     MSM_HIP(hipGetLastError());
     if (u.ev_stop) MSM_HIP(hipEventRecord(u.ev_stop, ctx->stream));
-    hipLaunchKernelGGL(k_unary_fixup, dim3(4096), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_unary_fixup, dim3(kFixBlocks + (prepare_rows ? (u.N + 3) / 4 : 0)), dim3(256), 0, ctx->stream, a);
     MSM_HIP(hipGetLastError());
     return MSM_OK;
 }

@@ -2,7 +2,9 @@
 // with the label's sampled target patch, and the two launchers of a table: sampler (unary_kernels.hip: launch_samples), then one of
 //
 //   univariate (the samplers filled tval)
-//     k_unary_reduce_flat         correlation / SSD, behind either sampler: eight lanes per label, all control points
+//     k_unary_reduce_rows         correlation / SSD, behind either sampler, patches up to 96 points: eight lanes per table row, the moving side
+//                                 prepared by the passengers of the fix-up launch (unary_kernels.hip: k_unary_fixup)
+//     k_unary_reduce_flat         the same for larger patches: a workgroup per control point, eight lanes per label, the moving patch staged in LDS
 //     k_unary_reduce_univariate   DICE / genDICE, a wavefront per label: all control points behind k_unary_rays; behind k_unary_samples only the
 //                                 control points of its redo list (that sampler reduces the ones it settles itself)
 //   multivariate / patchwise (the samplers stored triangle and raw weights per sample), behind either sampler
@@ -10,7 +12,8 @@
 //     k_unary_reduce_pw8<4|8>     patchwise, 12 <= D <= 32 | 64, correlation / SSD: the same layout
 //     k_unary_reduce_features     every other D, and DICE: a lane per patch point
 //
-// Which of them runs is the plan's decision (unary_plan.cpp: unary_plan), not this unit's.
+// Which of them runs is the plan's decision (unary_plan.cpp: unary_plan), not this unit's; only the form of the plan's "flat" reduction (rows or the
+// staged kernel, unary.hpp: unary_row_form) is settled here, in launch_unary_univariate.
 #include <algorithm>
 
 #include "similarity_device.hpp"
@@ -28,7 +31,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 }  // namespace
 
-// One argument block for the five kernels; each reads the members its comment names and ignores the rest.
+// One argument block for the six kernels; each reads the members its comment names and ignores the rest.
 struct ReduceArgs {
     int N, L, Nsrc, D;
     const int *pptr, *pidx;
@@ -50,6 +53,7 @@ struct ReduceArgs {
     int patchwise;                // features
     int pmax;                     // the LDS slices' stride (flat, univariate, features)
     double *U;
+    const double *mov_a, *mov_w, *mov_stat;  // the prepared moving side (rows): patches and weights in patch order, 3 x N statistics
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -197,6 +201,74 @@ __global__ __launch_bounds__(256) void k_unary_reduce_flat(ReduceArgs a, unsigne
         }
         if (sub == 0) a.U[(size_t)l * a.N + node] = absw * cost;
     }
+}
+
+// The same reduction by table row, for patches that fit the registers (P <= kRedKeep * kRedLanes): row r = node * L + l belongs to one 8-lane group,
+// 32 rows to a workgroup, nodes in their natural order.  The moving patch arrives prepared (mov_a, mov_w in patch order, mov_stat: k_unary_fixup's
+// passengers), so a group depends on pptr alone before it issues every load it needs in one batch, and nothing ties it to the other rows of its control
+// point: no LDS, no barrier, every lane at work, and the whole table of the benchmark resident at once.  The arithmetic is k_unary_reduce_flat's,
+// statement for statement (W: a weight row exists; without one the weights are 1.0 and the products by them are left out, 1.0 * x being x).
+static_assert(kRedKeep * kRedLanes == kRowsPmax, "the row form's patch bound is what one group keeps in registers");
+
+template <bool W>
+__global__ __launch_bounds__(256) void k_unary_reduce_rows(ReduceArgs a, unsigned int *clear, int clear_words) {
+    const int tid = threadIdx.x, sub = tid & (kRedLanes - 1);
+    if (blockIdx.x == 0 && clear)
+        for (int k = tid; k < clear_words; k += 256) clear[k] = 0u;
+    const long long row = (long long)blockIdx.x * (256 / kRedLanes) + tid / kRedLanes;
+    if (row >= (long long)a.N * a.L) return;  // whole groups leave: the sums below stay inside a group
+    const int node = (int)(row / a.L), l = (int)(row - (long long)node * a.L);
+    const int beg = a.pptr[node], P = a.pptr[node + 1] - beg;
+    const double *B = a.tval + (size_t)a.L * beg + (size_t)l * P;
+    const double *A = a.mov_a + beg, *Wt = W ? a.mov_w + beg : nullptr;
+    double breg[kRedKeep], areg[kRedKeep], wreg[kRedKeep];  // (wreg: unread without a weight row)
+#pragma unroll
+    for (int k = 0; k < kRedKeep; ++k) {
+        const int i = sub + kRedLanes * k;
+        breg[k] = i < P ? B[i] : 0.0;
+        areg[k] = i < P ? A[i] : 0.0;
+        wreg[k] = (W && i < P) ? Wt[i] : 0.0;
+    }
+    const double absw = a.absw[node];
+    double cost;
+    if (a.simmeasure == 2) {  // sparsesimkernel::corr, M/similarities.cpp:129-158
+        const double sw = a.mov_stat[3 * (size_t)node], ma = a.mov_stat[3 * (size_t)node + 1];
+        double va = a.mov_stat[3 * (size_t)node + 2];
+        double mb = 0;
+#pragma unroll
+        for (int k = 0; k < kRedKeep; ++k)
+            if (sub + kRedLanes * k < P) mb += W ? wreg[k] * breg[k] : breg[k];
+        mb = group_sum(mb);
+        if (sw > 0.0) mb /= sw;
+        double pr = 0, vb = 0;
+#pragma unroll
+        for (int k = 0; k < kRedKeep; ++k)
+            if (sub + kRedLanes * k < P) {
+                const double da = areg[k] - ma, db = breg[k] - mb;
+                pr += W ? wreg[k] * da * db : da * db;
+                vb += W ? wreg[k] * db * db : db * db;
+            }
+        pr = group_sum(pr);
+        vb = group_sum(vb);
+        if (sw > 0.0) {
+            pr /= sw;
+            va /= sw;
+            vb /= sw;
+        }
+        const double r = (va == 0.0 || vb == 0.0) ? 0.0 : pr / (sqrt(va) * sqrt(vb));
+        cost = 1 - (1 + r) * 0.5;
+    } else {  // sparsesimkernel::SSD, M/similarities.cpp:179-188
+        double pr = 0;
+#pragma unroll
+        for (int k = 0; k < kRedKeep; ++k)
+            if (sub + kRedLanes * k < P) {
+                const double df = areg[k] - breg[k];
+                pr += W ? wreg[k] * df * df : df * df;
+            }
+        pr = group_sum(pr);
+        cost = sqrt(pr) / P;
+    }
+    if (sub == 0) a.U[(size_t)l * a.N + node] = absw * cost;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -509,6 +581,7 @@ static ReduceArgs reduce_args(const UnaryLaunch &u, const UnaryWeightsScratch *w
     r.patchwise = 0;
     r.pmax = u.pmax;
     r.U = u.U;
+    r.mov_a = u.mov_a, r.mov_w = u.mov_w, r.mov_stat = u.mov_stat;
     return r;
 }
 
@@ -520,11 +593,21 @@ int launch_unary_univariate(msm_ctx *ctx, const UnaryLaunch &u) {
     // Correlation / SSD: both search paths only fill tval and one kernel reduces it, so the table does not depend on
     // which of them ran (the ray table of a target arrives in the background, api.cpp: ensure_rays).  DICE costs are
     // ratios of counts -- the same from any summation order -- and keep the reduction fused into the complete sampler.
-    MSM_TRY(dice ? allow_lds(k_unary_reduce_univariate, plan.reduce_lds) : allow_lds(k_unary_reduce_flat, plan.reduce_lds));
-    MSM_TRY(launch_samples(ctx, u, plan, nullptr, dice));
+    // ... and one of two kernels: by rows where every patch fits a group's registers and the cost object brought the buffers of the moving side
+    const bool rows = !dice && unary_row_form(u.simmeasure, u.pmax) && u.mov_a && u.mov_stat;
+    if (!rows) MSM_TRY(dice ? allow_lds(k_unary_reduce_univariate, plan.reduce_lds) : allow_lds(k_unary_reduce_flat, plan.reduce_lds));
+    MSM_TRY(launch_samples(ctx, u, plan, nullptr, dice, rows));
     ReduceArgs r = reduce_args(u, nullptr);
     if (u.route) *u.route = plan.reduce;
-    if (!dice) {
+    if (u.form) *u.form = rows ? MSM_UNARY_FORM_ROWS : MSM_UNARY_FORM_STAGED;
+    if (rows) {
+        const unsigned blocks = (unsigned)(((long long)u.N * u.L + 256 / kRedLanes - 1) / (256 / kRedLanes));
+        if (u.cfw && u.cfw_rows >= 1) {
+            hipLaunchKernelGGL(k_unary_reduce_rows<true>, dim3(blocks), dim3(256), 0, ctx->stream, r, u.fix_cnt, (int)unary_fix_counter_words());
+        } else {
+            hipLaunchKernelGGL(k_unary_reduce_rows<false>, dim3(blocks), dim3(256), 0, ctx->stream, r, u.fix_cnt, (int)unary_fix_counter_words());
+        }
+    } else if (!dice) {
         hipLaunchKernelGGL(k_unary_reduce_flat, dim3(u.N), dim3(256), plan.reduce_lds, ctx->stream, r, u.fix_cnt, (int)unary_fix_counter_words());
     } else {
         int blocks = 64;

@@ -11,19 +11,28 @@ tag = sys.argv[1]
 prefix = sys.argv[2] if len(sys.argv) > 2 else "msm::k_unary"
 command = sys.argv[3] if len(sys.argv) > 3 else "python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras"
 per = collections.defaultdict(dict)
+
+
+def kernel_name(s):
+    """the name without its argument list, and without the return type that a template instance carries: "void msm::k_unary_reduce_rows<false>(...)"
+    and "msm::k_unary_rays(...)" give "msm::k_unary_reduce_rows<false>" and "msm::k_unary_rays" """
+    s = s.split("(")[0]
+    return s[5:] if s.startswith("void ") else s
+
+
 for d in sorted(glob.glob("gpurun_out/pmc_%s_*" % tag)):
     for f in glob.glob(d + "/*/*counter_collection.csv"):
         acc = collections.defaultdict(list)
         for r in csv.DictReader(open(f)):
-            acc[(r["Kernel_Name"].split("(")[0], r["Counter_Name"])].append(float(r["Counter_Value"]))
+            acc[(kernel_name(r["Kernel_Name"]), r["Counter_Name"])].append(float(r["Counter_Value"]))
         for (k, c), v in acc.items():
             per[k][c] = sum(v) / len(v)
 import os
 
 avg_ns, calls = {}, {}
 for r in csv.DictReader(open("gpurun_out/%s_kernel_stats.csv" % tag)):
-    avg_ns[r["Name"].split("(")[0]] = float(r["AverageNs"])
-    calls[r["Name"].split("(")[0]] = int(r["Calls"])
+    avg_ns[kernel_name(r["Name"])] = float(r["AverageNs"])
+    calls[kernel_name(r["Name"])] = int(r["Calls"])
 steps = int(os.environ.get("MSM_PROFILE_STEPS", "0"))  # label steps the profiled command ran (tools/collect_group_profile.sh): launches per step
 import hashlib
 
